@@ -14,7 +14,10 @@ ABI's (hspf_multi_run): whole 64-root batches per rank, ONE RCCL all-gather of t
 communication stream so that it overlaps the next step's kernels.  At N = 1 the same entry point runs
 a one-rank job.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (--warmup steps), times exactly --steps steps and prints
+the headline; --dump-outputs DIR also writes what the last timed step computed.  --full adds, outside the timed region,
+the oracle check of that step, the one-step-at-a-time pass with the roofline and phase figures, the exchange block
+(N > 1) and, at N = 1, the CPU baselines and the blocks beside the headline (--no-cpu-baseline leaves those out).
 """
 from __future__ import annotations
 
@@ -852,6 +855,58 @@ def preflight(rank: int, world: int, local_rank: int, dist) -> None:
         sys.stderr.write("[bench preflight] " + json.dumps(allp) + "\n")
 
 
+def headline(world, steps, warmup, timed_steps, dt, R, n, e, W, depth, gather_via, stub) -> dict:
+    """The result line of a plain run (and the head of the --full one): `value` = SPF runs retired per second over the
+    timed steps, `ms_per_step` = wall milliseconds of one timed step."""
+    return {
+        "metric": "full-SPF runs/sec on 100k-vertex synthetic LSDB",
+        "value": round(timed_steps * R * world / dt, 2), "unit": "spf_runs/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": round(dt / timed_steps * 1e3, 4),
+        "timed_steps": timed_steps, "timed_ms": round(dt * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic" if not stub else "synthetic (STUB engine: rank-code test, not a measurement)",
+        "config": {"workload": "isis-100k: IS-IS L2 100000 routers / 1000000 directed entries, metrics U[1,100], "
+                               "64 concurrent SPF roots per GPU per step (BASELINE.json configs[2])",
+                   "n_vertices": n, "n_entries": e, "roots_per_step_per_gpu": R, "mask_words": W,
+                   "outputs": "dist u32 + hops u16 + flags u16 + first-hop mask u64 per (root,vertex), in HBM",
+                   "parallelism": f"roots sharded over {world} GPU(s) by hspf_multi_run_async / _wait (C ABI), graph replicated",
+                   "steps_in_flight": depth,
+                   "gather": gather_via},
+    }
+
+
+DUMP_BYTES = 60_000_000      # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path: str, b: dict, hrow: slice, dist_roots: np.ndarray, roots: np.ndarray, n: int, W: int) -> None:
+    """--dump-outputs: the tables the last timed step delivered, as a caller reads them, for every root and a fixed, seeded
+    sample of vertices (the same for every run with the same arguments):
+      dist.npy [len(dist_roots), k] float64 (u32; HSPF_DIST_INF = 4294967295), hops.npy / flags.npy [R, k] float32 (u16;
+      flags: the HSPF_RF_* bits), first_hop_mask_lo.npy / _hi.npy [R, k, W] float64 (low / high 32 bits of each u64 word),
+      vertex_index.npy [k], dist_roots.npy, roots.npy float64."""
+    import torch
+    rd = len(dist_roots)
+    per_vertex = 8 * rd + len(roots) * (4 + 4 + 16 * W) + 8
+    k = min(n, DUMP_BYTES // per_vertex)
+    vidx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    sel = torch.from_numpy(vidx.astype(np.int64)).to(b["dist"].device)
+
+    def take(t):
+        return t.index_select(1, sel).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    mask = take(b["mask"][hrow]).view(np.uint64)
+    arrays = {"dist": take(b["dist"]).view(np.uint32).astype(np.float64),
+              "hops": take(b["hops"][hrow]).view(np.uint16).astype(np.float32),
+              "flags": (take(b["flags"][hrow]).view(np.uint16) & 3).astype(np.float32),     # HSPF_RF_IN_SPT | HSPF_RF_EXACT
+              "first_hop_mask_lo": (mask & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "first_hop_mask_hi": (mask >> np.uint64(32)).astype(np.float64),
+              "vertex_index": vidx.astype(np.float64),
+              "dist_roots": np.asarray(dist_roots).astype(np.float64), "roots": np.asarray(roots).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -859,10 +914,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--gather", choices=["dist", "none"], default="dist",
                     help="N>1: all-gather the per-root distance tables each step (default) or not")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--min-timed-ms", type=float, default=200.0,
-                    help="the timed region is repeated in whole multiples of --steps until it holds at least this much work")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and the measurements beside the headline: oracle verification, one-step-at-a-time "
+                         "pass, roofline and phase figures, the exchange block (N > 1), CPU baselines and the other blocks (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and the blocks beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result tables (a fixed, seeded sample of vertices) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # the host driver only supports dmabuf IPC (RCCL / cross-process device memory); harmless when already set
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -960,12 +1020,13 @@ def main():
     nb = depth + 1
     # device results (row-major [root][vertex]), one set per step in flight + 1; the distance table holds ALL roots when gathered
     bufs = []
+    # (zero-filled: every table is touched once during setup, not by the first timed step that writes it)
     for _ in range(nb + 1):                    # (+ 1: the untimed one-at-a-time pass and the row-count run keep out of the timed steps' tables)
         bufs.append(dict(
-            dist=torch.empty((RA, n), dtype=torch.int32, device=dev),
-            hops=torch.empty((RA if sharded_in_lib else R, n), dtype=torch.int16, device=dev),
-            flags=torch.empty((RA if sharded_in_lib else R, n), dtype=torch.int16, device=dev),
-            mask=torch.empty((RA if sharded_in_lib else R, n, W), dtype=torch.int64, device=dev)))
+            dist=torch.zeros((RA, n), dtype=torch.int32, device=dev),
+            hops=torch.zeros((RA if sharded_in_lib else R, n), dtype=torch.int16, device=dev),
+            flags=torch.zeros((RA if sharded_in_lib else R, n), dtype=torch.int16, device=dev),
+            mask=torch.zeros((RA if sharded_in_lib else R, n, W), dtype=torch.int64, device=dev)))
 
     pending = [None]
     phase = {"relax_ms": 0.0, "dag_ms": 0.0, "finish_ms": 0.0, "total_ms": 0.0, "n_relax": 0, "n_dag": 0,
@@ -1022,29 +1083,11 @@ def main():
             dist.barrier()
         cuda.synchronize()
 
-    tw = time.perf_counter()
     for i in range(args.warmup):
         step(i, False)
     fence()
-    tw = time.perf_counter() - tw
-    # The timed region: --steps steps, repeated in whole multiples until it holds >= --min-timed-ms of work (one clock
-    # hiccup must not move the headline; 20 steps are 9 ms).  The multiple is fixed BEFORE timing, from the warm-up
-    # rate (max over ranks), so every rank times the same number of steps.
-    est = tw / max(args.warmup, 1) if args.warmup else 1e-3
-    # The warm-up holds the slow runs of a fresh instance (first touch of every buffer): its rate under-counts how many
-    # steps 200 ms take.  A few more untimed steps give the rate the timed region will run at (warm-up too: nothing of
-    # them is reported).
-    tc = time.perf_counter()
-    for i in range(12):
-        step(i, False)
-    fence()
-    est = min(est, (time.perf_counter() - tc) / 12)
-    if world > 1:
-        t = torch.tensor([est], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        est = float(t.item())
-    reps = max(1, int(np.ceil(1.3 * args.min_timed_ms * 1e-3 / max(args.steps * est, 1e-9))))   # warm-up steps run long: margin
-    timed_steps = args.steps * reps
+    # The timed region: exactly --steps steps (every rank times the same number).
+    timed_steps = args.steps
     t0 = time.perf_counter()
     for i in range(timed_steps):
         step(i, True)
@@ -1055,6 +1098,25 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    last = bufs[(timed_steps - 1) % nb]
+    own = slice(row0, row0 + R)
+    hrow = own if sharded_in_lib else slice(0, R)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, hrow, all_roots if RA == len(all_roots) else roots, roots, n, W)
+    head = dict(world=world, steps=args.steps, warmup=args.warmup, timed_steps=timed_steps, dt=dt, R=R, n=n, e=e, W=W,
+                depth=depth, gather_via=gather_via, stub=stub)
+
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline(**head)), flush=True)
+        m.free_graph(mg)
+        m.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # --full: everything below is beside the headline, outside the timed region.
     # One step at a time on the same context, UNTIMED for the headline: the per-kernel figures of the roofline block come
     # from here (a lane's HIP events also span the launches of the other steps in flight), and so does the rate a caller
     # gets that has only one batch to run.
@@ -1069,10 +1131,6 @@ def main():
             record_stats()
     cuda.synchronize()
     one_dt = (time.perf_counter() - t1) / one_steps
-
-    last = bufs[(timed_steps - 1) % nb]
-    own = slice(row0, row0 + R)
-    hrow = own if sharded_in_lib else slice(0, R)
     assert phase["n_exact"] == 0, "headline workload must stay on the wavefront-parallel path"
 
     # what was timed is what is checked: the last timed step's results of this rank's 64 roots, every (root, vertex),
@@ -1148,21 +1206,9 @@ def main():
             except Exception:   # noqa: BLE001
                 traffic = None
         dev_ms = phase["total_ms"] / K
-        out = {
-            "metric": "full-SPF runs/sec on 100k-vertex synthetic LSDB",
-            "value": round(value, 2), "unit": "spf_runs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / timed_steps * 1e3, 4),
-            "timed_steps": timed_steps, "timed_ms": round(dt * 1e3, 2), "verified_roots": verified,
-            "verified_gathered_dist_roots": verified_gathered,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic" if not stub else "synthetic (STUB engine: rank-code test, not a measurement)",
-            "config": {"workload": "isis-100k: IS-IS L2 100000 routers / 1000000 directed entries, metrics U[1,100], "
-                                   "64 concurrent SPF roots per GPU per step (BASELINE.json configs[2])",
-                       "n_vertices": n, "n_entries": e, "roots_per_step_per_gpu": R, "mask_words": W,
-                       "outputs": "dist u32 + hops u16 + flags u16 + first-hop mask u64 per (root,vertex), in HBM",
-                       "parallelism": f"roots sharded over {world} GPU(s) by hspf_multi_run_async / _wait (C ABI), graph replicated",
-                       "steps_in_flight": depth,
-                       "gather": gather_via},
+        out = headline(**head)
+        out.update({
+            "verified_roots": verified, "verified_gathered_dist_roots": verified_gathered,
             "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved / 1e9, 3),
                          "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK, 5),
                          "frac_is": "whole run: value x B_alg / peak (emit, init and launch gaps included)",
@@ -1186,7 +1232,7 @@ def main():
                                    "dense_passes": phase.get("dense_passes"),
                                    "fused_state_bytes": phase["state_bytes"], "narrow_overflows": phase["narrow_overflow"],
                                    "rows_recomputed_per_step": rows_recomputed, "rows_x_N": round(rows_recomputed / n, 2)},
-        }
+        })
         if exchange is not None:
             out["exchange"] = exchange
         if world == 1 and not args.no_cpu_baseline:

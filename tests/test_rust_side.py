@@ -1,9 +1,8 @@
 """The Rust side of the binding (rust/): what can be checked without rustc.  SURVEY.md section 7 step 9 / north_star
 "new holo-spf-hip crate": the crate, the two glue modules and the call-site patches are FILES; here: sys.rs is the
-header, the wrapper and the glue only use names that exist, the patches apply to the reference tree."""
+header, the wrapper and the glue only use names that exist."""
 import os
 import re
-import subprocess
 import sys
 
 import pytest
@@ -11,7 +10,6 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 RUST = os.path.join(ROOT, "rust")
-REF = "/root/reference"
 
 
 def _hdr():
@@ -92,51 +90,68 @@ def test_every_function_of_the_header_has_a_safe_wrapper_or_is_on_the_inspection
     assert unbound == ["hspf_get_stream", "hspf_graph_n_edges", "hspf_graph_n_edges_kept", "hspf_graph_n_vertices", "hspf_set_stream"], unbound
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "holo-isis")), reason="reference tree not mounted")
-def test_patches_are_current_and_apply_to_the_reference_tree(tmp_path):
-    import make_rust_patches
-    old = {p: open(os.path.join(RUST, "patches", p)).read() for p in os.listdir(os.path.join(RUST, "patches"))}
-    make_rust_patches.OUT = str(tmp_path)
-    sys.argv = ["make_rust_patches.py", REF]
-    make_rust_patches.main()
-    for p, text in old.items():
-        assert open(os.path.join(str(tmp_path), p)).read() == text, f"rust/patches/{p} is stale"
-        r = subprocess.run(["patch", "--dry-run", "-p1", "-d", REF, "-i", os.path.join(RUST, "patches", p)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
+def _calls(text: str, callee: str) -> list:
+    """Argument counts of every call `callee(...)` in Rust source `text` (line comments dropped; a match must not be
+    the tail of a longer name; a callee ".name" is a method call)."""
+    code = re.sub(r"//[^\n]*", "", text)
+    out = []
+    head = "" if callee.startswith(".") else r"(?<![A-Za-z0-9_])"
+    for m in re.finditer(head + r"%s\(" % re.escape(callee), code):
+        depth, i, args, cur = 1, m.end(), [], ""
+        while depth:
+            c = code[i]
+            if c in "([{":
+                depth += 1
+            elif c in ")]}":
+                depth -= 1
+            if depth == 1 and c == ",":
+                args.append(cur); cur = ""
+            elif depth:
+                cur += c
+            i += 1
+        args.append(cur)
+        out.append(len([a for a in args if a.strip()]))
+    return out
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "holo-isis")), reason="reference tree not mounted")
 def test_glue_calls_reference_items_that_exist_with_the_reference_arity():
-    """The parent-module items the glue relies on: still there, still taking what the glue passes."""
-    isis = open(os.path.join(REF, "holo-isis", "src", "spf.rs")).read()
-    for fn, nargs in (("vertex_edges", 6), ("zeroth_lsp", 3), ("resolve_nexthop", 8)):
-        m = re.search(r"fn %s(?:<[^>]*>)?\(\s*(.*?)\)\s*(?:->|\{)" % fn, isis, flags=re.S)
-        assert m, fn
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == nargs, fn
+    """The parent-module items the glue relies on: still there, still taking what the glue passes.  The holo side is
+    recorded in tests/golden/rust_reference_items.json (names and parameter counts; tools/make_rust_reference_items.py
+    re-records it from a holo tree); every call site of the glue is checked against it."""
+    import json
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "rust_reference_items.json")))
+    fns = ref["functions"]
+    for fn, nargs in (("vertex_edges", 6), ("zeroth_lsp", 3), ("resolve_nexthop", 8), ("vertex_networks", 11),
+                      ("route_install", 6), ("route_uninstall", 3), ("Route::new", 3), ("Route::distance", 1)):
+        assert len(fns[fn]["params"]) == nargs, fn
     glue = open(os.path.join(RUST, "holo-isis", "src", "spf", "hip.rs")).read()
+    # every call of a recorded function passes what the recorded signature takes
+    for fn in ("vertex_edges", "zeroth_lsp", "resolve_nexthop", "vertex_networks", "route_install", "route_uninstall", "Route::new"):
+        got = _calls(glue, fn)
+        assert got and all(k == len(fns[fn]["params"]) for k in got), (fn, got)
+    got = _calls(glue, ".distance")
+    assert got and all(k == len(fns["Route::distance"]["params"]) for k in got), got
     assert glue.count("resolve_nexthop(&mut nexthop, level, mt_id, &parent, &link, &mut used_adjs, interfaces, adjacencies)") == 1
     assert "vertex_edges(vid, mt_id, metric_mode, metric_type, lsdb, lsp_entries)" in glue
     # round 5: the routes / wire step from device tables (hip::update_rib) and the MANET ancestor sets
-    m = re.search(r"fn vertex_networks<'a>\(\s*(.*?)\)\s*->", isis, flags=re.S)
-    assert m and len([a for a in m.group(1).split(",") if a.strip()]) == 11
     assert glue.count("vertex_networks(") == 1 and "Route::new(&vertex, network, level)" in glue
-    route = open(os.path.join(REF, "holo-isis", "src", "route.rs")).read()
-    for name in ("pub(crate) fn new(\n        vertex: &Vertex,\n        vertex_network: &VertexNetwork,\n        level: LevelNumber,", "const INSTALLED", "const CONNECTED",
-                 "pub(crate) const fn distance(&self, config: &InstanceCfg)", "pub struct Nexthop {"):
-        assert name in route, name
-    tx = open(os.path.join(REF, "holo-isis", "src", "ibus", "tx.rs")).read()
-    m = re.search(r"pub\(crate\) fn route_install\(\s*(.*?)\)\s*\{", tx, flags=re.S)
-    assert m and len([a for a in m.group(1).split(",") if a.strip()]) == 6
     assert "ibus::tx::route_install(&instance.tx.ibus, &prefix, &route, old_sr_label, distance, interfaces)" in glue
-    m = re.search(r"pub\(crate\) fn route_uninstall\(\s*(.*?)\)\s*\{", tx, flags=re.S)
-    assert m and len([a for a in m.group(1).split(",") if a.strip()]) == 3
-    inst = open(os.path.join(REF, "holo-isis", "src", "instance.rs")).read()
-    assert "pub(crate) fn rib_mut(" in inst and "pub(crate) fn is_l2_attached_to_backbone(" in inst
-    manet = open(os.path.join(REF, "holo-isis", "src", "flooding", "manet.rs")).read()
-    assert manet.count("spt_hopcount.is_on_path(") + manet.count(".spt_hopcount\n                .is_on_path(") == 3     # the three queries the patch redirects
-    ospf = open(os.path.join(REF, "holo-ospf", "src", "spf.rs")).read()
-    for name in ("fn vertex_lsa_find(", "fn vertex_lsa_links<'a>(", "fn calc_nexthops(", "RouteRtr::new(", "is_vlink_endpoint()", "spf_run_count += 1"):
-        assert name in ospf, name
+    assert "ibus::tx::route_uninstall(&instance.tx.ibus, &prefix, &route)" in glue
+    # the struct the glue builds names every recorded field; the flags it tests exist
+    lits = re.findall(r"\bNexthop \{([^{}]*)\}", glue)
+    assert lits
+    for lit in lits:
+        names = [re.split(r"[:\s]", f.strip())[0] for f in lit.split(",") if f.strip()]
+        assert sorted(names) == sorted(ref["structs"]["Nexthop"]["fields"]), names
+    used_flags = set(re.findall(r"RouteFlags::([A-Z_0-9]+)", glue))
+    assert {"INSTALLED", "CONNECTED"} <= used_flags <= set(ref["flags"]["RouteFlags"]["names"]), used_flags
+    for name in ("rib_mut", "is_l2_attached_to_backbone"):
+        assert name in ref["items"]["holo-isis/src/instance.rs"] and f".{name}(" in glue, name
+    # the MANET patch redirects every recorded is_on_path query of flooding/manet.rs
+    patch = open(os.path.join(RUST, "patches", "holo-isis.patch")).read()
+    removed = [ln for ln in patch.splitlines() if ln.startswith("-") and not ln.startswith("---") and "is_on_path(" in ln]
+    assert ref["is_on_path_queries"]["count"] == 3 and len(removed) == ref["is_on_path_queries"]["count"], removed
     g2 = open(os.path.join(RUST, "holo-ospf", "src", "spf", "hip.rs")).read()
     assert "V::calc_nexthops(" in g2 and "V::vertex_lsa_links(" in g2 and "V::vertex_lsa_find(" in g2
+    for name in ("vertex_lsa_find", "vertex_lsa_links", "calc_nexthops", "RouteRtr::new", "is_vlink_endpoint", "spf_run_count"):
+        assert name in ref["items"]["holo-ospf/src/spf.rs"] and name in g2, name

@@ -16,9 +16,9 @@ PY
 }
 for rep in 1 2; do
   cp /tmp/lib_default.so holo_amd/libholo_spf_hip.so
-  python bench.py --no-cpu-baseline > $OUT/default_$rep.json 2> $OUT/default_$rep.err; pick $OUT/default_$rep.json
+  python bench.py --full --no-cpu-baseline > $OUT/default_$rep.json 2> $OUT/default_$rep.err; pick $OUT/default_$rep.json
   cp $EXP holo_amd/libholo_spf_hip.so
-  python bench.py --no-cpu-baseline > $OUT/exp_$rep.json 2> $OUT/exp_$rep.err; pick $OUT/exp_$rep.json
+  python bench.py --full --no-cpu-baseline > $OUT/exp_$rep.json 2> $OUT/exp_$rep.err; pick $OUT/exp_$rep.json
 done
 cp $EXP holo_amd/libholo_spf_hip.so
 timeout 600 python -m pytest tests/test_gpu_parity.py -x -q -k "isis_100k or random_lsdb_normal or lean" 2>&1 | tail -3

@@ -16,11 +16,11 @@ PY
 }
 for rep in 1 2; do
   cp /tmp/lib_default.so holo_amd/libholo_spf_hip.so
-  python bench.py --no-cpu-baseline > $OUT/default_$rep.json 2> $OUT/default_$rep.err; pick $OUT/default_$rep.json
+  python bench.py --full --no-cpu-baseline > $OUT/default_$rep.json 2> $OUT/default_$rep.err; pick $OUT/default_$rep.json
   for L in "$@"; do
     b=$(basename $L .so)
     cp $L holo_amd/libholo_spf_hip.so
-    python bench.py --no-cpu-baseline > $OUT/${b}_$rep.json 2> $OUT/${b}_$rep.err; pick $OUT/${b}_$rep.json
+    python bench.py --full --no-cpu-baseline > $OUT/${b}_$rep.json 2> $OUT/${b}_$rep.err; pick $OUT/${b}_$rep.json
   done
 done
 cp /tmp/lib_default.so holo_amd/libholo_spf_hip.so

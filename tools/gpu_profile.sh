@@ -8,10 +8,10 @@ export TMPDIR=/tmp
 STAGE=${STAGE:-0}
 R=$(pwd); OUT=$R/gpurun_out/prof; rm -rf $OUT; mkdir -p $OUT
 if [ "$STAGE" != "2" ]; then
-python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err < /dev/null
 tail -c 2500 $OUT/bench.json
 cd /tmp
-timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o spf -- python $R/bench.py --steps 10 --warmup 2 --min-timed-ms 0 --no-cpu-baseline > $OUT/trace.log 2>&1 < /dev/null
+timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o spf -- python $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/trace.log 2>&1 < /dev/null
 cp $OUT/trace/spf_kernel_stats.csv $OUT/kernel_stats.csv
 find $OUT -name "*kernel_trace.csv" -size +2M -delete
 cd $R
@@ -22,7 +22,7 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_
             "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM" \
             "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE"; do
   i=$(echo "$pass" | md5sum | cut -c1-6)
-  timeout -k 5 120 rocprofv3 --pmc $pass --output-format csv -d $OUT/pmc_$i -o q -- python $R/bench.py --steps 3 --warmup 1 --min-timed-ms 0 --no-cpu-baseline > $OUT/pmc_$i.log 2>&1 < /dev/null
+  timeout -k 5 120 rocprofv3 --pmc $pass --output-format csv -d $OUT/pmc_$i -o q -- python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/pmc_$i.log 2>&1 < /dev/null
 done
 # calibration of FETCH_SIZE / WRITE_SIZE on known byte counts in the access shapes of the engine's kernels (4 B per lane:
 # 256-byte rows streamed and gathered; 16 B per lane; Infinity-Cache hits) — tools/ubench/fetch_calib.hip
