@@ -1971,6 +1971,14 @@ int Run::run_phase(uint32_t est, uint32_t pre_zeroed, Launch &&launch, uint32_t 
     return HSPF_OK;
   }
 
+// Multiplier and shift that divide every x < 2^31 by d (DivMagic, spf_kernels.hip.h); a dense launch's grid stays below 2^31.
+static DivMagic div_magic_of(uint32_t d) {
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;
+  return DivMagic{(uint32_t)(((1ull << (31u + l)) + d - 1u) / d), 31u + l};
+}
+static PassGrid pass_grid(uint32_t per_pass, uint32_t blocks) { return PassGrid{per_pass, blocks, div_magic_of(per_pass), div_magic_of(blocks)}; }
+
 // One fixed point over the packed state.  mode 0: 8-byte state, 1: 4-byte state (k_fused), 2: 4-byte state, lean sweep (k_fused_lean).
 int Run::fused_run(int mode) {
       const bool nar = mode != 0, use_lean = mode == 2;
@@ -2019,6 +2027,8 @@ int Run::fused_run(int mode) {
       if (use_lean) on_retry = [&]() { hipLaunchKernelGGL(k_clear_lane_flag, dim3((L + 255) / 256), dim3(256), 0, s, d_lf, L, (uint32_t)LF_OVERFLOW); };
       if (giant && hipMemsetAsync(ctx->giant_part.p, 0, giant_tags * 4, s) != hipSuccess) { ctx->last_error = "giant tags"; return HSPF_E_HIP; }
       const bool dyn_parts = g->n_zero_rows && !g->hopcount_like;      // FusedGraph::dyn_part is in use
+      const bool zrows = dyn_parts;                                    // k_fused_lean<.., ZROWS>: the same condition
+      if (use_lean && zrows) st.dbg[0] |= 2u;                          // hspf_stats::dbg[0] bit 1: ... with the zero-cost row instantiation
       if (dyn_parts && hipMemsetAsync(ctx->dyn_part.p, 0, (size_t)DYN_PARTS * L * 4, s) != hipSuccess) { ctx->last_error = "dyn partials"; return HSPF_E_HIP; }
       if (nar) hipLaunchKernelGGL((k_init_fused<uint32_t>), dim3((L + 3) / 4), dim3(256), 0, s, gd, (uint32_t *)d_st, d_stamp, (uint8_t *)ctx->hnb.p, d_roots, tabs, L, ns);
       else     hipLaunchKernelGGL((k_init_fused<uint64_t>), dim3((L + 3) / 4), dim3(256), 0, s, gd, d_st, d_stamp, (uint8_t *)ctx->hnb.p, d_roots, tabs, L, ns);
@@ -2061,29 +2071,32 @@ int Run::fused_run(int mode) {
 #define HSPF_LAUNCH_FUSED(ST_, MI_, CN_, stp_) do { if (units) HSPF_LAUNCH_FUSED2(ST_, MI_, CN_, true, stp_); else HSPF_LAUNCH_FUSED2(ST_, MI_, CN_, false, stp_); } while (0)
         const bool units = g->n_heavy_chunks != 0;
         if (use_lean) {
-#define HSPF_LAUNCH_LEAN(CN_, MD_, HD_, grid_, pb_, base_, thr_) hipLaunchKernelGGL((k_fused_lean<CN_, MD_, HD_>), grid_, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n, (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (uint32_t *)d_st, (const uint32_t *)g->d_ell_od, d_roots, d_lf, net_nh, ignore_ovl, P, d_ctl, pb_, B, base_, thr_)
-#define HSPF_LAUNCH_LEAN_C(MD_, HD_, grid_, pb_, base_, thr_) do { if (count_rows) HSPF_LAUNCH_LEAN(true, MD_, HD_, grid_, pb_, base_, thr_); else HSPF_LAUNCH_LEAN(false, MD_, HD_, grid_, pb_, base_, thr_); } while (0)
-          // dense launch in batch-major placement (k_fused_lean<.., BMAJ>; pass_blocks = row blocks of one batch)
-#define HSPF_LAUNCH_LEAN_BM(CN_, MD_, HD_, grid_, pb_, base_, thr_) hipLaunchKernelGGL((k_fused_lean<CN_, MD_, HD_, true>), grid_, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n, (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (uint32_t *)d_st, (const uint32_t *)g->d_ell_od, d_roots, d_lf, net_nh, ignore_ovl, P, d_ctl, pb_, B, base_, thr_)
-#define HSPF_LAUNCH_LEAN_B(MD_, HD_, grid_, pb_, base_, thr_) do { if (count_rows) HSPF_LAUNCH_LEAN_BM(true, MD_, HD_, grid_, pb_, base_, thr_); else HSPF_LAUNCH_LEAN_BM(false, MD_, HD_, grid_, pb_, base_, thr_); } while (0)
+          // k_fused_lean<COUNT, MODE, HEAD, BMAJ, ZROWS>: ZROWS = the graph has RF_ZERO rows and is not hop-count-like (the
+          // count is kept current by every patch path: cost-only, structural-incremental, rebuild); without them the
+          // kernel carries no zero-cost row path and no LF_DYN bookkeeping
+#define HSPF_LAUNCH_LEAN3(CN_, MD_, HD_, BM_, ZR_, grid_, pgr_, base_, thr_) hipLaunchKernelGGL((k_fused_lean<CN_, MD_, HD_, BM_, ZR_>), grid_, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n, (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (uint32_t *)d_st, (const uint32_t *)g->d_ell_od, d_roots, d_lf, net_nh, ignore_ovl, P, d_ctl, B, pgr_, base_, thr_)
+#define HSPF_LAUNCH_LEAN2(CN_, MD_, HD_, BM_, grid_, pgr_, base_, thr_) do { if (zrows) HSPF_LAUNCH_LEAN3(CN_, MD_, HD_, BM_, true, grid_, pgr_, base_, thr_); else HSPF_LAUNCH_LEAN3(CN_, MD_, HD_, BM_, false, grid_, pgr_, base_, thr_); } while (0)
+#define HSPF_LAUNCH_LEAN_C(MD_, HD_, grid_, pgr_, base_, thr_) do { if (count_rows) HSPF_LAUNCH_LEAN2(true, MD_, HD_, false, grid_, pgr_, base_, thr_); else HSPF_LAUNCH_LEAN2(false, MD_, HD_, false, grid_, pgr_, base_, thr_); } while (0)
+          // dense launch in batch-major placement (k_fused_lean<.., BMAJ, ..>; PassGrid::blocks = row blocks of one batch)
+#define HSPF_LAUNCH_LEAN_B(MD_, HD_, grid_, pgr_, base_, thr_) do { if (count_rows) HSPF_LAUNCH_LEAN2(true, MD_, HD_, true, grid_, pgr_, base_, thr_); else HSPF_LAUNCH_LEAN2(false, MD_, HD_, true, grid_, pgr_, base_, thr_); } while (0)
           // at least 8 batches: each XCD takes whole batches (their state stays in its L2 across the passes); HSPF_VARIANT bit 24: off (A/B)
           const uint32_t bm_blocks = (n + (uint32_t)FVPB - 1u) / (uint32_t)FVPB;
           const bool bmaj = B >= 8u && 8ull * ((B + 7u) / 8u) * bm_blocks * per_launch < (1ull << 31);
           const dim3 bgrid(8u * ((B + 7u) / 8u) * bm_blocks);        // one pass over all batches, batch-major
           // (the stamped sweeps keep the row-major placement: in batch-major form they were slower — 4.48 against 4.33 ms for the
           // ten areas of configs[3], profiles/r04_notes.md r04y)
-          if (sweep < plan_h) HSPF_LAUNCH_LEAN_C(0, true, fgrid, 0u, 0u, thr_enter);
-          else if (sweep < plan_h + plan_nd) {
+          const PassGrid pg0{};                                    // (the stamped modes: 2-D grid, no passes)
+          if (sweep < plan_h) HSPF_LAUNCH_LEAN_C(0, true, fgrid, pg0, 0u, thr_enter);
+          else if (sweep < plan_h + plan_nd) {                     // np passes, 1-D
             const uint32_t base = (sweep - plan_h) * per_launch, np = std::min(per_launch, plan_P - base);
-            if (bmaj)         HSPF_LAUNCH_LEAN_B(1, false, dim3(bgrid.x * np), bm_blocks, base, thr_stay);
-            else if (np > 1u) HSPF_LAUNCH_LEAN_C(1, false, dim3(fgrid.x * B * np), fgrid.x, base, thr_stay);
-            else              HSPF_LAUNCH_LEAN_C(1, false, fgrid, 0u, base, thr_stay);
-          } else if (plan_on && sweep == plan_h + plan_nd) HSPF_LAUNCH_LEAN_C(2, false, fgrid, 0u, 0u, 0u);
-          else HSPF_LAUNCH_LEAN_C(0, false, fgrid, 0u, 0u, 0u);
+            if (bmaj) HSPF_LAUNCH_LEAN_B(1, false, dim3(bgrid.x * np), pass_grid(bgrid.x, bm_blocks), base, thr_stay);
+            else      HSPF_LAUNCH_LEAN_C(1, false, dim3(fgrid.x * B * np), pass_grid(fgrid.x * B, fgrid.x), base, thr_stay);
+          } else if (plan_on && sweep == plan_h + plan_nd) HSPF_LAUNCH_LEAN_C(2, false, fgrid, pg0, 0u, 0u);
+          else HSPF_LAUNCH_LEAN_C(0, false, fgrid, pg0, 0u, 0u);
 #undef HSPF_LAUNCH_LEAN_C
 #undef HSPF_LAUNCH_LEAN_B
-#undef HSPF_LAUNCH_LEAN_BM
-#undef HSPF_LAUNCH_LEAN
+#undef HSPF_LAUNCH_LEAN2
+#undef HSPF_LAUNCH_LEAN3
           return;
         }
         if (giant) {                                   // slices of the due giant rows, ahead of the sweep that merges them

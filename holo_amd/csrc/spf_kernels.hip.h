@@ -1140,7 +1140,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_fu
 // below: 1 % of the rows, and through the general routine 14 % of the run, because a sweep ends with its LAST wave.
 // What moved the run after the per-row cost had stopped mattering (profiles/r03_notes.md r03k, r03o, r03q): that path;
 // launches WITHOUT activation stamps for the sweeps in which nearly every row is due (MODE, learned schedule); and a
-// whole stretch of such sweeps as ONE launch of several passes (pass_blocks), so that a pass starts while the one
+// whole stretch of such sweeps as ONE launch of several passes (PassGrid), so that a pass starts while the one
 // before it drains instead of behind a kernel boundary.
 template <int J> __device__ __forceinline__ uint32_t dpp_bcast16(uint32_t v) {     // lane 16 r + J of every DPP row r
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + J, 0xF, 0xF, false);
@@ -1209,7 +1209,11 @@ __device__ __forceinline__ LeanOut lean_case(__amdgpu_buffer_rsrc_t rs, uint32_t
 // whole stretch, link records staged once in LDS: 25.6 us per pass instead of 20.0 and a stretch that converges like plain
 // Jacobi, because it loses what the in-order grid gives for free: a row reads the lower-numbered neighbours of the SAME
 // pass.  profiles/r04_notes.md r04t; removed.)  Everything is passed in registers.
-template <bool COUNT, int MODE>
+// ZROWS (chosen by the host from the graph's count of RF_ZERO rows): the graph has rows with a zero-cost link from a higher- or
+// equal-numbered source and is not hop-count-like, i.e. the pop order of some root may be dynamic.  Without it the RF_ZERO path,
+// the zcyc loads and the LF_DYN bookkeeping are compiled out: fused_row_any raises `dyn` only through such a link (the links
+// that make a row RF_ZERO), and never on a hop-count graph, whose zero-cost links have their own rule (finish_row_z).
+template <bool COUNT, int MODE, bool ZROWS>
 __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, const __amdgpu_buffer_rsrc_t rs, const __amdgpu_buffer_rsrc_t ra,
                                            const uint32_t lane, const uint32_t lane4, const uint32_t wbeg, const uint32_t cur, const FusedParams &P,
                                            const uint32_t *__restrict__ roots, const uint32_t root_slot, const uint32_t net_nexthops,
@@ -1316,7 +1320,7 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
   // wins and is never tight); the first SAFE one with the smallest distance (whole-word minimum: distance, then row order) is
   // the row's one parent when it beats the rest — its hops and ITS mask, no union —, an UNSAFE one that beats everything
   // leaves the distance alone (hops 0, mask 0: the placeholder k_repair fills in).  Either way the lane's root is LF_DYN.
-  if (fastz4 != 0u) {
+  if (ZROWS && fastz4 != 0u) {
     const uint8_t *__restrict__ zc = gp->g.zcyc;
 #pragma unroll 1
     for (uint32_t hm = fastz4; hm != 0u; hm &= hm - 1u) {
@@ -1374,7 +1378,7 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
     RowOut<ST> r;
     if (P.hc) r = fused_row_any<ST, false, true, 4>(g, rs, v, e0, e1, sv, wv, lane, lane4, my_root, root_slot, gp->tabs, net_nexthops, ignore_ovl, P);
     else r = fused_row_any<ST, false, false, 4>(g, rs, v, e0, e1, sv, wv, lane, lane4, my_root, root_slot, gp->tabs, net_nexthops, ignore_ovl, P);
-    dyn = dyn || r.dyn;       // (r.ovf is a per-evaluation test of TRANSIENT values: the lean state's fields are tested on the final words, k_emit_fused)
+    if (ZROWS) dyn = dyn || r.dyn;       // (r.ovf is a per-evaluation test of TRANSIENT values: the lean state's fields are tested on the final words, k_emit_fused)
     if (COUNT) ++n_done;
     const uint64_t ch = __ballot(r.nw != old);
     if (ch == 0ull) continue;
@@ -1414,17 +1418,24 @@ constexpr uint32_t LEAN_CTL_STRIDE = 32u;
 constexpr uint32_t LEAN_CTL_DUE = 0u, LEAN_CTL_PCH = 64u * LEAN_CTL_STRIDE, LEAN_CTL_WORDS = 128u * LEAN_CTL_STRIDE;   // 64 head sweeps, 64 dense passes
 constexpr uint32_t LEAN_SAMPLE = 32u;                                             // wave 0 of every 8th block of an XCD's range counts
 constexpr uint32_t LEAN_SENTINEL = 0xFFFFFFFFu;
-template <bool COUNT, int MODE, bool HEAD, bool BMAJ = false>
-// (amdgpu_num_sgpr: 80 leaves 28 scalar spills in the prologue and ~10 reloads per row — v_readlane from a spill VGPR —, 96 keeps the same
-// 8 waves per SIMD with 40 % fewer of them and 104 has none at 7 waves: 148.3 / 148.2 / 146.6 k runs/s in flight, 117.3 / 115.1 / 112.5 k
-// one at a time; and TWENTY extra vector instructions per row cost 4 %, ten 1.5 %: a dense pass is not bound by VALU issue, although the
-// counters show the vector ALUs ~85 % "busy" — profiles/r06_notes.md r06zf.)
+// x / d for x < 2^31 without a division: (x * m) >> sh with m = ceil(2^(31 + l) / d), sh = 31 + l, l = ceil(log2 d) (exact for
+// every x < 2^31, Granlund & Montgomery 1994; m < 2^32).  Computed on the host, applied by two scalar multiplies and a shift.
+struct DivMagic { uint32_t m, sh; };
+__device__ __forceinline__ uint32_t div_magic(uint32_t x, DivMagic d) { return (uint32_t)(((uint64_t)x * d.m) >> d.sh); }
+// The 1-D grid of a dense launch: per_pass workgroups per pass, blocks = row blocks of a batch (BMAJ: of ONE batch, see below).
+struct PassGrid { uint32_t per_pass, blocks; DivMagic by_pass, by_blocks; };
+template <bool COUNT, int MODE, bool HEAD, bool BMAJ, bool ZROWS>
+// (amdgpu_num_sgpr: round 6 measured 80 / 96 / 104 — 8, 8 and 7 waves per SIMD — at 148.3 / 148.2 / 146.6 k runs/s in flight, 117.3 / 115.1 /
+// 112.5 k one at a time; and TWENTY extra vector instructions per row cost 4 %, ten 1.5 %: a dense pass is not bound by VALU issue, although
+// the counters show the vector ALUs ~85 % "busy" — profiles/r06_notes.md r06zf.  Round 7, with the divisions and (ZROWS = false) the
+// zero-cost row state gone: at 80 the dense instantiation has 52 SGPR spills (62 with ZROWS, 74 before), 55 VGPRs, 8 waves; 96 leaves 27 and
+// measured no faster — profiles/r07_notes.md r07a.)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fused_lean(
     const FusedGraph *__restrict__ gp, int *changed, int sweep, uint32_t *__restrict__ act,
     const uint8_t *__restrict__ hnb, uint32_t n_arg, const uint32_t *__restrict__ ell_so, const uint32_t *__restrict__ ell_w,
     uint32_t *__restrict__ st, const uint32_t *__restrict__ ell_od, const uint32_t *__restrict__ roots, uint32_t *lane_flags,
-    uint32_t net_nexthops, uint32_t ignore_ovl, FusedParams P, uint32_t *__restrict__ ctl, uint32_t pass_blocks, uint32_t pass_batches,
-    uint32_t pass_base, uint32_t thr) {
+    uint32_t net_nexthops, uint32_t ignore_ovl, FusedParams P, uint32_t *__restrict__ ctl, uint32_t pass_batches,
+    PassGrid pgr, uint32_t pass_base, uint32_t thr) {
   typedef uint32_t ST;
   if (sweep > 0 && changed[sweep - 1] == 0) return;
   if (HEAD && sweep > 0 && ctl[LEAN_CTL_DUE + ((uint32_t)sweep - 1u) * LEAN_CTL_STRIDE] >= thr) {   // the dense stretch is due: pass the word on, keep the chain alive
@@ -1439,25 +1450,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fu
   // Blocks are dispatched in order, so a pass starts while the one before it drains — no kernel boundary between two dense
   // sweeps (a dense sweep keeps ~76 % of the wave slots busy: ramp and drain) — and reads what that pass has written
   // except in the rows still in flight; any interleaving is a valid chaotic iteration of the same monotone fixed point,
-  // and the run's end is decided by stamped sweeps behind the stretch.  pass_blocks = G (0: one pass, 2-D grid), pass_batches = B.
+  // and the run's end is decided by stamped sweeps behind the stretch.  pgr: per_pass = G B, blocks = G, and the
+  // multipliers that divide by them (DivMagic: the 32-bit divisions of the block index were ~60 vector instructions of
+  // every wave's prologue); pass_batches = B.  The stamped modes (0, 2) take a 2-D grid (x = block, y = batch).
   // BATCH-MAJOR placement (template BMAJ; dense launches of calls with at least 8 batches): consecutive
   // workgroups go round-robin to the 8 XCDs, so block f of a pass belongs to XCD f % 8 — which then owns the batches
   // x, x + 8, ... whole (all their rows, pass after pass) instead of an eighth of the rows of every batch: the state of a batch
   // of a 5 000-router area is 1.3 MB, two of them and the link records stay in the XCD's 4 MB L2 for the whole stretch,
   // and every neighbour row a wave reads was written on its own XCD (no stale line of another L2 in the way of the pass
-  // order).  pass_blocks = row blocks of ONE batch in this form.  Speed only: any placement gives the same result.
+  // order).  pgr.blocks = row blocks of ONE batch in this form.  Speed only: any placement gives the same result.
   // (BMAJ: its own instantiation — the index arithmetic of both forms in one kernel cost the one-batch headline 3-4 %)
   const bool bmaj = BMAJ && MODE == 1;
   const uint32_t nbat = pass_batches;
-  const uint32_t per_pass = bmaj ? 8u * ((nbat + 7u) >> 3) * pass_blocks : pass_blocks * nbat;      // blocks of one pass
-  const uint32_t fpass = bmaj ? blockIdx.x % per_pass : 0u;
-  const uint32_t batch = bmaj ? (fpass & 7u) + 8u * ((fpass >> 3) / pass_blocks)
-                              : ((MODE == 1 && pass_blocks != 0u) ? (blockIdx.x / pass_blocks) % pass_batches : blockIdx.y);
+  const uint32_t pidx = MODE == 1 ? div_magic(blockIdx.x, pgr.by_pass) : 0u;            // pass of this launch
+  const uint32_t fpass = blockIdx.x - pidx * pgr.per_pass;                              // block of the pass
+  const uint32_t fq = bmaj ? div_magic(fpass >> 3, pgr.by_blocks) : (MODE == 1 ? div_magic(fpass, pgr.by_blocks) : 0u);
+  const uint32_t batch = bmaj ? (fpass & 7u) + 8u * fq : (MODE == 1 ? fq : blockIdx.y);
   const uint32_t n = n_arg;
-  const uint32_t bx = bmaj ? (fpass >> 3) % pass_blocks : ((MODE == 1 && pass_blocks != 0u) ? blockIdx.x % pass_blocks : blockIdx.x);
+  const uint32_t bx = bmaj ? (fpass >> 3) - fq * pgr.blocks : (MODE == 1 ? fpass - fq * pgr.blocks : blockIdx.x);
   // dense pass p of the stretch (counted across its launches): nothing to do when pass p - 2 or p - 3 saw the corrections
   // thin out (their counters: plain loads, one line each, see LEAN_CTL_STRIDE)
-  const uint32_t pg = MODE == 1 ? pass_base + (pass_blocks != 0u ? blockIdx.x / per_pass : 0u) : 0u;
+  const uint32_t pg = MODE == 1 ? pass_base + pidx : 0u;
   uint32_t pc2 = LEAN_SENTINEL, pc3 = LEAN_SENTINEL;
   if (MODE == 1 && thr != 0u && pg >= 2u && pg < 64u) {                 // thr = 0 (HSPF_DENSE_STAY_PCT=0): every planned pass runs
     pc2 = ctl[LEAN_CTL_PCH + (pg - 2u) * LEAN_CTL_STRIDE];
@@ -1497,7 +1510,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fu
   }
   const uint32_t fast4 = (uint32_t)__ballot(lane < (uint32_t)VPW && hb == 0u) & due4;
   const uint32_t fasth4 = (uint32_t)__ballot(lane < (uint32_t)VPW && (hb & ~RF_ROOT) == RF_HNB) & due4;   // next to a root of the batch (or the row of one), nothing else
-  const uint32_t fastz4 = P.hc ? 0u : ((uint32_t)__ballot(lane < (uint32_t)VPW && hb == RF_ZERO) & due4);  // a zero-cost link from a higher-numbered source, nothing else
+  const uint32_t fastz4 = (!ZROWS || P.hc) ? 0u : ((uint32_t)__ballot(lane < (uint32_t)VPW && hb == RF_ZERO) & due4);  // a zero-cost link from a higher-numbered source, nothing else
   const uint32_t root_slot = batch * 64 + lane;
   const __amdgpu_buffer_rsrc_t ra = st_rsrc(A, n * 4u);
   uint32_t info[VPW];                                             // low byte of ELL entry 0: in-degree | (> 16 out-links) << 5 | network << 7
@@ -1511,7 +1524,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fu
   uint64_t any = 0ull;
   bool dyn = false;
   uint32_t n_done = 0, n_chg = 0;
-  lean_group<COUNT, MODE>(gp, rs, ra, lane, lane4, wbeg, cur, P, roots, root_slot, net_nexthops, ignore_ovl, due4, fast4, fasth4, fastz4,
+  lean_group<COUNT, MODE, ZROWS>(gp, rs, ra, lane, lane4, wbeg, cur, P, roots, root_slot, net_nexthops, ignore_ovl, due4, fast4, fasth4, fastz4,
                           sov, wk, od, oldq, info, any, dyn, n_done, n_chg);
   // (Round 5, r05c: INNER iterations — the wave evaluating its rows again with the records it holds, no set-up and no record
   // round trip — were measured and rejected: an iteration that sees only its own rows' and some neighbouring waves' stores
@@ -1524,7 +1537,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fu
   else if (any != 0ull && lane == 0) changed[sweep] = 1;
   if (COUNT && lane == 0) atomicAdd(&gp->rows_done[(blockIdx.x + wave) & 255u], n_done);
   if (MODE == 1 && sampler && lane == 0 && n_chg != 0u && pg < 64u) atomicAdd(&ctl[LEAN_CTL_PCH + pg * LEAN_CTL_STRIDE], n_chg);
-  if (dyn) raise_dyn(gp, lane_flags, root_slot, blockIdx.x * 4u + wave);
+  if (ZROWS && dyn) raise_dyn(gp, lane_flags, root_slot, blockIdx.x * 4u + wave);
 }
 
 // ---------------------------------------------------------------------------------------------

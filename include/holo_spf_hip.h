@@ -169,7 +169,8 @@ typedef struct {
                                   2: one to eight roots on a mid-size graph, one XCD per root (k_xcd, one launch):
                                   dbg[1] then holds its sweeps (bits 0-15; bit 31: a workgroup ran on another XCD) */
   uint32_t lane_vertex;        /* 1: a few roots on a larger graph, the run took the lane = vertex kernel (k_lv)   */
-  uint32_t dbg[4];             /* [0]: 1 = the run took the lean sweep (k_fused_lean); [1]: lean sweep: bits 0-7 = dense passes that did
+  uint32_t dbg[4];             /* [0]: bit 0 = the run took the lean sweep (k_fused_lean), bit 1 = its instantiation for graphs with zero-cost rows
+                                  (RF_ZERO rows, not hop-count-like); [1]: lean sweep: bits 0-7 = dense passes that did
                                   work, 8-15 = head sweeps that ran, 16-23 = dense passes planned, 24-30 = head sweeps planned
                                   (the plan is sized from the previous run, the launches decide on the device);
                                   bit 31 = a wide-mask run left the graph's leaves to the emit;
