@@ -214,6 +214,16 @@ struct hspf_ctx {
   const void *pf_res_ptr = nullptr, *pf_res_vtx = nullptr, *pf_res_met = nullptr;
   DevBuf pack;                                      // record stream of hspf_routes_pack
   uint32_t last_diff_count = 0;                     // changed pairs of the last hspf_routes_diff_device (hspf_routes_diff_count)
+  // hspf_routes_events: action bytes + tile offsets + total | the record stream's staging (grown from what calls needed)
+  DevBuf evs_scr, evs_rec;
+  uint32_t *h_ev = nullptr;                          // pinned: the event total, stored by k_events_scan itself
+  struct EvState {                                   // the last hspf_routes_events, for hspf_routes_events_rest
+    bool valid = false;
+    uint32_t n_prefixes = 0, W = 0, with_silent = 0, total = 0, staged = 0;   // staged: records of the stream the staging holds
+    uint64_t count = 0;
+    hspf_routes o{}, n{};
+  } evs;
+  uint32_t ev_hint = 0, ev_hint2 = 0;                // records the last call and the one before produced: the smaller sizes the ONE copy of the next
   DevBuf gb_kx;                                                 // hspf_graph_upload_keyed: keys, ranks, resolved targets
   DevBuf gb, gb_delta, gb_hub, giant_part;                      // graph build scratch, patch delta, hub-mode sort buffers
   DevBuf leaf_jobs;                                             // run_classes: the rows derived for leaf roots (LeafRootJob)
@@ -851,7 +861,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -862,6 +872,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->h_up) (void)hipHostFree(ctx->h_up);
   release(ctx->up);
   if (ctx->h_info) (void)hipHostFree(ctx->h_info);
+  if (ctx->h_ev) (void)hipHostFree(ctx->h_ev);
   for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -3334,6 +3345,7 @@ uint32_t hspf_async_lanes(const hspf_ctx *ctx) { return ctx ? (ctx->lanes.empty(
 static int routes_device_impl(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_roots, uint32_t n_mask_words,
                               const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                               const hspf_prefix_table *t, hspf_routes *out) {
+  if (ctx) ctx->evs.valid = false;                        // a route call: the kept event stream (hspf_routes_events_rest) is void
   if (!ctx || !t || !out || !dist_dev || !flags_dev || !mask_dev || !out->best_metric || !out->best_entry ||
       !out->nexthop_mask || n_roots == 0 || n_mask_words == 0 || !t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric)))
     return HSPF_E_INVAL;
@@ -3440,6 +3452,7 @@ int hspf_rib_clear_device(hspf_ctx *ctx, const hspf_rib_device *rib) {
 int hspf_rib_fold_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t area_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
                          const uint64_t *mask_dev, const hspf_prefix_table *t, const uint32_t *prefix_map, uint32_t area_index, uint32_t word_offset,
                          const hspf_rib_device *rib) {
+  if (ctx) ctx->evs.valid = false;
   if (!ctx || !t || !rib || !dist_dev || !flags_dev || !mask_dev || !rib->best_metric || !rib->best_entry || !rib->nexthop_mask || !rib->origin ||
       area_mask_words == 0 || rib->n_mask_words == 0 || !t->pfx_ptr || (t->n_prefixes && !prefix_map) || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric || !t->pfx_origin)))
     return HSPF_E_INVAL;
@@ -3490,6 +3503,7 @@ int hspf_rib_fold_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t area_mask_
 static int routes_diff_device_impl(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint32_t n_mask_words,
                                    const hspf_routes *old_dev, const hspf_routes *new_dev,
                                    uint8_t *action_dev, uint32_t *changed_dev, uint32_t *changed_ptr_dev) {
+  if (ctx) ctx->evs.valid = false;                        // a route call: the kept event stream (hspf_routes_events_rest) is void
   if (!ctx || !old_dev || !new_dev || !action_dev || !changed_dev || !changed_ptr_dev || n_roots == 0 || n_mask_words == 0 ||
       !old_dev->best_metric || !old_dev->best_entry || !old_dev->nexthop_mask ||
       !new_dev->best_metric || !new_dev->best_entry || !new_dev->nexthop_mask)
@@ -3542,6 +3556,7 @@ int hspf_routes_pack(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint3
   if (!ctx || !new_dev || !action_dev || !changed_dev || !changed_ptr_dev || n_roots == 0 || n_mask_words == 0 ||
       !new_dev->best_metric || !new_dev->best_entry || !new_dev->nexthop_mask || (n_records && !records_host))
     return HSPF_E_INVAL;
+  ctx->evs.valid = false;                                  // a route call: the kept event stream is void
   if (n_records == 0) return HSPF_OK;
   // more records than the last hspf_routes_diff_device of this context compacted: the kernel would read list entries nobody wrote
   if (n_records > ctx->last_diff_count) { ctx->last_error = "hspf_routes_pack: n_records exceeds hspf_routes_diff_count()"; return HSPF_E_INVAL; }
@@ -3558,6 +3573,123 @@ int hspf_routes_pack(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint3
     HIPCHK(ctx, hipStreamSynchronize(s));
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) { ctx->last_error = std::string("k_routes_pack: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    return HSPF_OK;
+  });
+}
+
+// ---- the route event stream (include/holo_spf_hip.h): classify -> scan -> write, one synchronisation, one copy ---------
+// Scratch layout (ev_scr): tile_off[n_tiles] | total | action[count] (u8).
+static uint32_t *ev_tile_off(hspf_ctx *ctx) { return (uint32_t *)ctx->evs_scr.p; }
+static uint8_t *ev_action(hspf_ctx *ctx, size_t n_tiles) { return (uint8_t *)((uint32_t *)ctx->evs_scr.p + n_tiles + 4); }
+
+static void events_launch_write(hspf_ctx *ctx, uint32_t clip) {
+  const hspf_ctx::EvState &e = ctx->evs;
+  const size_t n_tiles = (size_t)((e.count + EV_TILE - 1) / EV_TILE);
+  hipLaunchKernelGGL(k_events_write, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, (size_t)e.count, e.n_prefixes, e.W, e.with_silent, clip,
+                     (const uint8_t *)ev_action(ctx, n_tiles), (const uint32_t *)ev_tile_off(ctx),
+                     (const uint32_t *)e.o.best_metric, (const uint32_t *)e.o.best_entry, (const uint32_t *)e.o.nexthop_mask,
+                     (const uint32_t *)e.n.best_metric, (const uint32_t *)e.n.best_entry, (const uint32_t *)e.n.nexthop_mask,
+                     (uint32_t *)ctx->evs_rec.p);
+}
+
+// The staging holds records [0, need) of the last call's stream: grow + rewrite when the write pass was clipped below that.
+static int events_stage(hspf_ctx *ctx, uint32_t need) {
+  hspf_ctx::EvState &e = ctx->evs;
+  if (need <= e.staged) return HSPF_OK;
+  const size_t rec_bytes = (size_t)(EVENT_REC_WORDS + 4u * e.W) * 4;
+  int rc = ensure(ctx, ctx->evs_rec, (size_t)e.total * rec_bytes, false);      // (the whole stream: a caller that asks for a tail usually wants the rest too)
+  if (rc) { e.staged = 0; return rc; }
+  events_launch_write(ctx, e.total);
+  HIPCHK(ctx, hipGetLastError());
+  e.staged = e.total;
+  return HSPF_OK;
+}
+
+static int routes_events_impl(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint32_t n_mask_words,
+                              const hspf_routes *old_dev, const hspf_routes *new_dev, uint32_t flags,
+                              uint32_t capacity, uint32_t *records_host, uint32_t *n_records) {
+  if (n_records) *n_records = 0;
+  ctx->evs.valid = false;
+  if (!old_dev || !new_dev || !n_records || n_roots == 0 || n_mask_words == 0 ||
+      !old_dev->best_metric || !old_dev->best_entry || !old_dev->nexthop_mask ||
+      !new_dev->best_metric || !new_dev->best_entry || !new_dev->nexthop_mask) {
+    ctx->last_error = "hspf_routes_events: NULL table or result pointer, or no roots / mask words"; return HSPF_E_INVAL;
+  }
+  if (capacity && !records_host) { ctx->last_error = "hspf_routes_events: capacity_records > 0 without records_host"; return HSPF_E_INVAL; }
+  if (flags & ~HSPF_EV_SILENT) { ctx->last_error = "hspf_routes_events: unknown flag"; return HSPF_E_INVAL; }
+  const uint64_t count = (uint64_t)n_roots * n_prefixes;
+  if (count >= 0xFFFFFFF0ull) { ctx->last_error = "hspf_routes_events: more than 2^32 (root, prefix) pairs"; return HSPF_E_INVAL; }
+  // (k_events_write counts the words of a 64-pair segment, 64 * (8 + 4 W), in 32 bits)
+  if (n_mask_words > (1u << 20)) { ctx->last_error = "hspf_routes_events: more than 2^20 mask words"; return HSPF_E_INVAL; }
+  hspf_ctx::EvState &e = ctx->evs;
+  e.n_prefixes = n_prefixes; e.W = n_mask_words; e.with_silent = (flags & HSPF_EV_SILENT) ? 1u : 0u; e.count = count;
+  e.o = *old_dev; e.n = *new_dev; e.total = 0; e.staged = 0;
+  if (count == 0) { e.valid = true; return HSPF_OK; }
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (!ctx->h_ev) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ev, 64, hipHostMallocDefault));
+  uint32_t *d_hev = nullptr;
+  HIPCHK(ctx, hipHostGetDevicePointer((void **)&d_hev, ctx->h_ev, 0));
+  const size_t n_tiles = (size_t)((count + EV_TILE - 1) / EV_TILE);
+  const size_t rec_words = EVENT_REC_WORDS + 4u * (size_t)n_mask_words, rec_bytes = rec_words * 4;
+  int rc = ensure(ctx, ctx->evs_scr, (n_tiles + 4) * 4 + (size_t)count + 64, false);
+  if (rc) return rc;
+  // staging: what the previous calls needed (the buffer only grows), never the worst case n_roots * n_prefixes up front
+  // (the SMALLER of the last two totals: one cold start between LSP changes does not make the next call copy megabytes for a
+  // handful of events, and a caller whose streams are large call after call still gets them in one copy)
+  const uint64_t hint = std::min(ctx->ev_hint, ctx->ev_hint2);
+  const uint64_t predicted = std::min<uint64_t>(count, std::max<uint64_t>(1024u, hint + hint / 4u));
+  if ((rc = ensure(ctx, ctx->evs_rec, (size_t)predicted * rec_bytes, false))) return rc;
+  const uint32_t clip = (uint32_t)std::min<uint64_t>(count, ctx->evs_rec.cap / rec_bytes);
+  uint32_t *tile_off = ev_tile_off(ctx);
+  hipLaunchKernelGGL(k_events_classify, dim3((unsigned)n_tiles), dim3(256), 0, s, (size_t)count, n_mask_words, e.with_silent,
+                     (const uint32_t *)old_dev->best_metric, (const uint32_t *)old_dev->best_entry, (const uint64_t *)old_dev->nexthop_mask,
+                     (const uint32_t *)new_dev->best_metric, (const uint32_t *)new_dev->best_entry, (const uint64_t *)new_dev->nexthop_mask,
+                     ev_action(ctx, n_tiles), tile_off);
+  hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(1024), 0, s, (uint32_t)n_tiles, tile_off, tile_off + n_tiles, d_hev);
+  events_launch_write(ctx, clip);
+  HIPCHK(ctx, hipGetLastError());
+  // THE copy, sized before the total is known: as many records as the previous call produced (+ 1/4), within what the
+  // caller takes and the staging holds.  The total itself arrives in the pinned word k_events_scan stored.
+  const uint32_t first_copy = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(capacity, clip), predicted);
+  if (first_copy && (rc = copy_to_host(ctx, records_host, ctx->evs_rec.p, (size_t)first_copy * rec_bytes, s))) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(s));                        // THE synchronisation
+  const uint32_t total = ctx->h_ev[0];
+  e.total = total; e.staged = std::min(total, clip);
+  ctx->ev_hint2 = ctx->ev_hint; ctx->ev_hint = total;
+  *n_records = total;
+  const uint32_t n_out = std::min(total, capacity);
+  if (n_out > first_copy) {                                    // the prediction fell short: the tail (after a grow + rewrite when the write pass was clipped)
+    if ((rc = events_stage(ctx, n_out))) return rc;
+    if ((rc = copy_to_host(ctx, records_host + (size_t)first_copy * rec_words, (const char *)ctx->evs_rec.p + (size_t)first_copy * rec_bytes,
+                           (size_t)(n_out - first_copy) * rec_bytes, s))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+  }
+  e.valid = true;                                              // (last: a call that failed on the way leaves no stream behind)
+  return HSPF_OK;
+}
+
+int hspf_routes_events(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint32_t n_mask_words,
+                       const hspf_routes *old_dev, const hspf_routes *new_dev, uint32_t flags,
+                       uint32_t capacity_records, uint32_t *records_host, uint32_t *n_records) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int { return routes_events_impl(ctx, n_roots, n_prefixes, n_mask_words, old_dev, new_dev, flags, capacity_records, records_host, n_records); });
+}
+
+int hspf_routes_events_rest(hspf_ctx *ctx, uint32_t first, uint32_t count, uint32_t *records_host) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const hspf_ctx::EvState &e = ctx->evs;
+    if (!e.valid) { ctx->last_error = "hspf_routes_events_rest: no hspf_routes_events stream on this context"; return HSPF_E_INVAL; }
+    if ((uint64_t)first + count > e.total) { ctx->last_error = "hspf_routes_events_rest: range beyond the stream's n_records"; return HSPF_E_INVAL; }
+    if (count == 0) return HSPF_OK;
+    if (!records_host) { ctx->last_error = "hspf_routes_events_rest: records_host is NULL"; return HSPF_E_INVAL; }
+    (void)hipSetDevice(ctx->device);
+    int rc = events_stage(ctx, first + count);
+    if (rc) return rc;
+    const size_t rec_bytes = (size_t)(EVENT_REC_WORDS + 4u * e.W) * 4;
+    if ((rc = copy_to_host(ctx, records_host, (const char *)ctx->evs_rec.p + (size_t)first * rec_bytes, (size_t)count * rec_bytes, ctx->stream))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return HSPF_OK;
   });
 }

@@ -3430,14 +3430,12 @@ __global__ __launch_bounds__(256) void k_rib_clear(uint32_t n_pfx, uint32_t rib_
 
 // RIB diff: update_global_rib's comparison (holo-isis/src/route.rs:254-312) on two result sets of
 // k_routes.  One thread per (root, prefix); HBM bound: 2 x (8 + 8W) bytes read, 1 + 1 written per pair.
-__global__ __launch_bounds__(256) void k_routes_diff(size_t count, uint32_t W,
-                                                     const uint32_t *__restrict__ om, const uint32_t *__restrict__ oe,
-                                                     const uint64_t *__restrict__ on,
-                                                     const uint32_t *__restrict__ nm, const uint32_t *__restrict__ ne,
-                                                     const uint64_t *__restrict__ nn,
-                                                     uint8_t *__restrict__ action, uint8_t *__restrict__ flag) {
-  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= count) return;
+// The action of one pair: the rule of include/holo_spf_hip.h (HSPF_DIFF_*), stated ONCE for k_routes_diff and the event stream.
+__device__ __forceinline__ uint32_t route_action(size_t i, uint32_t W,
+                                                 const uint32_t *__restrict__ om, const uint32_t *__restrict__ oe,
+                                                 const uint64_t *__restrict__ on,
+                                                 const uint32_t *__restrict__ nm, const uint32_t *__restrict__ ne,
+                                                 const uint64_t *__restrict__ nn) {
   const bool had = oe[i] != INF, has = ne[i] != INF;
   bool same_nh = true, old_nh = false, new_nh = false;
   for (uint32_t w = 0; w < W; ++w) {
@@ -3446,9 +3444,19 @@ __global__ __launch_bounds__(256) void k_routes_diff(size_t count, uint32_t W,
     old_nh = old_nh || a != 0ull;
     new_nh = new_nh || b != 0ull;
   }
-  uint32_t act;
-  if (has) act = (had && om[i] == nm[i] && same_nh) ? HSPF_DIFF_SAME : (new_nh ? HSPF_DIFF_INSTALL : HSPF_DIFF_SILENT);
-  else act = had ? (old_nh ? HSPF_DIFF_WITHDRAW : HSPF_DIFF_SILENT) : HSPF_DIFF_SAME;
+  if (has) return (had && om[i] == nm[i] && same_nh) ? HSPF_DIFF_SAME : (new_nh ? HSPF_DIFF_INSTALL : HSPF_DIFF_SILENT);
+  return had ? (old_nh ? HSPF_DIFF_WITHDRAW : HSPF_DIFF_SILENT) : HSPF_DIFF_SAME;
+}
+
+__global__ __launch_bounds__(256) void k_routes_diff(size_t count, uint32_t W,
+                                                     const uint32_t *__restrict__ om, const uint32_t *__restrict__ oe,
+                                                     const uint64_t *__restrict__ on,
+                                                     const uint32_t *__restrict__ nm, const uint32_t *__restrict__ ne,
+                                                     const uint64_t *__restrict__ nn,
+                                                     uint8_t *__restrict__ action, uint8_t *__restrict__ flag) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t act = route_action(i, W, om, oe, on, nm, ne, nn);
   action[i] = (uint8_t)act;
   flag[i] = (act == HSPF_DIFF_INSTALL || act == HSPF_DIFF_WITHDRAW) ? 1 : 0;
 }
@@ -3489,6 +3497,124 @@ __global__ __launch_bounds__(256) void k_routes_pack(uint32_t n_records, uint32_
   for (uint32_t w = 0; w < W; ++w) {
     const uint64_t m = nexthop_mask[i * W + w];
     o[ROUTE_REC_WORDS + 2u * w] = (uint32_t)m; o[ROUTE_REC_WORDS + 2u * w + 1u] = (uint32_t)(m >> 32);
+  }
+}
+
+// The route event stream (include/holo_spf_hip.h hspf_routes_events): every pair whose action is not SAME (SILENT pairs on
+// request) as ONE stream of paired old -> new records in global pair order, EVENT_REC_WORDS + 4 W u32 words each:
+// [root, prefix, action, new metric, new entry, old metric, old entry, 0 | new mask (2W words) | old mask (2W words)].
+// The order is the pair index, so a record's place is a rank, and ranks come from a scan — no global atomic anywhere:
+//   k_events_classify   a tile of EV_TILE = 1024 pairs per workgroup, wave w the four 64-pair segments 4w .. 4w+3 (lane =
+//                       pair inside the segment: dword / qword loads of consecutive pairs); action byte per pair, events
+//                       counted per segment with __ballot, ONE total per tile.
+//                       HBM bound: 2 x (8 + 8W) bytes read, 1 written per pair (+ 4 per 1024 pairs).
+//   k_events_scan       one workgroup: exclusive scan over the tile totals in place (carry across chunks of 1024), the
+//                       total into device memory and straight into a pinned host word.
+//   k_events_write      same tiling; a segment's events are consecutive in the stream, from tile offset + the counts of the
+//                       segments before it; rank inside the segment = mbcnt of the ballot.  The wave then writes the
+//                       segment's records as contiguous dwords (lane = WORD of the stream, not lane = record: the stores
+//                       of a wave cover 256 consecutive bytes), each lane fetching the one table word its stream word is —
+//                       also for the mask words at W > 1, read as dwords of the qword tables.  Records at or beyond `clip`
+//                       (the staging's capacity) are not written.
+//                       1 byte read per pair; per EVENT 2 x (8 + 8W) read, 32 + 16W written.
+constexpr uint32_t EVENT_REC_WORDS = 8u;
+constexpr uint32_t EV_TILE = 1024u;
+__device__ __forceinline__ bool event_selected(uint32_t act, uint32_t with_silent) {
+  return act == HSPF_DIFF_INSTALL || act == HSPF_DIFF_WITHDRAW || (with_silent && act == HSPF_DIFF_SILENT);
+}
+
+__global__ __launch_bounds__(256) void k_events_classify(size_t count, uint32_t W, uint32_t with_silent,
+                                                         const uint32_t *__restrict__ om, const uint32_t *__restrict__ oe,
+                                                         const uint64_t *__restrict__ on,
+                                                         const uint32_t *__restrict__ nm, const uint32_t *__restrict__ ne,
+                                                         const uint64_t *__restrict__ nn,
+                                                         uint8_t *__restrict__ action, uint32_t *__restrict__ tile_total) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const size_t base = (size_t)blockIdx.x * EV_TILE + (size_t)wave * 256u + lane;
+  uint32_t cnt = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < 4u; ++q) {
+    const size_t i = base + q * 64u;
+    uint32_t act = HSPF_DIFF_SAME;
+    if (i < count) { act = route_action(i, W, om, oe, on, nm, ne, nn); action[i] = (uint8_t)act; }
+    cnt += (uint32_t)__popcll(__ballot(event_selected(act, with_silent)));
+  }
+  if (lane == 0) s_w[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_total[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ __launch_bounds__(1024) void k_events_scan(uint32_t n_tiles, uint32_t *__restrict__ tile_total,
+                                                      uint32_t *__restrict__ total_dev, uint32_t *__restrict__ total_host) {
+  __shared__ uint32_t s_wave[16];
+  __shared__ uint32_t s_carry;
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  if (t == 0) s_carry = 0;
+  __syncthreads();
+  for (uint32_t b0 = 0; b0 < n_tiles; b0 += 1024u) {
+    const uint32_t idx = b0 + t;
+    const uint32_t v = idx < n_tiles ? tile_total[idx] : 0u;
+    uint32_t inc = v;                                            // inclusive scan inside the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
+    if (lane == 63u) s_wave[wave] = inc;
+    __syncthreads();
+    uint32_t before = s_carry;
+    for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
+    if (idx < n_tiles) tile_total[idx] = before + inc - v;
+    __syncthreads();
+    if (t == 1023u) s_carry = before + inc;
+    __syncthreads();
+  }
+  if (t == 0) { *total_dev = s_carry; *total_host = s_carry; }
+}
+
+__global__ __launch_bounds__(256) void k_events_write(size_t count, uint32_t n_pfx, uint32_t W, uint32_t with_silent, uint32_t clip,
+                                                      const uint8_t *__restrict__ action, const uint32_t *__restrict__ tile_off,
+                                                      const uint32_t *__restrict__ om, const uint32_t *__restrict__ oe,
+                                                      const uint32_t *__restrict__ on32,
+                                                      const uint32_t *__restrict__ nm, const uint32_t *__restrict__ ne,
+                                                      const uint32_t *__restrict__ nn32,
+                                                      uint32_t *__restrict__ rec) {
+  __shared__ uint32_t s_cnt[16];
+  __shared__ uint8_t s_lane[16][64];                            // [segment][rank] -> lane (pair inside the segment) of the rank-th event
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const size_t tile0 = (size_t)blockIdx.x * EV_TILE;
+  uint64_t bal[4];
+#pragma unroll
+  for (uint32_t q = 0; q < 4u; ++q) {
+    const uint32_t seg = wave * 4u + q;
+    const size_t i = tile0 + seg * 64u + lane;
+    const bool ev = i < count && event_selected(action[i], with_silent);
+    bal[q] = __ballot(ev);
+    if (ev) s_lane[seg][__builtin_amdgcn_mbcnt_hi((uint32_t)(bal[q] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[q], 0u))] = (uint8_t)lane;
+    if (lane == 0) s_cnt[seg] = (uint32_t)__popcll(bal[q]);
+  }
+  __syncthreads();
+  uint32_t first = tile_off[blockIdx.x];
+  for (uint32_t sg = 0; sg < wave * 4u; ++sg) first += s_cnt[sg];
+  const uint32_t RW = EVENT_REC_WORDS + 4u * W, W2 = 2u * W;
+  for (uint32_t q = 0; q < 4u; ++q) {
+    const uint32_t seg = wave * 4u + q;
+    const uint32_t nev = (uint32_t)__popcll(bal[q]);           // (wave-uniform)
+    const uint32_t words = nev * RW;
+    for (uint32_t j = lane; j < words; j += 64u) {
+      const uint32_t k = j / RW, wd = j - k * RW;
+      const uint32_t gk = first + k;
+      if (gk >= clip) continue;
+      const size_t i = tile0 + seg * 64u + s_lane[seg][k];
+      uint32_t v;
+      if (wd < 3u) v = wd == 0u ? (uint32_t)(i / n_pfx) : wd == 1u ? (uint32_t)(i % n_pfx) : (uint32_t)action[i];
+      else if (wd == 7u) v = 0u;
+      else {
+        const uint32_t *src = wd == 3u ? nm + i : wd == 4u ? ne + i : wd == 5u ? om + i : wd == 6u ? oe + i :
+                              wd < EVENT_REC_WORDS + W2 ? nn32 + i * W2 + (wd - EVENT_REC_WORDS) : on32 + i * W2 + (wd - EVENT_REC_WORDS - W2);
+        v = *src;
+      }
+      rec[(size_t)gk * RW + wd] = v;
+    }
+    first += nev;
   }
 }
 

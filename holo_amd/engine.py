@@ -31,6 +31,8 @@ PFX_ORDERED = 0x4
 PFX_RESIDENT = 0x8        # the three main arrays are what the previous routes_device call on this context passed
 PFX_ENTRY_NETWORK = 0x80000000
 PFX_KEPT_INIT = 0xFFFFFFFE
+EV_SILENT = 0x1           # hspf_routes_events: SILENT pairs are part of the stream
+EVENT_REC_WORDS = 8       # HSPF_EVENT_REC_WORDS
 DIFF_SAME, DIFF_INSTALL, DIFF_WITHDRAW, DIFF_SILENT = 0, 1, 2, 3
 
 RF_IN_SPT = 0x0001
@@ -330,6 +332,7 @@ class SpfContext:
     """One engine context: device, HIP stream, scratch (hspf_ctx).  One thread at a time."""
 
     def __init__(self, device: int = 0):
+        self._events_hint = 0        # records the previous routes_events() produced
         self.lib = L.load()
         h = ctypes.c_void_p()
         rc = self.lib.hspf_init(device, ctypes.byref(h))
@@ -574,6 +577,34 @@ class SpfContext:
             if rc != 0:
                 raise HspfError(rc, "hspf_routes_pack", self.last_error())
         return rec
+
+    def routes_events(self, n_roots: int, n_prefixes: int, mask_words: int, old: tuple, new: tuple, *, with_silent: bool = True,
+                      capacity: int | None = None) -> np.ndarray:
+        """hspf_routes_events(): every (root, prefix) pair of two hspf_routes_device() result sets whose action is not SAME
+        (SILENT pairs with `with_silent`) as ONE stream of paired old -> new records, one device call.  old / new as for
+        routes_diff_device().  Returns [n_records, 8 + 4 W] u32: root, prefix, action, new metric, new entry, old metric,
+        old entry, 0, new mask words, old mask words.  `capacity`: records taken by the first call (default: what the
+        previous call on this context produced, at least 1024); whatever the stream holds beyond it is fetched with
+        hspf_routes_events_rest(), so the result is always the whole stream."""
+        o, n = L.HspfRoutes(*old), L.HspfRoutes(*new)
+        rw = EVENT_REC_WORDS + 4 * mask_words
+        cap = max(1024, self._events_hint + self._events_hint // 4) if capacity is None else int(capacity)
+        rec = np.zeros((cap, rw), np.uint32)
+        total = ctypes.c_uint32(0)
+        rc = self.lib.hspf_routes_events(self.handle, n_roots, n_prefixes, mask_words, ctypes.byref(o), ctypes.byref(n),
+                                         EV_SILENT if with_silent else 0, cap, _u32(rec) if cap else None, ctypes.byref(total))
+        if rc != 0:
+            raise HspfError(rc, "hspf_routes_events", self.last_error())
+        k = int(total.value)
+        self._events_hint = k
+        if k <= cap:
+            return rec[:k]
+        full = np.zeros((k, rw), np.uint32)
+        full[:cap] = rec
+        rc = self.lib.hspf_routes_events_rest(self.handle, cap, k - cap, _u32(full[cap:]))
+        if rc != 0:
+            raise HspfError(rc, "hspf_routes_events_rest", self.last_error())
+        return full
 
     def close(self):
         if self.handle:

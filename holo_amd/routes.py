@@ -211,6 +211,48 @@ def expand_route_records(records: np.ndarray, prefixes: Sequence[str], slot_nh: 
     return adds + dels
 
 
+def apply_route_events(tables, records: np.ndarray):
+    """The meaning of the hspf_routes_events stream: patch host copies of two-dimensional route tables with it, in place.
+    tables = (best_metric [R, P] u32, best_entry [R, P] u32, nexthop_mask [R, P, W] u64) as hspf_routes_device wrote them
+    for the OLD set; records = [n, 8 + 4 W] u32.  Every record overwrites its (root, prefix) row with its NEW half — a SILENT
+    record like any other: it is a change of the table that no message announces.  With a stream taken with HSPF_EV_SILENT
+    the tables ARE the new set afterwards; a record whose OLD half is not what the tables hold is a stream for other tables
+    (ValueError).  Returns the tables."""
+    bm, be, nm = tables
+    records = np.asarray(records, np.uint32)
+    if records.size == 0:
+        return tables
+    W = nm.shape[2]
+    if records.ndim != 2 or records.shape[1] != E.EVENT_REC_WORDS + 4 * W:
+        raise ValueError(f"records of {records.shape[1:]} words for tables of {W} mask words")
+    r, p = records[:, 0].astype(np.int64), records[:, 1].astype(np.int64)
+    if (r >= bm.shape[0]).any() or (p >= bm.shape[1]).any():
+        raise ValueError("record outside the tables")
+    h = E.EVENT_REC_WORDS
+    halves = np.ascontiguousarray(records[:, h:]).view(np.uint64).reshape(len(records), 2, W)     # (low half first: little endian)
+    if not (np.array_equal(bm[r, p], records[:, 5]) and np.array_equal(be[r, p], records[:, 6]) and np.array_equal(nm[r, p], halves[:, 1])):
+        raise ValueError("the old half of a record is not what the tables hold")
+    bm[r, p] = records[:, 3]
+    be[r, p] = records[:, 4]
+    nm[r, p] = halves[:, 0]
+    return tables
+
+
+def events_as_pack_records(records: np.ndarray, old_half: bool = False) -> np.ndarray:
+    """The INSTALL / WITHDRAW records of an hspf_routes_events stream in the layout of hspf_routes_pack ([n, 6 + 2 W]: root,
+    prefix, action, metric, entry, 0, mask words) — the new half, or the old one — so that expand_route_records and every
+    other consumer of the pack stream takes them as they are."""
+    records = np.asarray(records, np.uint32)
+    h = E.EVENT_REC_WORDS
+    W2 = (records.shape[1] - h) // 2
+    keep = records[(records[:, 2] == E.DIFF_INSTALL) | (records[:, 2] == E.DIFF_WITHDRAW)]
+    out = np.zeros((len(keep), 6 + W2), np.uint32)
+    out[:, :3] = keep[:, :3]
+    out[:, 3:5] = keep[:, 5:7] if old_half else keep[:, 3:5]
+    out[:, 6:] = keep[:, h + W2:] if old_half else keep[:, h:h + W2]
+    return out
+
+
 def update_global_rib_device(instance: I.Instance, engine, rib_before: List[dict], ifindex: Dict[str, int], device="cuda:0"):
     """compute_spf + update_global_rib with the SPT, the prefix attachment, the comparison with the previous RIB and the
     compaction of what changed ALL on the device; one record stream comes back (hspf_routes_pack).  For instances with

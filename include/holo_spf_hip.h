@@ -579,6 +579,50 @@ int hspf_routes_pack(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint3
                      const uint8_t *action_dev, const uint32_t *changed_dev, const uint32_t *changed_ptr_dev,
                      uint32_t n_records, uint32_t *records_host);
 
+/* ---- the route event stream: old -> new pairs, SILENT changes included, one device call (same ABI: a new symbol) -------
+ * hspf_routes_diff_device + hspf_routes_pack hand over the pairs that need a MESSAGE.  A caller that keeps its own RIB
+ * needs more: what every changed route WAS (to withdraw or replace it) and the changes that put nothing on the wire
+ * (HSPF_DIFF_SILENT: a route that turns into one without next hops, or one that had none and vanishes).
+ * hspf_routes_events compares two table sets of hspf_routes_device (same PRECONDITION as hspf_routes_diff_device, same
+ * action rule — one device function computes both) and brings every pair whose action is not HSPF_DIFF_SAME to the host as
+ * ONE stream of paired records.  Record k, HSPF_EVENT_REC_WORDS + 4 * n_mask_words u32 words:
+ *     [0] root index   [1] prefix index   [2] action (HSPF_DIFF_INSTALL | HSPF_DIFF_WITHDRAW | HSPF_DIFF_SILENT)
+ *     [3] NEW best_metric   [4] NEW best_entry (0xFFFFFFFF: no route now)
+ *     [5] OLD best_metric   [6] OLD best_entry (0xFFFFFFFF: no route before)   [7] 0
+ *     [8 ..)                       NEW nexthop_mask words, low half first (2 * n_mask_words words)
+ *     [8 + 2 * n_mask_words ..)    OLD nexthop_mask words, low half first
+ * roots ascending, prefixes ascending inside a root (the reference's emission order).  Applying the new half of every
+ * record of a HSPF_EV_SILENT stream to a copy of the old tables gives the new tables (holo_amd.routes.apply_route_events).
+ *   flags            HSPF_EV_SILENT: SILENT pairs are part of the stream; without it INSTALL / WITHDRAW pairs only.
+ *   *n_records       always the TOTAL number of events.  min(total, capacity_records) records are written to records_host
+ *                    (what lies behind them in records_host is unspecified); a total above the capacity is not an error:
+ *                    hspf_routes_events_rest(first, count) copies any range [first, first + count) of the same stream — no
+ *                    second comparison, no lost event — until the next route call on the context (hspf_routes_device,
+ *                    hspf_rib_fold_device, hspf_routes_diff_device, hspf_routes_pack, hspf_routes_events: each voids the
+ *                    stream, a later _rest is HSPF_E_INVAL) and as long as neither table set was written to (a tail the
+ *                    staging did not hold is written from the tables).  A range beyond the total is HSPF_E_INVAL.
+ *                    capacity_records == 0 with records_host == NULL asks for the count alone.
+ * Cost and staging policy: three kernels (classify + count per 1024-pair tile, one scan over the tile totals, the write
+ * pass) and, in the steady state, ONE synchronisation and ONE device-to-host copy: the total comes back in a pinned word
+ * the scan kernel stores itself, and the copy is issued BEFORE the total is known, for as many records as the SMALLER of the
+ * last two calls on this context produced plus a quarter (at least 1024), within capacity_records — the smaller, so that the
+ * call after one cold start does not copy megabytes for a handful of events, while streams that are large call after call
+ * still arrive in one copy.  The device staging is sized the same
+ * way — from what earlier calls needed, never for n_roots * n_prefixes records — and only grows; the write pass clips at its
+ * capacity.  A call that produces more than predicted pays for it once: the staging grows to the whole stream, the write
+ * pass alone runs again (the action bytes and ranks are kept), and a second copy fetches the tail.
+ * The ONE synchronisation / ONE copy holds for a PAGE-LOCKED records_host (hspf_host_alloc): pageable memory is filled
+ * through the context's two page-locked staging blocks, one event wait per 8 MB block, at the speed of a host memcpy.  The
+ * early copy always moves the predicted number of records (48 KB at least with one mask word), also when fewer events exist:
+ * what lies in records_host behind the stream is stale staging content.  n_mask_words is at most 2^20.
+ * All table pointers are DEVICE pointers; argument errors are HSPF_E_INVAL with a text in hspf_last_error. */
+#define HSPF_EV_SILENT       0x1u
+#define HSPF_EVENT_REC_WORDS 8u
+int hspf_routes_events(hspf_ctx *ctx, uint32_t n_roots, uint32_t n_prefixes, uint32_t n_mask_words,
+                       const hspf_routes *old_dev, const hspf_routes *new_dev, uint32_t flags,
+                       uint32_t capacity_records, uint32_t *records_host, uint32_t *n_records);
+int hspf_routes_events_rest(hspf_ctx *ctx, uint32_t first, uint32_t count, uint32_t *records_host);
+
 /* ---- ancestor sets on device (the queries of flooding::manet::reflood_list) ------------------------
  * For every root of a previous hspf_run_device() and a level L (1 = first hops / remote-neighbour list, 2 = second
  * hops): the root's level-L routers = router vertices of its SPT with hops == L, numbered in ascending vertex index

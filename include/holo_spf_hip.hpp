@@ -214,6 +214,23 @@ class Engine {
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_wait (") + hspf_last_error(ctx_) + ")");
     return st;
   }
+  // The route event stream (hspf_routes_events): every (root, prefix) pair of two DEVICE table sets whose action is not
+  // SAME, SILENT pairs included when asked for, as paired old -> new records of HSPF_EVENT_REC_WORDS + 4 * n_mask_words words.
+  // `records` is resized to the whole stream (a stream longer than its capacity on entry is completed with
+  // hspf_routes_events_rest); pass the same vector again and the steady state is one device call.
+  uint32_t routes_events(uint32_t n_roots, uint32_t n_prefixes, uint32_t n_mask_words, const hspf_routes &old_dev, const hspf_routes &new_dev,
+                         bool with_silent, std::vector<uint32_t> &records) {
+    const size_t stride = HSPF_EVENT_REC_WORDS + 4u * (size_t)n_mask_words;
+    if (records.size() < 1024u * stride) records.resize(1024u * stride);
+    const uint32_t cap = (uint32_t)std::min<size_t>(records.size() / stride, 0xFFFFFFFFu);
+    uint32_t total = 0;
+    int rc = hspf_routes_events(ctx_, n_roots, n_prefixes, n_mask_words, &old_dev, &new_dev, with_silent ? HSPF_EV_SILENT : 0u, cap, records.data(), &total);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_events (") + hspf_last_error(ctx_) + ")");
+    records.resize((size_t)total * stride);
+    if (total > cap && (rc = hspf_routes_events_rest(ctx_, cap, total - cap, records.data() + (size_t)cap * stride)) != HSPF_OK)
+      throw Error(rc, std::string("hspf_routes_events_rest (") + hspf_last_error(ctx_) + ")");
+    return total;
+  }
   void wait_all() { (void)hspf_wait_all(ctx_); }
   uint32_t async_lanes() const { return hspf_async_lanes(ctx_); }
   // true: these runs are too small to pay for a launch — the caller keeps its own CPU loop (hspf_recommend_cpu)

@@ -6,6 +6,7 @@
 #include <array>
 #include <chrono>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -74,6 +75,28 @@ struct RouteRecords {
   size_t count() const { return words.size() / stride(); }
   const uint32_t *rec(size_t k) const { return words.data() + k * stride(); }
 };
+// The event stream of hspf_routes_events: every pair that is not SAME as ONE record with the new and the old half of the
+// route (HSPF_EVENT_REC_WORDS + 4 * mask_words words).  supported == false: the engine has no such call (the caller keeps
+// routes_changed).  `data` points into a buffer the engine keeps: valid until its next routes_events.
+struct RouteEvents {
+  bool supported = false;
+  uint32_t mask_words = 1;
+  size_t n = 0;
+  const uint32_t *data = nullptr;
+  std::vector<uint32_t> own;           // (engines without a kept buffer put the stream here and point `data` at it)
+  size_t stride() const { return HSPF_EVENT_REC_WORDS + 4u * mask_words; }
+  size_t count() const { return n; }
+  const uint32_t *rec(size_t k) const { return (own.empty() ? data : own.data()) + k * stride(); }
+  uint32_t root(size_t k) const { return rec(k)[0]; }
+  uint32_t prefix(size_t k) const { return rec(k)[1]; }
+  uint32_t action(size_t k) const { return rec(k)[2]; }
+  uint32_t new_metric(size_t k) const { return rec(k)[3]; }
+  uint32_t new_entry(size_t k) const { return rec(k)[4]; }
+  uint32_t old_metric(size_t k) const { return rec(k)[5]; }
+  uint32_t old_entry(size_t k) const { return rec(k)[6]; }
+  const uint32_t *new_mask(size_t k) const { return rec(k) + HSPF_EVENT_REC_WORDS; }                       // 2 * mask_words words, low half first
+  const uint32_t *old_mask(size_t k) const { return rec(k) + HSPF_EVENT_REC_WORDS + 2u * mask_words; }
+};
 class Engine {
  public:
   virtual ~Engine() = default;
@@ -105,6 +128,9 @@ class Engine {
                                                       const std::vector<uint32_t> &pfx_metric, uint32_t flags) = 0;
   virtual std::unique_ptr<DeviceRoutes> routes_upload(const RoutesOut &t, uint32_t n_roots, uint32_t n_prefixes, uint32_t mask_words) = 0;
   virtual RouteRecords routes_changed(DeviceRoutes &old_set, DeviceRoutes &new_set) = 0;
+  // routes_changed with the old half in the same record and, with_silent, the HSPF_DIFF_SILENT pairs too: one device call.
+  // The default: not supported (RouteEvents::supported == false) — the caller uses routes_changed.
+  virtual RouteEvents routes_events(DeviceRoutes &, DeviceRoutes &, bool /*with_silent*/) { return RouteEvents{}; }
   // Several areas, ONE RIB (hspf_rib_clear_device / hspf_rib_fold_device): an empty instance-wide state over `n_prefixes`
   // prefixes and `mask_words` words of instance-wide first-hop slots, and the ordered fold (HSPF_PFX_ORDERED rules) of one
   // area's table into it — `prefix_map`: area prefix -> instance prefix, the area's slots start at word `word_offset`.
@@ -383,7 +409,7 @@ class HipEngine : public Engine {
     const int rc = hspf_init(device, &ctx_);
     if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_init: ") + hspf_strerror(rc));   // no CPU fallback
   }
-  ~HipEngine() override { if (diff_) (void)hipFree(diff_); if (pin_) hspf_host_free(ctx_, pin_); if (ctx_) hspf_shutdown(ctx_); }
+  ~HipEngine() override { if (diff_) (void)hipFree(diff_); if (ev_pin_) hspf_host_free(ctx_, ev_pin_); if (pin_) hspf_host_free(ctx_, pin_); if (ctx_) hspf_shutdown(ctx_); }
   hspf_ctx *raw() const { return ctx_; }
   std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                 const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
@@ -603,7 +629,38 @@ class HipEngine : public Engine {
     }
     return out;
   }
+  RouteEvents routes_events(DeviceRoutes &old_set, DeviceRoutes &new_set, bool with_silent) override {
+    auto &a = static_cast<HipDeviceRoutes &>(old_set);
+    auto &b = static_cast<HipDeviceRoutes &>(new_set);
+    if (a.n_roots != b.n_roots || a.n_prefixes != b.n_prefixes || a.mask_words != b.mask_words) throw std::runtime_error("routes_events: the two sets differ in shape");
+    RouteEvents out;
+    out.supported = true;
+    out.mask_words = b.mask_words;
+    if ((size_t)b.n_roots * b.n_prefixes == 0) return out;
+    const size_t stride = out.stride();
+    auto grow = [&](size_t records) {                                // the page-locked record buffer: kept, grown on demand (contents carried over)
+      void *p = nullptr;
+      if (hspf_host_alloc(ctx_, records * stride * 4, &p) != HSPF_OK) throw std::runtime_error(std::string("hspf_host_alloc: ") + hspf_last_error(ctx_));
+      if (ev_pin_) { memcpy(p, ev_pin_, std::min(ev_pin_bytes_, records * stride * 4)); hspf_host_free(ctx_, ev_pin_); }
+      ev_pin_ = (uint32_t *)p; ev_pin_bytes_ = records * stride * 4;
+    };
+    if (ev_pin_bytes_ < 1024 * stride * 4) grow(1024);
+    const uint32_t cap = (uint32_t)std::min<size_t>(ev_pin_bytes_ / (stride * 4), 0xFFFFFFFFu);
+    hspf_routes ro = a.raw(), rn = b.raw();
+    uint32_t total = 0;
+    int rc = hspf_routes_events(ctx_, b.n_roots, b.n_prefixes, b.mask_words, &ro, &rn, with_silent ? HSPF_EV_SILENT : 0u, cap, ev_pin_, &total);
+    if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_routes_events: ") + hspf_last_error(ctx_));
+    if (total > cap) {
+      grow((size_t)total + total / 4);
+      rc = hspf_routes_events_rest(ctx_, cap, total - cap, ev_pin_ + (size_t)cap * stride);
+      if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_routes_events_rest: ") + hspf_last_error(ctx_));
+    }
+    out.n = total; out.data = ev_pin_;
+    return out;
+  }
  private:
+  uint32_t *ev_pin_ = nullptr;         // page-locked record buffer of routes_events
+  size_t ev_pin_bytes_ = 0;
   void *diff_ = nullptr;
   size_t diff_cap_ = 0;
   template <typename WT>

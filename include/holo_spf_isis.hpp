@@ -1505,6 +1505,10 @@ inline std::vector<IbusMsg> update_global_rib_device(const Instance &inst, Engin
 // installed is read off the previous tables at that moment (settle_installed: rows with resolved next hops), not kept from
 // the messages: a route that loses its next hops changes the RIB without a message (route.rs:283-301; HSPF_DIFF_SILENT, no
 // record) and a set kept from messages would go stale — the random chains of tests/test_cpp_driver.py found exactly that.
+// With an engine that has the route event stream (Engine::routes_events -> hspf_routes_events) none of that is needed: ONE call
+// brings every pair that is not SAME, the old and the new half of the route in one record, SILENT pairs included; the messages come
+// from its INSTALL / WITHDRAW records through the same code, and every event is applied to `rib_`, which is then the instance's whole
+// RIB after every step (full_rib(); rib() stays the installed view) — settle_installed() only drops the tables.
 // step() = trigger_lsps -> messages.  One (level, topology), local root; interfaces / adjacencies as at
 // construction (an adjacency change is a new pipeline).
 class RibPipeline {
@@ -1540,6 +1544,7 @@ class RibPipeline {
       std::vector<IbusMsg> msgs;
       for (auto &kv : rib_) if (!kv.second.nexthops.empty()) msgs.push_back(IbusMsg{false, kv.second.prefix, 0, {}});
       rib_.clear();
+      rib_current_ = true;                                            // (the empty RIB: current whatever the engine can do)
       return msgs;
     }
     t = C::now();
@@ -1581,9 +1586,27 @@ class RibPipeline {
       prev_ = engine_.routes_upload(old, 1, P, W);
       last.full = true;
     }
-    const RouteRecords rec = engine_.routes_changed(*prev_, *fresh);
-    last.diff_pack_ms = ms(t); t = C::now();
-    last.records = rec.count();
+    // An engine with the event stream (hspf_routes_events) hands over EVERY pair that is not SAME in one call, the old and the new
+    // half of the route in one record, SILENT pairs included: the INSTALL / WITHDRAW subset is what routes_changed gives (same
+    // records, same order: the messages below come from the same code), and the whole stream keeps `rib_` current further down.
+    const RouteEvents ev = engine_.routes_events(*prev_, *fresh, true);
+    RouteRecords rec;
+    if (ev.supported) {
+      last.diff_pack_ms = ms(t); t = C::now();
+      rec.mask_words = W;
+      for (size_t k = 0; k < ev.count(); ++k) {
+        const uint32_t *e = ev.rec(k);
+        if (e[2] != HSPF_DIFF_INSTALL && e[2] != HSPF_DIFF_WITHDRAW) continue;
+        rec.words.insert(rec.words.end(), {e[0], e[1], e[2], e[3], e[4], 0u});
+        rec.words.insert(rec.words.end(), ev.new_mask(k), ev.new_mask(k) + 2 * W);
+        rec.old_words.insert(rec.old_words.end(), {e[0], e[1], e[2], e[5], e[6], 0u});
+        rec.old_words.insert(rec.old_words.end(), ev.old_mask(k), ev.old_mask(k) + 2 * W);
+      }
+    } else {
+      rec = engine_.routes_changed(*prev_, *fresh);
+      last.diff_pack_ms = ms(t); t = C::now();
+    }
+    last.records = ev.supported ? ev.count() : rec.count();
     // the route each record REPLACES: from the host's view after a reset, else from the old set's own record (metric + slot
     // masks resolved like the new ones: equal resolved next hops = the reference's "unchanged", route.rs:268-277)
     std::vector<RibRow> old_store;
@@ -1628,8 +1651,27 @@ class RibPipeline {
         for (size_t i = 0; i < dels.size(); ++i) *(first_del + i) = std::move(dels[i].second);
       }
     }
-    rib_.clear();                                                     // (void from here on: settle_installed() reads it off `prev_` when it is needed)
     max_paths_ = cfg.max_paths;
+    if (ev.supported) {
+      // every event applied: `rib_` IS the instance's RIB after this step (prefix, metric, level, resolved next hops with max-paths
+      // applied; a route without next hops is a row with none) — a SILENT record like any other, it only sent no message
+      if (host_old)
+        for (auto it = rib_.begin(); it != rib_.end();) it = table_.find(it->first) < 0 ? rib_.erase(it) : std::next(it);
+      const SlotTableRes res = resolve_slots(W);
+      for (size_t k = 0; k < ev.count(); ++k) {
+        const uint32_t p = ev.prefix(k);
+        const IpKey &key = table_.keys[p];
+        if (ev.new_entry(k) == 0xFFFFFFFFu) { rib_.erase(key); continue; }
+        RibRow row = resolved_row(res, p, ev.new_metric(k), ev.new_mask(k), W);
+        auto it = rib_.lower_bound(key);
+        if (it != rib_.end() && it->first == key) it->second = std::move(row);
+        else rib_.emplace_hint(it, key, std::move(row));
+      }
+      rib_current_ = true;
+    } else {
+      rib_.clear();                                                   // (void from here on: settle_installed() reads it off `prev_` when it is needed)
+      rib_current_ = false;
+    }
     prev_ = std::move(fresh);
     last.expand_ms = ms(t);
     if (getenv("HSPF_TWIN_TIMING")) fprintf(stderr, "[twin pipeline step]  refresh %.2f run %.2f routes %.2f slots %.2f diff_pack %.2f expand %.2f ms (%zu records)\n", last.refresh_ms, last.run_ms, last.routes_ms, last.slots_ms, last.diff_pack_ms, last.expand_ms, last.records);
@@ -1637,7 +1679,17 @@ class RibPipeline {
   }
   // The installed routes (rows of the RIB that have next hops), read off the tables of the last step (one copy of the tables
   // to the host: for inspection and tests, not for the per-event path).
-  std::map<IpKey, RibRow> rib() const { return read_installed(); }
+  std::map<IpKey, RibRow> rib() const {
+    if (!rib_current_) return read_installed();
+    std::map<IpKey, RibRow> rows;
+    for (auto &kv : rib_) if (!kv.second.nexthops.empty()) rows.emplace_hint(rows.end(), kv.first, kv.second);
+    return rows;
+  }
+  // The instance's whole RIB — every route of the (level, topology) table, those without next hops included (CONNECTED, unresolved:
+  // rows with an empty next-hop list) — kept current from the engine's event stream, no copy of the tables.  Only with an engine
+  // that has the stream (Engine::routes_events supported): rib_is_current() says so after the first step; without it use rib().
+  const std::map<IpKey, RibRow> &full_rib() const { return rib_; }
+  bool rib_is_current() const { return rib_current_; }
   LevelGraph &graph() { return *graph_; }
 
  private:
@@ -1676,8 +1728,59 @@ class RibPipeline {
   // dropped.  One copy of the tables to the host (16 bytes per prefix and mask word) at the few events that void them.
   void settle_installed() {
     if (!prev_) return;                                               // (nothing since the last settle: rib_ stands)
+    if (rib_current_) {
+      // rib_ followed every event: nothing to copy.  HSPF_RIB_CROSSCHECK=1 (off by default): the copy of the tables all the same,
+      // and its installed rows must be rib_'s rows with next hops
+      static const bool check = getenv("HSPF_RIB_CROSSCHECK") && *getenv("HSPF_RIB_CROSSCHECK") == '1';
+      if (check) {
+        const std::map<IpKey, RibRow> want = read_installed(), got = rib();
+        bool same = want.size() == got.size();
+        for (auto a = want.begin(), b = got.begin(); same && a != want.end(); ++a, ++b)
+          same = a->first == b->first && a->second.metric == b->second.metric && a->second.nexthops == b->second.nexthops;
+        if (!same) throw std::logic_error("RibPipeline: the RIB kept from the event stream differs from the tables");
+      }
+      prev_.reset();
+      return;
+    }
     rib_ = read_installed();
     prev_.reset();
+  }
+  // every slot's next hop per address family (0: IPv4, 1: IPv6), resolved once per step
+  struct SlotRes { bool has = false; IpKey key; std::string addr, ifname; };
+  struct SlotTableRes { std::vector<SlotRes> res[2]; };
+  SlotTableRes resolve_slots(uint32_t W) const {
+    SlotTableRes t;
+    t.res[0].resize((size_t)W * 64); t.res[1].resize((size_t)W * 64);
+    for (auto &kv : slot_nh_) {
+      if (kv.first >= (size_t)W * 64) continue;
+      for (int f = 0; f < 2; ++f) {
+        const auto &addr = f ? kv.second->ipv6 : kv.second->ipv4;
+        if (addr) t.res[f][kv.first] = SlotRes{true, parse_ip(*addr), *addr, kv.second->iface_name.value_or("")};
+      }
+    }
+    return t;
+  }
+  // a route of prefix p from its metric and slot mask (u32 halves, low first), next hops as the route holds them: ascending
+  // address, a later slot with the same address replaces the earlier one, the first max-paths (as read_installed)
+  RibRow resolved_row(const SlotTableRes &t, uint32_t p, uint32_t metric, const uint32_t *mask32, uint32_t W) const {
+    RibRow row{table_.prefixes[p], metric, level_, {}};
+    const std::vector<SlotRes> &res = t.res[table_.keys[p].version == 6 ? 1 : 0];
+    std::vector<const SlotRes *> pick;
+    for (uint32_t w = 0; w < W; ++w) {
+      uint64_t m = (uint64_t)mask32[2 * w] | ((uint64_t)mask32[2 * w + 1] << 32);
+      while (m) {
+        const int b = __builtin_ctzll(m);
+        m &= m - 1;
+        const SlotRes &sr = res[w * 64 + b];
+        if (sr.has) pick.push_back(&sr);
+      }
+    }
+    std::stable_sort(pick.begin(), pick.end(), [](const SlotRes *a, const SlotRes *b) { return a->key < b->key; });
+    for (size_t i = 0; i < pick.size() && row.nexthops.size() < max_paths_; ++i) {
+      if (i + 1 < pick.size() && pick[i + 1]->key == pick[i]->key) continue;
+      row.nexthops.push_back({pick[i]->addr, pick[i]->ifname});
+    }
+    return row;
   }
   std::map<IpKey, RibRow> read_installed() const {
     if (!prev_) return rib_;
@@ -1728,9 +1831,10 @@ class RibPipeline {
   std::vector<PfxSig> pfx_sig_;                                       // by vertex index of graph_
   std::map<uint32_t, std::shared_ptr<VertexNexthop>> slot_nh_;
   std::unique_ptr<DeviceRoutes> prev_;
-  std::map<IpKey, RibRow> rib_;                                       // installed routes as of the last settle_installed(); void while `prev_` holds tables
+  std::map<IpKey, RibRow> rib_;                                       // rib_current_: the whole RIB after the last step; else installed routes as of the last settle_installed(), void while `prev_` holds tables
   uint32_t max_paths_ = 16;
   bool resident_ = false;
+  bool rib_current_ = false;                                          // rib_ followed every event of the last step (engine with the event stream)
 };
 
 // ---- flooding::manet (holo-isis/src/flooding/manet.rs) ---------------------------------------------------------------

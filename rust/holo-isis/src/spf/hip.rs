@@ -347,7 +347,7 @@ pub(crate) fn compute_spt(
 //   the level graph on the device (CsrCache: rows of the changed LSPs are patched),
 //   the prefix table on the device (PrefixTable, HSPF_PFX_RESIDENT; rebuilt when a changed LSP's prefixes differ),
 //   the route tables of the PREVIOUS event on the device = the "RIB held before".
-// Per event: run_device -> routes_device -> routes_changed (comparison + ordered compaction + two small copies) ->
+// Per event: run_device -> routes_device -> routes_events (comparison + ordered compaction + ONE copy, SILENT pairs included) ->
 // a `Route` is built ONLY for the records, the stored RIB is updated in place, route_install / route_uninstall are called
 // for them in the reference's order.  A mechanical translation of the COMPILED AND TESTED C++ form,
 // include/holo_spf_isis.hpp `RibPipeline` of the engine repository (its messages equal the reference's recorded ibus
@@ -456,6 +456,8 @@ impl RibPipeline {
             .collect()
     }
 
+    // (Since update_rib takes the hspf_routes_events stream with SILENT pairs, the RIB is current after every event and this pass
+    // finds nothing to do; it is kept for the event that voids the tables, as the cross-check of that property.)
     // The instance's RIB brought in line with the tables of the last event, which are dropped: a change that puts nothing on
     // the wire leaves no record (HSPF_DIFF_SILENT) — a route that lost its next hops (route.rs:283-301 replaces it by a fresh
     // route without INSTALLED and sends nothing), a route without next hops whose prefix went away — so a RIB kept from records
@@ -574,7 +576,10 @@ pub(crate) fn update_rib(
                 }
                 pipe.prev = Some(eng.routes_upload(1, p as u32, fresh.words, &bm, &be, &nm).map_err(|e| e.log()).ok()?);
             }
-            let records = eng.routes_changed(pipe.prev.as_ref()?, &fresh).map_err(|e| e.log()).ok()?;
+            // every pair that is not SAME, HSPF_DIFF_SILENT pairs included (hspf_routes_events: one device call, old and new half in
+            // one record): a route that lost its next hops, or one without next hops that vanished, comes back as a record and
+            // the loop below replaces / removes its RIB row without a message — the operational RIB follows every event
+            let records = eng.routes_events(pipe.prev.as_ref()?, &fresh, true).map_err(|e| e.log()).ok()?;
             // the records: installs in prefix order, then the withdrawals (update_global_rib, route.rs:254-312)
             let mut withdrawn = vec![];
             for rec in &records {

@@ -327,7 +327,7 @@ impl DeviceRoutes<'_> {
 pub struct RouteRecord {
     pub root: u32,
     pub prefix: u32,
-    pub action: u32, // sys::HSPF_DIFF_INSTALL | sys::HSPF_DIFF_WITHDRAW
+    pub action: u32, // sys::HSPF_DIFF_INSTALL | sys::HSPF_DIFF_WITHDRAW; from routes_events(.., true) also sys::HSPF_DIFF_SILENT
     pub new_metric: u32,
     pub new_entry: u32, // 0xFFFFFFFF: the prefix has no route any more
     pub new_mask: Vec<u64>,
@@ -405,6 +405,8 @@ pub struct Engine {
     /// synchronise the device (the compiled C++ twin's `HipPool`: LSP change -> messages 0.94 -> 0.81 ms).  Every engine call
     /// that touches a block is synchronous, so a returned block is idle.
     pool: std::cell::RefCell<std::collections::BTreeMap<usize, Vec<*mut c_void>>>,
+    /// Records the previous `routes_events` produced: sizes the buffer of the next call.
+    events_hint: std::cell::Cell<usize>,
 }
 
 // One OS thread per protocol instance; a context is used by exactly one thread at a time.
@@ -432,7 +434,7 @@ impl Engine {
         if rc != sys::HSPF_OK {
             return Err(Error { code: rc, detail: "hspf_init".into() });
         }
-        Ok(Engine { ctx, pool: Default::default() })
+        Ok(Engine { ctx, pool: Default::default(), events_hint: Default::default() })
     }
 
     /// `HOLO_SPF_HIP_DEVICE=<ordinal>`; unset or unusable => `None` => today's code path, byte for byte.
@@ -703,6 +705,54 @@ impl Engine {
             best_entry: self.device_from(best_entry)?,
             nexthop_mask: self.device_from(nexthop_mask)?,
         })
+    }
+
+    /// `hspf_routes_events` (+ `hspf_routes_events_rest` when the stream is longer than the first call took): every
+    /// (root, prefix) pair whose action is not SAME — `HSPF_DIFF_SILENT` pairs included when `with_silent` — as paired
+    /// old -> new records in the reference's emission order.  ONE comparison on the device, one synchronisation and one
+    /// copy in the steady state; with `with_silent` a caller's own RIB follows every event of the engine.
+    pub fn routes_events(&self, old: &DeviceRoutes<'_>, new: &DeviceRoutes<'_>, with_silent: bool) -> Result<Vec<RouteRecord>, Error> {
+        if old.n_roots != new.n_roots || old.n_prefixes != new.n_prefixes || old.words != new.words {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_events: the two sets differ in shape".into() });
+        }
+        let w = new.words as usize;
+        let stride = sys::HSPF_EVENT_REC_WORDS as usize + 4 * w;
+        let hint = self.events_hint.get();
+        let cap = (hint + hint / 4).max(1024);
+        let mut rec = vec![0u32; cap * stride];
+        let mut total = 0u32;
+        let (ro, rn) = (old.raw(), new.raw());
+        let flags = if with_silent { sys::HSPF_EV_SILENT } else { 0 };
+        let rc = unsafe {
+            sys::hspf_routes_events(self.ctx, new.n_roots, new.n_prefixes, new.words, &ro, &rn, flags, cap as u32, rec.as_mut_ptr(), &mut total)
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let k = total as usize;
+        self.events_hint.set(k);
+        rec.resize(k * stride, 0);
+        if k > cap {
+            let rc = unsafe { sys::hspf_routes_events_rest(self.ctx, cap as u32, (k - cap) as u32, rec[cap * stride..].as_mut_ptr()) };
+            if rc != sys::HSPF_OK {
+                return Err(self.err(rc));
+            }
+        }
+        let words_of = |half: &[u32]| -> Vec<u64> { (0..w).map(|i| half[2 * i] as u64 | (half[2 * i + 1] as u64) << 32).collect() };
+        Ok(rec
+            .chunks_exact(stride)
+            .map(|r| RouteRecord {
+                root: r[0],
+                prefix: r[1],
+                action: r[2],
+                new_metric: r[3],
+                new_entry: r[4],
+                new_mask: words_of(&r[8..8 + 2 * w]),
+                old_metric: r[5],
+                old_entry: r[6],
+                old_mask: words_of(&r[8 + 2 * w..]),
+            })
+            .collect())
     }
 
     /// `hspf_routes_diff_device` + `hspf_routes_pack` (twice: the changed list packed from the new set and from the old
