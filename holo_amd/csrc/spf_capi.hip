@@ -1207,13 +1207,25 @@ static int graph_patch_impl(hspf_ctx *ctx, hspf_graph *g, const hspf_rows *rows,
   if (incremental) {
     aff.assign(rows->vertex, rows->vertex + m);
     aff.insert(aff.end(), rows->col, rows->col + de);
-    for (uint32_t j = 0; j < m && aff.size() <= 8u * PA_MAX_ROWS; ++j) {
+    // The list is deduplicated whenever it passes 8 x PA_MAX_ROWS entries, so it stays small and is COMPLETE when the path is
+    // taken: every old target of every replaced row is in it, or the unique rows alone are too many and the rebuild runs.
+    // (Until round 9 the loop simply stopped there and the path was chosen from what it had collected: the old targets of
+    // the rows behind the stop kept stale in- and out-rows, tests/test_gpu_patch_limits.py case b.)
+    auto dedup = [&]() {
+      std::sort(aff.begin(), aff.end());
+      aff.erase(std::unique(aff.begin(), aff.end()), aff.end());
+    };
+    bool complete = true;
+    for (uint32_t j = 0; j < m; ++j) {
+      if (aff.size() > 8u * PA_MAX_ROWS) {
+        dedup();
+        if (aff.size() > PA_MAX_ROWS) { complete = false; break; }
+      }
       const uint32_t v = rows->vertex[j];
       aff.insert(aff.end(), g->col.begin() + g->rb(v), g->col.begin() + g->re(v));
     }
-    std::sort(aff.begin(), aff.end());
-    aff.erase(std::unique(aff.begin(), aff.end()), aff.end());
-    incremental = aff.size() <= PA_MAX_ROWS && patch_prepare(ctx, g, (uint32_t)aff.size()) == HSPF_OK;   // (no room for the scratch: the rebuild)
+    dedup();
+    incremental = complete && aff.size() <= PA_MAX_ROWS && patch_prepare(ctx, g, (uint32_t)aff.size()) == HSPF_OK;   // (no room for the scratch: the rebuild)
   }
   const uint32_t na = incremental ? (uint32_t)aff.size() : 0u;
   // the delta, one pinned staging block, one copy: changed[m] | delta_ptr[m+1] | shift[m+1] | delta_col[de] | delta_metric[de] | flags[m] (bytes) | affected[na]

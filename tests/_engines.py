@@ -6,3 +6,4 @@ sweeps_engine = pytest.mark.parametrize("spf_ctx", ["sweeps"], indirect=True)
 all_engines = pytest.mark.parametrize("spf_ctx", ["default", "sweeps", "kfused", "twophase", "widemask", "lanevertex", "xcd"], indirect=True)
 hub_engines = pytest.mark.parametrize("spf_ctx", ["default", "hubsort", "patchfull"], indirect=True)
 hubsort_engine = pytest.mark.parametrize("spf_ctx", ["hubsort"], indirect=True)
+patch_engines = pytest.mark.parametrize("spf_ctx", ["default", "patchfull"], indirect=True)      # the incremental structural patch and the rebuild it replaced
