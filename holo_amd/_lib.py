@@ -73,6 +73,16 @@ class HspfRibDevice(ctypes.Structure):
                 ("best_entry", ctypes.c_void_p), ("nexthop_mask", ctypes.c_void_p), ("origin", ctypes.c_void_p)]
 
 
+class HspfLfaProtect(ctypes.Structure):
+    _fields_ = [("root_vertex", ctypes.c_uint32), ("root_row", ctypes.c_uint32), ("n_slots", ctypes.c_uint32),
+                ("nbr", u32p), ("nbr_row", u32p), ("cost", u32p), ("root_link", u32p), ("cflags", u8p)]
+
+
+class HspfLfaOut(ctypes.Structure):
+    _fields_ = [("alt_slot", ctypes.c_void_p), ("alt_metric", ctypes.c_void_p), ("alt_flags", ctypes.c_void_p),
+                ("cand_mask", ctypes.c_void_p), ("node_mask", ctypes.c_void_p), ("coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -146,6 +156,10 @@ SYMBOLS = [
     ("hspf_ancestors_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # loop-free alternates
+    ("hspf_lfa_candidates", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u8p, u32p]),
+    ("hspf_lfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfLfaOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

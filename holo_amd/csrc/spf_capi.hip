@@ -12,6 +12,7 @@
 #include "graph_build.hip.h"
 #include "graph_patch.hip.h"
 #include "hub_sort.h"
+#include "spf_lfa.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -216,6 +217,7 @@ struct hspf_ctx {
   uint32_t last_diff_count = 0;                     // changed pairs of the last hspf_routes_diff_device (hspf_routes_diff_count)
   // hspf_routes_events: action bytes + tile offsets + total | the record stream's staging (grown from what calls needed)
   DevBuf evs_scr, evs_rec;
+  DevBuf lfa_tab, lfa_scal;                          // hspf_lfa_device: the staged per-root slot tables | d(N, S) and d(N, N') of every protected root
   uint32_t *h_ev = nullptr;                          // pinned: the event total, stored by k_events_scan itself
   struct EvState {                                   // the last hspf_routes_events, for hspf_routes_events_rest
     bool valid = false;
@@ -861,7 +863,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -3767,6 +3769,129 @@ int hspf_ancestors_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *ro
     }
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { ctx->last_error = std::string("k_anc: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    return HSPF_OK;
+  });
+}
+
+// ---- loop-free alternates (include/holo_spf_hip.h "loop-free alternates on device"; kernels: spf_lfa.hip.h) ----------------
+int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *nbr, uint32_t *cost, uint32_t *root_link,
+                        uint8_t *cflags, uint32_t *out_total_slots) {
+  if (!csr || !csr->row_ptr || !csr->vflags || (csr->n_edges && (!csr->col || !csr->metric)) || root >= csr->n_vertices) return HSPF_E_INVAL;
+  return guarded(nullptr, [&]() -> int {
+    const uint32_t n = csr->n_vertices;
+    const uint32_t *rp = csr->row_ptr, *col = csr->col, *met = csr->metric;
+    auto row_ok = [&](uint32_t v) { return rp[v] <= rp[v + 1] && rp[v + 1] <= csr->n_edges; };
+    auto links_back = [&](uint32_t t, uint32_t v) {                 // the two-way check: does t's row list v?  (cost not compared)
+      if (!row_ok(t)) return false;
+      for (uint32_t k = rp[t]; k < rp[t + 1]; ++k) if (col[k] == v) return true;
+      return false;
+    };
+    // H = [root] ++ networks reached through networks only, breadth-first, links in row order, each once (hspf_slot_table);
+    // per entry the cost of its discovery path and the link of the root's row that starts it
+    struct HEnt { uint32_t v, path_cost, first_link; };
+    std::vector<HEnt> H{{root, 0u, 0u}};
+    std::vector<uint32_t> seen{root};                               // (sorted: H holds a handful of vertices)
+    uint64_t total = 0;
+    for (size_t qi = 0; qi < H.size(); ++qi) {
+      const HEnt p = H[qi];
+      if (!row_ok(p.v)) return HSPF_E_INVAL;
+      for (uint32_t k = rp[p.v]; k < rp[p.v + 1]; ++k, ++total) {
+        const uint32_t t = col[k], j = k - rp[p.v];
+        if (t >= n) return HSPF_E_INVAL;
+        if (total > 0xFFFFFFF0ull) return HSPF_E_INVAL;
+        const uint64_t c64 = (uint64_t)p.path_cost + met[k];
+        const uint32_t c = c64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c64;
+        const uint32_t first = qi == 0 ? j : p.first_link;
+        const bool net = (csr->vflags[t] & HSPF_VF_NETWORK) != 0;
+        const bool two = (net || t != root) && links_back(t, p.v);
+        if (total < cap) {
+          const bool is_cand = !net && t != root && two;
+          if (nbr) nbr[total] = is_cand ? t : HSPF_NO_ROOT;
+          if (cost) cost[total] = c;
+          if (root_link) root_link[total] = first;
+          if (cflags) cflags[total] = (is_cand && (csr->vflags[t] & HSPF_VF_NO_TRANSIT)) ? (uint8_t)HSPF_LFA_C_NO_TRANSIT : (uint8_t)0;
+        }
+        if (net && two) {
+          auto it = std::lower_bound(seen.begin(), seen.end(), t);
+          if (it == seen.end() || *it != t) { seen.insert(it, t); H.push_back({t, c, first}); }
+        }
+      }
+    }
+    if (out_total_slots) *out_total_slots = (uint32_t)total;
+    return (int)std::min<uint64_t>(total, 0x7FFFFFFFull);
+  });
+}
+
+int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                    const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                    const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    auto bad = [&](const std::string &what) { ctx->last_error = "hspf_lfa_device: " + what; return HSPF_E_INVAL; };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
+    // the staged block: headers, then per root nbr | row | cost | root_link | cflags | candidate list (K words each)
+    size_t tab_words = (size_t)n_prot * LFA_HDR_WORDS, scal_words = 0;
+    uint32_t max_k = 0;
+    for (uint32_t i = 0; i < n_prot; ++i) {
+      const hspf_lfa_protect &p = prot[i];
+      const std::string who = "protected root " + std::to_string(i) + ": ";
+      if (p.root_row >= n_rows) return bad(who + "root_row >= n_rows");
+      if (p.root_vertex >= n_vertices) return bad(who + "root_vertex >= n_vertices");
+      if (p.n_slots > 64ull * n_mask_words) return bad(who + "n_slots > 64 * n_mask_words");
+      if (p.n_slots && (!p.nbr || !p.nbr_row || !p.cost || !p.root_link || !p.cflags)) return bad(who + "NULL slot array");
+      for (uint32_t k = 0; k < p.n_slots; ++k) {
+        if (p.nbr[k] == HSPF_NO_ROOT) continue;
+        if (p.nbr[k] >= n_vertices) return bad(who + "nbr of slot " + std::to_string(k) + " >= n_vertices");
+        if (p.nbr_row[k] >= n_rows) return bad(who + "nbr_row of slot " + std::to_string(k) + " >= n_rows");
+      }
+      tab_words += (size_t)6 * p.n_slots;
+      scal_words += (size_t)p.n_slots * ((size_t)p.n_slots + 1);
+      max_k = std::max(max_k, p.n_slots);
+    }
+    if (tab_words > (1u << 28) || scal_words > (1u << 28)) { ctx->last_error = "hspf_lfa_device: the slot tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
+    std::vector<uint32_t> tab(tab_words, 0u);
+    size_t to = (size_t)n_prot * LFA_HDR_WORDS, so = 0;
+    for (uint32_t i = 0; i < n_prot; ++i) {
+      const hspf_lfa_protect &p = prot[i];
+      const uint32_t K = p.n_slots;
+      uint32_t *h = tab.data() + (size_t)i * LFA_HDR_WORDS, *t = tab.data() + to;
+      uint32_t C = 0;
+      for (uint32_t k = 0; k < K; ++k) {
+        const bool c = p.nbr[k] != HSPF_NO_ROOT;
+        t[k] = p.nbr[k]; t[K + k] = c ? p.nbr_row[k] : 0u; t[2 * K + k] = p.cost[k]; t[3 * K + k] = p.root_link[k];
+        t[4 * K + k] = c ? p.cflags[k] : 0u;
+        if (c) t[5 * K + C++] = k;
+      }
+      h[0] = p.root_vertex; h[1] = p.root_row; h[2] = K; h[3] = C; h[4] = (uint32_t)to; h[5] = (uint32_t)so;
+      to += (size_t)6 * K; so += (size_t)K * ((size_t)K + 1);
+    }
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = ensure(ctx, ctx->lfa_tab, tab_words * 4, false))) return rc;
+    if ((rc = ensure(ctx, ctx->lfa_scal, std::max<size_t>(scal_words, 1) * 4, false))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->lfa_tab.p, tab.data(), tab_words * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_COVERAGE_WORDS * 4, s));
+    LfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
+    a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev;
+    a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (uint32_t *)ctx->lfa_scal.p;
+    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
+    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
+    if (max_k) {
+      const uint32_t gx = (uint32_t)std::min<size_t>(((size_t)max_k * ((size_t)max_k + 1) + 255) / 256, 1024);
+      hipLaunchKernelGGL(k_lfa_gather, dim3(gx, n_prot), dim3(256), 0, s, a);
+    }
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    const bool one = max_k <= 64;
+    const dim3 grid(n_tiles, n_prot);
+    if (one) hipLaunchKernelGGL(k_lfa<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) { ctx->last_error = std::string("k_lfa: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    HIPCHK(ctx, hipStreamSynchronize(s));
     return HSPF_OK;
   });
 }

@@ -35,6 +35,12 @@ EV_SILENT = 0x1           # hspf_routes_events: SILENT pairs are part of the str
 EVENT_REC_WORDS = 8       # HSPF_EVENT_REC_WORDS
 DIFF_SAME, DIFF_INSTALL, DIFF_WITHDRAW, DIFF_SILENT = 0, 1, 2, 3
 
+LFA_C_NO_TRANSIT = 0x01         # HSPF_LFA_C_NO_TRANSIT (candidate flags)
+LFA_IGNORE_OVERLOAD = 0x01      # HSPF_LFA_IGNORE_OVERLOAD (lfa_device flags)
+LFA_HAS_PRIMARY, LFA_ECMP, LFA_LINK_PROTECT, LFA_NODE_PROTECT, LFA_DOWNSTREAM = 0x01, 0x02, 0x04, 0x08, 0x10
+LFA_NO_SLOT = 0xFFFFFFFF
+LFA_COVERAGE_WORDS = 5
+
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
 DIST_INF = 0xFFFFFFFF
@@ -147,6 +153,51 @@ def splice_rows(row_ptr, col, metric, vflags, vertices, cols, mets, new_flags):
     nvf = vflags.copy()
     nvf[np.asarray(vertices, dtype=np.int64)] = new_flags
     return nrp.astype(np.uint32), ncol, nmet, nvf
+
+
+@dataclass
+class LfaCandidates:
+    """hspf_lfa_candidates(): the candidate table of one root, one entry per first-hop slot (include/holo_spf_hip.h)."""
+    root: int
+    nbr: np.ndarray          # [K] u32 router behind the slot, NO_ROOT: not a candidate
+    cost: np.ndarray         # [K] u32 cost of the path the slot stands for
+    root_link: np.ndarray    # [K] u32 link of the root's own row that starts it
+    cflags: np.ndarray       # [K] u8  LFA_C_*
+    total_slots: int = 0     # slots of the root (more than the arrays hold when `cap` cut them short)
+
+    @property
+    def n_slots(self) -> int:
+        return len(self.nbr)
+
+
+@dataclass
+class LfaResult:
+    """Loop-free alternates of the protected roots of one lfa_device() call, on the host."""
+    alt_slot: np.ndarray     # [P, N] u32, LFA_NO_SLOT: none
+    alt_metric: np.ndarray   # [P, N] u32
+    alt_flags: np.ndarray    # [P, N] u8  LFA_HAS_PRIMARY | LFA_ECMP | LFA_LINK_PROTECT | LFA_NODE_PROTECT | LFA_DOWNSTREAM
+    cand_mask: Optional[np.ndarray]   # [P, N, W] u64 or None
+    node_mask: Optional[np.ndarray]   # [P, N, W] u64 or None
+    coverage: np.ndarray     # [P, 5] u32
+
+
+def lfa_candidates(row_ptr, col, metric, vflags, root: int, cap: Optional[int] = None) -> LfaCandidates:
+    """hspf_lfa_candidates(): pure host arithmetic on the caller's CSR (no context, no GPU).  `cap`: entries to fill
+    (default: all); the arrays always have one entry per slot that was filled."""
+    lib = L.load()
+    row_ptr = np.ascontiguousarray(row_ptr, np.uint32); col = np.ascontiguousarray(col, np.uint32)
+    metric = np.ascontiguousarray(metric, np.uint32); vflags = np.ascontiguousarray(vflags, np.uint8)
+    csr = L.HspfCsr(len(row_ptr) - 1, len(col), _u32(row_ptr), _u32(col), _u32(metric), vflags.ctypes.data_as(L.u8p), 0xFFFFFFFF)
+    total = ctypes.c_uint32()
+    k = lib.hspf_lfa_candidates(ctypes.byref(csr), root, 0, None, None, None, None, ctypes.byref(total))
+    if k < 0:
+        raise HspfError(k, "hspf_lfa_candidates")
+    k = k if cap is None else min(k, int(cap))
+    nbr, cost, rl, cf = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint8)
+    rc = lib.hspf_lfa_candidates(ctypes.byref(csr), root, k, _u32(nbr), _u32(cost), _u32(rl), cf.ctypes.data_as(L.u8p), ctypes.byref(total))
+    if rc < 0:
+        raise HspfError(rc, "hspf_lfa_candidates")
+    return LfaCandidates(int(root), nbr, cost, rl, cf, int(total.value))
 
 
 class SpfGraph:
@@ -605,6 +656,74 @@ class SpfContext:
         if rc != 0:
             raise HspfError(rc, "hspf_routes_events_rest", self.last_error())
         return full
+
+    def lfa_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
+                   alt_slot_ptr: int, alt_metric_ptr: int, alt_flags_ptr: int, coverage_ptr: int, cand_mask_ptr: int = 0,
+                   node_mask_ptr: int = 0, lfa_flags: int = 0) -> None:
+        """hspf_lfa_device(): loop-free alternates of every protected root from the table set of a previous run_device().
+        `protect`: a list of (root_row, LfaCandidates, nbr_row) — nbr_row[k] = table row of the SPT rooted at
+        candidates.nbr[k] (ignored where the slot is no candidate).  All `*_ptr` are device pointers; cand_mask_ptr /
+        node_mask_ptr may be 0."""
+        arr = (L.HspfLfaProtect * max(len(protect), 1))()
+        keep = []
+        for i, (root_row, c, nbr_row) in enumerate(protect):
+            cols = [np.ascontiguousarray(x, dt) for x, dt in ((c.nbr, np.uint32), (nbr_row, np.uint32), (c.cost, np.uint32),
+                                                             (c.root_link, np.uint32), (c.cflags, np.uint8))]
+            if len({len(x) for x in cols}) != 1:
+                raise ValueError("lfa_device: the slot arrays of a protected root differ in length")
+            keep.append(cols)
+            arr[i] = L.HspfLfaProtect(int(c.root), int(root_row), len(cols[0]), _u32(cols[0]), _u32(cols[1]), _u32(cols[2]), _u32(cols[3]),
+                                      cols[4].ctypes.data_as(L.u8p))
+        out = L.HspfLfaOut(alt_slot_ptr or None, alt_metric_ptr or None, alt_flags_ptr or None, cand_mask_ptr or None, node_mask_ptr or None,
+                           coverage_ptr or None)
+        rc = self.lib.hspf_lfa_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                      arr, len(protect), lfa_flags, ctypes.byref(out))
+        if rc != 0:
+            raise HspfError(rc, "hspf_lfa_device", self.last_error())
+
+    def _dev_alloc(self, nbytes: int) -> int:
+        p = ctypes.c_void_p()
+        rc = self.lib.hspf_device_alloc(self.handle, max(int(nbytes), 8), ctypes.byref(p))
+        if rc != 0:
+            raise HspfError(rc, "hspf_device_alloc", self.last_error())
+        return p.value
+
+    def lfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_masks: bool = True):
+        """Backup next hops of one root, start to finish: the candidate table of `root`, ONE run_device() for
+        [root] + its distinct neighbour routers, lfa_device() on those rows, the five arrays and the coverage on the host.
+        Returns (LfaCandidates, LfaResult with one row).  The SPT tables never leave the device."""
+        cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
+        nbrs = np.unique(cand.nbr[cand.nbr != NO_ROOT])
+        roots = np.concatenate([[root], nbrs]).astype(np.uint32)
+        nbr_row = np.zeros(cand.n_slots, np.uint32)
+        is_c = cand.nbr != NO_ROOT
+        nbr_row[is_c] = 1 + np.searchsorted(nbrs, cand.nbr[is_c])
+        R, n = len(roots), graph.n
+        W = max(graph.mask_words(roots), (cand.n_slots + 63) // 64)
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, slot=4 * n, metric=4 * n, aflags=n,
+                     cm=8 * n * W if want_masks else 0, nm=8 * n * W if want_masks else 0, cov=4 * LFA_COVERAGE_WORDS)
+        dev = {}
+        try:
+            for k, b in sizes.items():
+                dev[k] = self._dev_alloc(b) if b else 0
+            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], alt_slot_ptr=dev["slot"],
+                            alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], cand_mask_ptr=dev["cm"],
+                            node_mask_ptr=dev["nm"], lfa_flags=lfa_flags)
+            res = LfaResult(np.empty((1, n), np.uint32), np.empty((1, n), np.uint32), np.empty((1, n), np.uint8),
+                            np.empty((1, n, W), np.uint64) if want_masks else None, np.empty((1, n, W), np.uint64) if want_masks else None,
+                            np.empty((1, LFA_COVERAGE_WORDS), np.uint32))
+            for arr, k in ((res.alt_slot, "slot"), (res.alt_metric, "metric"), (res.alt_flags, "aflags"), (res.cand_mask, "cm"),
+                           (res.node_mask, "nm"), (res.coverage, "cov")):
+                if arr is not None:
+                    rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
+                    if rc != 0:
+                        raise HspfError(rc, "hspf_device_to_host", self.last_error())
+            return cand, res
+        finally:
+            for p in dev.values():
+                if p:
+                    self.lib.hspf_device_free(self.handle, ctypes.c_void_p(p))
 
     def close(self):
         if self.handle:

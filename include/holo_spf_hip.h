@@ -639,6 +639,94 @@ int hspf_ancestors_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *ro
                           uint32_t level, uint32_t n_words, uint32_t *level_rank_dev, uint32_t *level_count_dev,
                           uint64_t *anc_dev);
 
+/* ---- loop-free alternates on device (RFC 5286) from neighbour SPTs: new symbols, same ABI number -----------------------
+ * The consumer the many-roots batch was built for: a run of [S] ++ (S's neighbour routers) leaves their SPTs in HBM as
+ * rows of one table set, and the backup next hops of S are inequalities over those rows.  hspf_lfa_device evaluates them
+ * per (protected root, destination) where the tables are; hspf_lfa_candidates (host arithmetic, no context) says which
+ * first-hop slots of S are candidates at all.  The reference ships only the YANG for this (ietf-isis fast-reroute/lfa,
+ * frr-protection-available-{link,node,downstream}-type), no code.
+ *
+ * Terms.  S = a protected root; its SPT is row `root_row` of a table set [n_rows][n_vertices] (dist, vflags_out,
+ * first_hop_mask with W = n_mask_words words) exactly as hspf_run_device wrote it.  A slot k of S is a first-hop slot as
+ * defined above (hspf_result / hspf_slot_table): slot(p, j) = link j of H-vertex p.  Per slot k the candidate table holds
+ *   nbr[k]        the ROUTER the slot's link leads to, or HSPF_NO_ROOT when the slot is no candidate: its target is a network
+ *                 vertex, or S itself, or the link fails the two-way check;
+ *   nbr_row[k]    the table row that holds the SPT rooted at nbr[k] (the caller's: it made the run);
+ *   cost[k]       sum of the link costs along the path the slot stands for, S -> (network vertices) -> target (saturating u32):
+ *                 the path by which H reached p (its breadth-first discovery links) plus link j;
+ *   root_link[k]  position in S's OWN row of the link that starts that path (p == S: j itself);
+ *   cflags[k]     HSPF_LFA_C_NO_TRANSIT when the neighbour carries HSPF_VF_NO_TRANSIT.
+ * cost and root_link are filled for EVERY slot (a primary slot need not be a candidate), nbr / cflags for candidates.
+ *
+ * For a destination D in S's SPT, D != S:  P = the primary slots = the bits of mask_S[D]; d(X, Y) = dist in the row rooted
+ * at X.  All sums are evaluated in 64 bits (max_path_metric may be 0xFE000000: two terms overflow u32); a term that is
+ * HSPF_DIST_INF makes its inequality false.  Candidate k with N = nbr[k] belongs to
+ *   cand        (loop-free and link-protecting) iff  d(N, D) < d(N, S) + d(S, D),  and root_link[k] != root_link[p] for every p
+ *               in P,  and k is not in P,  and (cflags[k] has no NO_TRANSIT, or N == D, or the call passes HSPF_LFA_IGNORE_OVERLOAD);
+ *   node        (node-protecting) iff k is in cand, P has at least one slot whose nbr[p] is a router, and for every such p with
+ *               E = nbr[p]:  d(N, D) < d(N, E) + d(E, D)   (a primary slot whose target is not a router protects no node;
+ *               E == D makes the inequality false by itself);
+ *   downstream  iff  d(N, D) < d(S, D).
+ * Outputs per (S, D):
+ *   alt_flags   HSPF_LFA_HAS_PRIMARY   P is not empty
+ *               HSPF_LFA_ECMP          popcount(P) >= 2: no alternate is chosen (the other primaries are the alternates); the two
+ *                                      sets are still written
+ *               HSPF_LFA_LINK_PROTECT  an alternate was chosen (alt_slot is a member of cand)
+ *               HSPF_LFA_NODE_PROTECT  ... and it is a member of node
+ *               HSPF_LFA_DOWNSTREAM    ... and it is a downstream neighbour
+ *   alt_slot    HSPF_LFA_NO_SLOT for none.  Chosen only when popcount(P) == 1: a member of node before a member of cand only,
+ *               then the smallest cost[k] + d(N, D) (64 bits), then the smallest slot index
+ *   alt_metric  that sum, saturated at 0xFFFFFFFE (0 when there is no alternate)
+ *   cand_mask / node_mask   u64[W] per (S, D), bit k = slot k (optional: NULL skips the table)
+ * For D == S, or D not in S's SPT, every output is zero and alt_slot is HSPF_LFA_NO_SLOT.
+ * coverage[5] per protected root, counted on the device: destinations with a primary | ECMP destinations | destinations with
+ * an alternate | with a node-protecting alternate | with a downstream alternate (the five alt_flags bits, in that order).
+ *
+ * LAN pseudonodes are handled through root_link ALONE: a candidate reached over the same first link of S as a primary is never
+ * offered.  Loop-freeness with respect to the pseudonode itself (RFC 5286 section 3.3) is OUT OF SCOPE: a candidate on another
+ * link whose own shortest path to D crosses the primary's LAN is still offered as link-protecting. */
+#define HSPF_LFA_C_NO_TRANSIT    0x01u   /* hspf_lfa_protect.cflags */
+#define HSPF_LFA_IGNORE_OVERLOAD 0x01u   /* hspf_lfa_device lfa_flags */
+#define HSPF_LFA_HAS_PRIMARY     0x01u   /* alt_flags */
+#define HSPF_LFA_ECMP            0x02u
+#define HSPF_LFA_LINK_PROTECT    0x04u
+#define HSPF_LFA_NODE_PROTECT    0x08u
+#define HSPF_LFA_DOWNSTREAM      0x10u
+#define HSPF_LFA_NO_SLOT         0xFFFFFFFFu
+#define HSPF_LFA_COVERAGE_WORDS  5u
+/* Candidate table of one root from the caller's CSR: pure host arithmetic (no context, no device, like hspf_recommend_cpu).
+ * Restates the slot numbering of hspf_slot_table and applies the two-way check to the rows it touches (S's and those of the
+ * network vertices of H, and one scan of each target's row).  Writes up to `cap` entries of each array (any may be NULL);
+ * returns the number of slots (may exceed cap; also in *out_total_slots when not NULL), or HSPF_E_INVAL. */
+int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *nbr, uint32_t *cost, uint32_t *root_link,
+                        uint8_t *cflags, uint32_t *out_total_slots);
+typedef struct {
+  uint32_t        root_vertex;   /* S                                                                         */
+  uint32_t        root_row;      /* row of the table set that holds S's SPT                                    */
+  uint32_t        n_slots;       /* entries of the five arrays below: <= 64 * n_mask_words                     */
+  const uint32_t *nbr;           /* HOST arrays [n_slots] (hspf_lfa_candidates); nbr_row is read for candidates only */
+  const uint32_t *nbr_row;
+  const uint32_t *cost;
+  const uint32_t *root_link;
+  const uint8_t  *cflags;
+} hspf_lfa_protect;
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint32_t *alt_slot;            /* [n_prot][n_vertices]                                                       */
+  uint32_t *alt_metric;          /* [n_prot][n_vertices]                                                       */
+  uint8_t  *alt_flags;           /* [n_prot][n_vertices]                                                       */
+  uint64_t *cand_mask;           /* [n_prot][n_vertices][n_mask_words] or NULL                                 */
+  uint64_t *node_mask;           /* [n_prot][n_vertices][n_mask_words] or NULL                                 */
+  uint32_t *coverage;            /* [n_prot][HSPF_LFA_COVERAGE_WORDS]                                          */
+} hspf_lfa_out;
+/* Several protected roots may share one table set (whole-network coverage: a 64-root batch in which every root's neighbours
+ * are rows of the batch too).  The per-root tables are staged once, everything is enqueued on the context's stream, and the
+ * call synchronises once at the end (as hspf_ancestors_device).  Argument errors — a NULL required pointer, root_row or a
+ * candidate's nbr_row >= n_rows, root_vertex or a candidate's nbr >= n_vertices, n_slots > 64 * n_mask_words — return
+ * HSPF_E_INVAL with a text in hspf_last_error before anything is launched. */
+int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                    const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                    const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev);
+
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root
  * wavefront batches are dealt to the ranks (hspf_shard_bounds), every rank runs its slice, and ONE all-gather per

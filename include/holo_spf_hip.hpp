@@ -69,6 +69,51 @@ struct PackedTables {
   uint64_t mask(uint32_t r, uint32_t v) const { return hspf_packed_mask(&layout, word(r, v)); }
 };
 
+// Device memory from hspf_device_alloc (tables that stay in HBM between calls), freed with the object.
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  DeviceBuffer(hspf_ctx *ctx, size_t bytes) : ctx_(ctx), bytes_(bytes) {
+    const int rc = hspf_device_alloc(ctx, bytes ? bytes : 8, &p_);
+    if (rc != HSPF_OK) throw Error(rc, "hspf_device_alloc");
+  }
+  DeviceBuffer(DeviceBuffer &&o) noexcept : ctx_(o.ctx_), p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+  DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { if (this != &o) { reset(); ctx_ = o.ctx_; p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; } return *this; }
+  DeviceBuffer(const DeviceBuffer &) = delete;
+  DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+  ~DeviceBuffer() { reset(); }
+  void reset() { if (p_) hspf_device_free(ctx_, p_); p_ = nullptr; bytes_ = 0; }
+  template <typename T> T *as() const { return static_cast<T *>(p_); }
+  size_t size() const { return bytes_; }
+  template <typename T> std::vector<T> to_host(size_t count) const {
+    std::vector<T> v(count);
+    const int rc = count ? hspf_device_to_host(ctx_, v.data(), p_, count * sizeof(T)) : HSPF_OK;
+    if (rc != HSPF_OK) throw Error(rc, "hspf_device_to_host");
+    return v;
+  }
+ private:
+  hspf_ctx *ctx_ = nullptr;
+  void *p_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// Loop-free alternates (hspf_lfa_candidates / hspf_lfa_device): the candidate table of one root, one entry per first-hop
+// slot, and the per-destination results of one protected root on the host.
+struct LfaCandidates {
+  uint32_t root = 0, total_slots = 0;
+  std::vector<uint32_t> nbr, cost, root_link;
+  std::vector<uint8_t> cflags;
+};
+struct Lfa {
+  uint32_t n_vertices = 0, mask_words = 1;
+  LfaCandidates candidates;
+  std::vector<uint32_t> roots;                  // the SPF roots of the run behind it: [root] ++ its distinct neighbour routers
+  std::vector<uint32_t> alt_slot, alt_metric;   // [n_vertices]
+  std::vector<uint8_t> alt_flags;               // [n_vertices] HSPF_LFA_*
+  std::vector<uint64_t> cand_mask, node_mask;   // [n_vertices][mask_words]
+  uint32_t coverage[HSPF_LFA_COVERAGE_WORDS] = {};
+};
+
 class Engine;
 
 // The engine context, shared by the Engine and every Graph made from it: a Graph that outlives its Engine (members
@@ -230,6 +275,64 @@ class Engine {
     if (total > cap && (rc = hspf_routes_events_rest(ctx_, cap, total - cap, records.data() + (size_t)cap * stride)) != HSPF_OK)
       throw Error(rc, std::string("hspf_routes_events_rest (") + hspf_last_error(ctx_) + ")");
     return total;
+  }
+  // Loop-free alternates (RFC 5286).  lfa_candidates: host arithmetic on the caller's CSR, no device.
+  static LfaCandidates lfa_candidates(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                                      const std::vector<uint8_t> &vflags, uint32_t root) {
+    hspf_csr csr{(uint32_t)vflags.size(), (uint32_t)col.size(), row_ptr.data(), col.data(), metric.data(), vflags.data(), 0xFFFFFFFFu};
+    LfaCandidates c;
+    c.root = root;
+    const int k = hspf_lfa_candidates(&csr, root, 0, nullptr, nullptr, nullptr, nullptr, &c.total_slots);
+    if (k < 0) throw Error(k, "hspf_lfa_candidates");
+    c.nbr.resize(k); c.cost.resize(k); c.root_link.resize(k); c.cflags.resize(k);
+    hspf_lfa_candidates(&csr, root, (uint32_t)k, c.nbr.data(), c.cost.data(), c.root_link.data(), c.cflags.data(), nullptr);
+    return c;
+  }
+  // hspf_lfa_device on DEVICE tables of a previous run (several protected roots may share them).
+  void lfa_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                  const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, hspf_lfa_out out_dev) {
+    const int rc = hspf_lfa_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                   lfa_flags, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // One root start to finish: candidates, ONE run for [root] ++ its distinct neighbour routers with the tables left in HBM,
+  // the alternates evaluated there, the five arrays and the coverage on the host.  The four vectors must be the CSR `g` was
+  // uploaded from (and patched to): the candidate table comes from them, the SPTs from `g`.  Only the vertex count can be
+  // checked here (HSPF_E_INVAL); rows that differ give alternates of a graph that does not exist.
+  Lfa lfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+          const std::vector<uint8_t> &vflags, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0) {
+    if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
+      throw Error(HSPF_E_INVAL, "Engine::lfa: the CSR is not the one the graph was uploaded from");
+    Lfa r;
+    r.candidates = lfa_candidates(row_ptr, col, metric, vflags, root);
+    const LfaCandidates &c = r.candidates;
+    std::vector<uint32_t> nbrs;
+    for (uint32_t v : c.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
+    std::sort(nbrs.begin(), nbrs.end());
+    nbrs.erase(std::unique(nbrs.begin(), nbrs.end()), nbrs.end());
+    r.roots.push_back(root);
+    r.roots.insert(r.roots.end(), nbrs.begin(), nbrs.end());
+    std::vector<uint32_t> nbr_row(c.nbr.size(), 0u);
+    for (size_t k = 0; k < c.nbr.size(); ++k)
+      if (c.nbr[k] != HSPF_NO_ROOT) nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), c.nbr[k]) - nbrs.begin());
+    const uint32_t n = g.n_vertices(), R = (uint32_t)r.roots.size();
+    const uint32_t W = std::max(mask_words(g, r.roots), ((uint32_t)c.nbr.size() + 63u) / 64u);
+    r.n_vertices = n; r.mask_words = W;
+    const size_t rn = (size_t)R * n;
+    DeviceBuffer dist(ctx_, rn * 4), flags(ctx_, rn * 2), mask(ctx_, rn * 8 * W);
+    DeviceBuffer slot(ctx_, (size_t)n * 4), met(ctx_, (size_t)n * 4), fl(ctx_, n), cm(ctx_, (size_t)n * 8 * W), nm(ctx_, (size_t)n * 8 * W),
+        cov(ctx_, HSPF_LFA_COVERAGE_WORDS * 4);
+    hspf_result out{dist.as<uint32_t>(), nullptr, flags.as<uint16_t>(), mask.as<uint64_t>(), W, nullptr};
+    const int rc = hspf_run_device(ctx_, g.raw(), r.roots.data(), R, run_flags, &out);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device (") + hspf_last_error(ctx_) + ")");
+    const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
+    lfa_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags,
+               hspf_lfa_out{slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), cm.as<uint64_t>(), nm.as<uint64_t>(), cov.as<uint32_t>()});
+    r.alt_slot = slot.to_host<uint32_t>(n); r.alt_metric = met.to_host<uint32_t>(n); r.alt_flags = fl.to_host<uint8_t>(n);
+    r.cand_mask = cm.to_host<uint64_t>((size_t)n * W); r.node_mask = nm.to_host<uint64_t>((size_t)n * W);
+    const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
+    std::copy(cv.begin(), cv.end(), r.coverage);
+    return r;
   }
   void wait_all() { (void)hspf_wait_all(ctx_); }
   uint32_t async_lanes() const { return hspf_async_lanes(ctx_); }

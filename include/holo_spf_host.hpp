@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -97,9 +98,27 @@ struct RouteEvents {
   const uint32_t *new_mask(size_t k) const { return rec(k) + HSPF_EVENT_REC_WORDS; }                       // 2 * mask_words words, low half first
   const uint32_t *old_mask(size_t k) const { return rec(k) + HSPF_EVENT_REC_WORDS + 2u * mask_words; }
 };
+// Loop-free alternates (hspf_lfa_device) of protected roots whose SPTs — and their neighbour routers' — are rows of one
+// DeviceRun: what the caller passes per protected root, and what comes back on the host.  supported == false: the engine has
+// no such call (the caller evaluates RFC 5286's inequalities on host_tables() itself).
+struct LfaProtect {
+  uint32_t root_vertex = 0, root_row = 0;
+  std::vector<uint32_t> nbr, nbr_row, cost, root_link;      // one entry per first-hop slot (hspf_lfa_candidates)
+  std::vector<uint8_t> cflags;
+};
+struct LfaOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_vertices = 0, mask_words = 1;
+  std::vector<uint32_t> alt_slot, alt_metric;               // [n_protected][n_vertices]
+  std::vector<uint8_t> alt_flags;
+  std::vector<uint64_t> cand_mask, node_mask;               // [n_protected][n_vertices][mask_words] (empty without with_masks)
+  std::vector<uint32_t> coverage;                           // [n_protected][HSPF_LFA_COVERAGE_WORDS]
+};
 class Engine {
  public:
   virtual ~Engine() = default;
+  // The default: not supported (LfaOut::supported == false).
+  virtual LfaOut lfa(DeviceRun &, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) { return LfaOut{}; }
   virtual std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                         const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
                                         uint32_t max_path_metric) = 0;
@@ -628,6 +647,37 @@ class HipEngine : public Engine {
       if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_routes_pack (old set): ") + hspf_last_error(ctx_));
     }
     return out;
+  }
+  LfaOut lfa(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, bool with_masks) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    LfaOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.mask_words = r.mask_words;
+    if (protect.empty()) return o;
+    std::vector<hspf_lfa_protect> ps;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("lfa: the slot arrays of a protected root differ in length");
+      ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, mb = with_masks ? pn * 8 * o.mask_words : 0, cb = (size_t)o.n_protected * HSPF_LFA_COVERAGE_WORDS * 4;
+    uint32_t *slot = (uint32_t *)pool_->dev(pn * 4), *met = (uint32_t *)pool_->dev(pn * 4), *cov = (uint32_t *)pool_->dev(cb);
+    uint8_t *fl = (uint8_t *)pool_->dev(pn);
+    uint64_t *cm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr, *nm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr;
+    hspf_lfa_out out{slot, met, fl, cm, nm, cov};
+    const int rc = hspf_lfa_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, &out);
+    o.alt_slot.resize(pn); o.alt_metric.resize(pn); o.alt_flags.resize(pn); o.coverage.resize((size_t)o.n_protected * HSPF_LFA_COVERAGE_WORDS);
+    if (with_masks) { o.cand_mask.resize(pn * o.mask_words); o.node_mask.resize(pn * o.mask_words); }
+    const bool ok = rc == HSPF_OK && hipMemcpy(o.alt_slot.data(), slot, pn * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(o.alt_metric.data(), met, pn * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(o.alt_flags.data(), fl, pn, hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(o.coverage.data(), cov, cb, hipMemcpyDeviceToHost) == hipSuccess &&
+                    (!with_masks || (hipMemcpy(o.cand_mask.data(), cm, mb, hipMemcpyDeviceToHost) == hipSuccess &&
+                                     hipMemcpy(o.node_mask.data(), nm, mb, hipMemcpyDeviceToHost) == hipSuccess));
+    pool_->dev_free(slot, pn * 4); pool_->dev_free(met, pn * 4); pool_->dev_free(cov, cb); pool_->dev_free(fl, pn);
+    if (with_masks) { pool_->dev_free(cm, mb); pool_->dev_free(nm, mb); }
+    if (!ok) throw std::runtime_error(std::string("hspf_lfa_device: ") + hspf_last_error(ctx_));
+    return o;
   }
   RouteEvents routes_events(DeviceRoutes &old_set, DeviceRoutes &new_set, bool with_silent) override {
     auto &a = static_cast<HipDeviceRoutes &>(old_set);

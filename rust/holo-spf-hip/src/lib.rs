@@ -233,6 +233,39 @@ impl<'e> Tables<'e> {
     }
 }
 
+/// The candidate table of one root (`hspf_lfa_candidates`): one entry per first-hop slot.
+pub struct LfaCandidates {
+    pub root: u32,
+    pub nbr: Vec<u32>,
+    pub cost: Vec<u32>,
+    pub root_link: Vec<u32>,
+    pub cflags: Vec<u8>,
+}
+
+/// Loop-free alternates of the protected roots of one `Engine::lfa_device` call, row-major `[protected root][vertex]`.
+pub struct Lfa {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub words: u32,
+    pub alt_slot: Vec<u32>,
+    pub alt_metric: Vec<u32>,
+    pub alt_flags: Vec<u8>,
+    pub cand_mask: Vec<u64>,
+    pub node_mask: Vec<u64>,
+    pub coverage: Vec<u32>,
+}
+
+impl Lfa {
+    /// The chosen alternate of (protected root `i`, destination `v`): (slot, metric), `None` when there is none.
+    pub fn alternate(&self, i: usize, v: u32) -> Option<(u32, u32)> {
+        let k = i * self.n_vertices as usize + v as usize;
+        (self.alt_slot[k] != sys::HSPF_LFA_NO_SLOT).then(|| (self.alt_slot[k], self.alt_metric[k]))
+    }
+    pub fn node_protecting(&self, i: usize, v: u32) -> bool {
+        self.alt_flags[i * self.n_vertices as usize + v as usize] as u32 & sys::HSPF_LFA_NODE_PROTECT != 0
+    }
+}
+
 /// `hspf_run_device` results left in HBM: input of `routes_device` / `ancestors_device`.
 pub struct DeviceTables<'e> {
     pub n_roots: u32,
@@ -447,6 +480,102 @@ impl Engine {
                 None
             }
         }
+    }
+
+    /// `hspf_lfa_candidates`: the candidate table of `root`, one entry per first-hop slot — pure host arithmetic on the CSR
+    /// (no device).  `nbr[k] == HSPF_NO_ROOT`: slot k is no candidate (network target, the root itself, one-way link).
+    pub fn lfa_candidates(csr: &Csr, root: u32) -> Result<LfaCandidates, Error> {
+        let c = sys::hspf_csr {
+            n_vertices: csr.n_vertices(),
+            n_edges: csr.col.len() as u32,
+            row_ptr: csr.row_ptr.as_ptr(),
+            col: csr.col.as_ptr(),
+            metric: csr.metric.as_ptr(),
+            vflags: csr.vflags.as_ptr(),
+            max_path_metric: csr.max_path_metric,
+        };
+        let mut total = 0u32;
+        let k = unsafe { sys::hspf_lfa_candidates(&c, root, 0, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), &mut total) };
+        if k < 0 {
+            return Err(Error { code: k, detail: "hspf_lfa_candidates".into() });
+        }
+        let k = k as usize;
+        let mut out = LfaCandidates { root, nbr: vec![0; k], cost: vec![0; k], root_link: vec![0; k], cflags: vec![0; k] };
+        let rc = unsafe {
+            sys::hspf_lfa_candidates(&c, root, k as u32, out.nbr.as_mut_ptr(), out.cost.as_mut_ptr(), out.root_link.as_mut_ptr(), out.cflags.as_mut_ptr(), &mut total)
+        };
+        if rc < 0 {
+            return Err(Error { code: rc, detail: "hspf_lfa_candidates".into() });
+        }
+        Ok(out)
+    }
+
+    /// `hspf_lfa_device`: loop-free alternates (RFC 5286) of every protected root from the rows of `tables` (a previous
+    /// `run_device` whose roots hold each protected root and its neighbour routers).  `protect[i]` = (row of the root's SPT,
+    /// its candidate table, `nbr_row[k]` = row of the SPT rooted at `nbr[k]`).  The results come back on the host; the SPT
+    /// tables never leave the device.
+    pub fn lfa_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
+        let (n, w, np) = (tables.n_vertices as usize, tables.words as usize, protect.len());
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "lfa_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let cells = np * n;
+        let slot = self.device_alloc(cells * 4)?;
+        let metric = self.device_alloc(cells * 4)?;
+        let flags = self.device_alloc(cells)?;
+        let cov = self.device_alloc(np * sys::HSPF_LFA_COVERAGE_WORDS as usize * 4)?;
+        let masks = if with_masks { Some((self.device_alloc(cells * w * 8)?, self.device_alloc(cells * w * 8)?)) } else { None };
+        let mut out = sys::hspf_lfa_out {
+            alt_slot: slot.p as *mut u32,
+            alt_metric: metric.p as *mut u32,
+            alt_flags: flags.p as *mut u8,
+            cand_mask: masks.as_ref().map_or(ptr::null_mut(), |m| m.0.p as *mut u64),
+            node_mask: masks.as_ref().map_or(ptr::null_mut(), |m| m.1.p as *mut u64),
+            coverage: cov.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_lfa_device(
+                self.ctx,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(Lfa {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            words: tables.words,
+            alt_slot: slot.to_host(cells)?,
+            alt_metric: metric.to_host(cells)?,
+            alt_flags: flags.to_host(cells)?,
+            cand_mask: match &masks { Some(m) => m.0.to_host(cells * w)?, None => Vec::new() },
+            node_mask: match &masks { Some(m) => m.1.to_host(cells * w)?, None => Vec::new() },
+            coverage: cov.to_host(np * sys::HSPF_LFA_COVERAGE_WORDS as usize)?,
+        })
     }
 
     /// `true`: these runs are too small to pay for a launch — keep the CPU loop (hspf_recommend_cpu).
