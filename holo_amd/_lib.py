@@ -83,6 +83,12 @@ class HspfLfaOut(ctypes.Structure):
                 ("cand_mask", ctypes.c_void_p), ("node_mask", ctypes.c_void_p), ("coverage", ctypes.c_void_p)]
 
 
+class HspfRlfaOut(ctypes.Structure):
+    _fields_ = [("pq_node", ctypes.c_void_p), ("pq_via", ctypes.c_void_p), ("pq_metric", ctypes.c_void_p), ("pq_counts", ctypes.c_void_p),
+                ("space_flags", ctypes.c_void_p), ("space_via", ctypes.c_void_p), ("rl_node", ctypes.c_void_p), ("rl_via", ctypes.c_void_p),
+                ("rl_coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -160,6 +166,11 @@ SYMBOLS = [
     ("hspf_lfa_candidates", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u8p, u32p]),
     ("hspf_lfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfLfaOut)]),
+    # remote loop-free alternates
+    ("hspf_csr_transpose", ctypes.c_int, [ctypes.POINTER(HspfCsr), u32p, u32p, u32p]),
+    ("hspf_rlfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(HspfRlfaOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libholo_spf_hip.so")
 SOURCES = ["spf_capi.hip", "hub_sort.hip"]
-DEPS = ["spf_capi.hip", "spf_kernels.hip.h", "spf_repair.hip.h", "spf_lfa.hip.h", "graph_build.hip.h", "spf_multi.hip.h", "hub_sort.hip", "hub_sort.h", os.path.join("..", "..", "include", "holo_spf_hip.h")]
+DEPS = ["spf_capi.hip", "spf_kernels.hip.h", "spf_repair.hip.h", "spf_lfa.hip.h", "spf_rlfa.hip.h", "graph_build.hip.h", "spf_multi.hip.h", "hub_sort.hip", "hub_sort.h", os.path.join("..", "..", "include", "holo_spf_hip.h")]
 
 
 def hipcc_path() -> str:
@@ -58,6 +58,15 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
         os.remove(obj)
     os.replace(LIB + ".tmp", LIB)
     return LIB
+
+
+def build_driver(name: str) -> str:
+    """Compiles tests/cpp/<name>.cpp — a caller of the C ABI through include/*.hpp — against the in-tree library."""
+    root = os.path.dirname(HERE)
+    out = os.path.join(root, "tests", "cpp", name)
+    subprocess.check_call([hipcc_path(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-pthread", "-w", "-I" + os.path.join(root, "include"),
+                           out + ".cpp", "-L" + HERE, "-lholo_spf_hip", "-Wl,-rpath,$ORIGIN/../../holo_amd", "-ldl", "-o", out])
+    return out
 
 
 if __name__ == "__main__":

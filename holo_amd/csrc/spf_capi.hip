@@ -13,6 +13,7 @@
 #include "graph_patch.hip.h"
 #include "hub_sort.h"
 #include "spf_lfa.hip.h"
+#include "spf_rlfa.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -217,6 +218,7 @@ struct hspf_ctx {
   uint32_t last_diff_count = 0;                     // changed pairs of the last hspf_routes_diff_device (hspf_routes_diff_count)
   // hspf_routes_events: action bytes + tile offsets + total | the record stream's staging (grown from what calls needed)
   DevBuf evs_scr, evs_rec;
+  DevBuf rlfa_key;                                   // hspf_rlfa_device: the selection keys, one u64 per (protected root, slot)
   DevBuf lfa_tab, lfa_scal;                          // hspf_lfa_device: the staged per-root slot tables | d(N, S) and d(N, N') of every protected root
   uint32_t *h_ev = nullptr;                          // pinned: the event total, stored by k_events_scan itself
   struct EvState {                                   // the last hspf_routes_events, for hspf_routes_events_rest
@@ -863,7 +865,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->rlfa_key})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -3822,6 +3824,56 @@ int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32
   });
 }
 
+// What hspf_lfa_device and hspf_rlfa_device share: the checks of the protected roots, and the staged block — headers, then per root
+// nbr | row | cost | root_link | cflags | candidate list (K words each) — copied to ctx->lfa_tab on the context's stream, with
+// ctx->lfa_scal sized for k_lfa_gather.  `fn` names the caller in hspf_last_error.
+static int lfa_stage(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const hspf_lfa_protect *prot,
+                     uint32_t n_prot, std::vector<uint32_t> &tab, uint32_t *out_max_k) {
+  auto bad = [&](const std::string &what) { ctx->last_error = std::string(fn) + ": " + what; return HSPF_E_INVAL; };
+  size_t tab_words = (size_t)n_prot * LFA_HDR_WORDS, scal_words = 0;
+  uint32_t max_k = 0;
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const hspf_lfa_protect &p = prot[i];
+    const std::string who = "protected root " + std::to_string(i) + ": ";
+    if (p.root_row >= n_rows) return bad(who + "root_row >= n_rows");
+    if (p.root_vertex >= n_vertices) return bad(who + "root_vertex >= n_vertices");
+    if (p.n_slots > 64ull * n_mask_words) return bad(who + "n_slots > 64 * n_mask_words");
+    if (p.n_slots && (!p.nbr || !p.nbr_row || !p.cost || !p.root_link || !p.cflags)) return bad(who + "NULL slot array");
+    for (uint32_t k = 0; k < p.n_slots; ++k) {
+      if (p.nbr[k] == HSPF_NO_ROOT) continue;
+      if (p.nbr[k] >= n_vertices) return bad(who + "nbr of slot " + std::to_string(k) + " >= n_vertices");
+      if (p.nbr_row[k] >= n_rows) return bad(who + "nbr_row of slot " + std::to_string(k) + " >= n_rows");
+    }
+    tab_words += (size_t)6 * p.n_slots;
+    scal_words += (size_t)p.n_slots * ((size_t)p.n_slots + 1);
+    max_k = std::max(max_k, p.n_slots);
+  }
+  if (tab_words > (1u << 28) || scal_words > (1u << 28)) { ctx->last_error = std::string(fn) + ": the slot tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
+  tab.assign(tab_words, 0u);
+  size_t to = (size_t)n_prot * LFA_HDR_WORDS, so = 0;
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const hspf_lfa_protect &p = prot[i];
+    const uint32_t K = p.n_slots;
+    uint32_t *h = tab.data() + (size_t)i * LFA_HDR_WORDS, *t = tab.data() + to;
+    uint32_t C = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+      const bool c = p.nbr[k] != HSPF_NO_ROOT;
+      t[k] = p.nbr[k]; t[K + k] = c ? p.nbr_row[k] : 0u; t[2 * K + k] = p.cost[k]; t[3 * K + k] = p.root_link[k];
+      t[4 * K + k] = c ? p.cflags[k] : 0u;
+      if (c) t[5 * K + C++] = k;
+    }
+    h[0] = p.root_vertex; h[1] = p.root_row; h[2] = K; h[3] = C; h[4] = (uint32_t)to; h[5] = (uint32_t)so;
+    to += (size_t)6 * K; so += (size_t)K * ((size_t)K + 1);
+  }
+  (void)hipSetDevice(ctx->device);
+  int rc;
+  if ((rc = ensure(ctx, ctx->lfa_tab, tab_words * 4, false))) return rc;
+  if ((rc = ensure(ctx, ctx->lfa_scal, std::max<size_t>(scal_words, 1) * 4, false))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->lfa_tab.p, tab.data(), tab_words * 4, hipMemcpyHostToDevice, ctx->stream));
+  *out_max_k = max_k;
+  return HSPF_OK;
+}
+
 int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
@@ -3831,48 +3883,11 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
     if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
     if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
     if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
-    // the staged block: headers, then per root nbr | row | cost | root_link | cflags | candidate list (K words each)
-    size_t tab_words = (size_t)n_prot * LFA_HDR_WORDS, scal_words = 0;
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
     uint32_t max_k = 0;
-    for (uint32_t i = 0; i < n_prot; ++i) {
-      const hspf_lfa_protect &p = prot[i];
-      const std::string who = "protected root " + std::to_string(i) + ": ";
-      if (p.root_row >= n_rows) return bad(who + "root_row >= n_rows");
-      if (p.root_vertex >= n_vertices) return bad(who + "root_vertex >= n_vertices");
-      if (p.n_slots > 64ull * n_mask_words) return bad(who + "n_slots > 64 * n_mask_words");
-      if (p.n_slots && (!p.nbr || !p.nbr_row || !p.cost || !p.root_link || !p.cflags)) return bad(who + "NULL slot array");
-      for (uint32_t k = 0; k < p.n_slots; ++k) {
-        if (p.nbr[k] == HSPF_NO_ROOT) continue;
-        if (p.nbr[k] >= n_vertices) return bad(who + "nbr of slot " + std::to_string(k) + " >= n_vertices");
-        if (p.nbr_row[k] >= n_rows) return bad(who + "nbr_row of slot " + std::to_string(k) + " >= n_rows");
-      }
-      tab_words += (size_t)6 * p.n_slots;
-      scal_words += (size_t)p.n_slots * ((size_t)p.n_slots + 1);
-      max_k = std::max(max_k, p.n_slots);
-    }
-    if (tab_words > (1u << 28) || scal_words > (1u << 28)) { ctx->last_error = "hspf_lfa_device: the slot tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
-    std::vector<uint32_t> tab(tab_words, 0u);
-    size_t to = (size_t)n_prot * LFA_HDR_WORDS, so = 0;
-    for (uint32_t i = 0; i < n_prot; ++i) {
-      const hspf_lfa_protect &p = prot[i];
-      const uint32_t K = p.n_slots;
-      uint32_t *h = tab.data() + (size_t)i * LFA_HDR_WORDS, *t = tab.data() + to;
-      uint32_t C = 0;
-      for (uint32_t k = 0; k < K; ++k) {
-        const bool c = p.nbr[k] != HSPF_NO_ROOT;
-        t[k] = p.nbr[k]; t[K + k] = c ? p.nbr_row[k] : 0u; t[2 * K + k] = p.cost[k]; t[3 * K + k] = p.root_link[k];
-        t[4 * K + k] = c ? p.cflags[k] : 0u;
-        if (c) t[5 * K + C++] = k;
-      }
-      h[0] = p.root_vertex; h[1] = p.root_row; h[2] = K; h[3] = C; h[4] = (uint32_t)to; h[5] = (uint32_t)so;
-      to += (size_t)6 * K; so += (size_t)K * ((size_t)K + 1);
-    }
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
     int rc;
-    if ((rc = ensure(ctx, ctx->lfa_tab, tab_words * 4, false))) return rc;
-    if ((rc = ensure(ctx, ctx->lfa_scal, std::max<size_t>(scal_words, 1) * 4, false))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->lfa_tab.p, tab.data(), tab_words * 4, hipMemcpyHostToDevice, s));
+    if ((rc = lfa_stage(ctx, "hspf_lfa_device", n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
     HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_COVERAGE_WORDS * 4, s));
     LfaArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
@@ -3891,6 +3906,81 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
     else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { ctx->last_error = std::string("k_lfa: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return HSPF_OK;
+  });
+}
+
+// ---- remote loop-free alternates (include/holo_spf_hip.h "remote loop-free alternates on device"; kernels: spf_rlfa.hip.h) ----
+int hspf_csr_transpose(const hspf_csr *csr, uint32_t *row_ptr_out, uint32_t *col_out, uint32_t *metric_out) {
+  if (!csr || !row_ptr_out) return HSPF_E_INVAL;
+  const uint32_t n = csr->n_vertices, e = csr->n_edges;
+  if (n == 0 || n > (1u << 24) || e > HSPF_MAX_LINKS || !csr->row_ptr || !csr->vflags || (e && (!csr->col || !csr->metric || !col_out || !metric_out))) return HSPF_E_INVAL;
+  if (csr->row_ptr[0] != 0 || csr->row_ptr[n] != e) return HSPF_E_INVAL;
+  for (uint32_t u = 0; u < n; ++u)
+    if (csr->row_ptr[u + 1] < csr->row_ptr[u]) return HSPF_E_INVAL;
+  for (uint32_t k = 0; k < e; ++k)
+    if (csr->col[k] >= n) return HSPF_E_INVAL;
+  // a stable counting sort by target: the links are visited by ascending source, then by position in the source's row
+  for (uint32_t t = 0; t <= n; ++t) row_ptr_out[t] = 0;
+  for (uint32_t k = 0; k < e; ++k) ++row_ptr_out[csr->col[k] + 1];
+  for (uint32_t t = 0; t < n; ++t) row_ptr_out[t + 1] += row_ptr_out[t];
+  for (uint32_t u = 0; u < n; ++u)
+    for (uint32_t k = csr->row_ptr[u]; k < csr->row_ptr[u + 1]; ++k) {
+      const uint32_t o = row_ptr_out[csr->col[k]]++;                 // (row_ptr_out[t] runs from the start of row t to its end ...)
+      col_out[o] = u; metric_out[o] = csr->metric[k];
+    }
+  for (uint32_t t = n; t > 0; --t) row_ptr_out[t] = row_ptr_out[t - 1];      // (... which is the start of row t + 1: shift back)
+  row_ptr_out[0] = 0;
+  return HSPF_OK;
+}
+
+int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                     hspf_rlfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    auto bad = [&](const std::string &what) { ctx->last_error = "hspf_rlfa_device: " + what; return HSPF_E_INVAL; };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
+      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
+    if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
+    if (g->n != n_vertices) return bad("n_vertices is not the graph's");
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    int rc;
+    if ((rc = lfa_stage(ctx, "hspf_rlfa_device", n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    if ((rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * HSPF_RLFA_COUNT_WORDS * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * HSPF_RLFA_COVERAGE_WORDS * 4, s));
+    const uint32_t ign = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
+    if (max_k) {                                        // d(N_k, S) of every protected root: k_lfa_gather's block, as for LFA
+      LfaArgs ga{};
+      ga.n = n_vertices; ga.W = n_mask_words; ga.ignore_overload = ign;
+      ga.dist = dist_dev; ga.flags = flags_dev; ga.mask = mask_dev;
+      ga.tab = (const uint32_t *)ctx->lfa_tab.p; ga.scal = (uint32_t *)ctx->lfa_scal.p;
+      const uint32_t gx = (uint32_t)std::min<size_t>(((size_t)max_k * ((size_t)max_k + 1) + 255) / 256, 1024);
+      hipLaunchKernelGGL(k_lfa_gather, dim3(gx, n_prot), dim3(256), 0, s, ga);
+    }
+    RlfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ign; a.stride = (uint32_t)stride;
+    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
+    a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (const uint32_t *)ctx->lfa_scal.p;
+    a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
+    a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
+    a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
+    a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
+    hipLaunchKernelGGL(k_rlfa, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_rlfa_final, dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
+    hipLaunchKernelGGL(k_rlfa_dest, grid, dim3(256), 0, s, a);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) { ctx->last_error = std::string("k_rlfa: ") + hipGetErrorString(le); return HSPF_E_HIP; }
     HIPCHK(ctx, hipStreamSynchronize(s));
     return HSPF_OK;
   });

@@ -1,0 +1,235 @@
+// spf_rlfa.hip.h — remote loop-free alternates (RFC 7490): the PQ node of every (protected root S, protected slot e) from the
+// forward SPT rows of S and its neighbour routers and the rows of the same roots on the transposed graph (hspf_rlfa_device; the
+// semantics are written down once, in include/holo_spf_hip.h).
+//
+// Shape.  As k_lfa: lane = vertex, 256 consecutive v per workgroup, every row load coalesced; the per-root scalars d(N_k, S) come
+// from k_lfa_gather's scratch block.  The second dimension — the protected slots — is walked in chunks of RLFA_CH candidates:
+//   k_rlfa        per chunk the lane keeps c + d(E_e, v), the P / XP / Q bits and the running release point of its RLFA_CH slots
+//                 in registers; the candidates k are streamed ONCE per chunk — d(N_k, v) is loaded, judged against every slot of
+//                 the chunk and forgotten.  Nothing that scales with K lives in registers.  The counts are wave ballots +
+//                 popcounts, one LDS add per wave and one vector atomic add per workgroup, slot and counter; the selection is a
+//                 wave minimum of the 64-bit key (release metric << 32 | v), one LDS min per wave and one vector 64-bit atomicMin
+//                 per workgroup and slot into a key array the call initialises to all-ones.
+//   k_rlfa_final  one thread per (S, slot): the key becomes pq_node / pq_metric, and the via is recomputed for that one vertex —
+//                 so the per-vertex via table (space_via) can stay optional.
+//   k_rlfa_dest   lane = destination over S's mask row: the PQ node of the one primary slot, and the four coverage counts.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "spf_lfa.hip.h"
+
+namespace {
+
+constexpr uint32_t RLFA_CH = 8;                    // protected slots per chunk
+constexpr uint32_t RLFA_VIA_SELF = 0xFFFFFFFEu;    // HSPF_RLFA_VIA_SELF
+constexpr uint64_t RLFA_NO_KEY = ~0ull;
+
+struct RlfaArgs {
+  uint32_t n, W, ignore_overload, stride;                                  // stride = 64 * W slots per protected root
+  const uint32_t *dist, *rdist; const uint16_t *flags; const uint64_t *mask;   // the two table sets
+  const uint8_t *vf;                                                       // the graph's resident vertex flags
+  const uint32_t *tab, *scal;                                              // as LfaArgs (staged by the call, gathered by k_lfa_gather)
+  const uint8_t *alt_in;                                                   // [n_prot][n] alt_flags of hspf_lfa_device, or NULL
+  unsigned long long *key;                                                 // [n_prot][stride] scratch, all-ones
+  uint32_t *pq_node, *pq_via, *pq_metric, *pq_counts;
+  uint8_t *space_flags; uint32_t *space_via;
+  uint32_t *rl_node, *rl_via, *rl_cov;
+};
+
+__device__ __forceinline__ unsigned long long rlfa_wave_min(unsigned long long x) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const unsigned long long y = __shfl_xor(x, o);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(256) void k_rlfa(RlfaArgs a) {
+  __shared__ uint32_t s_cnt[RLFA_CH * 4];
+  __shared__ unsigned long long s_key[RLFA_CH];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.y;
+  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
+  const uint32_t S = hdr[0], srow = hdr[1], K = hdr[2], C = hdr[3];
+  const uint32_t n = a.n;
+  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K, *rl = nbr + 3 * K, *cf = nbr + 4 * K, *cl = nbr + 5 * K;
+  const uint32_t *dns = a.scal + hdr[5];
+  const uint32_t v = blockIdx.x * LFA_TILE + tid;
+  const bool valid = v < n;
+  const uint32_t vv = valid ? v : 0u;
+  const size_t sv = (size_t)srow * n + vv;
+  const uint32_t dSv = a.dist[sv], rSv = a.rdist[sv];
+  const uint32_t f = a.vf[vv];
+  const bool elig = valid && v != S && (a.flags[sv] & 1u) && dSv != LFA_NONE && !(f & 0x05u) &&      // a router, not NO_EXPAND
+                    (!(f & 0x02u) || a.ignore_overload);
+  const size_t slot0 = (size_t)pi * a.stride;
+  if (tid < RLFA_CH * 4) s_cnt[tid] = 0;
+  if (tid < RLFA_CH) s_key[tid] = RLFA_NO_KEY;
+  __syncthreads();
+  for (uint32_t c0 = 0; c0 < C; c0 += RLFA_CH) {
+    // the chunk: its slots' c + d(E, v), the P and Q bits, the release point so far
+    uint64_t t[RLFA_CH], best[RLFA_CH];
+    uint32_t via[RLFA_CH], rle[RLFA_CH], es[RLFA_CH];
+    uint32_t tm = 0, pm = 0, qm = 0, xm = 0;                                       // bit j: t[j] is finite | P | Q | some XP
+#pragma unroll
+    for (uint32_t j = 0; j < RLFA_CH; ++j) {
+      const bool live = c0 + j < C;
+      const uint32_t e = cl[live ? c0 + j : c0];
+      es[j] = e; rle[j] = rl[e];
+      const size_t ev = (size_t)row[e] * n + vv;
+      const uint32_t c = cost[e], dEv = a.dist[ev], rEv = a.rdist[ev];
+      t[j] = (uint64_t)c + dEv;
+      const bool tok = live && elig && dEv != LFA_NONE;
+      const bool p = tok && (uint64_t)dSv < t[j];
+      const bool q = live && elig && lfa_less(rEv, rSv, c);
+      tm |= (tok ? 1u : 0u) << j; pm |= (p ? 1u : 0u) << j; qm |= (q ? 1u : 0u) << j;
+      best[j] = p ? (uint64_t)dSv : ~0ull;
+      via[j] = p ? RLFA_VIA_SELF : LFA_NONE;
+    }
+    // the via-slots, once per chunk (ascending k: a tie keeps S, then the smaller slot)
+    if (__ballot(tm != 0)) {
+      for (uint32_t ci = 0; ci < C; ++ci) {
+        const uint32_t k = cl[ci];
+        if ((cf[k] & 1u) && !a.ignore_overload) continue;                          // an overloaded neighbour carries no transit traffic
+        const uint32_t dNS = dns[k];
+        if (dNS == LFA_NONE) continue;
+        const uint32_t dNv = a.dist[(size_t)row[k] * n + vv], rlk = rl[k];
+        const uint64_t rel = (uint64_t)cost[k] + dNv;
+        const uint32_t okm = dNv != LFA_NONE ? tm : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < RLFA_CH; ++j) {
+          if (((okm >> j) & 1u) && rlk != rle[j] && (uint64_t)dNv < (uint64_t)dNS + t[j]) {
+            xm |= 1u << j;
+            if (rel < best[j]) { best[j] = rel; via[j] = k; }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < RLFA_CH; ++j) {
+      if (c0 + j >= C) break;
+      const bool p = (pm >> j) & 1u, x = (xm >> j) & 1u, q = (qm >> j) & 1u;
+      const bool ext = p || x, pq = ext && q;
+      const uint32_t c_p = (uint32_t)__popcll(__ballot(p)), c_x = (uint32_t)__popcll(__ballot(ext)), c_q = (uint32_t)__popcll(__ballot(q));
+      const unsigned long long b_pq = __ballot(pq);
+      if (lane == 0) {
+        if (c_p) atomicAdd(&s_cnt[j * 4 + 0], c_p);
+        if (c_x) atomicAdd(&s_cnt[j * 4 + 1], c_x);
+        if (c_q) atomicAdd(&s_cnt[j * 4 + 2], c_q);
+        if (b_pq) atomicAdd(&s_cnt[j * 4 + 3], (uint32_t)__popcll(b_pq));
+      }
+      if (b_pq) {
+        const uint64_t sat = best[j] > 0xFFFFFFFEull ? 0xFFFFFFFEull : best[j];
+        const unsigned long long key = rlfa_wave_min(pq ? (unsigned long long)((sat << 32) | v) : RLFA_NO_KEY);
+        if (lane == 0) atomicMin(&s_key[j], key);
+      }
+      if (valid) {
+        const size_t o = (slot0 + es[j]) * n + v;
+        if (a.space_flags) a.space_flags[o] = (uint8_t)((p ? 1u : 0u) | (x ? 2u : 0u) | (q ? 4u : 0u) | (elig ? 8u : 0u));
+        if (a.space_via) a.space_via[o] = via[j];
+      }
+    }
+    __syncthreads();
+    // one vector atomic per workgroup, slot and counter; the owner of an LDS cell resets it for the next chunk
+    if (tid < RLFA_CH * 4) {
+      const uint32_t j = tid >> 2, cnt = s_cnt[tid];
+      if (cnt) { atomicAdd(a.pq_counts + (slot0 + cl[c0 + j]) * 4 + (tid & 3u), cnt); s_cnt[tid] = 0; }      // cnt != 0: slot j of the chunk exists
+    }
+    if (tid < RLFA_CH) {
+      const unsigned long long key = s_key[tid];
+      if (key != RLFA_NO_KEY) { atomicMin(a.key + slot0 + cl[c0 + tid], key); s_key[tid] = RLFA_NO_KEY; }
+    }
+    __syncthreads();
+  }
+  // the optional tables of the slots that are no candidates: "none"
+  if (valid && (a.space_flags || a.space_via)) {
+    for (uint32_t e = 0; e < a.stride; ++e) {
+      if (e < K && nbr[e] != LFA_NONE) continue;
+      const size_t o = (slot0 + e) * n + v;
+      if (a.space_flags) a.space_flags[o] = 0;
+      if (a.space_via) a.space_via[o] = LFA_NONE;
+    }
+  }
+}
+
+// one thread per (protected root, slot): key -> pq_node / pq_metric, and the via of that one vertex again
+__global__ __launch_bounds__(256) void k_rlfa_final(RlfaArgs a, uint32_t n_prot) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n_prot * a.stride) return;
+  const uint32_t pi = i / a.stride, e = i - pi * a.stride;
+  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
+  const uint32_t srow = hdr[1], K = hdr[2], C = hdr[3], n = a.n;
+  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K, *rl = nbr + 3 * K, *cf = nbr + 4 * K, *cl = nbr + 5 * K;
+  const uint32_t *dns = a.scal + hdr[5];
+  uint32_t node = LFA_NONE, via = LFA_NONE, met = 0;
+  const unsigned long long key = a.key[i];
+  if (e < K && nbr[e] != LFA_NONE && key != RLFA_NO_KEY) {
+    node = (uint32_t)key; met = (uint32_t)(key >> 32);
+    const uint32_t dSv = a.dist[(size_t)srow * n + node], dEv = a.dist[(size_t)row[e] * n + node];
+    if (dEv != LFA_NONE) {                                                         // (a PQ node has a P or an XP: d(E, v) is finite)
+      const uint64_t t = (uint64_t)cost[e] + dEv;
+      uint64_t best = ~0ull;
+      if (dSv != LFA_NONE && (uint64_t)dSv < t) { best = dSv; via = RLFA_VIA_SELF; }
+      for (uint32_t ci = 0; ci < C; ++ci) {
+        const uint32_t k = cl[ci];
+        if ((cf[k] & 1u) && !a.ignore_overload) continue;
+        const uint32_t dNS = dns[k], dNv = a.dist[(size_t)row[k] * n + node];
+        if (dNS == LFA_NONE || dNv == LFA_NONE || rl[k] == rl[e] || !((uint64_t)dNv < (uint64_t)dNS + t)) continue;
+        const uint64_t rel = (uint64_t)cost[k] + dNv;
+        if (rel < best) { best = rel; via = k; }
+      }
+    }
+  }
+  a.pq_node[i] = node; a.pq_via[i] = via; a.pq_metric[i] = met;
+}
+
+// per destination D of S: the PQ node of its one primary slot, where LFA left it unprotected; the four coverage counts
+__global__ __launch_bounds__(256) void k_rlfa_dest(RlfaArgs a) {
+  __shared__ uint32_t s_cov[4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.y;
+  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
+  const uint32_t S = hdr[0], srow = hdr[1], K = hdr[2];
+  const uint32_t n = a.n, W = a.W, Wk = (K + 63u) >> 6;
+  const uint32_t *nbr = a.tab + hdr[4];
+  if (tid < 4) s_cov[tid] = 0;
+  __syncthreads();
+  const uint64_t last_word = (K & 63u) ? ((1ull << (K & 63u)) - 1ull) : ~0ull;
+  const uint32_t D = blockIdx.x * LFA_TILE + tid;
+  const bool valid = D < n;
+  const size_t sd = (size_t)srow * n + (valid ? D : 0u);
+  const size_t od = (size_t)pi * n + D;
+  const bool in = valid && D != S && (a.flags[sd] & 1u) && a.dist[sd] != LFA_NONE;
+  uint32_t fl = 0, node = LFA_NONE, via = LFA_NONE;
+  if (in) {
+    const uint64_t *pm = a.mask + sd * W;
+    uint32_t np = 0, p0 = 0;
+    for (uint32_t w = 0; w < Wk; ++w) {
+      const uint64_t x = pm[w] & (w + 1 == Wk ? last_word : ~0ull);
+      if (x && !np) p0 = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
+      np += (uint32_t)__popcll(x);
+    }
+    if (np == 1) {
+      fl = 1u;
+      if (a.alt_in && (a.alt_in[od] & 0x04u)) fl |= 2u;                            // HSPF_LFA_LINK_PROTECT: LFA covers it
+      else {
+        const size_t o = (size_t)pi * a.stride + p0;
+        if (nbr[p0] != LFA_NONE && a.pq_node[o] != LFA_NONE) { node = a.pq_node[o]; via = a.pq_via[o]; fl |= 4u; }
+        else fl |= 8u;
+      }
+    }
+  }
+  if (valid) { a.rl_node[od] = node; a.rl_via[od] = via; }
+  uint32_t my_cov = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    const uint32_t c = (uint32_t)__popcll(__ballot((fl >> j) & 1u));
+    if (lane == j) my_cov = c;
+  }
+  if (lane < 4 && my_cov) atomicAdd(&s_cov[lane], my_cov);
+  __syncthreads();
+  if (tid < 4 && s_cov[tid]) atomicAdd(a.rl_cov + (size_t)pi * 4 + tid, s_cov[tid]);
+}
+
+}  // namespace

@@ -40,6 +40,10 @@ LFA_IGNORE_OVERLOAD = 0x01      # HSPF_LFA_IGNORE_OVERLOAD (lfa_device flags)
 LFA_HAS_PRIMARY, LFA_ECMP, LFA_LINK_PROTECT, LFA_NODE_PROTECT, LFA_DOWNSTREAM = 0x01, 0x02, 0x04, 0x08, 0x10
 LFA_NO_SLOT = 0xFFFFFFFF
 LFA_COVERAGE_WORDS = 5
+RLFA_VIA_SELF = 0xFFFFFFFE      # HSPF_RLFA_VIA_SELF: released by the root itself (P-space)
+RLFA_IN_P, RLFA_IN_XP, RLFA_IN_Q, RLFA_ELIGIBLE = 0x01, 0x02, 0x04, 0x08      # space_flags
+RLFA_COUNT_WORDS = 4
+RLFA_COVERAGE_WORDS = 4
 
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
@@ -200,6 +204,35 @@ def lfa_candidates(row_ptr, col, metric, vflags, root: int, cap: Optional[int] =
     return LfaCandidates(int(root), nbr, cost, rl, cf, int(total.value))
 
 
+@dataclass
+class RlfaResult:
+    """Remote loop-free alternates of the protected roots of one rlfa_device() call, on the host (S = 64 * mask words)."""
+    pq_node: np.ndarray      # [P, S] u32, NO_ROOT: none
+    pq_via: np.ndarray       # [P, S] u32, RLFA_VIA_SELF or a slot, LFA_NO_SLOT: none
+    pq_metric: np.ndarray    # [P, S] u32
+    pq_counts: np.ndarray    # [P, S, 4] u32
+    space_flags: Optional[np.ndarray]   # [P, S, N] u8 RLFA_IN_P | RLFA_IN_XP | RLFA_IN_Q | RLFA_ELIGIBLE, or None
+    space_via: Optional[np.ndarray]     # [P, S, N] u32 or None
+    rl_node: np.ndarray      # [P, N] u32
+    rl_via: np.ndarray       # [P, N] u32
+    rl_coverage: np.ndarray  # [P, 4] u32
+
+
+def csr_transpose(row_ptr, col, metric, vflags):
+    """hspf_csr_transpose(): (row_ptr, col, metric) of the reversed graph — pure host arithmetic, no context.  Row t lists the
+    sources of t's incoming links by ascending source, then by position in the source's row.  vflags and max_path_metric are
+    reused unchanged; of a run on the result only `dist` has a meaning (dist[row of X][v] = the distance from v to X)."""
+    lib = L.load()
+    row_ptr = np.ascontiguousarray(row_ptr, np.uint32); col = np.ascontiguousarray(col, np.uint32)
+    metric = np.ascontiguousarray(metric, np.uint32); vflags = np.ascontiguousarray(vflags, np.uint8)
+    csr = L.HspfCsr(len(row_ptr) - 1, len(col), _u32(row_ptr), _u32(col), _u32(metric), vflags.ctypes.data_as(L.u8p), 0xFFFFFFFF)
+    trp, tcol, tmet = np.empty(len(row_ptr), np.uint32), np.empty(len(col), np.uint32), np.empty(len(col), np.uint32)
+    rc = lib.hspf_csr_transpose(ctypes.byref(csr), _u32(trp), _u32(tcol), _u32(tmet))
+    if rc != 0:
+        raise HspfError(rc, "hspf_csr_transpose")
+    return trp, tcol, tmet
+
+
 class SpfGraph:
     """Device-resident graph of one LSDB generation (hspf_graph)."""
 
@@ -214,6 +247,7 @@ class SpfGraph:
         self._pending = []
         self._own_mirrors = False
         self.n = len(self._rp) - 1
+        self.max_path_metric = int(max_path_metric)
         csr = L.HspfCsr(self.n, len(self._col), _u32(self._rp), _u32(self._col), _u32(self._met),
                         self._vf.ctypes.data_as(L.u8p), ctypes.c_uint32(max_path_metric))
         h = ctypes.c_void_p()
@@ -241,6 +275,7 @@ class SpfGraph:
             raise HspfError(rc, "hspf_graph_upload_keyed", ctx.last_error())
         self = cls.__new__(cls)
         self.ctx, self.handle, self.n = ctx, h, len(vk)
+        self.max_path_metric = int(max_path_metric)
         self._pending, self._own_mirrors = [], True
         self._rp, self._col, self._met, self._vf = (self.export(x) for x in ("row_ptr", "col", "metric", "vflags"))
         return self, rank
@@ -657,6 +692,21 @@ class SpfContext:
             raise HspfError(rc, "hspf_routes_events_rest", self.last_error())
         return full
 
+    @staticmethod
+    def _protect_array(protect, who: str):
+        """The hspf_lfa_protect array of a call, and the numpy arrays it points into (to be kept alive for the call)."""
+        arr = (L.HspfLfaProtect * max(len(protect), 1))()
+        keep = []
+        for i, (root_row, c, nbr_row) in enumerate(protect):
+            cols = [np.ascontiguousarray(x, dt) for x, dt in ((c.nbr, np.uint32), (nbr_row, np.uint32), (c.cost, np.uint32),
+                                                             (c.root_link, np.uint32), (c.cflags, np.uint8))]
+            if len({len(x) for x in cols}) != 1:
+                raise ValueError(who + ": the slot arrays of a protected root differ in length")
+            keep.append(cols)
+            arr[i] = L.HspfLfaProtect(int(c.root), int(root_row), len(cols[0]), _u32(cols[0]), _u32(cols[1]), _u32(cols[2]), _u32(cols[3]),
+                                      cols[4].ctypes.data_as(L.u8p))
+        return arr, keep
+
     def lfa_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                    alt_slot_ptr: int, alt_metric_ptr: int, alt_flags_ptr: int, coverage_ptr: int, cand_mask_ptr: int = 0,
                    node_mask_ptr: int = 0, lfa_flags: int = 0) -> None:
@@ -664,16 +714,7 @@ class SpfContext:
         `protect`: a list of (root_row, LfaCandidates, nbr_row) — nbr_row[k] = table row of the SPT rooted at
         candidates.nbr[k] (ignored where the slot is no candidate).  All `*_ptr` are device pointers; cand_mask_ptr /
         node_mask_ptr may be 0."""
-        arr = (L.HspfLfaProtect * max(len(protect), 1))()
-        keep = []
-        for i, (root_row, c, nbr_row) in enumerate(protect):
-            cols = [np.ascontiguousarray(x, dt) for x, dt in ((c.nbr, np.uint32), (nbr_row, np.uint32), (c.cost, np.uint32),
-                                                             (c.root_link, np.uint32), (c.cflags, np.uint8))]
-            if len({len(x) for x in cols}) != 1:
-                raise ValueError("lfa_device: the slot arrays of a protected root differ in length")
-            keep.append(cols)
-            arr[i] = L.HspfLfaProtect(int(c.root), int(root_row), len(cols[0]), _u32(cols[0]), _u32(cols[1]), _u32(cols[2]), _u32(cols[3]),
-                                      cols[4].ctypes.data_as(L.u8p))
+        arr, keep = self._protect_array(protect, "lfa_device")
         out = L.HspfLfaOut(alt_slot_ptr or None, alt_metric_ptr or None, alt_flags_ptr or None, cand_mask_ptr or None, node_mask_ptr or None,
                            coverage_ptr or None)
         rc = self.lib.hspf_lfa_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
@@ -721,6 +762,76 @@ class SpfContext:
                         raise HspfError(rc, "hspf_device_to_host", self.last_error())
             return cand, res
         finally:
+            for p in dev.values():
+                if p:
+                    self.lib.hspf_device_free(self.handle, ctypes.c_void_p(p))
+
+    def rlfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
+                    protect, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int, rl_via_ptr: int,
+                    rl_coverage_ptr: int, space_flags_ptr: int = 0, space_via_ptr: int = 0, alt_flags_in_ptr: int = 0, lfa_flags: int = 0) -> None:
+        """hspf_rlfa_device(): the PQ node of every (protected root, slot) and the remote alternate of every destination with one
+        primary, from the forward table set of a run_device() and `rdist_ptr`, the dist of the same roots on the transposed
+        graph (the forward dist itself on a symmetric-cost graph).  `protect` as for lfa_device(); all `*_ptr` are device
+        pointers, the slot arrays are strided by 64 * mask_words; space_*_ptr / alt_flags_in_ptr may be 0."""
+        arr, keep = self._protect_array(protect, "rlfa_device")
+        out = L.HspfRlfaOut(pq_node_ptr or None, pq_via_ptr or None, pq_metric_ptr or None, pq_counts_ptr or None, space_flags_ptr or None,
+                            space_via_ptr or None, rl_node_ptr or None, rl_via_ptr or None, rl_coverage_ptr or None)
+        rc = self.lib.hspf_rlfa_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                       rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, ctypes.byref(out))
+        del keep
+        if rc != 0:
+            raise HspfError(rc, "hspf_rlfa_device", self.last_error())
+
+    def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False):
+        """Remote alternates of one root, start to finish: the candidate table, run_device() of [root] + its distinct neighbour
+        routers on `graph` and — unless `symmetric` says every link has its reverse at the same cost — on its transpose
+        (csr_transpose, uploaded for the call), lfa_device() then rlfa_device() on those rows, everything on the host.
+        Returns (LfaCandidates, LfaResult without masks, RlfaResult), one row each."""
+        cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
+        nbrs = np.unique(cand.nbr[cand.nbr != NO_ROOT])
+        roots = np.concatenate([[root], nbrs]).astype(np.uint32)
+        nbr_row = np.zeros(cand.n_slots, np.uint32)
+        is_c = cand.nbr != NO_ROOT
+        nbr_row[is_c] = 1 + np.searchsorted(nbrs, cand.nbr[is_c])
+        R, n = len(roots), graph.n
+        W = max(graph.mask_words(roots), (cand.n_slots + 63) // 64)
+        S = 64 * W
+        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cov=((1, LFA_COVERAGE_WORDS), np.uint32),
+                      pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
+                      pq_counts=((1, S, RLFA_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32), rl_via=((1, n), np.uint32),
+                      rl_cov=((1, RLFA_COVERAGE_WORDS), np.uint32))
+        if want_spaces:
+            shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
+        host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
+        sizes.update({k: a.nbytes for k, a in host.items()})
+        dev, GT = {}, None
+        try:
+            for k, b in sizes.items():
+                dev[k] = self._dev_alloc(b) if b else 0
+            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            if not symmetric:
+                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
+                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
+                self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
+            protect = [(0, cand, nbr_row)]
+            self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"],
+                            alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
+            self.rlfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
+                             pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
+                             rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
+                             space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
+                             lfa_flags=lfa_flags)
+            for k, arr in host.items():
+                rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
+                if rc != 0:
+                    raise HspfError(rc, "hspf_device_to_host", self.last_error())
+            lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
+            return cand, lfa, RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
+                                         host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
+        finally:
+            if GT is not None:
+                GT.free()
             for p in dev.values():
                 if p:
                     self.lib.hspf_device_free(self.handle, ctypes.c_void_p(p))

@@ -727,6 +727,87 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev);
 
+/* ---- remote loop-free alternates on device (RFC 7490): PQ nodes per protected link: new symbols, same ABI number --------
+ * hspf_lfa_device counts the destinations that get no alternate and leaves them unrepaired; on rings and sparse meshes that is
+ * most of them.  Remote LFA tunnels to a PQ node: a router that S — or another neighbour of S — reaches without crossing the
+ * protected link (P-space, extended P-space) and that reaches the link's far end E without crossing it either (Q-space).  P and
+ * extended P are inequalities over the forward rows a caller already has for LFA; Q needs distances TO S and TO E: one more
+ * run of the same root list on the transposed graph (hspf_csr_transpose).
+ *
+ * hspf_csr_transpose (host arithmetic, no context): row t of the result lists (source u, cost) of every link u -> t of `csr`,
+ * ordered by ascending u, then by position in u's row (a stable counting sort).  Outputs are the caller's: row_ptr_out[n + 1],
+ * col_out[e], metric_out[e].  vflags and max_path_metric are the caller's to reuse unchanged for the upload.  HSPF_E_INVAL on
+ * what hspf_graph_upload rejects (and on a link target >= n_vertices).  Of a run on the transposed graph ONLY `dist` has a
+ * meaning — dist[row of X][v] = d(v, X), the distance from v TO X: the two-way check, the overload rule ("not expanded unless
+ * root") and prefix pruning are symmetric under reversal, hops and first-hop masks depend on row order and are not.  One
+ * exception: a vertex with HSPF_VF_NO_EXPAND reaches nothing as a root but is reached as a target, so the row of such an X and
+ * the entries of such a v are NOT reverse distances; hspf_rlfa_device excludes such vertices from every set.
+ *
+ * hspf_rlfa_device.  The forward table set (dist, vflags_out, first_hop_mask: [n_rows][n_vertices]), `prot` and lfa_flags are
+ * exactly those of hspf_lfa_device; rdist_dev [n_rows][n_vertices] is `dist` of a run of the SAME root list on the transposed
+ * graph, so root_row / nbr_row index both sets and rdist[row of X][v] = d(v, X).  On a graph whose costs are symmetric
+ * (every link u -> v has its reverse at the same cost) d(v, X) = d(X, v) and the caller may pass the forward dist as rdist_dev;
+ * on any other graph that gives a wrong Q-space.  `g` is the (forward or transposed) uploaded graph: its resident vertex
+ * flags are read.  alt_flags_in_dev: NULL, or the alt_flags [n_prot][n_vertices] hspf_lfa_device wrote for the same `prot`.
+ *
+ * Per protected root S and per slot e with nbr[e] != HSPF_NO_ROOT (a candidate slot; E = nbr[e], c = cost[e]); N_k = nbr[k].
+ * Every sum is evaluated in 64 bits; a term that is HSPF_DIST_INF makes its inequality false.
+ *   eligible(v)   v is in S's SPT, v != S, v carries neither HSPF_VF_NETWORK nor HSPF_VF_NO_EXPAND, and no HSPF_VF_NO_TRANSIT
+ *                 unless the call passes HSPF_LFA_IGNORE_OVERLOAD.  E itself may be eligible (parallel links).
+ *                 Every set below holds eligible vertices only.
+ *   P(e, v)       d(S, v) < c + d(E, v)
+ *   XP(e, k, v)   d(N_k, v) < d(N_k, S) + c + d(E, v)   for a via-slot k: nbr[k] != HSPF_NO_ROOT, root_link[k] != root_link[e],
+ *                 and cflags[k] has no HSPF_LFA_C_NO_TRANSIT unless the call passes HSPF_LFA_IGNORE_OVERLOAD
+ *   Q(e, v)       d(v, E) < d(v, S) + c                 (rdist)
+ *   release point of v: the smallest (64 bits) of d(S, v) if P holds (via = HSPF_RLFA_VIA_SELF) and cost[k] + d(N_k, v) over
+ *                 the k with XP (via = k); on a tie S comes first, then the smaller k.  The release metric is that sum
+ *                 saturated at 0xFFFFFFFE.
+ *   PQ node of (S, e): among the v with (P or some XP) and Q, the smallest release metric, then the smallest vertex index.
+ * Outputs (DEVICE pointers; slots are strided by 64 * n_mask_words per protected root):
+ *   pq_node / pq_via / pq_metric [n_prot][stride]: the PQ node, the via of its release point, its release metric; HSPF_NO_ROOT /
+ *                 HSPF_LFA_NO_SLOT / 0 for "none" — also for slots that are no candidates and for slots >= n_slots.
+ *   pq_counts [n_prot][stride][4]: the number of v in P | in P or some XP | in Q | in (P or some XP) and Q.
+ *   space_flags u8 / space_via u32 [n_prot][stride][n_vertices], optional (NULL skips the table): HSPF_RLFA_IN_P, _IN_XP (some
+ *                 XP), _IN_Q, _ELIGIBLE; the via of v's release point (HSPF_LFA_NO_SLOT: v has none).  0 / HSPF_LFA_NO_SLOT for
+ *                 slots that are no candidates.
+ *   rl_node / rl_via [n_prot][n_vertices], per destination D of S (D != S, in S's SPT): filled for every D with exactly ONE
+ *                 primary slot e — and, when alt_flags_in_dev is given, no HSPF_LFA_LINK_PROTECT — with the PQ node and via of
+ *                 e; HSPF_NO_ROOT / HSPF_LFA_NO_SLOT everywhere else, also where that one slot is no candidate (its target
+ *                 is a network vertex or S) or has no PQ node.
+ *   rl_coverage [n_prot][4], counted on the device: destinations with exactly one primary | of those, the ones whose given
+ *                 alt_flags have HSPF_LFA_LINK_PROTECT (0 when alt_flags_in_dev is NULL) | of the rest, the ones with a PQ
+ *                 node | the ones still uncovered.
+ * Argument errors — a NULL required pointer, n_vertices not the graph's, and everything hspf_lfa_device rejects in `prot` —
+ * return HSPF_E_INVAL with a text in hspf_last_error that names hspf_rlfa_device, before anything is launched.  Everything is
+ * enqueued on the context's stream; the call synchronises once at the end.
+ *
+ * OUT OF SCOPE: node-protecting remote LFA (RFC 8102: the PQ node's path to D may cross E); loop-freeness with respect to a
+ * LAN pseudonode (the same root_link rule and the same limitation as hspf_lfa_device); TI-LFA (segment lists beyond one
+ * tunnel). */
+#define HSPF_RLFA_VIA_SELF       0xFFFFFFFEu   /* pq_via / space_via / rl_via: released by S itself (P-space) */
+#define HSPF_RLFA_IN_P           0x01u         /* space_flags */
+#define HSPF_RLFA_IN_XP          0x02u
+#define HSPF_RLFA_IN_Q           0x04u
+#define HSPF_RLFA_ELIGIBLE       0x08u
+#define HSPF_RLFA_COUNT_WORDS    4u
+#define HSPF_RLFA_COVERAGE_WORDS 4u
+int hspf_csr_transpose(const hspf_csr *csr, uint32_t *row_ptr_out, uint32_t *col_out, uint32_t *metric_out);
+typedef struct {                 /* DEVICE pointers; stride = 64 * n_mask_words                               */
+  uint32_t *pq_node;             /* [n_prot][stride]                                                           */
+  uint32_t *pq_via;              /* [n_prot][stride]                                                           */
+  uint32_t *pq_metric;           /* [n_prot][stride]                                                           */
+  uint32_t *pq_counts;           /* [n_prot][stride][HSPF_RLFA_COUNT_WORDS]                                    */
+  uint8_t  *space_flags;         /* [n_prot][stride][n_vertices] or NULL                                       */
+  uint32_t *space_via;           /* [n_prot][stride][n_vertices] or NULL                                       */
+  uint32_t *rl_node;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *rl_via;              /* [n_prot][n_vertices]                                                       */
+  uint32_t *rl_coverage;         /* [n_prot][HSPF_RLFA_COVERAGE_WORDS]                                         */
+} hspf_rlfa_out;
+int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                     hspf_rlfa_out *out_dev);
+
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root
  * wavefront batches are dealt to the ranks (hspf_shard_bounds), every rank runs its slice, and ONE all-gather per

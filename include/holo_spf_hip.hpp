@@ -114,6 +114,19 @@ struct Lfa {
   uint32_t coverage[HSPF_LFA_COVERAGE_WORDS] = {};
 };
 
+// Remote loop-free alternates (hspf_csr_transpose / hspf_rlfa_device) of one protected root on the host: the LFA result they
+// complete, the PQ node of every slot, the remote alternate of every destination.
+struct Rlfa {
+  Lfa lfa;                                      // (cand_mask / node_mask are not fetched: empty)
+  uint32_t slot_stride = 64;                    // 64 * mask_words
+  std::vector<uint32_t> pq_node, pq_via, pq_metric;   // [slot_stride]
+  std::vector<uint32_t> pq_counts;              // [slot_stride][HSPF_RLFA_COUNT_WORDS]
+  std::vector<uint8_t> space_flags;             // [slot_stride][n_vertices] HSPF_RLFA_IN_* (empty unless asked for)
+  std::vector<uint32_t> space_via;              // [slot_stride][n_vertices]
+  std::vector<uint32_t> rl_node, rl_via;        // [n_vertices]
+  uint32_t rl_coverage[HSPF_RLFA_COVERAGE_WORDS] = {};
+};
+
 class Engine;
 
 // The engine context, shared by the Engine and every Graph made from it: a Graph that outlives its Engine (members
@@ -332,6 +345,83 @@ class Engine {
     r.cand_mask = cm.to_host<uint64_t>((size_t)n * W); r.node_mask = nm.to_host<uint64_t>((size_t)n * W);
     const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
     std::copy(cv.begin(), cv.end(), r.coverage);
+    return r;
+  }
+  // Remote loop-free alternates (RFC 7490).  csr_transpose: host arithmetic, no device; of a run on the result only `dist`
+  // has a meaning (the distance TO the root).
+  struct Transposed { std::vector<uint32_t> row_ptr, col, metric; };
+  static Transposed csr_transpose(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                                  const std::vector<uint8_t> &vflags) {
+    hspf_csr csr{(uint32_t)vflags.size(), (uint32_t)col.size(), row_ptr.data(), col.data(), metric.data(), vflags.data(), 0xFFFFFFFFu};
+    Transposed t;
+    t.row_ptr.resize(vflags.size() + 1); t.col.resize(col.size()); t.metric.resize(col.size());
+    const int rc = hspf_csr_transpose(&csr, t.row_ptr.data(), t.col.data(), t.metric.data());
+    if (rc != HSPF_OK) throw Error(rc, "hspf_csr_transpose");
+    return t;
+  }
+  // hspf_rlfa_device on DEVICE tables: the forward set and rdist_dev, the dist of the same roots on the transposed graph.
+  void rlfa_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                   const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                   hspf_rlfa_out out_dev) {
+    const int rc = hspf_rlfa_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                                    (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // One root start to finish, as lfa(): ONE run of [root] ++ its neighbour routers on `g` and one on the upload of its transpose
+  // (skipped when `symmetric` says every link has its reverse at the same cost), hspf_lfa_device, hspf_rlfa_device, results on
+  // the host.  The four vectors must be the CSR `g` was uploaded from, max_path_metric the one it was uploaded with.
+  Rlfa rlfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+            const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
+            bool symmetric = false, bool with_spaces = false) {
+    if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
+      throw Error(HSPF_E_INVAL, "Engine::rlfa: the CSR is not the one the graph was uploaded from");
+    Rlfa r;
+    r.lfa.candidates = lfa_candidates(row_ptr, col, metric, vflags, root);
+    const LfaCandidates &c = r.lfa.candidates;
+    std::vector<uint32_t> nbrs;
+    for (uint32_t v : c.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
+    std::sort(nbrs.begin(), nbrs.end());
+    nbrs.erase(std::unique(nbrs.begin(), nbrs.end()), nbrs.end());
+    r.lfa.roots.push_back(root);
+    r.lfa.roots.insert(r.lfa.roots.end(), nbrs.begin(), nbrs.end());
+    std::vector<uint32_t> nbr_row(c.nbr.size(), 0u);
+    for (size_t k = 0; k < c.nbr.size(); ++k)
+      if (c.nbr[k] != HSPF_NO_ROOT) nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), c.nbr[k]) - nbrs.begin());
+    const uint32_t n = g.n_vertices(), R = (uint32_t)r.lfa.roots.size();
+    const uint32_t W = std::max(mask_words(g, r.lfa.roots), ((uint32_t)c.nbr.size() + 63u) / 64u), S = 64u * W;
+    r.lfa.n_vertices = n; r.lfa.mask_words = W; r.slot_stride = S;
+    const size_t rn = (size_t)R * n, sn = with_spaces ? (size_t)S * n : 0;
+    DeviceBuffer dist(ctx_, rn * 4), flags(ctx_, rn * 2), mask(ctx_, rn * 8 * W), rdist(ctx_, symmetric ? 0 : rn * 4);
+    DeviceBuffer slot(ctx_, (size_t)n * 4), met(ctx_, (size_t)n * 4), fl(ctx_, n), cov(ctx_, HSPF_LFA_COVERAGE_WORDS * 4);
+    DeviceBuffer pq_node(ctx_, S * 4), pq_via(ctx_, S * 4), pq_metric(ctx_, S * 4), pq_counts(ctx_, (size_t)S * 4 * HSPF_RLFA_COUNT_WORDS),
+        sp_flags(ctx_, sn), sp_via(ctx_, sn * 4), rl_node(ctx_, (size_t)n * 4), rl_via(ctx_, (size_t)n * 4), rl_cov(ctx_, HSPF_RLFA_COVERAGE_WORDS * 4);
+    hspf_result out{dist.as<uint32_t>(), nullptr, flags.as<uint16_t>(), mask.as<uint64_t>(), W, nullptr};
+    int rc = hspf_run_device(ctx_, g.raw(), r.lfa.roots.data(), R, run_flags, &out);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device (") + hspf_last_error(ctx_) + ")");
+    if (!symmetric) {
+      const Transposed t = csr_transpose(row_ptr, col, metric, vflags);
+      Graph gt = upload(t.row_ptr, t.col, t.metric, vflags, max_path_metric);
+      hspf_result rout{rdist.as<uint32_t>(), nullptr, nullptr, nullptr, 1, nullptr};
+      rc = hspf_run_device(ctx_, gt.raw(), r.lfa.roots.data(), R, run_flags, &rout);
+      if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device on the transposed graph (") + hspf_last_error(ctx_) + ")");
+    }
+    const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
+    lfa_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags,
+               hspf_lfa_out{slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), nullptr, nullptr, cov.as<uint32_t>()});
+    rlfa_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(), {p},
+                lfa_flags, fl.as<uint8_t>(),
+                hspf_rlfa_out{pq_node.as<uint32_t>(), pq_via.as<uint32_t>(), pq_metric.as<uint32_t>(), pq_counts.as<uint32_t>(),
+                              with_spaces ? sp_flags.as<uint8_t>() : nullptr, with_spaces ? sp_via.as<uint32_t>() : nullptr, rl_node.as<uint32_t>(),
+                              rl_via.as<uint32_t>(), rl_cov.as<uint32_t>()});
+    r.lfa.alt_slot = slot.to_host<uint32_t>(n); r.lfa.alt_metric = met.to_host<uint32_t>(n); r.lfa.alt_flags = fl.to_host<uint8_t>(n);
+    const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
+    std::copy(cv.begin(), cv.end(), r.lfa.coverage);
+    r.pq_node = pq_node.to_host<uint32_t>(S); r.pq_via = pq_via.to_host<uint32_t>(S); r.pq_metric = pq_metric.to_host<uint32_t>(S);
+    r.pq_counts = pq_counts.to_host<uint32_t>((size_t)S * HSPF_RLFA_COUNT_WORDS);
+    if (with_spaces) { r.space_flags = sp_flags.to_host<uint8_t>(sn); r.space_via = sp_via.to_host<uint32_t>(sn); }
+    r.rl_node = rl_node.to_host<uint32_t>(n); r.rl_via = rl_via.to_host<uint32_t>(n);
+    const std::vector<uint32_t> rc4 = rl_cov.to_host<uint32_t>(HSPF_RLFA_COVERAGE_WORDS);
+    std::copy(rc4.begin(), rc4.end(), r.rl_coverage);
     return r;
   }
   void wait_all() { (void)hspf_wait_all(ctx_); }

@@ -266,6 +266,37 @@ impl Lfa {
     }
 }
 
+/// Remote loop-free alternates (RFC 7490) of the protected roots of one `Engine::rlfa_device` call.  Slots are strided by
+/// `slot_stride` = 64 * mask words per protected root.
+pub struct Rlfa {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub slot_stride: u32,
+    pub pq_node: Vec<u32>,
+    pub pq_via: Vec<u32>,
+    pub pq_metric: Vec<u32>,
+    pub pq_counts: Vec<u32>,
+    pub space_flags: Vec<u8>,
+    pub space_via: Vec<u32>,
+    pub rl_node: Vec<u32>,
+    pub rl_via: Vec<u32>,
+    pub rl_coverage: Vec<u32>,
+}
+
+impl Rlfa {
+    /// The PQ node of (protected root `i`, slot `e`): (node, via, release metric), `None` when there is none.  `via` is a slot
+    /// of the root or `HSPF_RLFA_VIA_SELF`.
+    pub fn pq_node(&self, i: usize, e: u32) -> Option<(u32, u32, u32)> {
+        let k = i * self.slot_stride as usize + e as usize;
+        (self.pq_node[k] != sys::HSPF_NO_ROOT).then(|| (self.pq_node[k], self.pq_via[k], self.pq_metric[k]))
+    }
+    /// The remote alternate of (protected root `i`, destination `v`): (PQ node, via), `None` when there is none.
+    pub fn remote_alternate(&self, i: usize, v: u32) -> Option<(u32, u32)> {
+        let k = i * self.n_vertices as usize + v as usize;
+        (self.rl_node[k] != sys::HSPF_NO_ROOT).then(|| (self.rl_node[k], self.rl_via[k]))
+    }
+}
+
 /// `hspf_run_device` results left in HBM: input of `routes_device` / `ancestors_device`.
 pub struct DeviceTables<'e> {
     pub n_roots: u32,
@@ -575,6 +606,123 @@ impl Engine {
             cand_mask: match &masks { Some(m) => m.0.to_host(cells * w)?, None => Vec::new() },
             node_mask: match &masks { Some(m) => m.1.to_host(cells * w)?, None => Vec::new() },
             coverage: cov.to_host(np * sys::HSPF_LFA_COVERAGE_WORDS as usize)?,
+        })
+    }
+
+    /// `hspf_csr_transpose`: the reversed graph (row t lists the sources of t's incoming links by ascending source, then by
+    /// position in the source's row) with `vflags` and `max_path_metric` reused — pure host arithmetic.  Of a run on it only
+    /// `dist` has a meaning: the distance TO the root.
+    pub fn csr_transpose(csr: &Csr) -> Result<Csr, Error> {
+        let c = sys::hspf_csr {
+            n_vertices: csr.n_vertices(),
+            n_edges: csr.col.len() as u32,
+            row_ptr: csr.row_ptr.as_ptr(),
+            col: csr.col.as_ptr(),
+            metric: csr.metric.as_ptr(),
+            vflags: csr.vflags.as_ptr(),
+            max_path_metric: csr.max_path_metric,
+        };
+        let mut out = Csr {
+            row_ptr: vec![0; csr.row_ptr.len()],
+            col: vec![0; csr.col.len()],
+            metric: vec![0; csr.col.len()],
+            vflags: csr.vflags.clone(),
+            max_path_metric: csr.max_path_metric,
+        };
+        let rc = unsafe { sys::hspf_csr_transpose(&c, out.row_ptr.as_mut_ptr(), out.col.as_mut_ptr(), out.metric.as_mut_ptr()) };
+        if rc != sys::HSPF_OK {
+            return Err(Error { code: rc, detail: "hspf_csr_transpose".into() });
+        }
+        Ok(out)
+    }
+
+    /// `hspf_rlfa_device`: the PQ node of every (protected root, slot) and the remote alternate of every destination with one
+    /// primary.  `tables`: the forward run; `reverse`: the run of the SAME roots on the upload of `csr_transpose` (pass
+    /// `tables` again on a graph whose costs are symmetric); `protect` as for `lfa_device`; `lfa`: what `lfa_device` returned
+    /// for the same `protect`, so that only the destinations it left unprotected get a remote alternate.
+    pub fn rlfa_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
+                       ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
+        let (n, np) = (tables.n_vertices as usize, protect.len());
+        if reverse.n_vertices != tables.n_vertices || reverse.n_roots != tables.n_roots {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_device: the two table sets differ in shape".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let stride = 64 * tables.words as usize;
+        let (slots, cells) = (np * stride, np * n);
+        let pq_node = self.device_alloc(slots * 4)?;
+        let pq_via = self.device_alloc(slots * 4)?;
+        let pq_metric = self.device_alloc(slots * 4)?;
+        let pq_counts = self.device_alloc(slots * sys::HSPF_RLFA_COUNT_WORDS as usize * 4)?;
+        let rl_node = self.device_alloc(cells * 4)?;
+        let rl_via = self.device_alloc(cells * 4)?;
+        let rl_cov = self.device_alloc(np * sys::HSPF_RLFA_COVERAGE_WORDS as usize * 4)?;
+        let spaces = if with_spaces { Some((self.device_alloc(slots * n)?, self.device_alloc(slots * n * 4)?)) } else { None };
+        let alt = match lfa {
+            Some(l) if l.alt_flags.len() == cells => Some(self.device_from(&l.alt_flags)?),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_device: the LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let mut out = sys::hspf_rlfa_out {
+            pq_node: pq_node.p as *mut u32,
+            pq_via: pq_via.p as *mut u32,
+            pq_metric: pq_metric.p as *mut u32,
+            pq_counts: pq_counts.p as *mut u32,
+            space_flags: spaces.as_ref().map_or(ptr::null_mut(), |s| s.0.p as *mut u8),
+            space_via: spaces.as_ref().map_or(ptr::null_mut(), |s| s.1.p as *mut u32),
+            rl_node: rl_node.p as *mut u32,
+            rl_via: rl_via.p as *mut u32,
+            rl_coverage: rl_cov.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_rlfa_device(
+                self.ctx,
+                g.g,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                reverse.dist.p as *const u32,
+                raw.as_ptr(),
+                np as u32,
+                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
+                alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(Rlfa {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            slot_stride: stride as u32,
+            pq_node: pq_node.to_host(slots)?,
+            pq_via: pq_via.to_host(slots)?,
+            pq_metric: pq_metric.to_host(slots)?,
+            pq_counts: pq_counts.to_host(slots * sys::HSPF_RLFA_COUNT_WORDS as usize)?,
+            space_flags: match &spaces { Some(s) => s.0.to_host(slots * n)?, None => Vec::new() },
+            space_via: match &spaces { Some(s) => s.1.to_host(slots * n)?, None => Vec::new() },
+            rl_node: rl_node.to_host(cells)?,
+            rl_via: rl_via.to_host(cells)?,
+            rl_coverage: rl_cov.to_host(np * sys::HSPF_RLFA_COVERAGE_WORDS as usize)?,
         })
     }
 
