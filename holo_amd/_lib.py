@@ -89,6 +89,12 @@ class HspfRlfaOut(ctypes.Structure):
                 ("rl_coverage", ctypes.c_void_p)]
 
 
+class HspfTilfaOut(ctypes.Structure):
+    _fields_ = [("ti_kind", ctypes.c_void_p), ("ti_p", ctypes.c_void_p), ("ti_q", ctypes.c_void_p), ("ti_via", ctypes.c_void_p),
+                ("ti_link", ctypes.c_void_p), ("ti_metric", ctypes.c_void_p), ("ti_counts", ctypes.c_void_p), ("td_kind", ctypes.c_void_p),
+                ("td_coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -171,6 +177,10 @@ SYMBOLS = [
     ("hspf_rlfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(HspfRlfaOut)]),
+    # two-segment repair paths (TI-LFA, link protection)
+    ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfTilfaOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

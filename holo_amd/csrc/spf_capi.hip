@@ -14,6 +14,7 @@
 #include "hub_sort.h"
 #include "spf_lfa.hip.h"
 #include "spf_rlfa.hip.h"
+#include "spf_tilfa.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -219,6 +220,7 @@ struct hspf_ctx {
   // hspf_routes_events: action bytes + tile offsets + total | the record stream's staging (grown from what calls needed)
   DevBuf evs_scr, evs_rec;
   DevBuf rlfa_key;                                   // hspf_rlfa_device: the selection keys, one u64 per (protected root, slot)
+  DevBuf tilfa_key, tilfa_tw;                        // hspf_tilfa_device: its selection keys | the graph's two-way flags, one byte per link
   DevBuf lfa_tab, lfa_scal;                          // hspf_lfa_device: the staged per-root slot tables | d(N, S) and d(N, N') of every protected root
   uint32_t *h_ev = nullptr;                          // pinned: the event total, stored by k_events_scan itself
   struct EvState {                                   // the last hspf_routes_events, for hspf_routes_events_rest
@@ -865,7 +867,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->rlfa_key})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -3981,6 +3983,73 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
     hipLaunchKernelGGL(k_rlfa_dest, grid, dim3(256), 0, s, a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { ctx->last_error = std::string("k_rlfa: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return HSPF_OK;
+  });
+}
+
+// ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----
+int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                      const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  (void)lfa_flags;                                      // (eligibility and the overload rule are in the space tables)
+  return guarded(ctx, [&]() -> int {
+    auto bad = [&](const std::string &what) { ctx->last_error = "hspf_tilfa_device: " + what; return HSPF_E_INVAL; };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!space_flags_dev || !space_via_dev) return bad("NULL space_flags / space_via (the tables of hspf_rlfa_device are required)");
+    if (!out_dev->ti_kind || !out_dev->ti_p || !out_dev->ti_q || !out_dev->ti_via || !out_dev->ti_link || !out_dev->ti_metric || !out_dev->ti_counts ||
+        !out_dev->td_kind || !out_dev->td_coverage)
+      return bad("NULL ti_kind / ti_p / ti_q / ti_via / ti_link / ti_metric / ti_counts / td_kind / td_coverage");
+    if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
+    if (g->invalid) return bad("the graph is invalid after a failed hspf_graph_patch (free it and upload again)");
+    if (g->n != n_vertices) return bad("n_vertices is not the graph's");
+    if (n_vertices > 0x7FFFFFFFu) return bad("n_vertices does not fit the selection key");
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    const uint32_t e = g->e;
+    if (g->twoway.size() != g->col.size()) return bad("the graph holds no two-way flags");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    std::vector<uint8_t> tw;                            // (the same)
+    uint32_t max_k = 0;
+    int rc;
+    if ((rc = lfa_stage(ctx, "hspf_tilfa_device", n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    if ((rc = ensure(ctx, ctx->tilfa_key, n_slots * 8, false))) return rc;
+    if ((rc = ensure(ctx, ctx->tilfa_tw, std::max<size_t>(e, 1), false))) return rc;
+    hipStream_t s = ctx->stream;
+    // the two-way flags in the order of the device's raw CSR: the host mirror's pool is in that order unless a patch moved rows
+    const uint8_t *tw_src = g->twoway.data();
+    if (!g->pool_compact()) {
+      tw.resize(e);
+      size_t o = 0;
+      for (uint32_t v = 0; v < g->n; ++v) {
+        if (o + g->rlen[v] > e) return bad("the graph's host mirror and its link count disagree");
+        if (g->rlen[v]) memcpy(tw.data() + o, g->twoway.data() + g->rstart[v], g->rlen[v]);
+        o += g->rlen[v];
+      }
+      if (o != e) return bad("the graph's host mirror and its link count disagree");
+      tw_src = tw.data();
+    } else if (g->twoway.size() < e) return bad("the graph's host mirror and its link count disagree");
+    if (e) HIPCHK(ctx, hipMemcpyAsync(ctx->tilfa_tw.p, tw_src, e, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->tilfa_key.p, 0xFF, n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->ti_counts, 0, n_slots * HSPF_TILFA_COUNT_WORDS * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->td_coverage, 0, (size_t)n_prot * HSPF_TILFA_COVERAGE_WORDS * 4, s));
+    TilfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.stride = (uint32_t)stride;
+    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev;
+    a.tab = (const uint32_t *)ctx->lfa_tab.p; a.alt_in = alt_flags_in_dev;
+    a.sflags = space_flags_dev; a.svia = space_via_dev;
+    a.row_ptr = g->d_row_ptr[g->cur]; a.col = g->d_col[g->cur]; a.metric = g->d_metric[g->cur]; a.tw = (const uint8_t *)ctx->tilfa_tw.p;
+    a.key = (unsigned long long *)ctx->tilfa_key.p;
+    a.ti_kind = out_dev->ti_kind; a.ti_p = out_dev->ti_p; a.ti_q = out_dev->ti_q; a.ti_via = out_dev->ti_via; a.ti_link = out_dev->ti_link;
+    a.ti_metric = out_dev->ti_metric; a.ti_counts = out_dev->ti_counts; a.td_kind = out_dev->td_kind; a.td_cov = out_dev->td_coverage;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    if (max_k) hipLaunchKernelGGL(k_tilfa, dim3(n_tiles, std::min(max_k, 65535u), n_prot), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_tilfa_final, dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
+    hipLaunchKernelGGL(k_tilfa_dest, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) { ctx->last_error = std::string("k_tilfa: ") + hipGetErrorString(le); return HSPF_E_HIP; }
     HIPCHK(ctx, hipStreamSynchronize(s));
     return HSPF_OK;
   });

@@ -44,6 +44,10 @@ RLFA_VIA_SELF = 0xFFFFFFFE      # HSPF_RLFA_VIA_SELF: released by the root itsel
 RLFA_IN_P, RLFA_IN_XP, RLFA_IN_Q, RLFA_ELIGIBLE = 0x01, 0x02, 0x04, 0x08      # space_flags
 RLFA_COUNT_WORDS = 4
 RLFA_COVERAGE_WORDS = 4
+TILFA_NONE, TILFA_NODE, TILFA_PAIR = 0, 1, 2                                  # HSPF_TILFA_*: ti_kind
+TILFA_D_LFA, TILFA_D_NODE, TILFA_D_PAIR, TILFA_D_NONE = 1, 2, 3, 4            # HSPF_TILFA_D_*: td_kind
+TILFA_COUNT_WORDS = 2
+TILFA_COVERAGE_WORDS = 5
 
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
@@ -216,6 +220,20 @@ class RlfaResult:
     rl_node: np.ndarray      # [P, N] u32
     rl_via: np.ndarray       # [P, N] u32
     rl_coverage: np.ndarray  # [P, 4] u32
+
+
+@dataclass
+class TilfaResult:
+    """Two-segment repair paths of the protected roots of one tilfa_device() call, on the host (S = 64 * mask words)."""
+    ti_kind: np.ndarray      # [P, S] u8  TILFA_NONE | TILFA_NODE | TILFA_PAIR
+    ti_p: np.ndarray         # [P, S] u32, NO_ROOT: none
+    ti_q: np.ndarray         # [P, S] u32 (== ti_p for TILFA_NODE)
+    ti_via: np.ndarray       # [P, S] u32, RLFA_VIA_SELF or a slot, LFA_NO_SLOT: none
+    ti_link: np.ndarray      # [P, S] u32 position of the forced link in ti_p's row, LFA_NO_SLOT unless TILFA_PAIR
+    ti_metric: np.ndarray    # [P, S] u32
+    ti_counts: np.ndarray    # [P, S, 2] u32 single nodes | usable (p, link) pairs
+    td_kind: np.ndarray      # [P, N] u8  TILFA_D_* per destination with exactly one primary, 0 elsewhere
+    td_coverage: np.ndarray  # [P, 5] u32
 
 
 def csr_transpose(row_ptr, col, metric, vflags):
@@ -782,11 +800,37 @@ class SpfContext:
         if rc != 0:
             raise HspfError(rc, "hspf_rlfa_device", self.last_error())
 
+    def tilfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
+                     protect, *, space_flags_ptr: int, space_via_ptr: int, ti_kind_ptr: int, ti_p_ptr: int, ti_q_ptr: int, ti_via_ptr: int,
+                     ti_link_ptr: int, ti_metric_ptr: int, ti_counts_ptr: int, td_kind_ptr: int, td_coverage_ptr: int,
+                     alt_flags_in_ptr: int = 0, lfa_flags: int = 0) -> None:
+        """hspf_tilfa_device(): per (protected root, slot) the cheapest repair that is one PQ node or a node of the extended
+        P-space plus one forced adjacency into the Q-space, from the tables of a run_device(), `rdist_ptr` and the space tables
+        rlfa_device() wrote for the same `protect` and lfa_flags (both required).  `graph` is the FORWARD graph: its links are
+        scanned.  All `*_ptr` are device pointers, the slot arrays are strided by 64 * mask_words; alt_flags_in_ptr may be 0."""
+        arr, keep = self._protect_array(protect, "tilfa_device")
+        out = L.HspfTilfaOut(ti_kind_ptr or None, ti_p_ptr or None, ti_q_ptr or None, ti_via_ptr or None, ti_link_ptr or None, ti_metric_ptr or None,
+                             ti_counts_ptr or None, td_kind_ptr or None, td_coverage_ptr or None)
+        rc = self.lib.hspf_tilfa_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                        rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None,
+                                        space_via_ptr or None, ctypes.byref(out))
+        del keep
+        if rc != 0:
+            raise HspfError(rc, "hspf_tilfa_device", self.last_error())
+
     def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False):
         """Remote alternates of one root, start to finish: the candidate table, run_device() of [root] + its distinct neighbour
         routers on `graph` and — unless `symmetric` says every link has its reverse at the same cost — on its transpose
         (csr_transpose, uploaded for the call), lfa_device() then rlfa_device() on those rows, everything on the host.
         Returns (LfaCandidates, LfaResult without masks, RlfaResult), one row each."""
+        return self._rlfa(graph, root, run_flags, lfa_flags, want_spaces, symmetric, False)
+
+    def tilfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False):
+        """Two-segment repairs of one root, start to finish: rlfa(..., want_spaces=True) with everything kept on the device, then
+        tilfa_device() on the same rows and space tables.  Returns (LfaCandidates, LfaResult, RlfaResult, TilfaResult)."""
+        return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True)
+
+    def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool):
         cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
         nbrs = np.unique(cand.nbr[cand.nbr != NO_ROOT])
         roots = np.concatenate([[root], nbrs]).astype(np.uint32)
@@ -802,6 +846,11 @@ class SpfContext:
                       rl_cov=((1, RLFA_COVERAGE_WORDS), np.uint32))
         if want_spaces:
             shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
+        ti_names = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
+        if tilfa:
+            shapes.update(ti_kind=((1, S), np.uint8), ti_p=((1, S), np.uint32), ti_q=((1, S), np.uint32), ti_via=((1, S), np.uint32),
+                          ti_link=((1, S), np.uint32), ti_metric=((1, S), np.uint32), ti_counts=((1, S, TILFA_COUNT_WORDS), np.uint32),
+                          td_kind=((1, n), np.uint8), td_coverage=((1, TILFA_COVERAGE_WORDS), np.uint32))
         host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
         sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
         sizes.update({k: a.nbytes for k, a in host.items()})
@@ -822,13 +871,18 @@ class SpfContext:
                              rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
                              space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
                              lfa_flags=lfa_flags)
+            if tilfa:
+                self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
+                                  space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
+                                  **{k + "_ptr": dev[k] for k in ti_names})
             for k, arr in host.items():
                 rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
                 if rc != 0:
                     raise HspfError(rc, "hspf_device_to_host", self.last_error())
             lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
-            return cand, lfa, RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
-                                         host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
+            rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
+                            host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
+            return (cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, lfa, rl)
         finally:
             if GT is not None:
                 GT.free()

@@ -782,8 +782,8 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
  * enqueued on the context's stream; the call synchronises once at the end.
  *
  * OUT OF SCOPE: node-protecting remote LFA (RFC 8102: the PQ node's path to D may cross E); loop-freeness with respect to a
- * LAN pseudonode (the same root_link rule and the same limitation as hspf_lfa_device); TI-LFA (segment lists beyond one
- * tunnel). */
+ * LAN pseudonode (the same root_link rule and the same limitation as hspf_lfa_device); segment lists beyond one tunnel
+ * (hspf_tilfa_device, below, adds one forced adjacency). */
 #define HSPF_RLFA_VIA_SELF       0xFFFFFFFEu   /* pq_via / space_via / rl_via: released by S itself (P-space) */
 #define HSPF_RLFA_IN_P           0x01u         /* space_flags */
 #define HSPF_RLFA_IN_XP          0x02u
@@ -807,6 +807,77 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                      hspf_rlfa_out *out_dev);
+
+/* ---- two-segment repair paths on device (TI-LFA, link protection): new symbol, same ABI number ----------------------------
+ * hspf_rlfa_device leaves rl_coverage[3]: destinations whose one primary link has no LFA and whose extended P-space and
+ * Q-space do not intersect.  The segment-routing repair for them is two segments: tunnel to a node p of the extended P-space,
+ * force ONE adjacency p -> q into the Q-space, and let q forward normally.  hspf_tilfa_device finds, per protected link, the
+ * cheapest repair among the PQ nodes (one segment) and those (p, link) pairs (two segments).
+ *
+ * Inputs.  The forward table set, rdist_dev, `prot`, n_prot, lfa_flags and the optional alt_flags_in_dev are exactly those of
+ * hspf_rlfa_device.  space_flags_dev / space_via_dev [n_prot][stride][n_vertices] are REQUIRED: the tables hspf_rlfa_device wrote
+ * for the same `prot` and lfa_flags (eligibility and the overload rule are read from them, not evaluated again).  `g` must be
+ * the FORWARD graph — its links are scanned — where hspf_rlfa_device takes either.
+ *
+ * Per protected root S and candidate slot e (E = nbr[e], rowE = nbr_row[e]); every sum is evaluated in 64 bits.
+ *   rel(v)        the release metric of v, rebuilt from via = space_via[e][v]: d(S, v) for HSPF_RLFA_VIA_SELF, cost[via] +
+ *                 d(N_via, v) for a slot.
+ *   single node   v with HSPF_RLFA_ELIGIBLE, (HSPF_RLFA_IN_P or _IN_XP) and _IN_Q:   total = rel(v) + rdist[rowE][v].
+ *   pair          the link at position j of p's row in g, target q != p, cost w, where p has _ELIGIBLE and (_IN_P or _IN_XP),
+ *                 q has _ELIGIBLE and _IN_Q, and the link passes the two-way check (q's row lists p; the cost is not compared:
+ *                 the rule of hspf_slot_table / hspf_lfa_candidates):   total = rel(p) + w + rdist[rowE][q].
+ *                 S is never eligible, so the protected link itself is never the forced adjacency.
+ *   order         totals are saturated at 0xFFFFFFFE first and compared afterwards (as pq_metric); then: the smaller total, a
+ *                 single node before a pair, the smaller p, the smaller q, the smaller position j.
+ * On a graph of routers with symmetric costs >= 1 and no overload the best total is the SPF distance S -> E with the protected
+ * link removed, and there is no repair exactly when E is unreachable there (tests/test_host_tilfa.py).
+ * Outputs (DEVICE pointers; slots are strided by 64 * n_mask_words per protected root; "none" — also for slots that are no
+ * candidates and for slots >= n_slots — is HSPF_NO_ROOT / HSPF_LFA_NO_SLOT / 0):
+ *   ti_kind u8 [n_prot][stride]     HSPF_TILFA_NONE, HSPF_TILFA_NODE (one segment), HSPF_TILFA_PAIR (two)
+ *   ti_p / ti_q                     the chosen nodes; ti_q == ti_p for HSPF_TILFA_NODE
+ *   ti_via                          the via of p's release point (HSPF_RLFA_VIA_SELF or a slot of S)
+ *   ti_link                         position of the chosen link within p's row of g; HSPF_LFA_NO_SLOT unless HSPF_TILFA_PAIR
+ *   ti_metric                       the saturated total
+ *   ti_counts [n_prot][stride][2]   the number of single nodes (= pq_counts[..][3] of hspf_rlfa_device) | of usable (p, link) pairs
+ *   td_kind u8 [n_prot][n_vertices] per destination D of S with exactly one primary slot: HSPF_TILFA_D_LFA the given alt_flags
+ *                                   have HSPF_LFA_LINK_PROTECT, _D_NODE / _D_PAIR that slot has a one- / two-segment repair,
+ *                                   _D_NONE uncovered (also where the slot is no candidate); 0 everywhere else
+ *   td_coverage [n_prot][5]         counted on the device: destinations with exactly one primary, then the four classes
+ * Argument errors — what hspf_rlfa_device rejects, and NULL space tables — return HSPF_E_INVAL with a text in hspf_last_error
+ * that names hspf_tilfa_device, before anything is launched.  The call sizes its own scratch (the selection keys and the
+ * graph's two-way flags, staged from the host mirror: one byte per link), enqueues everything on the context's stream and
+ * synchronises once at the end.
+ *
+ * From a result to a segment list: the first segment is the Node-SID of ti_p, sent out of the first hop
+ * ti_via names (S's own primary next hops towards ti_p for HSPF_RLFA_VIA_SELF, else the neighbour of slot ti_via); for a pair
+ * the second segment is the Adj-SID p advertises for the link at position ti_link of its row.
+ *
+ * OUT OF SCOPE: adjacencies across a LAN pseudonode (p -> network vertex -> q is not offered: q must be a router in p's own
+ * row); node protection; segment lists longer than two; post-convergence-path selection among equal-cost repairs. */
+#define HSPF_TILFA_NONE           0u            /* ti_kind */
+#define HSPF_TILFA_NODE           1u
+#define HSPF_TILFA_PAIR           2u
+#define HSPF_TILFA_D_LFA          1u            /* td_kind */
+#define HSPF_TILFA_D_NODE         2u
+#define HSPF_TILFA_D_PAIR         3u
+#define HSPF_TILFA_D_NONE         4u
+#define HSPF_TILFA_COUNT_WORDS    2u
+#define HSPF_TILFA_COVERAGE_WORDS 5u
+typedef struct {                 /* DEVICE pointers; stride = 64 * n_mask_words                               */
+  uint8_t  *ti_kind;             /* [n_prot][stride]                                                           */
+  uint32_t *ti_p;                /* [n_prot][stride]                                                           */
+  uint32_t *ti_q;                /* [n_prot][stride]                                                           */
+  uint32_t *ti_via;              /* [n_prot][stride]                                                           */
+  uint32_t *ti_link;             /* [n_prot][stride]                                                           */
+  uint32_t *ti_metric;           /* [n_prot][stride]                                                           */
+  uint32_t *ti_counts;           /* [n_prot][stride][HSPF_TILFA_COUNT_WORDS]                                   */
+  uint8_t  *td_kind;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *td_coverage;         /* [n_prot][HSPF_TILFA_COVERAGE_WORDS]                                        */
+} hspf_tilfa_out;
+int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                      const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out *out_dev);
 
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root

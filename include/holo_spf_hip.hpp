@@ -127,6 +127,17 @@ struct Rlfa {
   uint32_t rl_coverage[HSPF_RLFA_COVERAGE_WORDS] = {};
 };
 
+// Two-segment repair paths (hspf_tilfa_device) of one protected root on the host: the RLFA result they complete (with its space
+// tables), per slot the cheapest one- or two-segment repair, per destination its class.
+struct Tilfa {
+  Rlfa rlfa;
+  std::vector<uint8_t> ti_kind;                 // [slot_stride] HSPF_TILFA_NONE / _NODE / _PAIR
+  std::vector<uint32_t> ti_p, ti_q, ti_via, ti_link, ti_metric;   // [slot_stride]
+  std::vector<uint32_t> ti_counts;              // [slot_stride][HSPF_TILFA_COUNT_WORDS]
+  std::vector<uint8_t> td_kind;                 // [n_vertices] HSPF_TILFA_D_*
+  uint32_t td_coverage[HSPF_TILFA_COVERAGE_WORDS] = {};
+};
+
 class Engine;
 
 // The engine context, shared by the Engine and every Graph made from it: a Graph that outlives its Engine (members
@@ -373,6 +384,36 @@ class Engine {
   Rlfa rlfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
             const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
             bool symmetric = false, bool with_spaces = false) {
+    return rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, with_spaces, nullptr);
+  }
+  // hspf_tilfa_device on DEVICE tables: those of rlfa_device plus the space tables it wrote (required); `g` is the FORWARD graph.
+  void tilfa_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                    const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                    const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out out_dev) {
+    const int rc = hspf_tilfa_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                                     (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // One root start to finish: rlfa() with the space tables, everything kept on the device, then hspf_tilfa_device on the same rows.
+  Tilfa tilfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+              const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
+              bool symmetric = false) {
+    Tilfa t;
+    t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, &t);
+    return t;
+  }
+  void wait_all() { (void)hspf_wait_all(ctx_); }
+  uint32_t async_lanes() const { return hspf_async_lanes(ctx_); }
+  // true: these runs are too small to pay for a launch — the caller keeps its own CPU loop (hspf_recommend_cpu)
+  static bool recommend_cpu(uint32_t n_vertices, uint32_t n_edges, uint32_t n_roots) {
+    return hspf_recommend_cpu(n_vertices, n_edges, n_roots) != 0;
+  }
+
+ private:
+  // rlfa(); with `ti` the two-segment step runs on the same device tables before anything is freed
+  Rlfa rlfa_impl(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                 const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags, uint32_t lfa_flags,
+                 bool symmetric, bool with_spaces, Tilfa *ti) {
     if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
       throw Error(HSPF_E_INVAL, "Engine::rlfa: the CSR is not the one the graph was uploaded from");
     Rlfa r;
@@ -422,16 +463,21 @@ class Engine {
     r.rl_node = rl_node.to_host<uint32_t>(n); r.rl_via = rl_via.to_host<uint32_t>(n);
     const std::vector<uint32_t> rc4 = rl_cov.to_host<uint32_t>(HSPF_RLFA_COVERAGE_WORDS);
     std::copy(rc4.begin(), rc4.end(), r.rl_coverage);
+    if (ti) {
+      DeviceBuffer kind(ctx_, S), tp(ctx_, S * 4), tq(ctx_, S * 4), tv(ctx_, S * 4), tl(ctx_, S * 4), tm(ctx_, S * 4),
+          tc(ctx_, (size_t)S * 4 * HSPF_TILFA_COUNT_WORDS), dk(ctx_, n), dc(ctx_, HSPF_TILFA_COVERAGE_WORDS * 4);
+      tilfa_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(), {p},
+                   lfa_flags, fl.as<uint8_t>(), sp_flags.as<uint8_t>(), sp_via.as<uint32_t>(),
+                   hspf_tilfa_out{kind.as<uint8_t>(), tp.as<uint32_t>(), tq.as<uint32_t>(), tv.as<uint32_t>(), tl.as<uint32_t>(), tm.as<uint32_t>(),
+                                  tc.as<uint32_t>(), dk.as<uint8_t>(), dc.as<uint32_t>()});
+      ti->ti_kind = kind.to_host<uint8_t>(S); ti->ti_p = tp.to_host<uint32_t>(S); ti->ti_q = tq.to_host<uint32_t>(S);
+      ti->ti_via = tv.to_host<uint32_t>(S); ti->ti_link = tl.to_host<uint32_t>(S); ti->ti_metric = tm.to_host<uint32_t>(S);
+      ti->ti_counts = tc.to_host<uint32_t>((size_t)S * HSPF_TILFA_COUNT_WORDS); ti->td_kind = dk.to_host<uint8_t>(n);
+      const std::vector<uint32_t> c5 = dc.to_host<uint32_t>(HSPF_TILFA_COVERAGE_WORDS);
+      std::copy(c5.begin(), c5.end(), ti->td_coverage);
+    }
     return r;
   }
-  void wait_all() { (void)hspf_wait_all(ctx_); }
-  uint32_t async_lanes() const { return hspf_async_lanes(ctx_); }
-  // true: these runs are too small to pay for a launch — the caller keeps its own CPU loop (hspf_recommend_cpu)
-  static bool recommend_cpu(uint32_t n_vertices, uint32_t n_edges, uint32_t n_roots) {
-    return hspf_recommend_cpu(n_vertices, n_edges, n_roots) != 0;
-  }
-
- private:
   std::shared_ptr<CtxHolder> holder_;
   hspf_ctx *ctx_ = nullptr;
 };

@@ -127,9 +127,24 @@ struct RlfaOut {
   std::vector<uint32_t> rl_node, rl_via;                    // [n_protected][n_vertices]
   std::vector<uint32_t> rl_coverage;                        // [n_protected][HSPF_RLFA_COVERAGE_WORDS]
 };
+// Two-segment repair paths (hspf_tilfa_device) of the same protected roots: per (protected root, slot) the cheapest repair that is
+// one PQ node or a node of the extended P-space plus one forced adjacency into the Q-space, and the class of every destination,
+// from the same two DeviceRuns and the space tables of rlfa(..., with_spaces = true).  supported == false: no such call.
+struct TilfaOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_vertices = 0, slot_stride = 64;
+  std::vector<uint8_t> ti_kind;                             // [n_protected][slot_stride] HSPF_TILFA_*
+  std::vector<uint32_t> ti_p, ti_q, ti_via, ti_link, ti_metric;
+  std::vector<uint32_t> ti_counts;                          // [n_protected][slot_stride][HSPF_TILFA_COUNT_WORDS]
+  std::vector<uint8_t> td_kind;                             // [n_protected][n_vertices] HSPF_TILFA_D_*
+  std::vector<uint32_t> td_coverage;                        // [n_protected][HSPF_TILFA_COVERAGE_WORDS]
+};
 class Engine {
  public:
   virtual ~Engine() = default;
+  // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph.  The default: not supported.
+  virtual TilfaOut tilfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
+                         const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/) { return TilfaOut{}; }
   // The default: not supported (LfaOut::supported == false).
   virtual LfaOut lfa(DeviceRun &, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) { return LfaOut{}; }
   // `reverse_run`: the run of the same roots on the upload of the transposed CSR (the forward run itself on a graph whose
@@ -739,6 +754,56 @@ class HipEngine : public Engine {
     }
     pool_->dev_free(blk, total);
     if (!ok) throw std::runtime_error(std::string("hspf_rlfa_device: ") + hspf_last_error(ctx_));
+    return o;
+  }
+  TilfaOut tilfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
+                 const RlfaOut &rl) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rr = static_cast<HipDeviceRun &>(reverse_run);
+    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error("tilfa: the two runs differ in shape");
+    TilfaOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words;
+    if (protect.empty()) return o;
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = ps * o.n_vertices;
+    if (rl.space_flags.size() != sp || rl.space_via.size() != sp) throw std::runtime_error("tilfa: the RLFA result holds no space tables of this protect list");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("tilfa: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t cb = (size_t)o.n_protected * HSPF_TILFA_COVERAGE_WORDS;
+    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
+    // one block: ti_p | ti_q | ti_via | ti_link | ti_metric | ti_counts | td_coverage | space_via | ti_kind | td_kind | space_flags | alt_flags
+    const size_t words = ps * 5 + ps * HSPF_TILFA_COUNT_WORDS + cb + sp, total = words * 4 + ps + pn + sp + (with_alt ? pn : 0);
+    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    uint32_t *w = (uint32_t *)blk;
+    hspf_tilfa_out out{};
+    out.ti_p = w; w += ps; out.ti_q = w; w += ps; out.ti_via = w; w += ps; out.ti_link = w; w += ps; out.ti_metric = w; w += ps;
+    out.ti_counts = w; w += ps * HSPF_TILFA_COUNT_WORDS; out.td_coverage = w; w += cb;
+    uint32_t *sv = w; w += sp;
+    uint8_t *b = (uint8_t *)w;
+    out.ti_kind = b; b += ps; out.td_kind = b; b += pn;
+    uint8_t *sf = b; b += sp;
+    uint8_t *alt = with_alt ? b : nullptr;
+    bool ok = hipMemcpy(sv, rl.space_via.data(), sp * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
+              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
+    const int rc = ok ? hspf_tilfa_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(),
+                                          o.n_protected, lfa_flags, alt, sf, sv, &out) : HSPF_E_HIP;
+    auto fetch = [&](auto &vec, const void *src, size_t count) {
+      vec.resize(count);
+      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
+    };
+    ok = ok && rc == HSPF_OK;
+    if (ok) {
+      fetch(o.ti_kind, out.ti_kind, ps); fetch(o.ti_p, out.ti_p, ps); fetch(o.ti_q, out.ti_q, ps); fetch(o.ti_via, out.ti_via, ps);
+      fetch(o.ti_link, out.ti_link, ps); fetch(o.ti_metric, out.ti_metric, ps); fetch(o.ti_counts, out.ti_counts, ps * HSPF_TILFA_COUNT_WORDS);
+      fetch(o.td_kind, out.td_kind, pn); fetch(o.td_coverage, out.td_coverage, cb);
+    }
+    pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string("hspf_tilfa_device: ") + hspf_last_error(ctx_));
     return o;
   }
   RouteEvents routes_events(DeviceRoutes &old_set, DeviceRoutes &new_set, bool with_silent) override {

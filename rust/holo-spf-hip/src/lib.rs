@@ -297,6 +297,35 @@ impl Rlfa {
     }
 }
 
+/// Two-segment repair paths (TI-LFA, link protection) of the protected roots of one `Engine::tilfa_device` call.  Slots are
+/// strided by `slot_stride` = 64 * mask words per protected root.
+pub struct Tilfa {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub slot_stride: u32,
+    pub ti_kind: Vec<u8>,
+    pub ti_p: Vec<u32>,
+    pub ti_q: Vec<u32>,
+    pub ti_via: Vec<u32>,
+    pub ti_link: Vec<u32>,
+    pub ti_metric: Vec<u32>,
+    pub ti_counts: Vec<u32>,
+    pub td_kind: Vec<u8>,
+    pub td_coverage: Vec<u32>,
+}
+
+impl Tilfa {
+    /// The repair of (protected root `i`, slot `e`): (via, p, forced link of p's row or `None` for a single node, total),
+    /// `None` when there is none.  The segment list is the Node-SID of p, then the Adj-SID of that link.
+    pub fn repair(&self, i: usize, e: u32) -> Option<(u32, u32, Option<u32>, u32)> {
+        let k = i * self.slot_stride as usize + e as usize;
+        (self.ti_kind[k] as u32 != sys::HSPF_TILFA_NONE).then(|| {
+            let link = (self.ti_kind[k] as u32 == sys::HSPF_TILFA_PAIR).then(|| self.ti_link[k]);
+            (self.ti_via[k], self.ti_p[k], link, self.ti_metric[k])
+        })
+    }
+}
+
 /// `hspf_run_device` results left in HBM: input of `routes_device` / `ancestors_device`.
 pub struct DeviceTables<'e> {
     pub n_roots: u32,
@@ -723,6 +752,103 @@ impl Engine {
             rl_node: rl_node.to_host(cells)?,
             rl_via: rl_via.to_host(cells)?,
             rl_coverage: rl_cov.to_host(np * sys::HSPF_RLFA_COVERAGE_WORDS as usize)?,
+        })
+    }
+
+    /// `hspf_tilfa_device`: per (protected root, slot) the cheapest repair that is one PQ node or a node of the extended P-space
+    /// plus one forced adjacency into the Q-space.  `g` is the FORWARD graph; `tables`, `reverse`, `protect`, `lfa` as for
+    /// `rlfa_device`; `rlfa`: what `rlfa_device` returned for the same `protect` with `with_spaces`.
+    pub fn tilfa_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
+                        ignore_overload: bool, lfa: Option<&Lfa>, rlfa: &Rlfa) -> Result<Tilfa, Error> {
+        let (n, np) = (tables.n_vertices as usize, protect.len());
+        if reverse.n_vertices != tables.n_vertices || reverse.n_roots != tables.n_roots {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_device: the two table sets differ in shape".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let stride = 64 * tables.words as usize;
+        let (slots, cells) = (np * stride, np * n);
+        if rlfa.space_flags.len() != slots * n || rlfa.space_via.len() != slots * n {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_device: the RLFA result holds no space tables of this protect list".into() });
+        }
+        let sp_flags = self.device_from(&rlfa.space_flags)?;
+        let sp_via = self.device_from(&rlfa.space_via)?;
+        let alt = match lfa {
+            Some(l) if l.alt_flags.len() == cells => Some(self.device_from(&l.alt_flags)?),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_device: the LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let ti_kind = self.device_alloc(slots)?;
+        let ti_p = self.device_alloc(slots * 4)?;
+        let ti_q = self.device_alloc(slots * 4)?;
+        let ti_via = self.device_alloc(slots * 4)?;
+        let ti_link = self.device_alloc(slots * 4)?;
+        let ti_metric = self.device_alloc(slots * 4)?;
+        let ti_counts = self.device_alloc(slots * sys::HSPF_TILFA_COUNT_WORDS as usize * 4)?;
+        let td_kind = self.device_alloc(cells)?;
+        let td_cov = self.device_alloc(np * sys::HSPF_TILFA_COVERAGE_WORDS as usize * 4)?;
+        let mut out = sys::hspf_tilfa_out {
+            ti_kind: ti_kind.p as *mut u8,
+            ti_p: ti_p.p as *mut u32,
+            ti_q: ti_q.p as *mut u32,
+            ti_via: ti_via.p as *mut u32,
+            ti_link: ti_link.p as *mut u32,
+            ti_metric: ti_metric.p as *mut u32,
+            ti_counts: ti_counts.p as *mut u32,
+            td_kind: td_kind.p as *mut u8,
+            td_coverage: td_cov.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_tilfa_device(
+                self.ctx,
+                g.g,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                reverse.dist.p as *const u32,
+                raw.as_ptr(),
+                np as u32,
+                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
+                alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
+                sp_flags.p as *const u8,
+                sp_via.p as *const u32,
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(Tilfa {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            slot_stride: stride as u32,
+            ti_kind: ti_kind.to_host(slots)?,
+            ti_p: ti_p.to_host(slots)?,
+            ti_q: ti_q.to_host(slots)?,
+            ti_via: ti_via.to_host(slots)?,
+            ti_link: ti_link.to_host(slots)?,
+            ti_metric: ti_metric.to_host(slots)?,
+            ti_counts: ti_counts.to_host(slots * sys::HSPF_TILFA_COUNT_WORDS as usize)?,
+            td_kind: td_kind.to_host(cells)?,
+            td_coverage: td_cov.to_host(np * sys::HSPF_TILFA_COVERAGE_WORDS as usize)?,
         })
     }
 
