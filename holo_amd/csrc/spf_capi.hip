@@ -3948,6 +3948,7 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
     if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
       return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
     if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
+    if (g->invalid) return bad("the graph is invalid after a failed hspf_graph_patch (free it and upload again)");
     if (g->n != n_vertices) return bad("n_vertices is not the graph's");
     const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
     if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");

@@ -11,12 +11,14 @@ import pytest
 import _lfa_model as M
 import _rlfa_model as R
 import _tilfa_model as T
-from test_gpu_rlfa import Case, Tables, lan, ring8, ring_chords
+from test_gpu_rlfa import PRUNE_SEED, Case, Tables, lan, ring8, ring_chords, with_island
 
 pytestmark = pytest.mark.gpu
 
 RING300 = (3, 110)            # (seed, protected root): the equal-cost repairs of a slot lie on both sides of vertex 256, the winner is 255
 E2E = (11, 100)               # (seed, protected root) of a 300-ring with six chords on which RLFA covers nothing and the pairs everything
+TILE_EDGE = {255: (1, 109), 256: (10, 152), 257: (53, 152)}      # n: (seed, protected root) of a ring with four chords whose winner is vertex n - 1
+BIG = 0x7FFFFFF0              # two such costs fit 32 bits, two and anything more than 14 do not
 
 
 def want_of(case, lfa_flags=0, with_lfa=True, rdist=None):
@@ -342,3 +344,127 @@ def test_tilfa_convenience_end_to_end(spf_ctx):
         assert np.array_equal(getattr(ti2, name), getattr(ti, name)), name
     assert ti.td_coverage[0].tolist() == wt.td_coverage.tolist() and ti.td_coverage[0, 0] == rl.rl_coverage[0, 0]
     assert ti.td_coverage[0, 1] == rl.rl_coverage[0, 1] and ti.td_coverage[0, 2] == rl.rl_coverage[0, 2]
+
+
+# ---- the edges hspf_rlfa_device's suite has: tile edge, totals beyond 32 bits, zero-cost links, unreachable and pruned vertices,
+# overload, self-loops, and a seeded sweep.  Every seed was chosen on the CPU so that the MODEL shows the class (asserted first).
+
+def all_repairs(case, wr):
+    return {int(e): T.repairs(case.fwd.dist, case.rdist, case.graph, case.cand, 0, case.nbr_row, e, wr.space_flags[e], wr.space_via[e])
+            for e in np.flatnonzero(case.cand.nbr != M.NONE)}
+
+
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_rings_with_chords_at_the_tile_edge(spf_ctx, n):
+    """The winner of both slots is vertex n - 1: the last valid lane of the one partial tile (255), the last lane of a full
+    tile (256), the only valid lane of the second tile (257)."""
+    seed, root = TILE_EDGE[n]
+    case = Case(ring_chords(n, seed, 1, 9, chords=4), root)
+
+    def need(wr, wt):
+        ks = np.flatnonzero(case.cand.nbr != M.NONE)
+        assert any(n - 1 in (int(wt.ti_p[e]), int(wt.ti_q[e])) for e in ks) and wt.td_coverage[2] > 0
+    check_one(spf_ctx, case, need=need)
+
+
+def test_totals_beyond_32_bits_saturate_and_tie(spf_ctx):
+    """The five-ring with 0x7FFFFFF0 on every link but 2-3: every repair of the link 2-3 adds three of them.  Six repairs
+    saturate at 0xFFFFFFFE and tie: the single node with the smallest p wins."""
+    case = Case(M.csr(5, M.both([(0, 1, BIG), (1, 2, BIG), (2, 3, 1), (3, 4, BIG), (4, 0, BIG)])), 2)
+
+    def need(wr, wt):
+        e = slot_of(case, 3)
+        reps = all_repairs(case, wr)[e]
+        assert sum(1 for r in reps if r[0] == T.SAT) >= 2 and len({r[1] for r in reps if r[0] == T.SAT}) == 2      # nodes and pairs tie
+        assert (wt.ti_kind[e], wt.ti_p[e], wt.ti_metric[e]) == (T.KIND_NODE, 0, 0xFFFFFFFE) and wt.ti_counts[e].tolist() == [2, 4]
+    check_one(spf_ctx, case, need=need)
+
+
+def test_saturated_pair_with_two_q_at_different_true_totals(spf_ctx):
+    """S = 0 - N = 2 - p = 3, E = 1; p reaches E through q = 4 at 0x60000000 + 0x60000000 and through q = 5 at 0x50000000 +
+    0x50000000; both totals are beyond 32 bits, so both are 0xFFFFFFFE and the order is (total, q, position): q = 4, the dearer
+    one before the clamp.  No single node: 4 and 5 are in no extended P-space, 3 is not in Q."""
+    B1, B2 = 0x60000000, 0x50000000
+    case = Case(M.csr(6, M.both([(0, 1, 1), (0, 2, 1), (2, 3, BIG), (3, 4, B1), (3, 5, B2), (4, 1, B1), (5, 1, B2)])), 0)
+
+    def need(wr, wt):
+        e = slot_of(case, 1)
+        reps = all_repairs(case, wr)[e]
+        assert sorted((r[1], r[2], r[3]) for r in reps) == [(T.KIND_PAIR, 3, 4), (T.KIND_PAIR, 3, 5)] and all(r[0] == T.SAT for r in reps)
+        rel = 1 + BIG                                                        # d(S, p); 3 is in P, released by S itself
+        assert case.fwd.dist[0, 3] == rel and wt.ti_via[e] == T.VIA_SELF
+        assert rel + 2 * B1 > rel + 2 * B2 > T.SAT                           # different totals before the clamp, the larger q the cheaper
+        assert (wt.ti_kind[e], wt.ti_p[e], wt.ti_q[e], wt.ti_link[e], wt.ti_metric[e]) == (T.KIND_PAIR, 3, 4, 1, 0xFFFFFFFE)
+        assert wt.ti_counts[e].tolist() == [0, 2]
+    check_one(spf_ctx, case, need=need)
+
+
+def test_zero_cost_links(spf_ctx):
+    case = Case(ring_chords(300, 8, 1, 6, chords=300, zero_share=0.01), 17)
+
+    def need(wr, wt):
+        rp, _, met, _ = case.graph
+        ks = np.flatnonzero(case.cand.nbr != M.NONE)
+        assert (wt.ti_kind[ks] != 0).all() and wt.ti_counts[ks, 1].min() > 0
+        assert any(r[1] == T.KIND_PAIR and met[rp[r[2]] + r[4]] == 0 for reps in all_repairs(case, wr).values() for r in reps)      # a forced link at cost 0
+    check_one(spf_ctx, case, need=need)
+
+
+def test_unreachable_island_is_in_no_repair(spf_ctx):
+    case = Case(with_island(ring_chords(100, 3)), 44)
+
+    def need(wr, wt):
+        ks = np.flatnonzero(case.cand.nbr != M.NONE)
+        assert (wt.ti_kind[ks] != 0).all() and not wt.td_kind[100:].any() and wt.td_coverage[0] == 99
+        assert all(r[2] < 100 and r[3] < 100 for reps in all_repairs(case, wr).values() for r in reps)
+    check_one(spf_ctx, case, need=need)
+
+
+def test_pruned_vertices_are_in_no_repair(spf_ctx):
+    case = Case(ring_chords(120, PRUNE_SEED, 1, 400), 7, maxp=1023)
+
+    def need(wr, wt):
+        pruned = case.fwd.dist[0] == R.INF
+        ks = np.flatnonzero(case.cand.nbr != M.NONE)
+        assert pruned.any() and not pruned.all() and (case.fwd.dist[1:][:, pruned] != R.INF).any()      # a neighbour still reaches some of them
+        assert (wt.ti_kind[ks] != 0).any() and wt.ti_counts[ks, 1].min() > 0 and not wt.td_kind[pruned].any()
+        assert all(not pruned[r[2]] and not pruned[r[3]] for reps in all_repairs(case, wr).values() for r in reps)
+    check_one(spf_ctx, case, need=need)
+
+
+def test_protected_link_to_an_overloaded_neighbour(spf_ctx):
+    """ring8, S = 0, the neighbour E = 1 overloaded: its own slot is repaired by the node 4 either way; the slot of 7 would be
+    repaired through 1 and is not, unless the overload is ignored."""
+    case = Case(ring8(no_transit=[1]), 0)
+    e1, e7 = slot_of(case, 1), slot_of(case, 7)
+    assert case.cand.cflags[e1] & M.C_NO_TRANSIT
+    plain, ign = want_of(case, 0)[1], want_of(case, M.IGNORE_OVERLOAD)[1]
+    assert (plain.ti_kind[e1], plain.ti_p[e1]) == (T.KIND_NODE, 4) and plain.ti_kind[e7] == T.KIND_NONE and plain.td_coverage[4] > 0
+    assert (ign.ti_kind[e7], ign.ti_p[e7]) == (T.KIND_NODE, 2) and ign.td_coverage[4] == 0
+    check_one(spf_ctx, case, lfa_flags=(0, M.IGNORE_OVERLOAD))
+
+
+def test_self_loop_in_the_row_of_a_pq_node(spf_ctx):
+    """The six-ring with a link 3 -> 3: 3 is in the extended P-space and in Q, so the link would count as a pair (3, 3) if a
+    vertex's links to itself were not skipped: two pairs, not three."""
+    case = Case(M.csr(6, M.both([(v, (v + 1) % 6, 1) for v in range(6)]) + [(3, 3, 1)]), 0)
+
+    def need(wr, wt):
+        e = slot_of(case, 1)
+        rp, col, _, _ = case.graph
+        assert 3 in col[rp[3]:rp[4]] and wr.space_flags[e][3] & (R.IN_P | R.IN_XP) and wr.space_flags[e][3] & R.IN_Q
+        assert (wt.ti_kind[e], wt.ti_p[e], wt.ti_metric[e]) == (T.KIND_NODE, 3, 5) and wt.ti_counts[e].tolist() == [1, 2]
+    check_one(spf_ctx, case, need=need)
+
+
+def test_seeded_sweep_of_forty_graphs(spf_ctx):
+    """40 graphs of the generator of tests/test_host_tilfa.py with 12 to 60 routers (tests/_frr_chains.py: sweep_graphs), half of
+    them with a cost per direction, a quarter with zero-cost links, a quarter with an overloaded router; one seeded root each,
+    none skipped.  Over the sweep the MODEL shows at least five slots of every ti_kind and a destination in every td_kind
+    class (tests/test_host_tilfa.py holds the seed to that on the CPU)."""
+    import _frr_chains as F
+    cases = [Case(g, root) for g, root, _ in F.sweep_graphs()]
+    assert len(cases) == 40 and all(12 <= len(c.graph[3]) <= 60 for c in cases)
+    F.check_sweep_classes([(np.flatnonzero(c.cand.nbr != M.NONE), want_of(c)[1]) for c in cases])
+    for c in cases:
+        check_one(spf_ctx, c)

@@ -8,6 +8,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 
 import _lfa_model as M
 import _rlfa_model as R
@@ -110,10 +111,10 @@ def test_pendant_bridge_has_no_repair():
 N_GRAPHS = 2000
 
 
-def _random_graph(r):
-    """A ring of 4-14 routers, unit costs or random costs 1-9, zero to n random chords, parallel links allowed.  Returns the
-    undirected links; link i is the two directed entries that M.both makes of und[i]."""
-    n = int(r.integers(4, 15))
+def _random_graph(r, n_lo=4, n_hi=14):
+    """A ring of n_lo .. n_hi routers, unit costs or random costs 1-9, zero to n random chords, parallel links allowed.  Returns
+    the undirected links; link i is the two directed entries that M.both makes of und[i]."""
+    n = int(r.integers(n_lo, n_hi + 1))
     unit = bool(r.integers(0, 2))
     cost = lambda: 1 if unit else int(r.integers(1, 10))      # noqa: E731
     und = [(v, (v + 1) % n, cost()) for v in range(n)]
@@ -158,3 +159,76 @@ def test_best_repair_is_the_shortest_path_without_the_link():
     assert skipped == 0 and slots >= 2 * N_GRAPHS                         # the property was applied to every generated slot
     # both kinds of repair occurred; a ring with chords has no bridge, so "unreachable" is test_pendant_bridge_has_no_repair's
     assert pairs > 0 and singles > 0 and none == 0, (pairs, singles, none)
+
+
+# ---- the model-only halves of tests/test_gpu_frr_patched.py and of the sweep of tests/test_gpu_tilfa.py: the same splices, the
+# same assertions on what each step changes, and the property above after every step it applies to — the inputs of the GPU
+# tests are proven meaningful without one.
+
+@pytest.mark.parametrize("name,applies", [("a", [0, 1, 2, 3, 4]), ("b", [0, 2]), ("c", [0, 1, 2, 3]), ("d", [0])])
+def test_patch_chains_on_the_model(name, applies):
+    """Every step of a chain: what it is meant to change, on the model; on the steps with routers only, symmetric costs >= 1 and
+    no overload (`applies`: chain b's middle step sets the overload, chain d's long rows hold parallel links) the best total of
+    every candidate slot is the SPF distance S -> E without the link."""
+    import _frr_chains as F
+    from test_gpu_rlfa import Case
+    chain = F.chain(name)
+    slots = 0
+    for i, step in enumerate(chain.steps):
+        chain.check(i)
+        m = chain.model(i)
+        assert F.property_applies(step.graph) == (i in applies), (name, i)
+        if i in applies:
+            slots += F.check_best_is_the_way_round(m)
+        if len(m.prot) == 1:                                             # one root: the rows, and so every table, are Case's
+            case = Case(step.graph, m.prot[0])
+            assert np.array_equal(case.roots, m.roots) and np.array_equal(case.nbr_row, m.nbr_row[0]) and case.W == m.W
+            assert np.array_equal(case.fwd.dist, m.fwd.dist) and np.array_equal(case.rdist, m.rdist)
+    assert slots >= 2 * len(applies)
+    # the patch model's word on the paths the device is to take: per engine configuration of tests/conftest.py
+    paths = {e: chain.paths(e) for e in F.ENGINES}
+    assert all(p.build_mode == F.pm.MODE_HUB or p.decision.path == "cost" for p in paths["hubsort"][1:])
+    assert all(p.build_mode == F.pm.MODE_REBUILD or p.decision.path == "cost" for p in paths["patchfull"][1:])
+    structural = [i for i, p in enumerate(paths["default"]) if i and p.decision.path != "cost"]
+    assert all(paths["hubsort"][i].flags_fetched and paths["hubsort"][i].pool_compact for i in structural)
+    if name != "b":                                                      # a row's length changes: the pool is out of order afterwards
+        assert any(not paths[e][i].pool_compact for e in ("default", "patchfull") for i in structural)
+    else:
+        assert all(p.pool_compact for e in F.ENGINES for p in paths[e])
+
+
+def test_patch_chains_reach_every_way_of_keeping_the_flags():
+    """Over the four chains, by the patch model: the incremental path, the rebuild, the cost-only path and an arena growth; the
+    two-way flags kept by the host's row scan with the pool left out of order, and fetched from the device — in the default
+    configuration too (chain d's last step)."""
+    import _frr_chains as F
+    steps = [(e, p) for name in "abcd" for e in F.ENGINES for p in F.chain(name).paths(e)[1:]]
+    modes = {(e, p.build_mode) for e, p in steps}
+    assert {("default", F.pm.MODE_INCREMENTAL), ("default", F.pm.MODE_REBUILD), ("default", F.pm.MODE_COST), ("hubsort", F.pm.MODE_HUB),
+            ("patchfull", F.pm.MODE_REBUILD)} <= modes
+    assert any(p.decision.grown for _, p in steps)
+    assert any(e == "default" and p.flags_fetched for e, p in steps) and any(e == "default" and not p.pool_compact for e, p in steps)
+
+
+def test_sweep_of_the_gpu_suite_shows_every_class():
+    """The 40 graphs of tests/test_gpu_tilfa.py's sweep, on the model: n between 12 and 60, the shares of asymmetric, zero-cost
+    and overloaded graphs, at least five slots of every ti_kind and a destination in every td_kind class; and the property above
+    on the graphs it applies to."""
+    import _frr_chains as F
+    graphs = F.sweep_graphs()
+    assert len(graphs) == 40 and all(12 <= w["n"] <= 60 for _, _, w in graphs)
+    assert sum(w["asym"] for _, _, w in graphs) == 20 and sum(w["zero"] for _, _, w in graphs) == 10 and sum(w["overload"] for _, _, w in graphs) == 10
+    models, checked = [], 0
+    for g, root, w in graphs:
+        assert (g[2] == 0).any() == w["zero"] and int((g[3] & M.VF_NO_TRANSIT != 0).sum()) == int(w["overload"]) and not g[3][root]
+        m = F.Protected(g, (root,))
+        models.append((m.slots(), m.want()[0][2]))
+        if not (w["asym"] or w["zero"] or w["overload"]):
+            d = {}
+            for u in range(w["n"]):
+                for k in range(int(g[0][u]), int(g[0][u + 1])):
+                    d.setdefault((u, int(g[1][k])), []).append(int(g[2][k]))
+            if all(len(v) == 1 for v in d.values()):                     # (no parallel links: cut_distance removes every S - E link)
+                checked += F.check_best_is_the_way_round(m)
+    kinds, dests = F.check_sweep_classes(models)
+    assert checked > 0
