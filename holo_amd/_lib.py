@@ -95,6 +95,11 @@ class HspfTilfaOut(ctypes.Structure):
                 ("td_coverage", ctypes.c_void_p)]
 
 
+class HspfBackupOut(ctypes.Structure):
+    _fields_ = [("bk_kind", ctypes.c_void_p), ("bk_primary", ctypes.c_void_p), ("bk_slot", ctypes.c_void_p), ("bk_metric", ctypes.c_void_p),
+                ("bk_flags", ctypes.c_void_p), ("bk_cand_mask", ctypes.c_void_p), ("bk_node_mask", ctypes.c_void_p), ("bk_coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -181,6 +186,11 @@ SYMBOLS = [
     ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
                                          ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfTilfaOut)]),
+    # per-prefix backup routes
+    ("hspf_routes_backup_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes), ctypes.POINTER(HspfTilfaOut),
+                                                 ctypes.POINTER(HspfBackupOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

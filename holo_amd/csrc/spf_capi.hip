@@ -15,6 +15,7 @@
 #include "spf_lfa.hip.h"
 #include "spf_rlfa.hip.h"
 #include "spf_tilfa.hip.h"
+#include "spf_backup.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3360,20 +3361,16 @@ int hspf_wait_all(hspf_ctx *ctx) {
 
 uint32_t hspf_async_lanes(const hspf_ctx *ctx) { return ctx ? (ctx->lanes.empty() ? ctx->lanes_cfg : (uint32_t)ctx->lanes.size()) : 0u; }
 
-static int routes_device_impl(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_roots, uint32_t n_mask_words,
-                              const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
-                              const hspf_prefix_table *t, hspf_routes *out) {
-  if (ctx) ctx->evs.valid = false;                        // a route call: the kept event stream (hspf_routes_events_rest) is void
-  if (!ctx || !t || !out || !dist_dev || !flags_dev || !mask_dev || !out->best_metric || !out->best_entry ||
-      !out->nexthop_mask || n_roots == 0 || n_mask_words == 0 || !t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric)))
-    return HSPF_E_INVAL;
-  if (t->flags & ~(HSPF_PFX_SATURATING | HSPF_PFX_LAST_MIN | HSPF_PFX_ORDERED | HSPF_PFX_RESIDENT)) { ctx->last_error = "hspf_prefix_table: unknown flags"; return HSPF_E_INVAL; }
+// What hspf_routes_device and hspf_routes_backup_device share: the checks of a prefix table and the staging of its three main
+// arrays in ctx->pf_ptr / pf_vtx / pf_met on the context's stream (nothing is staged for an empty table).  `fn` names the caller
+// in hspf_last_error (nullptr: hspf_routes_device's own texts).
+static int pfx_table_stage(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, const hspf_prefix_table *t) {
+  auto bad = [&](const char *what) { ctx->last_error = fn ? std::string(fn) + ": " + what : std::string(what); return HSPF_E_INVAL; };
+  if (t->flags & ~(HSPF_PFX_SATURATING | HSPF_PFX_LAST_MIN | HSPF_PFX_ORDERED | HSPF_PFX_RESIDENT)) return bad("hspf_prefix_table: unknown flags");
   const bool ordered = (t->flags & HSPF_PFX_ORDERED) != 0;
   if (ordered && ((t->flags & HSPF_PFX_LAST_MIN) || (t->n_entries && !t->pfx_origin) ||
-                  (t->init_exists && (!t->init_metric || !t->init_origin)))) {
-    ctx->last_error = "hspf_prefix_table: HSPF_PFX_ORDERED needs pfx_origin (and init_metric / init_origin with init_exists), not LAST_MIN";
-    return HSPF_E_INVAL;
-  }
+                  (t->init_exists && (!t->init_metric || !t->init_origin))))
+    return bad("hspf_prefix_table: HSPF_PFX_ORDERED needs pfx_origin (and init_metric / init_origin with init_exists), not LAST_MIN");
   // A prefix table changes with the LSDB, not with every SPF run.  HSPF_PFX_RESIDENT is the caller's word that the three
   // main arrays are exactly what its previous call on this context passed (same pointers, same sizes, contents untouched):
   // the checks and the three pageable copies — most of the call at 120 000 prefixes — are skipped.  Anything that does not
@@ -3381,33 +3378,46 @@ static int routes_device_impl(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_roo
   const bool resident = (t->flags & HSPF_PFX_RESIDENT) && !ordered && ctx->pf_shadow_ok && ctx->pf_shadow_nv == n_vertices &&
                         ctx->pf_res_np == t->n_prefixes && ctx->pf_res_ne == t->n_entries && ctx->pf_res_ptr == (const void *)t->pfx_ptr &&
                         ctx->pf_res_vtx == (const void *)t->pfx_vertex && ctx->pf_res_met == (const void *)t->pfx_metric;
-  if (!resident) {
-    ctx->pf_shadow_ok = false;
-    if (t->pfx_ptr[0] != 0 || t->pfx_ptr[t->n_prefixes] != t->n_entries) { ctx->last_error = "pfx_ptr malformed"; return HSPF_E_INVAL; }
-    for (uint32_t p = 0; p < t->n_prefixes; ++p)
-      if (t->pfx_ptr[p + 1] < t->pfx_ptr[p]) { ctx->last_error = "pfx_ptr not monotone"; return HSPF_E_INVAL; }
-    for (uint32_t e = 0; e < t->n_entries; ++e)
-      if ((ordered ? (t->pfx_vertex[e] & ~HSPF_PFX_ENTRY_NETWORK) : t->pfx_vertex[e]) >= n_vertices) { ctx->last_error = "pfx_vertex out of range"; return HSPF_E_INVAL; }
-  }
+  if (resident) return HSPF_OK;
+  ctx->pf_shadow_ok = false;
+  if (t->pfx_ptr[0] != 0 || t->pfx_ptr[t->n_prefixes] != t->n_entries) return bad("pfx_ptr malformed");
+  for (uint32_t p = 0; p < t->n_prefixes; ++p)
+    if (t->pfx_ptr[p + 1] < t->pfx_ptr[p]) return bad("pfx_ptr not monotone");
+  for (uint32_t e = 0; e < t->n_entries; ++e)
+    if ((ordered ? (t->pfx_vertex[e] & ~HSPF_PFX_ENTRY_NETWORK) : t->pfx_vertex[e]) >= n_vertices) return bad("pfx_vertex out of range");
   if (t->n_prefixes == 0) return HSPF_OK;
   (void)hipSetDevice(ctx->device);
   int rc;
   hipStream_t s = ctx->stream;
-  if (!resident) {
-    if ((rc = ensure(ctx, ctx->pf_ptr, (size_t)(t->n_prefixes + 1) * 4, false))) return rc;
-    if ((rc = ensure(ctx, ctx->pf_vtx, std::max<size_t>(t->n_entries, 1) * 4, false))) return rc;
-    if ((rc = ensure(ctx, ctx->pf_met, std::max<size_t>(t->n_entries, 1) * 4, false))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf_ptr.p, t->pfx_ptr, (size_t)(t->n_prefixes + 1) * 4, hipMemcpyHostToDevice, s));
-    if (t->n_entries) {
-      HIPCHK(ctx, hipMemcpyAsync(ctx->pf_vtx.p, t->pfx_vertex, (size_t)t->n_entries * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(ctx, hipMemcpyAsync(ctx->pf_met.p, t->pfx_metric, (size_t)t->n_entries * 4, hipMemcpyHostToDevice, s));
-    }
-    if (!ordered) {
-      ctx->pf_res_np = t->n_prefixes; ctx->pf_res_ne = t->n_entries; ctx->pf_res_ptr = t->pfx_ptr; ctx->pf_res_vtx = t->pfx_vertex;
-      ctx->pf_res_met = t->pfx_metric; ctx->pf_shadow_nv = n_vertices;
-      ctx->pf_shadow_ok = true;       // (the copies above are enqueued on the context's stream: every later use is ordered behind them)
-    }
+  if ((rc = ensure(ctx, ctx->pf_ptr, (size_t)(t->n_prefixes + 1) * 4, false))) return rc;
+  if ((rc = ensure(ctx, ctx->pf_vtx, std::max<size_t>(t->n_entries, 1) * 4, false))) return rc;
+  if ((rc = ensure(ctx, ctx->pf_met, std::max<size_t>(t->n_entries, 1) * 4, false))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pf_ptr.p, t->pfx_ptr, (size_t)(t->n_prefixes + 1) * 4, hipMemcpyHostToDevice, s));
+  if (t->n_entries) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pf_vtx.p, t->pfx_vertex, (size_t)t->n_entries * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pf_met.p, t->pfx_metric, (size_t)t->n_entries * 4, hipMemcpyHostToDevice, s));
   }
+  if (!ordered) {
+    ctx->pf_res_np = t->n_prefixes; ctx->pf_res_ne = t->n_entries; ctx->pf_res_ptr = t->pfx_ptr; ctx->pf_res_vtx = t->pfx_vertex;
+    ctx->pf_res_met = t->pfx_metric; ctx->pf_shadow_nv = n_vertices;
+    ctx->pf_shadow_ok = true;       // (the copies above are enqueued on the context's stream: every later use is ordered behind them)
+  }
+  return HSPF_OK;
+}
+
+static int routes_device_impl(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_roots, uint32_t n_mask_words,
+                              const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                              const hspf_prefix_table *t, hspf_routes *out) {
+  if (ctx) ctx->evs.valid = false;                        // a route call: the kept event stream (hspf_routes_events_rest) is void
+  if (!ctx || !t || !out || !dist_dev || !flags_dev || !mask_dev || !out->best_metric || !out->best_entry ||
+      !out->nexthop_mask || n_roots == 0 || n_mask_words == 0 || !t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric)))
+    return HSPF_E_INVAL;
+  int rc;
+  if ((rc = pfx_table_stage(ctx, nullptr, n_vertices, t))) return rc;
+  if (t->n_prefixes == 0) return HSPF_OK;
+  (void)hipSetDevice(ctx->device);
+  const bool ordered = (t->flags & HSPF_PFX_ORDERED) != 0;
+  hipStream_t s = ctx->stream;
   const uint8_t *d_iex = nullptr;
   const uint32_t *d_imet = nullptr, *d_iorg = nullptr;
   if (ordered) {
@@ -4051,6 +4061,66 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
     hipLaunchKernelGGL(k_tilfa_dest, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { ctx->last_error = std::string("k_tilfa: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return HSPF_OK;
+  });
+}
+
+// ---- per-prefix backup routes (include/holo_spf_hip.h "per-prefix backup routes on device"; kernels: spf_backup.hip.h) ----
+int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                              const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                              const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
+                              const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_routes_backup_device";
+    auto bad = [&](const std::string &what) { ctx->last_error = std::string(fn) + ": " + what; return HSPF_E_INVAL; };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
+    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
+      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
+    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric)) return bad("NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
+    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
+    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
+    const size_t stride = (size_t)64 * n_mask_words;
+    if ((size_t)n_prot * stride > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    int rc;
+    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    hipStream_t s = ctx->stream;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) {
+      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * HSPF_BK_COVERAGE_WORDS * 4, s));
+    if (t->n_prefixes) {
+      const uint32_t ign = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
+      if (max_k) {                                      // d(N_k, S) and d(N_k, N_p) of every protected root: k_lfa_gather's block, as for LFA
+        LfaArgs ga{};
+        ga.n = n_vertices; ga.W = n_mask_words; ga.ignore_overload = ign;
+        ga.dist = dist_dev; ga.flags = flags_dev; ga.mask = mask_dev;
+        ga.tab = (const uint32_t *)ctx->lfa_tab.p; ga.scal = (uint32_t *)ctx->lfa_scal.p;
+        const uint32_t gx = (uint32_t)std::min<size_t>(((size_t)max_k * ((size_t)max_k + 1) + 255) / 256, 1024);
+        hipLaunchKernelGGL(k_lfa_gather, dim3(gx, n_prot), dim3(256), 0, s, ga);
+      }
+      BackupArgs a{};
+      a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ign; a.stride = (uint32_t)stride;
+      a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
+      a.dist = dist_dev; a.flags = flags_dev;
+      a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (const uint32_t *)ctx->lfa_scal.p;
+      a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
+      a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
+      if (tilfa_dev) { a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric; }
+      a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
+      a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
+      const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
+      hipLaunchKernelGGL(k_backup, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
+      hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
+      const hipError_t le = hipGetLastError();
+      if (le != hipSuccess) { ctx->last_error = std::string("k_backup: ") + hipGetErrorString(le); return HSPF_E_HIP; }
+    }
     HIPCHK(ctx, hipStreamSynchronize(s));
     return HSPF_OK;
   });

@@ -48,6 +48,8 @@ TILFA_NONE, TILFA_NODE, TILFA_PAIR = 0, 1, 2                                  # 
 TILFA_D_LFA, TILFA_D_NODE, TILFA_D_PAIR, TILFA_D_NONE = 1, 2, 3, 4            # HSPF_TILFA_D_*: td_kind
 TILFA_COUNT_WORDS = 2
 TILFA_COVERAGE_WORDS = 5
+BK_NO_ROUTE, BK_LOCAL, BK_ECMP, BK_LFA, BK_NODE, BK_PAIR, BK_NONE = 0, 1, 2, 3, 4, 5, 6      # HSPF_BK_*: bk_kind
+BK_COVERAGE_WORDS = 7
 
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
@@ -234,6 +236,24 @@ class TilfaResult:
     ti_counts: np.ndarray    # [P, S, 2] u32 single nodes | usable (p, link) pairs
     td_kind: np.ndarray      # [P, N] u8  TILFA_D_* per destination with exactly one primary, 0 elsewhere
     td_coverage: np.ndarray  # [P, 5] u32
+
+
+@dataclass
+class BackupRoutes:
+    """Per-prefix routes of ONE root with their backups (SpfContext.backup_routes), on the host; one row each."""
+    candidates: LfaCandidates
+    best_metric: np.ndarray   # [1, P] u32      hspf_routes_device
+    best_entry: np.ndarray    # [1, P] u32
+    nexthop_mask: np.ndarray  # [1, P, W] u64
+    bk_kind: np.ndarray       # [1, P] u8  BK_*
+    bk_primary: np.ndarray    # [1, P] u32 the one primary slot for BK_LFA .. BK_NONE, LFA_NO_SLOT otherwise
+    bk_slot: np.ndarray       # [1, P] u32 BK_LFA: the alternate slot; BK_NODE / BK_PAIR: ti_via of the primary (may be RLFA_VIA_SELF)
+    bk_metric: np.ndarray     # [1, P] u32 BK_LFA: cost to the prefix; BK_NODE / BK_PAIR: the repair's cost to the primary's neighbour
+    bk_flags: np.ndarray      # [1, P] u8  LFA_NODE_PROTECT | LFA_DOWNSTREAM for BK_LFA
+    bk_cand_mask: np.ndarray  # [1, P, W] u64
+    bk_node_mask: np.ndarray  # [1, P, W] u64
+    bk_coverage: np.ndarray   # [1, 7] u32
+    tilfa: Optional["TilfaResult"] = None      # the per-slot repairs bk_primary indexes (remote=True)
 
 
 def csr_transpose(row_ptr, col, metric, vflags):
@@ -818,6 +838,53 @@ class SpfContext:
         if rc != 0:
             raise HspfError(rc, "hspf_tilfa_device", self.last_error())
 
+    def routes_backup_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
+                             pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
+                             bk_metric_ptr: int, bk_flags_ptr: int, bk_coverage_ptr: int, bk_cand_mask_ptr: int = 0, bk_node_mask_ptr: int = 0,
+                             tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> None:
+        """hspf_routes_backup_device(): per (protected root, prefix) the backup of the route hspf_routes_device wrote — an
+        alternate slot that is loop-free with respect to the PREFIX, or the per-link repair of the one primary.  `protect` as
+        for lfa_device(); the prefix table is host numpy as for routes_device() (`flags`: PFX_*; PFX_ORDERED is rejected);
+        routes = (best_metric_ptr, best_entry_ptr, nexthop_mask_ptr) of routes_device() on the same table set;
+        tilfa = (ti_kind_ptr, ti_via_ptr, ti_metric_ptr) of tilfa_device() for the same `protect`, or None.  All `*_ptr` are
+        device pointers; the two mask pointers may be 0."""
+        src = (pfx_ptr, pfx_vertex, pfx_metric)
+        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
+        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
+        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
+        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
+            raise ValueError("routes_backup_device: PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
+        org = None if pfx_origin is None else np.ascontiguousarray(pfx_origin, np.uint32)
+        arr, keep = self._protect_array(protect, "routes_backup_device")
+        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags,
+                              None if org is None else _u32(org), None, None, None)
+        r = L.HspfRoutes(*(x or None for x in routes))
+        ti = None
+        if tilfa is not None:
+            ti = L.HspfTilfaOut(tilfa[0] or None, None, None, tilfa[1] or None, None, tilfa[2] or None, None, None, None)
+        out = L.HspfBackupOut(bk_kind_ptr or None, bk_primary_ptr or None, bk_slot_ptr or None, bk_metric_ptr or None, bk_flags_ptr or None,
+                              bk_cand_mask_ptr or None, bk_node_mask_ptr or None, bk_coverage_ptr or None)
+        rc = self.lib.hspf_routes_backup_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                                arr, len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r),
+                                                None if ti is None else ctypes.byref(ti), ctypes.byref(out))
+        del keep
+        if rc != 0:
+            raise HspfError(rc, "hspf_routes_backup_device", self.last_error())
+
+    def backup_routes(self, graph: SpfGraph, root: int, prefix_table, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False,
+                      remote: bool = True) -> BackupRoutes:
+        """The routes of one root with their backups, start to finish: run_device() of [root] + its distinct neighbour routers,
+        routes_device(), lfa_device() and — with `remote` — rlfa_device() + tilfa_device() (on the transposed graph too unless
+        `symmetric`), then routes_backup_device(); only the route and bk_* arrays (and the per-slot repairs) come to the host.
+        prefix_table: an object with pfx_ptr / pfx_vertex / pfx_metric (holo_amd.routes.PrefixTable) and optionally `flags`
+        (PFX_SATURATING, PFX_LAST_MIN), or a tuple (pfx_ptr, pfx_vertex, pfx_metric[, flags])."""
+        if isinstance(prefix_table, (tuple, list)):
+            tab = tuple(prefix_table) + ((0,) if len(prefix_table) == 3 else ())
+        else:
+            tab = (prefix_table.pfx_ptr, prefix_table.pfx_vertex, prefix_table.pfx_metric, int(getattr(prefix_table, "flags", 0)))
+        tab = tuple(np.ascontiguousarray(a, np.uint32) for a in tab[:3]) + (int(tab[3]) & ~PFX_RESIDENT,)
+        return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab)
+
     def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False):
         """Remote alternates of one root, start to finish: the candidate table, run_device() of [root] + its distinct neighbour
         routers on `graph` and — unless `symmetric` says every link has its reverse at the same cost — on its transpose
@@ -830,7 +897,9 @@ class SpfContext:
         tilfa_device() on the same rows and space tables.  Returns (LfaCandidates, LfaResult, RlfaResult, TilfaResult)."""
         return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True)
 
-    def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool):
+    def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None):
+        """The chain behind rlfa(), tilfa() and backup_routes().  backup: None, or (pfx_ptr, pfx_vertex, pfx_metric, flags) — then
+        the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`)."""
         cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
         nbrs = np.unique(cand.nbr[cand.nbr != NO_ROOT])
         roots = np.concatenate([[root], nbrs]).astype(np.uint32)
@@ -851,9 +920,17 @@ class SpfContext:
             shapes.update(ti_kind=((1, S), np.uint8), ti_p=((1, S), np.uint32), ti_q=((1, S), np.uint32), ti_via=((1, S), np.uint32),
                           ti_link=((1, S), np.uint32), ti_metric=((1, S), np.uint32), ti_counts=((1, S, TILFA_COUNT_WORDS), np.uint32),
                           td_kind=((1, n), np.uint8), td_coverage=((1, TILFA_COVERAGE_WORDS), np.uint32))
+        bk_names = ("best_metric", "best_entry", "nexthop_mask", "bk_kind", "bk_primary", "bk_slot", "bk_metric", "bk_flags", "bk_cand_mask",
+                    "bk_node_mask", "bk_coverage")
+        if backup is not None:
+            NP = len(backup[0]) - 1
+            shapes.update(best_metric=((1, NP), np.uint32), best_entry=((1, NP), np.uint32), nexthop_mask=((1, NP, W), np.uint64),
+                          bk_kind=((1, NP), np.uint8), bk_primary=((1, NP), np.uint32), bk_slot=((1, NP), np.uint32), bk_metric=((1, NP), np.uint32),
+                          bk_flags=((1, NP), np.uint8), bk_cand_mask=((1, NP, W), np.uint64), bk_node_mask=((1, NP, W), np.uint64),
+                          bk_coverage=((1, BK_COVERAGE_WORDS), np.uint32))
         host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
         sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
-        sizes.update({k: a.nbytes for k, a in host.items()})
+        sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
         dev, GT = {}, None
         try:
             for k, b in sizes.items():
@@ -866,19 +943,36 @@ class SpfContext:
             protect = [(0, cand, nbr_row)]
             self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"],
                             alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
-            self.rlfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
-                             pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
-                             rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
-                             space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
-                             lfa_flags=lfa_flags)
+            if backup is None or tilfa:
+                self.rlfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
+                                 pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
+                                 rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
+                                 space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
+                                 lfa_flags=lfa_flags)
+            else:                                       # backup_routes(remote=False): nothing wrote the remote arrays, nothing reads them
+                for k in ("pq_node", "pq_via", "pq_metric", "pq_counts", "rl_node", "rl_via", "rl_cov"):
+                    del host[k]
             if tilfa:
                 self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
                                   space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
                                   **{k + "_ptr": dev[k] for k in ti_names})
+            if backup is not None:
+                self.routes_device(n, 1, W, dev["dist"], dev["flags"], dev["mask"], backup[0], backup[1], backup[2], flags=backup[3],
+                                   best_metric_ptr=dev["best_metric"], best_entry_ptr=dev["best_entry"], nexthop_mask_ptr=dev["nexthop_mask"])
+                self.routes_backup_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, backup[0], backup[1], backup[2],
+                                          routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
+                                          tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None,
+                                          flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags,
+                                          **{k + "_ptr": dev[k] for k in bk_names[3:]})
             for k, arr in host.items():
+                if not arr.nbytes:
+                    continue
                 rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
                 if rc != 0:
                     raise HspfError(rc, "hspf_device_to_host", self.last_error())
+            if backup is not None:
+                return BackupRoutes(cand, *(host[k] for k in bk_names),
+                                    tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None)
             lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])

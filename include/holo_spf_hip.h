@@ -879,6 +879,86 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
                       const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                       const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out *out_dev);
 
+/* ---- per-prefix backup routes on device (RFC 5286 section 6.1): new symbol, same ABI number --------------------------------
+ * hspf_lfa_device, hspf_rlfa_device and hspf_tilfa_device protect VERTICES and LINKS; what a RIB installs, and what
+ * hspf_routes_device delivers, is per PREFIX.  For a prefix with one advertiser the two agree; for a multi-homed prefix
+ * (anycast loopbacks, redistributed prefixes, an OSPF stub network on two routers) they do not: the loop-free inequality is
+ * evaluated against the neighbour's distance to the PREFIX, the minimum over all advertisers, not against its distance to the
+ * vertex S happens to use — a neighbour can be an alternate for the prefix and none for S's attaining vertex.
+ * hspf_routes_backup_device joins the tables: per (protected root, prefix) a backup next hop, or the per-link repair of the one
+ * primary link.  It takes no graph.
+ *
+ * Inputs.  The forward table set, `prot`, n_prot and lfa_flags are exactly those of hspf_lfa_device.  `table` is the HOST prefix
+ * table of hspf_routes_device: flags may be 0, HSPF_PFX_SATURATING, and HSPF_PFX_LAST_MIN together with either;
+ * HSPF_PFX_RESIDENT is honoured under hspf_routes_device's contract (the two calls share one staged copy: a table this call
+ * uploaded is resident for the next hspf_routes_device and the other way round).  routes_dev is what hspf_routes_device wrote for
+ * the same table set and table: protected root i reads row prot[i].root_row of it.  tilfa_dev: NULL (no remote fallback), or
+ * the hspf_tilfa_out hspf_tilfa_device wrote for the same `prot`; only ti_kind, ti_via and ti_metric are read.
+ *
+ * Per protected root S and prefix p; every sum is evaluated in 64 bits; a term that is HSPF_DIST_INF, or an advertiser whose
+ * vertex is not HSPF_RF_IN_SPT in the row, contributes nothing.
+ *   d_X(p)      for a row root X: the minimum over the entries (v, m) of p of d(X, v) + m.  With HSPF_PFX_SATURATING each
+ *               d(X, v) + m is first saturated at 0xFFFFFFFF as u32, as hspf_routes_device does (the saturated value is a
+ *               number, not "not reached").  HSPF_PFX_LAST_MIN changes nothing in d_X(p).
+ *   d_S(p)      routes.best_metric: read, not recomputed (a number whenever the route exists).  P = the bits of
+ *               routes.nexthop_mask[p] below n_slots, read as given (HSPF_PFX_LAST_MIN only changed which mask
+ *               hspf_routes_device left).  The route is absent when best_entry == 0xFFFFFFFF.
+ *   cand(p)     slot k with N = nbr[k] != HSPF_NO_ROOT iff  d_N(p) < d(N, S) + d_S(p),  and root_link[k] != root_link[e] for
+ *               every e in P,  and k is not in P,  and (cflags[k] has no HSPF_LFA_C_NO_TRANSIT, or the call passes
+ *               HSPF_LFA_IGNORE_OVERLOAD, or N's own entry (v == N) attains d_N(p): N delivers without transiting)
+ *   node(p)     k in cand(p), P has at least one slot whose nbr is a router, and for every such slot with E its nbr:
+ *               d_N(p) < d(N, E) + d_E(p)
+ *   downstream  d_N(p) < d_S(p)
+ *   choice      only when popcount(P) == 1: a member of node before a member of cand only, then the smallest cost[k] + d_N(p)
+ *               (64 bits), then the smallest k — the rule of hspf_lfa_device with p in place of D
+ *   fallback    popcount(P) == 1 with e the one primary slot, no slot chosen, tilfa_dev given and ti_kind[e] != HSPF_TILFA_NONE:
+ *               the per-link repair of e backs up the prefix (it delivers to E = nbr[e], and E is S's next hop towards p)
+ * Outputs (DEVICE pointers, [n_prot][n_prefixes] unless stated):
+ *   bk_kind u8     HSPF_BK_NO_ROUTE no route | _LOCAL a route and P is empty | _ECMP popcount(P) >= 2 | _LFA an alternate slot
+ *                  was chosen | _NODE / _PAIR the one- / two-segment repair of the primary link | _NONE one primary, nothing found
+ *   bk_primary     the one primary slot e for HSPF_BK_LFA .. HSPF_BK_NONE (the consumer indexes ti_p / ti_q / ti_link with it),
+ *                  HSPF_LFA_NO_SLOT otherwise
+ *   bk_slot        _LFA: the chosen slot; _NODE / _PAIR: ti_via[e] (may be HSPF_RLFA_VIA_SELF); HSPF_LFA_NO_SLOT otherwise
+ *   bk_metric      _LFA: cost[k] + d_N(p) saturated at 0xFFFFFFFE; _NODE / _PAIR: ti_metric[e] — the repair's cost to E, NOT a
+ *                  cost to p; 0 otherwise
+ *   bk_flags u8    _LFA: HSPF_LFA_NODE_PROTECT | HSPF_LFA_DOWNSTREAM with the bit values of alt_flags; 0 otherwise
+ *   bk_cand_mask / bk_node_mask   u64 [n_prot][n_prefixes][n_mask_words], optional (NULL skips the table): the two sets for
+ *                  HSPF_BK_ECMP .. HSPF_BK_NONE, zero elsewhere
+ *   bk_coverage    u32 [n_prot][HSPF_BK_COVERAGE_WORDS], counted on the device: the number of prefixes of each kind, 0 .. 6
+ * Argument errors — a NULL required pointer, everything hspf_lfa_device rejects in `prot`, HSPF_PFX_ORDERED, everything the
+ * table checks of hspf_routes_device reject — return HSPF_E_INVAL with a text in hspf_last_error that names
+ * hspf_routes_backup_device, before any kernel is launched.  Everything is enqueued on the context's stream; the call
+ * synchronises once at the end.
+ *
+ * From bk_* to a next hop with a backup and its label stack: INTEGRATION.md §5k.
+ *
+ * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (the other primaries
+ * are the backups; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
+ * td_kind); node-protecting remote repairs; loop-freeness with respect to a LAN pseudonode (the same limitation as
+ * hspf_lfa_device).  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
+#define HSPF_BK_NO_ROUTE       0u
+#define HSPF_BK_LOCAL          1u
+#define HSPF_BK_ECMP           2u
+#define HSPF_BK_LFA            3u
+#define HSPF_BK_NODE           4u
+#define HSPF_BK_PAIR           5u
+#define HSPF_BK_NONE           6u
+#define HSPF_BK_COVERAGE_WORDS 7u
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint8_t  *bk_kind;             /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bk_primary;          /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bk_slot;             /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bk_metric;           /* [n_prot][n_prefixes]                                                       */
+  uint8_t  *bk_flags;            /* [n_prot][n_prefixes]                                                       */
+  uint64_t *bk_cand_mask;        /* [n_prot][n_prefixes][n_mask_words] or NULL                                 */
+  uint64_t *bk_node_mask;        /* [n_prot][n_prefixes][n_mask_words] or NULL                                 */
+  uint32_t *bk_coverage;         /* [n_prot][HSPF_BK_COVERAGE_WORDS]                                           */
+} hspf_backup_out;
+int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                              const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                              const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *table,
+                              const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev);
+
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root
  * wavefront batches are dealt to the ranks (hspf_shard_bounds), every rank runs its slice, and ONE all-gather per

@@ -138,6 +138,19 @@ struct Tilfa {
   uint32_t td_coverage[HSPF_TILFA_COVERAGE_WORDS] = {};
 };
 
+// Per-prefix backup routes (hspf_routes_device + hspf_routes_backup_device) of one protected root on the host: the route of every
+// prefix, its backup (HSPF_BK_*), and the per-slot repairs bk_primary indexes (ti_* of `tilfa`: empty without `remote`).
+struct BackupRoutes {
+  Tilfa tilfa;                                  // (with remote; without it only tilfa.rlfa.lfa is filled)
+  uint32_t n_prefixes = 0;
+  std::vector<uint32_t> best_metric, best_entry;          // [n_prefixes]
+  std::vector<uint64_t> nexthop_mask;                     // [n_prefixes][mask_words]
+  std::vector<uint8_t> bk_kind, bk_flags;                 // [n_prefixes]
+  std::vector<uint32_t> bk_primary, bk_slot, bk_metric;   // [n_prefixes]
+  std::vector<uint64_t> bk_cand_mask, bk_node_mask;       // [n_prefixes][mask_words]
+  uint32_t bk_coverage[HSPF_BK_COVERAGE_WORDS] = {};
+};
+
 class Engine;
 
 // The engine context, shared by the Engine and every Graph made from it: a Graph that outlives its Engine (members
@@ -384,7 +397,7 @@ class Engine {
   Rlfa rlfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
             const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
             bool symmetric = false, bool with_spaces = false) {
-    return rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, with_spaces, nullptr);
+    return rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, with_spaces, nullptr, nullptr, nullptr);
   }
   // hspf_tilfa_device on DEVICE tables: those of rlfa_device plus the space tables it wrote (required); `g` is the FORWARD graph.
   void tilfa_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
@@ -399,8 +412,32 @@ class Engine {
               const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
               bool symmetric = false) {
     Tilfa t;
-    t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, &t);
+    t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, &t, nullptr, nullptr);
     return t;
+  }
+  // hspf_routes_backup_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the routes
+  // hspf_routes_device wrote for it, optionally the per-slot arrays of tilfa_device (nullptr: no remote fallback).
+  void routes_backup_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                            const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const hspf_prefix_table &table,
+                            const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out out_dev) {
+    const int rc = hspf_routes_backup_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                             lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // One root start to finish: the chain of tilfa() (of lfa() alone without `remote`), hspf_routes_device for the root's row and
+  // hspf_routes_backup_device, everything kept on the device in between.  table_flags: HSPF_PFX_SATURATING / HSPF_PFX_LAST_MIN.
+  BackupRoutes backup_routes(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                             const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, const std::vector<uint32_t> &pfx_ptr,
+                             const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric, uint32_t table_flags = 0,
+                             uint32_t run_flags = 0, uint32_t lfa_flags = 0, bool symmetric = false, bool remote = true) {
+    if (pfx_ptr.empty() || pfx_vertex.size() != pfx_metric.size()) throw Error(HSPF_E_INVAL, "Engine::backup_routes: malformed prefix table");
+    BackupRoutes b;
+    b.n_prefixes = (uint32_t)pfx_ptr.size() - 1u;
+    const hspf_prefix_table t{b.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.data(), pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT,
+                              nullptr, nullptr, nullptr, nullptr};
+    b.tilfa.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric || !remote, remote,
+                             remote ? &b.tilfa : nullptr, &b, &t);
+    return b;
   }
   void wait_all() { (void)hspf_wait_all(ctx_); }
   uint32_t async_lanes() const { return hspf_async_lanes(ctx_); }
@@ -410,10 +447,11 @@ class Engine {
   }
 
  private:
-  // rlfa(); with `ti` the two-segment step runs on the same device tables before anything is freed
+  // rlfa(); with `ti` the two-segment step runs on the same device tables before anything is freed; with `bk` the routes of `table`
+  // and their backups are derived there too (without `ti` the remote-LFA call is skipped: nothing reads it)
   Rlfa rlfa_impl(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
                  const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags, uint32_t lfa_flags,
-                 bool symmetric, bool with_spaces, Tilfa *ti) {
+                 bool symmetric, bool with_spaces, Tilfa *ti, BackupRoutes *bk, const hspf_prefix_table *table) {
     if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
       throw Error(HSPF_E_INVAL, "Engine::rlfa: the CSR is not the one the graph was uploaded from");
     Rlfa r;
@@ -449,6 +487,8 @@ class Engine {
     const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
     lfa_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags,
                hspf_lfa_out{slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), nullptr, nullptr, cov.as<uint32_t>()});
+    const bool remote = !bk || ti;
+    if (remote)
     rlfa_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(), {p},
                 lfa_flags, fl.as<uint8_t>(),
                 hspf_rlfa_out{pq_node.as<uint32_t>(), pq_via.as<uint32_t>(), pq_metric.as<uint32_t>(), pq_counts.as<uint32_t>(),
@@ -457,14 +497,17 @@ class Engine {
     r.lfa.alt_slot = slot.to_host<uint32_t>(n); r.lfa.alt_metric = met.to_host<uint32_t>(n); r.lfa.alt_flags = fl.to_host<uint8_t>(n);
     const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
     std::copy(cv.begin(), cv.end(), r.lfa.coverage);
+    if (remote) {
     r.pq_node = pq_node.to_host<uint32_t>(S); r.pq_via = pq_via.to_host<uint32_t>(S); r.pq_metric = pq_metric.to_host<uint32_t>(S);
     r.pq_counts = pq_counts.to_host<uint32_t>((size_t)S * HSPF_RLFA_COUNT_WORDS);
     if (with_spaces) { r.space_flags = sp_flags.to_host<uint8_t>(sn); r.space_via = sp_via.to_host<uint32_t>(sn); }
     r.rl_node = rl_node.to_host<uint32_t>(n); r.rl_via = rl_via.to_host<uint32_t>(n);
     const std::vector<uint32_t> rc4 = rl_cov.to_host<uint32_t>(HSPF_RLFA_COVERAGE_WORDS);
     std::copy(rc4.begin(), rc4.end(), r.rl_coverage);
+    }
+    DeviceBuffer kind(ctx_, ti ? S : 0), tv(ctx_, ti ? S * 4 : 0), tm(ctx_, ti ? S * 4 : 0);
     if (ti) {
-      DeviceBuffer kind(ctx_, S), tp(ctx_, S * 4), tq(ctx_, S * 4), tv(ctx_, S * 4), tl(ctx_, S * 4), tm(ctx_, S * 4),
+      DeviceBuffer tp(ctx_, S * 4), tq(ctx_, S * 4), tl(ctx_, S * 4),
           tc(ctx_, (size_t)S * 4 * HSPF_TILFA_COUNT_WORDS), dk(ctx_, n), dc(ctx_, HSPF_TILFA_COVERAGE_WORDS * 4);
       tilfa_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(), {p},
                    lfa_flags, fl.as<uint8_t>(), sp_flags.as<uint8_t>(), sp_via.as<uint32_t>(),
@@ -475,6 +518,26 @@ class Engine {
       ti->ti_counts = tc.to_host<uint32_t>((size_t)S * HSPF_TILFA_COUNT_WORDS); ti->td_kind = dk.to_host<uint8_t>(n);
       const std::vector<uint32_t> c5 = dc.to_host<uint32_t>(HSPF_TILFA_COVERAGE_WORDS);
       std::copy(c5.begin(), c5.end(), ti->td_coverage);
+    }
+    if (bk) {
+      const size_t np = table->n_prefixes, nz = std::max<size_t>(np, 1);
+      DeviceBuffer bm(ctx_, nz * 4), be(ctx_, nz * 4), nh(ctx_, nz * 8 * W), kk(ctx_, nz), pp(ctx_, nz * 4), ss(ctx_, nz * 4), mm(ctx_, nz * 4), ff(ctx_, nz),
+          cmk(ctx_, nz * 8 * W), nmk(ctx_, nz * 8 * W), cv7(ctx_, HSPF_BK_COVERAGE_WORDS * 4);
+      hspf_routes ro{bm.as<uint32_t>(), be.as<uint32_t>(), nh.as<uint64_t>()};
+      rc = hspf_routes_device(ctx_, n, 1, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), table, &ro);
+      if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_device (") + hspf_last_error(ctx_) + ")");
+      hspf_prefix_table tr = *table;
+      tr.flags |= HSPF_PFX_RESIDENT;                      // the arrays hspf_routes_device has just staged
+      const hspf_tilfa_out tio{kind.as<uint8_t>(), nullptr, nullptr, tv.as<uint32_t>(), nullptr, tm.as<uint32_t>(), nullptr, nullptr, nullptr};
+      routes_backup_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, tr, ro, ti ? &tio : nullptr,
+                           hspf_backup_out{kk.as<uint8_t>(), pp.as<uint32_t>(), ss.as<uint32_t>(), mm.as<uint32_t>(), ff.as<uint8_t>(), cmk.as<uint64_t>(),
+                                           nmk.as<uint64_t>(), cv7.as<uint32_t>()});
+      bk->best_metric = bm.to_host<uint32_t>(np); bk->best_entry = be.to_host<uint32_t>(np); bk->nexthop_mask = nh.to_host<uint64_t>(np * W);
+      bk->bk_kind = kk.to_host<uint8_t>(np); bk->bk_primary = pp.to_host<uint32_t>(np); bk->bk_slot = ss.to_host<uint32_t>(np);
+      bk->bk_metric = mm.to_host<uint32_t>(np); bk->bk_flags = ff.to_host<uint8_t>(np);
+      bk->bk_cand_mask = cmk.to_host<uint64_t>(np * W); bk->bk_node_mask = nmk.to_host<uint64_t>(np * W);
+      const std::vector<uint32_t> c7 = cv7.to_host<uint32_t>(HSPF_BK_COVERAGE_WORDS);
+      std::copy(c7.begin(), c7.end(), bk->bk_coverage);
     }
     return r;
   }

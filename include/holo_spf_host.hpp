@@ -139,9 +139,23 @@ struct TilfaOut {
   std::vector<uint8_t> td_kind;                             // [n_protected][n_vertices] HSPF_TILFA_D_*
   std::vector<uint32_t> td_coverage;                        // [n_protected][HSPF_TILFA_COVERAGE_WORDS]
 };
+// Per-prefix backup routes (hspf_routes_backup_device) of the same protected roots over the prefix table of a DeviceRoutes: per
+// (protected root, prefix) the kind of backup (HSPF_BK_*), the primary slot, the backup slot / metric / flags.  `tilfa`: nullptr, or
+// what tilfa() returned for the same protect list (the fallback to the primary link's repair).  supported == false: no such call.
+struct BackupOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_prefixes = 0, mask_words = 1;
+  std::vector<uint8_t> bk_kind, bk_flags;                   // [n_protected][n_prefixes]
+  std::vector<uint32_t> bk_primary, bk_slot, bk_metric;
+  std::vector<uint64_t> bk_cand_mask, bk_node_mask;         // [n_protected][n_prefixes][mask_words]
+  std::vector<uint32_t> bk_coverage;                        // [n_protected][HSPF_BK_COVERAGE_WORDS]
+};
 class Engine {
  public:
   virtual ~Engine() = default;
+  // `routes`: what routes_device() wrote for `run` and the prefix table.  The default: not supported.
+  virtual BackupOut backup_routes(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
+                                  const TilfaOut * /*tilfa*/) { return BackupOut{}; }
   // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph.  The default: not supported.
   virtual TilfaOut tilfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                          const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/) { return TilfaOut{}; }

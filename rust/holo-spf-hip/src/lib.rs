@@ -389,6 +389,22 @@ impl PrefixTable {
     }
 }
 
+/// Per-prefix backup routes of one `routes_backup_device` call, on the host: `[n_protected][n_prefixes]` (the masks with `words`
+/// words per entry), `bk_coverage` `[n_protected][HSPF_BK_COVERAGE_WORDS]`; `bk_kind` holds `HSPF_BK_*`.
+pub struct Backup {
+    pub n_protected: u32,
+    pub n_prefixes: u32,
+    pub words: u32,
+    pub bk_kind: Vec<u8>,
+    pub bk_primary: Vec<u32>,
+    pub bk_slot: Vec<u32>,
+    pub bk_metric: Vec<u32>,
+    pub bk_flags: Vec<u8>,
+    pub bk_cand_mask: Vec<u64>,
+    pub bk_node_mask: Vec<u64>,
+    pub bk_coverage: Vec<u32>,
+}
+
 /// Route tables of one `routes_device` call (or an uploaded set) in HBM: `hspf_routes`.
 pub struct DeviceRoutes<'e> {
     pub n_roots: u32,
@@ -849,6 +865,124 @@ impl Engine {
             ti_counts: ti_counts.to_host(slots * sys::HSPF_TILFA_COUNT_WORDS as usize)?,
             td_kind: td_kind.to_host(cells)?,
             td_coverage: td_cov.to_host(np * sys::HSPF_TILFA_COVERAGE_WORDS as usize)?,
+        })
+    }
+
+    /// `hspf_routes_backup_device`: per (protected root, prefix) the backup of the route `routes_device` wrote for the same
+    /// `tables` and `table` — an alternate slot that is loop-free with respect to the PREFIX, or the repair of the one primary
+    /// link out of `tilfa` (what `tilfa_device` returned for the same `protect`; `None`: no remote fallback).  `resident`: the
+    /// context still holds `table` from the `routes_device` call.
+    pub fn routes_backup_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool,
+                                table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
+        let (np, pf, w) = (protect.len(), table.n_prefixes() as usize, tables.words as usize);
+        if routes.n_prefixes != table.n_prefixes() || routes.words != tables.words {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_device: the routes are not of this table set and table".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let slots = np * 64 * w;
+        let ti = match tilfa {
+            Some(t) if t.ti_kind.len() == slots && t.ti_via.len() == slots && t.ti_metric.len() == slots => {
+                Some((self.device_from(&t.ti_kind)?, self.device_from(&t.ti_via)?, self.device_from(&t.ti_metric)?))
+            }
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_device: the TI-LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let ti_raw = ti.as_ref().map(|(k, v, m)| sys::hspf_tilfa_out {
+            ti_kind: k.p as *mut u8,
+            ti_p: ptr::null_mut(),
+            ti_q: ptr::null_mut(),
+            ti_via: v.p as *mut u32,
+            ti_link: ptr::null_mut(),
+            ti_metric: m.p as *mut u32,
+            ti_counts: ptr::null_mut(),
+            td_kind: ptr::null_mut(),
+            td_coverage: ptr::null_mut(),
+        });
+        let cells = np * pf;
+        let bk_kind = self.device_alloc(cells)?;
+        let bk_primary = self.device_alloc(cells * 4)?;
+        let bk_slot = self.device_alloc(cells * 4)?;
+        let bk_metric = self.device_alloc(cells * 4)?;
+        let bk_flags = self.device_alloc(cells)?;
+        let bk_cand = self.device_alloc(cells * 8 * w)?;
+        let bk_node = self.device_alloc(cells * 8 * w)?;
+        let bk_cov = self.device_alloc(np * sys::HSPF_BK_COVERAGE_WORDS as usize * 4)?;
+        let mut out = sys::hspf_backup_out {
+            bk_kind: bk_kind.p as *mut u8,
+            bk_primary: bk_primary.p as *mut u32,
+            bk_slot: bk_slot.p as *mut u32,
+            bk_metric: bk_metric.p as *mut u32,
+            bk_flags: bk_flags.p as *mut u8,
+            bk_cand_mask: bk_cand.p as *mut u64,
+            bk_node_mask: bk_node.p as *mut u64,
+            bk_coverage: bk_cov.p as *mut u32,
+        };
+        let t = sys::hspf_prefix_table {
+            n_prefixes: table.n_prefixes(),
+            n_entries: table.pfx_vertex.len() as u32,
+            pfx_ptr: table.pfx_ptr.as_ptr(),
+            pfx_vertex: table.pfx_vertex.as_ptr(),
+            pfx_metric: table.pfx_metric.as_ptr(),
+            flags: table.flags | if resident { sys::HSPF_PFX_RESIDENT } else { 0 },
+            pfx_origin: ptr::null(),
+            init_exists: ptr::null(),
+            init_metric: ptr::null(),
+            init_origin: ptr::null(),
+        };
+        let r = sys::hspf_routes {
+            best_metric: routes.best_metric.p as *mut u32,
+            best_entry: routes.best_entry.p as *mut u32,
+            nexthop_mask: routes.nexthop_mask.p as *mut u64,
+        };
+        let rc = unsafe {
+            sys::hspf_routes_backup_device(
+                self.ctx,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
+                &t,
+                &r,
+                ti_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_out),
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(Backup {
+            n_protected: np as u32,
+            n_prefixes: table.n_prefixes(),
+            words: tables.words,
+            bk_kind: bk_kind.to_host(cells)?,
+            bk_primary: bk_primary.to_host(cells)?,
+            bk_slot: bk_slot.to_host(cells)?,
+            bk_metric: bk_metric.to_host(cells)?,
+            bk_flags: bk_flags.to_host(cells)?,
+            bk_cand_mask: bk_cand.to_host(cells * w)?,
+            bk_node_mask: bk_node.to_host(cells * w)?,
+            bk_coverage: bk_cov.to_host(np * sys::HSPF_BK_COVERAGE_WORDS as usize)?,
         })
     }
 
