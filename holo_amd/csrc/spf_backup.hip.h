@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "spf_lfa.hip.h"
+#include "spf_frr_common.hip.h"
 
 namespace {
 
@@ -64,34 +64,24 @@ __device__ __forceinline__ bool bk_less(uint64_t x, uint32_t b, uint64_t c) {
 
 __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
   const uint32_t pi = blockIdx.y;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t srow = hdr[1], K = hdr[2], C = hdr[3];
-  const uint32_t n = a.n, W = a.W, Wk = (K + 63u) >> 6;
-  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K, *rl = nbr + 3 * K, *cf = nbr + 4 * K, *cl = nbr + 5 * K;
-  const uint32_t *dns = a.scal + hdr[5], *m = dns + K;
+  const FrrTab tb = frr_tab(a.tab, a.scal, pi);
+  const uint32_t K = tb.K, C = tb.C, n = a.n, W = a.W, Wk = tb.Wk;
   const uint32_t p = blockIdx.x * LFA_TILE + threadIdx.x;
   if (p >= a.n_pfx) return;                                                        // (no barrier below)
-  const size_t oi = (size_t)srow * a.n_pfx + p, oo = (size_t)pi * a.n_pfx + p;
+  const size_t oi = (size_t)tb.srow * a.n_pfx + p, oo = (size_t)pi * a.n_pfx + p;
   const uint32_t lo = a.pfx_ptr[p], hi = a.pfx_ptr[p + 1];
   const bool route = a.best_entry[oi] != LFA_NONE;
   const uint64_t dSp = a.best_metric[oi];
-  const uint64_t last_word = (K & 63u) ? ((1ull << (K & 63u)) - 1ull) : ~0ull;     // slots of the last word that exist
   const uint64_t *pm = a.nh_mask + oi * W;
-  // the primaries: how many, and the first one
   uint32_t np = 0, p0 = 0;
-  if (route)
-    for (uint32_t w = 0; w < Wk; ++w) {
-      const uint64_t x = pm[w] & (w + 1 == Wk ? last_word : ~0ull);
-      if (x && !np) p0 = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-      np += (uint32_t)__popcll(x);
-    }
+  if (route) frr_primaries(tb, pm, np, p0);
   uint32_t kind = !route ? 0u : np == 0 ? 1u : np >= 2 ? 2u : 6u;
   const bool sets = kind >= 2;                                                     // the two sets are evaluated and written
   uint32_t rl0 = LFA_NONE, E0 = LFA_NONE;
   uint64_t dE0p = BK_NO_DIST;
   if (np == 1) {
-    rl0 = rl[p0]; E0 = nbr[p0];
-    if (E0 != LFA_NONE) dE0p = bk_dist_to_prefix(a, row[p0], lo, hi);
+    rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
+    if (E0 != LFA_NONE) dE0p = bk_dist_to_prefix(a, tb.row[p0], lo, hi);
   }
   bool have = false, bnode = false, bdown = false;
   uint64_t bsum = 0, cw = 0, nw = 0;
@@ -108,9 +98,9 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
 #pragma unroll
         for (uint32_t j = 0; j < BK_CH; ++j) {
           if (c0 + j >= C) break;
-          const uint32_t k = cl[c0 + j];
-          const uint64_t t = bk_term(a, (size_t)row[k] * n + v, met);
-          const bool mine = v == nbr[k];
+          const uint32_t k = tb.cl[c0 + j];
+          const uint64_t t = bk_term(a, (size_t)tb.row[k] * n + v, met);
+          const bool mine = v == tb.nbr[k];
           if (t < dNp[j]) { dNp[j] = t; own = (own & ~(1u << j)) | ((mine ? 1u : 0u) << j); }
           else if (t == dNp[j] && mine && t != BK_NO_DIST) own |= 1u << j;
         }
@@ -118,7 +108,7 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
 #pragma unroll
     for (uint32_t j = 0; j < BK_CH; ++j) {
       if (c0 + j >= C) break;
-      const uint32_t k = cl[c0 + j];                                               // ascending, the same for every lane
+      const uint32_t k = tb.cl[c0 + j];                                            // ascending, the same for every lane
       while (wi < (k >> 6)) {                                                      // the words in front of slot k are complete
         if (a.cand_mask) a.cand_mask[oo * W + wi] = cw;
         if (a.node_mask) a.node_mask[oo * W + wi] = nw;
@@ -126,28 +116,28 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
       }
       if (!sets) continue;
       const uint64_t d = dNp[j];
-      if (!bk_less(d, dns[k], dSp)) continue;                                      // loop-free with respect to the prefix
-      if ((cf[k] & 1u) && !a.ignore_overload && !((own >> j) & 1u)) continue;      // an overloaded neighbour carries no transit traffic
+      if (!bk_less(d, tb.dns[k], dSp)) continue;                                   // loop-free with respect to the prefix
+      if ((tb.cf[k] & 1u) && !a.ignore_overload && !((own >> j) & 1u)) continue;   // an overloaded neighbour carries no transit traffic
       bool ok, nd = false;
       if (np == 1) {
-        ok = rl[k] != rl0;                                                         // (k == p0 has p0's root_link)
-        nd = ok && E0 != LFA_NONE && dE0p != BK_NO_DIST && bk_less(d, m[k * K + p0], dE0p);
+        ok = tb.rl[k] != rl0;                                                      // (k == p0 has p0's root_link)
+        nd = ok && E0 != LFA_NONE && dE0p != BK_NO_DIST && bk_less(d, tb.m[k * K + p0], dE0p);
       } else {
         ok = !((pm[k >> 6] >> (k & 63u)) & 1ull);
         uint32_t n_router = 0;
         bool all = true;
-        const uint32_t rlk = rl[k];
+        const uint32_t rlk = tb.rl[k];
         for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
-          uint64_t x = pm[w2] & (w2 + 1 == Wk ? last_word : ~0ull);
+          uint64_t x = frr_word(tb, pm, w2);
           while (x) {
             const uint32_t q = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
             x &= x - 1;
-            if (rl[q] == rlk) { ok = false; break; }
-            if (nbr[q] != LFA_NONE) {
+            if (tb.rl[q] == rlk) { ok = false; break; }
+            if (tb.nbr[q] != LFA_NONE) {
               ++n_router;
               if (all) {
-                const uint64_t dEp = bk_dist_to_prefix(a, row[q], lo, hi);
-                all = dEp != BK_NO_DIST && bk_less(d, m[k * K + q], dEp);
+                const uint64_t dEp = bk_dist_to_prefix(a, tb.row[q], lo, hi);
+                all = dEp != BK_NO_DIST && bk_less(d, tb.m[k * K + q], dEp);
               }
             }
           }
@@ -158,7 +148,7 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
       cw |= 1ull << (k & 63u);
       if (nd) nw |= 1ull << (k & 63u);
       if (np == 1) {
-        const uint64_t sum = (uint64_t)cost[k] + d;
+        const uint64_t sum = (uint64_t)tb.cost[k] + d;
         if (!have || (nd && !bnode) || (nd == bnode && sum < bsum)) {              // ascending slot order: a tie keeps the smaller slot
           have = true; bnode = nd; bsum = sum; aslot = k; bdown = d < dSp;
         }

@@ -1,0 +1,361 @@
+// spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
+// hspf_csr_transpose, hspf_rlfa_device, hspf_tilfa_device, hspf_routes_backup_device.  Included by spf_capi.hip (one TU).
+//
+// The four device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
+// one frame: argument checks, lfa_stage, k_lfa_gather where the kernels need the per-root scalars, the call's own kernels,
+// frr_finish.  `fn` names the calling entry point in hspf_last_error.
+#pragma once
+
+#include "spf_lfa.hip.h"
+#include "spf_rlfa.hip.h"
+#include "spf_tilfa.hip.h"
+#include "spf_backup.hip.h"
+
+namespace {
+
+int frr_bad(hspf_ctx *ctx, const char *fn, const std::string &what) { ctx->last_error = std::string(fn) + ": " + what; return HSPF_E_INVAL; }
+
+int frr_check_dims(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, uint32_t n_prot) {
+  if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20))
+    return frr_bad(ctx, fn, "n_vertices, n_rows, n_mask_words or n_prot out of range");
+  return HSPF_OK;
+}
+
+int frr_check_graph(hspf_ctx *ctx, const char *fn, const hspf_graph *g, uint32_t n_vertices) {
+  if (g->invalid) return frr_bad(ctx, fn, "the graph is invalid after a failed hspf_graph_patch (free it and upload again)");
+  if (g->n != n_vertices) return frr_bad(ctx, fn, "n_vertices is not the graph's");
+  return HSPF_OK;
+}
+
+// The checks of the protected roots, and the staged block (its layout: spf_frr_common.hip.h) copied to ctx->lfa_tab on the context's
+// stream, with ctx->lfa_scal sized for k_lfa_gather.  `tab` is the copy's source: it lives until the caller has synchronised.
+int lfa_stage(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const hspf_lfa_protect *prot,
+                     uint32_t n_prot, std::vector<uint32_t> &tab, uint32_t *out_max_k) {
+  auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+  size_t tab_words = (size_t)n_prot * LFA_HDR_WORDS, scal_words = 0;
+  uint32_t max_k = 0;
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const hspf_lfa_protect &p = prot[i];
+    const std::string who = "protected root " + std::to_string(i) + ": ";
+    if (p.root_row >= n_rows) return bad(who + "root_row >= n_rows");
+    if (p.root_vertex >= n_vertices) return bad(who + "root_vertex >= n_vertices");
+    if (p.n_slots > 64ull * n_mask_words) return bad(who + "n_slots > 64 * n_mask_words");
+    if (p.n_slots && (!p.nbr || !p.nbr_row || !p.cost || !p.root_link || !p.cflags)) return bad(who + "NULL slot array");
+    for (uint32_t k = 0; k < p.n_slots; ++k) {
+      if (p.nbr[k] == HSPF_NO_ROOT) continue;
+      if (p.nbr[k] >= n_vertices) return bad(who + "nbr of slot " + std::to_string(k) + " >= n_vertices");
+      if (p.nbr_row[k] >= n_rows) return bad(who + "nbr_row of slot " + std::to_string(k) + " >= n_rows");
+    }
+    tab_words += (size_t)FRR_COLS * p.n_slots;
+    scal_words += (size_t)p.n_slots * ((size_t)p.n_slots + 1);
+    max_k = std::max(max_k, p.n_slots);
+  }
+  if (tab_words > (1u << 28) || scal_words > (1u << 28)) { ctx->last_error = std::string(fn) + ": the slot tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
+  tab.assign(tab_words, 0u);
+  size_t to = (size_t)n_prot * LFA_HDR_WORDS, so = 0;
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const hspf_lfa_protect &p = prot[i];
+    const uint32_t K = p.n_slots;
+    uint32_t *h = tab.data() + (size_t)i * LFA_HDR_WORDS, *t = tab.data() + to;
+    uint32_t C = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+      const bool c = p.nbr[k] != HSPF_NO_ROOT;
+      t[k] = p.nbr[k]; t[K + k] = c ? p.nbr_row[k] : 0u; t[2 * K + k] = p.cost[k]; t[3 * K + k] = p.root_link[k];
+      t[4 * K + k] = c ? p.cflags[k] : 0u;
+      if (c) t[5 * K + C++] = k;
+    }
+    h[0] = p.root_vertex; h[1] = p.root_row; h[2] = K; h[3] = C; h[4] = (uint32_t)to; h[5] = (uint32_t)so;
+    to += (size_t)FRR_COLS * K; so += (size_t)K * ((size_t)K + 1);
+  }
+  (void)hipSetDevice(ctx->device);
+  int rc;
+  if ((rc = ensure(ctx, ctx->lfa_tab, tab_words * 4, false))) return rc;
+  if ((rc = ensure(ctx, ctx->lfa_scal, std::max<size_t>(scal_words, 1) * 4, false))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->lfa_tab.p, tab.data(), tab_words * 4, hipMemcpyHostToDevice, ctx->stream));
+  *out_max_k = max_k;
+  return HSPF_OK;
+}
+
+// k_lfa_gather on the staged block: d(N_k, S) and d(N_k, N_p) of every protected root.  Returns the arguments it launched with
+// (hspf_lfa_device goes on with them).
+LfaArgs frr_gather(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words, uint32_t lfa_flags, const uint32_t *dist_dev,
+                   const uint16_t *flags_dev, const uint64_t *mask_dev, uint32_t n_prot, uint32_t max_k) {
+  LfaArgs a{};
+  a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
+  a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev;
+  a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (uint32_t *)ctx->lfa_scal.p;
+  if (max_k) {
+    const uint32_t gx = (uint32_t)std::min<size_t>(((size_t)max_k * ((size_t)max_k + 1) + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_lfa_gather, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a);
+  }
+  return a;
+}
+
+// the end of a call: a launch error is reported under the name of its kernels; then the stream is drained
+int frr_finish(hspf_ctx *ctx, const char *kernels) {
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) { ctx->last_error = std::string(kernels) + ": " + hipGetErrorString(le); return HSPF_E_HIP; }
+  hipStream_t s = ctx->stream;
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  return HSPF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- loop-free alternates (include/holo_spf_hip.h "loop-free alternates on device"; kernels: spf_lfa.hip.h) ----------------
+int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *nbr, uint32_t *cost, uint32_t *root_link,
+                        uint8_t *cflags, uint32_t *out_total_slots) {
+  if (!csr || !csr->row_ptr || !csr->vflags || (csr->n_edges && (!csr->col || !csr->metric)) || root >= csr->n_vertices) return HSPF_E_INVAL;
+  return guarded(nullptr, [&]() -> int {
+    const uint32_t n = csr->n_vertices;
+    const uint32_t *rp = csr->row_ptr, *col = csr->col, *met = csr->metric;
+    auto row_ok = [&](uint32_t v) { return rp[v] <= rp[v + 1] && rp[v + 1] <= csr->n_edges; };
+    auto links_back = [&](uint32_t t, uint32_t v) {                 // the two-way check: does t's row list v?  (cost not compared)
+      if (!row_ok(t)) return false;
+      for (uint32_t k = rp[t]; k < rp[t + 1]; ++k) if (col[k] == v) return true;
+      return false;
+    };
+    // H = [root] ++ networks reached through networks only, breadth-first, links in row order, each once (hspf_slot_table);
+    // per entry the cost of its discovery path and the link of the root's row that starts it
+    struct HEnt { uint32_t v, path_cost, first_link; };
+    std::vector<HEnt> H{{root, 0u, 0u}};
+    std::vector<uint32_t> seen{root};                               // (sorted: H holds a handful of vertices)
+    uint64_t total = 0;
+    for (size_t qi = 0; qi < H.size(); ++qi) {
+      const HEnt p = H[qi];
+      if (!row_ok(p.v)) return HSPF_E_INVAL;
+      for (uint32_t k = rp[p.v]; k < rp[p.v + 1]; ++k, ++total) {
+        const uint32_t t = col[k], j = k - rp[p.v];
+        if (t >= n) return HSPF_E_INVAL;
+        if (total > 0xFFFFFFF0ull) return HSPF_E_INVAL;
+        const uint64_t c64 = (uint64_t)p.path_cost + met[k];
+        const uint32_t c = c64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c64;
+        const uint32_t first = qi == 0 ? j : p.first_link;
+        const bool net = (csr->vflags[t] & HSPF_VF_NETWORK) != 0;
+        const bool two = (net || t != root) && links_back(t, p.v);
+        if (total < cap) {
+          const bool is_cand = !net && t != root && two;
+          if (nbr) nbr[total] = is_cand ? t : HSPF_NO_ROOT;
+          if (cost) cost[total] = c;
+          if (root_link) root_link[total] = first;
+          if (cflags) cflags[total] = (is_cand && (csr->vflags[t] & HSPF_VF_NO_TRANSIT)) ? (uint8_t)HSPF_LFA_C_NO_TRANSIT : (uint8_t)0;
+        }
+        if (net && two) {
+          auto it = std::lower_bound(seen.begin(), seen.end(), t);
+          if (it == seen.end() || *it != t) { seen.insert(it, t); H.push_back({t, c, first}); }
+        }
+      }
+    }
+    if (out_total_slots) *out_total_slots = (uint32_t)total;
+    return (int)std::min<uint64_t>(total, 0x7FFFFFFFull);
+  });
+}
+
+int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                    const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                    const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_lfa_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_COVERAGE_WORDS * 4, s));
+    LfaArgs a = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
+    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
+    if (max_k <= 64) hipLaunchKernelGGL(k_lfa<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_lfa");
+  });
+}
+
+// ---- remote loop-free alternates (include/holo_spf_hip.h "remote loop-free alternates on device"; kernels: spf_rlfa.hip.h) ----
+int hspf_csr_transpose(const hspf_csr *csr, uint32_t *row_ptr_out, uint32_t *col_out, uint32_t *metric_out) {
+  if (!csr || !row_ptr_out) return HSPF_E_INVAL;
+  const uint32_t n = csr->n_vertices, e = csr->n_edges;
+  if (n == 0 || n > (1u << 24) || e > HSPF_MAX_LINKS || !csr->row_ptr || !csr->vflags || (e && (!csr->col || !csr->metric || !col_out || !metric_out))) return HSPF_E_INVAL;
+  if (csr->row_ptr[0] != 0 || csr->row_ptr[n] != e) return HSPF_E_INVAL;
+  for (uint32_t u = 0; u < n; ++u)
+    if (csr->row_ptr[u + 1] < csr->row_ptr[u]) return HSPF_E_INVAL;
+  for (uint32_t k = 0; k < e; ++k)
+    if (csr->col[k] >= n) return HSPF_E_INVAL;
+  // a stable counting sort by target: the links are visited by ascending source, then by position in the source's row
+  for (uint32_t t = 0; t <= n; ++t) row_ptr_out[t] = 0;
+  for (uint32_t k = 0; k < e; ++k) ++row_ptr_out[csr->col[k] + 1];
+  for (uint32_t t = 0; t < n; ++t) row_ptr_out[t + 1] += row_ptr_out[t];
+  for (uint32_t u = 0; u < n; ++u)
+    for (uint32_t k = csr->row_ptr[u]; k < csr->row_ptr[u + 1]; ++k) {
+      const uint32_t o = row_ptr_out[csr->col[k]]++;                 // (row_ptr_out[t] runs from the start of row t to its end ...)
+      col_out[o] = u; metric_out[o] = csr->metric[k];
+    }
+  for (uint32_t t = n; t > 0; --t) row_ptr_out[t] = row_ptr_out[t - 1];      // (... which is the start of row t + 1: shift back)
+  row_ptr_out[0] = 0;
+  return HSPF_OK;
+}
+
+int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                     hspf_rlfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_rlfa_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
+      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    if ((rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * HSPF_RLFA_COUNT_WORDS * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * HSPF_RLFA_COVERAGE_WORDS * 4, s));
+    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    RlfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)stride;
+    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
+    a.tab = ga.tab; a.scal = ga.scal;
+    a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
+    a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
+    a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
+    a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
+    hipLaunchKernelGGL(k_rlfa, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_rlfa_final, dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
+    hipLaunchKernelGGL(k_rlfa_dest, grid, dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_rlfa");
+  });
+}
+
+// ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----
+int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                      const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  (void)lfa_flags;                                      // (eligibility and the overload rule are in the space tables)
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_tilfa_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!space_flags_dev || !space_via_dev) return bad("NULL space_flags / space_via (the tables of hspf_rlfa_device are required)");
+    if (!out_dev->ti_kind || !out_dev->ti_p || !out_dev->ti_q || !out_dev->ti_via || !out_dev->ti_link || !out_dev->ti_metric || !out_dev->ti_counts ||
+        !out_dev->td_kind || !out_dev->td_coverage)
+      return bad("NULL ti_kind / ti_p / ti_q / ti_via / ti_link / ti_metric / ti_counts / td_kind / td_coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
+    if (n_vertices > 0x7FFFFFFFu) return bad("n_vertices does not fit the selection key");
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    const uint32_t e = g->e;
+    if (g->twoway.size() != g->col.size()) return bad("the graph holds no two-way flags");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    std::vector<uint8_t> tw;                            // (the same)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    if ((rc = ensure(ctx, ctx->tilfa_key, n_slots * 8, false))) return rc;
+    if ((rc = ensure(ctx, ctx->tilfa_tw, std::max<size_t>(e, 1), false))) return rc;
+    hipStream_t s = ctx->stream;
+    // the two-way flags in the order of the device's raw CSR: the host mirror's pool is in that order unless a patch moved rows
+    const uint8_t *tw_src = g->twoway.data();
+    if (!g->pool_compact()) {
+      tw.resize(e);
+      size_t o = 0;
+      for (uint32_t v = 0; v < g->n; ++v) {
+        if (o + g->rlen[v] > e) return bad("the graph's host mirror and its link count disagree");
+        if (g->rlen[v]) memcpy(tw.data() + o, g->twoway.data() + g->rstart[v], g->rlen[v]);
+        o += g->rlen[v];
+      }
+      if (o != e) return bad("the graph's host mirror and its link count disagree");
+      tw_src = tw.data();
+    } else if (g->twoway.size() < e) return bad("the graph's host mirror and its link count disagree");
+    if (e) HIPCHK(ctx, hipMemcpyAsync(ctx->tilfa_tw.p, tw_src, e, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->tilfa_key.p, 0xFF, n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->ti_counts, 0, n_slots * HSPF_TILFA_COUNT_WORDS * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->td_coverage, 0, (size_t)n_prot * HSPF_TILFA_COVERAGE_WORDS * 4, s));
+    TilfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.stride = (uint32_t)stride;
+    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev;
+    a.tab = (const uint32_t *)ctx->lfa_tab.p; a.alt_in = alt_flags_in_dev;
+    a.sflags = space_flags_dev; a.svia = space_via_dev;
+    a.row_ptr = g->d_row_ptr[g->cur]; a.col = g->d_col[g->cur]; a.metric = g->d_metric[g->cur]; a.tw = (const uint8_t *)ctx->tilfa_tw.p;
+    a.key = (unsigned long long *)ctx->tilfa_key.p;
+    a.ti_kind = out_dev->ti_kind; a.ti_p = out_dev->ti_p; a.ti_q = out_dev->ti_q; a.ti_via = out_dev->ti_via; a.ti_link = out_dev->ti_link;
+    a.ti_metric = out_dev->ti_metric; a.ti_counts = out_dev->ti_counts; a.td_kind = out_dev->td_kind; a.td_cov = out_dev->td_coverage;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    if (max_k) hipLaunchKernelGGL(k_tilfa, dim3(n_tiles, std::min(max_k, 65535u), n_prot), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_tilfa_final, dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
+    hipLaunchKernelGGL(k_tilfa_dest, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_tilfa");
+  });
+}
+
+// ---- per-prefix backup routes (include/holo_spf_hip.h "per-prefix backup routes on device"; kernels: spf_backup.hip.h) ----
+int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                              const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                              const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
+                              const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_routes_backup_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
+    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
+      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
+    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric)) return bad("NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
+    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
+    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    hipStream_t s = ctx->stream;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) {
+      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * HSPF_BK_COVERAGE_WORDS * 4, s));
+    if (!t->n_prefixes) {                               // nothing to launch
+      HIPCHK(ctx, hipStreamSynchronize(s));
+      return HSPF_OK;
+    }
+    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    BackupArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
+    a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
+    a.dist = dist_dev; a.flags = flags_dev;
+    a.tab = ga.tab; a.scal = ga.scal;
+    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
+    a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
+    if (tilfa_dev) { a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric; }
+    a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
+    a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
+    const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
+    hipLaunchKernelGGL(k_backup, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_backup");
+  });
+}
+
+}  // extern "C"

@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "spf_lfa.hip.h"
+#include "spf_frr_common.hip.h"
 
 namespace {
 
@@ -51,15 +51,12 @@ __global__ __launch_bounds__(256) void k_rlfa(RlfaArgs a) {
   __shared__ uint32_t s_cnt[RLFA_CH * 4];
   __shared__ unsigned long long s_key[RLFA_CH];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.y;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t S = hdr[0], srow = hdr[1], K = hdr[2], C = hdr[3];
-  const uint32_t n = a.n;
-  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K, *rl = nbr + 3 * K, *cf = nbr + 4 * K, *cl = nbr + 5 * K;
-  const uint32_t *dns = a.scal + hdr[5];
+  const FrrTab tb = frr_tab(a.tab, a.scal, pi);
+  const uint32_t S = tb.S, C = tb.C, n = a.n;
   const uint32_t v = blockIdx.x * LFA_TILE + tid;
   const bool valid = v < n;
   const uint32_t vv = valid ? v : 0u;
-  const size_t sv = (size_t)srow * n + vv;
+  const size_t sv = (size_t)tb.srow * n + vv;
   const uint32_t dSv = a.dist[sv], rSv = a.rdist[sv];
   const uint32_t f = a.vf[vv];
   const bool elig = valid && v != S && (a.flags[sv] & 1u) && dSv != LFA_NONE && !(f & 0x05u) &&      // a router, not NO_EXPAND
@@ -76,10 +73,10 @@ __global__ __launch_bounds__(256) void k_rlfa(RlfaArgs a) {
 #pragma unroll
     for (uint32_t j = 0; j < RLFA_CH; ++j) {
       const bool live = c0 + j < C;
-      const uint32_t e = cl[live ? c0 + j : c0];
-      es[j] = e; rle[j] = rl[e];
-      const size_t ev = (size_t)row[e] * n + vv;
-      const uint32_t c = cost[e], dEv = a.dist[ev], rEv = a.rdist[ev];
+      const uint32_t e = tb.cl[live ? c0 + j : c0];
+      es[j] = e; rle[j] = tb.rl[e];
+      const size_t ev = (size_t)tb.row[e] * n + vv;
+      const uint32_t c = tb.cost[e], dEv = a.dist[ev], rEv = a.rdist[ev];
       t[j] = (uint64_t)c + dEv;
       const bool tok = live && elig && dEv != LFA_NONE;
       const bool p = tok && (uint64_t)dSv < t[j];
@@ -91,12 +88,12 @@ __global__ __launch_bounds__(256) void k_rlfa(RlfaArgs a) {
     // the via-slots, once per chunk (ascending k: a tie keeps S, then the smaller slot)
     if (__ballot(tm != 0)) {
       for (uint32_t ci = 0; ci < C; ++ci) {
-        const uint32_t k = cl[ci];
-        if ((cf[k] & 1u) && !a.ignore_overload) continue;                          // an overloaded neighbour carries no transit traffic
-        const uint32_t dNS = dns[k];
+        const uint32_t k = tb.cl[ci];
+        if ((tb.cf[k] & 1u) && !a.ignore_overload) continue;                       // an overloaded neighbour carries no transit traffic
+        const uint32_t dNS = tb.dns[k];
         if (dNS == LFA_NONE) continue;
-        const uint32_t dNv = a.dist[(size_t)row[k] * n + vv], rlk = rl[k];
-        const uint64_t rel = (uint64_t)cost[k] + dNv;
+        const uint32_t dNv = a.dist[(size_t)tb.row[k] * n + vv], rlk = tb.rl[k];
+        const uint64_t rel = (uint64_t)tb.cost[k] + dNv;
         const uint32_t okm = dNv != LFA_NONE ? tm : 0u;
 #pragma unroll
         for (uint32_t j = 0; j < RLFA_CH; ++j) {
@@ -135,18 +132,18 @@ __global__ __launch_bounds__(256) void k_rlfa(RlfaArgs a) {
     // one vector atomic per workgroup, slot and counter; the owner of an LDS cell resets it for the next chunk
     if (tid < RLFA_CH * 4) {
       const uint32_t j = tid >> 2, cnt = s_cnt[tid];
-      if (cnt) { atomicAdd(a.pq_counts + (slot0 + cl[c0 + j]) * 4 + (tid & 3u), cnt); s_cnt[tid] = 0; }      // cnt != 0: slot j of the chunk exists
+      if (cnt) { atomicAdd(a.pq_counts + (slot0 + tb.cl[c0 + j]) * 4 + (tid & 3u), cnt); s_cnt[tid] = 0; }      // cnt != 0: slot j of the chunk exists
     }
     if (tid < RLFA_CH) {
       const unsigned long long key = s_key[tid];
-      if (key != RLFA_NO_KEY) { atomicMin(a.key + slot0 + cl[c0 + tid], key); s_key[tid] = RLFA_NO_KEY; }
+      if (key != RLFA_NO_KEY) { atomicMin(a.key + slot0 + tb.cl[c0 + tid], key); s_key[tid] = RLFA_NO_KEY; }
     }
     __syncthreads();
   }
   // the optional tables of the slots that are no candidates: "none"
   if (valid && (a.space_flags || a.space_via)) {
     for (uint32_t e = 0; e < a.stride; ++e) {
-      if (e < K && nbr[e] != LFA_NONE) continue;
+      if (e < tb.K && tb.nbr[e] != LFA_NONE) continue;
       const size_t o = (slot0 + e) * n + v;
       if (a.space_flags) a.space_flags[o] = 0;
       if (a.space_via) a.space_via[o] = LFA_NONE;
@@ -159,25 +156,23 @@ __global__ __launch_bounds__(256) void k_rlfa_final(RlfaArgs a, uint32_t n_prot)
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n_prot * a.stride) return;
   const uint32_t pi = i / a.stride, e = i - pi * a.stride;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t srow = hdr[1], K = hdr[2], C = hdr[3], n = a.n;
-  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K, *rl = nbr + 3 * K, *cf = nbr + 4 * K, *cl = nbr + 5 * K;
-  const uint32_t *dns = a.scal + hdr[5];
+  const FrrTab tb = frr_tab(a.tab, a.scal, pi);
+  const uint32_t n = a.n;
   uint32_t node = LFA_NONE, via = LFA_NONE, met = 0;
   const unsigned long long key = a.key[i];
-  if (e < K && nbr[e] != LFA_NONE && key != RLFA_NO_KEY) {
+  if (e < tb.K && tb.nbr[e] != LFA_NONE && key != RLFA_NO_KEY) {
     node = (uint32_t)key; met = (uint32_t)(key >> 32);
-    const uint32_t dSv = a.dist[(size_t)srow * n + node], dEv = a.dist[(size_t)row[e] * n + node];
+    const uint32_t dSv = a.dist[(size_t)tb.srow * n + node], dEv = a.dist[(size_t)tb.row[e] * n + node];
     if (dEv != LFA_NONE) {                                                         // (a PQ node has a P or an XP: d(E, v) is finite)
-      const uint64_t t = (uint64_t)cost[e] + dEv;
+      const uint64_t t = (uint64_t)tb.cost[e] + dEv;
       uint64_t best = ~0ull;
       if (dSv != LFA_NONE && (uint64_t)dSv < t) { best = dSv; via = RLFA_VIA_SELF; }
-      for (uint32_t ci = 0; ci < C; ++ci) {
-        const uint32_t k = cl[ci];
-        if ((cf[k] & 1u) && !a.ignore_overload) continue;
-        const uint32_t dNS = dns[k], dNv = a.dist[(size_t)row[k] * n + node];
-        if (dNS == LFA_NONE || dNv == LFA_NONE || rl[k] == rl[e] || !((uint64_t)dNv < (uint64_t)dNS + t)) continue;
-        const uint64_t rel = (uint64_t)cost[k] + dNv;
+      for (uint32_t ci = 0; ci < tb.C; ++ci) {
+        const uint32_t k = tb.cl[ci];
+        if ((tb.cf[k] & 1u) && !a.ignore_overload) continue;
+        const uint32_t dNS = tb.dns[k], dNv = a.dist[(size_t)tb.row[k] * n + node];
+        if (dNS == LFA_NONE || dNv == LFA_NONE || tb.rl[k] == tb.rl[e] || !((uint64_t)dNv < (uint64_t)dNS + t)) continue;
+        const uint64_t rel = (uint64_t)tb.cost[k] + dNv;
         if (rel < best) { best = rel; via = k; }
       }
     }
@@ -188,48 +183,32 @@ __global__ __launch_bounds__(256) void k_rlfa_final(RlfaArgs a, uint32_t n_prot)
 // per destination D of S: the PQ node of its one primary slot, where LFA left it unprotected; the four coverage counts
 __global__ __launch_bounds__(256) void k_rlfa_dest(RlfaArgs a) {
   __shared__ uint32_t s_cov[4];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.y;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t S = hdr[0], srow = hdr[1], K = hdr[2];
-  const uint32_t n = a.n, W = a.W, Wk = (K + 63u) >> 6;
-  const uint32_t *nbr = a.tab + hdr[4];
+  const uint32_t tid = threadIdx.x, pi = blockIdx.y;
+  const FrrTab tb = frr_tab(a.tab, pi);
+  const uint32_t n = a.n;
   if (tid < 4) s_cov[tid] = 0;
   __syncthreads();
-  const uint64_t last_word = (K & 63u) ? ((1ull << (K & 63u)) - 1ull) : ~0ull;
   const uint32_t D = blockIdx.x * LFA_TILE + tid;
   const bool valid = D < n;
-  const size_t sd = (size_t)srow * n + (valid ? D : 0u);
+  const size_t sd = (size_t)tb.srow * n + (valid ? D : 0u);
   const size_t od = (size_t)pi * n + D;
-  const bool in = valid && D != S && (a.flags[sd] & 1u) && a.dist[sd] != LFA_NONE;
+  const bool in = valid && D != tb.S && (a.flags[sd] & 1u) && a.dist[sd] != LFA_NONE;
   uint32_t fl = 0, node = LFA_NONE, via = LFA_NONE;
   if (in) {
-    const uint64_t *pm = a.mask + sd * W;
-    uint32_t np = 0, p0 = 0;
-    for (uint32_t w = 0; w < Wk; ++w) {
-      const uint64_t x = pm[w] & (w + 1 == Wk ? last_word : ~0ull);
-      if (x && !np) p0 = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-      np += (uint32_t)__popcll(x);
-    }
+    uint32_t np, p0;
+    frr_primaries(tb, a.mask + sd * a.W, np, p0);
     if (np == 1) {
       fl = 1u;
       if (a.alt_in && (a.alt_in[od] & 0x04u)) fl |= 2u;                            // HSPF_LFA_LINK_PROTECT: LFA covers it
       else {
         const size_t o = (size_t)pi * a.stride + p0;
-        if (nbr[p0] != LFA_NONE && a.pq_node[o] != LFA_NONE) { node = a.pq_node[o]; via = a.pq_via[o]; fl |= 4u; }
+        if (tb.nbr[p0] != LFA_NONE && a.pq_node[o] != LFA_NONE) { node = a.pq_node[o]; via = a.pq_via[o]; fl |= 4u; }
         else fl |= 8u;
       }
     }
   }
   if (valid) { a.rl_node[od] = node; a.rl_via[od] = via; }
-  uint32_t my_cov = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 4; ++j) {
-    const uint32_t c = (uint32_t)__popcll(__ballot((fl >> j) & 1u));
-    if (lane == j) my_cov = c;
-  }
-  if (lane < 4 && my_cov) atomicAdd(&s_cov[lane], my_cov);
-  __syncthreads();
-  if (tid < 4 && s_cov[tid]) atomicAdd(a.rl_cov + (size_t)pi * 4 + tid, s_cov[tid]);
+  frr_cover<4>(fl, s_cov, a.rl_cov + (size_t)pi * 4);
 }
 
 }  // namespace

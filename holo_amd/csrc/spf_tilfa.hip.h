@@ -42,11 +42,10 @@ struct TilfaArgs {
 };
 
 // the release metric of v under slot e from its via (64 bits); false: v has no release point (or the table holds no slot of S)
-__device__ __forceinline__ bool tilfa_rel(const TilfaArgs &a, uint32_t via, uint32_t K, uint32_t srow, const uint32_t *row, const uint32_t *cost,
-                                          uint32_t v, uint64_t &rel) {
-  if (via == RLFA_VIA_SELF) { rel = a.dist[(size_t)srow * a.n + v]; return true; }
-  if (via >= K) return false;
-  rel = (uint64_t)cost[via] + a.dist[(size_t)row[via] * a.n + v];
+__device__ __forceinline__ bool tilfa_rel(const TilfaArgs &a, const FrrTab &tb, uint32_t via, uint32_t v, uint64_t &rel) {
+  if (via == RLFA_VIA_SELF) { rel = a.dist[(size_t)tb.srow * a.n + v]; return true; }
+  if (via >= tb.K) return false;
+  rel = (uint64_t)tb.cost[via] + a.dist[(size_t)tb.row[via] * a.n + v];
   return true;
 }
 
@@ -54,10 +53,8 @@ __global__ __launch_bounds__(256) void k_tilfa(TilfaArgs a) {
   __shared__ uint32_t s_cnt[2];
   __shared__ unsigned long long s_key;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.z;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t srow = hdr[1], K = hdr[2], C = hdr[3];
+  const FrrTab tb = frr_tab(a.tab, pi);
   const uint32_t n = a.n;
-  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K, *cl = nbr + 5 * K;
   const uint32_t p = blockIdx.x * LFA_TILE + tid;
   const bool valid = p < n;
   const uint32_t pp = valid ? p : 0u;
@@ -66,13 +63,13 @@ __global__ __launch_bounds__(256) void k_tilfa(TilfaArgs a) {
   if (tid < 2) s_cnt[tid] = 0;
   if (tid == 0) s_key = RLFA_NO_KEY;
   __syncthreads();
-  for (uint32_t ci = blockIdx.y; ci < C; ci += gridDim.y) {
-    const uint32_t e = cl[ci];
+  for (uint32_t ci = blockIdx.y; ci < tb.C; ci += gridDim.y) {
+    const uint32_t e = tb.cl[ci];
     const size_t so = (slot0 + e) * n;
-    const uint32_t *rdE = a.rdist + (size_t)row[e] * n;
+    const uint32_t *rdE = a.rdist + (size_t)tb.row[e] * n;
     const uint32_t sf = valid ? a.sflags[so + pp] : 0u;
     uint64_t rel = 0;
-    const bool in_xp = (sf & 0x08u) && (sf & 0x03u) && tilfa_rel(a, a.svia[so + pp], K, srow, row, cost, pp, rel);   // eligible, in P or some XP
+    const bool in_xp = (sf & 0x08u) && (sf & 0x03u) && tilfa_rel(a, tb, a.svia[so + pp], pp, rel);   // eligible, in P or some XP
     const bool single = in_xp && (sf & 0x04u);
     unsigned long long key = RLFA_NO_KEY;
     if (single) {
@@ -126,19 +123,18 @@ __global__ __launch_bounds__(256) void k_tilfa_final(TilfaArgs a, uint32_t n_pro
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n_prot * a.stride) return;
   const uint32_t pi = i / a.stride, e = i - pi * a.stride;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t srow = hdr[1], K = hdr[2], n = a.n;
-  const uint32_t *nbr = a.tab + hdr[4], *row = nbr + K, *cost = nbr + 2 * K;
+  const FrrTab tb = frr_tab(a.tab, pi);
+  const uint32_t n = a.n;
   uint32_t kind = 0, p = LFA_NONE, q = LFA_NONE, via = LFA_NONE, link = LFA_NONE, met = 0;
   const unsigned long long key = a.key[i];
-  if (e < K && nbr[e] != LFA_NONE && key != RLFA_NO_KEY) {
+  if (e < tb.K && tb.nbr[e] != LFA_NONE && key != RLFA_NO_KEY) {
     const size_t so = (size_t)i * n;
     met = (uint32_t)(key >> 32); p = (uint32_t)key & 0x7FFFFFFFu; kind = (key & TILFA_PAIR_BIT) ? 2u : 1u;
     via = a.svia[so + p];
     q = p;
     uint64_t rel = 0;
-    if (kind == 2u && tilfa_rel(a, via, K, srow, row, cost, p, rel)) {
-      const uint32_t *rdE = a.rdist + (size_t)row[e] * n;
+    if (kind == 2u && tilfa_rel(a, tb, via, p, rel)) {
+      const uint32_t *rdE = a.rdist + (size_t)tb.row[e] * n;
       const uint32_t rb = a.row_ptr[p], re = a.row_ptr[p + 1];
       uint64_t bt = ~0ull;
       for (uint32_t k = rb; k < re; ++k) {
@@ -156,27 +152,20 @@ __global__ __launch_bounds__(256) void k_tilfa_final(TilfaArgs a, uint32_t n_pro
 // per destination D of S with exactly one primary slot: covered by LFA | by a single node | by a pair | uncovered; the five counts
 __global__ __launch_bounds__(256) void k_tilfa_dest(TilfaArgs a) {
   __shared__ uint32_t s_cov[5];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.y;
-  const uint32_t *hdr = a.tab + (size_t)pi * LFA_HDR_WORDS;
-  const uint32_t S = hdr[0], srow = hdr[1], K = hdr[2];
-  const uint32_t n = a.n, W = a.W, Wk = (K + 63u) >> 6;
+  const uint32_t tid = threadIdx.x, pi = blockIdx.y;
+  const FrrTab tb = frr_tab(a.tab, pi);
+  const uint32_t n = a.n;
   if (tid < 5) s_cov[tid] = 0;
   __syncthreads();
-  const uint64_t last_word = (K & 63u) ? ((1ull << (K & 63u)) - 1ull) : ~0ull;
   const uint32_t D = blockIdx.x * LFA_TILE + tid;
   const bool valid = D < n;
-  const size_t sd = (size_t)srow * n + (valid ? D : 0u);
+  const size_t sd = (size_t)tb.srow * n + (valid ? D : 0u);
   const size_t od = (size_t)pi * n + D;
-  const bool in = valid && D != S && (a.flags[sd] & 1u) && a.dist[sd] != LFA_NONE;
+  const bool in = valid && D != tb.S && (a.flags[sd] & 1u) && a.dist[sd] != LFA_NONE;
   uint32_t cls = 0;
   if (in) {
-    const uint64_t *pm = a.mask + sd * W;
-    uint32_t np = 0, p0 = 0;
-    for (uint32_t w = 0; w < Wk; ++w) {
-      const uint64_t x = pm[w] & (w + 1 == Wk ? last_word : ~0ull);
-      if (x && !np) p0 = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-      np += (uint32_t)__popcll(x);
-    }
+    uint32_t np, p0;
+    frr_primaries(tb, a.mask + sd * a.W, np, p0);
     if (np == 1) {
       if (a.alt_in && (a.alt_in[od] & 0x04u)) cls = 1u;                            // HSPF_LFA_LINK_PROTECT: LFA covers it
       else {
@@ -186,15 +175,7 @@ __global__ __launch_bounds__(256) void k_tilfa_dest(TilfaArgs a) {
     }
   }
   if (valid) a.td_kind[od] = (uint8_t)cls;
-  uint32_t my_cov = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 5; ++j) {
-    const uint32_t c = (uint32_t)__popcll(__ballot(j == 0 ? cls != 0 : cls == j));
-    if (lane == j) my_cov = c;
-  }
-  if (lane < 5 && my_cov) atomicAdd(&s_cov[lane], my_cov);
-  __syncthreads();
-  if (tid < 5 && s_cov[tid]) atomicAdd(a.td_cov + (size_t)pi * 5 + tid, s_cov[tid]);
+  frr_cover<5>(cls ? 1u | (1u << cls) : 0u, s_cov, a.td_cov + (size_t)pi * 5);      // counter 0: any class; counter j: class j (1 .. 4)
 }
 
 }  // namespace

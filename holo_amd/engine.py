@@ -6,6 +6,7 @@ in the HIP library; there is no Python or CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import time
 from dataclasses import dataclass
@@ -757,52 +758,68 @@ class SpfContext:
                            coverage_ptr or None)
         rc = self.lib.hspf_lfa_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
                                       arr, len(protect), lfa_flags, ctypes.byref(out))
+        self._check_rc("hspf_lfa_device", rc)
+
+    def _check_rc(self, name: str, rc: int) -> None:
         if rc != 0:
-            raise HspfError(rc, "hspf_lfa_device", self.last_error())
+            raise HspfError(rc, name, self.last_error())
 
     def _dev_alloc(self, nbytes: int) -> int:
         p = ctypes.c_void_p()
         rc = self.lib.hspf_device_alloc(self.handle, max(int(nbytes), 8), ctypes.byref(p))
-        if rc != 0:
-            raise HspfError(rc, "hspf_device_alloc", self.last_error())
+        self._check_rc("hspf_device_alloc", rc)
         return p.value
 
-    def lfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_masks: bool = True):
-        """Backup next hops of one root, start to finish: the candidate table of `root`, ONE run_device() for
-        [root] + its distinct neighbour routers, lfa_device() on those rows, the five arrays and the coverage on the host.
-        Returns (LfaCandidates, LfaResult with one row).  The SPT tables never leave the device."""
+    @contextlib.contextmanager
+    def _dev_buffers(self, sizes: dict):
+        """One device buffer per entry of `sizes` (bytes; 0: no buffer, pointer 0): yields {name: pointer}, frees them all."""
+        dev = {}
+        try:
+            for k, b in sizes.items():
+                dev[k] = self._dev_alloc(b) if b else 0
+            yield dev
+        finally:
+            for p in dev.values():
+                if p:
+                    self.lib.hspf_device_free(self.handle, ctypes.c_void_p(p))
+
+    def _fetch(self, host_arrays: dict, dev: dict) -> None:
+        """dev[k] -> host_arrays[k] for every array that is there and not empty."""
+        for k, arr in host_arrays.items():
+            if arr is not None and arr.nbytes:
+                rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
+                self._check_rc("hspf_device_to_host", rc)
+
+    def _frr_plan(self, graph: SpfGraph, root: int):
+        """What the chains below start from: the candidate table of `root`, the roots of the run ([root] + its distinct
+        neighbour routers), per slot the table row of its neighbour's SPT, and the mask words of that run."""
         cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
         nbrs = np.unique(cand.nbr[cand.nbr != NO_ROOT])
         roots = np.concatenate([[root], nbrs]).astype(np.uint32)
         nbr_row = np.zeros(cand.n_slots, np.uint32)
         is_c = cand.nbr != NO_ROOT
         nbr_row[is_c] = 1 + np.searchsorted(nbrs, cand.nbr[is_c])
+        return cand, roots, nbr_row, max(graph.mask_words(roots), (cand.n_slots + 63) // 64)
+
+    def lfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_masks: bool = True):
+        """Backup next hops of one root, start to finish: the candidate table of `root`, ONE run_device() for
+        [root] + its distinct neighbour routers, lfa_device() on those rows, the five arrays and the coverage on the host.
+        Returns (LfaCandidates, LfaResult with one row).  The SPT tables never leave the device."""
+        cand, roots, nbr_row, W = self._frr_plan(graph, root)
         R, n = len(roots), graph.n
-        W = max(graph.mask_words(roots), (cand.n_slots + 63) // 64)
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, slot=4 * n, metric=4 * n, aflags=n,
-                     cm=8 * n * W if want_masks else 0, nm=8 * n * W if want_masks else 0, cov=4 * LFA_COVERAGE_WORDS)
-        dev = {}
-        try:
-            for k, b in sizes.items():
-                dev[k] = self._dev_alloc(b) if b else 0
+        masks = ((1, n, W), np.uint64) if want_masks else None
+        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cm=masks, nm=masks,
+                      cov=((1, LFA_COVERAGE_WORDS), np.uint32))
+        host = {k: np.empty(*sh) if sh else None for k, sh in shapes.items()}
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W)
+        sizes.update({k: 0 if a is None else a.nbytes for k, a in host.items()})
+        with self._dev_buffers(sizes) as dev:
             self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
             self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], alt_slot_ptr=dev["slot"],
                             alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], cand_mask_ptr=dev["cm"],
                             node_mask_ptr=dev["nm"], lfa_flags=lfa_flags)
-            res = LfaResult(np.empty((1, n), np.uint32), np.empty((1, n), np.uint32), np.empty((1, n), np.uint8),
-                            np.empty((1, n, W), np.uint64) if want_masks else None, np.empty((1, n, W), np.uint64) if want_masks else None,
-                            np.empty((1, LFA_COVERAGE_WORDS), np.uint32))
-            for arr, k in ((res.alt_slot, "slot"), (res.alt_metric, "metric"), (res.alt_flags, "aflags"), (res.cand_mask, "cm"),
-                           (res.node_mask, "nm"), (res.coverage, "cov")):
-                if arr is not None:
-                    rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
-                    if rc != 0:
-                        raise HspfError(rc, "hspf_device_to_host", self.last_error())
-            return cand, res
-        finally:
-            for p in dev.values():
-                if p:
-                    self.lib.hspf_device_free(self.handle, ctypes.c_void_p(p))
+            self._fetch(host, dev)
+        return cand, LfaResult(*host.values())
 
     def rlfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                     protect, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int, rl_via_ptr: int,
@@ -817,8 +834,7 @@ class SpfContext:
         rc = self.lib.hspf_rlfa_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
                                        rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, ctypes.byref(out))
         del keep
-        if rc != 0:
-            raise HspfError(rc, "hspf_rlfa_device", self.last_error())
+        self._check_rc("hspf_rlfa_device", rc)
 
     def tilfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                      protect, *, space_flags_ptr: int, space_via_ptr: int, ti_kind_ptr: int, ti_p_ptr: int, ti_q_ptr: int, ti_via_ptr: int,
@@ -835,8 +851,7 @@ class SpfContext:
                                         rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None,
                                         space_via_ptr or None, ctypes.byref(out))
         del keep
-        if rc != 0:
-            raise HspfError(rc, "hspf_tilfa_device", self.last_error())
+        self._check_rc("hspf_tilfa_device", rc)
 
     def routes_backup_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                              pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
@@ -868,8 +883,7 @@ class SpfContext:
                                                 arr, len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r),
                                                 None if ti is None else ctypes.byref(ti), ctypes.byref(out))
         del keep
-        if rc != 0:
-            raise HspfError(rc, "hspf_routes_backup_device", self.last_error())
+        self._check_rc("hspf_routes_backup_device", rc)
 
     def backup_routes(self, graph: SpfGraph, root: int, prefix_table, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False,
                       remote: bool = True) -> BackupRoutes:
@@ -900,15 +914,8 @@ class SpfContext:
     def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None):
         """The chain behind rlfa(), tilfa() and backup_routes().  backup: None, or (pfx_ptr, pfx_vertex, pfx_metric, flags) — then
         the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`)."""
-        cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
-        nbrs = np.unique(cand.nbr[cand.nbr != NO_ROOT])
-        roots = np.concatenate([[root], nbrs]).astype(np.uint32)
-        nbr_row = np.zeros(cand.n_slots, np.uint32)
-        is_c = cand.nbr != NO_ROOT
-        nbr_row[is_c] = 1 + np.searchsorted(nbrs, cand.nbr[is_c])
-        R, n = len(roots), graph.n
-        W = max(graph.mask_words(roots), (cand.n_slots + 63) // 64)
-        S = 64 * W
+        cand, roots, nbr_row, W = self._frr_plan(graph, root)
+        R, n, S = len(roots), graph.n, 64 * W
         shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cov=((1, LFA_COVERAGE_WORDS), np.uint32),
                       pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
                       pq_counts=((1, S, RLFA_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32), rl_via=((1, n), np.uint32),
@@ -931,14 +938,12 @@ class SpfContext:
         host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
         sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
         sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
-        dev, GT = {}, None
-        try:
-            for k, b in sizes.items():
-                dev[k] = self._dev_alloc(b) if b else 0
+        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
             self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
             if not symmetric:
                 trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
                 GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
+                cleanup.callback(GT.free)
                 self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
             protect = [(0, cand, nbr_row)]
             self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"],
@@ -964,12 +969,7 @@ class SpfContext:
                                           tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None,
                                           flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags,
                                           **{k + "_ptr": dev[k] for k in bk_names[3:]})
-            for k, arr in host.items():
-                if not arr.nbytes:
-                    continue
-                rc = self.lib.hspf_device_to_host(self.handle, arr.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev[k]), arr.nbytes)
-                if rc != 0:
-                    raise HspfError(rc, "hspf_device_to_host", self.last_error())
+            self._fetch(host, dev)
             if backup is not None:
                 return BackupRoutes(cand, *(host[k] for k in bk_names),
                                     tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None)
@@ -977,12 +977,6 @@ class SpfContext:
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
             return (cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, lfa, rl)
-        finally:
-            if GT is not None:
-                GT.free()
-            for p in dev.values():
-                if p:
-                    self.lib.hspf_device_free(self.handle, ctypes.c_void_p(p))
 
     def close(self):
         if self.handle:
