@@ -100,6 +100,15 @@ class HspfBackupOut(ctypes.Structure):
                 ("bk_flags", ctypes.c_void_p), ("bk_cand_mask", ctypes.c_void_p), ("bk_node_mask", ctypes.c_void_p), ("bk_coverage", ctypes.c_void_p)]
 
 
+class HspfRlfaNodeSel(ctypes.Structure):
+    _fields_ = [("nq_node", ctypes.c_void_p), ("nq_via", ctypes.c_void_p), ("nq_metric", ctypes.c_void_p), ("nq_count", ctypes.c_void_p)]
+
+
+class HspfRlfaNodeOut(ctypes.Structure):
+    _fields_ = [("nd_kind", ctypes.c_void_p), ("nd_node", ctypes.c_void_p), ("nd_via", ctypes.c_void_p), ("nd_metric", ctypes.c_void_p),
+                ("nd_set", ctypes.c_void_p), ("nd_coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -191,6 +200,14 @@ SYMBOLS = [
                                                  ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes), ctypes.POINTER(HspfTilfaOut),
                                                  ctypes.POINTER(HspfBackupOut)]),
+    # node-protecting remote loop-free alternates
+    ("hspf_rlfa_node_select_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(HspfRlfaNodeSel)]),
+    ("hspf_rlfa_node_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                             ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.POINTER(HspfRlfaNodeSel), ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.POINTER(HspfRlfaNodeOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

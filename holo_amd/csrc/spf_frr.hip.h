@@ -1,7 +1,8 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
-// hspf_csr_transpose, hspf_rlfa_device, hspf_tilfa_device, hspf_routes_backup_device.  Included by spf_capi.hip (one TU).
+// hspf_csr_transpose, hspf_rlfa_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
+// hspf_rlfa_node_device.  Included by spf_capi.hip (one TU).
 //
-// The four device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
+// The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
 // one frame: argument checks, lfa_stage, k_lfa_gather where the kernels need the per-root scalars, the call's own kernels,
 // frr_finish.  `fn` names the calling entry point in hspf_last_error.
 #pragma once
@@ -10,6 +11,7 @@
 #include "spf_rlfa.hip.h"
 #include "spf_tilfa.hip.h"
 #include "spf_backup.hip.h"
+#include "spf_rlfa_node.hip.h"
 
 namespace {
 
@@ -355,6 +357,90 @@ int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_row
     hipLaunchKernelGGL(k_backup, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
     return frr_finish(ctx, "k_backup");
+  });
+}
+
+// ---- node-protecting remote LFA (include/holo_spf_hip.h "node-protecting remote loop-free alternates on device"; kernels:
+// spf_rlfa_node.hip.h) ----
+int hspf_rlfa_node_select_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                 const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                 const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *space_flags_dev,
+                                 uint32_t max_pq, hspf_rlfa_node_sel *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_rlfa_node_select_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!space_flags_dev) return bad("NULL space_flags (the table of hspf_rlfa_device is required)");
+    if (!out_dev->nq_node || !out_dev->nq_via || !out_dev->nq_metric || !out_dev->nq_count) return bad("NULL nq_node / nq_via / nq_metric / nq_count");
+    if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) return bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    const size_t part_keys = (size_t)n_prot * max_k * n_tiles * max_pq;      // one list per workgroup
+    if (part_keys > ((size_t)1 << 30)) { ctx->last_error = std::string(fn) + ": the partial lists of this call need more than 8 GiB of scratch"; return HSPF_E_NOMEM; }
+    if ((rc = ensure(ctx, ctx->rnode_part, std::max<size_t>(part_keys, 1) * 8, false))) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(out_dev->nq_count, 0, n_slots * 4, s));
+    RnodeSelArgs a{};
+    a.n = n_vertices; a.stride = (uint32_t)stride; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u; a.max_pq = max_pq;
+    a.max_k = max_k; a.n_tiles = n_tiles;
+    a.dist = dist_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p; a.sflags = space_flags_dev;
+    a.part = (unsigned long long *)ctx->rnode_part.p;
+    a.nq_node = out_dev->nq_node; a.nq_via = out_dev->nq_via; a.nq_metric = out_dev->nq_metric; a.nq_count = out_dev->nq_count;
+    if (max_k) hipLaunchKernelGGL(k_rlfa_nsel, dim3(n_tiles, std::min(max_k, 65535u), n_prot), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_rlfa_nsel_final, dim3((uint32_t)stride, n_prot), dim3(64), 0, s, a);
+    return frr_finish(ctx, "k_rlfa_nsel");
+  });
+}
+
+int hspf_rlfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                          const hspf_lfa_protect *prot, uint32_t n_prot,
+                          const uint32_t *ydist_dev, const uint32_t *y_roots, uint32_t n_yrows,
+                          const hspf_rlfa_node_sel *sel_dev, uint32_t max_pq,
+                          const uint8_t *alt_flags_in_dev, hspf_rlfa_node_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_rlfa_node_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!ydist_dev || !y_roots || !sel_dev) return bad("NULL ydist, y_roots or sel pointer");
+    if (!sel_dev->nq_node || !sel_dev->nq_via || !sel_dev->nq_metric || !sel_dev->nq_count) return bad("NULL nq_node / nq_via / nq_metric / nq_count in sel_dev");
+    if (!out_dev->nd_kind || !out_dev->nd_node || !out_dev->nd_via || !out_dev->nd_metric || !out_dev->nd_coverage)
+      return bad("NULL nd_kind / nd_node / nd_via / nd_metric / nd_coverage");
+    if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) return bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
+    if (n_yrows == 0) return bad("n_yrows is 0");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    for (uint32_t i = 0; i < n_yrows; ++i)
+      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n_vertices) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    if ((rc = ensure(ctx, ctx->rnode_map, ((size_t)n_vertices + n_yrows) * 4, false))) return rc;
+    hipStream_t s = ctx->stream;
+    uint32_t *ymap = (uint32_t *)ctx->rnode_map.p, *yroots = ymap + n_vertices;
+    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n_vertices * 4, s));
+    HIPCHK(ctx, hipMemcpyAsync(yroots, y_roots, (size_t)n_yrows * 4, hipMemcpyHostToDevice, s));      // (the caller's: it lives through the call)
+    HIPCHK(ctx, hipMemsetAsync(out_dev->nd_coverage, 0, (size_t)n_prot * HSPF_NP_COVERAGE_WORDS * 4, s));
+    RnodeDestArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.stride = 64u * n_mask_words; a.max_pq = max_pq;
+    a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p;
+    a.ydist = ydist_dev; a.yroots = yroots; a.n_yrows = n_yrows; a.ymap = ymap;
+    a.nq_node = sel_dev->nq_node; a.nq_via = sel_dev->nq_via; a.nq_metric = sel_dev->nq_metric; a.nq_count = sel_dev->nq_count;
+    a.alt_in = alt_flags_in_dev;
+    a.nd_kind = out_dev->nd_kind; a.nd_node = out_dev->nd_node; a.nd_via = out_dev->nd_via; a.nd_metric = out_dev->nd_metric;
+    a.nd_set = out_dev->nd_set; a.nd_cov = out_dev->nd_coverage;
+    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_rlfa_ndest, dim3((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_rlfa_ndest");
   });
 }
 

@@ -51,6 +51,9 @@ TILFA_COUNT_WORDS = 2
 TILFA_COVERAGE_WORDS = 5
 BK_NO_ROUTE, BK_LOCAL, BK_ECMP, BK_LFA, BK_NODE, BK_PAIR, BK_NONE = 0, 1, 2, 3, 4, 5, 6      # HSPF_BK_*: bk_kind
 BK_COVERAGE_WORDS = 7
+RLFA_NODE_MAX_PQ = 32           # HSPF_RLFA_NODE_MAX_PQ
+NP_D_LFA, NP_D_PQ, NP_D_LAST_HOP, NP_D_NONE = 1, 2, 3, 4      # HSPF_NP_D_* (nd_kind)
+NP_COVERAGE_WORDS = 5
 
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
@@ -237,6 +240,26 @@ class TilfaResult:
     ti_counts: np.ndarray    # [P, S, 2] u32 single nodes | usable (p, link) pairs
     td_kind: np.ndarray      # [P, N] u8  TILFA_D_* per destination with exactly one primary, 0 elsewhere
     td_coverage: np.ndarray  # [P, 5] u32
+
+
+@dataclass
+class RlfaNodeResult:
+    """Node-protecting remote alternates (RFC 8102) of the protected roots of one rlfa_node_select_device() +
+    rlfa_node_device() pair, on the host (S = 64 * mask words, M = max_pq).  SpfContext.rlfa_node() also fills `candidates` and
+    `lfa`: the candidate table and the loop-free alternates its chain computed on the way."""
+    nq_node: np.ndarray      # [P, S, M] u32 the cheapest PQ nodes whose release path avoids the neighbour, NO_ROOT padding
+    nq_via: np.ndarray       # [P, S, M] u32 RLFA_VIA_SELF or a slot, LFA_NO_SLOT padding
+    nq_metric: np.ndarray    # [P, S, M] u32 release metric
+    nq_count: np.ndarray     # [P, S] u32 all qualifying vertices (may exceed M)
+    y_roots: np.ndarray      # [Y] u32 the roots of the PQ-node rows: the ascending union of the lists
+    nd_kind: np.ndarray      # [P, N] u8  NP_D_* per destination with exactly one primary, 0 elsewhere
+    nd_node: np.ndarray      # [P, N] u32, NO_ROOT: none
+    nd_via: np.ndarray       # [P, N] u32
+    nd_metric: np.ndarray    # [P, N] u32
+    nd_set: np.ndarray       # [P, N] u32 bit j: list entry j protects the destination
+    nd_coverage: np.ndarray  # [P, 5] u32
+    candidates: Optional[LfaCandidates] = None
+    lfa: Optional[LfaResult] = None
 
 
 @dataclass
@@ -977,6 +1000,85 @@ class SpfContext:
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
             return (cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, lfa, rl)
+
+    def rlfa_node_select_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
+                                space_flags_ptr: int, max_pq: int, nq_node_ptr: int, nq_via_ptr: int, nq_metric_ptr: int, nq_count_ptr: int,
+                                lfa_flags: int = 0) -> None:
+        """hspf_rlfa_node_select_device(): per (protected root, slot) the cheapest `max_pq` link-protecting PQ nodes whose release
+        path avoids the neighbour behind the slot, from the tables of a run_device() and the space_flags rlfa_device() wrote for the
+        same `protect` and lfa_flags.  All `*_ptr` are device pointers; the lists are [P][64 * mask_words][max_pq]."""
+        arr, keep = self._protect_array(protect, "rlfa_node_select_device")
+        out = L.HspfRlfaNodeSel(nq_node_ptr or None, nq_via_ptr or None, nq_metric_ptr or None, nq_count_ptr or None)
+        rc = self.lib.hspf_rlfa_node_select_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                                   arr, len(protect), lfa_flags, space_flags_ptr or None, max_pq, ctypes.byref(out))
+        del keep
+        self._check_rc("hspf_rlfa_node_select_device", rc)
+
+    def rlfa_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
+                         ydist_ptr: int, y_roots, sel: tuple, max_pq: int, nd_kind_ptr: int, nd_node_ptr: int, nd_via_ptr: int,
+                         nd_metric_ptr: int, nd_coverage_ptr: int, nd_set_ptr: int = 0, alt_flags_in_ptr: int = 0) -> None:
+        """hspf_rlfa_node_device(): per destination with one primary, the cheapest listed PQ node whose own path to it avoids the
+        primary's neighbour.  ydist_ptr: `dist` [len(y_roots)][n] of a forward run_device() of `y_roots` (host array; NO_ROOT
+        entries are skipped); sel = (nq_node_ptr, nq_via_ptr, nq_metric_ptr, nq_count_ptr) of rlfa_node_select_device() with the
+        same max_pq.  nd_set_ptr / alt_flags_in_ptr may be 0."""
+        arr, keep = self._protect_array(protect, "rlfa_node_device")
+        yr = np.ascontiguousarray(y_roots, np.uint32)
+        se = L.HspfRlfaNodeSel(*(x or None for x in sel))
+        out = L.HspfRlfaNodeOut(nd_kind_ptr or None, nd_node_ptr or None, nd_via_ptr or None, nd_metric_ptr or None, nd_set_ptr or None,
+                                nd_coverage_ptr or None)
+        rc = self.lib.hspf_rlfa_node_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                            arr, len(protect), ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), ctypes.byref(se), max_pq,
+                                            alt_flags_in_ptr or None, ctypes.byref(out))
+        del keep
+        self._check_rc("hspf_rlfa_node_device", rc)
+
+    def rlfa_node(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, max_pq: int = 16, symmetric: bool = False):
+        """Node-protecting remote alternates of one root, start to finish: run_device() of [root] + its distinct neighbour routers
+        (on the transposed graph too unless `symmetric`), lfa_device(), rlfa_device() with the space tables,
+        rlfa_node_select_device(), the lists to the host, ONE run_device() over the ascending union of the listed nodes,
+        rlfa_node_device().  Returns a RlfaNodeResult with one row (its `candidates` and `lfa` — without masks — filled)."""
+        cand, roots, nbr_row, W = self._frr_plan(graph, root)
+        R, n, S, M = len(roots), graph.n, 64 * W, int(max_pq)
+        host = dict(slot=np.empty((1, n), np.uint32), metric=np.empty((1, n), np.uint32), aflags=np.empty((1, n), np.uint8),
+                    cov=np.empty((1, LFA_COVERAGE_WORDS), np.uint32))
+        sel = dict(nq_node=np.empty((1, S, M), np.uint32), nq_via=np.empty((1, S, M), np.uint32), nq_metric=np.empty((1, S, M), np.uint32),
+                   nq_count=np.empty((1, S), np.uint32))
+        nd = dict(nd_kind=np.empty((1, n), np.uint8), nd_node=np.empty((1, n), np.uint32), nd_via=np.empty((1, n), np.uint32),
+                  nd_metric=np.empty((1, n), np.uint32), nd_set=np.empty((1, n), np.uint32), nd_coverage=np.empty((1, NP_COVERAGE_WORDS), np.uint32))
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n, sp_flags=S * n,
+                     pq_node=4 * S, pq_via=4 * S, pq_metric=4 * S, pq_counts=4 * S * RLFA_COUNT_WORDS, rl_node=4 * n, rl_via=4 * n,
+                     rl_cov=4 * RLFA_COVERAGE_WORDS)
+        for d in (host, sel, nd):
+            sizes.update({k: max(a.nbytes, 8) for k, a in d.items()})
+        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
+            tables = (dev["dist"], dev["flags"], dev["mask"])
+            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            if not symmetric:
+                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
+                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
+                cleanup.callback(GT.free)
+                self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
+            protect = [(0, cand, nbr_row)]
+            self.lfa_device(n, R, W, *tables, protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"],
+                            coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
+            self.rlfa_device(graph, R, W, *tables, dev["dist"] if symmetric else dev["rdist"], protect, pq_node_ptr=dev["pq_node"],
+                             pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"], rl_node_ptr=dev["rl_node"],
+                             rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"], space_flags_ptr=dev["sp_flags"], alt_flags_in_ptr=dev["aflags"],
+                             lfa_flags=lfa_flags)
+            self.rlfa_node_select_device(n, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pq=M, lfa_flags=lfa_flags,
+                                         **{k + "_ptr": dev[k] for k in sel})
+            self._fetch(dict(host, **sel), dev)
+            y_roots = np.unique(sel["nq_node"][sel["nq_node"] != NO_ROOT]).astype(np.uint32)
+            if len(y_roots) == 0:                       # no list holds a node: one padding row keeps the test's arguments valid
+                y_roots = np.array([NO_ROOT], np.uint32)
+            with self._dev_buffers(dict(ydist=4 * len(y_roots) * n)) as ydev:
+                if y_roots[0] != NO_ROOT:
+                    self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
+                self.rlfa_node_device(n, R, W, *tables, protect, ydist_ptr=ydev["ydist"], y_roots=y_roots, sel=tuple(dev[k] for k in sel),
+                                      max_pq=M, alt_flags_in_ptr=dev["aflags"], **{k + "_ptr": dev[k] for k in nd})
+                self._fetch(nd, dev)
+        lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
+        return RlfaNodeResult(*sel.values(), y_roots, *nd.values(), candidates=cand, lfa=lfa)
 
     def close(self):
         if self.handle:

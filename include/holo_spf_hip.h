@@ -781,7 +781,8 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
  * return HSPF_E_INVAL with a text in hspf_last_error that names hspf_rlfa_device, before anything is launched.  Everything is
  * enqueued on the context's stream; the call synchronises once at the end.
  *
- * OUT OF SCOPE: node-protecting remote LFA (RFC 8102: the PQ node's path to D may cross E); loop-freeness with respect to a
+ * Node-protecting remote LFA (RFC 8102: the PQ node's path to D may cross E) is hspf_rlfa_node_select_device /
+ * hspf_rlfa_node_device, below.  OUT OF SCOPE: loop-freeness with respect to a
  * LAN pseudonode (the same root_link rule and the same limitation as hspf_lfa_device); segment lists beyond one tunnel
  * (hspf_tilfa_device, below, adds one forced adjacency). */
 #define HSPF_RLFA_VIA_SELF       0xFFFFFFFEu   /* pq_via / space_via / rl_via: released by S itself (P-space) */
@@ -853,7 +854,8 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
  * the second segment is the Adj-SID p advertises for the link at position ti_link of its row.
  *
  * OUT OF SCOPE: adjacencies across a LAN pseudonode (p -> network vertex -> q is not offered: q must be a router in p's own
- * row); node protection; segment lists longer than two; post-convergence-path selection among equal-cost repairs. */
+ * row); node protection (one-segment node-protecting repairs: hspf_rlfa_node_device, below; two-segment ones are out of
+ * scope there too); segment lists longer than two; post-convergence-path selection among equal-cost repairs. */
 #define HSPF_TILFA_NONE           0u            /* ti_kind */
 #define HSPF_TILFA_NODE           1u
 #define HSPF_TILFA_PAIR           2u
@@ -934,7 +936,7 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
  *
  * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (the other primaries
  * are the backups; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
- * td_kind); node-protecting remote repairs; loop-freeness with respect to a LAN pseudonode (the same limitation as
+ * td_kind); node-protecting remote repairs per prefix (per destination vertex: hspf_rlfa_node_device, below); loop-freeness with respect to a LAN pseudonode (the same limitation as
  * hspf_lfa_device).  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
 #define HSPF_BK_NO_ROUTE       0u
 #define HSPF_BK_LOCAL          1u
@@ -958,6 +960,88 @@ int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_row
                               const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                               const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *table,
                               const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev);
+
+/* ---- node-protecting remote loop-free alternates on device (RFC 8102): new symbols, same ABI number -------------------------
+ * hspf_rlfa_device protects LINKS: the tunnel to its PQ node, and that node's own path on to the destination, may run straight
+ * through the router E behind the protected link.  RFC 8102 keeps the cheapest few link-protecting PQ nodes of every protected
+ * link whose release path avoids the node E (the RFC's default limit is 16), runs a forward SPF rooted at each of them, and
+ * tests per destination whether the node's own path avoids E.  "A forward SPF per PQ node" is one more hspf_run_device of a
+ * many-roots batch on the same read-only graph; the two steps around it are the calls below.  Neither takes a graph.
+ *
+ * hspf_rlfa_node_select_device.  The forward table set, `prot` and lfa_flags are exactly those of hspf_lfa_device;
+ * space_flags_dev [n_prot][stride][n_vertices] is what hspf_rlfa_device wrote for the same `prot` and lfa_flags (Q-space is read
+ * from it: no reverse distances).  max_pq is 1 .. HSPF_RLFA_NODE_MAX_PQ.
+ * Per protected root S and candidate slot e (E = nbr[e]); N_k = nbr[k]; every sum is evaluated in 64 bits; a term that is
+ * HSPF_DIST_INF makes its inequality false.
+ *   NP(e, v)      d(S, v) < d(S, E) + d(E, v): S's own shortest paths to v avoid the node E
+ *   NXP(e, k, v)  d(N_k, v) < d(N_k, E) + d(E, v)   for a via-slot k of hspf_rlfa_device's XP rule (nbr[k] != HSPF_NO_ROOT,
+ *                 root_link[k] != root_link[e], cflags[k] without HSPF_LFA_C_NO_TRANSIT unless the call passes
+ *                 HSPF_LFA_IGNORE_OVERLOAD) with N_k != E (a parallel link to E is no way round E)
+ *   v qualifies   iff space_flags[e][v] has HSPF_RLFA_ELIGIBLE and _IN_Q, and _IN_P or _IN_XP (so the list is a subset of the
+ *                 link-protecting PQ set whatever the vertex flags of the graph), v != E, and NP or some NXP holds
+ *   release point the smallest (64 bits) of d(S, v) if NP holds (via = HSPF_RLFA_VIA_SELF) and cost[k] + d(N_k, v) over the k
+ *                 with NXP (via = k); on a tie S comes first, then the smaller k.  The release metric is that sum saturated
+ *                 at 0xFFFFFFFE.
+ * Outputs (DEVICE pointers; slots are strided by 64 * n_mask_words per protected root):
+ *   nq_node / nq_via / nq_metric [n_prot][stride][max_pq]: the qualifying vertices in ascending order of (release metric, vertex
+ *                 index), the first min(nq_count, max_pq) of them; the rest of a list, and the lists of slots that are no
+ *                 candidates or >= n_slots, are HSPF_NO_ROOT / HSPF_LFA_NO_SLOT / 0.
+ *   nq_count [n_prot][stride]: ALL qualifying vertices of the slot (may exceed max_pq); 0 for slots that are no candidates.
+ *
+ * hspf_rlfa_node_device.  ydist_dev [n_yrows][n_vertices] is `dist` of a FORWARD hspf_run_device whose root list was y_roots
+ * (HOST array): the caller's choice — the union of the lists, or fewer.  HSPF_NO_ROOT entries are skipped; a vertex listed
+ * twice may use either row; a listed node without a row is skipped.  The vertex -> row map is built on the device.  sel_dev
+ * and max_pq are those of the select call; alt_flags_in_dev: NULL, or the alt_flags of hspf_lfa_device for the same `prot`.
+ * Per S and destination D in S's SPT, D != S, with exactly ONE primary slot e (E = nbr[e]):
+ *   entry j < min(nq_count[e], max_pq) with Y = nq_node[e][j] protects D iff  d(Y, D) < d(Y, E) + d(E, D)   (d(Y, .) from Y's
+ *                 row, d(E, D) from row nbr_row[e] of the forward set)
+ *   choice        among the protecting entries the smallest nq_metric[e][j] + d(Y, D) (64 bits), then the smaller j
+ *   nd_kind u8    0 unless D has exactly one primary; else, in this order: HSPF_NP_D_LFA the given alt_flags have
+ *                 HSPF_LFA_NODE_PROTECT | HSPF_NP_D_NONE the slot is no candidate | HSPF_NP_D_LAST_HOP D == E (node protection is
+ *                 undefined: the link repair is all there is) | HSPF_NP_D_PQ an entry was chosen | HSPF_NP_D_NONE
+ *   nd_node / nd_via / nd_metric   for HSPF_NP_D_PQ the chosen entry's node and via, and the sum saturated at 0xFFFFFFFE;
+ *                 HSPF_NO_ROOT / HSPF_LFA_NO_SLOT / 0 otherwise
+ *   nd_set u32    optional (NULL skips the table): bit j = entry j protects D, for the D that reach the test; 0 otherwise
+ *   nd_coverage [n_prot][5], counted on the device: destinations with exactly one primary, then the four classes.
+ * Argument errors of both — a NULL required pointer, everything hspf_lfa_device rejects in `prot`, max_pq outside
+ * 1 .. HSPF_RLFA_NODE_MAX_PQ, n_yrows == 0, a y_roots entry >= n_vertices that is not HSPF_NO_ROOT — return HSPF_E_INVAL with a
+ * text in hspf_last_error that names the function, before anything is launched.  Everything is enqueued on the context's
+ * stream; each call synchronises once at the end.
+ *
+ * From nd_* to a tunnel that survives the neighbour's failure: INTEGRATION.md §5l.
+ *
+ * OUT OF SCOPE: two-segment node-protecting repairs (a forced adjacency after the tunnel); LAN pseudonodes as the protected
+ * node (the failure of every router behind the primary's LAN); per-prefix node-protecting remote repairs; SRLGs. */
+#define HSPF_RLFA_NODE_MAX_PQ   32u
+#define HSPF_NP_D_LFA           1u             /* nd_kind */
+#define HSPF_NP_D_PQ            2u
+#define HSPF_NP_D_LAST_HOP      3u
+#define HSPF_NP_D_NONE          4u
+#define HSPF_NP_COVERAGE_WORDS  5u
+typedef struct {                 /* DEVICE pointers; stride = 64 * n_mask_words                               */
+  uint32_t *nq_node;             /* [n_prot][stride][max_pq]  HSPF_NO_ROOT-padded                              */
+  uint32_t *nq_via;              /* [n_prot][stride][max_pq]  HSPF_RLFA_VIA_SELF or a slot; HSPF_LFA_NO_SLOT padding */
+  uint32_t *nq_metric;           /* [n_prot][stride][max_pq]  release metric; 0 padding                        */
+  uint32_t *nq_count;            /* [n_prot][stride]          ALL qualifying vertices (may exceed max_pq)      */
+} hspf_rlfa_node_sel;
+int hspf_rlfa_node_select_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                 const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                 const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags,
+                                 const uint8_t *space_flags_dev, uint32_t max_pq, hspf_rlfa_node_sel *out_dev);
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint8_t  *nd_kind;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *nd_node;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *nd_via;              /* [n_prot][n_vertices]                                                       */
+  uint32_t *nd_metric;           /* [n_prot][n_vertices]                                                       */
+  uint32_t *nd_set;              /* [n_prot][n_vertices] bit j = list entry j protects; or NULL                */
+  uint32_t *nd_coverage;         /* [n_prot][HSPF_NP_COVERAGE_WORDS]                                           */
+} hspf_rlfa_node_out;
+int hspf_rlfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                          const hspf_lfa_protect *prot, uint32_t n_prot,
+                          const uint32_t *ydist_dev, const uint32_t *y_roots /* HOST */, uint32_t n_yrows,
+                          const hspf_rlfa_node_sel *sel_dev, uint32_t max_pq,
+                          const uint8_t *alt_flags_in_dev, hspf_rlfa_node_out *out_dev);
 
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root

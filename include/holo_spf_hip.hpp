@@ -415,6 +415,25 @@ class Engine {
     t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, &t, nullptr, nullptr);
     return t;
   }
+  // hspf_rlfa_node_select_device on DEVICE tables: the table set and protect list of lfa_device and the space_flags rlfa_device
+  // wrote for them; the lists are [protect.size()][64 * n_mask_words][max_pq].
+  void rlfa_node_select_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                               const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags,
+                               const uint8_t *space_flags_dev, uint32_t max_pq, hspf_rlfa_node_sel out_dev) {
+    const int rc = hspf_rlfa_node_select_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                                (uint32_t)protect.size(), lfa_flags, space_flags_dev, max_pq, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_node_select_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // hspf_rlfa_node_device on DEVICE tables: ydist_dev is the dist of a forward run of y_roots (host list: the caller's choice among
+  // the listed nodes), sel_dev what rlfa_node_select_device wrote with the same max_pq.
+  void rlfa_node_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                        const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const uint32_t *ydist_dev,
+                        const std::vector<uint32_t> &y_roots, const hspf_rlfa_node_sel &sel_dev, uint32_t max_pq, const uint8_t *alt_flags_in_dev,
+                        hspf_rlfa_node_out out_dev) {
+    const int rc = hspf_rlfa_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                         ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pq, alt_flags_in_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_node_device (") + hspf_last_error(ctx_) + ")");
+  }
   // hspf_routes_backup_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the routes
   // hspf_routes_device wrote for it, optionally the per-slot arrays of tilfa_device (nullptr: no remote fallback).
   void routes_backup_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,

@@ -139,6 +139,20 @@ struct TilfaOut {
   std::vector<uint8_t> td_kind;                             // [n_protected][n_vertices] HSPF_TILFA_D_*
   std::vector<uint32_t> td_coverage;                        // [n_protected][HSPF_TILFA_COVERAGE_WORDS]
 };
+// Node-protecting remote loop-free alternates (RFC 8102: hspf_rlfa_node_select_device, one run over the listed nodes,
+// hspf_rlfa_node_device) of the same protected roots: per (protected root, slot) the cheapest max_pq PQ nodes whose release path
+// avoids the neighbour behind the slot, and per destination the cheapest of them whose own path avoids it too, from the forward
+// DeviceRun and the space_flags of rlfa(..., with_spaces = true).  supported == false: no such call.
+struct RlfaNodeOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_vertices = 0, slot_stride = 64, max_pq = 0;
+  std::vector<uint32_t> nq_node, nq_via, nq_metric;         // [n_protected][slot_stride][max_pq]
+  std::vector<uint32_t> nq_count;                           // [n_protected][slot_stride]
+  std::vector<uint32_t> y_roots;                            // the roots of the PQ-node rows: the ascending union of the lists
+  std::vector<uint8_t> nd_kind;                             // [n_protected][n_vertices] HSPF_NP_D_*
+  std::vector<uint32_t> nd_node, nd_via, nd_metric, nd_set; // [n_protected][n_vertices]
+  std::vector<uint32_t> nd_coverage;                        // [n_protected][HSPF_NP_COVERAGE_WORDS]
+};
 // Per-prefix backup routes (hspf_routes_backup_device) of the same protected roots over the prefix table of a DeviceRoutes: per
 // (protected root, prefix) the kind of backup (HSPF_BK_*), the primary slot, the backup slot / metric / flags.  `tilfa`: nullptr, or
 // what tilfa() returned for the same protect list (the fallback to the primary link's repair).  supported == false: no such call.
@@ -156,6 +170,10 @@ class Engine {
   // `routes`: what routes_device() wrote for `run` and the prefix table.  The default: not supported.
   virtual BackupOut backup_routes(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                                   const TilfaOut * /*tilfa*/) { return BackupOut{}; }
+  // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph `run` was made on, the
+  // PQ-node rows are run on it with `run_flags`.  The default: not supported.
+  virtual RlfaNodeOut rlfa_node(Graph &, DeviceRun & /*run*/, const std::vector<LfaProtect> &, uint32_t /*run_flags*/, uint32_t /*lfa_flags*/,
+                                const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/, uint32_t /*max_pq*/) { return RlfaNodeOut{}; }
   // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph.  The default: not supported.
   virtual TilfaOut tilfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                          const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/) { return TilfaOut{}; }
@@ -818,6 +836,81 @@ class HipEngine : public Engine {
     }
     pool_->dev_free(blk, total);
     if (!ok) throw std::runtime_error(std::string("hspf_tilfa_device: ") + hspf_last_error(ctx_));
+    return o;
+  }
+  RlfaNodeOut rlfa_node(Graph &gr, DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t run_flags, uint32_t lfa_flags, const LfaOut *lfa,
+                        const RlfaOut &rl, uint32_t max_pq) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    RlfaNodeOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words; o.max_pq = max_pq;
+    if (protect.empty()) return o;
+    if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) throw std::runtime_error("rlfa_node: max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = ps * o.n_vertices, pm = ps * max_pq;
+    if (rl.space_flags.size() != sp) throw std::runtime_error("rlfa_node: the RLFA result holds no space tables of this protect list");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("rlfa_node: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t cb = (size_t)o.n_protected * HSPF_NP_COVERAGE_WORDS;
+    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
+    // one block: nq_node | nq_via | nq_metric | nq_count | nd_node | nd_via | nd_metric | nd_set | nd_coverage | nd_kind | space_flags | alt_flags
+    const size_t words = pm * 3 + ps + pn * 4 + cb, total = words * 4 + pn + sp + (with_alt ? pn : 0);
+    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    uint32_t *w = (uint32_t *)blk;
+    hspf_rlfa_node_sel sel{};
+    hspf_rlfa_node_out out{};
+    sel.nq_node = w; w += pm; sel.nq_via = w; w += pm; sel.nq_metric = w; w += pm; sel.nq_count = w; w += ps;
+    out.nd_node = w; w += pn; out.nd_via = w; w += pn; out.nd_metric = w; w += pn; out.nd_set = w; w += pn; out.nd_coverage = w; w += cb;
+    uint8_t *b = (uint8_t *)w;
+    out.nd_kind = b; b += pn;
+    uint8_t *sf = b; b += sp;
+    uint8_t *alt = with_alt ? b : nullptr;
+    bool ok = hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
+              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
+    auto fetch = [&](auto &vec, const void *src, size_t count) {
+      vec.resize(count);
+      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
+    };
+    const char *what = "hspf_rlfa_node_select_device: ";
+    int rc = ok ? hspf_rlfa_node_select_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, sf,
+                                               max_pq, &sel) : HSPF_E_HIP;
+    ok = ok && rc == HSPF_OK;
+    uint32_t *ydist = nullptr;
+    size_t ybytes = 0;
+    if (ok) {
+      fetch(o.nq_node, sel.nq_node, pm); fetch(o.nq_via, sel.nq_via, pm); fetch(o.nq_metric, sel.nq_metric, pm); fetch(o.nq_count, sel.nq_count, ps);
+    }
+    if (ok) {
+      for (uint32_t v : o.nq_node) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
+      std::sort(o.y_roots.begin(), o.y_roots.end());
+      o.y_roots.erase(std::unique(o.y_roots.begin(), o.y_roots.end()), o.y_roots.end());
+      const bool none = o.y_roots.empty();
+      if (none) o.y_roots.push_back(HSPF_NO_ROOT);        // one padding row keeps the arguments of the second call valid
+      ybytes = o.y_roots.size() * (size_t)o.n_vertices * 4;
+      ydist = (uint32_t *)pool_->dev(ybytes);
+      if (!none) {
+        what = "hspf_run_device (the PQ-node rows): ";
+        hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
+        rc = hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, o.y_roots.data(), (uint32_t)o.y_roots.size(), run_flags, &yres);
+        ok = rc == HSPF_OK;
+      }
+      if (ok) {
+        what = "hspf_rlfa_node_device: ";
+        rc = hspf_rlfa_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, ydist, o.y_roots.data(),
+                                   (uint32_t)o.y_roots.size(), &sel, max_pq, alt, &out);
+        ok = rc == HSPF_OK;
+      }
+      if (ok) {
+        fetch(o.nd_kind, out.nd_kind, pn); fetch(o.nd_node, out.nd_node, pn); fetch(o.nd_via, out.nd_via, pn); fetch(o.nd_metric, out.nd_metric, pn);
+        fetch(o.nd_set, out.nd_set, pn); fetch(o.nd_coverage, out.nd_coverage, cb);
+      }
+    }
+    if (ydist) pool_->dev_free(ydist, ybytes);
+    pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
     return o;
   }
   RouteEvents routes_events(DeviceRoutes &old_set, DeviceRoutes &new_set, bool with_silent) override {

@@ -326,6 +326,35 @@ impl Tilfa {
     }
 }
 
+/// Node-protecting remote loop-free alternates (RFC 8102) of the protected roots of one `Engine::rlfa_node_device` call.  Slots
+/// are strided by `slot_stride` = 64 * mask words per protected root, lists by `max_pq` per slot.
+pub struct RlfaNode {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub slot_stride: u32,
+    pub max_pq: u32,
+    pub nq_node: Vec<u32>,
+    pub nq_via: Vec<u32>,
+    pub nq_metric: Vec<u32>,
+    pub nq_count: Vec<u32>,
+    pub y_roots: Vec<u32>,
+    pub nd_kind: Vec<u8>,
+    pub nd_node: Vec<u32>,
+    pub nd_via: Vec<u32>,
+    pub nd_metric: Vec<u32>,
+    pub nd_set: Vec<u32>,
+    pub nd_coverage: Vec<u32>,
+}
+
+impl RlfaNode {
+    /// The tunnel that protects destination `d` of protected root `i` against the failure of its primary neighbour:
+    /// (PQ node, via, cost), `None` unless its class is `HSPF_NP_D_PQ`.
+    pub fn repair(&self, i: usize, d: u32) -> Option<(u32, u32, u32)> {
+        let k = i * self.n_vertices as usize + d as usize;
+        (self.nd_kind[k] as u32 == sys::HSPF_NP_D_PQ).then(|| (self.nd_node[k], self.nd_via[k], self.nd_metric[k]))
+    }
+}
+
 /// `hspf_run_device` results left in HBM: input of `routes_device` / `ancestors_device`.
 pub struct DeviceTables<'e> {
     pub n_roots: u32,
@@ -865,6 +894,140 @@ impl Engine {
             ti_counts: ti_counts.to_host(slots * sys::HSPF_TILFA_COUNT_WORDS as usize)?,
             td_kind: td_kind.to_host(cells)?,
             td_coverage: td_cov.to_host(np * sys::HSPF_TILFA_COVERAGE_WORDS as usize)?,
+        })
+    }
+
+    /// `hspf_rlfa_node_select_device`, one `hspf_run_device` over the ascending union of the listed nodes, then
+    /// `hspf_rlfa_node_device`: per destination with one primary the cheapest of the `max_pq` listed PQ nodes whose release path
+    /// and whose own path to the destination both avoid the primary's neighbour.  `g` is the FORWARD graph; `tables`, `protect`,
+    /// `lfa` as for `rlfa_device`; `rlfa`: what `rlfa_device` returned for the same `protect` with `with_spaces`; `run_flags`: those
+    /// `tables` were made with (the PQ-node rows come from a run of the same kind).
+    pub fn rlfa_node_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, run_flags: u32, protect: &[(u32, &LfaCandidates, &[u32])],
+                            ignore_overload: bool, lfa: Option<&Lfa>, rlfa: &Rlfa, max_pq: u32) -> Result<RlfaNode, Error> {
+        let (n, np) = (tables.n_vertices as usize, protect.len());
+        if max_pq == 0 || max_pq > sys::HSPF_RLFA_NODE_MAX_PQ {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_node_device: max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_node_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let stride = 64 * tables.words as usize;
+        let (slots, cells, m) = (np * stride, np * n, max_pq as usize);
+        if rlfa.space_flags.len() != slots * n {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_node_device: the RLFA result holds no space tables of this protect list".into() });
+        }
+        let sp_flags = self.device_from(&rlfa.space_flags)?;
+        let alt = match lfa {
+            Some(l) if l.alt_flags.len() == cells => Some(self.device_from(&l.alt_flags)?),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_node_device: the LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let nq_node = self.device_alloc(slots * m * 4)?;
+        let nq_via = self.device_alloc(slots * m * 4)?;
+        let nq_metric = self.device_alloc(slots * m * 4)?;
+        let nq_count = self.device_alloc(slots * 4)?;
+        let mut sel = sys::hspf_rlfa_node_sel {
+            nq_node: nq_node.p as *mut u32,
+            nq_via: nq_via.p as *mut u32,
+            nq_metric: nq_metric.p as *mut u32,
+            nq_count: nq_count.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_rlfa_node_select_device(
+                self.ctx,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                lfa_flags,
+                sp_flags.p as *const u8,
+                max_pq,
+                &mut sel,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let nodes: Vec<u32> = nq_node.to_host(slots * m)?;
+        let mut y_roots: Vec<u32> = nodes.iter().copied().filter(|&v| v != sys::HSPF_NO_ROOT).collect();
+        y_roots.sort_unstable();
+        y_roots.dedup();
+        if y_roots.is_empty() {
+            y_roots.push(sys::HSPF_NO_ROOT); // one padding row keeps the arguments of the second call valid
+        }
+        let y = self.run_device(g, &y_roots, run_flags)?;
+        let nd_kind = self.device_alloc(cells)?;
+        let nd_node = self.device_alloc(cells * 4)?;
+        let nd_via = self.device_alloc(cells * 4)?;
+        let nd_metric = self.device_alloc(cells * 4)?;
+        let nd_set = self.device_alloc(cells * 4)?;
+        let nd_cov = self.device_alloc(np * sys::HSPF_NP_COVERAGE_WORDS as usize * 4)?;
+        let mut out = sys::hspf_rlfa_node_out {
+            nd_kind: nd_kind.p as *mut u8,
+            nd_node: nd_node.p as *mut u32,
+            nd_via: nd_via.p as *mut u32,
+            nd_metric: nd_metric.p as *mut u32,
+            nd_set: nd_set.p as *mut u32,
+            nd_coverage: nd_cov.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_rlfa_node_device(
+                self.ctx,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                y.dist.p as *const u32,
+                y_roots.as_ptr(),
+                y_roots.len() as u32,
+                &sel,
+                max_pq,
+                alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(RlfaNode {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            slot_stride: stride as u32,
+            max_pq,
+            nq_node: nodes,
+            nq_via: nq_via.to_host(slots * m)?,
+            nq_metric: nq_metric.to_host(slots * m)?,
+            nq_count: nq_count.to_host(slots)?,
+            y_roots,
+            nd_kind: nd_kind.to_host(cells)?,
+            nd_node: nd_node.to_host(cells)?,
+            nd_via: nd_via.to_host(cells)?,
+            nd_metric: nd_metric.to_host(cells)?,
+            nd_set: nd_set.to_host(cells)?,
+            nd_coverage: nd_cov.to_host(np * sys::HSPF_NP_COVERAGE_WORDS as usize)?,
         })
     }
 
