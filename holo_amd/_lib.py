@@ -78,6 +78,10 @@ class HspfLfaProtect(ctypes.Structure):
                 ("nbr", u32p), ("nbr_row", u32p), ("cost", u32p), ("root_link", u32p), ("cflags", u8p)]
 
 
+class HspfLfaLan(ctypes.Structure):
+    _fields_ = [("lan", u32p), ("lan_row", u32p)]
+
+
 class HspfLfaOut(ctypes.Structure):
     _fields_ = [("alt_slot", ctypes.c_void_p), ("alt_metric", ctypes.c_void_p), ("alt_flags", ctypes.c_void_p),
                 ("cand_mask", ctypes.c_void_p), ("node_mask", ctypes.c_void_p), ("coverage", ctypes.c_void_p)]
@@ -186,6 +190,15 @@ SYMBOLS = [
     ("hspf_lfa_candidates", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u8p, u32p]),
     ("hspf_lfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfLfaOut)]),
+    # broadcast-link protection (RFC 5286 section 3.3)
+    ("hspf_lfa_lan_candidates", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, ctypes.c_uint32, u32p, u32p]),
+    ("hspf_lfa_lan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.POINTER(HspfLfaLan), ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.POINTER(HspfLfaOut)]),
+    ("hspf_routes_backup_lan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.POINTER(HspfLfaLan),
+                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes),
+                                                     ctypes.POINTER(HspfTilfaOut), ctypes.POINTER(HspfBackupOut)]),
     # remote loop-free alternates
     ("hspf_csr_transpose", ctypes.c_int, [ctypes.POINTER(HspfCsr), u32p, u32p, u32p]),
     ("hspf_rlfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,

@@ -12,6 +12,9 @@
 //   k_backup       everything but the counts.
 //   k_backup_cov   the coverage: a wave counts the kinds of its prefixes with ballots (grid-stride over the tiles of one
 //                  protected root), then one vector atomic add per wave and kind.
+// The LAN variants (hspf_routes_backup_lan_device) are k_backup_lan, a further instantiation of the same body, and
+// k_backup_cov_lan: d_L(p) of the one primary's LAN is computed once next to d_E(p); a candidate that has passed every plain
+// condition is then held against d(N, L) + d_L(p); the per-link repair is taken only for a point-to-point primary.
 // There is no wave-per-prefix path: a prefix with very many advertisers is walked by ONE lane and holds its wave back.
 #pragma once
 
@@ -62,7 +65,8 @@ __device__ __forceinline__ bool bk_less(uint64_t x, uint32_t b, uint64_t c) {
   return x != BK_NO_DIST && b != LFA_NONE && x < (uint64_t)b + c;
 }
 
-__global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
+template <bool LAN>
+__device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &la) {
   const uint32_t pi = blockIdx.y;
   const FrrTab tb = frr_tab(a.tab, a.scal, pi);
   const uint32_t K = tb.K, C = tb.C, n = a.n, W = a.W, Wk = tb.Wk;
@@ -82,6 +86,19 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
   if (np == 1) {
     rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
     if (E0 != LFA_NONE) dE0p = bk_dist_to_prefix(a, tb.row[p0], lo, hi);
+  }
+  LanTab lt{};
+  uint32_t li0 = LFA_NONE, lfl = 0;                                                // LAN: the one primary's LAN; the two LAN bits
+  uint64_t dL0p = BK_NO_DIST;
+  bool lanp = false;                                                               // LAN: some primary crosses a LAN of S
+  if constexpr (LAN) {
+    lt = lan_tab(la, pi, K);
+    if (np == 1) {
+      li0 = lt.li[p0];
+      lanp = li0 != LFA_NONE;
+      if (lanp) dL0p = bk_dist_to_prefix(a, lt.lrow[p0], lo, hi);
+    } else if (np >= 2) lanp = lan_any_primary(tb, lt, pm);
+    if (lanp) lfl |= 0x20u;
   }
   bool have = false, bnode = false, bdown = false;
   uint64_t bsum = 0, cw = 0, nw = 0;
@@ -121,11 +138,14 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
       bool ok, nd = false;
       if (np == 1) {
         ok = tb.rl[k] != rl0;                                                      // (k == p0 has p0's root_link)
+        if constexpr (LAN) {                                                       // every plain condition holds: now the pseudonode
+          if (ok && lanp && !(dL0p != BK_NO_DIST && bk_less(d, lt.ml[k * lt.NL + li0], dL0p))) { ok = false; lfl |= 0x40u; }
+        }
         nd = ok && E0 != LFA_NONE && dE0p != BK_NO_DIST && bk_less(d, tb.m[k * K + p0], dE0p);
       } else {
         ok = !((pm[k >> 6] >> (k & 63u)) & 1ull);
         uint32_t n_router = 0;
-        bool all = true;
+        bool all = true, lanok = true;
         const uint32_t rlk = tb.rl[k];
         for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
           uint64_t x = frr_word(tb, pm, w2);
@@ -140,7 +160,19 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
                 all = dEp != BK_NO_DIST && bk_less(d, tb.m[k * K + q], dEp);
               }
             }
+            if constexpr (LAN) {
+              if (lanp && lanok) {
+                const uint32_t j = lt.li[q];
+                if (j != LFA_NONE) {
+                  const uint64_t dLp = bk_dist_to_prefix(a, lt.lrow[q], lo, hi);
+                  lanok = dLp != BK_NO_DIST && bk_less(d, lt.ml[k * lt.NL + j], dLp);
+                }
+              }
+            }
           }
+        }
+        if constexpr (LAN) {
+          if (ok && !lanok) { ok = false; lfl |= 0x40u; }
         }
         nd = ok && n_router && all;
       }
@@ -167,14 +199,18 @@ __global__ __launch_bounds__(256) void k_backup(BackupArgs a) {
       kind = 3u; slot = aslot;
       met = bsum > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)bsum;
       fl = (bnode ? 0x08u : 0u) | (bdown ? 0x10u : 0u);
-    } else if (a.ti_kind) {
+    } else if (a.ti_kind && !(LAN && lanp)) {                                               // (the per-link repairs are not known to avoid a LAN)
       const size_t o = (size_t)pi * a.stride + p0;
       const uint32_t tk = a.ti_kind[o];
       if (tk) { kind = tk == 1u ? 4u : 5u; slot = a.ti_via[o]; met = a.ti_metric[o]; }
     }
   }
+  if constexpr (LAN) fl |= lfl;
   a.bk_kind[oo] = (uint8_t)kind; a.bk_primary[oo] = prim; a.bk_slot[oo] = slot; a.bk_metric[oo] = met; a.bk_flags[oo] = (uint8_t)fl;
 }
+
+__global__ __launch_bounds__(256) void k_backup(BackupArgs a) { backup_body<false>(a, LanArgs{}); }
+__global__ __launch_bounds__(256) void k_backup_lan(BackupArgs a, LanArgs la) { backup_body<true>(a, la); }
 
 // coverage[pi][kind]: ballots per tile, the counts kept in lanes 0 .. 6, one vector atomic add per wave and kind
 __global__ __launch_bounds__(256) void k_backup_cov(BackupArgs a) {
@@ -191,6 +227,25 @@ __global__ __launch_bounds__(256) void k_backup_cov(BackupArgs a) {
     }
   }
   if (lane < BK_KINDS && mine) atomicAdd(a.coverage + (size_t)pi * BK_KINDS + lane, mine);
+}
+
+// the LAN call's coverage[pi][9]: the seven kinds, then the prefixes with HSPF_LFA_LAN_PRIMARY and with HSPF_LFA_LAN_REFUSED in bk_flags
+__global__ __launch_bounds__(256) void k_backup_cov_lan(BackupArgs a) {
+  const uint32_t pi = blockIdx.y, lane = threadIdx.x & 63u;
+  const uint8_t *kinds = a.bk_kind + (size_t)pi * a.n_pfx, *fls = a.bk_flags + (size_t)pi * a.n_pfx;
+  uint32_t mine = 0;
+  for (uint32_t t0 = blockIdx.x * 256u; t0 < a.n_pfx; t0 += gridDim.x * 256u) {
+    const uint32_t p = t0 + threadIdx.x;
+    const uint32_t kind = p < a.n_pfx ? kinds[p] : BK_KINDS;
+    const uint32_t fl = p < a.n_pfx ? fls[p] : 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < BK_KINDS + 2; ++j) {
+      const bool hit = j < BK_KINDS ? kind == j : ((fl >> (5u + j - BK_KINDS)) & 1u) != 0;
+      const uint32_t c = (uint32_t)__popcll(__ballot(hit));
+      if (lane == j) mine += c;
+    }
+  }
+  if (lane < BK_KINDS + 2 && mine) atomicAdd(a.coverage + (size_t)pi * (BK_KINDS + 2) + lane, mine);
 }
 
 }  // namespace

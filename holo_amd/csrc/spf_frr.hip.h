@@ -1,11 +1,14 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
 // hspf_csr_transpose, hspf_rlfa_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
-// hspf_rlfa_node_device.  Included by spf_capi.hip (one TU).
+// hspf_rlfa_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
+// Included by spf_capi.hip (one TU).
 //
 // The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
 // one frame: argument checks, lfa_stage, k_lfa_gather where the kernels need the per-root scalars, the call's own kernels,
 // frr_finish.  `fn` names the calling entry point in hspf_last_error.
 #pragma once
+
+#include <unordered_map>
 
 #include "spf_lfa.hip.h"
 #include "spf_rlfa.hip.h"
@@ -93,6 +96,77 @@ LfaArgs frr_gather(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words, ui
   return a;
 }
 
+// The LAN columns of a LAN call, checked: before anything is staged or launched.
+int lan_check(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const hspf_lfa_protect *prot,
+              const hspf_lfa_lan *lan, uint32_t n_prot) {
+  if (!lan) return frr_bad(ctx, fn, "NULL lan pointer");
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const std::string who = "protected root " + std::to_string(i) + ": ";
+    if (prot[i].n_slots > 64ull * n_mask_words) return frr_bad(ctx, fn, who + "n_slots > 64 * n_mask_words");      // (before lan is read that far)
+    if (prot[i].n_slots && (!lan[i].lan || !lan[i].lan_row)) return frr_bad(ctx, fn, who + "NULL lan / lan_row array");
+    for (uint32_t k = 0; k < prot[i].n_slots; ++k) {
+      if (lan[i].lan[k] == HSPF_NO_ROOT) continue;
+      if (lan[i].lan[k] >= n_vertices) return frr_bad(ctx, fn, who + "lan of slot " + std::to_string(k) + " >= n_vertices");
+      if (lan[i].lan_row[k] >= n_rows) return frr_bad(ctx, fn, who + "lan_row of slot " + std::to_string(k) + " >= n_rows");
+    }
+  }
+  return HSPF_OK;
+}
+
+// The LAN block (its layout: spf_frr_common.hip.h) copied to ctx->lan_tab on the context's stream, with ctx->lan_scal sized for
+// k_lfa_gather_lan.  After lan_check and lfa_stage.  `ltab` is the copy's source: it lives until the caller has synchronised.
+int lan_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, std::vector<uint32_t> &ltab,
+              LanArgs *out, size_t *out_max_gather) {
+  ltab.assign((size_t)n_prot * LAN_HDR_WORDS, 0u);
+  size_t so = 0, max_gather = 0;
+  std::vector<uint32_t> lv;
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const uint32_t K = prot[i].n_slots;
+    const size_t to = ltab.size();
+    ltab.resize(to + 2 * (size_t)K, 0u);
+    lv.clear();
+    std::unordered_map<uint32_t, uint32_t> index;                   // LAN vertex -> its index, in order of first appearance
+    for (uint32_t k = 0; k < K; ++k) {
+      const uint32_t L = lan[i].lan[k];
+      uint32_t j = LFA_NONE;
+      if (L != HSPF_NO_ROOT) {
+        auto it = index.find(L);
+        if (it == index.end()) { it = index.emplace(L, (uint32_t)lv.size()).first; lv.push_back(L); }
+        j = it->second;
+      }
+      ltab[to + k] = j; ltab[to + K + k] = j != LFA_NONE ? lan[i].lan_row[k] : 0u;
+    }
+    ltab.insert(ltab.end(), lv.begin(), lv.end());
+    const size_t NL = lv.size();
+    if (ltab.size() > (1u << 28) || so + (size_t)K * NL > (1u << 28)) { ctx->last_error = std::string(fn) + ": the LAN tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
+    uint32_t *h = ltab.data() + (size_t)i * LAN_HDR_WORDS;
+    h[0] = (uint32_t)NL; h[1] = (uint32_t)to; h[2] = (uint32_t)so;
+    so += (size_t)K * NL;
+    max_gather = std::max(max_gather, (size_t)K * ((size_t)K + 1 + NL));
+  }
+  int rc;
+  if ((rc = ensure(ctx, ctx->lan_tab, ltab.size() * 4, false))) return rc;
+  if ((rc = ensure(ctx, ctx->lan_scal, std::max<size_t>(so, 1) * 4, false))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->lan_tab.p, ltab.data(), ltab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  out->ltab = (const uint32_t *)ctx->lan_tab.p; out->lscal = (uint32_t *)ctx->lan_scal.p;
+  *out_max_gather = max_gather;
+  return HSPF_OK;
+}
+
+// k_lfa_gather_lan on the two staged blocks: what frr_gather leaves, and d(N_k, L) of every protected root
+LfaArgs frr_gather_lan(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words, uint32_t lfa_flags, const uint32_t *dist_dev,
+                       const uint16_t *flags_dev, const uint64_t *mask_dev, uint32_t n_prot, size_t max_gather, const LanArgs &la) {
+  LfaArgs a{};
+  a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
+  a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev;
+  a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (uint32_t *)ctx->lfa_scal.p;
+  if (max_gather) {
+    const uint32_t gx = (uint32_t)std::min<size_t>((max_gather + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_lfa_gather_lan, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a, la);
+  }
+  return a;
+}
+
 // the end of a call: a launch error is reported under the name of its kernels; then the stream is drained
 int frr_finish(hspf_ctx *ctx, const char *kernels) {
   const hipError_t le = hipGetLastError();
@@ -102,13 +176,10 @@ int frr_finish(hspf_ctx *ctx, const char *kernels) {
   return HSPF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-// ---- loop-free alternates (include/holo_spf_hip.h "loop-free alternates on device"; kernels: spf_lfa.hip.h) ----------------
-int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *nbr, uint32_t *cost, uint32_t *root_link,
-                        uint8_t *cflags, uint32_t *out_total_slots) {
+// The walk behind hspf_lfa_candidates and hspf_lfa_lan_candidates: slot(index, target, cost, first link, target is a network,
+// two-way) for every first-hop slot of `root` in slot order.  Returns the number of slots as hspf_lfa_candidates does.
+template <class F>
+int lfa_walk(const hspf_csr *csr, uint32_t root, uint32_t *out_total_slots, F &&slot) {
   if (!csr || !csr->row_ptr || !csr->vflags || (csr->n_edges && (!csr->col || !csr->metric)) || root >= csr->n_vertices) return HSPF_E_INVAL;
   return guarded(nullptr, [&]() -> int {
     const uint32_t n = csr->n_vertices;
@@ -137,13 +208,7 @@ int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32
         const uint32_t first = qi == 0 ? j : p.first_link;
         const bool net = (csr->vflags[t] & HSPF_VF_NETWORK) != 0;
         const bool two = (net || t != root) && links_back(t, p.v);
-        if (total < cap) {
-          const bool is_cand = !net && t != root && two;
-          if (nbr) nbr[total] = is_cand ? t : HSPF_NO_ROOT;
-          if (cost) cost[total] = c;
-          if (root_link) root_link[total] = first;
-          if (cflags) cflags[total] = (is_cand && (csr->vflags[t] & HSPF_VF_NO_TRANSIT)) ? (uint8_t)HSPF_LFA_C_NO_TRANSIT : (uint8_t)0;
-        }
+        slot(total, t, c, first, net, two);
         if (net && two) {
           auto it = std::lower_bound(seen.begin(), seen.end(), t);
           if (it == seen.end() || *it != t) { seen.insert(it, t); H.push_back({t, c, first}); }
@@ -152,6 +217,93 @@ int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32
     }
     if (out_total_slots) *out_total_slots = (uint32_t)total;
     return (int)std::min<uint64_t>(total, 0x7FFFFFFFull);
+  });
+}
+
+// the one frame of hspf_routes_backup_device (with_lan false, `lan` unread) and hspf_routes_backup_lan_device
+int routes_backup(hspf_ctx *ctx, const char *fn, bool with_lan, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                  const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                  const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
+                  const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
+    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
+      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
+    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric)) return bad("NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
+    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
+    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
+    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
+    std::vector<uint32_t> tab, ltab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0;
+    size_t max_gather = 0;
+    LanArgs la{};
+    hipStream_t s = ctx->stream;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
+        (with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, ltab, &la, &max_gather)))) {
+      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * (with_lan ? HSPF_BK_LAN_COVERAGE_WORDS : HSPF_BK_COVERAGE_WORDS) * 4, s));
+    if (!t->n_prefixes) {                               // nothing to launch
+      HIPCHK(ctx, hipStreamSynchronize(s));
+      return HSPF_OK;
+    }
+    const LfaArgs ga = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
+                                : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    BackupArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
+    a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
+    a.dist = dist_dev; a.flags = flags_dev;
+    a.tab = ga.tab; a.scal = ga.scal;
+    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
+    a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
+    if (tilfa_dev) { a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric; }
+    a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
+    a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
+    const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
+    if (with_lan) {
+      hipLaunchKernelGGL(k_backup_lan, dim3(n_tiles, n_prot), dim3(256), 0, s, a, la);
+      hipLaunchKernelGGL(k_backup_cov_lan, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL(k_backup, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
+      hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
+    }
+    return frr_finish(ctx, with_lan ? "k_backup_lan" : "k_backup");
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- loop-free alternates (include/holo_spf_hip.h "loop-free alternates on device"; kernels: spf_lfa.hip.h) ----------------
+int hspf_lfa_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *nbr, uint32_t *cost, uint32_t *root_link,
+                        uint8_t *cflags, uint32_t *out_total_slots) {
+  return lfa_walk(csr, root, out_total_slots, [&](uint64_t k, uint32_t t, uint32_t c, uint32_t first, bool net, bool two) {
+    if (k >= cap) return;
+    const bool is_cand = !net && t != root && two;
+    if (nbr) nbr[k] = is_cand ? t : HSPF_NO_ROOT;
+    if (cost) cost[k] = c;
+    if (root_link) root_link[k] = first;
+    if (cflags) cflags[k] = (is_cand && (csr->vflags[t] & HSPF_VF_NO_TRANSIT)) ? (uint8_t)HSPF_LFA_C_NO_TRANSIT : (uint8_t)0;
+  });
+}
+
+// The slots of the root's own row come first and in link order, so link `first` of a deeper slot has been seen when the slot is.
+int hspf_lfa_lan_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *lan, uint32_t *out_total_slots) {
+  std::vector<uint32_t> of_link;                                    // per link of the root's row: the LAN it leads to
+  uint32_t own = 0;
+  if (csr && csr->row_ptr && root < csr->n_vertices && csr->row_ptr[root] <= csr->row_ptr[root + 1]) own = csr->row_ptr[root + 1] - csr->row_ptr[root];
+  return lfa_walk(csr, root, out_total_slots, [&](uint64_t k, uint32_t t, uint32_t, uint32_t first, bool net, bool two) {
+    if (k < own) of_link.push_back(net && two ? t : HSPF_NO_ROOT);
+    if (k < cap && lan) lan[k] = first < of_link.size() ? of_link[first] : HSPF_NO_ROOT;
   });
 }
 
@@ -178,6 +330,39 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
     if (max_k <= 64) hipLaunchKernelGGL(k_lfa<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
     return frr_finish(ctx, "k_lfa");
+  });
+}
+
+int hspf_lfa_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                        const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                        const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_lfa_lan_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
+    std::vector<uint32_t> tab, ltab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0;
+    size_t max_gather = 0;
+    LanArgs la{};
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = lan_stage(ctx, fn, prot, lan, n_prot, ltab, &la, &max_gather))) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_LAN_COVERAGE_WORDS * 4, s));
+    LfaArgs a = frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la);
+    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
+    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
+    if (max_k <= 64) hipLaunchKernelGGL(k_lfa_lan<true>, grid, dim3(256), 0, s, a, la);
+    else hipLaunchKernelGGL(k_lfa_lan<false>, grid, dim3(256), 0, s, a, la);
+    return frr_finish(ctx, "k_lfa_lan");
   });
 }
 
@@ -315,49 +500,17 @@ int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_row
                               const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                               const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
                               const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_routes_backup_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
-    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
-    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
-      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
-    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric)) return bad("NULL ti_kind / ti_via / ti_metric in tilfa_dev");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
-    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    hipStream_t s = ctx->stream;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) {
-      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
-      return rc;
-    }
-    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * HSPF_BK_COVERAGE_WORDS * 4, s));
-    if (!t->n_prefixes) {                               // nothing to launch
-      HIPCHK(ctx, hipStreamSynchronize(s));
-      return HSPF_OK;
-    }
-    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    BackupArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
-    a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
-    a.dist = dist_dev; a.flags = flags_dev;
-    a.tab = ga.tab; a.scal = ga.scal;
-    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
-    a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
-    if (tilfa_dev) { a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric; }
-    a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
-    a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
-    const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
-    hipLaunchKernelGGL(k_backup, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_backup");
-  });
+  return routes_backup(ctx, "hspf_routes_backup_device", false, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr, n_prot,
+                       lfa_flags, t, routes_dev, tilfa_dev, out_dev);
+}
+
+int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                  const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                  const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
+                                  const hspf_prefix_table *t, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                  hspf_backup_out *out_dev) {
+  return routes_backup(ctx, "hspf_routes_backup_lan_device", true, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, lan, n_prot,
+                       lfa_flags, t, routes_dev, tilfa_dev, out_dev);
 }
 
 // ---- node-protecting remote LFA (include/holo_spf_hip.h "node-protecting remote loop-free alternates on device"; kernels:

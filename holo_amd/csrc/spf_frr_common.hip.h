@@ -17,6 +17,17 @@
 //     candidate slots in ascending order (its other K - C words are 0).
 // `scal` is k_lfa_gather's block, per root at its offset:  d(N_k, S) [K] | d(N_k, N_p) [K][K]   (LFA_NONE where a slot is no
 // candidate or the vertex is not reached).
+//
+// The LAN block of the calls that protect broadcast links (hspf_lfa_lan_device, hspf_routes_backup_lan_device) is a SECOND pair of
+// blocks next to these, written by lan_stage in spf_frr.hip.h; the layout above does not change.  `ltab`:
+//   [n_prot][LAN_HDR_WORDS] headers:  word 0  NL  the distinct LANs of the root's slots
+//                                     word 1  offset (in words, from `ltab`) of the root's LAN columns
+//                                     word 2  offset (in words, from `lscal`) of the root's LAN scalars;   word 3  0
+//   then per root, at its offset:  li [K] | lrow [K] | lv [NL]
+//     li[k] the index (< NL) of the LAN that slot k crosses, LFA_NONE for a point-to-point slot; lrow[k] the row of the SPT rooted
+//     at that LAN's vertex; lv[j] the vertex of LAN j.
+// `lscal` is the LAN part of k_lfa_gather_lan's output, per root at its offset:  d(N_k, lv[j]) [K][NL]  (LFA_NONE where slot k is no
+// candidate).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,6 +39,8 @@ constexpr uint32_t LFA_HDR_WORDS = 8;
 constexpr uint32_t LFA_NONE = 0xFFFFFFFFu;
 constexpr uint32_t LFA_TILE = 256;
 constexpr uint32_t FRR_COLS = 6;           // columns of a root's table: what frr_tab_over names, lfa_stage writes and k_lfa<true> copies
+
+constexpr uint32_t LAN_HDR_WORDS = 4;
 
 // `a < b + c` in 64 bits; any term "not reached" makes it false
 __device__ __forceinline__ bool lfa_less(uint32_t a, uint32_t b, uint32_t c) {
@@ -80,6 +93,33 @@ __device__ __forceinline__ void frr_primaries(const FrrTab &t, const uint64_t *p
     if (x && !np) p0 = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
     np += (uint32_t)__popcll(x);
   }
+}
+
+// the LAN block of the call (both NULL in a call without one), and the view of one protected root over it
+struct LanArgs { const uint32_t *ltab; uint32_t *lscal; };
+struct LanTab {
+  uint32_t NL;
+  const uint32_t *li, *lrow, *lv;                       // [K] | [K] | [NL]
+  const uint32_t *ml;                                   // d(N_k, lv[j]) [K][NL]
+};
+__device__ __forceinline__ LanTab lan_tab(const LanArgs &la, uint32_t pi, uint32_t K) {
+  const uint32_t *hdr = la.ltab + (size_t)pi * LAN_HDR_WORDS;
+  const uint32_t *c = la.ltab + hdr[1];
+  return LanTab{hdr[0], c, c + K, c + 2 * K, la.lscal + hdr[2]};
+}
+
+// does any primary of the destination cross a LAN of S?
+__device__ __forceinline__ bool lan_any_primary(const FrrTab &t, const LanTab &lt, const uint64_t *pm) {
+  bool any = false;
+  for (uint32_t w = 0; w < t.Wk; ++w) {
+    uint64_t x = frr_word(t, pm, w);
+    while (x) {
+      const uint32_t p = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
+      x &= x - 1;
+      any = any || lt.li[p] != LFA_NONE;
+    }
+  }
+  return any;
 }
 
 // The coverage tail of a lane-per-destination kernel: bit j of `fl` counts towards out[j], j < NC.  Wave ballots + popcounts, one

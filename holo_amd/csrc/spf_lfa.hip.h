@@ -15,6 +15,12 @@
 //                  the K x K matrix sit in LDS (at most 18.3 KB), the sets are two registers.  ONE = false: any K, tables
 //                  and matrix are read through the caches (K = 128: 64 KB of matrix, L2-resident), the sets are produced
 //                  word by word.
+// The LAN variants (hspf_lfa_lan_device: RFC 5286 section 3.3, loop-freeness with respect to the pseudonode of a primary's LAN)
+// are further instantiations of the same bodies, k_lfa_gather_lan and k_lfa_lan<ONE>.  The gather adds d(N_k, L) for the
+// distinct LANs L of S — a [K][NL] block indexed by a compact LAN index, not a second K x K matrix — and the streaming kernel
+// reads it through the caches, only for a candidate that has passed every plain condition at a destination whose primary
+// crosses a LAN: the LDS footprint of ONE = true is that of k_lfa<true> (plus two coverage words), and a table set without LANs
+// never evaluates a LAN term.  d(L, D) of the one primary is one more coalesced row read, like d(E, D).
 // Coverage: wave ballots + popcounts, one LDS add per wave and one vector atomic add per workgroup and counter.
 #pragma once
 
@@ -33,7 +39,8 @@ struct LfaArgs {
   uint32_t *alt_slot, *alt_metric; uint8_t *alt_flags; uint64_t *cand_mask, *node_mask; uint32_t *coverage;
 };
 
-__global__ __launch_bounds__(256) void k_lfa_gather(LfaArgs a) {
+template <bool LAN>
+__device__ __forceinline__ void lfa_gather_body(const LfaArgs &a, const LanArgs &la) {
   const FrrTab tb = frr_tab(a.tab, blockIdx.y);
   const uint32_t S = tb.S, K = tb.K;
   uint32_t *out = a.scal + frr_scal_offset(a.tab, blockIdx.y);
@@ -48,17 +55,30 @@ __global__ __launch_bounds__(256) void k_lfa_gather(LfaArgs a) {
     }
     out[i] = v;
   }
+  if constexpr (LAN) {                                                             // d(N_k, L_j): [K][NL]
+    const LanTab lt = lan_tab(la, blockIdx.y, K);
+    uint32_t *lout = la.lscal + la.ltab[(size_t)blockIdx.y * LAN_HDR_WORDS + 2];
+    const uint32_t ltotal = K * lt.NL;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < ltotal; i += gridDim.x * 256u) {
+      const uint32_t k = i / lt.NL, j = i - k * lt.NL;
+      lout[i] = tb.nbr[k] != LFA_NONE ? a.dist[(size_t)tb.row[k] * a.n + lt.lv[j]] : LFA_NONE;
+    }
+  }
 }
 
-template <bool ONE>
-__global__ __launch_bounds__(256) void k_lfa(LfaArgs a) {
-  __shared__ uint32_t s_cov[5];
+__global__ __launch_bounds__(256) void k_lfa_gather(LfaArgs a) { lfa_gather_body<false>(a, LanArgs{}); }
+__global__ __launch_bounds__(256) void k_lfa_gather_lan(LfaArgs a, LanArgs la) { lfa_gather_body<true>(a, la); }
+
+template <bool ONE, bool LAN>
+__device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
+  constexpr uint32_t NC = LAN ? 7 : 5;                                             // alt_flags bits that are counted
+  __shared__ uint32_t s_cov[NC];
   __shared__ uint32_t s_tab[ONE ? (FRR_COLS + 1) * 64 : 1];             // the columns, then d(N_k, S)
   __shared__ uint32_t s_m[ONE ? 64 * 64 : 1];
   const uint32_t tid = threadIdx.x, pi = blockIdx.y;
   FrrTab tb = frr_tab(a.tab, a.scal, pi);
   const uint32_t S = tb.S, K = tb.K, n = a.n, W = a.W, Wk = tb.Wk;
-  if (tid < 5) s_cov[tid] = 0;
+  if (tid < NC) s_cov[tid] = 0;
   if constexpr (ONE) {                                                             // the same view over a copy in LDS
     for (uint32_t i = tid; i < FRR_COLS * K; i += 256u) s_tab[i] = tb.cols[i];
     for (uint32_t i = tid; i < K; i += 256u) s_tab[FRR_COLS * K + i] = tb.dns[i];
@@ -74,6 +94,8 @@ __global__ __launch_bounds__(256) void k_lfa(LfaArgs a) {
   const bool in = valid && D != S && (a.flags[sd] & 1u) && dSD != LFA_NONE;
   uint32_t fl = 0, aslot = LFA_NONE, amet = 0;
   uint64_t cw = 0, nw = 0;                                                         // ONE: the two sets
+  LanTab lt{};
+  if constexpr (LAN) lt = lan_tab(la, pi, K);
   if (in) {
     const uint64_t *pm = a.mask + sd * W;
     uint32_t np, p0;
@@ -83,6 +105,16 @@ __global__ __launch_bounds__(256) void k_lfa(LfaArgs a) {
     if (np == 1) {
       rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
       if (E0 != LFA_NONE) dE0D = a.dist[(size_t)tb.row[p0] * n + D];
+    }
+    uint32_t li0 = LFA_NONE, dL0D = LFA_NONE;                                      // LAN: the one primary's LAN and d(L, D)
+    bool lanp = false;                                                             // LAN: some primary crosses a LAN of S
+    if constexpr (LAN) {
+      if (np == 1) {
+        li0 = lt.li[p0];
+        lanp = li0 != LFA_NONE;
+        if (lanp) dL0D = a.dist[(size_t)lt.lrow[p0] * n + D];
+      } else if (np >= 2) lanp = lan_any_primary(tb, lt, pm);
+      if (lanp) fl |= 0x20u;
     }
     bool have = false, bnode = false, bdown = false;
     uint64_t bsum = 0;
@@ -98,10 +130,13 @@ __global__ __launch_bounds__(256) void k_lfa(LfaArgs a) {
         bool ok = true, nd = false;
         if (np == 1) {
           ok = tb.rl[k] != rl0;
+          if constexpr (LAN) {                                                     // every plain condition holds: now the pseudonode
+            if (ok && lanp && !lfa_less(dND, lt.ml[k * lt.NL + li0], dL0D)) { ok = false; fl |= 0x40u; }
+          }
           nd = ok && E0 != LFA_NONE && lfa_less(dND, tb.m[k * K + p0], dE0D);
         } else if (np >= 2) {
           uint32_t n_router = 0;
-          bool all = true;
+          bool all = true, lanok = true;
           const uint32_t rlk = tb.rl[k];
           for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
             uint64_t x = frr_word(tb, pm, w2);
@@ -113,7 +148,16 @@ __global__ __launch_bounds__(256) void k_lfa(LfaArgs a) {
                 ++n_router;
                 all = all && lfa_less(dND, tb.m[k * K + p], a.dist[(size_t)tb.row[p] * n + D]);
               }
+              if constexpr (LAN) {
+                if (lanp && lanok) {
+                  const uint32_t j = lt.li[p];
+                  if (j != LFA_NONE) lanok = lfa_less(dND, lt.ml[k * lt.NL + j], a.dist[(size_t)lt.lrow[p] * n + D]);
+                }
+              }
             }
+          }
+          if constexpr (LAN) {
+            if (ok && !lanok) { ok = false; fl |= 0x40u; }
           }
           nd = ok && n_router && all;
         }
@@ -146,7 +190,12 @@ __global__ __launch_bounds__(256) void k_lfa(LfaArgs a) {
       if (a.node_mask) a.node_mask[od * W + w] = (ONE && w == 0) ? nw : 0ull;
     }
   }
-  frr_cover<5>(fl, s_cov, a.coverage + (size_t)pi * 5);
+  frr_cover<NC>(fl, s_cov, a.coverage + (size_t)pi * NC);
 }
+
+template <bool ONE>
+__global__ __launch_bounds__(256) void k_lfa(LfaArgs a) { lfa_body<ONE, false>(a, LanArgs{}); }
+template <bool ONE>
+__global__ __launch_bounds__(256) void k_lfa_lan(LfaArgs a, LanArgs la) { lfa_body<ONE, true>(a, la); }
 
 }  // namespace

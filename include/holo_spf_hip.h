@@ -683,8 +683,9 @@ int hspf_ancestors_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *ro
  * an alternate | with a node-protecting alternate | with a downstream alternate (the five alt_flags bits, in that order).
  *
  * LAN pseudonodes are handled through root_link ALONE: a candidate reached over the same first link of S as a primary is never
- * offered.  Loop-freeness with respect to the pseudonode itself (RFC 5286 section 3.3) is OUT OF SCOPE: a candidate on another
- * link whose own shortest path to D crosses the primary's LAN is still offered as link-protecting. */
+ * offered.  Loop-freeness with respect to the pseudonode itself (RFC 5286 section 3.3) is not checked by THIS call: a candidate on
+ * another link whose own shortest path to D crosses the primary's LAN is still offered as link-protecting.  hspf_lfa_lan_device
+ * ("broadcast-link protection", below) adds that check. */
 #define HSPF_LFA_C_NO_TRANSIT    0x01u   /* hspf_lfa_protect.cflags */
 #define HSPF_LFA_IGNORE_OVERLOAD 0x01u   /* hspf_lfa_device lfa_flags */
 #define HSPF_LFA_HAS_PRIMARY     0x01u   /* alt_flags */
@@ -726,6 +727,62 @@ typedef struct {                 /* DEVICE pointers                             
 int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev);
+
+/* ---- broadcast-link protection (RFC 5286 section 3.3) for the alternates and the per-prefix backups: new symbols, same ABI number --
+ * When S reaches D across a LAN, what S detects is the loss of its attachment to that LAN, and an alternate must not cross the LAN
+ * either: it must be loop-free with respect to the pseudonode.  root_link alone refuses only candidates behind the same first link
+ * of S; a neighbour on another link whose own shortest path to D crosses the LAN passes hspf_lfa_device.  The two calls below are
+ * hspf_lfa_device and hspf_routes_backup_device with that one more condition.  It needs d(N, L), an entry of a row the caller
+ * already has, and d(L, D): one more row of the same batch, rooted at the LAN's network vertex L — the run is
+ * [S] ++ (S's neighbour routers) ++ (S's LANs), same run_flags.
+ *
+ * hspf_lfa_lan_candidates (host arithmetic, no context; slot numbering, row checks and return convention of hspf_lfa_candidates):
+ *   lan[k]  the vertex that link root_link[k] of S's OWN row leads to, when that vertex carries HSPF_VF_NETWORK and the link passes
+ *           the two-way check; HSPF_NO_ROOT otherwise (a point-to-point link).  Filled for EVERY slot, like cost / root_link: a
+ *           slot's LAN is a function of its root_link alone, so all slots behind one link of S agree.
+ * hspf_lfa_lan is parallel to hspf_lfa_protect: entry i belongs to prot[i], with the same n_slots.
+ *
+ * hspf_lfa_lan_device.  Everything of hspf_lfa_device, with one more condition on membership of `cand` (and through it on `node`,
+ * the choice, alt_* and both masks): for every primary slot p in P with L = lan[p] != HSPF_NO_ROOT
+ *     d(N, D) < d(N, L) + d(L, D)
+ * d(N, L) is read from N's row at vertex L, d(L, D) from row lan_row[p]; the sum is evaluated in 64 bits and an HSPF_DIST_INF term
+ * makes the inequality false.  D == L makes it false by itself: nothing protects the LAN's own vertex against the LAN's failure.
+ * alt_flags gains
+ *   HSPF_LFA_LAN_PRIMARY   some primary of D crosses a LAN of S
+ *   HSPF_LFA_LAN_REFUSED   at least one slot met every condition of hspf_lfa_device's cand and failed only the LAN inequality
+ * and coverage is [n_prot][HSPF_LFA_LAN_COVERAGE_WORDS]: the five words of hspf_lfa_device, then the destinations with each of the
+ * two new bits.  With every lan[k] == HSPF_NO_ROOT the outputs are those of hspf_lfa_device (and coverage words 5, 6 are 0).
+ * Argument errors — everything hspf_lfa_device rejects, lan == NULL, a NULL lan / lan_row array with n_slots > 0, lan[k] >=
+ * n_vertices where it is not HSPF_NO_ROOT, lan_row[k] >= n_rows for such a k — return HSPF_E_INVAL with a text that names
+ * hspf_lfa_lan_device, before anything is launched.
+ *
+ * hspf_routes_backup_lan_device.  Everything of hspf_routes_backup_device ("per-prefix backup routes on device", below), with
+ * cand(p) additionally requiring, for every e in P with L = lan[e] != HSPF_NO_ROOT
+ *     d_N(p) < d(N, L) + d_L(p)
+ * where d_L(p) is d_X(p) of that section evaluated on row lan_row[e] (no advertiser reached from L: false; HSPF_PFX_SATURATING as
+ * there).  The fallback to the per-link repair (HSPF_BK_NODE / _PAIR) is taken only when lan[e] == HSPF_NO_ROOT: the repairs of
+ * hspf_tilfa_device are not known to avoid the LAN, so a LAN primary without an alternate is HSPF_BK_NONE.  bk_flags gains the two
+ * bits above with the same values (for HSPF_BK_ECMP .. HSPF_BK_NONE); bk_coverage is [n_prot][HSPF_BK_LAN_COVERAGE_WORDS]: the
+ * seven kinds, then the prefixes with each of the two bits.  Argument errors name hspf_routes_backup_lan_device.
+ *
+ * OUT OF SCOPE: LAN-aware P / extended-P / Q spaces, and thereby LAN-safe hspf_rlfa_device, hspf_tilfa_device and
+ * hspf_rlfa_node_device repairs (the follow-up: the lan / lan_row columns staged here are what it will read); alternates over the
+ * protected LAN itself to another attached router (node-protecting but not link-protecting in RFC 5286 Figure 5: root_link keeps
+ * refusing them); a pseudonode deeper on the path than S's own attachment; SRLGs. */
+#define HSPF_LFA_LAN_PRIMARY         0x20u   /* alt_flags / bk_flags of the LAN calls */
+#define HSPF_LFA_LAN_REFUSED         0x40u
+#define HSPF_LFA_LAN_COVERAGE_WORDS  7u
+#define HSPF_BK_LAN_COVERAGE_WORDS   9u
+int hspf_lfa_lan_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *lan, uint32_t *out_total_slots);
+typedef struct {                 /* parallel to hspf_lfa_protect: entry i belongs to prot[i]                   */
+  const uint32_t *lan;           /* HOST [n_slots]  hspf_lfa_lan_candidates                                    */
+  const uint32_t *lan_row;       /* HOST [n_slots]  row of the table set holding the SPT ROOTED AT lan[k]; read only where
+                                    lan[k] != HSPF_NO_ROOT                                                     */
+} hspf_lfa_lan;
+int hspf_lfa_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                        const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                        const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
+                        hspf_lfa_out *out_dev);
 
 /* ---- remote loop-free alternates on device (RFC 7490): PQ nodes per protected link: new symbols, same ABI number --------
  * hspf_lfa_device counts the destinations that get no alternate and leaves them unrepaired; on rings and sparse meshes that is
@@ -936,8 +993,8 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
  *
  * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (the other primaries
  * are the backups; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
- * td_kind); node-protecting remote repairs per prefix (per destination vertex: hspf_rlfa_node_device, below); loop-freeness with respect to a LAN pseudonode (the same limitation as
- * hspf_lfa_device).  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
+ * td_kind); node-protecting remote repairs per prefix (per destination vertex: hspf_rlfa_node_device, below).  Loop-freeness with respect to a LAN pseudonode is not checked by THIS
+ * call: hspf_routes_backup_lan_device ("broadcast-link protection", above) adds it.  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
 #define HSPF_BK_NO_ROUTE       0u
 #define HSPF_BK_LOCAL          1u
 #define HSPF_BK_ECMP           2u
@@ -960,6 +1017,12 @@ int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_row
                               const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                               const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *table,
                               const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev);
+/* The same with loop-freeness towards the pseudonodes of the primaries' LANs ("broadcast-link protection", above). */
+int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                  const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                  const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
+                                  const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                  hspf_backup_out *out_dev);
 
 /* ---- node-protecting remote loop-free alternates on device (RFC 8102): new symbols, same ABI number -------------------------
  * hspf_rlfa_device protects LINKS: the tunnel to its PQ node, and that node's own path on to the destination, may run straight

@@ -332,6 +332,26 @@ class Engine {
                                    lfa_flags, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_device (") + hspf_last_error(ctx_) + ")");
   }
+  // Broadcast-link protection (RFC 5286 section 3.3).  lfa_lan_candidates: per slot the LAN behind its first link (host arithmetic);
+  // lfa_lan_device: lfa_device with loop-freeness towards those pseudonodes; `lans[i]` belongs to `protect[i]`, coverage has
+  // HSPF_LFA_LAN_COVERAGE_WORDS words per root.  (No start-to-finish chain here yet: Python's SpfContext.lfa(lan_protect=True) has one.)
+  static std::vector<uint32_t> lfa_lan_candidates(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                                                  const std::vector<uint8_t> &vflags, uint32_t root) {
+    hspf_csr csr{(uint32_t)vflags.size(), (uint32_t)col.size(), row_ptr.data(), col.data(), metric.data(), vflags.data(), 0xFFFFFFFFu};
+    const int k = hspf_lfa_lan_candidates(&csr, root, 0, nullptr, nullptr);
+    if (k < 0) throw Error(k, "hspf_lfa_lan_candidates");
+    std::vector<uint32_t> lan((size_t)k);
+    hspf_lfa_lan_candidates(&csr, root, (uint32_t)k, lan.data(), nullptr);
+    return lan;
+  }
+  void lfa_lan_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                      const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_lfa_lan> &lans, uint32_t lfa_flags,
+                      hspf_lfa_out out_dev) {
+    if (lans.size() != protect.size()) throw Error(HSPF_E_INVAL, "lfa_lan_device: one hspf_lfa_lan per protected root");
+    const int rc = hspf_lfa_lan_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), lans.data(),
+                                       (uint32_t)protect.size(), lfa_flags, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_lan_device (") + hspf_last_error(ctx_) + ")");
+  }
   // One root start to finish: candidates, ONE run for [root] ++ its distinct neighbour routers with the tables left in HBM,
   // the alternates evaluated there, the five arrays and the coverage on the host.  The four vectors must be the CSR `g` was
   // uploaded from (and patched to): the candidate table comes from them, the SPTs from `g`.  Only the vertex count can be
@@ -442,6 +462,17 @@ class Engine {
     const int rc = hspf_routes_backup_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
                                              lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // hspf_routes_backup_lan_device: the same with loop-freeness towards the pseudonodes of the primaries' LANs (`lans` as for
+  // lfa_lan_device; bk_coverage has HSPF_BK_LAN_COVERAGE_WORDS words per root).
+  void routes_backup_lan_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                                const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_lfa_lan> &lans,
+                                uint32_t lfa_flags, const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                hspf_backup_out out_dev) {
+    if (lans.size() != protect.size()) throw Error(HSPF_E_INVAL, "routes_backup_lan_device: one hspf_lfa_lan per protected root");
+    const int rc = hspf_routes_backup_lan_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), lans.data(),
+                                                 (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_lan_device (") + hspf_last_error(ctx_) + ")");
   }
   // One root start to finish: the chain of tilfa() (of lfa() alone without `remote`), hspf_routes_device for the root's row and
   // hspf_routes_backup_device, everything kept on the device in between.  table_flags: HSPF_PFX_SATURATING / HSPF_PFX_LAST_MIN.

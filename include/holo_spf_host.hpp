@@ -106,13 +106,19 @@ struct LfaProtect {
   std::vector<uint32_t> nbr, nbr_row, cost, root_link;      // one entry per first-hop slot (hspf_lfa_candidates)
   std::vector<uint8_t> cflags;
 };
+// Broadcast-link protection (hspf_lfa_lan_device / hspf_routes_backup_lan_device): parallel to LfaProtect, one entry per slot —
+// the LAN behind the slot's first link (hspf_lfa_lan_candidates, HSPF_NO_ROOT: point-to-point) and the row of the SPT rooted at it.
+// The outputs are LfaOut / BackupOut with HSPF_LFA_LAN_COVERAGE_WORDS / HSPF_BK_LAN_COVERAGE_WORDS coverage words per root.
+struct LfaLan {
+  std::vector<uint32_t> lan, lan_row;
+};
 struct LfaOut {
   bool supported = false;
   uint32_t n_protected = 0, n_vertices = 0, mask_words = 1;
   std::vector<uint32_t> alt_slot, alt_metric;               // [n_protected][n_vertices]
   std::vector<uint8_t> alt_flags;
   std::vector<uint64_t> cand_mask, node_mask;               // [n_protected][n_vertices][mask_words] (empty without with_masks)
-  std::vector<uint32_t> coverage;                           // [n_protected][HSPF_LFA_COVERAGE_WORDS]
+  std::vector<uint32_t> coverage;                           // [n_protected][HSPF_LFA_COVERAGE_WORDS] (lfa_lan: HSPF_LFA_LAN_COVERAGE_WORDS)
 };
 // Remote loop-free alternates (hspf_rlfa_device) of the same protected roots: PQ nodes per (protected root, slot) and the remote
 // alternate per destination, from the forward DeviceRun and the DeviceRun of the SAME roots on the transposed graph
@@ -177,6 +183,13 @@ class Engine {
   // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph.  The default: not supported.
   virtual TilfaOut tilfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                          const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/) { return TilfaOut{}; }
+  // lfa() / backup_routes() with loop-freeness towards the pseudonodes of the primaries' LANs; lans[i] belongs to protect[i], the
+  // run holds the SPTs rooted at the LANs too.  The defaults: not supported.
+  virtual LfaOut lfa_lan(DeviceRun &, const std::vector<LfaProtect> &, const std::vector<LfaLan> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) {
+    return LfaOut{};
+  }
+  virtual BackupOut backup_routes_lan(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<LfaProtect> &, const std::vector<LfaLan> &,
+                                      uint32_t /*lfa_flags*/, const TilfaOut * /*tilfa*/) { return BackupOut{}; }
   // The default: not supported (LfaOut::supported == false).
   virtual LfaOut lfa(DeviceRun &, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) { return LfaOut{}; }
   // `reverse_run`: the run of the same roots on the upload of the transposed CSR (the forward run itself on a graph whose
@@ -713,7 +726,19 @@ class HipEngine : public Engine {
     return out;
   }
   LfaOut lfa(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, bool with_masks) override {
+    return lfa_with(run, protect, nullptr, lfa_flags, with_masks);
+  }
+  // (backup_routes / backup_routes_lan stay the base's "not supported": a DeviceRoutes does not keep its prefix table, which
+  // hspf_routes_backup_device needs; hspf::Engine::routes_backup_device / routes_backup_lan_device take it explicitly.)
+  LfaOut lfa_lan(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans, uint32_t lfa_flags, bool with_masks) override {
+    if (lans.size() != protect.size()) throw std::runtime_error("lfa_lan: one LfaLan per protected root");
+    return lfa_with(run, protect, &lans, lfa_flags, with_masks);
+  }
+  // the frame of lfa() (lans == nullptr: hspf_lfa_device) and lfa_lan() (hspf_lfa_lan_device)
+  LfaOut lfa_with(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans, uint32_t lfa_flags, bool with_masks) {
     auto &r = static_cast<HipDeviceRun &>(run);
+    const uint32_t cw = lans ? HSPF_LFA_LAN_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
+    const char *fn = lans ? "hspf_lfa_lan_device: " : "hspf_lfa_device: ";
     LfaOut o;
     o.supported = true;
     o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.mask_words = r.mask_words;
@@ -724,13 +749,20 @@ class HipEngine : public Engine {
         throw std::runtime_error("lfa: the slot arrays of a protected root differ in length");
       ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
     }
-    const size_t pn = (size_t)o.n_protected * o.n_vertices, mb = with_masks ? pn * 8 * o.mask_words : 0, cb = (size_t)o.n_protected * HSPF_LFA_COVERAGE_WORDS * 4;
+    std::vector<hspf_lfa_lan> ls;
+    for (size_t i = 0; lans && i < lans->size(); ++i) {
+      const LfaLan &l = (*lans)[i];
+      if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error("lfa_lan: lan / lan_row differ in length from the slot arrays");
+      ls.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
+    }
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, mb = with_masks ? pn * 8 * o.mask_words : 0, cb = (size_t)o.n_protected * cw * 4;
     uint32_t *slot = (uint32_t *)pool_->dev(pn * 4), *met = (uint32_t *)pool_->dev(pn * 4), *cov = (uint32_t *)pool_->dev(cb);
     uint8_t *fl = (uint8_t *)pool_->dev(pn);
     uint64_t *cm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr, *nm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr;
     hspf_lfa_out out{slot, met, fl, cm, nm, cov};
-    const int rc = hspf_lfa_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, &out);
-    o.alt_slot.resize(pn); o.alt_metric.resize(pn); o.alt_flags.resize(pn); o.coverage.resize((size_t)o.n_protected * HSPF_LFA_COVERAGE_WORDS);
+    const int rc = lans ? hspf_lfa_lan_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), ls.data(), o.n_protected, lfa_flags, &out)
+                        : hspf_lfa_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, &out);
+    o.alt_slot.resize(pn); o.alt_metric.resize(pn); o.alt_flags.resize(pn); o.coverage.resize((size_t)o.n_protected * cw);
     if (with_masks) { o.cand_mask.resize(pn * o.mask_words); o.node_mask.resize(pn * o.mask_words); }
     const bool ok = rc == HSPF_OK && hipMemcpy(o.alt_slot.data(), slot, pn * 4, hipMemcpyDeviceToHost) == hipSuccess &&
                     hipMemcpy(o.alt_metric.data(), met, pn * 4, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -740,7 +772,7 @@ class HipEngine : public Engine {
                                      hipMemcpy(o.node_mask.data(), nm, mb, hipMemcpyDeviceToHost) == hipSuccess));
     pool_->dev_free(slot, pn * 4); pool_->dev_free(met, pn * 4); pool_->dev_free(cov, cb); pool_->dev_free(fl, pn);
     if (with_masks) { pool_->dev_free(cm, mb); pool_->dev_free(nm, mb); }
-    if (!ok) throw std::runtime_error(std::string("hspf_lfa_device: ") + hspf_last_error(ctx_));
+    if (!ok) throw std::runtime_error(std::string(fn) + hspf_last_error(ctx_));
     return o;
   }
   RlfaOut rlfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,

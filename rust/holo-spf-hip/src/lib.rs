@@ -615,12 +615,61 @@ impl Engine {
         Ok(out)
     }
 
+    /// `hspf_lfa_lan_candidates`: per first-hop slot of `root` the network vertex its `root_link` leads to over a two-way link,
+    /// `HSPF_NO_ROOT` for a point-to-point link — pure host arithmetic on the CSR (no device).
+    pub fn lfa_lan_candidates(csr: &Csr, root: u32) -> Result<Vec<u32>, Error> {
+        let c = sys::hspf_csr {
+            n_vertices: csr.n_vertices(),
+            n_edges: csr.col.len() as u32,
+            row_ptr: csr.row_ptr.as_ptr(),
+            col: csr.col.as_ptr(),
+            metric: csr.metric.as_ptr(),
+            vflags: csr.vflags.as_ptr(),
+            max_path_metric: csr.max_path_metric,
+        };
+        let mut total = 0u32;
+        let k = unsafe { sys::hspf_lfa_lan_candidates(&c, root, 0, ptr::null_mut(), &mut total) };
+        if k < 0 {
+            return Err(Error { code: k, detail: "hspf_lfa_lan_candidates".into() });
+        }
+        let mut lan = vec![0u32; k as usize];
+        let rc = unsafe { sys::hspf_lfa_lan_candidates(&c, root, k as u32, lan.as_mut_ptr(), &mut total) };
+        if rc < 0 {
+            return Err(Error { code: rc, detail: "hspf_lfa_lan_candidates".into() });
+        }
+        Ok(lan)
+    }
+
+    /// The `hspf_lfa_lan` array of a LAN call: `lans[i]` = (`lan`, `lan_row`) of `protect[i]`, one entry per slot each.
+    fn lan_raw(who: &str, protect: &[(u32, &LfaCandidates, &[u32])], lans: &[(&[u32], &[u32])]) -> Result<Vec<sys::hspf_lfa_lan>, Error> {
+        if lans.len() != protect.len() || protect.iter().zip(lans).any(|((_, c, _), (l, r))| l.len() != c.nbr.len() || r.len() != c.nbr.len()) {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: format!("{who}: lan / lan_row do not match the slot arrays of the protected roots") });
+        }
+        Ok(lans.iter().map(|(l, r)| sys::hspf_lfa_lan { lan: l.as_ptr(), lan_row: r.as_ptr() }).collect())
+    }
+
+    /// `hspf_lfa_lan_device`: `lfa_device` with loop-freeness towards the pseudonode of every primary's LAN (RFC 5286 section
+    /// 3.3).  `lans[i]` = (`lfa_lan_candidates` of the root, per slot the row of the SPT rooted at that LAN).  `coverage` has
+    /// `HSPF_LFA_LAN_COVERAGE_WORDS` words per root; `alt_flags` may carry `HSPF_LFA_LAN_PRIMARY` / `HSPF_LFA_LAN_REFUSED`.
+    pub fn lfa_lan_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: &[(&[u32], &[u32])],
+                          ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
+        self.lfa_device_with(tables, protect, Some(lans), ignore_overload, with_masks)
+    }
+
     /// `hspf_lfa_device`: loop-free alternates (RFC 5286) of every protected root from the rows of `tables` (a previous
     /// `run_device` whose roots hold each protected root and its neighbour routers).  `protect[i]` = (row of the root's SPT,
     /// its candidate table, `nbr_row[k]` = row of the SPT rooted at `nbr[k]`).  The results come back on the host; the SPT
     /// tables never leave the device.
     pub fn lfa_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
+        self.lfa_device_with(tables, protect, None, ignore_overload, with_masks)
+    }
+
+    /// The frame of `lfa_device` (`lans` None) and `lfa_lan_device`.
+    fn lfa_device_with(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: Option<&[(&[u32], &[u32])]>,
+                       ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
         let (n, w, np) = (tables.n_vertices as usize, tables.words as usize, protect.len());
+        let lan_raw = match lans { Some(l) => Some(Self::lan_raw("lfa_lan_device", protect, l)?), None => None };
+        let cov_words = if lans.is_some() { sys::HSPF_LFA_LAN_COVERAGE_WORDS } else { sys::HSPF_LFA_COVERAGE_WORDS } as usize;
         let mut raw = Vec::with_capacity(np);
         for (root_row, c, nbr_row) in protect {
             let k = c.nbr.len();
@@ -642,7 +691,7 @@ impl Engine {
         let slot = self.device_alloc(cells * 4)?;
         let metric = self.device_alloc(cells * 4)?;
         let flags = self.device_alloc(cells)?;
-        let cov = self.device_alloc(np * sys::HSPF_LFA_COVERAGE_WORDS as usize * 4)?;
+        let cov = self.device_alloc(np * cov_words * 4)?;
         let masks = if with_masks { Some((self.device_alloc(cells * w * 8)?, self.device_alloc(cells * w * 8)?)) } else { None };
         let mut out = sys::hspf_lfa_out {
             alt_slot: slot.p as *mut u32,
@@ -652,20 +701,15 @@ impl Engine {
             node_mask: masks.as_ref().map_or(ptr::null_mut(), |m| m.1.p as *mut u64),
             coverage: cov.p as *mut u32,
         };
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
         let rc = unsafe {
-            sys::hspf_lfa_device(
-                self.ctx,
-                tables.n_vertices,
-                tables.n_roots,
-                tables.words,
-                tables.dist.p as *const u32,
-                tables.flags.p as *const u16,
-                tables.mask.p as *const u64,
-                raw.as_ptr(),
-                np as u32,
-                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
-                &mut out,
-            )
+            match &lan_raw {
+                None => sys::hspf_lfa_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &mut out),
+                Some(l) => {
+                    sys::hspf_lfa_lan_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), l.as_ptr(), np as u32, lfa_flags, &mut out)
+                }
+            }
         };
         if rc != sys::HSPF_OK {
             return Err(self.err(rc));
@@ -679,7 +723,7 @@ impl Engine {
             alt_flags: flags.to_host(cells)?,
             cand_mask: match &masks { Some(m) => m.0.to_host(cells * w)?, None => Vec::new() },
             node_mask: match &masks { Some(m) => m.1.to_host(cells * w)?, None => Vec::new() },
-            coverage: cov.to_host(np * sys::HSPF_LFA_COVERAGE_WORDS as usize)?,
+            coverage: cov.to_host(np * cov_words)?,
         })
     }
 
@@ -1037,7 +1081,27 @@ impl Engine {
     /// context still holds `table` from the `routes_device` call.
     pub fn routes_backup_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool,
                                 table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
+        self.routes_backup_device_with(tables, protect, None, ignore_overload, table, resident, routes, tilfa)
+    }
+
+    /// `hspf_routes_backup_lan_device`: `routes_backup_device` with loop-freeness towards the pseudonode of every primary's LAN;
+    /// a LAN primary never takes the per-link repair.  `lans` as for `lfa_lan_device`; `bk_coverage` has
+    /// `HSPF_BK_LAN_COVERAGE_WORDS` words per root.
+    #[allow(clippy::too_many_arguments)]
+    pub fn routes_backup_lan_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: &[(&[u32], &[u32])],
+                                    ignore_overload: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
+                                    tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
+        self.routes_backup_device_with(tables, protect, Some(lans), ignore_overload, table, resident, routes, tilfa)
+    }
+
+    /// The frame of `routes_backup_device` (`lans` None) and `routes_backup_lan_device`.
+    #[allow(clippy::too_many_arguments)]
+    fn routes_backup_device_with(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: Option<&[(&[u32], &[u32])]>,
+                                 ignore_overload: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
+                                 tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
         let (np, pf, w) = (protect.len(), table.n_prefixes() as usize, tables.words as usize);
+        let lan_raw = match lans { Some(l) => Some(Self::lan_raw("routes_backup_lan_device", protect, l)?), None => None };
+        let cov_words = if lans.is_some() { sys::HSPF_BK_LAN_COVERAGE_WORDS } else { sys::HSPF_BK_COVERAGE_WORDS } as usize;
         if routes.n_prefixes != table.n_prefixes() || routes.words != tables.words {
             return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_device: the routes are not of this table set and table".into() });
         }
@@ -1085,7 +1149,7 @@ impl Engine {
         let bk_flags = self.device_alloc(cells)?;
         let bk_cand = self.device_alloc(cells * 8 * w)?;
         let bk_node = self.device_alloc(cells * 8 * w)?;
-        let bk_cov = self.device_alloc(np * sys::HSPF_BK_COVERAGE_WORDS as usize * 4)?;
+        let bk_cov = self.device_alloc(np * cov_words * 4)?;
         let mut out = sys::hspf_backup_out {
             bk_kind: bk_kind.p as *mut u8,
             bk_primary: bk_primary.p as *mut u32,
@@ -1113,23 +1177,16 @@ impl Engine {
             best_entry: routes.best_entry.p as *mut u32,
             nexthop_mask: routes.nexthop_mask.p as *mut u64,
         };
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
+        let ti_ptr = ti_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_out);
         let rc = unsafe {
-            sys::hspf_routes_backup_device(
-                self.ctx,
-                tables.n_vertices,
-                tables.n_roots,
-                tables.words,
-                tables.dist.p as *const u32,
-                tables.flags.p as *const u16,
-                tables.mask.p as *const u64,
-                raw.as_ptr(),
-                np as u32,
-                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
-                &t,
-                &r,
-                ti_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_out),
-                &mut out,
-            )
+            match &lan_raw {
+                None => sys::hspf_routes_backup_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, &mut out),
+                Some(l) => sys::hspf_routes_backup_lan_device(
+                    self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), l.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, &mut out,
+                ),
+            }
         };
         if rc != sys::HSPF_OK {
             return Err(self.err(rc));
@@ -1145,7 +1202,7 @@ impl Engine {
             bk_flags: bk_flags.to_host(cells)?,
             bk_cand_mask: bk_cand.to_host(cells * w)?,
             bk_node_mask: bk_node.to_host(cells * w)?,
-            bk_coverage: bk_cov.to_host(np * sys::HSPF_BK_COVERAGE_WORDS as usize)?,
+            bk_coverage: bk_cov.to_host(np * cov_words)?,
         })
     }
 
