@@ -204,6 +204,10 @@ SYMBOLS = [
     ("hspf_rlfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(HspfRlfaOut)]),
+    ("hspf_rlfa_lan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect),
+                                            ctypes.POINTER(HspfLfaLan), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.POINTER(HspfRlfaOut)]),
     # two-segment repair paths (TI-LFA, link protection)
     ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,

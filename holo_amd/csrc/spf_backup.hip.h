@@ -14,7 +14,8 @@
 //                  protected root), then one vector atomic add per wave and kind.
 // The LAN variants (hspf_routes_backup_lan_device) are k_backup_lan, a further instantiation of the same body, and
 // k_backup_cov_lan: d_L(p) of the one primary's LAN is computed once next to d_E(p); a candidate that has passed every plain
-// condition is then held against d(N, L) + d_L(p); the per-link repair is taken only for a point-to-point primary.
+// condition is then held against d(N, L) + d_L(p); the per-link repair is taken for a point-to-point primary, and for a LAN
+// primary only under HSPF_LFA_LAN_SAFE_REPAIRS (the caller's word that the repairs come from hspf_rlfa_lan_device's tables).
 // There is no wave-per-prefix path: a prefix with very many advertisers is walked by ONE lane and holds its wave back.
 #pragma once
 
@@ -31,7 +32,7 @@ constexpr uint32_t BK_KINDS = 7;                   // HSPF_BK_*
 
 struct BackupArgs {
   uint32_t n, W, ignore_overload, stride;                                  // stride = 64 * W slots per protected root
-  uint32_t n_pfx, sat, pad0, pad1;
+  uint32_t n_pfx, sat, lan_repairs, pad1;                                   // lan_repairs: HSPF_LFA_LAN_SAFE_REPAIRS (k_backup_lan)
   const uint32_t *dist; const uint16_t *flags;                             // the table set
   const uint32_t *tab, *scal;                                              // as LfaArgs (staged by the call, gathered by k_lfa_gather)
   const uint32_t *pfx_ptr, *pfx_vertex, *pfx_metric;                       // the staged prefix table
@@ -199,7 +200,7 @@ __device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &
       kind = 3u; slot = aslot;
       met = bsum > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)bsum;
       fl = (bnode ? 0x08u : 0u) | (bdown ? 0x10u : 0u);
-    } else if (a.ti_kind && !(LAN && lanp)) {                                               // (the per-link repairs are not known to avoid a LAN)
+    } else if (a.ti_kind && !(LAN && lanp && !a.lan_repairs)) {                             // (a LAN primary: only repairs the caller vouches for)
       const size_t o = (size_t)pi * a.stride + p0;
       const uint32_t tk = a.ti_kind[o];
       if (tk) { kind = tk == 1u ? 4u : 5u; slot = a.ti_via[o]; met = a.ti_metric[o]; }

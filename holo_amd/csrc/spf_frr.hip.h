@@ -1,5 +1,5 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
-// hspf_csr_transpose, hspf_rlfa_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
+// hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
 // hspf_rlfa_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
 // Included by spf_capi.hip (one TU).
 //
@@ -260,6 +260,7 @@ int routes_backup(hspf_ctx *ctx, const char *fn, bool with_lan, uint32_t n_verti
     BackupArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
     a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
+    a.lan_repairs = (with_lan && (lfa_flags & HSPF_LFA_LAN_SAFE_REPAIRS)) ? 1u : 0u;
     a.dist = dist_dev; a.flags = flags_dev;
     a.tab = ga.tab; a.scal = ga.scal;
     a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
@@ -276,6 +277,64 @@ int routes_backup(hspf_ctx *ctx, const char *fn, bool with_lan, uint32_t n_verti
       hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
     }
     return frr_finish(ctx, with_lan ? "k_backup_lan" : "k_backup");
+  });
+}
+
+static_assert(RLFA_CW == HSPF_RLFA_COUNT_WORDS && RLFA_LAN_CW == HSPF_RLFA_LAN_COUNT_WORDS, "the kernels' count widths are the header's");
+
+// the one frame of hspf_rlfa_device (with_lan false, `lan` unread) and hspf_rlfa_lan_device
+int rlfa_call(hspf_ctx *ctx, const char *fn, bool with_lan, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+              const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+              const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+              hspf_rlfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
+      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
+    std::vector<uint32_t> tab, ltab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0;
+    size_t max_gather = 0;
+    LanArgs la{};
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if ((with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, ltab, &la, &max_gather))) || (rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      return rc;
+    }
+    const uint32_t count_words = with_lan ? HSPF_RLFA_LAN_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS;
+    const uint32_t coverage_words = with_lan ? HSPF_RLFA_LAN_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
+    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * count_words * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * coverage_words * 4, s));
+    const LfaArgs ga = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
+                                : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    RlfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)stride;
+    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
+    a.tab = ga.tab; a.scal = ga.scal;
+    a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
+    a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
+    a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
+    a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), fgrid((uint32_t)((n_slots + 255) / 256));
+    if (with_lan) {
+      hipLaunchKernelGGL(k_rlfa_lan, grid, dim3(256), 0, s, a, RlfaLan<true>{la});
+      hipLaunchKernelGGL(k_rlfa_final_lan, fgrid, dim3(256), 0, s, a, n_prot, RlfaLan<true>{la});
+      hipLaunchKernelGGL(k_rlfa_dest_lan, grid, dim3(256), 0, s, a, RlfaLan<true>{la});
+    } else {
+      hipLaunchKernelGGL(k_rlfa, grid, dim3(256), 0, s, a, RlfaLan<false>{});
+      hipLaunchKernelGGL(k_rlfa_final, fgrid, dim3(256), 0, s, a, n_prot, RlfaLan<false>{});
+      hipLaunchKernelGGL(k_rlfa_dest, grid, dim3(256), 0, s, a, RlfaLan<false>{});
+    }
+    return frr_finish(ctx, with_lan ? "k_rlfa_lan" : "k_rlfa");
   });
 }
 
@@ -394,41 +453,16 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                      hspf_rlfa_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_rlfa_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
-    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
-      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
-    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
-    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    if ((rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * HSPF_RLFA_COUNT_WORDS * 4, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * HSPF_RLFA_COVERAGE_WORDS * 4, s));
-    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    RlfaArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)stride;
-    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
-    a.tab = ga.tab; a.scal = ga.scal;
-    a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
-    a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
-    a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
-    a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
-    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
-    hipLaunchKernelGGL(k_rlfa, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_rlfa_final, dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
-    hipLaunchKernelGGL(k_rlfa_dest, grid, dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_rlfa");
-  });
+  return rlfa_call(ctx, "hspf_rlfa_device", false, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, nullptr, n_prot,
+                   lfa_flags, alt_flags_in_dev, out_dev);
+}
+
+int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                         const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
+                         const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev) {
+  return rlfa_call(ctx, "hspf_rlfa_lan_device", true, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, lan, n_prot,
+                   lfa_flags, alt_flags_in_dev, out_dev);
 }
 
 // ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----

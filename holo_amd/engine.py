@@ -43,6 +43,9 @@ LFA_NO_SLOT = 0xFFFFFFFF
 LFA_COVERAGE_WORDS = 5
 LFA_LAN_PRIMARY, LFA_LAN_REFUSED = 0x20, 0x40     # HSPF_LFA_LAN_*: alt_flags / bk_flags of the LAN calls
 LFA_LAN_COVERAGE_WORDS = 7
+LFA_LAN_SAFE_REPAIRS = 0x02     # HSPF_LFA_LAN_SAFE_REPAIRS (routes_backup_lan_device flags): tilfa comes from rlfa_lan_device()'s tables
+RLFA_LAN_COUNT_WORDS = 5
+RLFA_LAN_COVERAGE_WORDS = 6
 RLFA_VIA_SELF = 0xFFFFFFFE      # HSPF_RLFA_VIA_SELF: released by the root itself (P-space)
 RLFA_IN_P, RLFA_IN_XP, RLFA_IN_Q, RLFA_ELIGIBLE = 0x01, 0x02, 0x04, 0x08      # space_flags
 RLFA_COUNT_WORDS = 4
@@ -259,12 +262,12 @@ class RlfaResult:
     pq_node: np.ndarray      # [P, S] u32, NO_ROOT: none
     pq_via: np.ndarray       # [P, S] u32, RLFA_VIA_SELF or a slot, LFA_NO_SLOT: none
     pq_metric: np.ndarray    # [P, S] u32
-    pq_counts: np.ndarray    # [P, S, 4] u32
+    pq_counts: np.ndarray    # [P, S, 4] u32; [P, S, 5] from rlfa_lan_device()
     space_flags: Optional[np.ndarray]   # [P, S, N] u8 RLFA_IN_P | RLFA_IN_XP | RLFA_IN_Q | RLFA_ELIGIBLE, or None
     space_via: Optional[np.ndarray]     # [P, S, N] u32 or None
     rl_node: np.ndarray      # [P, N] u32
     rl_via: np.ndarray       # [P, N] u32
-    rl_coverage: np.ndarray  # [P, 4] u32
+    rl_coverage: np.ndarray  # [P, 4] u32; [P, 6] from rlfa_lan_device()
 
 
 @dataclass
@@ -941,6 +944,24 @@ class SpfContext:
         del keep
         self._check_rc("hspf_rlfa_device", rc)
 
+    def rlfa_lan_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
+                        protect, lans, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int,
+                        rl_via_ptr: int, rl_coverage_ptr: int, space_flags_ptr: int = 0, space_via_ptr: int = 0, alt_flags_in_ptr: int = 0,
+                        lfa_flags: int = 0) -> None:
+        """hspf_rlfa_lan_device(): rlfa_device() with P, extended P and Q loop-free towards the pseudonode of every slot's LAN.
+        `lans` as for lfa_lan_device(); both table sets come from the run [root] + neighbour routers + LANs, and `rdist_ptr` is
+        ALWAYS the dist of that list on the transposed graph (a pseudonode's links cost 0 one way: the forward dist is no
+        substitute).  pq_counts_ptr: [P, S, RLFA_LAN_COUNT_WORDS] u32, rl_coverage_ptr: [P, RLFA_LAN_COVERAGE_WORDS] u32."""
+        arr, keep = self._protect_array(protect, "rlfa_lan_device")
+        larr, lkeep = self._lan_array(lans, protect, "rlfa_lan_device")
+        out = L.HspfRlfaOut(pq_node_ptr or None, pq_via_ptr or None, pq_metric_ptr or None, pq_counts_ptr or None, space_flags_ptr or None,
+                            space_via_ptr or None, rl_node_ptr or None, rl_via_ptr or None, rl_coverage_ptr or None)
+        rc = self.lib.hspf_rlfa_lan_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
+                                           mask_ptr or None, rdist_ptr or None, arr, larr, len(protect), lfa_flags, alt_flags_in_ptr or None,
+                                           ctypes.byref(out))
+        del keep, lkeep
+        self._check_rc("hspf_rlfa_lan_device", rc)
+
     def tilfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                      protect, *, space_flags_ptr: int, space_via_ptr: int, ti_kind_ptr: int, ti_p_ptr: int, ti_q_ptr: int, ti_via_ptr: int,
                      ti_link_ptr: int, ti_metric_ptr: int, ti_counts_ptr: int, td_kind_ptr: int, td_coverage_ptr: int,
@@ -1008,50 +1029,63 @@ class SpfContext:
     def routes_backup_lan_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, lans,
                                  pfx_ptr, pfx_vertex, pfx_metric, **kw) -> None:
         """hspf_routes_backup_lan_device(): routes_backup_device() with loop-freeness towards the pseudonode of every primary's LAN;
-        a LAN primary never takes the per-link repair.  `lans` as for lfa_lan_device(); bk_coverage_ptr: [P, BK_LAN_COVERAGE_WORDS]
+        a LAN primary takes the per-link repair only under lfa_flags LFA_LAN_SAFE_REPAIRS (the caller's word that `tilfa` comes from
+        rlfa_lan_device()'s tables).  `lans` as for lfa_lan_device(); bk_coverage_ptr: [P, BK_LAN_COVERAGE_WORDS]
         u32; every other argument as for routes_backup_device()."""
         self._routes_backup(list(lans), n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr, protect, pfx_ptr, pfx_vertex, pfx_metric, **kw)
 
     def backup_routes(self, graph: SpfGraph, root: int, prefix_table, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False,
-                      remote: bool = True, lan_protect: bool = False) -> BackupRoutes:
+                      remote: bool = True, lan_protect: bool = False, lan_repairs: bool = False) -> BackupRoutes:
         """The routes of one root with their backups, start to finish: run_device() of [root] + its distinct neighbour routers,
         routes_device(), lfa_device() and — with `remote` — rlfa_device() + tilfa_device() (on the transposed graph too unless
         `symmetric`), then routes_backup_device(); only the route and bk_* arrays (and the per-slot repairs) come to the host.
         prefix_table: an object with pfx_ptr / pfx_vertex / pfx_metric (holo_amd.routes.PrefixTable) and optionally `flags`
         (PFX_SATURATING, PFX_LAST_MIN), or a tuple (pfx_ptr, pfx_vertex, pfx_metric[, flags]).  lan_protect: the run also holds the
         SPTs of the root's LANs, and lfa_lan_device() / routes_backup_lan_device() take the places of the plain calls (bk_coverage
-        has nine words)."""
+        has nine words).  lan_repairs (needs lan_protect and remote, excludes symmetric): rlfa_lan_device() takes rlfa_device()'s
+        place, so the per-link repairs avoid the primaries' LANs, and a LAN primary without an alternate takes its repair
+        (LFA_LAN_SAFE_REPAIRS) instead of BK_NONE."""
+        if lan_repairs and (not lan_protect or not remote or symmetric):
+            raise ValueError("backup_routes: lan_repairs needs lan_protect=True, remote=True and symmetric=False")
         if isinstance(prefix_table, (tuple, list)):
             tab = tuple(prefix_table) + ((0,) if len(prefix_table) == 3 else ())
         else:
             tab = (prefix_table.pfx_ptr, prefix_table.pfx_vertex, prefix_table.pfx_metric, int(getattr(prefix_table, "flags", 0)))
         tab = tuple(np.ascontiguousarray(a, np.uint32) for a in tab[:3]) + (int(tab[3]) & ~PFX_RESIDENT,)
-        return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab, lan_protect=lan_protect)
+        return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab, lan_protect=lan_protect,
+                          lan_spaces=lan_repairs)
 
-    def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False):
+    def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False,
+             lan_protect: bool = False):
         """Remote alternates of one root, start to finish: the candidate table, run_device() of [root] + its distinct neighbour
         routers on `graph` and — unless `symmetric` says every link has its reverse at the same cost — on its transpose
         (csr_transpose, uploaded for the call), lfa_device() then rlfa_device() on those rows, everything on the host.
-        Returns (LfaCandidates, LfaResult without masks, RlfaResult), one row each."""
-        return self._rlfa(graph, root, run_flags, lfa_flags, want_spaces, symmetric, False)
+        Returns (LfaCandidates, LfaResult without masks, RlfaResult), one row each.  lan_protect (excludes symmetric): both runs
+        also hold the SPTs of the root's LANs, and lfa_lan_device() / rlfa_lan_device() take the places of the plain calls
+        (pq_counts has five words, rl_coverage six; LfaResult.lan is filled)."""
+        return self._rlfa(graph, root, run_flags, lfa_flags, want_spaces, symmetric, False, lan_protect=lan_protect, lan_spaces=lan_protect)
 
-    def tilfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False):
+    def tilfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False, lan_protect: bool = False):
         """Two-segment repairs of one root, start to finish: rlfa(..., want_spaces=True) with everything kept on the device, then
-        tilfa_device() on the same rows and space tables.  Returns (LfaCandidates, LfaResult, RlfaResult, TilfaResult)."""
-        return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True)
+        tilfa_device() on the same rows and space tables.  Returns (LfaCandidates, LfaResult, RlfaResult, TilfaResult).
+        lan_protect: as for rlfa(); tilfa_device() then reads LAN-safe tables and its repairs avoid the primaries' LANs."""
+        return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True, lan_protect=lan_protect, lan_spaces=lan_protect)
 
     def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None,
-              lan_protect: bool = False):
+              lan_protect: bool = False, lan_spaces: bool = False):
         """The chain behind rlfa(), tilfa() and backup_routes().  backup: None, or (pfx_ptr, pfx_vertex, pfx_metric, flags) — then
-        the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`)."""
+        the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`).  lan_spaces
+        (with lan_protect): rlfa_lan_device() instead of rlfa_device(), and LFA_LAN_SAFE_REPAIRS for the backups."""
+        if lan_spaces and (not lan_protect or symmetric):
+            raise ValueError("the LAN-safe remote calls need lan_protect and the transposed run (symmetric=False)")
         plan = self._frr_plan(graph, root, lan_protect)
         cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
         R, n, S = len(roots), graph.n, 64 * W
         shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8),
                       cov=((1, LFA_LAN_COVERAGE_WORDS if lan_protect else LFA_COVERAGE_WORDS), np.uint32),
                       pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
-                      pq_counts=((1, S, RLFA_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32), rl_via=((1, n), np.uint32),
-                      rl_cov=((1, RLFA_COVERAGE_WORDS), np.uint32))
+                      pq_counts=((1, S, RLFA_LAN_COUNT_WORDS if lan_spaces else RLFA_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32),
+                      rl_via=((1, n), np.uint32), rl_cov=((1, RLFA_LAN_COVERAGE_WORDS if lan_spaces else RLFA_COVERAGE_WORDS), np.uint32))
         if want_spaces:
             shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
         ti_names = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
@@ -1085,11 +1119,15 @@ class SpfContext:
                 self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"],
                                 alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
             if backup is None or tilfa:
-                self.rlfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
-                                 pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
-                                 rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
-                                 space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
-                                 lfa_flags=lfa_flags)
+                tabs = (graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect)
+                out = dict(pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
+                           rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
+                           space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
+                           lfa_flags=lfa_flags)
+                if lan_spaces:
+                    self.rlfa_lan_device(*tabs, plan.lans, **out)
+                else:
+                    self.rlfa_device(*tabs, **out)
             else:                                       # backup_routes(remote=False): nothing wrote the remote arrays, nothing reads them
                 for k in ("pq_node", "pq_via", "pq_metric", "pq_counts", "rl_node", "rl_via", "rl_cov"):
                     del host[k]
@@ -1103,12 +1141,13 @@ class SpfContext:
                 self._routes_backup(plan.lans if lan_protect else None, n, R, W, dev["dist"], dev["flags"], dev["mask"], protect,
                                     backup[0], backup[1], backup[2], routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
                                     tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None,
-                                    flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags, **{k + "_ptr": dev[k] for k in bk_names[3:]})
+                                    flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_LAN_SAFE_REPAIRS if lan_spaces else 0),
+                                    **{k + "_ptr": dev[k] for k in bk_names[3:]})
             self._fetch(host, dev)
             if backup is not None:
                 return BackupRoutes(cand, *(host[k] for k in bk_names),
                                     tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None)
-            lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
+            lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"], lan=plan.lan)
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
             return (cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, lfa, rl)

@@ -761,16 +761,19 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
  *     d_N(p) < d(N, L) + d_L(p)
  * where d_L(p) is d_X(p) of that section evaluated on row lan_row[e] (no advertiser reached from L: false; HSPF_PFX_SATURATING as
  * there).  The fallback to the per-link repair (HSPF_BK_NODE / _PAIR) is taken only when lan[e] == HSPF_NO_ROOT: the repairs of
- * hspf_tilfa_device are not known to avoid the LAN, so a LAN primary without an alternate is HSPF_BK_NONE.  bk_flags gains the two
+ * hspf_tilfa_device are not known to avoid the LAN, so a LAN primary without an alternate is HSPF_BK_NONE — unless lfa_flags has
+ * HSPF_LFA_LAN_SAFE_REPAIRS, the caller's word that tilfa_dev was computed from hspf_rlfa_lan_device's tables: then the fallback
+ * is taken for a LAN primary too.  Every other call ignores that bit.  bk_flags gains the two
  * bits above with the same values (for HSPF_BK_ECMP .. HSPF_BK_NONE); bk_coverage is [n_prot][HSPF_BK_LAN_COVERAGE_WORDS]: the
  * seven kinds, then the prefixes with each of the two bits.  Argument errors name hspf_routes_backup_lan_device.
  *
- * OUT OF SCOPE: LAN-aware P / extended-P / Q spaces, and thereby LAN-safe hspf_rlfa_device, hspf_tilfa_device and
- * hspf_rlfa_node_device repairs (the follow-up: the lan / lan_row columns staged here are what it will read); alternates over the
+ * LAN-aware P / extended-P / Q spaces are hspf_rlfa_lan_device ("remote loop-free alternates with LAN-safe spaces", below).
+ * OUT OF SCOPE: LAN-safe hspf_rlfa_node_device repairs; alternates over the
  * protected LAN itself to another attached router (node-protecting but not link-protecting in RFC 5286 Figure 5: root_link keeps
  * refusing them); a pseudonode deeper on the path than S's own attachment; SRLGs. */
 #define HSPF_LFA_LAN_PRIMARY         0x20u   /* alt_flags / bk_flags of the LAN calls */
 #define HSPF_LFA_LAN_REFUSED         0x40u
+#define HSPF_LFA_LAN_SAFE_REPAIRS    0x02u   /* lfa_flags of hspf_routes_backup_lan_device */
 #define HSPF_LFA_LAN_COVERAGE_WORDS  7u
 #define HSPF_BK_LAN_COVERAGE_WORDS   9u
 int hspf_lfa_lan_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, uint32_t *lan, uint32_t *out_total_slots);
@@ -840,7 +843,8 @@ int hspf_lfa_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uin
  *
  * Node-protecting remote LFA (RFC 8102: the PQ node's path to D may cross E) is hspf_rlfa_node_select_device /
  * hspf_rlfa_node_device, below.  OUT OF SCOPE: loop-freeness with respect to a
- * LAN pseudonode (the same root_link rule and the same limitation as hspf_lfa_device); segment lists beyond one tunnel
+ * LAN pseudonode in THIS call (the same root_link rule and the same limitation as hspf_lfa_device: hspf_rlfa_lan_device, below,
+ * adds it); segment lists beyond one tunnel
  * (hspf_tilfa_device, below, adds one forced adjacency). */
 #define HSPF_RLFA_VIA_SELF       0xFFFFFFFEu   /* pq_via / space_via / rl_via: released by S itself (P-space) */
 #define HSPF_RLFA_IN_P           0x01u         /* space_flags */
@@ -866,6 +870,45 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                      hspf_rlfa_out *out_dev);
 
+/* ---- remote loop-free alternates with LAN-safe spaces (RFC 7490 on broadcast links): new symbol, same ABI number --------------
+ * hspf_rlfa_device builds P, extended P and Q against the far router E only.  When the protected slot crosses a LAN of S
+ * (lan[e] of hspf_lfa_lan_candidates is a vertex L), what fails is S's attachment to L, and a tunnel to the PQ node — or the PQ
+ * node's own path on to E — that crosses the pseudonode breaks on exactly the failure it repairs.  hspf_rlfa_lan_device is
+ * hspf_rlfa_device with the hspf_lfa_lan columns of hspf_lfa_lan_device (`lan` parallel to `prot`) and one more condition per set.
+ *
+ * Both table sets come from the root list [S] ++ (S's neighbour routers) ++ (S's LANs) that hspf_lfa_lan_device asks for: `dist`
+ * is the forward run, rdist_dev the `dist` of the SAME list on the transposed graph, so rdist[lan_row[e]][v] = d(v, L).  The
+ * forward-dist-as-rdist shortcut of hspf_rlfa_device is NEVER valid here: a pseudonode's links cost 0 one way, so no graph with a
+ * LAN has symmetric costs.
+ *
+ * For a candidate slot e with L = lan[e] != HSPF_NO_ROOT and lr = lan_row[e] (sums in 64 bits; an HSPF_DIST_INF term makes the
+ * inequality false):
+ *   P_lan(e, v)      P(e, v)      and  d(S, v)   < d(S, L)   + d(L, v)      S's row at v and at L; row lr at v
+ *   XP_lan(e, k, v)  XP(e, k, v)  and  d(N_k, v) < d(N_k, L) + d(L, v)      N_k's row at v and at L; row lr at v
+ *   Q_lan(e, v)      Q(e, v)      and  d(v, E)   < d(v, L)   + d(L, E)      rdist[rowE][v], rdist[lr][v]; dist[lr][E]
+ * Each is the literal conjunction, so every LAN-safe set is a subset of hspf_rlfa_device's.  Eligibility, via-slot admission, the
+ * tie order, the release point and its metric (now over P_lan / XP_lan), the PQ choice, rl_node / rl_via and the four bits of
+ * space_flags are those of hspf_rlfa_device — the bits now mean the LAN-safe sets, so the tables can be fed to hspf_tilfa_device
+ * as they are.  A slot with lan[e] == HSPF_NO_ROOT is computed exactly as by hspf_rlfa_device.
+ * Outputs: hspf_rlfa_out with wider count arrays.
+ *   pq_counts   [n_prot][stride][HSPF_RLFA_LAN_COUNT_WORDS]: the four words of hspf_rlfa_device over the LAN-safe sets, then the
+ *               number of v in the plain (P or some XP) and Q that are not in the LAN-safe one (0 for a point-to-point slot).
+ *   rl_coverage [n_prot][HSPF_RLFA_LAN_COVERAGE_WORDS]: the four words of hspf_rlfa_device, then the one-primary destinations
+ *               whose primary crosses a LAN | of those, the ones left uncovered although the plain rule had a PQ node.
+ * With every lan[k] == HSPF_NO_ROOT all shared outputs equal hspf_rlfa_device's and the new words are 0.  Argument errors —
+ * everything hspf_rlfa_device rejects, everything hspf_lfa_lan_device rejects in `lan` — return HSPF_E_INVAL with a text that names
+ * hspf_rlfa_lan_device, before anything is launched.  From rl_* / ti_* on a LAN primary to a tunnel: INTEGRATION.md 5n.
+ *
+ * OUT OF SCOPE: a forced adjacency across another LAN (p -> network vertex -> q is still not offered by hspf_tilfa_device, so
+ * LAN-heavy graphs keep more HSPF_TILFA_NONE than necessary); hspf_rlfa_node_select_device on these tables (its NP / NXP release
+ * paths are re-derived against E only: not LAN-safe); LAN pseudonodes as the protected node; per-prefix Q-spaces; SRLGs. */
+#define HSPF_RLFA_LAN_COUNT_WORDS    5u
+#define HSPF_RLFA_LAN_COVERAGE_WORDS 6u
+int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                         const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
+                         const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev);
+
 /* ---- two-segment repair paths on device (TI-LFA, link protection): new symbol, same ABI number ----------------------------
  * hspf_rlfa_device leaves rl_coverage[3]: destinations whose one primary link has no LFA and whose extended P-space and
  * Q-space do not intersect.  The segment-routing repair for them is two segments: tunnel to a node p of the extended P-space,
@@ -876,6 +919,10 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
  * hspf_rlfa_device.  space_flags_dev / space_via_dev [n_prot][stride][n_vertices] are REQUIRED: the tables hspf_rlfa_device wrote
  * for the same `prot` and lfa_flags (eligibility and the overload rule are read from them, not evaluated again).  `g` must be
  * the FORWARD graph — its links are scanned — where hspf_rlfa_device takes either.
+ * LAN-safe use: fed with the tables hspf_rlfa_lan_device wrote (same `prot`, same two table sets) and the alt_flags of
+ * hspf_lfa_lan_device, every repair avoids the pseudonode of the slot's LAN by construction — p is in P_lan / XP_lan, q in Q_lan,
+ * and the forced adjacency joins two routers; ti_counts[..][0] then equals pq_counts[..][3] of hspf_rlfa_lan_device.  The kernel
+ * is the same (tests/test_gpu_rlfa_lan.py holds it to that contract).
  *
  * Per protected root S and candidate slot e (E = nbr[e], rowE = nbr_row[e]); every sum is evaluated in 64 bits.
  *   rel(v)        the release metric of v, rebuilt from via = space_via[e][v]: d(S, v) for HSPF_RLFA_VIA_SELF, cost[via] +

@@ -411,6 +411,17 @@ class Engine {
                                     (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_device (") + hspf_last_error(ctx_) + ")");
   }
+  // hspf_rlfa_lan_device: rlfa_device with P, extended P and Q loop-free towards the pseudonode of every slot's LAN.  `lans[i]`
+  // belongs to `protect[i]`; both table sets come from the run [S] ++ neighbour routers ++ LANs, rdist_dev ALWAYS from the transposed
+  // graph; pq_counts has HSPF_RLFA_LAN_COUNT_WORDS words per slot, rl_coverage HSPF_RLFA_LAN_COVERAGE_WORDS per root.
+  void rlfa_lan_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                       const uint64_t *mask_dev, const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect,
+                       const std::vector<hspf_lfa_lan> &lans, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev, hspf_rlfa_out out_dev) {
+    if (lans.size() != protect.size()) throw Error(HSPF_E_INVAL, "rlfa_lan_device: one hspf_lfa_lan per protected root");
+    const int rc = hspf_rlfa_lan_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                                        lans.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_lan_device (") + hspf_last_error(ctx_) + ")");
+  }
   // One root start to finish, as lfa(): ONE run of [root] ++ its neighbour routers on `g` and one on the upload of its transpose
   // (skipped when `symmetric` says every link has its reverse at the same cost), hspf_lfa_device, hspf_rlfa_device, results on
   // the host.  The four vectors must be the CSR `g` was uploaded from, max_path_metric the one it was uploaded with.

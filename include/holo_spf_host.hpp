@@ -127,11 +127,11 @@ struct RlfaOut {
   bool supported = false;
   uint32_t n_protected = 0, n_vertices = 0, slot_stride = 64;
   std::vector<uint32_t> pq_node, pq_via, pq_metric;         // [n_protected][slot_stride]
-  std::vector<uint32_t> pq_counts;                          // [n_protected][slot_stride][HSPF_RLFA_COUNT_WORDS]
+  std::vector<uint32_t> pq_counts;                          // [n_protected][slot_stride][HSPF_RLFA_COUNT_WORDS] (rlfa_lan: HSPF_RLFA_LAN_COUNT_WORDS)
   std::vector<uint8_t> space_flags;                         // [n_protected][slot_stride][n_vertices] (empty without with_spaces)
   std::vector<uint32_t> space_via;
   std::vector<uint32_t> rl_node, rl_via;                    // [n_protected][n_vertices]
-  std::vector<uint32_t> rl_coverage;                        // [n_protected][HSPF_RLFA_COVERAGE_WORDS]
+  std::vector<uint32_t> rl_coverage;                        // [n_protected][HSPF_RLFA_COVERAGE_WORDS] (rlfa_lan: HSPF_RLFA_LAN_COVERAGE_WORDS)
 };
 // Two-segment repair paths (hspf_tilfa_device) of the same protected roots: per (protected root, slot) the cheapest repair that is
 // one PQ node or a node of the extended P-space plus one forced adjacency into the Q-space, and the class of every destination,
@@ -196,6 +196,11 @@ class Engine {
   // costs are symmetric); `lfa`: nullptr, or what lfa() returned for the same protect list.  The default: not supported.
   virtual RlfaOut rlfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                        const LfaOut * /*lfa*/, bool /*with_spaces*/) { return RlfaOut{}; }
+  // rlfa() with P, extended P and Q loop-free towards the pseudonode of every slot's LAN (hspf_rlfa_lan_device); lans[i] belongs to
+  // protect[i]; both runs hold the SPTs rooted at the LANs too and `reverse_run` is ALWAYS the run on the transposed graph; `lfa`:
+  // nullptr, or what lfa_lan() returned.  The result feeds tilfa() unchanged.  The default: not supported.
+  virtual RlfaOut rlfa_lan(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, const std::vector<LfaLan> &,
+                           uint32_t /*lfa_flags*/, const LfaOut * /*lfa*/, bool /*with_spaces*/) { return RlfaOut{}; }
   virtual std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                         const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
                                         uint32_t max_path_metric) = 0;
@@ -777,9 +782,23 @@ class HipEngine : public Engine {
   }
   RlfaOut rlfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
                bool with_spaces) override {
+    return rlfa_with(gr, run, reverse_run, protect, nullptr, lfa_flags, lfa, with_spaces);
+  }
+  RlfaOut rlfa_lan(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans,
+                   uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) override {
+    if (lans.size() != protect.size()) throw std::runtime_error("rlfa_lan: one LfaLan per protected root");
+    return rlfa_with(gr, run, reverse_run, protect, &lans, lfa_flags, lfa, with_spaces);
+  }
+ private:
+  // the frame of rlfa() (lans == nullptr: hspf_rlfa_device) and rlfa_lan() (hspf_rlfa_lan_device)
+  RlfaOut rlfa_with(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans,
+                    uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) {
+    const uint32_t nw = lans ? HSPF_RLFA_LAN_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS, cw = lans ? HSPF_RLFA_LAN_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
+    const char *fn = lans ? "hspf_rlfa_lan_device: " : "hspf_rlfa_device: ";
+    const std::string who = lans ? "rlfa_lan: " : "rlfa: ";
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rr = static_cast<HipDeviceRun &>(reverse_run);
-    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error("rlfa: the two runs differ in shape");
+    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error(who + "the two runs differ in shape");
     RlfaOut o;
     o.supported = true;
     o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words;
@@ -787,24 +806,34 @@ class HipEngine : public Engine {
     std::vector<hspf_lfa_protect> ps;
     for (const LfaProtect &p : protect) {
       if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("rlfa: the slot arrays of a protected root differ in length");
+        throw std::runtime_error(who + "the slot arrays of a protected root differ in length");
       ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
     }
     const size_t pn = (size_t)o.n_protected * o.n_vertices, ps4 = (size_t)o.n_protected * o.slot_stride * 4, sp = with_spaces ? (size_t)o.n_protected * o.slot_stride * o.n_vertices : 0;
-    const size_t cb = (size_t)o.n_protected * HSPF_RLFA_COVERAGE_WORDS * 4;
+    std::vector<hspf_lfa_lan> ls;
+    for (size_t i = 0; lans && i < lans->size(); ++i) {
+      const LfaLan &l = (*lans)[i];
+      if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error("rlfa_lan: lan / lan_row differ in length from the slot arrays");
+      ls.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
+    }
+    const size_t cb = (size_t)o.n_protected * cw * 4;
     const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
     // one block: pq_node | pq_via | pq_metric | pq_counts | rl_node | rl_via | rl_coverage | space_via | space_flags | alt_flags
-    const size_t total = ps4 * 3 + ps4 * HSPF_RLFA_COUNT_WORDS + pn * 8 + cb + sp * 5 + (with_alt ? pn : 0);
+    const size_t total = ps4 * 3 + ps4 * nw + pn * 8 + cb + sp * 5 + (with_alt ? pn : 0);
     uint8_t *blk = (uint8_t *)pool_->dev(total);
     uint32_t *w = (uint32_t *)blk;
     hspf_rlfa_out out{};
-    out.pq_node = w; w += ps4 / 4; out.pq_via = w; w += ps4 / 4; out.pq_metric = w; w += ps4 / 4; out.pq_counts = w; w += ps4 / 4 * HSPF_RLFA_COUNT_WORDS;
+    out.pq_node = w; w += ps4 / 4; out.pq_via = w; w += ps4 / 4; out.pq_metric = w; w += ps4 / 4; out.pq_counts = w; w += ps4 / 4 * nw;
     out.rl_node = w; w += pn; out.rl_via = w; w += pn; out.rl_coverage = w; w += cb / 4;
     if (with_spaces) { out.space_via = w; w += sp; out.space_flags = (uint8_t *)w; }
     uint8_t *alt = with_alt ? (uint8_t *)w + sp : nullptr;
     bool ok = !with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess;
-    const int rc = ok ? hspf_rlfa_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(),
-                                         o.n_protected, lfa_flags, alt, &out) : HSPF_E_HIP;
+    hspf_graph *g = static_cast<HipGraph &>(gr).g;
+    const int rc = !ok ? HSPF_E_HIP
+                 : lans ? hspf_rlfa_lan_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), ls.data(),
+                                               o.n_protected, lfa_flags, alt, &out)
+                        : hspf_rlfa_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), o.n_protected,
+                                           lfa_flags, alt, &out);
     auto fetch = [&](auto &vec, const void *src, size_t count) {
       vec.resize(count);
       ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
@@ -812,14 +841,15 @@ class HipEngine : public Engine {
     ok = ok && rc == HSPF_OK;
     if (ok) {
       fetch(o.pq_node, out.pq_node, ps4 / 4); fetch(o.pq_via, out.pq_via, ps4 / 4); fetch(o.pq_metric, out.pq_metric, ps4 / 4);
-      fetch(o.pq_counts, out.pq_counts, ps4 / 4 * HSPF_RLFA_COUNT_WORDS); fetch(o.rl_node, out.rl_node, pn); fetch(o.rl_via, out.rl_via, pn);
+      fetch(o.pq_counts, out.pq_counts, ps4 / 4 * nw); fetch(o.rl_node, out.rl_node, pn); fetch(o.rl_via, out.rl_via, pn);
       fetch(o.rl_coverage, out.rl_coverage, cb / 4);
       if (with_spaces) { fetch(o.space_via, out.space_via, sp); fetch(o.space_flags, out.space_flags, sp); }
     }
     pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string("hspf_rlfa_device: ") + hspf_last_error(ctx_));
+    if (!ok) throw std::runtime_error(std::string(fn) + hspf_last_error(ctx_));
     return o;
   }
+ public:
   TilfaOut tilfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
                  const RlfaOut &rl) override {
     auto &r = static_cast<HipDeviceRun &>(run);

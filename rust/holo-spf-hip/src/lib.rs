@@ -760,15 +760,37 @@ impl Engine {
     /// for the same `protect`, so that only the destinations it left unprotected get a remote alternate.
     pub fn rlfa_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
                        ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
+        self.rlfa_device_with(g, tables, reverse, protect, None, ignore_overload, lfa, with_spaces)
+    }
+
+    /// `hspf_rlfa_lan_device`: `rlfa_device` with P, extended P and Q loop-free towards the pseudonode of every slot's LAN.
+    /// `lans` as for `lfa_lan_device`; both table sets come from the run [root] + neighbour routers + LANs and `reverse` is
+    /// ALWAYS the run on the upload of `csr_transpose`; `lfa`: what `lfa_lan_device` returned.  `pq_counts` has
+    /// `HSPF_RLFA_LAN_COUNT_WORDS` words per slot, `rl_coverage` `HSPF_RLFA_LAN_COVERAGE_WORDS` per root; the result feeds
+    /// `tilfa_device` unchanged.
+    pub fn rlfa_lan_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
+                           lans: &[(&[u32], &[u32])], ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
+        self.rlfa_device_with(g, tables, reverse, protect, Some(lans), ignore_overload, lfa, with_spaces)
+    }
+
+    /// The frame of `rlfa_device` (`lans` None) and `rlfa_lan_device`.
+    #[allow(clippy::too_many_arguments)]
+    fn rlfa_device_with(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
+                        lans: Option<&[(&[u32], &[u32])]>, ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
         let (n, np) = (tables.n_vertices as usize, protect.len());
+        let who = if lans.is_some() { "rlfa_lan_device" } else { "rlfa_device" };
+        let lan_raw = match lans { Some(l) => Some(Self::lan_raw(who, protect, l)?), None => None };
+        let count_words = if lans.is_some() { sys::HSPF_RLFA_LAN_COUNT_WORDS } else { sys::HSPF_RLFA_COUNT_WORDS } as usize;
+        let cov_words = if lans.is_some() { sys::HSPF_RLFA_LAN_COVERAGE_WORDS } else { sys::HSPF_RLFA_COVERAGE_WORDS } as usize;
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
         if reverse.n_vertices != tables.n_vertices || reverse.n_roots != tables.n_roots {
-            return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_device: the two table sets differ in shape".into() });
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: format!("{who}: the two table sets differ in shape") });
         }
         let mut raw = Vec::with_capacity(np);
         for (root_row, c, nbr_row) in protect {
             let k = c.nbr.len();
             if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
-                return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_device: the slot arrays of a protected root differ in length".into() });
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: format!("{who}: the slot arrays of a protected root differ in length") });
             }
             raw.push(sys::hspf_lfa_protect {
                 root_vertex: c.root,
@@ -786,14 +808,14 @@ impl Engine {
         let pq_node = self.device_alloc(slots * 4)?;
         let pq_via = self.device_alloc(slots * 4)?;
         let pq_metric = self.device_alloc(slots * 4)?;
-        let pq_counts = self.device_alloc(slots * sys::HSPF_RLFA_COUNT_WORDS as usize * 4)?;
+        let pq_counts = self.device_alloc(slots * count_words * 4)?;
         let rl_node = self.device_alloc(cells * 4)?;
         let rl_via = self.device_alloc(cells * 4)?;
-        let rl_cov = self.device_alloc(np * sys::HSPF_RLFA_COVERAGE_WORDS as usize * 4)?;
+        let rl_cov = self.device_alloc(np * cov_words * 4)?;
         let spaces = if with_spaces { Some((self.device_alloc(slots * n)?, self.device_alloc(slots * n * 4)?)) } else { None };
         let alt = match lfa {
             Some(l) if l.alt_flags.len() == cells => Some(self.device_from(&l.alt_flags)?),
-            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "rlfa_device: the LFA result is not of this protect list".into() }),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: format!("{who}: the LFA result is not of this protect list") }),
             None => None,
         };
         let mut out = sys::hspf_rlfa_out {
@@ -807,23 +829,15 @@ impl Engine {
             rl_via: rl_via.p as *mut u32,
             rl_coverage: rl_cov.p as *mut u32,
         };
+        let (dist, flags_in, mask, rdist) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64, reverse.dist.p as *const u32);
+        let alt_p = alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8);
         let rc = unsafe {
-            sys::hspf_rlfa_device(
-                self.ctx,
-                g.g,
-                tables.n_vertices,
-                tables.n_roots,
-                tables.words,
-                tables.dist.p as *const u32,
-                tables.flags.p as *const u16,
-                tables.mask.p as *const u64,
-                reverse.dist.p as *const u32,
-                raw.as_ptr(),
-                np as u32,
-                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
-                alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
-                &mut out,
-            )
+            match &lan_raw {
+                None => sys::hspf_rlfa_device(self.ctx, g.g, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, rdist, raw.as_ptr(), np as u32, lfa_flags, alt_p, &mut out),
+                Some(l) => {
+                    sys::hspf_rlfa_lan_device(self.ctx, g.g, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, rdist, raw.as_ptr(), l.as_ptr(), np as u32, lfa_flags, alt_p, &mut out)
+                }
+            }
         };
         if rc != sys::HSPF_OK {
             return Err(self.err(rc));
@@ -835,12 +849,12 @@ impl Engine {
             pq_node: pq_node.to_host(slots)?,
             pq_via: pq_via.to_host(slots)?,
             pq_metric: pq_metric.to_host(slots)?,
-            pq_counts: pq_counts.to_host(slots * sys::HSPF_RLFA_COUNT_WORDS as usize)?,
+            pq_counts: pq_counts.to_host(slots * count_words)?,
             space_flags: match &spaces { Some(s) => s.0.to_host(slots * n)?, None => Vec::new() },
             space_via: match &spaces { Some(s) => s.1.to_host(slots * n)?, None => Vec::new() },
             rl_node: rl_node.to_host(cells)?,
             rl_via: rl_via.to_host(cells)?,
-            rl_coverage: rl_cov.to_host(np * sys::HSPF_RLFA_COVERAGE_WORDS as usize)?,
+            rl_coverage: rl_cov.to_host(np * cov_words)?,
         })
     }
 
