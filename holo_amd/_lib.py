@@ -113,6 +113,16 @@ class HspfRlfaNodeOut(ctypes.Structure):
                 ("nd_set", ctypes.c_void_p), ("nd_coverage", ctypes.c_void_p)]
 
 
+class HspfTilfaNodeSel(ctypes.Structure):
+    _fields_ = [("tq_q", ctypes.c_void_p), ("tq_p", ctypes.c_void_p), ("tq_link", ctypes.c_void_p), ("tq_via", ctypes.c_void_p),
+                ("tq_metric", ctypes.c_void_p), ("tq_count", ctypes.c_void_p)]
+
+
+class HspfTilfaNodeOut(ctypes.Structure):
+    _fields_ = [("tn_kind", ctypes.c_void_p), ("tn_p", ctypes.c_void_p), ("tn_q", ctypes.c_void_p), ("tn_link", ctypes.c_void_p),
+                ("tn_via", ctypes.c_void_p), ("tn_metric", ctypes.c_void_p), ("tn_set", ctypes.c_void_p), ("tn_coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -225,6 +235,14 @@ SYMBOLS = [
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
                                              ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.POINTER(HspfRlfaNodeSel), ctypes.c_uint32,
                                              ctypes.c_void_p, ctypes.POINTER(HspfRlfaNodeOut)]),
+    # two-segment node-protecting repairs
+    ("hspf_tilfa_node_select_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(HspfTilfaNodeSel)]),
+    ("hspf_tilfa_node_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                              ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.POINTER(HspfTilfaNodeSel), ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfTilfaNodeOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

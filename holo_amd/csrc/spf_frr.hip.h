@@ -1,6 +1,6 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
 // hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
-// hspf_rlfa_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
+// hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
 // Included by spf_capi.hip (one TU).
 //
 // The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
@@ -15,6 +15,7 @@
 #include "spf_tilfa.hip.h"
 #include "spf_backup.hip.h"
 #include "spf_rlfa_node.hip.h"
+#include "spf_tilfa_node.hip.h"
 
 namespace {
 
@@ -165,6 +166,30 @@ LfaArgs frr_gather_lan(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words
     hipLaunchKernelGGL(k_lfa_gather_lan, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a, la);
   }
   return a;
+}
+
+// The graph's two-way flags, one byte per link in the order of the device's raw CSR, copied to ctx->tilfa_tw on the context's stream
+// (hspf_tilfa_device, hspf_tilfa_node_select_device).  The host mirror's pool is in that order unless a patch moved rows; then `tw`
+// is the copy's source: it lives until the caller has synchronised.
+int tw_stage(hspf_ctx *ctx, const char *fn, const hspf_graph *g, std::vector<uint8_t> &tw) {
+  auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+  const uint32_t e = g->e;
+  int rc;
+  if ((rc = ensure(ctx, ctx->tilfa_tw, std::max<size_t>(e, 1), false))) return rc;
+  const uint8_t *tw_src = g->twoway.data();
+  if (!g->pool_compact()) {
+    tw.resize(e);
+    size_t o = 0;
+    for (uint32_t v = 0; v < g->n; ++v) {
+      if (o + g->rlen[v] > e) return bad("the graph's host mirror and its link count disagree");
+      if (g->rlen[v]) memcpy(tw.data() + o, g->twoway.data() + g->rstart[v], g->rlen[v]);
+      o += g->rlen[v];
+    }
+    if (o != e) return bad("the graph's host mirror and its link count disagree");
+    tw_src = tw.data();
+  } else if (g->twoway.size() < e) return bad("the graph's host mirror and its link count disagree");
+  if (e) HIPCHK(ctx, hipMemcpyAsync(ctx->tilfa_tw.p, tw_src, e, hipMemcpyHostToDevice, ctx->stream));
+  return HSPF_OK;
 }
 
 // the end of a call: a launch error is reported under the name of its kernels; then the stream is drained
@@ -486,29 +511,14 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
     if (n_vertices > 0x7FFFFFFFu) return bad("n_vertices does not fit the selection key");
     const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
     if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    const uint32_t e = g->e;
     if (g->twoway.size() != g->col.size()) return bad("the graph holds no two-way flags");
     std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
     std::vector<uint8_t> tw;                            // (the same)
     uint32_t max_k = 0;
     if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
     if ((rc = ensure(ctx, ctx->tilfa_key, n_slots * 8, false))) return rc;
-    if ((rc = ensure(ctx, ctx->tilfa_tw, std::max<size_t>(e, 1), false))) return rc;
+    if ((rc = tw_stage(ctx, fn, g, tw))) return rc;
     hipStream_t s = ctx->stream;
-    // the two-way flags in the order of the device's raw CSR: the host mirror's pool is in that order unless a patch moved rows
-    const uint8_t *tw_src = g->twoway.data();
-    if (!g->pool_compact()) {
-      tw.resize(e);
-      size_t o = 0;
-      for (uint32_t v = 0; v < g->n; ++v) {
-        if (o + g->rlen[v] > e) return bad("the graph's host mirror and its link count disagree");
-        if (g->rlen[v]) memcpy(tw.data() + o, g->twoway.data() + g->rstart[v], g->rlen[v]);
-        o += g->rlen[v];
-      }
-      if (o != e) return bad("the graph's host mirror and its link count disagree");
-      tw_src = tw.data();
-    } else if (g->twoway.size() < e) return bad("the graph's host mirror and its link count disagree");
-    if (e) HIPCHK(ctx, hipMemcpyAsync(ctx->tilfa_tw.p, tw_src, e, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemsetAsync(ctx->tilfa_key.p, 0xFF, n_slots * 8, s));
     HIPCHK(ctx, hipMemsetAsync(out_dev->ti_counts, 0, n_slots * HSPF_TILFA_COUNT_WORDS * 4, s));
     HIPCHK(ctx, hipMemsetAsync(out_dev->td_coverage, 0, (size_t)n_prot * HSPF_TILFA_COVERAGE_WORDS * 4, s));
@@ -628,6 +638,120 @@ int hspf_rlfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, u
     hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_rlfa_ndest, dim3((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
     return frr_finish(ctx, "k_rlfa_ndest");
+  });
+}
+
+// ---- two-segment node-protecting repairs (include/holo_spf_hip.h "two-segment node-protecting repairs on device"; kernels:
+// spf_tilfa_node.hip.h) ----
+static_assert(TNODE_MAX_PAIRS == HSPF_TILFA_NODE_MAX_PAIRS, "the kernels' list length is the header's");
+
+int hspf_tilfa_node_select_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                  const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                  const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *space_flags_dev,
+                                  uint32_t max_pairs, hspf_tilfa_node_sel *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_tilfa_node_select_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!space_flags_dev) return bad("NULL space_flags (the table of hspf_rlfa_device is required)");
+    if (!out_dev->tq_q || !out_dev->tq_p || !out_dev->tq_link || !out_dev->tq_via || !out_dev->tq_metric || !out_dev->tq_count)
+      return bad("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count");
+    if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) return bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    if (g->twoway.size() != g->col.size()) return bad("the graph holds no two-way flags");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    std::vector<uint8_t> tw;                            // (the same)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    const size_t cells = (size_t)n_prot * max_k * n_vertices;                  // one per (root, candidate, vertex): not tiled
+    const size_t part_keys = (size_t)n_prot * max_k * n_tiles * max_pairs;     // one list per workgroup
+    if (cells > ((size_t)1 << 30)) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      ctx->last_error = std::string(fn) + ": the cells of this call (8 bytes x slots x n_vertices per protected root) need more than 8 GiB of scratch: split prot";
+      return HSPF_E_NOMEM;
+    }
+    if ((rc = ensure(ctx, ctx->tnode_cell, std::max<size_t>(cells, 1) * 8, false)) ||
+        (rc = ensure(ctx, ctx->rnode_part, std::max<size_t>(part_keys, 1) * 8, false)) || (rc = tw_stage(ctx, fn, g, tw))) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(ctx->tnode_cell.p, 0xFF, std::max<size_t>(cells, 1) * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->tq_count, 0, n_slots * 4, s));
+    TnSelArgs a{};
+    a.r.n = n_vertices; a.r.stride = (uint32_t)stride; a.r.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u; a.r.max_pq = max_pairs;
+    a.r.max_k = max_k; a.r.n_tiles = n_tiles;
+    a.r.dist = dist_dev; a.r.tab = (const uint32_t *)ctx->lfa_tab.p; a.r.sflags = space_flags_dev;
+    a.r.part = (unsigned long long *)ctx->rnode_part.p;
+    a.row_ptr = g->d_row_ptr[g->cur]; a.col = g->d_col[g->cur]; a.metric = g->d_metric[g->cur]; a.tw = (const uint8_t *)ctx->tilfa_tw.p;
+    a.cell = (unsigned long long *)ctx->tnode_cell.p;
+    a.tq_q = out_dev->tq_q; a.tq_p = out_dev->tq_p; a.tq_link = out_dev->tq_link; a.tq_via = out_dev->tq_via; a.tq_metric = out_dev->tq_metric;
+    a.tq_count = out_dev->tq_count;
+    if (max_k) {
+      const dim3 grid(n_tiles, std::min(max_k, 65535u), n_prot);
+      hipLaunchKernelGGL(k_tn_link, grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL(k_tn_sel, grid, dim3(256), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_tn_sel_final, dim3((uint32_t)stride, n_prot), dim3(64), 0, s, a);
+    return frr_finish(ctx, "k_tn_link");
+  });
+}
+
+int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                           const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                           const hspf_lfa_protect *prot, uint32_t n_prot,
+                           const uint32_t *ydist_dev, const uint32_t *y_roots, uint32_t n_yrows,
+                           const hspf_tilfa_node_sel *sel_dev, uint32_t max_pairs,
+                           const uint8_t *alt_flags_in_dev, const uint8_t *nd_kind_in_dev, hspf_tilfa_node_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_tilfa_node_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!ydist_dev || !y_roots || !sel_dev) return bad("NULL ydist, y_roots or sel pointer");
+    if (!sel_dev->tq_q || !sel_dev->tq_p || !sel_dev->tq_link || !sel_dev->tq_via || !sel_dev->tq_metric || !sel_dev->tq_count)
+      return bad("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count in sel_dev");
+    if (!out_dev->tn_kind || !out_dev->tn_p || !out_dev->tn_q || !out_dev->tn_link || !out_dev->tn_via || !out_dev->tn_metric || !out_dev->tn_coverage)
+      return bad("NULL tn_kind / tn_p / tn_q / tn_link / tn_via / tn_metric / tn_coverage");
+    if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) return bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
+    if (n_yrows == 0) return bad("n_yrows is 0");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    for (uint32_t i = 0; i < n_yrows; ++i)
+      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n_vertices) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = ensure(ctx, ctx->rnode_map, ((size_t)n_vertices + n_yrows) * 4, false))) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      return rc;
+    }
+    uint32_t *ymap = (uint32_t *)ctx->rnode_map.p, *yroots = ymap + n_vertices;
+    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n_vertices * 4, s));
+    HIPCHK(ctx, hipMemcpyAsync(yroots, y_roots, (size_t)n_yrows * 4, hipMemcpyHostToDevice, s));      // (the caller's: it lives through the call)
+    HIPCHK(ctx, hipMemsetAsync(out_dev->tn_coverage, 0, (size_t)n_prot * HSPF_TN_COVERAGE_WORDS * 4, s));
+    RnodeDestArgs m{};                                  // k_rlfa_nmap reads n, the root list and the map
+    m.n = n_vertices; m.yroots = yroots; m.n_yrows = n_yrows; m.ymap = ymap;
+    TnDestArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.stride = 64u * n_mask_words; a.max_pairs = max_pairs;
+    a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p;
+    a.ydist = ydist_dev; a.ymap = ymap;
+    a.tq_q = sel_dev->tq_q; a.tq_p = sel_dev->tq_p; a.tq_link = sel_dev->tq_link; a.tq_via = sel_dev->tq_via; a.tq_metric = sel_dev->tq_metric;
+    a.tq_count = sel_dev->tq_count;
+    a.alt_in = alt_flags_in_dev; a.nd_in = nd_kind_in_dev;
+    a.tn_kind = out_dev->tn_kind; a.tn_p = out_dev->tn_p; a.tn_q = out_dev->tn_q; a.tn_link = out_dev->tn_link; a.tn_via = out_dev->tn_via;
+    a.tn_metric = out_dev->tn_metric; a.tn_set = out_dev->tn_set; a.tn_cov = out_dev->tn_coverage;
+    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, m);
+    hipLaunchKernelGGL(k_tn_dest, dim3((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_tn_dest");
   });
 }
 

@@ -67,10 +67,73 @@ __device__ __forceinline__ bool rnode_release(const RnodeSelArgs &a, const FrrTa
   return via != LFA_NONE;
 }
 
+// The top-M extraction the select kernels share (this file and spf_tilfa_node.hip.h).  Keys are unique or all-ones.
+// the M smallest of the wave's 2 x 64 keys in ascending order, by repeated extraction of "the smallest key not below the last one + 1"
+// (a wave minimum each): lane j returns the j-th
+__device__ __forceinline__ unsigned long long rnode_wave_top(unsigned long long k0, unsigned long long k1, uint32_t M, uint32_t lane) {
+  unsigned long long out = RLFA_NO_KEY, lo = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const unsigned long long c0 = k0 >= lo ? k0 : RLFA_NO_KEY, c1 = k1 >= lo ? k1 : RLFA_NO_KEY;
+    const unsigned long long m = rlfa_wave_min(c0 < c1 ? c0 : c1);
+    if (m == RLFA_NO_KEY) break;
+    if (lane == j) out = m;
+    lo = m + 1;
+  }
+  return out;
+}
+
+// One key per thread of a 256-thread workgroup -> the workgroup's M smallest, stored (plain vector stores, all-ones padded) to
+// part[0 .. M), and the number of keys added to *count.  Per wave into s_list[4 * RNODE_MAX_PQ], wave 0 merges the four lists the
+// same way.  *s_cnt is the workgroup's, 0 on entry and on return; every thread comes here (two barriers inside).
+__device__ __forceinline__ void rnode_block_top(unsigned long long key, uint32_t M, unsigned long long *s_list, uint32_t *s_cnt,
+                                                unsigned long long *part, uint32_t *count) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  unsigned long long mine = RLFA_NO_KEY;
+  const unsigned long long b = __ballot(key != RLFA_NO_KEY);
+  if (b) {                                                                         // (wave-uniform)
+    if (lane == 0) atomicAdd(s_cnt, (uint32_t)__popcll(b));
+    mine = rnode_wave_top(key, RLFA_NO_KEY, M, lane);
+  }
+  if (lane < RNODE_MAX_PQ) s_list[wave * RNODE_MAX_PQ + lane] = mine;
+  __syncthreads();
+  if (wave == 0) {
+    // the four sorted lists -> the workgroup's: two cells per lane, the same extraction
+    const unsigned long long out = rnode_wave_top(s_list[lane], s_list[lane + 64], M, lane);
+    if (lane < M) part[lane] = out;
+    if (lane == 0 && *s_cnt) { atomicAdd(count, *s_cnt); *s_cnt = 0; }
+  }
+  __syncthreads();
+}
+
+// One wave: the n_tiles sorted, all-ones padded lists of M keys at `lists` -> their M smallest; lane j returns the j-th.  Lane t holds
+// the smallest unused key of tiles t, t + 64, ...; a wave minimum per extraction, and only the winner's lane walks its lists again.
+__device__ __forceinline__ unsigned long long rnode_merge_tiles(const unsigned long long *lists, uint32_t n_tiles, uint32_t M, uint32_t lane) {
+  // the lane's candidate: the smallest key not below `lo` in its tiles' lists (sorted: the first one counts)
+  auto scan = [&](unsigned long long lo) {
+    unsigned long long c = RLFA_NO_KEY;
+    for (uint32_t t = lane; t < n_tiles; t += 64u) {
+      const unsigned long long *L = lists + (size_t)t * M;
+      for (uint32_t i = 0; i < M; ++i) {
+        const unsigned long long k = L[i];
+        if (k >= lo) { c = k < c ? k : c; break; }
+      }
+    }
+    return c;
+  };
+  unsigned long long mine = RLFA_NO_KEY, c = scan(0);
+  for (uint32_t j = 0; j < M; ++j) {
+    const unsigned long long m = rlfa_wave_min(c);
+    if (m == RLFA_NO_KEY) break;
+    if (lane == j) mine = m;
+    if (c == m) c = scan(m + 1);                                                   // keys are unique: only the winner's lane looks again
+  }
+  return mine;
+}
+
 __global__ __launch_bounds__(256) void k_rlfa_nsel(RnodeSelArgs a) {
   __shared__ unsigned long long s_list[4 * RNODE_MAX_PQ];
   __shared__ uint32_t s_cnt;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, pi = blockIdx.z;
+  const uint32_t tid = threadIdx.x, pi = blockIdx.z;
   const FrrTab tb = frr_tab(a.tab, pi);
   const uint32_t n = a.n, M = a.max_pq;
   const uint32_t v = blockIdx.x * LFA_TILE + tid;
@@ -83,42 +146,13 @@ __global__ __launch_bounds__(256) void k_rlfa_nsel(RnodeSelArgs a) {
     const uint32_t e = tb.cl[ci], E = tb.nbr[e];
     const uint32_t sf = valid ? a.sflags[(slot0 + e) * n + vv] : 0u;
     const bool lpq = (sf & 0x0Cu) == 0x0Cu && (sf & 0x03u) && vv != E;             // eligible, in Q, in P or some XP: a link-protecting PQ node
-    unsigned long long key = RLFA_NO_KEY, mine = RLFA_NO_KEY;
-    if (__ballot(lpq)) {                                                           // (wave-uniform)
-      if (lpq) {
-        uint64_t best; uint32_t via;
-        if (rnode_release(a, tb, e, E, vv, a.dist[(size_t)tb.row[e] * n + vv], best, via))
-          key = ((best > RNODE_SAT ? RNODE_SAT : best) << 32) | vv;
-      }
-      const unsigned long long b = __ballot(key != RLFA_NO_KEY);
-      if (b) {
-        if (lane == 0) atomicAdd(&s_cnt, (uint32_t)__popcll(b));
-        unsigned long long lo = 0;
-        for (uint32_t j = 0; j < M; ++j) {
-          const unsigned long long m = rlfa_wave_min(key >= lo ? key : RLFA_NO_KEY);
-          if (m == RLFA_NO_KEY) break;
-          if (lane == j) mine = m;
-          lo = m + 1;
-        }
-      }
+    unsigned long long key = RLFA_NO_KEY;
+    if (lpq) {                                                                     // (a wave without one loads nothing more)
+      uint64_t best; uint32_t via;
+      if (rnode_release(a, tb, e, E, vv, a.dist[(size_t)tb.row[e] * n + vv], best, via))
+        key = ((best > RNODE_SAT ? RNODE_SAT : best) << 32) | vv;
     }
-    if (lane < RNODE_MAX_PQ) s_list[wave * RNODE_MAX_PQ + lane] = mine;
-    __syncthreads();
-    if (wave == 0) {
-      // the four sorted lists -> the workgroup's: two cells per lane, the same extraction
-      const unsigned long long k0 = s_list[lane], k1 = s_list[lane + 64];
-      unsigned long long out = RLFA_NO_KEY, lo = 0;
-      for (uint32_t j = 0; j < M; ++j) {
-        const unsigned long long c0 = k0 >= lo ? k0 : RLFA_NO_KEY, c1 = k1 >= lo ? k1 : RLFA_NO_KEY;
-        const unsigned long long m = rlfa_wave_min(c0 < c1 ? c0 : c1);
-        if (m == RLFA_NO_KEY) break;
-        if (lane == j) out = m;
-        lo = m + 1;
-      }
-      if (lane < M) a.part[(((size_t)pi * a.max_k + ci) * a.n_tiles + blockIdx.x) * M + lane] = out;
-      if (lane == 0 && s_cnt) { atomicAdd(a.nq_count + slot0 + e, s_cnt); s_cnt = 0; }
-    }
-    __syncthreads();
+    rnode_block_top(key, M, s_list, &s_cnt, a.part + (((size_t)pi * a.max_k + ci) * a.n_tiles + blockIdx.x) * M, a.nq_count + slot0 + e);
   }
 }
 
@@ -133,25 +167,7 @@ __global__ __launch_bounds__(64) void k_rlfa_nsel_final(RnodeSelArgs a) {
     uint32_t ci = 0;                                                               // e's place in the candidate list
     for (uint32_t k0 = 0; k0 < e; k0 += 64u) ci += (uint32_t)__popcll(__ballot(k0 + lane < e && tb.nbr[k0 + lane] != LFA_NONE));
     const unsigned long long *lists = a.part + ((size_t)pi * a.max_k + ci) * a.n_tiles * M;
-    // the lane's candidate: the smallest key not below `lo` in its tiles' lists (sorted, all-ones padded: the first one counts)
-    auto scan = [&](unsigned long long lo) {
-      unsigned long long c = RLFA_NO_KEY;
-      for (uint32_t t = lane; t < a.n_tiles; t += 64u) {
-        const unsigned long long *L = lists + (size_t)t * M;
-        for (uint32_t i = 0; i < M; ++i) {
-          const unsigned long long k = L[i];
-          if (k >= lo) { c = k < c ? k : c; break; }
-        }
-      }
-      return c;
-    };
-    unsigned long long mine = RLFA_NO_KEY, c = scan(0);
-    for (uint32_t j = 0; j < M; ++j) {
-      const unsigned long long m = rlfa_wave_min(c);
-      if (m == RLFA_NO_KEY) break;
-      if (lane == j) mine = m;
-      if (c == m) c = scan(m + 1);                                                 // keys are unique: only the winner's lane looks again
-    }
+    const unsigned long long mine = rnode_merge_tiles(lists, a.n_tiles, M, lane);
     if (mine != RLFA_NO_KEY) {
       const uint32_t v = (uint32_t)mine, E = tb.nbr[e];
       uint64_t best;

@@ -60,6 +60,9 @@ BK_LAN_COVERAGE_WORDS = 9
 RLFA_NODE_MAX_PQ = 32           # HSPF_RLFA_NODE_MAX_PQ
 NP_D_LFA, NP_D_PQ, NP_D_LAST_HOP, NP_D_NONE = 1, 2, 3, 4      # HSPF_NP_D_* (nd_kind)
 NP_COVERAGE_WORDS = 5
+TILFA_NODE_MAX_PAIRS = 32       # HSPF_TILFA_NODE_MAX_PAIRS
+TN_D_LFA, TN_D_PQ, TN_D_LAST_HOP, TN_D_NONE, TN_D_PAIR = 1, 2, 3, 4, 5      # HSPF_TN_D_* (tn_kind)
+TN_COVERAGE_WORDS = 6
 
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
@@ -302,6 +305,29 @@ class RlfaNodeResult:
     nd_coverage: np.ndarray  # [P, 5] u32
     candidates: Optional[LfaCandidates] = None
     lfa: Optional[LfaResult] = None
+
+
+@dataclass
+class TilfaNodeResult:
+    """Two-segment node-protecting repairs of the protected roots of one tilfa_node_select_device() + tilfa_node_device() pair, on
+    the host (S = 64 * mask words, M = max_pairs).  SpfContext.tilfa_node() also fills `rlfa_node`: the RlfaNodeResult (with its
+    `candidates` and `lfa`) its chain computed on the way."""
+    tq_q: np.ndarray         # [P, S, M] u32 the cheapest routers of the Q-space a forced adjacency enters, NO_ROOT padding
+    tq_p: np.ndarray         # [P, S, M] u32 the node of the extended P-space the adjacency starts at
+    tq_link: np.ndarray      # [P, S, M] u32 position of the link in p's row, LFA_NO_SLOT padding
+    tq_via: np.ndarray       # [P, S, M] u32 RLFA_VIA_SELF or a slot, LFA_NO_SLOT padding
+    tq_metric: np.ndarray    # [P, S, M] u32 entry metric
+    tq_count: np.ndarray     # [P, S] u32 all q with a qualifying link (may exceed M)
+    y_roots: np.ndarray      # [Y] u32 the roots of the q rows: the ascending union of the lists
+    tn_kind: np.ndarray      # [P, N] u8  TN_D_* per destination with exactly one primary, 0 elsewhere
+    tn_p: np.ndarray         # [P, N] u32, NO_ROOT: none
+    tn_q: np.ndarray         # [P, N] u32
+    tn_link: np.ndarray      # [P, N] u32
+    tn_via: np.ndarray       # [P, N] u32
+    tn_metric: np.ndarray    # [P, N] u32
+    tn_set: np.ndarray       # [P, N] u32 bit j: list entry j protects the destination
+    tn_coverage: np.ndarray  # [P, 6] u32
+    rlfa_node: Optional[RlfaNodeResult] = None
 
 
 @dataclass
@@ -1188,6 +1214,12 @@ class SpfContext:
         (on the transposed graph too unless `symmetric`), lfa_device(), rlfa_device() with the space tables,
         rlfa_node_select_device(), the lists to the host, ONE run_device() over the ascending union of the listed nodes,
         rlfa_node_device().  Returns a RlfaNodeResult with one row (its `candidates` and `lfa` — without masks — filled)."""
+        return self._rlfa_node(graph, root, run_flags, lfa_flags, max_pq, symmetric)[0]
+
+    def _rlfa_node(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, max_pq: int, symmetric: bool, tail=None):
+        """The chain of rlfa_node().  tail(dev, tables, protect, R, W): what tilfa_node() goes on with while the tables, the
+        space_flags (dev["sp_flags"]), the alt_flags (dev["aflags"]) and nd_kind (dev["nd_kind"]) are on the device.  Returns
+        (RlfaNodeResult, what `tail` returned)."""
         plan = self._frr_plan(graph, root)
         cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
         R, n, S, M = len(roots), graph.n, 64 * W, int(max_pq)
@@ -1229,8 +1261,76 @@ class SpfContext:
                 self.rlfa_node_device(n, R, W, *tables, protect, ydist_ptr=ydev["ydist"], y_roots=y_roots, sel=tuple(dev[k] for k in sel),
                                       max_pq=M, alt_flags_in_ptr=dev["aflags"], **{k + "_ptr": dev[k] for k in nd})
                 self._fetch(nd, dev)
+            more = tail(dev, tables, protect, R, W) if tail else None
         lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
-        return RlfaNodeResult(*sel.values(), y_roots, *nd.values(), candidates=cand, lfa=lfa)
+        return RlfaNodeResult(*sel.values(), y_roots, *nd.values(), candidates=cand, lfa=lfa), more
+
+    def tilfa_node_select_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
+                                 space_flags_ptr: int, max_pairs: int, tq_q_ptr: int, tq_p_ptr: int, tq_link_ptr: int, tq_via_ptr: int,
+                                 tq_metric_ptr: int, tq_count_ptr: int, lfa_flags: int = 0) -> None:
+        """hspf_tilfa_node_select_device(): per (protected root, slot) the cheapest `max_pairs` routers q of the Q-space that a forced
+        adjacency p -> q enters from a node p of the extended P-space whose release path avoids the neighbour behind the slot, from
+        the tables of a run_device(), the links of `graph` (the FORWARD graph) and the space_flags rlfa_device() wrote for the same
+        `protect` and lfa_flags.  All `*_ptr` are device pointers; the lists are [P][64 * mask_words][max_pairs]."""
+        arr, keep = self._protect_array(protect, "tilfa_node_select_device")
+        out = L.HspfTilfaNodeSel(tq_q_ptr or None, tq_p_ptr or None, tq_link_ptr or None, tq_via_ptr or None, tq_metric_ptr or None, tq_count_ptr or None)
+        rc = self.lib.hspf_tilfa_node_select_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
+                                                    mask_ptr or None, arr, len(protect), lfa_flags, space_flags_ptr or None, max_pairs, ctypes.byref(out))
+        del keep
+        self._check_rc("hspf_tilfa_node_select_device", rc)
+
+    def tilfa_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
+                          ydist_ptr: int, y_roots, sel: tuple, max_pairs: int, tn_kind_ptr: int, tn_p_ptr: int, tn_q_ptr: int, tn_link_ptr: int,
+                          tn_via_ptr: int, tn_metric_ptr: int, tn_coverage_ptr: int, tn_set_ptr: int = 0, alt_flags_in_ptr: int = 0,
+                          nd_kind_in_ptr: int = 0) -> None:
+        """hspf_tilfa_node_device(): per destination with one primary, the cheapest listed pair whose q reaches it without the
+        primary's neighbour.  ydist_ptr: `dist` [len(y_roots)][n] of a forward run_device() of `y_roots` (host array; NO_ROOT
+        entries are skipped); sel = (tq_q_ptr, tq_p_ptr, tq_link_ptr, tq_via_ptr, tq_metric_ptr, tq_count_ptr) of
+        tilfa_node_select_device() with the same max_pairs.  tn_set_ptr / alt_flags_in_ptr / nd_kind_in_ptr (the nd_kind of
+        rlfa_node_device()) may be 0."""
+        arr, keep = self._protect_array(protect, "tilfa_node_device")
+        yr = np.ascontiguousarray(y_roots, np.uint32)
+        se = L.HspfTilfaNodeSel(*(x or None for x in sel))
+        out = L.HspfTilfaNodeOut(tn_kind_ptr or None, tn_p_ptr or None, tn_q_ptr or None, tn_link_ptr or None, tn_via_ptr or None, tn_metric_ptr or None,
+                                 tn_set_ptr or None, tn_coverage_ptr or None)
+        rc = self.lib.hspf_tilfa_node_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                             arr, len(protect), ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), ctypes.byref(se), max_pairs,
+                                             alt_flags_in_ptr or None, nd_kind_in_ptr or None, ctypes.byref(out))
+        del keep
+        self._check_rc("hspf_tilfa_node_device", rc)
+
+    def tilfa_node(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, max_pq: int = 16, max_pairs: int = 16,
+                   symmetric: bool = False):
+        """Two-segment node-protecting repairs of one root, start to finish: the chain of rlfa_node(), then
+        tilfa_node_select_device() on the same tables, the lists to the host, ONE run_device() over the ascending union of the
+        listed q's, tilfa_node_device() with the alt_flags of lfa_device() and the nd_kind of rlfa_node_device().  Returns a
+        TilfaNodeResult with one row; its `rlfa_node` is what rlfa_node() returns."""
+        n, M = graph.n, int(max_pairs)
+
+        def tail(dev, tables, protect, R, W):
+            S = 64 * W
+            sel = {k: np.empty((1, S, M), np.uint32) for k in ("tq_q", "tq_p", "tq_link", "tq_via", "tq_metric")}
+            sel["tq_count"] = np.empty((1, S), np.uint32)
+            tn = dict(tn_kind=np.empty((1, n), np.uint8), **{k: np.empty((1, n), np.uint32) for k in ("tn_p", "tn_q", "tn_link", "tn_via", "tn_metric", "tn_set")},
+                      tn_coverage=np.empty((1, TN_COVERAGE_WORDS), np.uint32))
+            with self._dev_buffers({k: max(a.nbytes, 8) for k, a in dict(sel, **tn).items()}) as tdev:
+                self.tilfa_node_select_device(graph, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pairs=M, lfa_flags=lfa_flags,
+                                              **{k + "_ptr": tdev[k] for k in sel})
+                self._fetch(sel, tdev)
+                y_roots = np.unique(sel["tq_q"][sel["tq_q"] != NO_ROOT]).astype(np.uint32)
+                if len(y_roots) == 0:                   # no list holds a q: one padding row keeps the second call's arguments valid
+                    y_roots = np.array([NO_ROOT], np.uint32)
+                with self._dev_buffers(dict(ydist=4 * len(y_roots) * n)) as ydev:
+                    if y_roots[0] != NO_ROOT:
+                        self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
+                    self.tilfa_node_device(n, R, W, *tables, protect, ydist_ptr=ydev["ydist"], y_roots=y_roots, sel=tuple(tdev[k] for k in sel),
+                                           max_pairs=M, alt_flags_in_ptr=dev["aflags"], nd_kind_in_ptr=dev["nd_kind"],
+                                           **{k + "_ptr": tdev[k] for k in tn})
+                    self._fetch(tn, tdev)
+            return sel, y_roots, tn
+
+        nd, (sel, y_roots, tn) = self._rlfa_node(graph, root, run_flags, lfa_flags, max_pq, symmetric, tail)
+        return TilfaNodeResult(*sel.values(), y_roots, *tn.values(), rlfa_node=nd)
 
     def close(self):
         if self.handle:

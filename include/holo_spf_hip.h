@@ -958,8 +958,9 @@ int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices
  * the second segment is the Adj-SID p advertises for the link at position ti_link of its row.
  *
  * OUT OF SCOPE: adjacencies across a LAN pseudonode (p -> network vertex -> q is not offered: q must be a router in p's own
- * row); node protection (one-segment node-protecting repairs: hspf_rlfa_node_device, below; two-segment ones are out of
- * scope there too); segment lists longer than two; post-convergence-path selection among equal-cost repairs. */
+ * row); node protection (one-segment node-protecting repairs: hspf_rlfa_node_device, below; two-segment ones:
+ * hspf_tilfa_node_select_device / hspf_tilfa_node_device, below that); segment lists longer than two; post-convergence-path
+ * selection among equal-cost repairs. */
 #define HSPF_TILFA_NONE           0u            /* ti_kind */
 #define HSPF_TILFA_NODE           1u
 #define HSPF_TILFA_PAIR           2u
@@ -1120,7 +1121,9 @@ int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n
  *
  * From nd_* to a tunnel that survives the neighbour's failure: INTEGRATION.md §5l.
  *
- * OUT OF SCOPE: two-segment node-protecting repairs (a forced adjacency after the tunnel); LAN pseudonodes as the protected
+ * Where no listed PQ node protects a destination (HSPF_NP_D_NONE), a forced adjacency after the tunnel may: the two-segment
+ * node-protecting repairs of hspf_tilfa_node_select_device / hspf_tilfa_node_device, below.
+ * OUT OF SCOPE: LAN pseudonodes as the protected
  * node (the failure of every router behind the primary's LAN); per-prefix node-protecting remote repairs; SRLGs. */
 #define HSPF_RLFA_NODE_MAX_PQ   32u
 #define HSPF_NP_D_LFA           1u             /* nd_kind */
@@ -1152,6 +1155,103 @@ int hspf_rlfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, u
                           const uint32_t *ydist_dev, const uint32_t *y_roots /* HOST */, uint32_t n_yrows,
                           const hspf_rlfa_node_sel *sel_dev, uint32_t max_pq,
                           const uint8_t *alt_flags_in_dev, hspf_rlfa_node_out *out_dev);
+
+/* ---- two-segment node-protecting repairs on device (TI-LFA node protection): new symbols, same ABI number -------------------
+ * hspf_rlfa_node_device can only choose among the link-protecting PQ nodes: routers in both the extended P-space and the Q-space
+ * of the protected link.  Where that set is empty — exactly where hspf_tilfa_device needs a pair — or where every PQ node's own
+ * path to the destination crosses the neighbour, every destination ends as HSPF_NP_D_NONE.  The repair for them is the pair of
+ * hspf_tilfa_device made node-protecting: a tunnel to a node p of the extended P-space whose release path avoids the NODE E, one
+ * forced adjacency p -> q into the Q-space, and a q whose own path to the destination avoids E.  The destination test depends
+ * on q alone, so the select call lists q's (each with the cheapest way into it), the caller runs ONE forward hspf_run_device
+ * over the listed q's, and the second call tests per destination — the shape of the RLFA-node pair above.
+ *
+ * hspf_tilfa_node_select_device.  The forward table set, `prot`, n_prot and lfa_flags are exactly those of hspf_lfa_device; `g` is
+ * the FORWARD graph (its links are scanned, as by hspf_tilfa_device); space_flags_dev [n_prot][stride][n_vertices] is what
+ * hspf_rlfa_device wrote for the same `prot` and lfa_flags.  max_pairs is 1 .. HSPF_TILFA_NODE_MAX_PAIRS.
+ * Per protected root S and candidate slot e (E = nbr[e]); every sum is evaluated in 64 bits; a term that is HSPF_DIST_INF makes
+ * its inequality false.
+ *   relN(p), via  the release point of p under hspf_rlfa_node_select_device's rule (NP: S itself, via = HSPF_RLFA_VIA_SELF; NXP
+ *                 for a via-slot k with N_k != E; S first, then the smaller k), as the UNSATURATED 64-bit sum.  p has a
+ *                 node-avoiding release point iff NP or some NXP holds.
+ *   a link qualifies   the link at position j of p's row in g, target q, cost w, iff it is a usable pair of hspf_tilfa_device (p has
+ *                 HSPF_RLFA_ELIGIBLE and _IN_P or _IN_XP; q != p; q has _ELIGIBLE and _IN_Q; the link passes the two-way check),
+ *                 p != E, q != E, and p has a node-avoiding release point.
+ *   entry of q    over the qualifying links into q the smallest relN(p) + w, saturated at 0xFFFFFFFE first and compared
+ *                 afterwards (as ti_metric); then the smaller p, then the smaller j.  Only the cheapest way into a q matters.
+ *   list          the q's with a qualifying link in ascending (saturated entry metric, q); the first min(tq_count, max_pairs).
+ * Outputs (DEVICE pointers; slots are strided by 64 * n_mask_words per protected root):
+ *   tq_q / tq_p / tq_link / tq_via / tq_metric [n_prot][stride][max_pairs]: per list entry q, the p of its entry, the position j
+ *                 of the link in p's row of g, the via of p's release point, the saturated entry metric.  The rest of a list,
+ *                 and the lists of slots that are no candidates or >= n_slots, are HSPF_NO_ROOT / HSPF_NO_ROOT /
+ *                 HSPF_LFA_NO_SLOT / HSPF_LFA_NO_SLOT / 0.
+ *   tq_count [n_prot][stride]: ALL distinct q with a qualifying link (may exceed max_pairs); 0 for slots that are no candidates.
+ * Scratch.  The call keeps one 8-byte cell per (protected root, candidate slot, vertex): 8 bytes x (the largest n_slots of the
+ * call) x n_vertices per protected root, next to the staged two-way bytes (one per link).  It does NOT tile: a call whose cells
+ * exceed 2^30 (8 GiB) returns HSPF_E_NOMEM and the caller splits `prot`.  At 100 000 routers and 4 slots that is 3.2 MB per root.
+ *
+ * hspf_tilfa_node_device.  The inputs of hspf_rlfa_node_device with sel_dev / max_pairs of the select call above in place of
+ * hspf_rlfa_node_sel / max_pq: ydist_dev [n_yrows][n_vertices] is `dist` of a FORWARD hspf_run_device whose root list was y_roots
+ * (HOST array) — the caller's choice of listed q's; HSPF_NO_ROOT entries are skipped, a vertex listed twice may use either
+ * row, a listed q without a row is skipped.  nd_kind_in_dev: NULL, or the nd_kind [n_prot][n_vertices] hspf_rlfa_node_device wrote
+ * for the same `prot`.
+ * Per S and destination D in S's SPT, D != S, with exactly ONE primary slot e (E = nbr[e]):
+ *   entry j < min(tq_count[e], max_pairs) with q = tq_q[e][j] protects D iff  d(q, D) < d(q, E) + d(E, D)   (d(q, .) from q's row,
+ *                 d(E, D) from row nbr_row[e] of the forward set)
+ *   choice        among the protecting entries the smallest tq_metric[e][j] + d(q, D) (64 bits), then the smaller j
+ *   tn_kind u8    0 unless D has exactly one primary; else, in this order: HSPF_TN_D_LFA the given alt_flags have
+ *                 HSPF_LFA_NODE_PROTECT | HSPF_TN_D_NONE the slot is no candidate | HSPF_TN_D_LAST_HOP D == E | HSPF_TN_D_PQ
+ *                 nd_kind_in is given and says HSPF_NP_D_PQ (the one-segment repair stands; nothing is chosen here) |
+ *                 HSPF_TN_D_PAIR an entry was chosen | HSPF_TN_D_NONE
+ *   tn_p / tn_q / tn_link / tn_via / tn_metric   for HSPF_TN_D_PAIR the chosen entry's fields and the sum saturated at 0xFFFFFFFE;
+ *                 HSPF_NO_ROOT / HSPF_NO_ROOT / HSPF_LFA_NO_SLOT / HSPF_LFA_NO_SLOT / 0 otherwise
+ *   tn_set u32    optional (NULL skips the table): bit j = entry j protects D, for the D that reach the test; 0 otherwise
+ *   tn_coverage [n_prot][6], counted on the device: destinations with exactly one primary, then the five classes by their numbers.
+ * Argument errors of both — everything the RLFA-node pair rejects, max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS, and for the
+ * select call a NULL graph, n_vertices not the graph's, a NULL space table — return HSPF_E_INVAL with a text in hspf_last_error
+ * that names the function, before anything is launched.  Each call stages once, enqueues everything on the context's stream and
+ * synchronises once at the end.
+ *
+ * From tn_* to a label stack: INTEGRATION.md §5o.
+ *
+ * OUT OF SCOPE: LAN pseudonodes as the protected node; LAN-safe release paths (the NP / NXP release paths are derived against E
+ * only — the limitation of hspf_rlfa_node_select_device — so on the tables of hspf_rlfa_lan_device the tunnel may still cross the
+ * slot's pseudonode); forced adjacencies across a pseudonode (q must be a router in p's own row); per-prefix node-protecting
+ * repairs; segment lists longer than two; SRLGs. */
+#define HSPF_TILFA_NODE_MAX_PAIRS 32u
+#define HSPF_TN_D_LFA             1u           /* tn_kind */
+#define HSPF_TN_D_PQ              2u
+#define HSPF_TN_D_LAST_HOP        3u
+#define HSPF_TN_D_NONE            4u
+#define HSPF_TN_D_PAIR            5u
+#define HSPF_TN_COVERAGE_WORDS    6u
+typedef struct {                 /* DEVICE pointers; stride = 64 * n_mask_words                               */
+  uint32_t *tq_q;                /* [n_prot][stride][max_pairs]  HSPF_NO_ROOT-padded                           */
+  uint32_t *tq_p;                /* [n_prot][stride][max_pairs]  HSPF_NO_ROOT-padded                           */
+  uint32_t *tq_link;             /* [n_prot][stride][max_pairs]  position in p's row; HSPF_LFA_NO_SLOT padding */
+  uint32_t *tq_via;              /* [n_prot][stride][max_pairs]  HSPF_RLFA_VIA_SELF or a slot; HSPF_LFA_NO_SLOT padding */
+  uint32_t *tq_metric;           /* [n_prot][stride][max_pairs]  entry metric; 0 padding                       */
+  uint32_t *tq_count;            /* [n_prot][stride]             ALL q with a qualifying link (may exceed max_pairs) */
+} hspf_tilfa_node_sel;
+int hspf_tilfa_node_select_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                  const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                  const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags,
+                                  const uint8_t *space_flags_dev, uint32_t max_pairs, hspf_tilfa_node_sel *out_dev);
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint8_t  *tn_kind;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *tn_p;                /* [n_prot][n_vertices]                                                       */
+  uint32_t *tn_q;                /* [n_prot][n_vertices]                                                       */
+  uint32_t *tn_link;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *tn_via;              /* [n_prot][n_vertices]                                                       */
+  uint32_t *tn_metric;           /* [n_prot][n_vertices]                                                       */
+  uint32_t *tn_set;              /* [n_prot][n_vertices] bit j = list entry j protects; or NULL                */
+  uint32_t *tn_coverage;         /* [n_prot][HSPF_TN_COVERAGE_WORDS]                                           */
+} hspf_tilfa_node_out;
+int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                           const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                           const hspf_lfa_protect *prot, uint32_t n_prot,
+                           const uint32_t *ydist_dev, const uint32_t *y_roots /* HOST */, uint32_t n_yrows,
+                           const hspf_tilfa_node_sel *sel_dev, uint32_t max_pairs,
+                           const uint8_t *alt_flags_in_dev, const uint8_t *nd_kind_in_dev, hspf_tilfa_node_out *out_dev);
 
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root

@@ -138,6 +138,26 @@ struct Tilfa {
   uint32_t td_coverage[HSPF_TILFA_COVERAGE_WORDS] = {};
 };
 
+// Two-segment node-protecting repairs (hspf_tilfa_node_select_device / hspf_tilfa_node_device) of one protected root on the host:
+// the RLFA result they complete (with its space tables), the node-protecting remote LFA in front of them (hspf_rlfa_node_*: its
+// one-segment repairs stand), per slot the listed q's, per destination its class and repair.
+struct TilfaNode {
+  Rlfa rlfa;
+  uint32_t max_pq = 0, max_pairs = 0;
+  std::vector<uint32_t> nq_node, nq_via, nq_metric;       // [slot_stride][max_pq]
+  std::vector<uint32_t> nq_count;                         // [slot_stride]
+  std::vector<uint32_t> pq_roots;                         // the roots of the PQ-node rows: the ascending union of the nq lists
+  std::vector<uint8_t> nd_kind;                           // [n_vertices] HSPF_NP_D_*
+  std::vector<uint32_t> nd_node, nd_via, nd_metric;       // [n_vertices]
+  uint32_t nd_coverage[HSPF_NP_COVERAGE_WORDS] = {};
+  std::vector<uint32_t> tq_q, tq_p, tq_link, tq_via, tq_metric;   // [slot_stride][max_pairs]
+  std::vector<uint32_t> tq_count;                         // [slot_stride]
+  std::vector<uint32_t> y_roots;                          // the roots of the q rows: the ascending union of the tq lists
+  std::vector<uint8_t> tn_kind;                           // [n_vertices] HSPF_TN_D_*
+  std::vector<uint32_t> tn_p, tn_q, tn_link, tn_via, tn_metric, tn_set;   // [n_vertices]
+  uint32_t tn_coverage[HSPF_TN_COVERAGE_WORDS] = {};
+};
+
 // Per-prefix backup routes (hspf_routes_device + hspf_routes_backup_device) of one protected root on the host: the route of every
 // prefix, its backup (HSPF_BK_*), and the per-slot repairs bk_primary indexes (ti_* of `tilfa`: empty without `remote`).
 struct BackupRoutes {
@@ -465,6 +485,40 @@ class Engine {
                                          ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pq, alt_flags_in_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_node_device (") + hspf_last_error(ctx_) + ")");
   }
+  // hspf_tilfa_node_select_device on DEVICE tables: the table set and protect list of lfa_device, the FORWARD graph and the
+  // space_flags rlfa_device wrote for them; the lists are [protect.size()][64 * n_mask_words][max_pairs].
+  void tilfa_node_select_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                                const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags,
+                                const uint8_t *space_flags_dev, uint32_t max_pairs, hspf_tilfa_node_sel out_dev) {
+    const int rc = hspf_tilfa_node_select_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                                 (uint32_t)protect.size(), lfa_flags, space_flags_dev, max_pairs, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_node_select_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // hspf_tilfa_node_device on DEVICE tables: ydist_dev is the dist of a forward run of y_roots (host list: the caller's choice among
+  // the listed q's), sel_dev what tilfa_node_select_device wrote with the same max_pairs; nd_kind_in_dev: the nd_kind of
+  // rlfa_node_device for the same protect list, or nullptr.
+  void tilfa_node_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                         const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const uint32_t *ydist_dev,
+                         const std::vector<uint32_t> &y_roots, const hspf_tilfa_node_sel &sel_dev, uint32_t max_pairs, const uint8_t *alt_flags_in_dev,
+                         const uint8_t *nd_kind_in_dev, hspf_tilfa_node_out out_dev) {
+    const int rc = hspf_tilfa_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                          ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pairs, alt_flags_in_dev, nd_kind_in_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_node_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // One root start to finish: rlfa() with the space tables, everything kept on the device, then the node-protecting remote LFA
+  // (select, ONE run over the union of the listed PQ nodes, evaluate) and the two-segment node-protecting repairs (select, ONE run
+  // over the union of the listed q's, evaluate with the alt_flags of hspf_lfa_device and the nd_kind of hspf_rlfa_node_device) on
+  // the same rows.
+  TilfaNode tilfa_node(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                       const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
+                       bool symmetric = false, uint32_t max_pq = 16, uint32_t max_pairs = 16) {
+    if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) throw Error(HSPF_E_INVAL, "Engine::tilfa_node: max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
+    if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) throw Error(HSPF_E_INVAL, "Engine::tilfa_node: max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
+    TilfaNode t;
+    t.max_pq = max_pq; t.max_pairs = max_pairs;
+    t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, nullptr, nullptr, nullptr, &t);
+    return t;
+  }
   // hspf_routes_backup_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the routes
   // hspf_routes_device wrote for it, optionally the per-slot arrays of tilfa_device (nullptr: no remote fallback).
   void routes_backup_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
@@ -509,10 +563,11 @@ class Engine {
 
  private:
   // rlfa(); with `ti` the two-segment step runs on the same device tables before anything is freed; with `bk` the routes of `table`
-  // and their backups are derived there too (without `ti` the remote-LFA call is skipped: nothing reads it)
+  // and their backups are derived there too (without `ti` the remote-LFA call is skipped: nothing reads it); with `tn` (and the
+  // space tables) the two node-protecting pairs of calls run there, each with its own run over the union of its lists
   Rlfa rlfa_impl(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
                  const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags, uint32_t lfa_flags,
-                 bool symmetric, bool with_spaces, Tilfa *ti, BackupRoutes *bk, const hspf_prefix_table *table) {
+                 bool symmetric, bool with_spaces, Tilfa *ti, BackupRoutes *bk, const hspf_prefix_table *table, TilfaNode *tn = nullptr) {
     if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
       throw Error(HSPF_E_INVAL, "Engine::rlfa: the CSR is not the one the graph was uploaded from");
     Rlfa r;
@@ -579,6 +634,51 @@ class Engine {
       ti->ti_counts = tc.to_host<uint32_t>((size_t)S * HSPF_TILFA_COUNT_WORDS); ti->td_kind = dk.to_host<uint8_t>(n);
       const std::vector<uint32_t> c5 = dc.to_host<uint32_t>(HSPF_TILFA_COVERAGE_WORDS);
       std::copy(c5.begin(), c5.end(), ti->td_coverage);
+    }
+    if (tn) {
+      // the ascending union of the vertices a select call listed, its rows (dist only) on the forward graph; one padding row keeps the
+      // arguments of the evaluate call valid where no list holds a vertex
+      auto rows_of = [&](const std::vector<uint32_t> &listed, std::vector<uint32_t> &y, DeviceBuffer &ydist) {
+        for (uint32_t v : listed) if (v != HSPF_NO_ROOT) y.push_back(v);
+        std::sort(y.begin(), y.end());
+        y.erase(std::unique(y.begin(), y.end()), y.end());
+        const bool none = y.empty();
+        if (none) y.push_back(HSPF_NO_ROOT);
+        ydist = DeviceBuffer(ctx_, y.size() * (size_t)n * 4);
+        if (none) return;
+        hspf_result yout{ydist.as<uint32_t>(), nullptr, nullptr, nullptr, 1, nullptr};
+        const int yrc = hspf_run_device(ctx_, g.raw(), y.data(), (uint32_t)y.size(), run_flags, &yout);
+        if (yrc != HSPF_OK) throw Error(yrc, std::string("hspf_run_device over the listed vertices (") + hspf_last_error(ctx_) + ")");
+      };
+      const size_t SQ = (size_t)S * tn->max_pq, SP = (size_t)S * tn->max_pairs;
+      DeviceBuffer qn(ctx_, SQ * 4), qv(ctx_, SQ * 4), qm(ctx_, SQ * 4), qc(ctx_, S * 4), ydn(ctx_, 0);
+      const hspf_rlfa_node_sel nsel{qn.as<uint32_t>(), qv.as<uint32_t>(), qm.as<uint32_t>(), qc.as<uint32_t>()};
+      rlfa_node_select_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, sp_flags.as<uint8_t>(), tn->max_pq, nsel);
+      tn->nq_node = qn.to_host<uint32_t>(SQ); tn->nq_via = qv.to_host<uint32_t>(SQ); tn->nq_metric = qm.to_host<uint32_t>(SQ);
+      tn->nq_count = qc.to_host<uint32_t>(S);
+      rows_of(tn->nq_node, tn->pq_roots, ydn);
+      DeviceBuffer dk(ctx_, n), dn(ctx_, (size_t)n * 4), dv(ctx_, (size_t)n * 4), dm(ctx_, (size_t)n * 4), dc(ctx_, HSPF_NP_COVERAGE_WORDS * 4);
+      rlfa_node_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, ydn.as<uint32_t>(), tn->pq_roots, nsel, tn->max_pq,
+                       fl.as<uint8_t>(), hspf_rlfa_node_out{dk.as<uint8_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(), dm.as<uint32_t>(), nullptr, dc.as<uint32_t>()});
+      tn->nd_kind = dk.to_host<uint8_t>(n); tn->nd_node = dn.to_host<uint32_t>(n); tn->nd_via = dv.to_host<uint32_t>(n); tn->nd_metric = dm.to_host<uint32_t>(n);
+      const std::vector<uint32_t> c5 = dc.to_host<uint32_t>(HSPF_NP_COVERAGE_WORDS);
+      std::copy(c5.begin(), c5.end(), tn->nd_coverage);
+      DeviceBuffer tq(ctx_, SP * 4), tp(ctx_, SP * 4), tl(ctx_, SP * 4), tvi(ctx_, SP * 4), tme(ctx_, SP * 4), tc(ctx_, S * 4), ydq(ctx_, 0);
+      const hspf_tilfa_node_sel tsel{tq.as<uint32_t>(), tp.as<uint32_t>(), tl.as<uint32_t>(), tvi.as<uint32_t>(), tme.as<uint32_t>(), tc.as<uint32_t>()};
+      tilfa_node_select_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, sp_flags.as<uint8_t>(), tn->max_pairs, tsel);
+      tn->tq_q = tq.to_host<uint32_t>(SP); tn->tq_p = tp.to_host<uint32_t>(SP); tn->tq_link = tl.to_host<uint32_t>(SP);
+      tn->tq_via = tvi.to_host<uint32_t>(SP); tn->tq_metric = tme.to_host<uint32_t>(SP); tn->tq_count = tc.to_host<uint32_t>(S);
+      rows_of(tn->tq_q, tn->y_roots, ydq);
+      DeviceBuffer ek(ctx_, n), ep(ctx_, (size_t)n * 4), eq(ctx_, (size_t)n * 4), el(ctx_, (size_t)n * 4), ev(ctx_, (size_t)n * 4), em(ctx_, (size_t)n * 4),
+          es(ctx_, (size_t)n * 4), ec(ctx_, HSPF_TN_COVERAGE_WORDS * 4);
+      tilfa_node_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, ydq.as<uint32_t>(), tn->y_roots, tsel, tn->max_pairs,
+                        fl.as<uint8_t>(), dk.as<uint8_t>(),
+                        hspf_tilfa_node_out{ek.as<uint8_t>(), ep.as<uint32_t>(), eq.as<uint32_t>(), el.as<uint32_t>(), ev.as<uint32_t>(), em.as<uint32_t>(),
+                                            es.as<uint32_t>(), ec.as<uint32_t>()});
+      tn->tn_kind = ek.to_host<uint8_t>(n); tn->tn_p = ep.to_host<uint32_t>(n); tn->tn_q = eq.to_host<uint32_t>(n); tn->tn_link = el.to_host<uint32_t>(n);
+      tn->tn_via = ev.to_host<uint32_t>(n); tn->tn_metric = em.to_host<uint32_t>(n); tn->tn_set = es.to_host<uint32_t>(n);
+      const std::vector<uint32_t> c6 = ec.to_host<uint32_t>(HSPF_TN_COVERAGE_WORDS);
+      std::copy(c6.begin(), c6.end(), tn->tn_coverage);
     }
     if (bk) {
       const size_t np = table->n_prefixes, nz = std::max<size_t>(np, 1);

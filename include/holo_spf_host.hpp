@@ -159,6 +159,21 @@ struct RlfaNodeOut {
   std::vector<uint32_t> nd_node, nd_via, nd_metric, nd_set; // [n_protected][n_vertices]
   std::vector<uint32_t> nd_coverage;                        // [n_protected][HSPF_NP_COVERAGE_WORDS]
 };
+// Two-segment node-protecting repairs (hspf_tilfa_node_select_device, one run over the listed q's, hspf_tilfa_node_device) of the
+// same protected roots: per (protected root, slot) the cheapest max_pairs routers q of the Q-space a forced adjacency p -> q enters
+// from a node p whose release path avoids the neighbour behind the slot, and per destination the cheapest of them whose q reaches it
+// without that neighbour, from the forward DeviceRun and the space_flags of rlfa(..., with_spaces = true).  supported == false: no
+// such call.
+struct TilfaNodeOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_vertices = 0, slot_stride = 64, max_pairs = 0;
+  std::vector<uint32_t> tq_q, tq_p, tq_link, tq_via, tq_metric;   // [n_protected][slot_stride][max_pairs]
+  std::vector<uint32_t> tq_count;                           // [n_protected][slot_stride]
+  std::vector<uint32_t> y_roots;                            // the roots of the q rows: the ascending union of the lists
+  std::vector<uint8_t> tn_kind;                             // [n_protected][n_vertices] HSPF_TN_D_*
+  std::vector<uint32_t> tn_p, tn_q, tn_link, tn_via, tn_metric, tn_set;   // [n_protected][n_vertices]
+  std::vector<uint32_t> tn_coverage;                        // [n_protected][HSPF_TN_COVERAGE_WORDS]
+};
 // Per-prefix backup routes (hspf_routes_backup_device) of the same protected roots over the prefix table of a DeviceRoutes: per
 // (protected root, prefix) the kind of backup (HSPF_BK_*), the primary slot, the backup slot / metric / flags.  `tilfa`: nullptr, or
 // what tilfa() returned for the same protect list (the fallback to the primary link's repair).  supported == false: no such call.
@@ -180,6 +195,10 @@ class Engine {
   // PQ-node rows are run on it with `run_flags`.  The default: not supported.
   virtual RlfaNodeOut rlfa_node(Graph &, DeviceRun & /*run*/, const std::vector<LfaProtect> &, uint32_t /*run_flags*/, uint32_t /*lfa_flags*/,
                                 const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/, uint32_t /*max_pq*/) { return RlfaNodeOut{}; }
+  // As rlfa_node(); `node`: what rlfa_node() returned for the same protect list (its one-segment repairs stand: HSPF_TN_D_PQ), or
+  // nullptr.  The default: not supported.
+  virtual TilfaNodeOut tilfa_node(Graph &, DeviceRun & /*run*/, const std::vector<LfaProtect> &, uint32_t /*run_flags*/, uint32_t /*lfa_flags*/,
+                                  const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/, const RlfaNodeOut * /*node*/, uint32_t /*max_pairs*/) { return TilfaNodeOut{}; }
   // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph.  The default: not supported.
   virtual TilfaOut tilfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                          const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/) { return TilfaOut{}; }
@@ -968,6 +987,88 @@ class HipEngine : public Engine {
       if (ok) {
         fetch(o.nd_kind, out.nd_kind, pn); fetch(o.nd_node, out.nd_node, pn); fetch(o.nd_via, out.nd_via, pn); fetch(o.nd_metric, out.nd_metric, pn);
         fetch(o.nd_set, out.nd_set, pn); fetch(o.nd_coverage, out.nd_coverage, cb);
+      }
+    }
+    if (ydist) pool_->dev_free(ydist, ybytes);
+    pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    return o;
+  }
+  TilfaNodeOut tilfa_node(Graph &gr, DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t run_flags, uint32_t lfa_flags, const LfaOut *lfa,
+                          const RlfaOut &rl, const RlfaNodeOut *node, uint32_t max_pairs) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    TilfaNodeOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words; o.max_pairs = max_pairs;
+    if (protect.empty()) return o;
+    if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) throw std::runtime_error("tilfa_node: max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = ps * o.n_vertices, pm = ps * max_pairs;
+    if (rl.space_flags.size() != sp) throw std::runtime_error("tilfa_node: the RLFA result holds no space tables of this protect list");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("tilfa_node: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t cb = (size_t)o.n_protected * HSPF_TN_COVERAGE_WORDS;
+    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
+    const bool with_nd = node && node->supported && node->nd_kind.size() == pn;
+    // one block: tq_q | tq_p | tq_link | tq_via | tq_metric | tq_count | tn_p | tn_q | tn_link | tn_via | tn_metric | tn_set | tn_coverage | tn_kind |
+    // space_flags | alt_flags | nd_kind
+    const size_t words = pm * 5 + ps + pn * 6 + cb, total = words * 4 + pn + sp + (with_alt ? pn : 0) + (with_nd ? pn : 0);
+    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    uint32_t *w = (uint32_t *)blk;
+    hspf_tilfa_node_sel sel{};
+    hspf_tilfa_node_out out{};
+    sel.tq_q = w; w += pm; sel.tq_p = w; w += pm; sel.tq_link = w; w += pm; sel.tq_via = w; w += pm; sel.tq_metric = w; w += pm; sel.tq_count = w; w += ps;
+    out.tn_p = w; w += pn; out.tn_q = w; w += pn; out.tn_link = w; w += pn; out.tn_via = w; w += pn; out.tn_metric = w; w += pn; out.tn_set = w; w += pn;
+    out.tn_coverage = w; w += cb;
+    uint8_t *b = (uint8_t *)w;
+    out.tn_kind = b; b += pn;
+    uint8_t *sf = b; b += sp;
+    uint8_t *alt = with_alt ? b : nullptr;
+    if (with_alt) b += pn;
+    uint8_t *ndk = with_nd ? b : nullptr;
+    bool ok = hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
+              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess) &&
+              (!with_nd || hipMemcpy(ndk, node->nd_kind.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
+    auto fetch = [&](auto &vec, const void *src, size_t count) {
+      vec.resize(count);
+      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
+    };
+    const char *what = "hspf_tilfa_node_select_device: ";
+    int rc = ok ? hspf_tilfa_node_select_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(),
+                                                o.n_protected, lfa_flags, sf, max_pairs, &sel) : HSPF_E_HIP;
+    ok = ok && rc == HSPF_OK;
+    uint32_t *ydist = nullptr;
+    size_t ybytes = 0;
+    if (ok) {
+      fetch(o.tq_q, sel.tq_q, pm); fetch(o.tq_p, sel.tq_p, pm); fetch(o.tq_link, sel.tq_link, pm); fetch(o.tq_via, sel.tq_via, pm);
+      fetch(o.tq_metric, sel.tq_metric, pm); fetch(o.tq_count, sel.tq_count, ps);
+    }
+    if (ok) {
+      for (uint32_t v : o.tq_q) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
+      std::sort(o.y_roots.begin(), o.y_roots.end());
+      o.y_roots.erase(std::unique(o.y_roots.begin(), o.y_roots.end()), o.y_roots.end());
+      const bool none = o.y_roots.empty();
+      if (none) o.y_roots.push_back(HSPF_NO_ROOT);        // one padding row keeps the arguments of the second call valid
+      ybytes = o.y_roots.size() * (size_t)o.n_vertices * 4;
+      ydist = (uint32_t *)pool_->dev(ybytes);
+      if (!none) {
+        what = "hspf_run_device (the q rows): ";
+        hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
+        rc = hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, o.y_roots.data(), (uint32_t)o.y_roots.size(), run_flags, &yres);
+        ok = rc == HSPF_OK;
+      }
+      if (ok) {
+        what = "hspf_tilfa_node_device: ";
+        rc = hspf_tilfa_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, ydist, o.y_roots.data(),
+                                    (uint32_t)o.y_roots.size(), &sel, max_pairs, alt, ndk, &out);
+        ok = rc == HSPF_OK;
+      }
+      if (ok) {
+        fetch(o.tn_kind, out.tn_kind, pn); fetch(o.tn_p, out.tn_p, pn); fetch(o.tn_q, out.tn_q, pn); fetch(o.tn_link, out.tn_link, pn);
+        fetch(o.tn_via, out.tn_via, pn); fetch(o.tn_metric, out.tn_metric, pn); fetch(o.tn_set, out.tn_set, pn); fetch(o.tn_coverage, out.tn_coverage, cb);
       }
     }
     if (ydist) pool_->dev_free(ydist, ybytes);

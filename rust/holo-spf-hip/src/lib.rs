@@ -355,6 +355,39 @@ impl RlfaNode {
     }
 }
 
+/// Two-segment node-protecting repairs of the protected roots of one `Engine::tilfa_node_device` call.  Slots are strided by
+/// `slot_stride` = 64 * mask words per protected root, lists by `max_pairs` per slot.
+pub struct TilfaNode {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub slot_stride: u32,
+    pub max_pairs: u32,
+    pub tq_q: Vec<u32>,
+    pub tq_p: Vec<u32>,
+    pub tq_link: Vec<u32>,
+    pub tq_via: Vec<u32>,
+    pub tq_metric: Vec<u32>,
+    pub tq_count: Vec<u32>,
+    pub y_roots: Vec<u32>,
+    pub tn_kind: Vec<u8>,
+    pub tn_p: Vec<u32>,
+    pub tn_q: Vec<u32>,
+    pub tn_link: Vec<u32>,
+    pub tn_via: Vec<u32>,
+    pub tn_metric: Vec<u32>,
+    pub tn_set: Vec<u32>,
+    pub tn_coverage: Vec<u32>,
+}
+
+impl TilfaNode {
+    /// The two-segment repair that protects destination `d` of protected root `i` against the failure of its primary neighbour:
+    /// (p, via, position of the forced link in p's row, q, cost), `None` unless its class is `HSPF_TN_D_PAIR`.
+    pub fn repair(&self, i: usize, d: u32) -> Option<(u32, u32, u32, u32, u32)> {
+        let k = i * self.n_vertices as usize + d as usize;
+        (self.tn_kind[k] as u32 == sys::HSPF_TN_D_PAIR).then(|| (self.tn_p[k], self.tn_via[k], self.tn_link[k], self.tn_q[k], self.tn_metric[k]))
+    }
+}
+
 /// `hspf_run_device` results left in HBM: input of `routes_device` / `ancestors_device`.
 pub struct DeviceTables<'e> {
     pub n_roots: u32,
@@ -1086,6 +1119,159 @@ impl Engine {
             nd_metric: nd_metric.to_host(cells)?,
             nd_set: nd_set.to_host(cells)?,
             nd_coverage: nd_cov.to_host(np * sys::HSPF_NP_COVERAGE_WORDS as usize)?,
+        })
+    }
+
+    /// `hspf_tilfa_node_select_device`, one `hspf_run_device` over the ascending union of the listed q's, then
+    /// `hspf_tilfa_node_device`: per destination with one primary the cheapest of the `max_pairs` listed pairs — a tunnel to p that
+    /// avoids the primary's neighbour, one forced adjacency p -> q — whose q reaches the destination without that neighbour.  `g`
+    /// is the FORWARD graph; `tables`, `protect`, `lfa`, `rlfa`, `run_flags` as for `rlfa_node_device`; `node`: what
+    /// `rlfa_node_device` returned for the same `protect` (its one-segment repairs stand), or `None`.
+    pub fn tilfa_node_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, run_flags: u32, protect: &[(u32, &LfaCandidates, &[u32])],
+                             ignore_overload: bool, lfa: Option<&Lfa>, rlfa: &Rlfa, node: Option<&RlfaNode>, max_pairs: u32) -> Result<TilfaNode, Error> {
+        let (n, np) = (tables.n_vertices as usize, protect.len());
+        if max_pairs == 0 || max_pairs > sys::HSPF_TILFA_NODE_MAX_PAIRS {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_node_device: max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_node_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let stride = 64 * tables.words as usize;
+        let (slots, cells, m) = (np * stride, np * n, max_pairs as usize);
+        if rlfa.space_flags.len() != slots * n {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_node_device: the RLFA result holds no space tables of this protect list".into() });
+        }
+        let sp_flags = self.device_from(&rlfa.space_flags)?;
+        let alt = match lfa {
+            Some(l) if l.alt_flags.len() == cells => Some(self.device_from(&l.alt_flags)?),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_node_device: the LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let nd = match node {
+            Some(r) if r.nd_kind.len() == cells => Some(self.device_from(&r.nd_kind)?),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_node_device: the RLFA-node result is not of this protect list".into() }),
+            None => None,
+        };
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let tq_q = self.device_alloc(slots * m * 4)?;
+        let tq_p = self.device_alloc(slots * m * 4)?;
+        let tq_link = self.device_alloc(slots * m * 4)?;
+        let tq_via = self.device_alloc(slots * m * 4)?;
+        let tq_metric = self.device_alloc(slots * m * 4)?;
+        let tq_count = self.device_alloc(slots * 4)?;
+        let mut sel = sys::hspf_tilfa_node_sel {
+            tq_q: tq_q.p as *mut u32,
+            tq_p: tq_p.p as *mut u32,
+            tq_link: tq_link.p as *mut u32,
+            tq_via: tq_via.p as *mut u32,
+            tq_metric: tq_metric.p as *mut u32,
+            tq_count: tq_count.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_tilfa_node_select_device(
+                self.ctx,
+                g.g,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                lfa_flags,
+                sp_flags.p as *const u8,
+                max_pairs,
+                &mut sel,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let qs: Vec<u32> = tq_q.to_host(slots * m)?;
+        let mut y_roots: Vec<u32> = qs.iter().copied().filter(|&v| v != sys::HSPF_NO_ROOT).collect();
+        y_roots.sort_unstable();
+        y_roots.dedup();
+        if y_roots.is_empty() {
+            y_roots.push(sys::HSPF_NO_ROOT); // one padding row keeps the arguments of the second call valid
+        }
+        let y = self.run_device(g, &y_roots, run_flags)?;
+        let tn_kind = self.device_alloc(cells)?;
+        let tn_p = self.device_alloc(cells * 4)?;
+        let tn_q = self.device_alloc(cells * 4)?;
+        let tn_link = self.device_alloc(cells * 4)?;
+        let tn_via = self.device_alloc(cells * 4)?;
+        let tn_metric = self.device_alloc(cells * 4)?;
+        let tn_set = self.device_alloc(cells * 4)?;
+        let tn_cov = self.device_alloc(np * sys::HSPF_TN_COVERAGE_WORDS as usize * 4)?;
+        let mut out = sys::hspf_tilfa_node_out {
+            tn_kind: tn_kind.p as *mut u8,
+            tn_p: tn_p.p as *mut u32,
+            tn_q: tn_q.p as *mut u32,
+            tn_link: tn_link.p as *mut u32,
+            tn_via: tn_via.p as *mut u32,
+            tn_metric: tn_metric.p as *mut u32,
+            tn_set: tn_set.p as *mut u32,
+            tn_coverage: tn_cov.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_tilfa_node_device(
+                self.ctx,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                y.dist.p as *const u32,
+                y_roots.as_ptr(),
+                y_roots.len() as u32,
+                &sel,
+                max_pairs,
+                alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
+                nd.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(TilfaNode {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            slot_stride: stride as u32,
+            max_pairs,
+            tq_q: qs,
+            tq_p: tq_p.to_host(slots * m)?,
+            tq_link: tq_link.to_host(slots * m)?,
+            tq_via: tq_via.to_host(slots * m)?,
+            tq_metric: tq_metric.to_host(slots * m)?,
+            tq_count: tq_count.to_host(slots)?,
+            y_roots,
+            tn_kind: tn_kind.to_host(cells)?,
+            tn_p: tn_p.to_host(cells)?,
+            tn_q: tn_q.to_host(cells)?,
+            tn_link: tn_link.to_host(cells)?,
+            tn_via: tn_via.to_host(cells)?,
+            tn_metric: tn_metric.to_host(cells)?,
+            tn_set: tn_set.to_host(cells)?,
+            tn_coverage: tn_cov.to_host(np * sys::HSPF_TN_COVERAGE_WORDS as usize)?,
         })
     }
 
