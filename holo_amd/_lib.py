@@ -123,6 +123,12 @@ class HspfTilfaNodeOut(ctypes.Structure):
                 ("tn_via", ctypes.c_void_p), ("tn_metric", ctypes.c_void_p), ("tn_set", ctypes.c_void_p), ("tn_coverage", ctypes.c_void_p)]
 
 
+class HspfBackupNodeOut(ctypes.Structure):
+    _fields_ = [("bn_kind", ctypes.c_void_p), ("bn_primary", ctypes.c_void_p), ("bn_p", ctypes.c_void_p), ("bn_q", ctypes.c_void_p),
+                ("bn_link", ctypes.c_void_p), ("bn_via", ctypes.c_void_p), ("bn_metric", ctypes.c_void_p), ("bn_set_pq", ctypes.c_void_p),
+                ("bn_set_pair", ctypes.c_void_p), ("bn_coverage", ctypes.c_void_p)]
+
+
 class HspfMultiConfig(ctypes.Structure):
     _fields_ = [("n_local", ctypes.c_uint32), ("device_ordinals", ctypes.POINTER(ctypes.c_int)),
                 ("world", ctypes.c_uint32), ("first_rank", ctypes.c_uint32), ("unique_id", u8p)]
@@ -243,6 +249,13 @@ SYMBOLS = [
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
                                               ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.POINTER(HspfTilfaNodeSel), ctypes.c_uint32,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfTilfaNodeOut)]),
+    # per-prefix node-protecting backups
+    ("hspf_routes_backup_node_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                                      ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes), ctypes.c_void_p, u32p,
+                                                      ctypes.c_uint32, ctypes.POINTER(HspfRlfaNodeSel), ctypes.c_uint32,
+                                                      ctypes.POINTER(HspfTilfaNodeSel), ctypes.c_uint32, ctypes.POINTER(HspfBackupOut),
+                                                      ctypes.POINTER(HspfBackupNodeOut)]),
     # several GPUs
     ("hspf_multi_unique_id", ctypes.c_int, [u8p]),
     ("hspf_multi_init", ctypes.c_int, [ctypes.POINTER(HspfMultiConfig), ctypes.POINTER(ctypes.c_void_p)]),

@@ -1,6 +1,6 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
 // hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
-// hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
+// hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, hspf_routes_backup_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
 // Included by spf_capi.hip (one TU).
 //
 // The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
@@ -16,6 +16,7 @@
 #include "spf_backup.hip.h"
 #include "spf_rlfa_node.hip.h"
 #include "spf_tilfa_node.hip.h"
+#include "spf_backup_node.hip.h"
 
 namespace {
 
@@ -752,6 +753,91 @@ int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, 
     hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, m);
     hipLaunchKernelGGL(k_tn_dest, dim3((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
     return frr_finish(ctx, "k_tn_dest");
+  });
+}
+
+// ---- per-prefix node-protecting backups (include/holo_spf_hip.h "per-prefix node-protecting backups on device"; kernel:
+// spf_backup_node.hip.h) ----
+static_assert(BN_CW == HSPF_BN_COVERAGE_WORDS, "the kernel's count width is the header's");
+static_assert(BN_LFA == HSPF_BN_LFA && BN_PQ == HSPF_BN_PQ && BN_LAST_HOP == HSPF_BN_LAST_HOP && BN_NONE == HSPF_BN_NONE && BN_PAIR == HSPF_BN_PAIR &&
+              BN_PAIR < BN_CW && BN_BK_LFA == HSPF_BK_LFA && BN_NODE_PROTECT == HSPF_LFA_NODE_PROTECT, "the kernel's kinds and bits are the header's");
+
+int hspf_routes_backup_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                   const hspf_lfa_protect *prot, uint32_t n_prot,
+                                   const hspf_prefix_table *t, const hspf_routes *routes_dev,
+                                   const uint32_t *ydist_dev, const uint32_t *y_roots, uint32_t n_yrows,
+                                   const hspf_rlfa_node_sel *rn_sel_dev, uint32_t max_pq,
+                                   const hspf_tilfa_node_sel *tn_sel_dev, uint32_t max_pairs,
+                                   const hspf_backup_out *bk_in_dev, hspf_backup_node_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_routes_backup_node_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
+    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    if (!out_dev->bn_kind || !out_dev->bn_primary || !out_dev->bn_p || !out_dev->bn_q || !out_dev->bn_link || !out_dev->bn_via || !out_dev->bn_metric ||
+        !out_dev->bn_coverage)
+      return bad("NULL bn_kind / bn_primary / bn_p / bn_q / bn_link / bn_via / bn_metric / bn_coverage");
+    if (!ydist_dev || !y_roots) return bad("NULL ydist or y_roots pointer");
+    if (!rn_sel_dev && !tn_sel_dev) return bad("NULL rn_sel_dev and tn_sel_dev (at least one list is required)");
+    if (rn_sel_dev) {
+      if (!rn_sel_dev->nq_node || !rn_sel_dev->nq_via || !rn_sel_dev->nq_metric || !rn_sel_dev->nq_count)
+        return bad("NULL nq_node / nq_via / nq_metric / nq_count in rn_sel_dev");
+      if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) return bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
+    }
+    if (tn_sel_dev) {
+      if (!tn_sel_dev->tq_q || !tn_sel_dev->tq_p || !tn_sel_dev->tq_link || !tn_sel_dev->tq_via || !tn_sel_dev->tq_metric || !tn_sel_dev->tq_count)
+        return bad("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count in tn_sel_dev");
+      if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) return bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
+    }
+    if (bk_in_dev && (!bk_in_dev->bk_kind || !bk_in_dev->bk_flags)) return bad("NULL bk_kind / bk_flags in bk_in_dev");
+    if (n_yrows == 0) return bad("n_yrows is 0");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
+    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
+    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    for (uint32_t i = 0; i < n_yrows; ++i)
+      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n_vertices) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
+    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    hipStream_t s = ctx->stream;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
+        (rc = ensure(ctx, ctx->rnode_map, ((size_t)n_vertices + n_yrows) * 4, false))) {
+      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bn_coverage, 0, (size_t)n_prot * HSPF_BN_COVERAGE_WORDS * 4, s));
+    if (!t->n_prefixes) {                               // nothing to launch
+      HIPCHK(ctx, hipStreamSynchronize(s));
+      return HSPF_OK;
+    }
+    uint32_t *ymap = (uint32_t *)ctx->rnode_map.p, *yroots = ymap + n_vertices;
+    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n_vertices * 4, s));
+    HIPCHK(ctx, hipMemcpyAsync(yroots, y_roots, (size_t)n_yrows * 4, hipMemcpyHostToDevice, s));      // (the caller's: it lives through the call)
+    RnodeDestArgs m{};                                  // k_rlfa_nmap reads n, the root list and the map
+    m.n = n_vertices; m.yroots = yroots; m.n_yrows = n_yrows; m.ymap = ymap;
+    BackupNodeArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.stride = 64u * n_mask_words; a.n_pfx = t->n_prefixes;
+    a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u; a.max_pq = rn_sel_dev ? max_pq : 0u; a.max_pairs = tn_sel_dev ? max_pairs : 0u;
+    a.dist = dist_dev; a.flags = flags_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p;
+    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
+    a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
+    a.ydist = ydist_dev; a.ymap = ymap;
+    if (rn_sel_dev) { a.nq_node = rn_sel_dev->nq_node; a.nq_via = rn_sel_dev->nq_via; a.nq_metric = rn_sel_dev->nq_metric; a.nq_count = rn_sel_dev->nq_count; }
+    if (tn_sel_dev) {
+      a.tq_q = tn_sel_dev->tq_q; a.tq_p = tn_sel_dev->tq_p; a.tq_link = tn_sel_dev->tq_link; a.tq_via = tn_sel_dev->tq_via;
+      a.tq_metric = tn_sel_dev->tq_metric; a.tq_count = tn_sel_dev->tq_count;
+    }
+    if (bk_in_dev) { a.bk_kind_in = bk_in_dev->bk_kind; a.bk_flags_in = bk_in_dev->bk_flags; }
+    a.bn_kind = out_dev->bn_kind; a.bn_primary = out_dev->bn_primary; a.bn_p = out_dev->bn_p; a.bn_q = out_dev->bn_q; a.bn_link = out_dev->bn_link;
+    a.bn_via = out_dev->bn_via; a.bn_metric = out_dev->bn_metric; a.bn_set_pq = out_dev->bn_set_pq; a.bn_set_pair = out_dev->bn_set_pair;
+    a.bn_cov = out_dev->bn_coverage;
+    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, m);
+    hipLaunchKernelGGL(k_backup_node, dim3((t->n_prefixes + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_backup_node");
   });
 }
 

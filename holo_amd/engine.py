@@ -63,6 +63,8 @@ NP_COVERAGE_WORDS = 5
 TILFA_NODE_MAX_PAIRS = 32       # HSPF_TILFA_NODE_MAX_PAIRS
 TN_D_LFA, TN_D_PQ, TN_D_LAST_HOP, TN_D_NONE, TN_D_PAIR = 1, 2, 3, 4, 5      # HSPF_TN_D_* (tn_kind)
 TN_COVERAGE_WORDS = 6
+BN_LFA, BN_PQ, BN_LAST_HOP, BN_NONE, BN_PAIR = 1, 2, 3, 4, 5                # HSPF_BN_* (bn_kind)
+BN_COVERAGE_WORDS = 6
 
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
@@ -346,6 +348,17 @@ class BackupRoutes:
     bk_node_mask: np.ndarray  # [1, P, W] u64
     bk_coverage: np.ndarray   # [1, 7] u32; [1, 9] with lan_protect
     tilfa: Optional["TilfaResult"] = None      # the per-slot repairs bk_primary indexes (remote=True)
+    # node_protect=True (hspf_routes_backup_node_device), None otherwise:
+    bn_kind: Optional[np.ndarray] = None       # [1, P] u8  BN_* per prefix with exactly one primary, 0 elsewhere
+    bn_primary: Optional[np.ndarray] = None    # [1, P] u32 the one primary slot for BN_LFA .. BN_PAIR, LFA_NO_SLOT otherwise
+    bn_p: Optional[np.ndarray] = None          # [1, P] u32 BN_PQ: the PQ node; BN_PAIR: the node the forced adjacency starts at
+    bn_q: Optional[np.ndarray] = None          # [1, P] u32 BN_PQ: == bn_p; BN_PAIR: the router the adjacency enters
+    bn_link: Optional[np.ndarray] = None       # [1, P] u32 BN_PAIR: position of the link in bn_p's row, LFA_NO_SLOT otherwise
+    bn_via: Optional[np.ndarray] = None        # [1, P] u32 RLFA_VIA_SELF or a slot, LFA_NO_SLOT: none
+    bn_metric: Optional[np.ndarray] = None     # [1, P] u32 the repair's cost to the PREFIX
+    bn_set_pq: Optional[np.ndarray] = None     # [1, P] u32 bit j: one-segment list entry j protects the prefix
+    bn_set_pair: Optional[np.ndarray] = None   # [1, P] u32 bit j: two-segment list entry j protects the prefix
+    bn_coverage: Optional[np.ndarray] = None   # [1, 6] u32
 
 
 def csr_transpose(row_ptr, col, metric, vflags):
@@ -1060,8 +1073,78 @@ class SpfContext:
         u32; every other argument as for routes_backup_device()."""
         self._routes_backup(list(lans), n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr, protect, pfx_ptr, pfx_vertex, pfx_metric, **kw)
 
+    def routes_backup_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
+                                  pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, ydist_ptr: int, y_roots, bn_kind_ptr: int, bn_primary_ptr: int,
+                                  bn_p_ptr: int, bn_q_ptr: int, bn_link_ptr: int, bn_via_ptr: int, bn_metric_ptr: int, bn_coverage_ptr: int,
+                                  bn_set_pq_ptr: int = 0, bn_set_pair_ptr: int = 0, rn_sel: Optional[tuple] = None, max_pq: int = 0,
+                                  tn_sel: Optional[tuple] = None, max_pairs: int = 0, bk_in: Optional[tuple] = None, flags: int = 0) -> None:
+        """hspf_routes_backup_node_device(): per (protected root, prefix) with one primary, the cheapest listed PQ node — or, where
+        none protects, the cheapest listed pair — that reaches the PREFIX without the primary's neighbour.  `protect`, the prefix
+        table and `routes` as for routes_backup_device(); ydist_ptr: `dist` [len(y_roots)][n] of a forward run_device() of `y_roots`
+        (host array; NO_ROOT entries are skipped); rn_sel = the four pointers of rlfa_node_select_device() with max_pq, tn_sel = the
+        six of tilfa_node_select_device() with max_pairs (at least one of the two); bk_in = (bk_kind_ptr, bk_flags_ptr) of
+        routes_backup_device(), or None.  The two set pointers may be 0."""
+        name = "routes_backup_node_device"
+        src = (pfx_ptr, pfx_vertex, pfx_metric)
+        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
+        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
+        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
+        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
+            raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
+        arr, keep = self._protect_array(protect, name)
+        yr = np.ascontiguousarray(y_roots, np.uint32)
+        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags, None, None, None, None)
+        r = L.HspfRoutes(*(x or None for x in routes))
+        rn = None if rn_sel is None else L.HspfRlfaNodeSel(*(x or None for x in rn_sel))
+        tn = None if tn_sel is None else L.HspfTilfaNodeSel(*(x or None for x in tn_sel))
+        bk = None if bk_in is None else L.HspfBackupOut(bk_in[0] or None, None, None, None, bk_in[1] or None, None, None, None)
+        out = L.HspfBackupNodeOut(bn_kind_ptr or None, bn_primary_ptr or None, bn_p_ptr or None, bn_q_ptr or None, bn_link_ptr or None,
+                                  bn_via_ptr or None, bn_metric_ptr or None, bn_set_pq_ptr or None, bn_set_pair_ptr or None, bn_coverage_ptr or None)
+        ref = lambda x: None if x is None else ctypes.byref(x)      # noqa: E731
+        rc = self.lib.hspf_routes_backup_node_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
+                                                     mask_ptr or None, arr, len(protect), ctypes.byref(t), ctypes.byref(r), ydist_ptr or None,
+                                                     _u32(yr) if len(yr) else None, len(yr), ref(rn), max_pq, ref(tn), max_pairs, ref(bk),
+                                                     ctypes.byref(out))
+        del keep
+        self._check_rc("hspf_" + name, rc)
+
+    def _backup_node_tail(self, graph: SpfGraph, run_flags: int, lfa_flags: int, backup, dev, protect, R: int, W: int, max_pq: int, max_pairs: int):
+        """backup_routes(node_protect=True) while the tables, the space_flags, the routes and bk_* are on the device: the two select
+        calls, ONE run_device() over the ascending union of the listed PQ nodes and q's, routes_backup_node_device().  Returns the
+        bn_* arrays on the host."""
+        n, S, NP = graph.n, 64 * W, len(backup[0]) - 1
+        tables = (dev["dist"], dev["flags"], dev["mask"])
+        rn = {k: np.empty((1, S, max_pq), np.uint32) for k in ("nq_node", "nq_via", "nq_metric")}
+        rn["nq_count"] = np.empty((1, S), np.uint32)
+        tn = {k: np.empty((1, S, max_pairs), np.uint32) for k in ("tq_q", "tq_p", "tq_link", "tq_via", "tq_metric")}
+        tn["tq_count"] = np.empty((1, S), np.uint32)
+        bn = dict(bn_kind=np.empty((1, NP), np.uint8),
+                  **{k: np.empty((1, NP), np.uint32) for k in ("bn_primary", "bn_p", "bn_q", "bn_link", "bn_via", "bn_metric", "bn_set_pq", "bn_set_pair")},
+                  bn_coverage=np.empty((1, BN_COVERAGE_WORDS), np.uint32))
+        with self._dev_buffers({k: max(a.nbytes, 8) for k, a in dict(rn, **tn, **bn).items()}) as ndev:
+            self.rlfa_node_select_device(n, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pq=max_pq, lfa_flags=lfa_flags,
+                                         **{k + "_ptr": ndev[k] for k in rn})
+            self.tilfa_node_select_device(graph, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pairs=max_pairs, lfa_flags=lfa_flags,
+                                          **{k + "_ptr": ndev[k] for k in tn})
+            self._fetch(dict(nq_node=rn["nq_node"], tq_q=tn["tq_q"]), ndev)
+            listed = np.concatenate([rn["nq_node"].ravel(), tn["tq_q"].ravel()])
+            y_roots = np.unique(listed[listed != NO_ROOT]).astype(np.uint32)
+            if len(y_roots) == 0:                       # no list holds a node: one padding row keeps the call's arguments valid
+                y_roots = np.array([NO_ROOT], np.uint32)
+            with self._dev_buffers(dict(ydist=4 * len(y_roots) * n)) as ydev:
+                if y_roots[0] != NO_ROOT:
+                    self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
+                self.routes_backup_node_device(n, R, W, *tables, protect, backup[0], backup[1], backup[2],
+                                               routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]), ydist_ptr=ydev["ydist"],
+                                               y_roots=y_roots, rn_sel=tuple(ndev[k] for k in rn), max_pq=max_pq, tn_sel=tuple(ndev[k] for k in tn),
+                                               max_pairs=max_pairs, bk_in=(dev["bk_kind"], dev["bk_flags"]), flags=backup[3] | PFX_RESIDENT,
+                                               **{k + "_ptr": ndev[k] for k in bn})
+                self._fetch(bn, ndev)
+        return bn
+
     def backup_routes(self, graph: SpfGraph, root: int, prefix_table, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False,
-                      remote: bool = True, lan_protect: bool = False, lan_repairs: bool = False) -> BackupRoutes:
+                      remote: bool = True, lan_protect: bool = False, lan_repairs: bool = False, node_protect: bool = False, max_pq: int = 16,
+                      max_pairs: int = 16) -> BackupRoutes:
         """The routes of one root with their backups, start to finish: run_device() of [root] + its distinct neighbour routers,
         routes_device(), lfa_device() and — with `remote` — rlfa_device() + tilfa_device() (on the transposed graph too unless
         `symmetric`), then routes_backup_device(); only the route and bk_* arrays (and the per-slot repairs) come to the host.
@@ -1070,16 +1153,20 @@ class SpfContext:
         SPTs of the root's LANs, and lfa_lan_device() / routes_backup_lan_device() take the places of the plain calls (bk_coverage
         has nine words).  lan_repairs (needs lan_protect and remote, excludes symmetric): rlfa_lan_device() takes rlfa_device()'s
         place, so the per-link repairs avoid the primaries' LANs, and a LAN primary without an alternate takes its repair
-        (LFA_LAN_SAFE_REPAIRS) instead of BK_NONE."""
+        (LFA_LAN_SAFE_REPAIRS) instead of BK_NONE.  node_protect (needs remote, excludes lan_protect): the chain goes on with
+        rlfa_node_select_device(max_pq) and tilfa_node_select_device(max_pairs), ONE run_device() over the ascending union of the
+        listed nodes, and routes_backup_node_device() with the bk_kind / bk_flags just written; the bn_* fields are filled."""
         if lan_repairs and (not lan_protect or not remote or symmetric):
             raise ValueError("backup_routes: lan_repairs needs lan_protect=True, remote=True and symmetric=False")
+        if node_protect and (not remote or lan_protect):
+            raise ValueError("backup_routes: node_protect needs remote=True and lan_protect=False")
         if isinstance(prefix_table, (tuple, list)):
             tab = tuple(prefix_table) + ((0,) if len(prefix_table) == 3 else ())
         else:
             tab = (prefix_table.pfx_ptr, prefix_table.pfx_vertex, prefix_table.pfx_metric, int(getattr(prefix_table, "flags", 0)))
         tab = tuple(np.ascontiguousarray(a, np.uint32) for a in tab[:3]) + (int(tab[3]) & ~PFX_RESIDENT,)
         return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab, lan_protect=lan_protect,
-                          lan_spaces=lan_repairs)
+                          lan_spaces=lan_repairs, node=(int(max_pq), int(max_pairs)) if node_protect else None)
 
     def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False,
              lan_protect: bool = False):
@@ -1098,10 +1185,11 @@ class SpfContext:
         return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True, lan_protect=lan_protect, lan_spaces=lan_protect)
 
     def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None,
-              lan_protect: bool = False, lan_spaces: bool = False):
+              lan_protect: bool = False, lan_spaces: bool = False, node=None):
         """The chain behind rlfa(), tilfa() and backup_routes().  backup: None, or (pfx_ptr, pfx_vertex, pfx_metric, flags) — then
         the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`).  lan_spaces
-        (with lan_protect): rlfa_lan_device() instead of rlfa_device(), and LFA_LAN_SAFE_REPAIRS for the backups."""
+        (with lan_protect): rlfa_lan_device() instead of rlfa_device(), and LFA_LAN_SAFE_REPAIRS for the backups.  node (with backup):
+        None, or (max_pq, max_pairs) of backup_routes(node_protect=True) — then _backup_node_tail() runs on the same rows."""
         if lan_spaces and (not lan_protect or symmetric):
             raise ValueError("the LAN-safe remote calls need lan_protect and the transposed run (symmetric=False)")
         plan = self._frr_plan(graph, root, lan_protect)
@@ -1169,10 +1257,11 @@ class SpfContext:
                                     tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None,
                                     flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_LAN_SAFE_REPAIRS if lan_spaces else 0),
                                     **{k + "_ptr": dev[k] for k in bk_names[3:]})
+            bn = self._backup_node_tail(graph, run_flags, lfa_flags, backup, dev, protect, R, W, *node) if backup is not None and node else {}
             self._fetch(host, dev)
             if backup is not None:
                 return BackupRoutes(cand, *(host[k] for k in bk_names),
-                                    tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None)
+                                    tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None, **bn)
             lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"], lan=plan.lan)
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])

@@ -1041,7 +1041,7 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
  *
  * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (the other primaries
  * are the backups; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
- * td_kind); node-protecting remote repairs per prefix (per destination vertex: hspf_rlfa_node_device, below).  Loop-freeness with respect to a LAN pseudonode is not checked by THIS
+ * td_kind; node-protecting remote repairs per prefix are hspf_routes_backup_node_device's, below).  Loop-freeness with respect to a LAN pseudonode is not checked by THIS
  * call: hspf_routes_backup_lan_device ("broadcast-link protection", above) adds it.  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
 #define HSPF_BK_NO_ROUTE       0u
 #define HSPF_BK_LOCAL          1u
@@ -1124,7 +1124,7 @@ int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n
  * Where no listed PQ node protects a destination (HSPF_NP_D_NONE), a forced adjacency after the tunnel may: the two-segment
  * node-protecting repairs of hspf_tilfa_node_select_device / hspf_tilfa_node_device, below.
  * OUT OF SCOPE: LAN pseudonodes as the protected
- * node (the failure of every router behind the primary's LAN); per-prefix node-protecting remote repairs; SRLGs. */
+ * node (the failure of every router behind the primary's LAN); SRLGs.  Per prefix: hspf_routes_backup_node_device, below. */
 #define HSPF_RLFA_NODE_MAX_PQ   32u
 #define HSPF_NP_D_LFA           1u             /* nd_kind */
 #define HSPF_NP_D_PQ            2u
@@ -1215,8 +1215,8 @@ int hspf_rlfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, u
  *
  * OUT OF SCOPE: LAN pseudonodes as the protected node; LAN-safe release paths (the NP / NXP release paths are derived against E
  * only — the limitation of hspf_rlfa_node_select_device — so on the tables of hspf_rlfa_lan_device the tunnel may still cross the
- * slot's pseudonode); forced adjacencies across a pseudonode (q must be a router in p's own row); per-prefix node-protecting
- * repairs; segment lists longer than two; SRLGs. */
+ * slot's pseudonode); forced adjacencies across a pseudonode (q must be a router in p's own row); segment
+ * lists longer than two; SRLGs.  Per prefix: hspf_routes_backup_node_device, below. */
 #define HSPF_TILFA_NODE_MAX_PAIRS 32u
 #define HSPF_TN_D_LFA             1u           /* tn_kind */
 #define HSPF_TN_D_PQ              2u
@@ -1252,6 +1252,97 @@ int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, 
                            const uint32_t *ydist_dev, const uint32_t *y_roots /* HOST */, uint32_t n_yrows,
                            const hspf_tilfa_node_sel *sel_dev, uint32_t max_pairs,
                            const uint8_t *alt_flags_in_dev, const uint8_t *nd_kind_in_dev, hspf_tilfa_node_out *out_dev);
+
+/* ---- per-prefix node-protecting backups on device: new symbol, same ABI number -------------------------------------------------
+ * hspf_rlfa_node_device and hspf_tilfa_node_device protect destination VERTICES; what a RIB installs is per PREFIX, and
+ * hspf_routes_backup_device gives node protection only through the HSPF_LFA_NODE_PROTECT bit of a directly connected alternate (its
+ * remote fallback is the LINK repair of the primary, which need not survive the neighbour's failure).  For a prefix with one
+ * advertiser the per-vertex answer at that advertiser is the prefix's; for a multi-homed prefix it is not: whether a listed node
+ * Y reaches the prefix without the neighbour E is a question about Y's distance to the PREFIX, the minimum over all advertisers.
+ * The sharpest case is an anycast prefix advertised by E itself and by a router behind it: per vertex the destination is E
+ * (HSPF_NP_D_LAST_HOP, nothing to protect), per prefix a PQ node reaches the other advertiser without touching E.
+ * hspf_routes_backup_node_device is that join, per (protected root, prefix).  It takes no graph.
+ *
+ * Inputs.  The forward table set and `prot` are exactly those of hspf_lfa_device.  `table` and routes_dev are those of
+ * hspf_routes_backup_device, under the same flag rules (HSPF_PFX_ORDERED is rejected, HSPF_PFX_RESIDENT shares the one staged
+ * copy, HSPF_PFX_LAST_MIN changes nothing here).  ydist_dev [n_yrows][n_vertices] is `dist` of ONE forward hspf_run_device whose
+ * root list was y_roots (HOST array) — the caller's choice, usually the union of the listed PQ nodes and the listed q's;
+ * HSPF_NO_ROOT entries are skipped, a vertex listed twice may use either row, a listed node without a row is skipped; the vertex
+ * -> row map is built on the device.  rn_sel_dev / max_pq: NULL (no one-segment entries), or what hspf_rlfa_node_select_device
+ * wrote for the same `prot`; tn_sel_dev / max_pairs: NULL (no two-segment entries), or what hspf_tilfa_node_select_device wrote;
+ * at least one of the two.  bk_in_dev: NULL, or the hspf_backup_out hspf_routes_backup_device wrote for the same `prot` and
+ * table; only bk_kind and bk_flags are read.
+ *
+ * Per protected root S and prefix p whose route exists (routes.best_entry != 0xFFFFFFFF) with exactly ONE primary slot e
+ * (popcount of routes.nexthop_mask[p] below n_slots is 1), E = nbr[e]; every sum is evaluated in 64 bits.
+ *   d_E(p)      as in hspf_routes_backup_device, from row nbr_row[e] of the forward set: the minimum over the entries (v, m) of p
+ *               with v HSPF_RF_IN_SPT in that row and d(E, v) != HSPF_DIST_INF of d(E, v) + m, each sum first saturated at
+ *               0xFFFFFFFF under HSPF_PFX_SATURATING
+ *   d_Y(p)      for a listed node Y with a row: the minimum over the entries (v, m) of p of ydist[row(Y)][v] + m; an
+ *               HSPF_DIST_INF entry contributes nothing (the rows are read as hspf_rlfa_node_device reads them: `dist` alone); each
+ *               sum first saturated at 0xFFFFFFFF under HSPF_PFX_SATURATING
+ *   entry j protects p   iff  d_Y(p) < d(Y, E) + d_E(p)  with d(Y, E) = ydist[row(Y)][E]; a missing d_Y(p), a missing d_E(p) or an
+ *               HSPF_DIST_INF d(Y, E) makes it false.  One-segment entries: j < min(nq_count[e], max_pq), Y = nq_node[e][j];
+ *               two-segment entries: j < min(tq_count[e], max_pairs), Y = tq_q[e][j] (the test depends on q alone)
+ *   choice      among the protecting one-segment entries the smallest nq_metric[e][j] + d_Y(p), then the smaller j
+ *               (HSPF_BN_PQ); ONLY when none protects, the same over the two-segment entries with tq_metric[e][j] + d_q(p)
+ *               (HSPF_BN_PAIR): a one-segment repair stands before any pair whatever the cost, as in hspf_tilfa_node_device
+ *   bn_kind u8  0 unless the route exists with exactly one primary; else, in this order: HSPF_BN_LFA bk_in_dev is given, its
+ *               bk_kind is HSPF_BK_LFA and its bk_flags has HSPF_LFA_NODE_PROTECT | HSPF_BN_NONE the slot is no candidate
+ *               (nbr[e] == HSPF_NO_ROOT) | HSPF_BN_PQ | HSPF_BN_PAIR | HSPF_BN_LAST_HOP nothing protects and E's own entry
+ *               (v == E) attains d_E(p): the link repair is all there is | HSPF_BN_NONE.
+ *               The entries are tested BEFORE the last-hop class — deliberately unlike the per-vertex calls: that is what lets an
+ *               anycast prefix on E be protected.  The numbering follows HSPF_TN_D_*.
+ * Outputs (DEVICE pointers, [n_prot][n_prefixes] unless stated; "none" is HSPF_NO_ROOT / HSPF_LFA_NO_SLOT / 0 as elsewhere):
+ *   bn_primary  the one primary slot e for kinds 1 .. 5, HSPF_LFA_NO_SLOT otherwise
+ *   bn_p / bn_q the chosen nodes: HSPF_BN_PQ bn_p == bn_q == the PQ node; HSPF_BN_PAIR tq_p / tq_q of the entry; HSPF_NO_ROOT
+ *               otherwise
+ *   bn_link     HSPF_BN_PAIR: the position of the forced link in p's row (tq_link); HSPF_LFA_NO_SLOT otherwise
+ *   bn_via      nq_via / tq_via of the chosen entry (may be HSPF_RLFA_VIA_SELF); HSPF_LFA_NO_SLOT otherwise
+ *   bn_metric   the chosen sum saturated at 0xFFFFFFFE — here a cost to the PREFIX (bk_metric of a remote repair is not); 0 otherwise
+ *   bn_set_pq / bn_set_pair   u32, optional (NULL skips the table): bit j = entry j of the one- / two-segment list protects p,
+ *               for the prefixes that reach the test (one primary, not HSPF_BN_LFA, the slot a candidate); 0 otherwise.  With
+ *               bn_set_pair given the two-segment entries are tested even when a PQ entry was chosen.
+ *   bn_coverage u32 [n_prot][HSPF_BN_COVERAGE_WORDS], counted on the device: prefixes with exactly one primary, then classes 1 .. 5.
+ * Argument errors — everything hspf_routes_backup_device rejects (without its lfa_flags and tilfa_dev), everything
+ * hspf_rlfa_node_device rejects about the y rows (NULL ydist_dev / y_roots, n_yrows == 0, a y_roots entry >= n_vertices that is not
+ * HSPF_NO_ROOT), both sel pointers NULL, a NULL array in a given sel or in bk_in_dev (bk_kind, bk_flags), max_pq outside
+ * 1 .. HSPF_RLFA_NODE_MAX_PQ with rn_sel_dev given, max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS with tn_sel_dev given (the limit of
+ * a sel that is NULL is not read) — return HSPF_E_INVAL with a text in hspf_last_error that names
+ * hspf_routes_backup_node_device, before anything is launched.  The call stages once, enqueues everything on the context's stream
+ * and synchronises once at the end.
+ *
+ * From bn_* to a next hop with a label stack: INTEGRATION.md §5p.
+ *
+ * OUT OF SCOPE: LAN pseudonodes as the protected node; LAN-safe release paths (the limitation of the two select calls); ECMP routes
+ * (bn_kind 0: the other primaries are the backups); a wave-per-prefix path for prefixes with very many advertisers (one lane walks
+ * one prefix); SRLGs. */
+#define HSPF_BN_LFA            1u             /* bn_kind */
+#define HSPF_BN_PQ             2u
+#define HSPF_BN_LAST_HOP       3u
+#define HSPF_BN_NONE           4u
+#define HSPF_BN_PAIR           5u
+#define HSPF_BN_COVERAGE_WORDS 6u
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint8_t  *bn_kind;             /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_primary;          /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_p;                /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_q;                /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_link;             /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_via;              /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_metric;           /* [n_prot][n_prefixes]                                                       */
+  uint32_t *bn_set_pq;           /* [n_prot][n_prefixes] bit j = one-segment entry j protects; or NULL         */
+  uint32_t *bn_set_pair;         /* [n_prot][n_prefixes] bit j = two-segment entry j protects; or NULL         */
+  uint32_t *bn_coverage;         /* [n_prot][HSPF_BN_COVERAGE_WORDS]                                           */
+} hspf_backup_node_out;
+int hspf_routes_backup_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                   const hspf_lfa_protect *prot, uint32_t n_prot,
+                                   const hspf_prefix_table *table, const hspf_routes *routes_dev,
+                                   const uint32_t *ydist_dev, const uint32_t *y_roots /* HOST */, uint32_t n_yrows,
+                                   const hspf_rlfa_node_sel *rn_sel_dev, uint32_t max_pq,
+                                   const hspf_tilfa_node_sel *tn_sel_dev, uint32_t max_pairs,
+                                   const hspf_backup_out *bk_in_dev, hspf_backup_node_out *out_dev);
 
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root

@@ -539,6 +539,20 @@ class Engine {
                                                  (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_lan_device (") + hspf_last_error(ctx_) + ")");
   }
+  // hspf_routes_backup_node_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the
+  // routes hspf_routes_device wrote for it, ydist_dev the dist of a forward run of y_roots (host list: the caller's choice among the
+  // listed nodes), rn_sel_dev / tn_sel_dev what the two select calls wrote with max_pq / max_pairs (nullptr: no such entries; at
+  // least one), bk_in_dev what routes_backup_device wrote (nullptr: node-protecting alternates are not looked at).
+  void routes_backup_node_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                                 const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const hspf_prefix_table &table,
+                                 const hspf_routes &routes_dev, const uint32_t *ydist_dev, const std::vector<uint32_t> &y_roots,
+                                 const hspf_rlfa_node_sel *rn_sel_dev, uint32_t max_pq, const hspf_tilfa_node_sel *tn_sel_dev, uint32_t max_pairs,
+                                 const hspf_backup_out *bk_in_dev, hspf_backup_node_out out_dev) {
+    const int rc = hspf_routes_backup_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                                  (uint32_t)protect.size(), &table, &routes_dev, ydist_dev, y_roots.data(), (uint32_t)y_roots.size(),
+                                                  rn_sel_dev, max_pq, tn_sel_dev, max_pairs, bk_in_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_node_device (") + hspf_last_error(ctx_) + ")");
+  }
   // One root start to finish: the chain of tilfa() (of lfa() alone without `remote`), hspf_routes_device for the root's row and
   // hspf_routes_backup_device, everything kept on the device in between.  table_flags: HSPF_PFX_SATURATING / HSPF_PFX_LAST_MIN.
   BackupRoutes backup_routes(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,

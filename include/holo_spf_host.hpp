@@ -185,9 +185,30 @@ struct BackupOut {
   std::vector<uint64_t> bk_cand_mask, bk_node_mask;         // [n_protected][n_prefixes][mask_words]
   std::vector<uint32_t> bk_coverage;                        // [n_protected][HSPF_BK_COVERAGE_WORDS]
 };
+// Per-prefix node-protecting backups (hspf_routes_backup_node_device) of the same protected roots over the prefix table of a
+// DeviceRoutes: per (protected root, prefix) with one primary the kind (HSPF_BN_*), the primary slot and the chosen repair.
+// supported == false: no such call.
+struct BackupNodeOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_prefixes = 0;
+  std::vector<uint32_t> y_roots;                            // the roots of the rows: the ascending union of both lists
+  std::vector<uint8_t> bn_kind;                             // [n_protected][n_prefixes] HSPF_BN_*
+  std::vector<uint32_t> bn_primary, bn_p, bn_q, bn_link, bn_via, bn_metric, bn_set_pq, bn_set_pair;
+  std::vector<uint32_t> bn_coverage;                        // [n_protected][HSPF_BN_COVERAGE_WORDS]
+};
 class Engine {
  public:
   virtual ~Engine() = default;
+  // `routes`: what routes_device() wrote for `run` and the prefix table given here again (pfx_* / table_flags: the call reads the
+  // advertisers); `node` / `pairs`: what rlfa_node() / tilfa_node() returned for the same protect list (nullptr: no such entries; at
+  // least one); `backup`: what backup_routes() returned (only bk_kind and bk_flags are read), or nullptr.  The rows of the listed
+  // nodes are run on `gr` with `run_flags`.  The default: not supported.
+  virtual BackupNodeOut backup_routes_node(Graph &, DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<uint32_t> & /*pfx_ptr*/,
+                                           const std::vector<uint32_t> & /*pfx_vertex*/, const std::vector<uint32_t> & /*pfx_metric*/,
+                                           uint32_t /*table_flags*/, const std::vector<LfaProtect> &, uint32_t /*run_flags*/,
+                                           const RlfaNodeOut * /*node*/, const TilfaNodeOut * /*pairs*/, const BackupOut * /*backup*/) {
+    return BackupNodeOut{};
+  }
   // `routes`: what routes_device() wrote for `run` and the prefix table.  The default: not supported.
   virtual BackupOut backup_routes(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                                   const TilfaOut * /*tilfa*/) { return BackupOut{}; }
@@ -1072,6 +1093,103 @@ class HipEngine : public Engine {
       }
     }
     if (ydist) pool_->dev_free(ydist, ybytes);
+    pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    return o;
+  }
+  BackupNodeOut backup_routes_node(Graph &gr, DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr,
+                                   const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric, uint32_t table_flags,
+                                   const std::vector<LfaProtect> &protect, uint32_t run_flags, const RlfaNodeOut *node, const TilfaNodeOut *pairs,
+                                   const BackupOut *backup) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rt = static_cast<HipDeviceRoutes &>(routes);
+    BackupNodeOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes;
+    if (protect.empty()) return o;
+    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
+      throw std::runtime_error("backup_routes_node: the routes are not of this run and prefix table");
+    const size_t ps = (size_t)o.n_protected * 64u * r.mask_words, pp = (size_t)o.n_protected * o.n_prefixes;
+    const bool with_rn = node && node->supported, with_tn = pairs && pairs->supported, with_bk = backup && backup->supported;
+    if (!with_rn && !with_tn) throw std::runtime_error("backup_routes_node: at least one of the two lists is required");
+    const size_t pq = with_rn ? ps * node->max_pq : 0, pm = with_tn ? ps * pairs->max_pairs : 0;
+    if (with_rn && (node->nq_count.size() != ps || node->nq_node.size() != pq || node->nq_via.size() != pq || node->nq_metric.size() != pq))
+      throw std::runtime_error("backup_routes_node: the RLFA-node result is not of this protect list");
+    if (with_tn && (pairs->tq_count.size() != ps || pairs->tq_q.size() != pm || pairs->tq_p.size() != pm || pairs->tq_link.size() != pm ||
+                    pairs->tq_via.size() != pm || pairs->tq_metric.size() != pm))
+      throw std::runtime_error("backup_routes_node: the TI-LFA-node result is not of this protect list");
+    if (with_bk && (backup->bk_kind.size() != pp || backup->bk_flags.size() != pp))
+      throw std::runtime_error("backup_routes_node: the backup result is not of this protect list and table");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("backup_routes_node: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    if (with_rn) for (uint32_t v : node->nq_node) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
+    if (with_tn) for (uint32_t v : pairs->tq_q) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
+    std::sort(o.y_roots.begin(), o.y_roots.end());
+    o.y_roots.erase(std::unique(o.y_roots.begin(), o.y_roots.end()), o.y_roots.end());
+    const bool none = o.y_roots.empty();
+    if (none) o.y_roots.push_back(HSPF_NO_ROOT);          // one padding row keeps the arguments of the call valid
+    const size_t cb = (size_t)o.n_protected * HSPF_BN_COVERAGE_WORDS, yw = o.y_roots.size() * (size_t)r.n_vertices;
+    // one block: the lists (nq_node | nq_via | nq_metric | nq_count | tq_q | tq_p | tq_link | tq_via | tq_metric | tq_count) | bn_primary .. bn_set_pair |
+    // bn_coverage | ydist | bn_kind | bk_kind | bk_flags
+    const size_t words = pq * 3 + (with_rn ? ps : 0) + pm * 5 + (with_tn ? ps : 0) + pp * 8 + cb + yw, total = words * 4 + pp + (with_bk ? 2 * pp : 0);
+    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    uint32_t *w = (uint32_t *)blk;
+    hspf_rlfa_node_sel rn{};
+    hspf_tilfa_node_sel tn{};
+    hspf_backup_node_out out{};
+    bool ok = true;
+    auto put = [&](uint32_t *&dst, const std::vector<uint32_t> &src) {
+      dst = w; w += src.size();
+      ok = ok && (src.empty() || hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    if (with_rn) { put(rn.nq_node, node->nq_node); put(rn.nq_via, node->nq_via); put(rn.nq_metric, node->nq_metric); put(rn.nq_count, node->nq_count); }
+    if (with_tn) {
+      put(tn.tq_q, pairs->tq_q); put(tn.tq_p, pairs->tq_p); put(tn.tq_link, pairs->tq_link); put(tn.tq_via, pairs->tq_via); put(tn.tq_metric, pairs->tq_metric);
+      put(tn.tq_count, pairs->tq_count);
+    }
+    out.bn_primary = w; w += pp; out.bn_p = w; w += pp; out.bn_q = w; w += pp; out.bn_link = w; w += pp; out.bn_via = w; w += pp; out.bn_metric = w; w += pp;
+    out.bn_set_pq = w; w += pp; out.bn_set_pair = w; w += pp; out.bn_coverage = w; w += cb;
+    uint32_t *ydist = w; w += yw;
+    uint8_t *b = (uint8_t *)w;
+    out.bn_kind = b; b += pp;
+    hspf_backup_out bk{};
+    if (with_bk) {
+      bk.bk_kind = b; b += pp; bk.bk_flags = b;
+      ok = ok && (pp == 0 || (hipMemcpy(bk.bk_kind, backup->bk_kind.data(), pp, hipMemcpyHostToDevice) == hipSuccess &&
+                              hipMemcpy(bk.bk_flags, backup->bk_flags.data(), pp, hipMemcpyHostToDevice) == hipSuccess));
+    }
+    const char *what = "hipMemcpy of the lists: ";
+    int rc = ok ? HSPF_OK : HSPF_E_HIP;
+    if (ok && !none) {
+      what = "hspf_run_device (the rows of the listed nodes): ";
+      hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
+      rc = hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, o.y_roots.data(), (uint32_t)o.y_roots.size(), run_flags, &yres);
+      ok = rc == HSPF_OK;
+    }
+    if (ok) {
+      what = "hspf_routes_backup_node_device: ";
+      static const uint32_t zero = 0;
+      const hspf_prefix_table tab{o.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
+                                  pfx_metric.empty() ? &zero : pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT};
+      const hspf_routes ro = rt.raw();
+      rc = hspf_routes_backup_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, &tab, &ro, ydist,
+                                          o.y_roots.data(), (uint32_t)o.y_roots.size(), with_rn ? &rn : nullptr, with_rn ? node->max_pq : 0u,
+                                          with_tn ? &tn : nullptr, with_tn ? pairs->max_pairs : 0u, with_bk ? &bk : nullptr, &out);
+      ok = rc == HSPF_OK;
+    }
+    auto fetch = [&](auto &vec, const void *src, size_t count) {
+      vec.resize(count);
+      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
+    };
+    if (ok) {
+      fetch(o.bn_kind, out.bn_kind, pp); fetch(o.bn_primary, out.bn_primary, pp); fetch(o.bn_p, out.bn_p, pp); fetch(o.bn_q, out.bn_q, pp);
+      fetch(o.bn_link, out.bn_link, pp); fetch(o.bn_via, out.bn_via, pp); fetch(o.bn_metric, out.bn_metric, pp); fetch(o.bn_set_pq, out.bn_set_pq, pp);
+      fetch(o.bn_set_pair, out.bn_set_pair, pp); fetch(o.bn_coverage, out.bn_coverage, cb);
+    }
     pool_->dev_free(blk, total);
     if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
     return o;

@@ -388,6 +388,36 @@ impl TilfaNode {
     }
 }
 
+/// Per-prefix node-protecting backups of the protected roots of one `Engine::routes_backup_node_device` call, `n_prefixes` cells
+/// per protected root.
+pub struct BackupNode {
+    pub n_protected: u32,
+    pub n_prefixes: u32,
+    pub y_roots: Vec<u32>,
+    pub bn_kind: Vec<u8>,
+    pub bn_primary: Vec<u32>,
+    pub bn_p: Vec<u32>,
+    pub bn_q: Vec<u32>,
+    pub bn_link: Vec<u32>,
+    pub bn_via: Vec<u32>,
+    pub bn_metric: Vec<u32>,
+    pub bn_set_pq: Vec<u32>,
+    pub bn_set_pair: Vec<u32>,
+    pub bn_coverage: Vec<u32>,
+}
+
+impl BackupNode {
+    /// The repair that protects prefix `p` of protected root `i` against the failure of its primary neighbour: (tunnel end,
+    /// via, position of the forced link in its row or `None` for a PQ node, q, cost to the prefix); `None` unless its kind is
+    /// `HSPF_BN_PQ` or `HSPF_BN_PAIR`.
+    pub fn repair(&self, i: usize, p: u32) -> Option<(u32, u32, Option<u32>, u32, u32)> {
+        let k = i * self.n_prefixes as usize + p as usize;
+        let kind = self.bn_kind[k] as u32;
+        (kind == sys::HSPF_BN_PQ || kind == sys::HSPF_BN_PAIR)
+            .then(|| (self.bn_p[k], self.bn_via[k], (kind == sys::HSPF_BN_PAIR).then(|| self.bn_link[k]), self.bn_q[k], self.bn_metric[k]))
+    }
+}
+
 /// `hspf_run_device` results left in HBM: input of `routes_device` / `ancestors_device`.
 pub struct DeviceTables<'e> {
     pub n_roots: u32,
@@ -1403,6 +1433,180 @@ impl Engine {
             bk_cand_mask: bk_cand.to_host(cells * w)?,
             bk_node_mask: bk_node.to_host(cells * w)?,
             bk_coverage: bk_cov.to_host(np * cov_words)?,
+        })
+    }
+
+    /// `hspf_routes_backup_node_device`: per (protected root, prefix) with one primary the cheapest listed PQ node of `rlfa_node`
+    /// — or, where none protects, the cheapest listed pair of `tilfa_node` — that reaches the PREFIX without the primary's
+    /// neighbour; one `hspf_run_device` over the ascending union of the listed nodes on the way.  At least one of the two lists;
+    /// `backup`: what `routes_backup_device` returned for the same `protect` and `table` (its node-protecting alternates stand),
+    /// or `None`.  `resident`: the context still holds `table`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn routes_backup_node_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, run_flags: u32, protect: &[(u32, &LfaCandidates, &[u32])],
+                                     table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, rlfa_node: Option<&RlfaNode>,
+                                     tilfa_node: Option<&TilfaNode>, backup: Option<&Backup>) -> Result<BackupNode, Error> {
+        let (np, pf, w) = (protect.len(), table.n_prefixes() as usize, tables.words as usize);
+        let bad = |what: &str| Error { code: sys::HSPF_E_INVAL, detail: format!("routes_backup_node_device: {what}") };
+        if routes.n_prefixes != table.n_prefixes() || routes.words != tables.words {
+            return Err(bad("the routes are not of this table set and table"));
+        }
+        if rlfa_node.is_none() && tilfa_node.is_none() {
+            return Err(bad("at least one of the two lists is required"));
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(bad("the slot arrays of a protected root differ in length"));
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let slots = np * 64 * w;
+        let cells = np * pf;
+        let mut y_roots: Vec<u32> = Vec::new();
+        let rn = match rlfa_node {
+            Some(r) if r.nq_count.len() == slots && r.nq_node.len() == slots * r.max_pq as usize => {
+                y_roots.extend(r.nq_node.iter().copied().filter(|&v| v != sys::HSPF_NO_ROOT));
+                Some((self.device_from(&r.nq_node)?, self.device_from(&r.nq_via)?, self.device_from(&r.nq_metric)?, self.device_from(&r.nq_count)?, r.max_pq))
+            }
+            Some(_) => return Err(bad("the RLFA-node result is not of this protect list")),
+            None => None,
+        };
+        let tn = match tilfa_node {
+            Some(t) if t.tq_count.len() == slots && t.tq_q.len() == slots * t.max_pairs as usize => {
+                y_roots.extend(t.tq_q.iter().copied().filter(|&v| v != sys::HSPF_NO_ROOT));
+                Some((
+                    self.device_from(&t.tq_q)?,
+                    self.device_from(&t.tq_p)?,
+                    self.device_from(&t.tq_link)?,
+                    self.device_from(&t.tq_via)?,
+                    self.device_from(&t.tq_metric)?,
+                    self.device_from(&t.tq_count)?,
+                    t.max_pairs,
+                ))
+            }
+            Some(_) => return Err(bad("the TI-LFA-node result is not of this protect list")),
+            None => None,
+        };
+        let bk = match backup {
+            Some(b) if b.bk_kind.len() == cells && b.bk_flags.len() == cells => Some((self.device_from(&b.bk_kind)?, self.device_from(&b.bk_flags)?)),
+            Some(_) => return Err(bad("the backup result is not of this protect list and table")),
+            None => None,
+        };
+        y_roots.sort_unstable();
+        y_roots.dedup();
+        if y_roots.is_empty() {
+            y_roots.push(sys::HSPF_NO_ROOT); // one padding row keeps the arguments of the call valid
+        }
+        let y = self.run_device(g, &y_roots, run_flags)?;
+        let rn_raw = rn.as_ref().map(|(a, b, c, d, _)| sys::hspf_rlfa_node_sel { nq_node: a.p as *mut u32, nq_via: b.p as *mut u32, nq_metric: c.p as *mut u32, nq_count: d.p as *mut u32 });
+        let tn_raw = tn.as_ref().map(|(a, b, c, d, e, f, _)| sys::hspf_tilfa_node_sel {
+            tq_q: a.p as *mut u32,
+            tq_p: b.p as *mut u32,
+            tq_link: c.p as *mut u32,
+            tq_via: d.p as *mut u32,
+            tq_metric: e.p as *mut u32,
+            tq_count: f.p as *mut u32,
+        });
+        let bk_raw = bk.as_ref().map(|(k, f)| sys::hspf_backup_out {
+            bk_kind: k.p as *mut u8,
+            bk_primary: ptr::null_mut(),
+            bk_slot: ptr::null_mut(),
+            bk_metric: ptr::null_mut(),
+            bk_flags: f.p as *mut u8,
+            bk_cand_mask: ptr::null_mut(),
+            bk_node_mask: ptr::null_mut(),
+            bk_coverage: ptr::null_mut(),
+        });
+        let bn_kind = self.device_alloc(cells)?;
+        let bn_primary = self.device_alloc(cells * 4)?;
+        let bn_p = self.device_alloc(cells * 4)?;
+        let bn_q = self.device_alloc(cells * 4)?;
+        let bn_link = self.device_alloc(cells * 4)?;
+        let bn_via = self.device_alloc(cells * 4)?;
+        let bn_metric = self.device_alloc(cells * 4)?;
+        let bn_set_pq = self.device_alloc(cells * 4)?;
+        let bn_set_pair = self.device_alloc(cells * 4)?;
+        let bn_cov = self.device_alloc(np * sys::HSPF_BN_COVERAGE_WORDS as usize * 4)?;
+        let mut out = sys::hspf_backup_node_out {
+            bn_kind: bn_kind.p as *mut u8,
+            bn_primary: bn_primary.p as *mut u32,
+            bn_p: bn_p.p as *mut u32,
+            bn_q: bn_q.p as *mut u32,
+            bn_link: bn_link.p as *mut u32,
+            bn_via: bn_via.p as *mut u32,
+            bn_metric: bn_metric.p as *mut u32,
+            bn_set_pq: bn_set_pq.p as *mut u32,
+            bn_set_pair: bn_set_pair.p as *mut u32,
+            bn_coverage: bn_cov.p as *mut u32,
+        };
+        let t = sys::hspf_prefix_table {
+            n_prefixes: table.n_prefixes(),
+            n_entries: table.pfx_vertex.len() as u32,
+            pfx_ptr: table.pfx_ptr.as_ptr(),
+            pfx_vertex: table.pfx_vertex.as_ptr(),
+            pfx_metric: table.pfx_metric.as_ptr(),
+            flags: table.flags | if resident { sys::HSPF_PFX_RESIDENT } else { 0 },
+            pfx_origin: ptr::null(),
+            init_exists: ptr::null(),
+            init_metric: ptr::null(),
+            init_origin: ptr::null(),
+        };
+        let r = sys::hspf_routes {
+            best_metric: routes.best_metric.p as *mut u32,
+            best_entry: routes.best_entry.p as *mut u32,
+            nexthop_mask: routes.nexthop_mask.p as *mut u64,
+        };
+        let rc = unsafe {
+            sys::hspf_routes_backup_node_device(
+                self.ctx,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                raw.as_ptr(),
+                np as u32,
+                &t,
+                &r,
+                y.dist.p as *const u32,
+                y_roots.as_ptr(),
+                y_roots.len() as u32,
+                rn_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_rlfa_node_sel),
+                rn.as_ref().map_or(0, |x| x.4),
+                tn_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_node_sel),
+                tn.as_ref().map_or(0, |x| x.6),
+                bk_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_backup_out),
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(BackupNode {
+            n_protected: np as u32,
+            n_prefixes: table.n_prefixes(),
+            y_roots,
+            bn_kind: bn_kind.to_host(cells)?,
+            bn_primary: bn_primary.to_host(cells)?,
+            bn_p: bn_p.to_host(cells)?,
+            bn_q: bn_q.to_host(cells)?,
+            bn_link: bn_link.to_host(cells)?,
+            bn_via: bn_via.to_host(cells)?,
+            bn_metric: bn_metric.to_host(cells)?,
+            bn_set_pq: bn_set_pq.to_host(cells)?,
+            bn_set_pair: bn_set_pair.to_host(cells)?,
+            bn_coverage: bn_cov.to_host(np * sys::HSPF_BN_COVERAGE_WORDS as usize)?,
         })
     }
 
