@@ -82,6 +82,10 @@ class HspfLfaLan(ctypes.Structure):
     _fields_ = [("lan", u32p), ("lan_row", u32p)]
 
 
+class HspfSrlg(ctypes.Structure):
+    _fields_ = [("mem_ptr", u32p), ("tail", u32p), ("pos", u32p), ("head", u32p), ("cost", u32p), ("tail_row", u32p), ("head_row", u32p)]
+
+
 class HspfLfaOut(ctypes.Structure):
     _fields_ = [("alt_slot", ctypes.c_void_p), ("alt_metric", ctypes.c_void_p), ("alt_flags", ctypes.c_void_p),
                 ("cand_mask", ctypes.c_void_p), ("node_mask", ctypes.c_void_p), ("coverage", ctypes.c_void_p)]
@@ -224,6 +228,16 @@ SYMBOLS = [
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect),
                                             ctypes.POINTER(HspfLfaLan), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                             ctypes.POINTER(HspfRlfaOut)]),
+    # SRLG-safe alternates and remote-LFA spaces
+    ("hspf_srlg_members", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, u32p, u32p, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p,
+                                         u32p, u32p, u32p, u32p]),
+    ("hspf_lfa_srlg_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.POINTER(HspfSrlg), ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.POINTER(HspfLfaOut)]),
+    ("hspf_rlfa_srlg_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect),
+                                             ctypes.POINTER(HspfSrlg), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.POINTER(HspfRlfaOut)]),
     # two-segment repair paths (TI-LFA, link protection)
     ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,

@@ -1,6 +1,7 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
 // hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
-// hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, hspf_routes_backup_node_device, and the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device.
+// hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, hspf_routes_backup_node_device, the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device,
+// and the shared-risk calls hspf_srlg_members, hspf_lfa_srlg_device, hspf_rlfa_srlg_device.
 // Included by spf_capi.hip (one TU).
 //
 // The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
@@ -17,6 +18,7 @@
 #include "spf_rlfa_node.hip.h"
 #include "spf_tilfa_node.hip.h"
 #include "spf_backup_node.hip.h"
+#include "spf_srlg.hip.h"
 
 namespace {
 
@@ -167,6 +169,96 @@ LfaArgs frr_gather_lan(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words
     hipLaunchKernelGGL(k_lfa_gather_lan, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a, la);
   }
   return a;
+}
+
+static_assert(SRLG_MAXM == HSPF_SRLG_MAX_MEMBERS && RLFA_SRLG_CW == HSPF_RLFA_SRLG_COUNT_WORDS, "the kernels' member bound and count width are the header's");
+
+// The member columns of an SRLG call, checked: before anything is staged or launched.  Every index a kernel dereferences is held
+// to its bound here.
+int srlg_check(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const hspf_lfa_protect *prot,
+               const hspf_srlg *srlg, uint32_t n_prot) {
+  if (!srlg) return frr_bad(ctx, fn, "NULL srlg pointer");
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const std::string who = "protected root " + std::to_string(i) + ": ";
+    const uint32_t K = prot[i].n_slots;
+    const hspf_srlg &g = srlg[i];
+    if (K > 64ull * n_mask_words) return frr_bad(ctx, fn, who + "n_slots > 64 * n_mask_words");      // (before mem_ptr is read that far)
+    if (!g.mem_ptr) return frr_bad(ctx, fn, who + "NULL mem_ptr");
+    for (uint32_t k = 0; k < K; ++k) {
+      if (g.mem_ptr[k + 1] < g.mem_ptr[k]) return frr_bad(ctx, fn, who + "mem_ptr is not monotone at slot " + std::to_string(k));
+      if (g.mem_ptr[k + 1] - g.mem_ptr[k] > HSPF_SRLG_MAX_MEMBERS) return frr_bad(ctx, fn, who + "slot " + std::to_string(k) + " has more than HSPF_SRLG_MAX_MEMBERS members");
+    }
+    if (g.mem_ptr[K] > g.mem_ptr[0] && (!g.tail || !g.pos || !g.head || !g.cost || !g.tail_row || !g.head_row)) return frr_bad(ctx, fn, who + "NULL member column");
+    for (uint32_t m = g.mem_ptr[0]; m < g.mem_ptr[K]; ++m) {
+      const std::string mem = "member " + std::to_string(m);
+      if (g.tail[m] >= n_vertices || g.head[m] >= n_vertices) return frr_bad(ctx, fn, who + "tail or head of " + mem + " >= n_vertices");
+      if (g.tail_row[m] >= n_rows || g.head_row[m] >= n_rows) return frr_bad(ctx, fn, who + "tail_row or head_row of " + mem + " >= n_rows");
+    }
+  }
+  return HSPF_OK;
+}
+
+// The member block (its layout: spf_srlg.hip.h) copied to ctx->srlg_tab on the context's stream, with ctx->srlg_scal sized for
+// k_srlg_gather.  After srlg_check and lfa_stage.  `stab` is the copy's source: it lives until the caller has synchronised.
+int srlg_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, std::vector<uint32_t> &stab,
+               SrlgArgs *out, size_t *out_max_gather, uint32_t *out_max_nms) {
+  stab.assign((size_t)n_prot * SRLG_HDR_WORDS, 0u);
+  size_t so = 0, max_gather = 0;
+  uint32_t max_nms = 0;
+  struct Mem { uint32_t tail, pos, head, cost, trow, hrow; };
+  std::vector<Mem> dm;                                              // the distinct members, in order of first appearance
+  std::vector<uint32_t> sidx;
+  for (uint32_t i = 0; i < n_prot; ++i) {
+    const uint32_t K = prot[i].n_slots, S = prot[i].root_vertex;
+    const hspf_srlg &g = srlg[i];
+    const size_t to = stab.size();
+    dm.clear(); sidx.clear();
+    std::unordered_map<uint64_t, std::vector<uint32_t>> index;      // (tail, pos) -> the distinct members that carry it
+    stab.resize(to + 2 * (size_t)K + 1, 0u);
+    uint32_t nms = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+      stab[to + k] = (uint32_t)sidx.size();
+      for (uint32_t m = g.mem_ptr[k]; m < g.mem_ptr[k + 1]; ++m) {
+        const Mem x{g.tail[m], g.pos[m], g.head[m], g.cost[m], g.tail_row[m], g.head_row[m]};
+        std::vector<uint32_t> &same = index[((uint64_t)x.tail << 32) | x.pos];
+        uint32_t j = LFA_NONE;
+        for (uint32_t c : same)
+          if (dm[c].head == x.head && dm[c].cost == x.cost && dm[c].trow == x.trow && dm[c].hrow == x.hrow) j = c;
+        if (j == LFA_NONE) { j = (uint32_t)dm.size(); dm.push_back(x); same.push_back(j); }
+        sidx.push_back(j);
+      }
+      if (g.mem_ptr[k + 1] > g.mem_ptr[k] && prot[i].nbr[k] != HSPF_NO_ROOT) stab[to + K + 1 + nms++] = k;
+    }
+    stab[to + K] = (uint32_t)sidx.size();
+    stab.insert(stab.end(), sidx.begin(), sidx.end());
+    const size_t NM = dm.size(), mo = stab.size();
+    stab.resize(mo + 6 * NM);
+    for (size_t j = 0; j < NM; ++j) {
+      stab[mo + j] = dm[j].tail; stab[mo + NM + j] = dm[j].head; stab[mo + 2 * NM + j] = dm[j].cost;
+      stab[mo + 3 * NM + j] = dm[j].trow; stab[mo + 4 * NM + j] = dm[j].hrow; stab[mo + 5 * NM + j] = dm[j].tail == S ? dm[j].pos : LFA_NONE;
+    }
+    const size_t scal = NM * (1 + 2 * (size_t)K);
+    if (stab.size() > (1u << 28) || so + scal > (1u << 28)) { ctx->last_error = std::string(fn) + ": the member tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
+    uint32_t *h = stab.data() + (size_t)i * SRLG_HDR_WORDS;
+    h[0] = (uint32_t)NM; h[1] = (uint32_t)to; h[2] = (uint32_t)so; h[3] = (uint32_t)sidx.size(); h[4] = nms;
+    so += scal;
+    max_gather = std::max(max_gather, scal);
+    max_nms = std::max(max_nms, nms);
+  }
+  int rc;
+  if ((rc = ensure(ctx, ctx->srlg_tab, stab.size() * 4, false))) return rc;
+  if ((rc = ensure(ctx, ctx->srlg_scal, std::max<size_t>(so, 1) * 4, false))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->srlg_tab.p, stab.data(), stab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  out->stab = (const uint32_t *)ctx->srlg_tab.p; out->sscal = (uint32_t *)ctx->srlg_scal.p;
+  *out_max_gather = max_gather; *out_max_nms = max_nms;
+  return HSPF_OK;
+}
+
+// k_srlg_gather on the staged blocks, behind frr_gather
+void srlg_gather(hspf_ctx *ctx, const LfaArgs &a, const SrlgArgs &sa, uint32_t n_prot, size_t max_gather) {
+  if (!max_gather) return;
+  const uint32_t gx = (uint32_t)std::min<size_t>((max_gather + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_srlg_gather, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a, sa);
 }
 
 // The graph's two-way flags, one byte per link in the order of the device's raw CSR, copied to ctx->tilfa_tw on the context's stream
@@ -489,6 +581,161 @@ int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices
                          const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev) {
   return rlfa_call(ctx, "hspf_rlfa_lan_device", true, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, lan, n_prot,
                    lfa_flags, alt_flags_in_dev, out_dev);
+}
+
+// ---- shared-risk link groups (include/holo_spf_hip.h "SRLG-safe alternates and remote-LFA spaces"; kernels: spf_srlg.hip.h) ----
+int hspf_srlg_members(const hspf_csr *csr, uint32_t root, const uint32_t *grp_ptr, const uint32_t *grp, uint32_t cap_slots, uint32_t cap_members,
+                      uint32_t *mem_ptr, uint32_t *tail, uint32_t *pos, uint32_t *head, uint32_t *cost, uint32_t *out_total_slots,
+                      uint32_t *out_total_members) {
+  if (!csr || !csr->row_ptr || !grp_ptr || root >= csr->n_vertices) return HSPF_E_INVAL;
+  const uint32_t n = csr->n_vertices, e = csr->n_edges;
+  if (csr->row_ptr[0] != 0 || csr->row_ptr[n] != e || (e && (!csr->col || !csr->metric))) return HSPF_E_INVAL;
+  for (uint32_t u = 0; u < n; ++u)
+    if (csr->row_ptr[u + 1] < csr->row_ptr[u]) return HSPF_E_INVAL;
+  for (uint32_t l = 0; l < e; ++l)
+    if (grp_ptr[l + 1] < grp_ptr[l]) return HSPF_E_INVAL;
+  if (grp_ptr[e] > grp_ptr[0] && !grp) return HSPF_E_INVAL;
+  std::vector<uint32_t> rl;                                         // root_link of every slot
+  uint32_t total_slots = 0;
+  const int K = lfa_walk(csr, root, &total_slots, [&](uint64_t, uint32_t, uint32_t, uint32_t first, bool, bool) { rl.push_back(first); });
+  if (K < 0) return K;
+  return guarded(nullptr, [&]() -> int {
+    const uint32_t own = csr->row_ptr[root + 1] - csr->row_ptr[root];
+    // per link of the root's row that some slot stands behind: the links that share a group with it, ascending, itself left out
+    std::vector<std::vector<uint32_t>> of_link(own);
+    std::vector<uint8_t> wanted(own, 0), done(own, 0);
+    for (uint32_t f : rl) if (f < own) wanted[f] = 1;
+    std::unordered_map<uint32_t, std::vector<uint32_t>> by_group;   // group id -> its links, ascending (filled on first need)
+    bool filled = false;
+    uint64_t total = 0;
+    for (size_t k = 0; k < rl.size(); ++k) {
+      if (k <= cap_slots && mem_ptr) mem_ptr[k] = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull);      // (entry cap_slots closes slot cap_slots - 1)
+      const uint32_t f = rl[k];
+      if (f >= own) continue;
+      const uint32_t prot_link = csr->row_ptr[root] + f;
+      if (!done[f]) {
+        done[f] = 1;
+        if (grp_ptr[prot_link + 1] > grp_ptr[prot_link]) {
+          if (!filled) {
+            filled = true;
+            for (uint32_t l = 0; l < e; ++l)
+              for (uint32_t x = grp_ptr[l]; x < grp_ptr[l + 1]; ++x) {
+                std::vector<uint32_t> &v = by_group[grp[x]];
+                if (v.empty() || v.back() != l) v.push_back(l);
+              }
+          }
+          std::vector<uint32_t> &m = of_link[f];
+          for (uint32_t x = grp_ptr[prot_link]; x < grp_ptr[prot_link + 1]; ++x) {
+            const std::vector<uint32_t> &v = by_group[grp[x]];
+            m.insert(m.end(), v.begin(), v.end());
+          }
+          std::sort(m.begin(), m.end());
+          m.erase(std::unique(m.begin(), m.end()), m.end());
+          m.erase(std::remove(m.begin(), m.end(), prot_link), m.end());
+        }
+      }
+      for (uint32_t l : of_link[f]) {
+        if (csr->col[l] >= n) return HSPF_E_INVAL;
+        if (total < cap_members) {
+          const uint32_t a = (uint32_t)(std::upper_bound(csr->row_ptr, csr->row_ptr + n + 1, l) - csr->row_ptr) - 1u;      // the row that holds link l
+          if (tail) tail[total] = a;
+          if (pos) pos[total] = l - csr->row_ptr[a];
+          if (head) head[total] = csr->col[l];
+          if (cost) cost[total] = csr->metric[l];
+        }
+        ++total;
+      }
+    }
+    if (total > 0xFFFFFFF0ull) return HSPF_E_INVAL;
+    if (rl.size() <= cap_slots && mem_ptr) mem_ptr[rl.size()] = (uint32_t)total;
+    if (out_total_slots) *out_total_slots = total_slots;
+    if (out_total_members) *out_total_members = (uint32_t)total;
+    return K;
+  });
+}
+
+int hspf_lfa_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                         const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_lfa_srlg_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
+    std::vector<uint32_t> tab, stab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0, max_nms = 0;
+    size_t max_gather = 0;
+    SrlgArgs sa{};
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = srlg_stage(ctx, fn, prot, srlg, n_prot, stab, &sa, &max_gather, &max_nms))) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_SRLG_COVERAGE_WORDS * 4, s));
+    LfaArgs a = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    srlg_gather(ctx, a, sa, n_prot, max_gather);
+    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
+    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
+    if (max_k <= 64) hipLaunchKernelGGL(k_lfa_srlg<true>, grid, dim3(256), 0, s, a, sa);
+    else hipLaunchKernelGGL(k_lfa_srlg<false>, grid, dim3(256), 0, s, a, sa);
+    return frr_finish(ctx, "k_lfa_srlg");
+  });
+}
+
+int hspf_rlfa_srlg_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                          const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                          const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_rlfa_srlg_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
+    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
+      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
+    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
+    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    if ((rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
+    std::vector<uint32_t> tab, stab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0, max_nms = 0;
+    size_t max_gather = 0;
+    SrlgArgs sa{};
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = srlg_stage(ctx, fn, prot, srlg, n_prot, stab, &sa, &max_gather, &max_nms)) || (rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * HSPF_RLFA_SRLG_COUNT_WORDS * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * HSPF_RLFA_SRLG_COVERAGE_WORDS * 4, s));
+    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    srlg_gather(ctx, ga, sa, n_prot, max_gather);
+    RlfaArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)stride;
+    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
+    a.tab = ga.tab; a.scal = ga.scal;
+    a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
+    a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
+    a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
+    a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    const dim3 grid(n_tiles, n_prot), fgrid((uint32_t)((n_slots + 255) / 256));
+    hipLaunchKernelGGL(k_rlfa_srlg, grid, dim3(256), 0, s, a, sa);
+    if (max_nms) hipLaunchKernelGGL(k_rlfa_srlg_slot, dim3(n_tiles, std::min(max_nms, 65535u), n_prot), dim3(256), 0, s, a, sa);
+    hipLaunchKernelGGL(k_rlfa_srlg_final, fgrid, dim3(256), 0, s, a, n_prot, sa);
+    hipLaunchKernelGGL(k_rlfa_srlg_dest, grid, dim3(256), 0, s, a, sa);
+    return frr_finish(ctx, "k_rlfa_srlg");
+  });
 }
 
 // ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----

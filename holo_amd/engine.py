@@ -46,6 +46,11 @@ LFA_LAN_COVERAGE_WORDS = 7
 LFA_LAN_SAFE_REPAIRS = 0x02     # HSPF_LFA_LAN_SAFE_REPAIRS (routes_backup_lan_device flags): tilfa comes from rlfa_lan_device()'s tables
 RLFA_LAN_COUNT_WORDS = 5
 RLFA_LAN_COVERAGE_WORDS = 6
+SRLG_MAX_MEMBERS = 16           # HSPF_SRLG_MAX_MEMBERS: members per slot of the SRLG calls
+LFA_SRLG_REFUSED = 0x80         # HSPF_LFA_SRLG_REFUSED: alt_flags of lfa_srlg_device()
+LFA_SRLG_COVERAGE_WORDS = 7
+RLFA_SRLG_COUNT_WORDS = 5
+RLFA_SRLG_COVERAGE_WORDS = 6
 RLFA_VIA_SELF = 0xFFFFFFFE      # HSPF_RLFA_VIA_SELF: released by the root itself (P-space)
 RLFA_IN_P, RLFA_IN_XP, RLFA_IN_Q, RLFA_ELIGIBLE = 0x01, 0x02, 0x04, 0x08      # space_flags
 RLFA_COUNT_WORDS = 4
@@ -243,6 +248,49 @@ def lfa_lan_candidates(row_ptr, col, metric, vflags, root: int, cap: Optional[in
     if rc < 0:
         raise HspfError(rc, "hspf_lfa_lan_candidates")
     return lan
+
+
+@dataclass
+class SrlgMembers:
+    """The shared-risk members of every first-hop slot of one root (srlg_members()): slot k's members are entries
+    mem_ptr[k] .. mem_ptr[k + 1] of the columns.  tail_row / head_row are the caller's to fill: it makes the run."""
+    mem_ptr: np.ndarray       # [K + 1] u32
+    tail: np.ndarray          # [M] u32 the member link's source ...
+    pos: np.ndarray           # [M] u32 ... its position in that row
+    head: np.ndarray          # [M] u32
+    cost: np.ndarray          # [M] u32
+    tail_row: Optional[np.ndarray] = None   # [M] u32 row of the SPT rooted at tail
+    head_row: Optional[np.ndarray] = None   # [M] u32 row of the SPT rooted at head
+    total_slots: int = 0
+    total_members: int = 0
+
+
+def srlg_members(row_ptr, col, metric, vflags, root: int, grp_ptr, grp, cap_slots: Optional[int] = None,
+                 cap_members: Optional[int] = None) -> SrlgMembers:
+    """hspf_srlg_members(): per first-hop slot of `root` the other links that share a group id with the link of the root's row
+    that the slot stands behind — pure host arithmetic on the caller's CSR (no context, no GPU).  grp_ptr [n_links + 1] / grp:
+    the group ids of every directed link, by its position in `col`.  cap_slots / cap_members: entries to fill (default: all)."""
+    lib = L.load()
+    row_ptr = np.ascontiguousarray(row_ptr, np.uint32); col = np.ascontiguousarray(col, np.uint32)
+    metric = np.ascontiguousarray(metric, np.uint32); vflags = np.ascontiguousarray(vflags, np.uint8)
+    grp_ptr = np.ascontiguousarray(grp_ptr, np.uint32); grp = np.ascontiguousarray(grp, np.uint32)
+    if len(grp_ptr) != len(col) + 1:
+        raise ValueError("srlg_members: grp_ptr needs one entry per link and one more")
+    csr = L.HspfCsr(len(row_ptr) - 1, len(col), _u32(row_ptr), _u32(col), _u32(metric), vflags.ctypes.data_as(L.u8p), 0xFFFFFFFF)
+    ts, tm = ctypes.c_uint32(), ctypes.c_uint32()
+    gp = _u32(grp) if len(grp) else None
+    k = lib.hspf_srlg_members(ctypes.byref(csr), root, _u32(grp_ptr), gp, 0, 0, None, None, None, None, None, ctypes.byref(ts), ctypes.byref(tm))
+    if k < 0:
+        raise HspfError(k, "hspf_srlg_members")
+    K = k if cap_slots is None else min(k, int(cap_slots))
+    M = int(tm.value) if cap_members is None else min(int(tm.value), int(cap_members))
+    mem_ptr = np.zeros(K + 1, np.uint32)
+    cols = [np.empty(M, np.uint32) for _ in range(4)]
+    rc = lib.hspf_srlg_members(ctypes.byref(csr), root, _u32(grp_ptr), gp, K, M, _u32(mem_ptr), *(_u32(c) if M else None for c in cols),
+                               ctypes.byref(ts), ctypes.byref(tm))
+    if rc < 0:
+        raise HspfError(rc, "hspf_srlg_members")
+    return SrlgMembers(mem_ptr, *cols, total_slots=int(ts.value), total_members=int(tm.value))
 
 
 @dataclass
@@ -1001,6 +1049,153 @@ class SpfContext:
         del keep, lkeep
         self._check_rc("hspf_rlfa_lan_device", rc)
 
+    @staticmethod
+    def _srlg_array(srlgs, protect, who: str):
+        """The hspf_srlg array of an SRLG call — `srlgs`: one SrlgMembers (tail_row / head_row filled) per protected root — and the
+        arrays it points into."""
+        if len(srlgs) != len(protect):
+            raise ValueError(who + ": one SrlgMembers per protected root is required")
+        arr = (L.HspfSrlg * max(len(srlgs), 1))()
+        keep = []
+        for i, (m, (_, c, _)) in enumerate(zip(srlgs, protect)):
+            mp = np.ascontiguousarray(m.mem_ptr, np.uint32)
+            if len(mp) != len(c.nbr) + 1:
+                raise ValueError(who + ": mem_ptr needs one entry per slot of its protected root and one more")
+            M = int(mp[-1])
+            if M and (m.tail_row is None or m.head_row is None):
+                raise ValueError(who + ": tail_row / head_row are not filled")
+            cols = [np.ascontiguousarray(x if x is not None else [], np.uint32) for x in (m.tail, m.pos, m.head, m.cost, m.tail_row, m.head_row)]
+            if any(len(x) < M for x in cols):
+                raise ValueError(who + ": a member column is shorter than mem_ptr says")
+            keep.append([mp] + cols)
+            arr[i] = L.HspfSrlg(_u32(mp), *(_u32(x) if len(x) else None for x in cols))
+        return arr, keep
+
+    def lfa_srlg_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, srlgs, *,
+                        alt_slot_ptr: int, alt_metric_ptr: int, alt_flags_ptr: int, coverage_ptr: int, cand_mask_ptr: int = 0,
+                        node_mask_ptr: int = 0, lfa_flags: int = 0) -> None:
+        """hspf_lfa_srlg_device(): lfa_device() whose alternates neither start on nor cross a link that shares a risk group with a
+        primary's first link.  `srlgs`: per protected root a SrlgMembers with tail_row / head_row filled (the rows of the SPTs
+        rooted at the members' endpoints).  coverage_ptr: [P, LFA_SRLG_COVERAGE_WORDS] u32."""
+        arr, keep = self._protect_array(protect, "lfa_srlg_device")
+        sarr, skeep = self._srlg_array(srlgs, protect, "lfa_srlg_device")
+        out = L.HspfLfaOut(alt_slot_ptr or None, alt_metric_ptr or None, alt_flags_ptr or None, cand_mask_ptr or None, node_mask_ptr or None,
+                           coverage_ptr or None)
+        rc = self.lib.hspf_lfa_srlg_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                           arr, sarr, len(protect), lfa_flags, ctypes.byref(out))
+        del keep, skeep
+        self._check_rc("hspf_lfa_srlg_device", rc)
+
+    def rlfa_srlg_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
+                         protect, srlgs, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int,
+                         rl_via_ptr: int, rl_coverage_ptr: int, space_flags_ptr: int = 0, space_via_ptr: int = 0, alt_flags_in_ptr: int = 0,
+                         lfa_flags: int = 0) -> None:
+        """hspf_rlfa_srlg_device(): rlfa_device() with P, extended P and Q narrowed to the vertices whose paths cross no member of
+        the slot's risk group.  `srlgs` as for lfa_srlg_device(); both table sets come from the run [root] + neighbour routers +
+        member endpoints.  pq_counts_ptr: [P, S, RLFA_SRLG_COUNT_WORDS] u32, rl_coverage_ptr: [P, RLFA_SRLG_COVERAGE_WORDS] u32."""
+        arr, keep = self._protect_array(protect, "rlfa_srlg_device")
+        sarr, skeep = self._srlg_array(srlgs, protect, "rlfa_srlg_device")
+        out = L.HspfRlfaOut(pq_node_ptr or None, pq_via_ptr or None, pq_metric_ptr or None, pq_counts_ptr or None, space_flags_ptr or None,
+                            space_via_ptr or None, rl_node_ptr or None, rl_via_ptr or None, rl_coverage_ptr or None)
+        rc = self.lib.hspf_rlfa_srlg_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
+                                            mask_ptr or None, rdist_ptr or None, arr, sarr, len(protect), lfa_flags, alt_flags_in_ptr or None,
+                                            ctypes.byref(out))
+        del keep, skeep
+        self._check_rc("hspf_rlfa_srlg_device", rc)
+
+    def _srlg_plan(self, graph: SpfGraph, root: int, grp_ptr, grp):
+        """_frr_plan() for the SRLG calls: the distinct member endpoints that are not yet roots are appended to the run, and the
+        members come back with tail_row / head_row filled."""
+        plan = self._frr_plan(graph, root)
+        mem = srlg_members(graph.row_ptr, graph.col, graph.metric, graph.vflags, root, grp_ptr, grp)
+        ends = np.setdiff1d(np.concatenate([mem.tail, mem.head]), plan.roots)      # (sorted, distinct)
+        roots = np.concatenate([plan.roots, ends]).astype(np.uint32)
+        row_of = {int(v): i for i, v in enumerate(roots)}
+        mem.tail_row = np.array([row_of[int(v)] for v in mem.tail], np.uint32)
+        mem.head_row = np.array([row_of[int(v)] for v in mem.head], np.uint32)
+        return FrrPlan(plan.cand, roots, plan.nbr_row, max(graph.mask_words(roots), (plan.cand.n_slots + 63) // 64)), mem
+
+    def lfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int = 0, *, lfa_flags: int = 0, want_masks: bool = True):
+        """lfa() against shared-risk link groups: srlg_members() of `root`, ONE run_device() for [root] + its neighbour routers +
+        the members' endpoints, lfa_srlg_device() on those rows.  Returns (LfaCandidates, SrlgMembers, LfaResult with seven
+        coverage words)."""
+        plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
+        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
+        R, n = len(roots), graph.n
+        masks = ((1, n, W), np.uint64) if want_masks else None
+        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cm=masks, nm=masks,
+                      cov=((1, LFA_SRLG_COVERAGE_WORDS), np.uint32))
+        host = {k: np.empty(*sh) if sh else None for k, sh in shapes.items()}
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W)
+        sizes.update({k: 0 if a is None else a.nbytes for k, a in host.items()})
+        with self._dev_buffers(sizes) as dev:
+            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            self.lfa_srlg_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], [mem], alt_slot_ptr=dev["slot"],
+                                 alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], cand_mask_ptr=dev["cm"],
+                                 node_mask_ptr=dev["nm"], lfa_flags=lfa_flags)
+            self._fetch(host, dev)
+        return cand, mem, LfaResult(*host.values())
+
+    def rlfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False,
+                  symmetric: bool = False):
+        """rlfa() against shared-risk link groups: both runs hold [root] + its neighbour routers + the members' endpoints, and
+        lfa_srlg_device() / rlfa_srlg_device() take the places of the plain calls (pq_counts has five words, rl_coverage six).
+        Returns (LfaCandidates, SrlgMembers, LfaResult without masks, RlfaResult)."""
+        return self._rlfa_srlg(graph, root, grp_ptr, grp, run_flags, lfa_flags, want_spaces, symmetric, False)
+
+    def _rlfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool):
+        """The chain behind rlfa_srlg() and tilfa_srlg() (tilfa: tilfa_device() runs on the safe tables, its TilfaResult is appended;
+        a TILFA_PAIR's forced link is NOT checked against the members: compare (ti_p, ti_link) with the slot's (tail, pos) list)."""
+        plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
+        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
+        R, n, S = len(roots), graph.n, 64 * W
+        want_spaces = want_spaces or tilfa
+        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cov=((1, LFA_SRLG_COVERAGE_WORDS), np.uint32),
+                      pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
+                      pq_counts=((1, S, RLFA_SRLG_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32), rl_via=((1, n), np.uint32),
+                      rl_cov=((1, RLFA_SRLG_COVERAGE_WORDS), np.uint32))
+        if want_spaces:
+            shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
+        ti_names = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
+        if tilfa:
+            shapes.update(ti_kind=((1, S), np.uint8), ti_p=((1, S), np.uint32), ti_q=((1, S), np.uint32), ti_via=((1, S), np.uint32),
+                          ti_link=((1, S), np.uint32), ti_metric=((1, S), np.uint32), ti_counts=((1, S, TILFA_COUNT_WORDS), np.uint32),
+                          td_kind=((1, n), np.uint8), td_coverage=((1, TILFA_COVERAGE_WORDS), np.uint32))
+        host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
+        sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
+        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
+            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            if not symmetric:
+                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
+                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
+                cleanup.callback(GT.free)
+                self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
+            rdist = dev["dist"] if symmetric else dev["rdist"]
+            protect = [(0, cand, nbr_row)]
+            self.lfa_srlg_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, [mem], alt_slot_ptr=dev["slot"],
+                                 alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
+            self.rlfa_srlg_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, [mem], pq_node_ptr=dev["pq_node"],
+                                  pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
+                                  rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
+                                  space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
+                                  lfa_flags=lfa_flags)
+            if tilfa:
+                self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, space_flags_ptr=dev["sp_flags"],
+                                  space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
+                                  **{k + "_ptr": dev[k] for k in ti_names})
+            self._fetch(host, dev)
+        lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
+        rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"), host.get("sp_via"),
+                        host["rl_node"], host["rl_via"], host["rl_cov"])
+        return (cand, mem, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, mem, lfa, rl)
+
+    def tilfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False):
+        """tilfa() against shared-risk link groups: rlfa_srlg() with everything kept on the device, then tilfa_device() on the safe
+        space tables.  Returns (LfaCandidates, SrlgMembers, LfaResult, RlfaResult, TilfaResult).  A TILFA_NODE repair is
+        SRLG-safe; the forced link of a TILFA_PAIR is NOT checked against the members."""
+        return self._rlfa_srlg(graph, root, grp_ptr, grp, run_flags, lfa_flags, True, symmetric, True)
+
     def tilfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                      protect, *, space_flags_ptr: int, space_via_ptr: int, ti_kind_ptr: int, ti_p_ptr: int, ti_q_ptr: int, ti_via_ptr: int,
                      ti_link_ptr: int, ti_metric_ptr: int, ti_counts_ptr: int, td_kind_ptr: int, td_coverage_ptr: int,
@@ -1181,7 +1376,8 @@ class SpfContext:
     def tilfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False, lan_protect: bool = False):
         """Two-segment repairs of one root, start to finish: rlfa(..., want_spaces=True) with everything kept on the device, then
         tilfa_device() on the same rows and space tables.  Returns (LfaCandidates, LfaResult, RlfaResult, TilfaResult).
-        lan_protect: as for rlfa(); tilfa_device() then reads LAN-safe tables and its repairs avoid the primaries' LANs."""
+        lan_protect: as for rlfa(); tilfa_device() then reads LAN-safe tables and its repairs avoid the primaries' LANs.
+        Against shared-risk link groups: tilfa_srlg()."""
         return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True, lan_protect=lan_protect, lan_spaces=lan_protect)
 
     def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None,

@@ -685,7 +685,8 @@ int hspf_ancestors_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *ro
  * LAN pseudonodes are handled through root_link ALONE: a candidate reached over the same first link of S as a primary is never
  * offered.  Loop-freeness with respect to the pseudonode itself (RFC 5286 section 3.3) is not checked by THIS call: a candidate on
  * another link whose own shortest path to D crosses the primary's LAN is still offered as link-protecting.  hspf_lfa_lan_device
- * ("broadcast-link protection", below) adds that check. */
+ * ("broadcast-link protection", below) adds that check.  Shared-risk link groups: hspf_lfa_srlg_device ("SRLG-safe alternates and
+ * remote-LFA spaces", below). */
 #define HSPF_LFA_C_NO_TRANSIT    0x01u   /* hspf_lfa_protect.cflags */
 #define HSPF_LFA_IGNORE_OVERLOAD 0x01u   /* hspf_lfa_device lfa_flags */
 #define HSPF_LFA_HAS_PRIMARY     0x01u   /* alt_flags */
@@ -845,7 +846,8 @@ int hspf_lfa_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uin
  * hspf_rlfa_node_device, below.  OUT OF SCOPE: loop-freeness with respect to a
  * LAN pseudonode in THIS call (the same root_link rule and the same limitation as hspf_lfa_device: hspf_rlfa_lan_device, below,
  * adds it); segment lists beyond one tunnel
- * (hspf_tilfa_device, below, adds one forced adjacency). */
+ * (hspf_tilfa_device, below, adds one forced adjacency).  Shared-risk link groups: hspf_rlfa_srlg_device ("SRLG-safe alternates
+ * and remote-LFA spaces", below). */
 #define HSPF_RLFA_VIA_SELF       0xFFFFFFFEu   /* pq_via / space_via / rl_via: released by S itself (P-space) */
 #define HSPF_RLFA_IN_P           0x01u         /* space_flags */
 #define HSPF_RLFA_IN_XP          0x02u
@@ -908,6 +910,98 @@ int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices
                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                          const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
                          const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev);
+
+/* ---- SRLG-safe alternates and remote-LFA spaces on device: new symbols, same ABI number ----------------------------------------
+ * A shared-risk link group (SRLG) is a set of links that fail together: one fibre, one conduit, one line card.  hspf_lfa_device
+ * offers a neighbour whose own shortest path runs over a link in the same conduit as the primary; hspf_rlfa_device offers a PQ node
+ * whose tunnel or onward path does.  The two calls below are those calls with one more inequality per set and per group member,
+ * read from rows of the same batch: the SPTs rooted at the member links' endpoints.
+ *
+ * SRLG table.  The caller holds, per directed link of its CSR (a link is its position in `col`), a list of u32 group ids:
+ * grp_ptr[n_edges + 1] and grp[].  For a protected root S and a first-hop slot k the PROTECTED LINK is the link at position
+ * root_link[k] of S's own row; all slots behind one link of S agree, as lan[] does.  A MEMBER of slot k is any OTHER directed link
+ * of the graph that shares at least one group id with the protected link, described by six fields:
+ *   tail a | pos (its position within a's row) | head b | cost w | tail_row | head_row
+ * ordered by ascending (tail, pos).  tail_row / head_row are the rows of the table set that hold the SPTs rooted at a and at b
+ * (the caller's: it made the run).
+ * Root list.  The batch is [S] ++ (S's neighbour routers) ++ (the distinct tails and heads of all members that are not already in
+ * the list); the forward and the transposed run use the same list and the same run_flags.
+ *
+ * crosses(X -> v, i), for a source X, a target v and a member i, holds iff d(X, a_i) and d(b_i, v) are BOTH FINITE and
+ *     d(X, v) >= d(X, a_i) + w_i + d(b_i, v)                                   (the sum in 64 bits)
+ * A member that X does not reach, or whose head does not reach v, is not crossed.  This is NOT the LAN rule, where an
+ * HSPF_DIST_INF term makes the inequality false and so refuses: a member may lie anywhere in the graph, and an unreachable one
+ * must not refuse anything.  A head b_i that carries HSPF_VF_NO_TRANSIT is expanded as the root of its row, so d(b_i, v) may be
+ * finite where no transit path through b_i exists: the test is conservative there — it may refuse, it never wrongly admits.
+ * Member i is LOCAL to slot k when tail_i == S and pos_i == root_link[k]: slot k's own first link is in the group.
+ *
+ * hspf_srlg_members (host arithmetic, no context; slot numbering, row checks and return value of hspf_lfa_candidates): the members
+ * of every slot of `root`.  mem_ptr[k] .. mem_ptr[k + 1] delimit slot k's members in the four columns; mem_ptr holds the true
+ * offsets for k <= min(slots, cap_slots) (so it has cap_slots + 1 entries), the columns are written below cap_members (any
+ * output may be NULL).  *out_total_slots / *out_total_members say what to size the arrays for when calling again.  HSPF_E_INVAL
+ * on what hspf_lfa_candidates rejects, on a row_ptr that is not the one of a whole CSR (row_ptr[0] == 0, monotone,
+ * row_ptr[n_vertices] == n_edges), on a member's head >= n_vertices and on a grp_ptr that is not monotone.
+ *
+ * hspf_srlg is parallel to hspf_lfa_protect (entry i belongs to prot[i], same n_slots): mem_ptr[n_slots + 1] and the six member
+ * columns as HOST arrays.
+ *
+ * hspf_lfa_srlg_device.  Everything of hspf_lfa_device, with more conditions on membership of `cand` (and through it on `node`, the
+ * choice, alt_* and both masks): for every primary slot p in P and every member i of p
+ *     i is not local to k,   and   crosses(N_k -> D, i) is false
+ * d(N_k, a_i) is read from N_k's row at a_i, d(b_i, D) from row head_row_i at D.  alt_flags gains
+ *   HSPF_LFA_SRLG_REFUSED   at least one slot met every condition of hspf_lfa_device's cand and failed only an SRLG condition
+ * (0x20 and 0x40 stay with the LAN calls, so a combined call has room).  coverage is [n_prot][HSPF_LFA_SRLG_COVERAGE_WORDS]: the
+ * five words of hspf_lfa_device | destinations with a primary that has at least one member | destinations with
+ * HSPF_LFA_SRLG_REFUSED.  With every mem_ptr all zero the outputs are those of hspf_lfa_device and words 5, 6 are 0.
+ *
+ * hspf_rlfa_srlg_device.  Everything of hspf_rlfa_device, with the three spaces of a candidate slot e narrowed by its members i:
+ *   P_s(e, v)      P(e, v)      and for no i  crosses(S -> v, i)
+ *   XP_s(e, k, v)  XP(e, k, v)  and no member of e is local to k  and for no i  crosses(N_k -> v, i)
+ *   Q_s(e, v)      Q(e, v)      and for no i:  d(v, a_i) and d(b_i, E) both finite and d(v, E) >= d(v, a_i) + w_i + d(b_i, E)
+ * with d(v, E) = rdist[row of E][v], d(v, a_i) = rdist[tail_row_i][v], d(b_i, E) = dist[head_row_i][E].  Eligibility, via-slot
+ * admission, the tie order, the release point and its metric, the PQ choice, rl_* and the four space_flags bits are those of
+ * hspf_rlfa_device evaluated over the safe sets: the bits mean the safe sets, so the tables feed hspf_tilfa_device unchanged.
+ *   pq_counts   [n_prot][stride][HSPF_RLFA_SRLG_COUNT_WORDS]: the four words over the safe sets, then the number of v in the plain
+ *               (P or some XP) and Q that are not in the safe one.
+ *   rl_coverage [n_prot][HSPF_RLFA_SRLG_COVERAGE_WORDS]: the four plain words | one-primary destinations whose primary has
+ *               members | of those, the ones left uncovered although the plain rule had a PQ node.
+ * With no members all shared outputs equal hspf_rlfa_device's.  The forward-dist-as-rdist shortcut stays valid on graphs with
+ * symmetric costs.
+ *
+ * Argument errors of both device calls — everything the plain call rejects, srlg == NULL, a NULL mem_ptr, a NULL column where
+ * mem_ptr[n_slots] > mem_ptr[0], a mem_ptr that is not monotone, more than HSPF_SRLG_MAX_MEMBERS members on one slot, tail or head
+ * >= n_vertices, tail_row or head_row >= n_rows — return HSPF_E_INVAL with a text that names the call, before anything is launched.
+ *
+ * OUT OF SCOPE: the forced adjacency of a TI-LFA pair — HSPF_TILFA_NODE repairs from the safe tables are SRLG-safe, and a
+ * HSPF_TILFA_PAIR has its p in the safe P / XP set and its q in the safe Q set, but the forced link p -> q may itself be a member:
+ * the consumer compares (ti_p, ti_link) with the slot's (tail, pos) list; per-prefix backups with SRLGs;
+ * node-protecting calls with SRLGs; SRLGs combined with the LAN inequalities (a LAN slot is treated as by the plain calls);
+ * the fuzz_frr run of tools/gpu_fuzz.py (the randomised differential run does not draw group tables). */
+#define HSPF_SRLG_MAX_MEMBERS          16u
+#define HSPF_LFA_SRLG_REFUSED          0x80u   /* alt_flags of hspf_lfa_srlg_device */
+#define HSPF_LFA_SRLG_COVERAGE_WORDS   7u
+#define HSPF_RLFA_SRLG_COUNT_WORDS     5u
+#define HSPF_RLFA_SRLG_COVERAGE_WORDS  6u
+int hspf_srlg_members(const hspf_csr *csr, uint32_t root, const uint32_t *grp_ptr, const uint32_t *grp, uint32_t cap_slots,
+                      uint32_t cap_members, uint32_t *mem_ptr, uint32_t *tail, uint32_t *pos, uint32_t *head, uint32_t *cost,
+                      uint32_t *out_total_slots, uint32_t *out_total_members);
+typedef struct {                 /* parallel to hspf_lfa_protect: entry i belongs to prot[i]; HOST arrays       */
+  const uint32_t *mem_ptr;       /* [n_slots + 1]                                                              */
+  const uint32_t *tail;          /* [mem_ptr[n_slots]] each: hspf_srlg_members ...                             */
+  const uint32_t *pos;
+  const uint32_t *head;
+  const uint32_t *cost;
+  const uint32_t *tail_row;      /* ... and the rows of the SPTs rooted at tail / head                         */
+  const uint32_t *head_row;
+} hspf_srlg;
+int hspf_lfa_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                         const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                         hspf_lfa_out *out_dev);
+int hspf_rlfa_srlg_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                          const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                          const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev);
 
 /* ---- two-segment repair paths on device (TI-LFA, link protection): new symbol, same ABI number ----------------------------
  * hspf_rlfa_device leaves rl_coverage[3]: destinations whose one primary link has no LFA and whose extended P-space and

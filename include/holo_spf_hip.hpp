@@ -442,6 +442,48 @@ class Engine {
                                         lans.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_lan_device (") + hspf_last_error(ctx_) + ")");
   }
+  // Shared-risk link groups.  srlg_members: host arithmetic, no device (hspf_srlg_members): per first-hop slot of `root` the other
+  // links that share a group id with the link of the root's row the slot stands behind; tail_row / head_row are the caller's to fill.
+  struct SrlgMembers {
+    std::vector<uint32_t> mem_ptr, tail, pos, head, cost, tail_row, head_row;
+    hspf_srlg raw() const { return hspf_srlg{mem_ptr.data(), tail.data(), pos.data(), head.data(), cost.data(), tail_row.data(), head_row.data()}; }
+  };
+  static SrlgMembers srlg_members(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                                  const std::vector<uint8_t> &vflags, uint32_t root, const std::vector<uint32_t> &grp_ptr,
+                                  const std::vector<uint32_t> &grp) {
+    if (grp_ptr.size() != col.size() + 1) throw Error(HSPF_E_INVAL, "srlg_members: grp_ptr needs one entry per link and one more");
+    hspf_csr csr{(uint32_t)vflags.size(), (uint32_t)col.size(), row_ptr.data(), col.data(), metric.data(), vflags.data(), 0xFFFFFFFFu};
+    uint32_t slots = 0, total = 0;
+    int k = hspf_srlg_members(&csr, root, grp_ptr.data(), grp.data(), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &slots, &total);
+    if (k < 0) throw Error(k, "hspf_srlg_members");
+    SrlgMembers m;
+    m.mem_ptr.resize((size_t)k + 1); m.tail.resize(total); m.pos.resize(total); m.head.resize(total); m.cost.resize(total);
+    k = hspf_srlg_members(&csr, root, grp_ptr.data(), grp.data(), (uint32_t)k, total, m.mem_ptr.data(), m.tail.data(), m.pos.data(), m.head.data(),
+                          m.cost.data(), &slots, &total);
+    if (k < 0) throw Error(k, "hspf_srlg_members");
+    return m;
+  }
+  // hspf_lfa_srlg_device: lfa_device whose alternates neither start on nor cross a member of a primary's group.  `srlgs[i]` belongs
+  // to `protect[i]`; coverage has HSPF_LFA_SRLG_COVERAGE_WORDS words per root.
+  void lfa_srlg_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                       const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_srlg> &srlgs,
+                       uint32_t lfa_flags, hspf_lfa_out out_dev) {
+    if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "lfa_srlg_device: one hspf_srlg per protected root");
+    const int rc = hspf_lfa_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
+                                        (uint32_t)protect.size(), lfa_flags, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_srlg_device (") + hspf_last_error(ctx_) + ")");
+  }
+  // hspf_rlfa_srlg_device: rlfa_device with P, extended P and Q narrowed by the members of every slot's group; both table sets come
+  // from the run [S] ++ neighbour routers ++ member endpoints; pq_counts has HSPF_RLFA_SRLG_COUNT_WORDS words per slot, rl_coverage
+  // HSPF_RLFA_SRLG_COVERAGE_WORDS per root.  The space tables feed tilfa_device unchanged.
+  void rlfa_srlg_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                        const uint64_t *mask_dev, const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect,
+                        const std::vector<hspf_srlg> &srlgs, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev, hspf_rlfa_out out_dev) {
+    if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "rlfa_srlg_device: one hspf_srlg per protected root");
+    const int rc = hspf_rlfa_srlg_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                                         srlgs.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_srlg_device (") + hspf_last_error(ctx_) + ")");
+  }
   // One root start to finish, as lfa(): ONE run of [root] ++ its neighbour routers on `g` and one on the upload of its transpose
   // (skipped when `symmetric` says every link has its reverse at the same cost), hspf_lfa_device, hspf_rlfa_device, results on
   // the host.  The four vectors must be the CSR `g` was uploaded from, max_path_metric the one it was uploaded with.

@@ -112,6 +112,13 @@ struct LfaProtect {
 struct LfaLan {
   std::vector<uint32_t> lan, lan_row;
 };
+// Shared-risk link groups (hspf_lfa_srlg_device / hspf_rlfa_srlg_device): parallel to LfaProtect — the members of every slot
+// (hspf_srlg_members: slot k's are entries mem_ptr[k] .. mem_ptr[k + 1] of the columns) and the rows of the SPTs rooted at their
+// endpoints.  The outputs are LfaOut / RlfaOut with HSPF_LFA_SRLG_COVERAGE_WORDS / HSPF_RLFA_SRLG_COUNT_WORDS /
+// HSPF_RLFA_SRLG_COVERAGE_WORDS words.
+struct Srlg {
+  std::vector<uint32_t> mem_ptr, tail, pos, head, cost, tail_row, head_row;
+};
 struct LfaOut {
   bool supported = false;
   uint32_t n_protected = 0, n_vertices = 0, mask_words = 1;
@@ -241,6 +248,14 @@ class Engine {
   // nullptr, or what lfa_lan() returned.  The result feeds tilfa() unchanged.  The default: not supported.
   virtual RlfaOut rlfa_lan(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, const std::vector<LfaLan> &,
                            uint32_t /*lfa_flags*/, const LfaOut * /*lfa*/, bool /*with_spaces*/) { return RlfaOut{}; }
+  // lfa() / rlfa() against shared-risk link groups (hspf_lfa_srlg_device / hspf_rlfa_srlg_device); srlgs[i] belongs to protect[i];
+  // both runs hold the SPTs rooted at the members' endpoints too; `lfa`: nullptr, or what lfa_srlg() returned.  The result of
+  // rlfa_srlg() feeds tilfa() unchanged.  The defaults: not supported.
+  virtual LfaOut lfa_srlg(DeviceRun &, const std::vector<LfaProtect> &, const std::vector<Srlg> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) {
+    return LfaOut{};
+  }
+  virtual RlfaOut rlfa_srlg(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, const std::vector<Srlg> &,
+                            uint32_t /*lfa_flags*/, const LfaOut * /*lfa*/, bool /*with_spaces*/) { return RlfaOut{}; }
   virtual std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                         const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
                                         uint32_t max_path_metric) = 0;
@@ -771,19 +786,37 @@ class HipEngine : public Engine {
     return out;
   }
   LfaOut lfa(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, bool with_masks) override {
-    return lfa_with(run, protect, nullptr, lfa_flags, with_masks);
+    return lfa_with(run, protect, nullptr, nullptr, lfa_flags, with_masks);
   }
   // (backup_routes / backup_routes_lan stay the base's "not supported": a DeviceRoutes does not keep its prefix table, which
   // hspf_routes_backup_device needs; hspf::Engine::routes_backup_device / routes_backup_lan_device take it explicitly.)
   LfaOut lfa_lan(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans, uint32_t lfa_flags, bool with_masks) override {
     if (lans.size() != protect.size()) throw std::runtime_error("lfa_lan: one LfaLan per protected root");
-    return lfa_with(run, protect, &lans, lfa_flags, with_masks);
+    return lfa_with(run, protect, &lans, nullptr, lfa_flags, with_masks);
   }
-  // the frame of lfa() (lans == nullptr: hspf_lfa_device) and lfa_lan() (hspf_lfa_lan_device)
-  LfaOut lfa_with(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans, uint32_t lfa_flags, bool with_masks) {
+  LfaOut lfa_srlg(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<Srlg> &srlgs, uint32_t lfa_flags, bool with_masks) override {
+    return lfa_with(run, protect, nullptr, &srlgs, lfa_flags, with_masks);
+  }
+  // the hspf_srlg array of an SRLG call, its lengths held to the slot arrays
+  static std::vector<hspf_srlg> srlg_raw(const std::string &who, const std::vector<LfaProtect> &protect, const std::vector<Srlg> &srlgs) {
+    if (srlgs.size() != protect.size()) throw std::runtime_error(who + "one Srlg per protected root");
+    std::vector<hspf_srlg> out;
+    for (size_t i = 0; i < srlgs.size(); ++i) {
+      const Srlg &m = srlgs[i];
+      if (m.mem_ptr.size() != protect[i].nbr.size() + 1) throw std::runtime_error(who + "mem_ptr needs one entry per slot and one more");
+      const size_t t = m.mem_ptr.back();
+      if (m.tail.size() < t || m.pos.size() < t || m.head.size() < t || m.cost.size() < t || m.tail_row.size() < t || m.head_row.size() < t)
+        throw std::runtime_error(who + "a member column is shorter than mem_ptr says");
+      out.push_back(hspf_srlg{m.mem_ptr.data(), m.tail.data(), m.pos.data(), m.head.data(), m.cost.data(), m.tail_row.data(), m.head_row.data()});
+    }
+    return out;
+  }
+  // the frame of lfa() (lans == srlgs == nullptr: hspf_lfa_device), lfa_lan() (hspf_lfa_lan_device) and lfa_srlg() (hspf_lfa_srlg_device)
+  LfaOut lfa_with(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans, const std::vector<Srlg> *srlgs,
+                  uint32_t lfa_flags, bool with_masks) {
     auto &r = static_cast<HipDeviceRun &>(run);
-    const uint32_t cw = lans ? HSPF_LFA_LAN_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
-    const char *fn = lans ? "hspf_lfa_lan_device: " : "hspf_lfa_device: ";
+    const uint32_t cw = lans ? HSPF_LFA_LAN_COVERAGE_WORDS : srlgs ? HSPF_LFA_SRLG_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
+    const char *fn = lans ? "hspf_lfa_lan_device: " : srlgs ? "hspf_lfa_srlg_device: " : "hspf_lfa_device: ";
     LfaOut o;
     o.supported = true;
     o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.mask_words = r.mask_words;
@@ -800,12 +833,15 @@ class HipEngine : public Engine {
       if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error("lfa_lan: lan / lan_row differ in length from the slot arrays");
       ls.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
     }
+    std::vector<hspf_srlg> ss;
+    if (srlgs) ss = srlg_raw("lfa_srlg: ", protect, *srlgs);
     const size_t pn = (size_t)o.n_protected * o.n_vertices, mb = with_masks ? pn * 8 * o.mask_words : 0, cb = (size_t)o.n_protected * cw * 4;
     uint32_t *slot = (uint32_t *)pool_->dev(pn * 4), *met = (uint32_t *)pool_->dev(pn * 4), *cov = (uint32_t *)pool_->dev(cb);
     uint8_t *fl = (uint8_t *)pool_->dev(pn);
     uint64_t *cm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr, *nm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr;
     hspf_lfa_out out{slot, met, fl, cm, nm, cov};
     const int rc = lans ? hspf_lfa_lan_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), ls.data(), o.n_protected, lfa_flags, &out)
+                 : srlgs ? hspf_lfa_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), ss.data(), o.n_protected, lfa_flags, &out)
                         : hspf_lfa_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, &out);
     o.alt_slot.resize(pn); o.alt_metric.resize(pn); o.alt_flags.resize(pn); o.coverage.resize((size_t)o.n_protected * cw);
     if (with_masks) { o.cand_mask.resize(pn * o.mask_words); o.node_mask.resize(pn * o.mask_words); }
@@ -822,20 +858,26 @@ class HipEngine : public Engine {
   }
   RlfaOut rlfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
                bool with_spaces) override {
-    return rlfa_with(gr, run, reverse_run, protect, nullptr, lfa_flags, lfa, with_spaces);
+    return rlfa_with(gr, run, reverse_run, protect, nullptr, nullptr, lfa_flags, lfa, with_spaces);
   }
   RlfaOut rlfa_lan(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans,
                    uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) override {
     if (lans.size() != protect.size()) throw std::runtime_error("rlfa_lan: one LfaLan per protected root");
-    return rlfa_with(gr, run, reverse_run, protect, &lans, lfa_flags, lfa, with_spaces);
+    return rlfa_with(gr, run, reverse_run, protect, &lans, nullptr, lfa_flags, lfa, with_spaces);
+  }
+  RlfaOut rlfa_srlg(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<Srlg> &srlgs,
+                    uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) override {
+    return rlfa_with(gr, run, reverse_run, protect, nullptr, &srlgs, lfa_flags, lfa, with_spaces);
   }
  private:
-  // the frame of rlfa() (lans == nullptr: hspf_rlfa_device) and rlfa_lan() (hspf_rlfa_lan_device)
+  // the frame of rlfa() (lans == srlgs == nullptr: hspf_rlfa_device), rlfa_lan() (hspf_rlfa_lan_device) and rlfa_srlg()
+  // (hspf_rlfa_srlg_device)
   RlfaOut rlfa_with(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans,
-                    uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) {
-    const uint32_t nw = lans ? HSPF_RLFA_LAN_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS, cw = lans ? HSPF_RLFA_LAN_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
-    const char *fn = lans ? "hspf_rlfa_lan_device: " : "hspf_rlfa_device: ";
-    const std::string who = lans ? "rlfa_lan: " : "rlfa: ";
+                    const std::vector<Srlg> *srlgs, uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) {
+    const uint32_t nw = lans ? HSPF_RLFA_LAN_COUNT_WORDS : srlgs ? HSPF_RLFA_SRLG_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS;
+    const uint32_t cw = lans ? HSPF_RLFA_LAN_COVERAGE_WORDS : srlgs ? HSPF_RLFA_SRLG_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
+    const char *fn = lans ? "hspf_rlfa_lan_device: " : srlgs ? "hspf_rlfa_srlg_device: " : "hspf_rlfa_device: ";
+    const std::string who = lans ? "rlfa_lan: " : srlgs ? "rlfa_srlg: " : "rlfa: ";
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rr = static_cast<HipDeviceRun &>(reverse_run);
     if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error(who + "the two runs differ in shape");
@@ -856,6 +898,8 @@ class HipEngine : public Engine {
       if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error("rlfa_lan: lan / lan_row differ in length from the slot arrays");
       ls.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
     }
+    std::vector<hspf_srlg> ss;
+    if (srlgs) ss = srlg_raw(who, protect, *srlgs);
     const size_t cb = (size_t)o.n_protected * cw * 4;
     const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
     // one block: pq_node | pq_via | pq_metric | pq_counts | rl_node | rl_via | rl_coverage | space_via | space_flags | alt_flags
@@ -872,6 +916,8 @@ class HipEngine : public Engine {
     const int rc = !ok ? HSPF_E_HIP
                  : lans ? hspf_rlfa_lan_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), ls.data(),
                                                o.n_protected, lfa_flags, alt, &out)
+                 : srlgs ? hspf_rlfa_srlg_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), ss.data(),
+                                                 o.n_protected, lfa_flags, alt, &out)
                         : hspf_rlfa_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), o.n_protected,
                                            lfa_flags, alt, &out);
     auto fetch = [&](auto &vec, const void *src, size_t count) {

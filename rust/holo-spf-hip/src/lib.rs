@@ -242,6 +242,19 @@ pub struct LfaCandidates {
     pub cflags: Vec<u8>,
 }
 
+/// The shared-risk members of every first-hop slot of one root (`hspf_srlg_members`): slot k's members are entries
+/// `mem_ptr[k] .. mem_ptr[k + 1]` of the columns.  `tail_row` / `head_row` (the rows of the SPTs rooted at the members'
+/// endpoints) are the caller's to fill: it makes the run.
+pub struct SrlgMembers {
+    pub mem_ptr: Vec<u32>,
+    pub tail: Vec<u32>,
+    pub pos: Vec<u32>,
+    pub head: Vec<u32>,
+    pub cost: Vec<u32>,
+    pub tail_row: Vec<u32>,
+    pub head_row: Vec<u32>,
+}
+
 /// Loop-free alternates of the protected roots of one `Engine::lfa_device` call, row-major `[protected root][vertex]`.
 pub struct Lfa {
     pub n_protected: u32,
@@ -703,6 +716,67 @@ impl Engine {
         Ok(lan)
     }
 
+    /// `hspf_srlg_members`: per first-hop slot of `root` the other links that share a group id with the link of the root's row
+    /// the slot stands behind — pure host arithmetic on the CSR (no device).  `grp_ptr` has one entry per link and one more.
+    pub fn srlg_members(csr: &Csr, root: u32, grp_ptr: &[u32], grp: &[u32]) -> Result<SrlgMembers, Error> {
+        if grp_ptr.len() != csr.col.len() + 1 || grp_ptr.last().map_or(true, |e| *e as usize > grp.len()) {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "srlg_members: grp_ptr / grp do not match the links".into() });
+        }
+        let c = sys::hspf_csr {
+            n_vertices: csr.n_vertices(),
+            n_edges: csr.col.len() as u32,
+            row_ptr: csr.row_ptr.as_ptr(),
+            col: csr.col.as_ptr(),
+            metric: csr.metric.as_ptr(),
+            vflags: csr.vflags.as_ptr(),
+            max_path_metric: csr.max_path_metric,
+        };
+        let (mut slots, mut total) = (0u32, 0u32);
+        let k = unsafe {
+            sys::hspf_srlg_members(&c, root, grp_ptr.as_ptr(), grp.as_ptr(), 0, 0, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), &mut slots, &mut total)
+        };
+        if k < 0 {
+            return Err(Error { code: k, detail: "hspf_srlg_members".into() });
+        }
+        let m = total as usize;
+        let mut out = SrlgMembers { mem_ptr: vec![0; k as usize + 1], tail: vec![0; m], pos: vec![0; m], head: vec![0; m], cost: vec![0; m], tail_row: Vec::new(), head_row: Vec::new() };
+        let rc = unsafe {
+            sys::hspf_srlg_members(&c, root, grp_ptr.as_ptr(), grp.as_ptr(), k as u32, total, out.mem_ptr.as_mut_ptr(), out.tail.as_mut_ptr(), out.pos.as_mut_ptr(), out.head.as_mut_ptr(), out.cost.as_mut_ptr(), &mut slots, &mut total)
+        };
+        if rc < 0 {
+            return Err(Error { code: rc, detail: "hspf_srlg_members".into() });
+        }
+        Ok(out)
+    }
+
+    /// The `hspf_srlg` array of an SRLG call: `srlgs[i]` belongs to `protect[i]`, with `tail_row` / `head_row` filled.
+    fn srlg_raw(who: &str, protect: &[(u32, &LfaCandidates, &[u32])], srlgs: &[&SrlgMembers]) -> Result<Vec<sys::hspf_srlg>, Error> {
+        let fits = |c: &LfaCandidates, m: &SrlgMembers| {
+            let t = m.mem_ptr.last().map_or(0, |e| *e as usize);
+            m.mem_ptr.len() == c.nbr.len() + 1 && [&m.tail, &m.pos, &m.head, &m.cost, &m.tail_row, &m.head_row].iter().all(|x| x.len() >= t)
+        };
+        if srlgs.len() != protect.len() || protect.iter().zip(srlgs).any(|((_, c, _), m)| !fits(c, m)) {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: format!("{who}: the member lists do not match the slot arrays of the protected roots") });
+        }
+        Ok(srlgs.iter().map(|m| sys::hspf_srlg {
+            mem_ptr: m.mem_ptr.as_ptr(),
+            tail: m.tail.as_ptr(),
+            pos: m.pos.as_ptr(),
+            head: m.head.as_ptr(),
+            cost: m.cost.as_ptr(),
+            tail_row: m.tail_row.as_ptr(),
+            head_row: m.head_row.as_ptr(),
+        }).collect())
+    }
+
+    /// `hspf_lfa_srlg_device`: `lfa_device` whose alternates neither start on nor cross a link that shares a risk group with a
+    /// primary's first link.  `coverage` has `HSPF_LFA_SRLG_COVERAGE_WORDS` words per root; `alt_flags` may carry
+    /// `HSPF_LFA_SRLG_REFUSED`.
+    pub fn lfa_srlg_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], srlgs: &[&SrlgMembers],
+                           ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
+        self.lfa_device_with(tables, protect, None, Some(srlgs), ignore_overload, with_masks)
+    }
+
     /// The `hspf_lfa_lan` array of a LAN call: `lans[i]` = (`lan`, `lan_row`) of `protect[i]`, one entry per slot each.
     fn lan_raw(who: &str, protect: &[(u32, &LfaCandidates, &[u32])], lans: &[(&[u32], &[u32])]) -> Result<Vec<sys::hspf_lfa_lan>, Error> {
         if lans.len() != protect.len() || protect.iter().zip(lans).any(|((_, c, _), (l, r))| l.len() != c.nbr.len() || r.len() != c.nbr.len()) {
@@ -716,7 +790,7 @@ impl Engine {
     /// `HSPF_LFA_LAN_COVERAGE_WORDS` words per root; `alt_flags` may carry `HSPF_LFA_LAN_PRIMARY` / `HSPF_LFA_LAN_REFUSED`.
     pub fn lfa_lan_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: &[(&[u32], &[u32])],
                           ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
-        self.lfa_device_with(tables, protect, Some(lans), ignore_overload, with_masks)
+        self.lfa_device_with(tables, protect, Some(lans), None, ignore_overload, with_masks)
     }
 
     /// `hspf_lfa_device`: loop-free alternates (RFC 5286) of every protected root from the rows of `tables` (a previous
@@ -724,15 +798,16 @@ impl Engine {
     /// its candidate table, `nbr_row[k]` = row of the SPT rooted at `nbr[k]`).  The results come back on the host; the SPT
     /// tables never leave the device.
     pub fn lfa_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
-        self.lfa_device_with(tables, protect, None, ignore_overload, with_masks)
+        self.lfa_device_with(tables, protect, None, None, ignore_overload, with_masks)
     }
 
-    /// The frame of `lfa_device` (`lans` None) and `lfa_lan_device`.
+    /// The frame of `lfa_device` (`lans` and `srlgs` None), `lfa_lan_device` and `lfa_srlg_device` (at most one of the two).
     fn lfa_device_with(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: Option<&[(&[u32], &[u32])]>,
-                       ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
+                       srlgs: Option<&[&SrlgMembers]>, ignore_overload: bool, with_masks: bool) -> Result<Lfa, Error> {
         let (n, w, np) = (tables.n_vertices as usize, tables.words as usize, protect.len());
         let lan_raw = match lans { Some(l) => Some(Self::lan_raw("lfa_lan_device", protect, l)?), None => None };
-        let cov_words = if lans.is_some() { sys::HSPF_LFA_LAN_COVERAGE_WORDS } else { sys::HSPF_LFA_COVERAGE_WORDS } as usize;
+        let srlg_raw = match srlgs { Some(m) => Some(Self::srlg_raw("lfa_srlg_device", protect, m)?), None => None };
+        let cov_words = if lans.is_some() { sys::HSPF_LFA_LAN_COVERAGE_WORDS } else if srlgs.is_some() { sys::HSPF_LFA_SRLG_COVERAGE_WORDS } else { sys::HSPF_LFA_COVERAGE_WORDS } as usize;
         let mut raw = Vec::with_capacity(np);
         for (root_row, c, nbr_row) in protect {
             let k = c.nbr.len();
@@ -767,11 +842,14 @@ impl Engine {
         let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
         let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
         let rc = unsafe {
-            match &lan_raw {
-                None => sys::hspf_lfa_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &mut out),
-                Some(l) => {
+            match (&lan_raw, &srlg_raw) {
+                (Some(l), _) => {
                     sys::hspf_lfa_lan_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), l.as_ptr(), np as u32, lfa_flags, &mut out)
                 }
+                (None, Some(m)) => {
+                    sys::hspf_lfa_srlg_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), m.as_ptr(), np as u32, lfa_flags, &mut out)
+                }
+                (None, None) => sys::hspf_lfa_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &mut out),
             }
         };
         if rc != sys::HSPF_OK {
@@ -823,7 +901,7 @@ impl Engine {
     /// for the same `protect`, so that only the destinations it left unprotected get a remote alternate.
     pub fn rlfa_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
                        ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
-        self.rlfa_device_with(g, tables, reverse, protect, None, ignore_overload, lfa, with_spaces)
+        self.rlfa_device_with(g, tables, reverse, protect, None, None, ignore_overload, lfa, with_spaces)
     }
 
     /// `hspf_rlfa_lan_device`: `rlfa_device` with P, extended P and Q loop-free towards the pseudonode of every slot's LAN.
@@ -833,18 +911,31 @@ impl Engine {
     /// `tilfa_device` unchanged.
     pub fn rlfa_lan_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
                            lans: &[(&[u32], &[u32])], ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
-        self.rlfa_device_with(g, tables, reverse, protect, Some(lans), ignore_overload, lfa, with_spaces)
+        self.rlfa_device_with(g, tables, reverse, protect, Some(lans), None, ignore_overload, lfa, with_spaces)
     }
 
-    /// The frame of `rlfa_device` (`lans` None) and `rlfa_lan_device`.
+    /// `hspf_rlfa_srlg_device`: `rlfa_device` with P, extended P and Q narrowed to the vertices whose paths cross no member of
+    /// the slot's risk group.  `srlgs` as for `lfa_srlg_device`; both table sets come from the run [root] + neighbour routers +
+    /// member endpoints; `lfa`: what `lfa_srlg_device` returned.  `pq_counts` has `HSPF_RLFA_SRLG_COUNT_WORDS` words per slot,
+    /// `rl_coverage` `HSPF_RLFA_SRLG_COVERAGE_WORDS` per root; the result feeds `tilfa_device` unchanged (the forced link of a
+    /// pair is not checked against the members).
+    #[allow(clippy::too_many_arguments)]
+    pub fn rlfa_srlg_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
+                            srlgs: &[&SrlgMembers], ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
+        self.rlfa_device_with(g, tables, reverse, protect, None, Some(srlgs), ignore_overload, lfa, with_spaces)
+    }
+
+    /// The frame of `rlfa_device` (`lans` and `srlgs` None), `rlfa_lan_device` and `rlfa_srlg_device` (at most one of the two).
     #[allow(clippy::too_many_arguments)]
     fn rlfa_device_with(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
-                        lans: Option<&[(&[u32], &[u32])]>, ignore_overload: bool, lfa: Option<&Lfa>, with_spaces: bool) -> Result<Rlfa, Error> {
+                        lans: Option<&[(&[u32], &[u32])]>, srlgs: Option<&[&SrlgMembers]>, ignore_overload: bool, lfa: Option<&Lfa>,
+                        with_spaces: bool) -> Result<Rlfa, Error> {
         let (n, np) = (tables.n_vertices as usize, protect.len());
-        let who = if lans.is_some() { "rlfa_lan_device" } else { "rlfa_device" };
+        let who = if lans.is_some() { "rlfa_lan_device" } else if srlgs.is_some() { "rlfa_srlg_device" } else { "rlfa_device" };
         let lan_raw = match lans { Some(l) => Some(Self::lan_raw(who, protect, l)?), None => None };
-        let count_words = if lans.is_some() { sys::HSPF_RLFA_LAN_COUNT_WORDS } else { sys::HSPF_RLFA_COUNT_WORDS } as usize;
-        let cov_words = if lans.is_some() { sys::HSPF_RLFA_LAN_COVERAGE_WORDS } else { sys::HSPF_RLFA_COVERAGE_WORDS } as usize;
+        let srlg_raw = match srlgs { Some(m) => Some(Self::srlg_raw(who, protect, m)?), None => None };
+        let count_words = if lans.is_some() { sys::HSPF_RLFA_LAN_COUNT_WORDS } else if srlgs.is_some() { sys::HSPF_RLFA_SRLG_COUNT_WORDS } else { sys::HSPF_RLFA_COUNT_WORDS } as usize;
+        let cov_words = if lans.is_some() { sys::HSPF_RLFA_LAN_COVERAGE_WORDS } else if srlgs.is_some() { sys::HSPF_RLFA_SRLG_COVERAGE_WORDS } else { sys::HSPF_RLFA_COVERAGE_WORDS } as usize;
         let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
         if reverse.n_vertices != tables.n_vertices || reverse.n_roots != tables.n_roots {
             return Err(Error { code: sys::HSPF_E_INVAL, detail: format!("{who}: the two table sets differ in shape") });
@@ -895,11 +986,14 @@ impl Engine {
         let (dist, flags_in, mask, rdist) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64, reverse.dist.p as *const u32);
         let alt_p = alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8);
         let rc = unsafe {
-            match &lan_raw {
-                None => sys::hspf_rlfa_device(self.ctx, g.g, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, rdist, raw.as_ptr(), np as u32, lfa_flags, alt_p, &mut out),
-                Some(l) => {
+            match (&lan_raw, &srlg_raw) {
+                (Some(l), _) => {
                     sys::hspf_rlfa_lan_device(self.ctx, g.g, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, rdist, raw.as_ptr(), l.as_ptr(), np as u32, lfa_flags, alt_p, &mut out)
                 }
+                (None, Some(m)) => {
+                    sys::hspf_rlfa_srlg_device(self.ctx, g.g, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, rdist, raw.as_ptr(), m.as_ptr(), np as u32, lfa_flags, alt_p, &mut out)
+                }
+                (None, None) => sys::hspf_rlfa_device(self.ctx, g.g, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, rdist, raw.as_ptr(), np as u32, lfa_flags, alt_p, &mut out),
             }
         };
         if rc != sys::HSPF_OK {
