@@ -238,6 +238,11 @@ SYMBOLS = [
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect),
                                              ctypes.POINTER(HspfSrlg), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                              ctypes.POINTER(HspfRlfaOut)]),
+    # per-prefix SRLG-safe backups
+    ("hspf_routes_backup_srlg_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.POINTER(HspfSrlg),
+                                                      ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes),
+                                                      ctypes.POINTER(HspfTilfaOut), ctypes.POINTER(HspfBackupOut)]),
     # two-segment repair paths (TI-LFA, link protection)
     ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,

@@ -1,7 +1,7 @@
 // spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
 // hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
 // hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, hspf_routes_backup_node_device, the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device,
-// and the shared-risk calls hspf_srlg_members, hspf_lfa_srlg_device, hspf_rlfa_srlg_device.
+// and the shared-risk calls hspf_srlg_members, hspf_lfa_srlg_device, hspf_rlfa_srlg_device, hspf_routes_backup_srlg_device.
 // Included by spf_capi.hip (one TU).
 //
 // The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
@@ -19,6 +19,7 @@
 #include "spf_tilfa_node.hip.h"
 #include "spf_backup_node.hip.h"
 #include "spf_srlg.hip.h"
+#include "spf_backup_srlg.hip.h"
 
 namespace {
 
@@ -198,8 +199,8 @@ int srlg_check(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_ro
   return HSPF_OK;
 }
 
-// The member block (its layout: spf_srlg.hip.h) copied to ctx->srlg_tab on the context's stream, with ctx->srlg_scal sized for
-// k_srlg_gather.  After srlg_check and lfa_stage.  `stab` is the copy's source: it lives until the caller has synchronised.
+// The member block (its layout: spf_srlg.hip.h; behind its six member columns a seventh, pos [NM], that only k_backup_srlg reads)
+// copied to ctx->srlg_tab on the context's stream, with ctx->srlg_scal sized for k_srlg_gather.  After srlg_check and lfa_stage.  `stab` is the copy's source: it lives until the caller has synchronised.
 int srlg_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, std::vector<uint32_t> &stab,
                SrlgArgs *out, size_t *out_max_gather, uint32_t *out_max_nms) {
   stab.assign((size_t)n_prot * SRLG_HDR_WORDS, 0u);
@@ -232,10 +233,11 @@ int srlg_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, cons
     stab[to + K] = (uint32_t)sidx.size();
     stab.insert(stab.end(), sidx.begin(), sidx.end());
     const size_t NM = dm.size(), mo = stab.size();
-    stab.resize(mo + 6 * NM);
+    stab.resize(mo + SRLG_STAGED_COLS * NM);
     for (size_t j = 0; j < NM; ++j) {
       stab[mo + j] = dm[j].tail; stab[mo + NM + j] = dm[j].head; stab[mo + 2 * NM + j] = dm[j].cost;
       stab[mo + 3 * NM + j] = dm[j].trow; stab[mo + 4 * NM + j] = dm[j].hrow; stab[mo + 5 * NM + j] = dm[j].tail == S ? dm[j].pos : LFA_NONE;
+      stab[mo + SRLG_POS_COL * NM + j] = dm[j].pos;                      // (read through srlg_pos() in spf_backup_srlg.hip.h)
     }
     const size_t scal = NM * (1 + 2 * (size_t)K);
     if (stab.size() > (1u << 28) || so + scal > (1u << 28)) { ctx->last_error = std::string(fn) + ": the member tables of this call need more than 1 GiB of scratch"; return HSPF_E_NOMEM; }
@@ -395,6 +397,69 @@ int routes_backup(hspf_ctx *ctx, const char *fn, bool with_lan, uint32_t n_verti
       hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
     }
     return frr_finish(ctx, with_lan ? "k_backup_lan" : "k_backup");
+  });
+}
+
+static_assert(BK_SRLG_CW == HSPF_BK_SRLG_COVERAGE_WORDS, "the coverage kernel's width is the header's");
+
+// hspf_routes_backup_srlg_device: the frame of routes_backup with the member block of the SRLG calls next to the slot tables
+int routes_backup_srlg(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                       const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                       const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
+                       const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const char *fn = "hspf_routes_backup_srlg_device";
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
+    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
+      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
+    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric || !tilfa_dev->ti_p || !tilfa_dev->ti_link))
+      return bad("NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
+    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
+    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
+    if ((rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
+    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
+    std::vector<uint32_t> tab, stab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0, max_nms = 0;
+    size_t max_gather = 0;
+    SrlgArgs sa{};
+    hipStream_t s = ctx->stream;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
+        (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, stab, &sa, &max_gather, &max_nms))) {
+      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
+      return rc;
+    }
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * HSPF_BK_SRLG_COVERAGE_WORDS * 4, s));
+    if (!t->n_prefixes) {                               // nothing to launch
+      HIPCHK(ctx, hipStreamSynchronize(s));
+      return HSPF_OK;
+    }
+    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    srlg_gather(ctx, ga, sa, n_prot, max_gather);
+    BackupArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
+    a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
+    a.dist = dist_dev; a.flags = flags_dev;
+    a.tab = ga.tab; a.scal = ga.scal;
+    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
+    a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
+    BackupSrlgArgs b{};
+    b.sa = sa; b.repairs = (lfa_flags & HSPF_LFA_SRLG_SAFE_REPAIRS) ? 1u : 0u;
+    if (tilfa_dev) {
+      a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric;
+      b.ti_p = tilfa_dev->ti_p; b.ti_link = tilfa_dev->ti_link;
+    }
+    a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
+    a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
+    const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
+    hipLaunchKernelGGL(k_backup_srlg, dim3(n_tiles, n_prot), dim3(256), 0, s, a, b);
+    hipLaunchKernelGGL(k_backup_cov_srlg, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
+    return frr_finish(ctx, "k_backup_srlg");
   });
 }
 
@@ -736,6 +801,16 @@ int hspf_rlfa_srlg_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertice
     hipLaunchKernelGGL(k_rlfa_srlg_dest, grid, dim3(256), 0, s, a, sa);
     return frr_finish(ctx, "k_rlfa_srlg");
   });
+}
+
+// ---- per-prefix backups with shared-risk link groups (include/holo_spf_hip.h "per-prefix SRLG-safe backups"; kernels: spf_backup_srlg.hip.h) ----
+int hspf_routes_backup_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                   const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                                   const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                   hspf_backup_out *out_dev) {
+  return routes_backup_srlg(ctx, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, srlg, n_prot, lfa_flags, table, routes_dev,
+                            tilfa_dev, out_dev);
 }
 
 // ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----

@@ -51,6 +51,10 @@ LFA_SRLG_REFUSED = 0x80         # HSPF_LFA_SRLG_REFUSED: alt_flags of lfa_srlg_d
 LFA_SRLG_COVERAGE_WORDS = 7
 RLFA_SRLG_COUNT_WORDS = 5
 RLFA_SRLG_COVERAGE_WORDS = 6
+LFA_SRLG_SAFE_REPAIRS = 0x04    # HSPF_LFA_SRLG_SAFE_REPAIRS (routes_backup_srlg_device flags): tilfa comes from rlfa_srlg_device()'s tables
+BK_SRLG_PRIMARY = 0x01          # HSPF_BK_SRLG_PRIMARY: bk_flags of routes_backup_srlg_device(), next to LFA_SRLG_REFUSED
+BK_SRLG_PAIR_REFUSED = 0x02     # HSPF_BK_SRLG_PAIR_REFUSED
+BK_SRLG_COVERAGE_WORDS = 10
 RLFA_VIA_SELF = 0xFFFFFFFE      # HSPF_RLFA_VIA_SELF: released by the root itself (P-space)
 RLFA_IN_P, RLFA_IN_XP, RLFA_IN_Q, RLFA_ELIGIBLE = 0x01, 0x02, 0x04, 0x08      # space_flags
 RLFA_COUNT_WORDS = 4
@@ -394,8 +398,9 @@ class BackupRoutes:
     bk_flags: np.ndarray      # [1, P] u8  LFA_NODE_PROTECT | LFA_DOWNSTREAM for BK_LFA
     bk_cand_mask: np.ndarray  # [1, P, W] u64
     bk_node_mask: np.ndarray  # [1, P, W] u64
-    bk_coverage: np.ndarray   # [1, 7] u32; [1, 9] with lan_protect
+    bk_coverage: np.ndarray   # [1, 7] u32; [1, 9] with lan_protect; [1, 10] with srlg
     tilfa: Optional["TilfaResult"] = None      # the per-slot repairs bk_primary indexes (remote=True)
+    srlg: Optional["SrlgMembers"] = None       # backup_routes(srlg=...): the members of every slot, rows filled
     # node_protect=True (hspf_routes_backup_node_device), None otherwise:
     bn_kind: Optional[np.ndarray] = None       # [1, P] u8  BN_* per prefix with exactly one primary, 0 elsewhere
     bn_primary: Optional[np.ndarray] = None    # [1, P] u32 the one primary slot for BN_LFA .. BN_PAIR, LFA_NO_SLOT otherwise
@@ -1143,52 +1148,67 @@ class SpfContext:
         Returns (LfaCandidates, SrlgMembers, LfaResult without masks, RlfaResult)."""
         return self._rlfa_srlg(graph, root, grp_ptr, grp, run_flags, lfa_flags, want_spaces, symmetric, False)
 
-    def _rlfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool):
-        """The chain behind rlfa_srlg() and tilfa_srlg() (tilfa: tilfa_device() runs on the safe tables, its TilfaResult is appended;
-        a TILFA_PAIR's forced link is NOT checked against the members: compare (ti_p, ti_link) with the slot's (tail, pos) list)."""
-        plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n, S = len(roots), graph.n, 64 * W
-        want_spaces = want_spaces or tilfa
+    _TI_NAMES = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
+
+    @staticmethod
+    def _srlg_shapes(n: int, S: int, want_spaces: bool, tilfa: bool) -> dict:
+        """{name: (shape, dtype)} of what _srlg_chain() writes for one protected root."""
         shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cov=((1, LFA_SRLG_COVERAGE_WORDS), np.uint32),
                       pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
                       pq_counts=((1, S, RLFA_SRLG_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32), rl_via=((1, n), np.uint32),
                       rl_cov=((1, RLFA_SRLG_COVERAGE_WORDS), np.uint32))
-        if want_spaces:
+        if want_spaces or tilfa:
             shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
-        ti_names = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
         if tilfa:
             shapes.update(ti_kind=((1, S), np.uint8), ti_p=((1, S), np.uint32), ti_q=((1, S), np.uint32), ti_via=((1, S), np.uint32),
                           ti_link=((1, S), np.uint32), ti_metric=((1, S), np.uint32), ti_counts=((1, S, TILFA_COUNT_WORDS), np.uint32),
                           td_kind=((1, n), np.uint8), td_coverage=((1, TILFA_COVERAGE_WORDS), np.uint32))
-        host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
+        return shapes
+
+    def _srlg_chain(self, graph: SpfGraph, plan: FrrPlan, mem: SrlgMembers, run_flags: int, lfa_flags: int, symmetric: bool, tilfa: bool, dev: dict,
+                    cleanup) -> list:
+        """The device side rlfa_srlg(), tilfa_srlg() and backup_routes(srlg=...) share, everything left on the device in the buffers
+        of _srlg_shapes() (`dev`, next to dist / flags / mask / rdist): run_device() of the plan's roots (on the transposed graph too
+        unless `symmetric`), lfa_srlg_device(), rlfa_srlg_device() and — with `tilfa` — tilfa_device() on the safe tables.  Returns
+        the protect list."""
+        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
+        R, n = len(roots), graph.n
+        self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+        if not symmetric:
+            trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
+            GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
+            cleanup.callback(GT.free)
+            self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
+        rdist = dev["dist"] if symmetric else dev["rdist"]
+        protect = [(0, cand, nbr_row)]
+        self.lfa_srlg_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, [mem], alt_slot_ptr=dev["slot"],
+                             alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
+        self.rlfa_srlg_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, [mem], pq_node_ptr=dev["pq_node"],
+                              pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
+                              rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
+                              space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
+                              lfa_flags=lfa_flags)
+        if tilfa:
+            self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, space_flags_ptr=dev["sp_flags"],
+                              space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
+                              **{k + "_ptr": dev[k] for k in self._TI_NAMES})
+        return protect
+
+    def _rlfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool):
+        """The chain behind rlfa_srlg() and tilfa_srlg() (tilfa: tilfa_device() runs on the safe tables, its TilfaResult is appended;
+        a TILFA_PAIR's forced link is NOT checked against the members: compare (ti_p, ti_link) with the slot's (tail, pos) list)."""
+        plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
+        cand, R, n, W = plan.cand, len(plan.roots), graph.n, plan.mask_words
+        host = {k: np.empty(sh, dt) for k, (sh, dt) in self._srlg_shapes(n, 64 * W, want_spaces, tilfa).items()}
         sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
         sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
         with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
-            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-            if not symmetric:
-                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
-                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
-                cleanup.callback(GT.free)
-                self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
-            rdist = dev["dist"] if symmetric else dev["rdist"]
-            protect = [(0, cand, nbr_row)]
-            self.lfa_srlg_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, [mem], alt_slot_ptr=dev["slot"],
-                                 alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
-            self.rlfa_srlg_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, [mem], pq_node_ptr=dev["pq_node"],
-                                  pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
-                                  rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
-                                  space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
-                                  lfa_flags=lfa_flags)
-            if tilfa:
-                self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, space_flags_ptr=dev["sp_flags"],
-                                  space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
-                                  **{k + "_ptr": dev[k] for k in ti_names})
+            self._srlg_chain(graph, plan, mem, run_flags, lfa_flags, symmetric, tilfa, dev, cleanup)
             self._fetch(host, dev)
         lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
         rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"), host.get("sp_via"),
                         host["rl_node"], host["rl_via"], host["rl_cov"])
-        return (cand, mem, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, mem, lfa, rl)
+        return (cand, mem, lfa, rl, TilfaResult(*(host[k] for k in self._TI_NAMES))) if tilfa else (cand, mem, lfa, rl)
 
     def tilfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False):
         """tilfa() against shared-risk link groups: rlfa_srlg() with everything kept on the device, then tilfa_device() on the safe
@@ -1268,6 +1288,74 @@ class SpfContext:
         u32; every other argument as for routes_backup_device()."""
         self._routes_backup(list(lans), n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr, protect, pfx_ptr, pfx_vertex, pfx_metric, **kw)
 
+    def routes_backup_srlg_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, srlgs,
+                                  pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
+                                  bk_metric_ptr: int, bk_flags_ptr: int, bk_coverage_ptr: int, bk_cand_mask_ptr: int = 0, bk_node_mask_ptr: int = 0,
+                                  tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0) -> None:
+        """hspf_routes_backup_srlg_device(): routes_backup_device() whose alternates neither start on nor cross, on their way to the
+        PREFIX, a link that shares a risk group with a primary's first link.  `srlgs` as for lfa_srlg_device(); the table set holds
+        [root] + neighbour routers + member endpoints.  tilfa = (ti_kind_ptr, ti_via_ptr, ti_metric_ptr, ti_p_ptr, ti_link_ptr) of
+        tilfa_device(), or None; a primary with members takes its per-link repair only under lfa_flags LFA_SRLG_SAFE_REPAIRS (the
+        caller's word that `tilfa` comes from rlfa_srlg_device()'s tables), and a pair whose forced link is a member is refused
+        (BK_SRLG_PAIR_REFUSED).  bk_coverage_ptr: [P, BK_SRLG_COVERAGE_WORDS] u32; every other argument as for
+        routes_backup_device()."""
+        name = "routes_backup_srlg_device"
+        src = (pfx_ptr, pfx_vertex, pfx_metric)
+        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
+        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
+        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
+        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
+            raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
+        arr, keep = self._protect_array(protect, name)
+        sarr, skeep = self._srlg_array(srlgs, protect, name)
+        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags, None, None, None, None)
+        r = L.HspfRoutes(*(x or None for x in routes))
+        ti = None
+        if tilfa is not None:
+            ti = L.HspfTilfaOut(tilfa[0] or None, tilfa[3] or None, None, tilfa[1] or None, tilfa[4] or None, tilfa[2] or None, None, None, None)
+        out = L.HspfBackupOut(bk_kind_ptr or None, bk_primary_ptr or None, bk_slot_ptr or None, bk_metric_ptr or None, bk_flags_ptr or None,
+                              bk_cand_mask_ptr or None, bk_node_mask_ptr or None, bk_coverage_ptr or None)
+        rc = self.lib.hspf_routes_backup_srlg_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
+                                                     mask_ptr or None, arr, sarr, len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r),
+                                                     None if ti is None else ctypes.byref(ti), ctypes.byref(out))
+        del keep, skeep
+        self._check_rc("hspf_" + name, rc)
+
+    def _backup_srlg(self, graph: SpfGraph, root: int, tab, grp_ptr, grp, run_flags: int, lfa_flags: int, symmetric: bool, remote: bool,
+                     srlg_repairs: bool) -> BackupRoutes:
+        """backup_routes(srlg=...): on a run that also holds the member endpoints' rows, _srlg_chain() with `remote` (only the
+        per-slot repairs come to the host), then routes_device() and routes_backup_srlg_device()."""
+        plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
+        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
+        R, n, NP = len(roots), graph.n, len(tab[0]) - 1
+        shapes = dict(best_metric=((1, NP), np.uint32), best_entry=((1, NP), np.uint32), nexthop_mask=((1, NP, W), np.uint64),
+                      bk_kind=((1, NP), np.uint8), bk_primary=((1, NP), np.uint32), bk_slot=((1, NP), np.uint32), bk_metric=((1, NP), np.uint32),
+                      bk_flags=((1, NP), np.uint8), bk_cand_mask=((1, NP, W), np.uint64), bk_node_mask=((1, NP, W), np.uint64),
+                      bk_coverage=((1, BK_SRLG_COVERAGE_WORDS), np.uint32))
+        bk_names = tuple(shapes)
+        chain = self._srlg_shapes(n, 64 * W, True, True) if remote else {}
+        shapes.update({k: chain[k] for k in self._TI_NAMES if remote})
+        host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric or not remote else 4 * R * n)
+        sizes.update({k: max(int(np.prod(sh)) * np.dtype(dt).itemsize, 8) for k, (sh, dt) in chain.items()})      # (what stays on the device)
+        sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
+        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
+            tables = (dev["dist"], dev["flags"], dev["mask"])
+            if remote:
+                protect = self._srlg_chain(graph, plan, mem, run_flags, lfa_flags, symmetric, True, dev, cleanup)
+            else:
+                self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+                protect = [(0, cand, nbr_row)]
+            self.routes_device(n, 1, W, *tables, tab[0], tab[1], tab[2], flags=tab[3], best_metric_ptr=dev["best_metric"],
+                               best_entry_ptr=dev["best_entry"], nexthop_mask_ptr=dev["nexthop_mask"])
+            self.routes_backup_srlg_device(n, R, W, *tables, protect, [mem], tab[0], tab[1], tab[2],
+                                           routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
+                                           tilfa=tuple(dev[k] for k in ("ti_kind", "ti_via", "ti_metric", "ti_p", "ti_link")) if remote else None,
+                                           flags=tab[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_SRLG_SAFE_REPAIRS if srlg_repairs else 0),
+                                           **{k + "_ptr": dev[k] for k in bk_names[3:]})
+            self._fetch(host, dev)
+        return BackupRoutes(cand, *(host[k] for k in bk_names), tilfa=TilfaResult(*(host[k] for k in self._TI_NAMES)) if remote else None, srlg=mem)
+
     def routes_backup_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                                   pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, ydist_ptr: int, y_roots, bn_kind_ptr: int, bn_primary_ptr: int,
                                   bn_p_ptr: int, bn_q_ptr: int, bn_link_ptr: int, bn_via_ptr: int, bn_metric_ptr: int, bn_coverage_ptr: int,
@@ -1339,7 +1427,7 @@ class SpfContext:
 
     def backup_routes(self, graph: SpfGraph, root: int, prefix_table, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False,
                       remote: bool = True, lan_protect: bool = False, lan_repairs: bool = False, node_protect: bool = False, max_pq: int = 16,
-                      max_pairs: int = 16) -> BackupRoutes:
+                      max_pairs: int = 16, srlg: Optional[tuple] = None, srlg_repairs: bool = False) -> BackupRoutes:
         """The routes of one root with their backups, start to finish: run_device() of [root] + its distinct neighbour routers,
         routes_device(), lfa_device() and — with `remote` — rlfa_device() + tilfa_device() (on the transposed graph too unless
         `symmetric`), then routes_backup_device(); only the route and bk_* arrays (and the per-slot repairs) come to the host.
@@ -1350,7 +1438,16 @@ class SpfContext:
         place, so the per-link repairs avoid the primaries' LANs, and a LAN primary without an alternate takes its repair
         (LFA_LAN_SAFE_REPAIRS) instead of BK_NONE.  node_protect (needs remote, excludes lan_protect): the chain goes on with
         rlfa_node_select_device(max_pq) and tilfa_node_select_device(max_pairs), ONE run_device() over the ascending union of the
-        listed nodes, and routes_backup_node_device() with the bk_kind / bk_flags just written; the bn_* fields are filled."""
+        listed nodes, and routes_backup_node_device() with the bk_kind / bk_flags just written; the bn_* fields are filled.
+        srlg = (grp_ptr, grp), the group ids per directed link as for srlg_members() (excludes lan_protect and node_protect): the run
+        also holds the member endpoints' rows, lfa_srlg_device() and — with `remote` — rlfa_srlg_device() + tilfa_device() take the
+        plain calls' places, and routes_backup_srlg_device() writes the backups (bk_coverage has ten words, BackupRoutes.srlg holds
+        the members).  srlg_repairs (needs srlg and remote): LFA_SRLG_SAFE_REPAIRS — a primary with members and no alternate takes
+        its per-link repair instead of BK_NONE, unless the repair's forced link is itself a member."""
+        if srlg is not None and (lan_protect or node_protect):
+            raise ValueError("backup_routes: srlg excludes lan_protect and node_protect")
+        if srlg_repairs and (srlg is None or not remote):
+            raise ValueError("backup_routes: srlg_repairs needs srlg and remote=True")
         if lan_repairs and (not lan_protect or not remote or symmetric):
             raise ValueError("backup_routes: lan_repairs needs lan_protect=True, remote=True and symmetric=False")
         if node_protect and (not remote or lan_protect):
@@ -1360,6 +1457,8 @@ class SpfContext:
         else:
             tab = (prefix_table.pfx_ptr, prefix_table.pfx_vertex, prefix_table.pfx_metric, int(getattr(prefix_table, "flags", 0)))
         tab = tuple(np.ascontiguousarray(a, np.uint32) for a in tab[:3]) + (int(tab[3]) & ~PFX_RESIDENT,)
+        if srlg is not None:
+            return self._backup_srlg(graph, root, tab, srlg[0], srlg[1], run_flags, lfa_flags, symmetric, remote, srlg_repairs)
         return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab, lan_protect=lan_protect,
                           lan_spaces=lan_repairs, node=(int(max_pq), int(max_pairs)) if node_protect else None)
 

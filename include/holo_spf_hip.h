@@ -974,7 +974,8 @@ int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices
  *
  * OUT OF SCOPE: the forced adjacency of a TI-LFA pair — HSPF_TILFA_NODE repairs from the safe tables are SRLG-safe, and a
  * HSPF_TILFA_PAIR has its p in the safe P / XP set and its q in the safe Q set, but the forced link p -> q may itself be a member:
- * the consumer compares (ti_p, ti_link) with the slot's (tail, pos) list; per-prefix backups with SRLGs;
+ * the consumer compares (ti_p, ti_link) with the slot's (tail, pos) list (hspf_routes_backup_srlg_device, below,
+ * does it per prefix);
  * node-protecting calls with SRLGs; SRLGs combined with the LAN inequalities (a LAN slot is treated as by the plain calls);
  * the fuzz_frr run of tools/gpu_fuzz.py (the randomised differential run does not draw group tables). */
 #define HSPF_SRLG_MAX_MEMBERS          16u
@@ -1437,6 +1438,57 @@ int hspf_routes_backup_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
                                    const hspf_rlfa_node_sel *rn_sel_dev, uint32_t max_pq,
                                    const hspf_tilfa_node_sel *tn_sel_dev, uint32_t max_pairs,
                                    const hspf_backup_out *bk_in_dev, hspf_backup_node_out *out_dev);
+
+/* ---- per-prefix SRLG-safe backups on device: new symbol, same ABI number ---------------------------------------------------------
+ * hspf_lfa_srlg_device answers per VERTEX; what a RIB installs is per PREFIX, and for a multi-homed prefix the member inequality —
+ * like the loop-free one ("per-prefix backup routes", above) — must be held against the distances to the PREFIX: a neighbour whose
+ * shortest path to S's attaining vertex avoids the conduit may reach the prefix through another advertiser, over a member.
+ * hspf_routes_backup_srlg_device is everything hspf_routes_backup_device is, with the following on top.
+ *
+ * Inputs.  `srlg` is parallel to `prot` (hspf_srlg, "SRLG-safe alternates", above); the batch and root list are those of
+ * hspf_lfa_srlg_device: [S] ++ neighbour routers ++ member endpoints.  At most HSPF_SRLG_MAX_MEMBERS members per slot; the
+ * argument checks on `srlg` are the same as there.  tilfa_dev: NULL, or the hspf_tilfa_out of hspf_tilfa_device for the same `prot`;
+ * THIS call reads ti_kind, ti_via, ti_metric AND ti_p, ti_link (all five required when tilfa_dev is given; the plain call reads
+ * neither of the last two).
+ *   d_{b_i}(p)        d_X(p) of the per-prefix section evaluated on row head_row_i; HSPF_PFX_SATURATING is treated as there.
+ *   crosses_p(N_k, i) d(N_k, a_i) is finite, d_{b_i}(p) exists, and  d_{N_k}(p) >= d(N_k, a_i) + w_i + d_{b_i}(p)  (64 bits).
+ *                     An unreachable member refuses nothing: the SRLG rule, not the LAN rule.
+ *   cand(p)           additionally, for every primary slot e in P and every member i of e: i is not local to k (not (tail_i == S and
+ *                     pos_i == root_link[k])), and crosses_p(N_k, i) is false.
+ *   node(p), downstream and the choice are unchanged, evaluated over the narrowed cand.
+ *   fallback          one primary e, no slot chosen.  e without members: exactly the plain call's.  e with members: the per-link
+ *                     repair is taken only under HSPF_LFA_SRLG_SAFE_REPAIRS in lfa_flags — the caller's word that tilfa_dev was
+ *                     computed from hspf_rlfa_srlg_device's tables.  Then HSPF_TILFA_NODE gives HSPF_BK_NODE; HSPF_TILFA_PAIR gives
+ *                     HSPF_BK_PAIR unless (ti_p[e], ti_link[e]) equals (tail_i, pos_i) of a member of e: the forced adjacency is
+ *                     itself in the group, and the result is HSPF_BK_NONE with HSPF_BK_SRLG_PAIR_REFUSED.
+ * bk_flags gains (next to HSPF_LFA_NODE_PROTECT | HSPF_LFA_DOWNSTREAM; 0x20 and 0x40 stay with the LAN call):
+ *   HSPF_LFA_SRLG_REFUSED      some slot met every condition of the plain cand(p) and failed only a member condition
+ *   HSPF_BK_SRLG_PRIMARY       some slot in P has at least one member (kinds HSPF_BK_ECMP .. HSPF_BK_NONE)
+ *   HSPF_BK_SRLG_PAIR_REFUSED  as above
+ * bk_coverage is [n_prot][HSPF_BK_SRLG_COVERAGE_WORDS]: the seven kinds | prefixes with HSPF_BK_SRLG_PRIMARY | with
+ * HSPF_LFA_SRLG_REFUSED | with HSPF_BK_SRLG_PAIR_REFUSED.
+ * With every mem_ptr all zero all shared outputs equal hspf_routes_backup_device's, words 7 .. 9 are 0, and
+ * HSPF_LFA_SRLG_SAFE_REPAIRS has no effect.  No other call rejects or reads bit 0x04 of lfa_flags.
+ * Argument errors — everything hspf_routes_backup_device rejects (with ti_p / ti_link among the required tilfa_dev arrays) and
+ * everything hspf_lfa_srlg_device rejects in `srlg` — return HSPF_E_INVAL with a text that names hspf_routes_backup_srlg_device,
+ * before any kernel is launched.
+ *
+ * From bk_* to a next hop when SRLGs are configured: INTEGRATION.md §5r.
+ *
+ * OUT OF SCOPE: SRLGs combined with the LAN inequalities (a LAN primary is treated as by hspf_routes_backup_device); SRLGs combined
+ * with node-protecting backups (hspf_routes_backup_node_device); per-prefix Q-spaces (the remote repair is the primary LINK's);
+ * HSPF_PFX_ORDERED tables (HSPF_E_INVAL); group tables in the fuzz_frr run of tools/gpu_fuzz.py (existing seeds keep their meaning).
+ */
+#define HSPF_LFA_SRLG_SAFE_REPAIRS   0x04u   /* lfa_flags of hspf_routes_backup_srlg_device; every other call ignores it */
+#define HSPF_BK_SRLG_PRIMARY         0x01u   /* bk_flags: some primary slot of the prefix has members */
+#define HSPF_BK_SRLG_PAIR_REFUSED    0x02u   /* bk_flags: the primary's two-segment repair forces a member link */
+/* HSPF_LFA_SRLG_REFUSED 0x80u is reused in bk_flags */
+#define HSPF_BK_SRLG_COVERAGE_WORDS  10u
+int hspf_routes_backup_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                   const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                                   const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                   hspf_backup_out *out_dev);
 
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root

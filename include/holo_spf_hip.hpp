@@ -581,6 +581,18 @@ class Engine {
                                                  (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_lan_device (") + hspf_last_error(ctx_) + ")");
   }
+  // hspf_routes_backup_srlg_device: routes_backup_device whose alternates neither start on nor cross, on their way to the prefix, a
+  // member of a primary's shared-risk group (`srlgs` as for lfa_srlg_device; HSPF_LFA_SRLG_SAFE_REPAIRS in lfa_flags vouches for
+  // tilfa_dev, whose ti_p / ti_link are read too; bk_coverage has HSPF_BK_SRLG_COVERAGE_WORDS words per root).
+  void routes_backup_srlg_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                                 const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_srlg> &srlgs,
+                                 uint32_t lfa_flags, const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                 hspf_backup_out out_dev) {
+    if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "routes_backup_srlg_device: one hspf_srlg per protected root");
+    const int rc = hspf_routes_backup_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
+                                                  (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_srlg_device (") + hspf_last_error(ctx_) + ")");
+  }
   // hspf_routes_backup_node_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the
   // routes hspf_routes_device wrote for it, ydist_dev the dist of a forward run of y_roots (host list: the caller's choice among the
   // listed nodes), rn_sel_dev / tn_sel_dev what the two select calls wrote with max_pq / max_pairs (nullptr: no such entries; at

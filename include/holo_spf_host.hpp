@@ -190,7 +190,7 @@ struct BackupOut {
   std::vector<uint8_t> bk_kind, bk_flags;                   // [n_protected][n_prefixes]
   std::vector<uint32_t> bk_primary, bk_slot, bk_metric;
   std::vector<uint64_t> bk_cand_mask, bk_node_mask;         // [n_protected][n_prefixes][mask_words]
-  std::vector<uint32_t> bk_coverage;                        // [n_protected][HSPF_BK_COVERAGE_WORDS]
+  std::vector<uint32_t> bk_coverage;                        // [n_protected][HSPF_BK_COVERAGE_WORDS] (backup_routes_srlg: HSPF_BK_SRLG_COVERAGE_WORDS)
 };
 // Per-prefix node-protecting backups (hspf_routes_backup_node_device) of the same protected roots over the prefix table of a
 // DeviceRoutes: per (protected root, prefix) with one primary the kind (HSPF_BN_*), the primary slot and the chosen repair.
@@ -256,6 +256,14 @@ class Engine {
   }
   virtual RlfaOut rlfa_srlg(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, const std::vector<Srlg> &,
                             uint32_t /*lfa_flags*/, const LfaOut * /*lfa*/, bool /*with_spaces*/) { return RlfaOut{}; }
+  // backup_routes() against shared-risk link groups (hspf_routes_backup_srlg_device): srlgs[i] belongs to protect[i], the run holds
+  // the SPTs rooted at the members' endpoints too; the prefix table is given again (pfx_* / table_flags: the call reads the
+  // advertisers); HSPF_LFA_SRLG_SAFE_REPAIRS in lfa_flags vouches that `tilfa` comes from rlfa_srlg()'s tables.  bk_coverage has
+  // HSPF_BK_SRLG_COVERAGE_WORDS words per root.  The default: not supported.
+  virtual BackupOut backup_routes_srlg(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<uint32_t> & /*pfx_ptr*/,
+                                       const std::vector<uint32_t> & /*pfx_vertex*/, const std::vector<uint32_t> & /*pfx_metric*/,
+                                       uint32_t /*table_flags*/, const std::vector<LfaProtect> &, const std::vector<Srlg> &, uint32_t /*lfa_flags*/,
+                                       const TilfaOut * /*tilfa*/) { return BackupOut{}; }
   virtual std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                         const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
                                         uint32_t max_path_metric) = 0;
@@ -1139,6 +1147,72 @@ class HipEngine : public Engine {
       }
     }
     if (ydist) pool_->dev_free(ydist, ybytes);
+    pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    return o;
+  }
+  BackupOut backup_routes_srlg(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
+                               const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
+                               const std::vector<Srlg> &srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rt = static_cast<HipDeviceRoutes &>(routes);
+    BackupOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes; o.mask_words = r.mask_words;
+    if (protect.empty()) return o;
+    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
+      throw std::runtime_error("backup_routes_srlg: the routes are not of this run and prefix table");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("backup_routes_srlg: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const std::vector<hspf_srlg> ss = srlg_raw("backup_routes_srlg: ", protect, srlgs);
+    const size_t ps = (size_t)o.n_protected * 64u * r.mask_words, pp = (size_t)o.n_protected * o.n_prefixes, pw = pp * r.mask_words;
+    const bool with_ti = tilfa && tilfa->supported;
+    if (with_ti && (tilfa->ti_kind.size() != ps || tilfa->ti_via.size() != ps || tilfa->ti_metric.size() != ps || tilfa->ti_p.size() != ps || tilfa->ti_link.size() != ps))
+      throw std::runtime_error("backup_routes_srlg: the TI-LFA result is not of this protect list");
+    const size_t cb = (size_t)o.n_protected * HSPF_BK_SRLG_COVERAGE_WORDS;
+    // one block: bk_cand_mask | bk_node_mask | bk_primary | bk_slot | bk_metric | bk_coverage | ti_via | ti_metric | ti_p | ti_link | bk_kind | bk_flags | ti_kind
+    const size_t total = pw * 16 + pp * 12 + cb * 4 + (with_ti ? ps * 17 : 0) + pp * 2;
+    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    hspf_backup_out out{};
+    out.bk_cand_mask = (uint64_t *)blk; out.bk_node_mask = out.bk_cand_mask + pw;
+    uint32_t *w = (uint32_t *)(out.bk_node_mask + pw);
+    out.bk_primary = w; w += pp; out.bk_slot = w; w += pp; out.bk_metric = w; w += pp; out.bk_coverage = w; w += cb;
+    hspf_tilfa_out ti{};
+    bool ok = true;
+    auto put = [&](uint32_t *&dst, const std::vector<uint32_t> &src) {
+      dst = w; w += src.size();
+      ok = ok && (src.empty() || hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    if (with_ti) { put(ti.ti_via, tilfa->ti_via); put(ti.ti_metric, tilfa->ti_metric); put(ti.ti_p, tilfa->ti_p); put(ti.ti_link, tilfa->ti_link); }
+    uint8_t *b = (uint8_t *)w;
+    out.bk_kind = b; b += pp; out.bk_flags = b; b += pp;
+    if (with_ti) {
+      ti.ti_kind = b;
+      ok = ok && hipMemcpy(ti.ti_kind, tilfa->ti_kind.data(), ps, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    const char *what = "hipMemcpy of the repairs: ";
+    if (ok) {
+      what = "hspf_routes_backup_srlg_device: ";
+      static const uint32_t zero = 0;
+      const hspf_prefix_table tab{o.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
+                                  pfx_metric.empty() ? &zero : pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT};
+      const hspf_routes ro = rt.raw();
+      ok = hspf_routes_backup_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), ss.data(), o.n_protected, lfa_flags,
+                                          &tab, &ro, with_ti ? &ti : nullptr, &out) == HSPF_OK;
+    }
+    auto fetch = [&](auto &vec, const void *src, size_t count) {
+      vec.resize(count);
+      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
+    };
+    if (ok) {
+      fetch(o.bk_kind, out.bk_kind, pp); fetch(o.bk_flags, out.bk_flags, pp); fetch(o.bk_primary, out.bk_primary, pp); fetch(o.bk_slot, out.bk_slot, pp);
+      fetch(o.bk_metric, out.bk_metric, pp); fetch(o.bk_cand_mask, out.bk_cand_mask, pw); fetch(o.bk_node_mask, out.bk_node_mask, pw);
+      fetch(o.bk_coverage, out.bk_coverage, cb);
+    }
     pool_->dev_free(blk, total);
     if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
     return o;

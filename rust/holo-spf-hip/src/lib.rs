@@ -1405,7 +1405,19 @@ impl Engine {
     /// context still holds `table` from the `routes_device` call.
     pub fn routes_backup_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool,
                                 table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
-        self.routes_backup_device_with(tables, protect, None, ignore_overload, table, resident, routes, tilfa)
+        self.routes_backup_device_with(tables, protect, None, None, ignore_overload, table, resident, routes, tilfa)
+    }
+
+    /// `hspf_routes_backup_srlg_device`: `routes_backup_device` whose alternates neither start on nor cross, on their way to the
+    /// PREFIX, a member of a primary's shared-risk group.  `srlgs` as for `lfa_srlg_device` (the tables hold the member endpoints'
+    /// rows); `safe_repairs` is `HSPF_LFA_SRLG_SAFE_REPAIRS`: `tilfa` comes from `rlfa_srlg_device`'s tables, so a primary with
+    /// members may take its repair — unless the repair's forced link is a member (`HSPF_BK_SRLG_PAIR_REFUSED`).  `bk_coverage` has
+    /// `HSPF_BK_SRLG_COVERAGE_WORDS` words per root.
+    #[allow(clippy::too_many_arguments)]
+    pub fn routes_backup_srlg_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], srlgs: &[&SrlgMembers],
+                                     ignore_overload: bool, safe_repairs: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
+                                     tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
+        self.routes_backup_device_with(tables, protect, None, Some((srlgs, safe_repairs)), ignore_overload, table, resident, routes, tilfa)
     }
 
     /// `hspf_routes_backup_lan_device`: `routes_backup_device` with loop-freeness towards the pseudonode of every primary's LAN;
@@ -1415,17 +1427,18 @@ impl Engine {
     pub fn routes_backup_lan_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: &[(&[u32], &[u32])],
                                     ignore_overload: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
                                     tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
-        self.routes_backup_device_with(tables, protect, Some(lans), ignore_overload, table, resident, routes, tilfa)
+        self.routes_backup_device_with(tables, protect, Some(lans), None, ignore_overload, table, resident, routes, tilfa)
     }
 
-    /// The frame of `routes_backup_device` (`lans` None) and `routes_backup_lan_device`.
+    /// The frame of `routes_backup_device` (`lans` and `srlg` None), `routes_backup_lan_device` and `routes_backup_srlg_device`.
     #[allow(clippy::too_many_arguments)]
     fn routes_backup_device_with(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], lans: Option<&[(&[u32], &[u32])]>,
-                                 ignore_overload: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
+                                 srlg: Option<(&[&SrlgMembers], bool)>, ignore_overload: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
                                  tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
         let (np, pf, w) = (protect.len(), table.n_prefixes() as usize, tables.words as usize);
         let lan_raw = match lans { Some(l) => Some(Self::lan_raw("routes_backup_lan_device", protect, l)?), None => None };
-        let cov_words = if lans.is_some() { sys::HSPF_BK_LAN_COVERAGE_WORDS } else { sys::HSPF_BK_COVERAGE_WORDS } as usize;
+        let srlg_raw = match srlg { Some((m, _)) => Some(Self::srlg_raw("routes_backup_srlg_device", protect, m)?), None => None };
+        let cov_words = if srlg.is_some() { sys::HSPF_BK_SRLG_COVERAGE_WORDS } else if lans.is_some() { sys::HSPF_BK_LAN_COVERAGE_WORDS } else { sys::HSPF_BK_COVERAGE_WORDS } as usize;
         if routes.n_prefixes != table.n_prefixes() || routes.words != tables.words {
             return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_device: the routes are not of this table set and table".into() });
         }
@@ -1454,12 +1467,18 @@ impl Engine {
             Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_device: the TI-LFA result is not of this protect list".into() }),
             None => None,
         };
+        // the SRLG call also reads the forced adjacency of a pair
+        let ti_pl = match (tilfa, srlg) {
+            (Some(t), Some(_)) if t.ti_p.len() == slots && t.ti_link.len() == slots => Some((self.device_from(&t.ti_p)?, self.device_from(&t.ti_link)?)),
+            (Some(_), Some(_)) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_srlg_device: the TI-LFA result is not of this protect list".into() }),
+            _ => None,
+        };
         let ti_raw = ti.as_ref().map(|(k, v, m)| sys::hspf_tilfa_out {
             ti_kind: k.p as *mut u8,
-            ti_p: ptr::null_mut(),
+            ti_p: ti_pl.as_ref().map_or(ptr::null_mut(), |x| x.0.p as *mut u32),
             ti_q: ptr::null_mut(),
             ti_via: v.p as *mut u32,
-            ti_link: ptr::null_mut(),
+            ti_link: ti_pl.as_ref().map_or(ptr::null_mut(), |x| x.1.p as *mut u32),
             ti_metric: m.p as *mut u32,
             ti_counts: ptr::null_mut(),
             td_kind: ptr::null_mut(),
@@ -1501,11 +1520,15 @@ impl Engine {
             best_entry: routes.best_entry.p as *mut u32,
             nexthop_mask: routes.nexthop_mask.p as *mut u64,
         };
-        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 }
+            | if matches!(srlg, Some((_, true))) { sys::HSPF_LFA_SRLG_SAFE_REPAIRS } else { 0 };
         let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
         let ti_ptr = ti_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_out);
         let rc = unsafe {
             match &lan_raw {
+                None if srlg_raw.is_some() => sys::hspf_routes_backup_srlg_device(
+                    self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), srlg_raw.as_ref().unwrap().as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, &mut out,
+                ),
                 None => sys::hspf_routes_backup_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, &mut out),
                 Some(l) => sys::hspf_routes_backup_lan_device(
                     self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), l.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, &mut out,
