@@ -1119,9 +1119,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_fu
 // of per-row overhead —, a wave's life = six dependent round trips with at most ~10 row loads out, and an L1 that stalls
 // on pending misses half of the time because a CU never has enough of them in flight.  This kernel:
 //   * link records in a fixed-stride (ELL) copy built with the graph (kb_ell): 16 source byte offsets + 16 costs + 16
-//     wake-up offsets per vertex at addresses that depend on the vertex alone.  The source offsets come through the
-//     SCALAR cache (s_load) straight into the SGPRs the buffer loads take as row offset: no v_readlane, no hazard s_nop;
-//     the costs are one vector load per row with the 16 costs replicated in every 16-lane DPP row, so that
+//     wake-up offsets per vertex at addresses that depend on the vertex alone.  The records of a wave's four rows are 256
+//     contiguous bytes of each array and come with ONE coalesced load per array (lane 16 i + j = entry j of row i); a source
+//     offset goes by v_readlane into the SGPR a buffer load takes as row offset; the 16 costs of a row are spread into
+//     every 16-lane DPP row of a register of their own (lean_spread_rows), so that
 //     `v_add_u32_dpp ... row_newbcast:j` adds cost j to a neighbour's word in ONE instruction;
 //   * a DPP add cannot saturate, so "not reached" is stored as inf_t = (dmax - wmax) << sh instead of all ones: a sum
 //     with any cost stays inside 32 bits, and whatever reaches inf_t is "not reached" again;
@@ -1146,13 +1147,23 @@ template <int J> __device__ __forceinline__ uint32_t dpp_bcast16(uint32_t v) {  
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + J, 0xF, 0xF, false);
 }
 
+// x: lane 16 i + j = word j of row i  ->  out[i]: lane 16 r + j = word j of row i in EVERY 16-lane DPP row r.  Registers only:
+// v_permlane32_swap gathers the rows {0, 1} and {2, 3} into both halves, v_permlane16_swap the single rows (gfx950).
+__device__ __forceinline__ void lean_spread_rows(uint32_t x, uint32_t (&out)[VPW]) {
+  const auto h = __builtin_amdgcn_permlane32_swap(x, x, false, false);            // [r0 r1 r0 r1], [r2 r3 r2 r3]
+  const auto a = __builtin_amdgcn_permlane16_swap(h[0], h[0], false, false);      // [r0 r0 r0 r0], [r1 r1 r1 r1]
+  const auto b = __builtin_amdgcn_permlane16_swap(h[1], h[1], false, false);
+  out[0] = a[0]; out[1] = a[1]; out[2] = b[0]; out[3] = b[1];
+}
+
 struct LeanOut { uint32_t m, macc, bpay; };
 
 template <int J> struct LeanLinks {
-  // sov: lane 16 r + j = row byte offset of link j's source (low byte of link 0: the row's info byte, masked by the caller)
-  static __device__ __forceinline__ void load(uint32_t (&q)[16], __amdgpu_buffer_rsrc_t rs, uint32_t lane4, uint32_t sov) {
-    LeanLinks<J - 1>::load(q, rs, lane4, sov);
-    q[J - 1] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4, rdlane(sov, J - 1), 0);
+  // sov: lane 16 i + j = row byte offset of the source of link j of the wave's row i (low byte of link 0: the row's info byte, masked
+  // by the caller); l0 = 16 i, the lane of the row's first link (uniform)
+  static __device__ __forceinline__ void load(uint32_t (&q)[16], __amdgpu_buffer_rsrc_t rs, uint32_t lane4, uint32_t sov, uint32_t l0) {
+    LeanLinks<J - 1>::load(q, rs, lane4, sov, l0);
+    q[J - 1] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4, rdlane(sov, l0 + (J - 1)), 0);
   }
   static __device__ __forceinline__ void add(uint32_t (&q)[16], uint32_t wk) {
     LeanLinks<J - 1>::add(q, wk);
@@ -1160,7 +1171,7 @@ template <int J> struct LeanLinks {
   }
 };
 template <> struct LeanLinks<0> {
-  static __device__ __forceinline__ void load(uint32_t (&)[16], __amdgpu_buffer_rsrc_t, uint32_t, uint32_t) {}
+  static __device__ __forceinline__ void load(uint32_t (&)[16], __amdgpu_buffer_rsrc_t, uint32_t, uint32_t, uint32_t) {}
   static __device__ __forceinline__ void add(uint32_t (&)[16], uint32_t) {}
 };
 
@@ -1196,9 +1207,9 @@ __device__ __forceinline__ LeanOut lean_minor(uint32_t (&c)[16], uint32_t paym) 
 }
 
 template <int L>
-__device__ __forceinline__ LeanOut lean_case(__amdgpu_buffer_rsrc_t rs, uint32_t lane4, uint32_t sov, uint32_t wk, uint32_t paym) {
+__device__ __forceinline__ LeanOut lean_case(__amdgpu_buffer_rsrc_t rs, uint32_t lane4, uint32_t sov, uint32_t l0, uint32_t wk, uint32_t paym) {
   uint32_t c[16];
-  LeanLinks<L>::load(c, rs, lane4, sov);
+  LeanLinks<L>::load(c, rs, lane4, sov, l0);
   __builtin_amdgcn_s_waitcnt(0x0F70);                             // vmcnt(0): one wait for the row
   return lean_reduce<L>(c, wk, paym);
 }
@@ -1218,11 +1229,12 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
                                            const uint32_t lane, const uint32_t lane4, const uint32_t wbeg, const uint32_t cur, const FusedParams &P,
                                            const uint32_t *__restrict__ roots, const uint32_t root_slot, const uint32_t net_nexthops,
                                            const uint32_t ignore_ovl, const uint32_t due4, const uint32_t fast4, const uint32_t fasth4, const uint32_t fastz4,
-                                           uint32_t (&sov)[VPW], uint32_t (&wk)[VPW], uint32_t (&od)[VPW], uint32_t (&oldq)[VPW], uint32_t (&info)[VPW],
+                                           const uint32_t sov, uint32_t (&wk)[VPW], const uint32_t od, uint32_t (&oldq)[VPW], uint32_t (&info)[VPW],
                                            uint64_t &any, bool &dyn, uint32_t &n_done, uint32_t &n_chg) {
   typedef uint32_t ST;
   const uint32_t paym = (1u << P.sh) - 1u;
   const uint32_t hopm = P.hmax << P.mbits, maskm = (1u << P.mbits) - 1u;
+  const uint32_t lrow = lane >> 4;                                // sov, od: this lane holds an entry of the wave's row `lrow`
   // result of fast row i -> state, wake-ups (info bit 5: more than 16 out-links: they are walked, k_fused's loop)
   auto commit = [&](auto I, uint32_t nw) {
     constexpr int i = decltype(I)::value;
@@ -1233,7 +1245,7 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
     __builtin_amdgcn_raw_buffer_store_b32(nw, rs, lane4, v << 8, 0);          // the whole row: unchanged lanes rewrite their own value
     any |= ch;
     if (MODE == 1) { ++n_chg; return; }                                       // dense: nobody reads stamps
-    if (!(info[i] & 0x20u)) { __builtin_amdgcn_raw_buffer_store_b32(cur + 1u, ra, od[i], 0, 0); return; }   // wake the out-neighbours up
+    if (!(info[i] & 0x20u)) { __builtin_amdgcn_raw_buffer_store_b32(cur + 1u, ra, lrow == (uint32_t)i ? od : 0xFFFFFFFFu, 0, 0); return; }   // wake the out-neighbours up
     const GraphDev &g = gp->g;
     const uint32_t o0 = g.out_ptr[v], o1 = g.out_ptr[v + 1];
     for (uint32_t ob = o0 + lane; ob < o1; ob += 64) __builtin_amdgcn_raw_buffer_store_b32(cur + 1u, ra, g.out_dst[ob] * 4u, 0, 0);
@@ -1249,14 +1261,14 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
     LeanOut r{INF, 0u, INF};
     switch (((info[i] & 0x1Fu) + 1u) >> 1) {
       case 0: break;
-      case 1: r = lean_case<2>(rs, lane4, sov[i], wk[i], paym); break;
-      case 2: r = lean_case<4>(rs, lane4, sov[i], wk[i], paym); break;
-      case 3: r = lean_case<6>(rs, lane4, sov[i], wk[i], paym); break;
-      case 4: r = lean_case<8>(rs, lane4, sov[i], wk[i], paym); break;
-      case 5: r = lean_case<10>(rs, lane4, sov[i], wk[i], paym); break;
-      case 6: r = lean_case<12>(rs, lane4, sov[i], wk[i], paym); break;
-      case 7: r = lean_case<14>(rs, lane4, sov[i], wk[i], paym); break;
-      default: r = lean_case<16>(rs, lane4, sov[i], wk[i], paym); break;
+      case 1: r = lean_case<2>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      case 2: r = lean_case<4>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      case 3: r = lean_case<6>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      case 4: r = lean_case<8>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      case 5: r = lean_case<10>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      case 6: r = lean_case<12>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      case 7: r = lean_case<14>(rs, lane4, sov, 16u * i, wk[i], paym); break;
+      default: r = lean_case<16>(rs, lane4, sov, 16u * i, wk[i], paym); break;
     }
     commit(I, finish(r, info[i]));
   };
@@ -1280,22 +1292,21 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
     for (uint32_t hm = fasth4; hm != 0u; hm &= hm - 1u) {
       const uint32_t i = (uint32_t)__builtin_ctz(hm);
       const uint32_t v = wbeg + i;
-      const uint32_t sov_i = i == 0 ? sov[0] : i == 1 ? sov[1] : i == 2 ? sov[2] : sov[3];
       const uint32_t wk_i = i == 0 ? wk[0] : i == 1 ? wk[1] : i == 2 ? wk[2] : wk[3];
-      const uint32_t od_i = i == 0 ? od[0] : i == 1 ? od[1] : i == 2 ? od[2] : od[3];
+      const uint32_t od_i = lrow == i ? od : 0xFFFFFFFFu;                 // the row's 16 wake-up offsets; the other lanes: out of range = dropped
       const uint32_t old_i = i == 0 ? oldq[0] : i == 1 ? oldq[1] : i == 2 ? oldq[2] : oldq[3];
       const uint32_t inf_i = i == 0 ? info[0] : i == 1 ? info[1] : i == 2 ? info[2] : info[3];
       const uint32_t deg = inf_i & 0x1Fu;                                 // <= 16 (a longer row carries RF_MANY)
       const uint32_t e0 = gp->g.in_ptr[v];
       const uint32_t fpv = gp->g.in_fpos[e0 + min(lane & 15u, deg - 1u)];  // lane j (< 16) = position of link j in its source row
       uint32_t c[16];
-      LeanLinks<16>::load(c, rs, lane4, sov_i);
+      LeanLinks<16>::load(c, rs, lane4, sov, 16u * i);
       __builtin_amdgcn_s_waitcnt(0x0F70);
       LeanLinks<16>::add(c, wk_i);
       const bool slots_on = !(inf_i & 0x80u) || net_nexthops != 0u;       // next hops of a network vertex only on request
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        const uint32_t u = rdlane(sov_i, j) >> 8, fp = rdlane(fpv, j);
+        const uint32_t u = rdlane(sov, 16u * i + j) >> 8, fp = rdlane(fpv, j);
         const uint32_t bit = (slots_on && (uint32_t)j < deg && fp < P.mbits) ? (1u << fp) : 0u;
         c[j] |= (my_root == u) ? bit : 0u;
       }
@@ -1326,18 +1337,17 @@ __device__ __forceinline__ void lean_group(const FusedGraph *__restrict__ gp, co
     for (uint32_t hm = fastz4; hm != 0u; hm &= hm - 1u) {
       const uint32_t i = (uint32_t)__builtin_ctz(hm);
       const uint32_t v = wbeg + i;
-      const uint32_t sov_i = i == 0 ? sov[0] : i == 1 ? sov[1] : i == 2 ? sov[2] : sov[3];
       const uint32_t wk_i = i == 0 ? wk[0] : i == 1 ? wk[1] : i == 2 ? wk[2] : wk[3];
-      const uint32_t od_i = i == 0 ? od[0] : i == 1 ? od[1] : i == 2 ? od[2] : od[3];
+      const uint32_t od_i = lrow == i ? od : 0xFFFFFFFFu;                 // the row's 16 wake-up offsets; the other lanes: out of range = dropped
       const uint32_t old_i = i == 0 ? oldq[0] : i == 1 ? oldq[1] : i == 2 ? oldq[2] : oldq[3];
       const uint32_t inf_i = i == 0 ? info[0] : i == 1 ? info[1] : i == 2 ? info[2] : info[3];
       const uint32_t deg = inf_i & 0x1Fu;                                 // <= 16 (a longer row carries RF_MANY)
-      const uint32_t src_l = sov_i >> 8;                                  // lane 16 r + j: source of link j
-      const bool zl = (lane & 15u) < deg && (wk_i >> P.sh) == 0u && src_l >= v;
+      const uint32_t src_l = sov >> 8;                                    // lane 16 i + j: source of link j of this row
+      const bool zl = lrow == i && (lane & 15u) < deg && (wk_i >> P.sh) == 0u && src_l >= v;
       const bool ul = zl && (zc == nullptr || (zc[src_l] != 0 && zc[v] != 0));
-      const uint32_t zmask = (uint32_t)__ballot(zl) & 0xFFFFu, umask = (uint32_t)__ballot(ul) & 0xFFFFu;
+      const uint32_t zmask = (uint32_t)(__ballot(zl) >> (16u * i)) & 0xFFFFu, umask = (uint32_t)(__ballot(ul) >> (16u * i)) & 0xFFFFu;
       uint32_t c[16];
-      LeanLinks<16>::load(c, rs, lane4, sov_i);
+      LeanLinks<16>::load(c, rs, lane4, sov, 16u * i);
       __builtin_amdgcn_s_waitcnt(0x0F70);
       LeanLinks<16>::add(c, wk_i);
       uint32_t cz = INF, du = INF;
@@ -1499,15 +1509,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fu
   ST *S = st + (size_t)batch * (n + 1u) * 64;                      // slab of n + 1 rows: row n = the pad row (never reached)
   const __amdgpu_buffer_rsrc_t rs = st_rsrc(S, (n + 1u) << 8);
   const uint32_t lane4 = lane * 4u;
-  uint32_t sov[VPW], wk[VPW], od[VPW], oldq[VPW];
+  // The records of the wave's four rows are 256 contiguous bytes of each ELL array: ONE coalesced load per array, lane 16 i + j =
+  // entry j of row i (a row past the end reads the pad row n, lane by lane).  The costs are wanted in every 16-lane DPP row
+  // (row_newbcast): shifted into the distance field, j & 7 into the tag field below it, then spread over four registers without
+  // touching memory (lean_spread_rows).  Four replicated loads, one per row, were measured against this: a dense launch of 15
+  // passes takes 290 us with them, 284 us this way, 294 us before either (profiles/r24_notes.md).
+  static_assert(VPW == 4, "four rows of 16 records = the 64 lanes of one load");
+  const uint32_t e4 = (min(wbeg + (lane >> 4), n) * 16u + (lane & 15u)) * 4u;   // byte offset into the ELL arrays (n < 2^23)
+  uint32_t sov = *(const uint32_t *)((const char *)ell_so + e4);
+  uint32_t wk[VPW], oldq[VPW];
+  lean_spread_rows((*(const uint32_t *)((const char *)ell_w + e4) << P.sh) + ((lane & 7u) << (P.sh - 3u)), wk);
+  const uint32_t od = MODE == 1 ? 0u : *(const uint32_t *)((const char *)ell_od + e4);   // byte offsets into A; pad entries: out of range = dropped
 #pragma unroll
-  for (int i = 0; i < VPW; ++i) {
-    const uint32_t e = (min(wbeg + i, n) * 16u + (lane & 15u)) * 4u;          // byte offset into the ELL arrays (n < 2^23)
-    sov[i] = *(const uint32_t *)((const char *)ell_so + e);
-    wk[i] = *(const uint32_t *)((const char *)ell_w + e);
-    od[i] = MODE == 1 ? 0u : *(const uint32_t *)((const char *)ell_od + e);
-    oldq[i] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4, min(wbeg + i, n - 1) << 8, 0);
-  }
+  for (int i = 0; i < VPW; ++i) oldq[i] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4, min(wbeg + i, n - 1) << 8, 0);
   const uint32_t fast4 = (uint32_t)__ballot(lane < (uint32_t)VPW && hb == 0u) & due4;
   const uint32_t fasth4 = (uint32_t)__ballot(lane < (uint32_t)VPW && (hb & ~RF_ROOT) == RF_HNB) & due4;   // next to a root of the batch (or the row of one), nothing else
   const uint32_t fastz4 = (!ZROWS || P.hc) ? 0u : ((uint32_t)__ballot(lane < (uint32_t)VPW && hb == RF_ZERO) & due4);  // a zero-cost link from a higher-numbered source, nothing else
@@ -1515,12 +1529,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_fu
   const __amdgpu_buffer_rsrc_t ra = st_rsrc(A, n * 4u);
   uint32_t info[VPW];                                             // low byte of ELL entry 0: in-degree | (> 16 out-links) << 5 | network << 7
 #pragma unroll
-  for (int i = 0; i < VPW; ++i) {
-    info[i] = rdlane(sov[i], 0) & 0xFFu;
-    sov[i] &= ~0xFFu;
-    wk[i] = (wk[i] << P.sh) + ((lane & 7u) << (P.sh - 3u));       // cost in the distance field, j & 7 in the tag field below it
-    od[i] = lane < 16u ? od[i] : 0xFFFFFFFFu;                     // byte offsets into A; pad / upper lanes: out of range = dropped
-  }
+  for (int i = 0; i < VPW; ++i) info[i] = rdlane(sov, 16u * i) & 0xFFu;
+  sov &= ~0xFFu;                                                  // (entries 1 .. 15 have a zero low byte)
   uint64_t any = 0ull;
   bool dyn = false;
   uint32_t n_done = 0, n_chg = 0;
