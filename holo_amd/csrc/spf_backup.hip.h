@@ -10,10 +10,11 @@
 // lives in registers.  d_E(p) of the one primary is computed once, in front of the chunks; an ECMP prefix (whose sets are
 // written, no slot is chosen) streams its entries again per chunk and primary.
 //   k_backup       everything but the counts.
-//   k_backup_cov   the coverage: a wave counts the kinds of its prefixes with ballots (grid-stride over the tiles of one
-//                  protected root), then one vector atomic add per wave and kind.
-// The LAN variants (hspf_routes_backup_lan_device) are k_backup_lan, a further instantiation of the same body, and
-// k_backup_cov_lan: d_L(p) of the one primary's LAN is computed once next to d_E(p); a candidate that has passed every plain
+//   k_backup_cov_t<P>   the coverage of every protection mode P (FrrProt, spf_frr_common.hip.h): a wave counts the kinds of its
+//                  prefixes, and the mode's bits of bk_flags, with ballots (grid-stride over the tiles of one protected root),
+//                  then one vector atomic add per wave and word.
+// The LAN variant (hspf_routes_backup_lan_device) is k_backup_lan, a further instantiation of the same body: d_L(p) of the one
+// primary's LAN is computed once next to d_E(p); a candidate that has passed every plain
 // condition is then held against d(N, L) + d_L(p); the per-link repair is taken for a point-to-point primary, and for a LAN
 // primary only under HSPF_LFA_LAN_SAFE_REPAIRS (the caller's word that the repairs come from hspf_rlfa_lan_device's tables).
 // There is no wave-per-prefix path: a prefix with very many advertisers is walked by ONE lane and holds its wave back.
@@ -42,22 +43,28 @@ struct BackupArgs {
   uint64_t *cand_mask, *node_mask; uint32_t *coverage;
 };
 
-// one term d(X, v) + m of d_X(p); BK_NO_DIST when v is not in X's SPT
-__device__ __forceinline__ uint64_t bk_term(const BackupArgs &a, size_t xv, uint32_t m) {
+// one term d(X, v) + m of d_X(p); BK_NO_DIST when v is not in X's SPT.  Args: BackupArgs, or BackupNodeArgs (spf_backup_node.hip.h)
+template <class Args>
+__device__ __forceinline__ uint64_t bk_term(const Args &a, size_t xv, uint32_t m) {
   const uint32_t d = a.dist[xv];
   if (!(a.flags[xv] & 1u) || d == LFA_NONE) return BK_NO_DIST;
   const uint64_t s = (uint64_t)d + m;
   return (a.sat && s > 0xFFFFFFFFull) ? 0xFFFFFFFFull : s;
 }
 
-// d_X(p) for the row of X: the entries lo .. hi streamed once
-__device__ __forceinline__ uint64_t bk_dist_to_prefix(const BackupArgs &a, uint32_t row, uint32_t lo, uint32_t hi) {
+// d_X(p) for the row of X: the entries lo .. hi streamed once.  With `own`: does the entry of X itself attain it?
+template <class Args>
+__device__ __forceinline__ uint64_t bk_dist_to_prefix(const Args &a, uint32_t row, uint32_t lo, uint32_t hi, uint32_t X = LFA_NONE, bool *own = nullptr) {
   uint64_t best = BK_NO_DIST;
+  bool mine = false;
   const size_t base = (size_t)row * a.n;
   for (uint32_t e = lo; e < hi; ++e) {
-    const uint64_t t = bk_term(a, base + a.pfx_vertex[e], a.pfx_metric[e]);
-    best = t < best ? t : best;
+    const uint32_t v = a.pfx_vertex[e];
+    const uint64_t t = bk_term(a, base + v, a.pfx_metric[e]);
+    if (t < best) { best = t; mine = v == X; }
+    else if (t == best && v == X && t != BK_NO_DIST) mine = true;
   }
+  if (own) *own = mine;
   return best;
 }
 
@@ -213,40 +220,34 @@ __device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &
 __global__ __launch_bounds__(256) void k_backup(BackupArgs a) { backup_body<false>(a, LanArgs{}); }
 __global__ __launch_bounds__(256) void k_backup_lan(BackupArgs a, LanArgs la) { backup_body<true>(a, la); }
 
-// coverage[pi][kind]: ballots per tile, the counts kept in lanes 0 .. 6, one vector atomic add per wave and kind
-__global__ __launch_bounds__(256) void k_backup_cov(BackupArgs a) {
+// coverage[pi][]: the seven kinds, then the prefixes with one bit of bk_flags each:
+//   Lan   HSPF_LFA_LAN_PRIMARY, HSPF_LFA_LAN_REFUSED;   Srlg   HSPF_BK_SRLG_PRIMARY, HSPF_LFA_SRLG_REFUSED, HSPF_BK_SRLG_PAIR_REFUSED
+constexpr uint32_t bk_cov_words(FrrProt P) { return BK_KINDS + (P == FrrProt::Plain ? 0u : P == FrrProt::Lan ? 2u : 3u); }
+constexpr uint32_t bk_cov_flag(FrrProt P, uint32_t j) { return P == FrrProt::Lan ? 0x20u << j : j == 0 ? 0x01u : j == 1 ? 0x80u : 0x02u; }
+
+// ballots per tile, the counts kept in lanes 0 .. CW - 1, one vector atomic add per wave and word
+template <FrrProt P>
+__global__ __launch_bounds__(256) void k_backup_cov_t(BackupArgs a) {
+  constexpr uint32_t CW = bk_cov_words(P);
   const uint32_t pi = blockIdx.y, lane = threadIdx.x & 63u;
-  const uint8_t *kinds = a.bk_kind + (size_t)pi * a.n_pfx;
+  const uint8_t *kinds = a.bk_kind + (size_t)pi * a.n_pfx, *fls = a.bk_flags + (size_t)pi * a.n_pfx;
   uint32_t mine = 0;
   for (uint32_t t0 = blockIdx.x * 256u; t0 < a.n_pfx; t0 += gridDim.x * 256u) {    // t0 + 255 is the last prefix of the workgroup's tile
     const uint32_t p = t0 + threadIdx.x;
     const uint32_t kind = p < a.n_pfx ? kinds[p] : BK_KINDS;
+    uint32_t fl = 0;
+    if constexpr (P != FrrProt::Plain) fl = p < a.n_pfx ? fls[p] : 0u;
 #pragma unroll
-    for (uint32_t j = 0; j < BK_KINDS; ++j) {
-      const uint32_t c = (uint32_t)__popcll(__ballot(kind == j));
-      if (lane == j) mine += c;
-    }
-  }
-  if (lane < BK_KINDS && mine) atomicAdd(a.coverage + (size_t)pi * BK_KINDS + lane, mine);
-}
-
-// the LAN call's coverage[pi][9]: the seven kinds, then the prefixes with HSPF_LFA_LAN_PRIMARY and with HSPF_LFA_LAN_REFUSED in bk_flags
-__global__ __launch_bounds__(256) void k_backup_cov_lan(BackupArgs a) {
-  const uint32_t pi = blockIdx.y, lane = threadIdx.x & 63u;
-  const uint8_t *kinds = a.bk_kind + (size_t)pi * a.n_pfx, *fls = a.bk_flags + (size_t)pi * a.n_pfx;
-  uint32_t mine = 0;
-  for (uint32_t t0 = blockIdx.x * 256u; t0 < a.n_pfx; t0 += gridDim.x * 256u) {
-    const uint32_t p = t0 + threadIdx.x;
-    const uint32_t kind = p < a.n_pfx ? kinds[p] : BK_KINDS;
-    const uint32_t fl = p < a.n_pfx ? fls[p] : 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < BK_KINDS + 2; ++j) {
-      const bool hit = j < BK_KINDS ? kind == j : ((fl >> (5u + j - BK_KINDS)) & 1u) != 0;
+    for (uint32_t j = 0; j < CW; ++j) {
+      const bool hit = j < BK_KINDS ? kind == j : (fl & bk_cov_flag(P, j - BK_KINDS)) != 0;
       const uint32_t c = (uint32_t)__popcll(__ballot(hit));
       if (lane == j) mine += c;
     }
   }
-  if (lane < BK_KINDS + 2 && mine) atomicAdd(a.coverage + (size_t)pi * (BK_KINDS + 2) + lane, mine);
+  if (lane < CW && mine) atomicAdd(a.coverage + (size_t)pi * CW + lane, mine);
 }
+constexpr auto k_backup_cov = k_backup_cov_t<FrrProt::Plain>;
+constexpr auto k_backup_cov_lan = k_backup_cov_t<FrrProt::Lan>;
+constexpr auto k_backup_cov_srlg = k_backup_cov_t<FrrProt::Srlg>;
 
 }  // namespace

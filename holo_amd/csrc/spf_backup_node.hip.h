@@ -44,25 +44,6 @@ struct BackupNodeArgs {
   uint8_t *bn_kind; uint32_t *bn_primary, *bn_p, *bn_q, *bn_link, *bn_via, *bn_metric, *bn_set_pq, *bn_set_pair, *bn_cov;
 };
 
-// d_E(p) from the row of E in the forward set (BK_NO_DIST: no advertiser is reached); own: E's own entry attains it.  The twin of
-// bk_dist_to_prefix / bk_term in spf_backup.hip.h (the same terms, plus the own-entry bit k_backup keeps per candidate): a change to
-// how d_X(p) is formed belongs in both.  Kept apart so that k_backup compiles to what it was.
-__device__ __forceinline__ uint64_t bn_dist_from_nbr(const BackupNodeArgs &a, uint32_t row, uint32_t E, uint32_t lo, uint32_t hi, bool &own) {
-  uint64_t best = BK_NO_DIST;
-  own = false;
-  const size_t base = (size_t)row * a.n;
-  for (uint32_t e = lo; e < hi; ++e) {
-    const uint32_t v = a.pfx_vertex[e];
-    const uint32_t d = a.dist[base + v];
-    if (!(a.flags[base + v] & 1u) || d == LFA_NONE) continue;
-    uint64_t t = (uint64_t)d + a.pfx_metric[e];
-    if (a.sat && t > 0xFFFFFFFFull) t = 0xFFFFFFFFull;
-    if (t < best) { best = t; own = v == E; }
-    else if (t == best && v == E) own = true;
-  }
-  return best;
-}
-
 // One list (node[j], metric[j], j < L, at `lb`) against prefix entries lo .. hi: bit j of `set` = entry j protects; the smallest
 // metric[j] + d_Y(p) among them, then the smaller j.  dEp is a number.
 __device__ __forceinline__ void bn_walk(const BackupNodeArgs &a, const uint32_t *node, const uint32_t *metric, size_t lb, uint32_t L,
@@ -125,7 +106,7 @@ __global__ __launch_bounds__(256) void k_backup_node(BackupNodeArgs a) {
       const uint32_t lo = a.pfx_ptr[p], hi = a.pfx_ptr[p + 1];
       const size_t so = (size_t)pi * a.stride + p0;
       bool own;
-      const uint64_t dEp = bn_dist_from_nbr(a, tb.row[p0], E, lo, hi, own);
+      const uint64_t dEp = bk_dist_to_prefix(a, tb.row[p0], lo, hi, E, &own);        // (from the forward set; own: E's own entry attains it)
       if (dEp != BK_NO_DIST) {
         uint64_t best;
         uint32_t bj;

@@ -1,7 +1,9 @@
 // spf_backup_srlg.hip.h — per-prefix backup routes that avoid the shared-risk link groups of the primaries
 // (hspf_routes_backup_srlg_device; the semantics are written down once, in include/holo_spf_hip.h).  The kernels of
 // spf_backup.hip.h and spf_srlg.hip.h are not instantiated again: their text is untouched, and what they share (BackupArgs,
-// bk_term, bk_dist_to_prefix, bk_less, srlg_tab, frr_tab, frr_primaries) is used from here.
+// bk_term, bk_dist_to_prefix, bk_less, srlg_tab, frr_tab, frr_primaries) is used from here.  (k_backup_srlg is still a copy of
+// backup_body with the member conditions in it: as an instantiation of one body over FrrProt it lost the registers of d_{b_i}(p)
+// to scratch, profiles/r25_notes.md.)
 //
 // Staged blocks.  The slot tables and the prefix table are those of hspf_routes_backup_device; the member block is srlg_stage's
 // (spf_srlg.hip.h), with ONE column appended behind `loc`:  pos [NM], the member's position within its tail's row.  No offset that
@@ -21,7 +23,7 @@
 //                 evaluates no member term and streams nothing more than k_backup does.
 //   ECMP          sets only: a candidate that passed the plain conditions re-streams the entries per primary and member, as the
 //                 plain kernel re-streams them per primary.
-//   k_backup_cov_srlg   the ballot-per-kind shape of k_backup_cov_lan, ten words.
+//   k_backup_cov_srlg   k_backup_cov_t<Srlg> (spf_backup.hip.h), ten words.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,7 +42,6 @@ static_assert(SRLG_POS_COL >= SRLG_TAB_COLS && SRLG_POS_COL < SRLG_STAGED_COLS, 
 __device__ __forceinline__ const uint32_t *srlg_pos(const SrlgTab &st) { return st.tail + (size_t)SRLG_POS_COL * st.NM; }      // (tail is column 0)
 
 constexpr uint32_t BKS_MCH = 8;                    // member rows per stream of a prefix's entries
-constexpr uint32_t BK_SRLG_CW = 10;                // HSPF_BK_SRLG_COVERAGE_WORDS (held to it in spf_frr.hip.h)
 
 struct BackupSrlgArgs {
   SrlgArgs sa;
@@ -262,26 +263,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
   }
   fl |= sfl;
   a.bk_kind[oo] = (uint8_t)kind; a.bk_primary[oo] = prim; a.bk_slot[oo] = slot; a.bk_metric[oo] = met; a.bk_flags[oo] = (uint8_t)fl;
-}
-
-// coverage[pi][10]: the seven kinds, then the prefixes with HSPF_BK_SRLG_PRIMARY, HSPF_LFA_SRLG_REFUSED and HSPF_BK_SRLG_PAIR_REFUSED in
-// bk_flags; ballots per tile, the counts kept in lanes 0 .. 9, one vector atomic add per wave and word
-__global__ __launch_bounds__(256) void k_backup_cov_srlg(BackupArgs a) {
-  const uint32_t pi = blockIdx.y, lane = threadIdx.x & 63u;
-  const uint8_t *kinds = a.bk_kind + (size_t)pi * a.n_pfx, *fls = a.bk_flags + (size_t)pi * a.n_pfx;
-  uint32_t mine = 0;
-  for (uint32_t t0 = blockIdx.x * 256u; t0 < a.n_pfx; t0 += gridDim.x * 256u) {
-    const uint32_t p = t0 + threadIdx.x;
-    const uint32_t kind = p < a.n_pfx ? kinds[p] : BK_KINDS;
-    const uint32_t fl = p < a.n_pfx ? fls[p] : 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < BK_SRLG_CW; ++j) {
-      const bool hit = j < BK_KINDS ? kind == j : j == BK_KINDS ? (fl & 0x01u) != 0 : j == BK_KINDS + 1 ? (fl & 0x80u) != 0 : (fl & 0x02u) != 0;
-      const uint32_t c = (uint32_t)__popcll(__ballot(hit));
-      if (lane == j) mine += c;
-    }
-  }
-  if (lane < BK_SRLG_CW && mine) atomicAdd(a.coverage + (size_t)pi * BK_SRLG_CW + lane, mine);
 }
 
 }  // namespace

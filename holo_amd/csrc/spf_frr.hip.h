@@ -340,110 +340,58 @@ int lfa_walk(const hspf_csr *csr, uint32_t root, uint32_t *out_total_slots, F &&
   });
 }
 
-// the one frame of hspf_routes_backup_device (with_lan false, `lan` unread) and hspf_routes_backup_lan_device
-int routes_backup(hspf_ctx *ctx, const char *fn, bool with_lan, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+static_assert(bk_cov_words(FrrProt::Plain) == HSPF_BK_COVERAGE_WORDS && bk_cov_words(FrrProt::Lan) == HSPF_BK_LAN_COVERAGE_WORDS &&
+              bk_cov_words(FrrProt::Srlg) == HSPF_BK_SRLG_COVERAGE_WORDS, "the coverage kernel's widths are the header's");
+
+// The one frame of hspf_routes_backup_device, hspf_routes_backup_lan_device and hspf_routes_backup_srlg_device: `lan` is read in
+// the mode Lan alone, `srlg` in the mode Srlg alone.
+int routes_backup(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
-                  const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
-                  const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
+                  const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                  const hspf_prefix_table *t, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
+    const bool with_lan = mode == FrrProt::Lan, with_srlg = mode == FrrProt::Srlg;
     auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
     if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
     if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
     if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
       return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
-    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric)) return bad("NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric || (with_srlg && (!tilfa_dev->ti_p || !tilfa_dev->ti_link))))
+      return bad(with_srlg ? "NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev" : "NULL ti_kind / ti_via / ti_metric in tilfa_dev");
     int rc;
     if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
     if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
     if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
     if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
     if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
+    if (with_srlg && (rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
     if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
-    std::vector<uint32_t> tab, ltab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0;
+    std::vector<uint32_t> tab, mtab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0, max_nms = 0;
     size_t max_gather = 0;
     LanArgs la{};
+    SrlgArgs sa{};
     hipStream_t s = ctx->stream;
     if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
-        (with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, ltab, &la, &max_gather)))) {
+        (with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, mtab, &la, &max_gather))) ||
+        (with_srlg && (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms)))) {
       (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
       return rc;
     }
-    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * (with_lan ? HSPF_BK_LAN_COVERAGE_WORDS : HSPF_BK_COVERAGE_WORDS) * 4, s));
+    const uint32_t coverage_words = with_lan ? HSPF_BK_LAN_COVERAGE_WORDS : with_srlg ? HSPF_BK_SRLG_COVERAGE_WORDS : HSPF_BK_COVERAGE_WORDS;
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * coverage_words * 4, s));
     if (!t->n_prefixes) {                               // nothing to launch
       HIPCHK(ctx, hipStreamSynchronize(s));
       return HSPF_OK;
     }
     const LfaArgs ga = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
                                 : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    if (with_srlg) srlg_gather(ctx, ga, sa, n_prot, max_gather);
     BackupArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
     a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
     a.lan_repairs = (with_lan && (lfa_flags & HSPF_LFA_LAN_SAFE_REPAIRS)) ? 1u : 0u;
-    a.dist = dist_dev; a.flags = flags_dev;
-    a.tab = ga.tab; a.scal = ga.scal;
-    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
-    a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
-    if (tilfa_dev) { a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric; }
-    a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
-    a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
-    const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
-    if (with_lan) {
-      hipLaunchKernelGGL(k_backup_lan, dim3(n_tiles, n_prot), dim3(256), 0, s, a, la);
-      hipLaunchKernelGGL(k_backup_cov_lan, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL(k_backup, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
-      hipLaunchKernelGGL(k_backup_cov, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
-    }
-    return frr_finish(ctx, with_lan ? "k_backup_lan" : "k_backup");
-  });
-}
-
-static_assert(BK_SRLG_CW == HSPF_BK_SRLG_COVERAGE_WORDS, "the coverage kernel's width is the header's");
-
-// hspf_routes_backup_srlg_device: the frame of routes_backup with the member block of the SRLG calls next to the slot tables
-int routes_backup_srlg(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
-                       const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
-                       const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
-                       const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_routes_backup_srlg_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
-    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
-    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
-      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
-    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric || !tilfa_dev->ti_p || !tilfa_dev->ti_link))
-      return bad("NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
-    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if ((rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
-    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
-    std::vector<uint32_t> tab, stab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0, max_nms = 0;
-    size_t max_gather = 0;
-    SrlgArgs sa{};
-    hipStream_t s = ctx->stream;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
-        (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, stab, &sa, &max_gather, &max_nms))) {
-      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
-      return rc;
-    }
-    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * HSPF_BK_SRLG_COVERAGE_WORDS * 4, s));
-    if (!t->n_prefixes) {                               // nothing to launch
-      HIPCHK(ctx, hipStreamSynchronize(s));
-      return HSPF_OK;
-    }
-    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    srlg_gather(ctx, ga, sa, n_prot, max_gather);
-    BackupArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
-    a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
     a.dist = dist_dev; a.flags = flags_dev;
     a.tab = ga.tab; a.scal = ga.scal;
     a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
@@ -457,9 +405,67 @@ int routes_backup_srlg(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint
     a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
     a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
     const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
-    hipLaunchKernelGGL(k_backup_srlg, dim3(n_tiles, n_prot), dim3(256), 0, s, a, b);
-    hipLaunchKernelGGL(k_backup_cov_srlg, dim3(std::min(n_tiles, 64u), n_prot), dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_backup_srlg");
+    const dim3 grid(n_tiles, n_prot), cgrid(std::min(n_tiles, 64u), n_prot);
+    if (with_lan) {
+      hipLaunchKernelGGL(k_backup_lan, grid, dim3(256), 0, s, a, la);
+      hipLaunchKernelGGL(k_backup_cov_lan, cgrid, dim3(256), 0, s, a);
+    } else if (with_srlg) {
+      hipLaunchKernelGGL(k_backup_srlg, grid, dim3(256), 0, s, a, b);
+      hipLaunchKernelGGL(k_backup_cov_srlg, cgrid, dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL(k_backup, grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL(k_backup_cov, cgrid, dim3(256), 0, s, a);
+    }
+    return frr_finish(ctx, with_lan ? "k_backup_lan" : with_srlg ? "k_backup_srlg" : "k_backup");
+  });
+}
+
+// The one frame of hspf_lfa_device, hspf_lfa_lan_device and hspf_lfa_srlg_device (`lan`, `srlg`: as routes_backup)
+int lfa_call(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+             const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+             const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    const bool with_lan = mode == FrrProt::Lan, with_srlg = mode == FrrProt::Srlg;
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
+    if (with_srlg && (rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
+    std::vector<uint32_t> tab, mtab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0, max_nms = 0;
+    size_t max_gather = 0;
+    LanArgs la{};
+    SrlgArgs sa{};
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if ((with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, mtab, &la, &max_gather))) ||
+        (with_srlg && (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms)))) {
+      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
+      return rc;
+    }
+    const uint32_t coverage_words = with_lan ? HSPF_LFA_LAN_COVERAGE_WORDS : with_srlg ? HSPF_LFA_SRLG_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
+    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * coverage_words * 4, s));
+    LfaArgs a = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
+                         : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    if (with_srlg) srlg_gather(ctx, a, sa, n_prot, max_gather);
+    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
+    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
+    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
+    const bool one = max_k <= 64;                       // every root's slots fit one mask word: the tables go to LDS
+    if (with_lan) {
+      if (one) hipLaunchKernelGGL(k_lfa_lan<true>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Lan>{la});
+      else hipLaunchKernelGGL(k_lfa_lan<false>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Lan>{la});
+    } else if (with_srlg) {
+      if (one) hipLaunchKernelGGL(k_lfa_srlg<true>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Srlg>{sa});
+      else hipLaunchKernelGGL(k_lfa_srlg<false>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Srlg>{sa});
+    } else {
+      if (one) hipLaunchKernelGGL(k_lfa<true>, grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
+    }
+    return frr_finish(ctx, with_lan ? "k_lfa_lan" : with_srlg ? "k_lfa_srlg" : "k_lfa");
   });
 }
 
@@ -552,60 +558,15 @@ int hspf_lfa_lan_candidates(const hspf_csr *csr, uint32_t root, uint32_t cap, ui
 int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_lfa_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_COVERAGE_WORDS * 4, s));
-    LfaArgs a = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
-    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
-    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
-    if (max_k <= 64) hipLaunchKernelGGL(k_lfa<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_lfa");
-  });
+  return lfa_call(ctx, "hspf_lfa_device", FrrProt::Plain, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr, nullptr, n_prot,
+                  lfa_flags, out_dev);
 }
 
 int hspf_lfa_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                         const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_lfa_lan_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
-    std::vector<uint32_t> tab, ltab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0;
-    size_t max_gather = 0;
-    LanArgs la{};
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = lan_stage(ctx, fn, prot, lan, n_prot, ltab, &la, &max_gather))) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      return rc;
-    }
-    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_LAN_COVERAGE_WORDS * 4, s));
-    LfaArgs a = frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la);
-    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
-    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
-    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
-    if (max_k <= 64) hipLaunchKernelGGL(k_lfa_lan<true>, grid, dim3(256), 0, s, a, la);
-    else hipLaunchKernelGGL(k_lfa_lan<false>, grid, dim3(256), 0, s, a, la);
-    return frr_finish(ctx, "k_lfa_lan");
-  });
+  return lfa_call(ctx, "hspf_lfa_lan_device", FrrProt::Lan, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, lan, nullptr, n_prot,
+                  lfa_flags, out_dev);
 }
 
 // ---- remote loop-free alternates (include/holo_spf_hip.h "remote loop-free alternates on device"; kernels: spf_rlfa.hip.h) ----
@@ -722,35 +683,8 @@ int hspf_srlg_members(const hspf_csr *csr, uint32_t root, const uint32_t *grp_pt
 int hspf_lfa_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                          const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_lfa_srlg_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
-    std::vector<uint32_t> tab, stab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0, max_nms = 0;
-    size_t max_gather = 0;
-    SrlgArgs sa{};
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = srlg_stage(ctx, fn, prot, srlg, n_prot, stab, &sa, &max_gather, &max_nms))) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      return rc;
-    }
-    HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * HSPF_LFA_SRLG_COVERAGE_WORDS * 4, s));
-    LfaArgs a = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    srlg_gather(ctx, a, sa, n_prot, max_gather);
-    a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
-    a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
-    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
-    if (max_k <= 64) hipLaunchKernelGGL(k_lfa_srlg<true>, grid, dim3(256), 0, s, a, sa);
-    else hipLaunchKernelGGL(k_lfa_srlg<false>, grid, dim3(256), 0, s, a, sa);
-    return frr_finish(ctx, "k_lfa_srlg");
-  });
+  return lfa_call(ctx, "hspf_lfa_srlg_device", FrrProt::Srlg, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr, srlg, n_prot,
+                  lfa_flags, out_dev);
 }
 
 int hspf_rlfa_srlg_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
@@ -809,8 +743,8 @@ int hspf_routes_backup_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
                                    const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
                                    const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
                                    hspf_backup_out *out_dev) {
-  return routes_backup_srlg(ctx, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, srlg, n_prot, lfa_flags, table, routes_dev,
-                            tilfa_dev, out_dev);
+  return routes_backup(ctx, "hspf_routes_backup_srlg_device", FrrProt::Srlg, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr,
+                       srlg, n_prot, lfa_flags, table, routes_dev, tilfa_dev, out_dev);
 }
 
 // ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----
@@ -867,8 +801,8 @@ int hspf_routes_backup_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_row
                               const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                               const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
                               const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
-  return routes_backup(ctx, "hspf_routes_backup_device", false, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr, n_prot,
-                       lfa_flags, t, routes_dev, tilfa_dev, out_dev);
+  return routes_backup(ctx, "hspf_routes_backup_device", FrrProt::Plain, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr,
+                       nullptr, n_prot, lfa_flags, t, routes_dev, tilfa_dev, out_dev);
 }
 
 int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
@@ -876,8 +810,8 @@ int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n
                                   const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
                                   const hspf_prefix_table *t, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
                                   hspf_backup_out *out_dev) {
-  return routes_backup(ctx, "hspf_routes_backup_lan_device", true, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, lan, n_prot,
-                       lfa_flags, t, routes_dev, tilfa_dev, out_dev);
+  return routes_backup(ctx, "hspf_routes_backup_lan_device", FrrProt::Lan, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, lan,
+                       nullptr, n_prot, lfa_flags, t, routes_dev, tilfa_dev, out_dev);
 }
 
 // ---- node-protecting remote LFA (include/holo_spf_hip.h "node-protecting remote loop-free alternates on device"; kernels:

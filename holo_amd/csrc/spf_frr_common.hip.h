@@ -95,6 +95,30 @@ __device__ __forceinline__ void frr_primaries(const FrrTab &t, const uint64_t *p
   }
 }
 
+// f(q) for the primaries q of a destination in ascending order, until one returns false: did every one return true?
+template <class F>
+__device__ __forceinline__ bool frr_all_primaries(const FrrTab &t, const uint64_t *pm, F &&f) {
+  for (uint32_t w = 0; w < t.Wk; ++w) {
+    uint64_t x = frr_word(t, pm, w);
+    while (x) {
+      const uint32_t q = w * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
+      x &= x - 1;
+      if (!f(q)) return false;
+    }
+  }
+  return true;
+}
+
+// What a call protects against on top of the link itself: nothing more, the pseudonode of a primary's LAN (RFC 5286 section 3.3),
+// or the shared-risk link group of a primary.  A kernel family has ONE body, a template over the mode; per family and mode
+//   <Family>Prot<P>   the kernel arguments of the mode (empty for Plain), passed to the kernel next to the family's own;
+//   <Family>Lane<P>   what a lane keeps for the mode next to the body's own state (empty for Plain), with the mode's conditions
+//                     as members where they are more than a line;
+// selected with `if constexpr`: an instantiation holds nothing of another mode.  The Srlg specialisations stand in spf_srlg.hip.h,
+// next to the member block they read, and the Srlg kernels are instantiated there.  (Folded so far: lfa_body in spf_lfa.hip.h and
+// k_backup_cov_t in spf_backup.hip.h; k_backup_srlg is still its own body, see spf_backup_srlg.hip.h.)
+enum class FrrProt { Plain, Lan, Srlg };
+
 // the LAN block of the call (both NULL in a call without one), and the view of one protected root over it
 struct LanArgs { const uint32_t *ltab; uint32_t *lscal; };
 struct LanTab {

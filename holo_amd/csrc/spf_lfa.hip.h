@@ -15,8 +15,10 @@
 //                  the K x K matrix sit in LDS (at most 18.3 KB), the sets are two registers.  ONE = false: any K, tables
 //                  and matrix are read through the caches (K = 128: 64 KB of matrix, L2-resident), the sets are produced
 //                  word by word.
+// One source per kernel: lfa_body<ONE, P> is every streaming kernel, P the protection mode (FrrProt, spf_frr_common.hip.h);
+// k_lfa<ONE>, k_lfa_lan<ONE> and k_lfa_srlg<ONE> (spf_srlg.hip.h, with the Srlg mode's conditions) are its instantiations.
 // The LAN variants (hspf_lfa_lan_device: RFC 5286 section 3.3, loop-freeness with respect to the pseudonode of a primary's LAN)
-// are further instantiations of the same bodies, k_lfa_gather_lan and k_lfa_lan<ONE>.  The gather adds d(N_k, L) for the
+// are k_lfa_gather_lan and k_lfa_lan<ONE>.  The gather adds d(N_k, L) for the
 // distinct LANs L of S — a [K][NL] block indexed by a compact LAN index, not a second K x K matrix — and the streaming kernel
 // reads it through the caches, only for a candidate that has passed every plain condition at a destination whose primary
 // crosses a LAN: the LDS footprint of ONE = true is that of k_lfa<true> (plus two coverage words), and a table set without LANs
@@ -69,9 +71,22 @@ __device__ __forceinline__ void lfa_gather_body(const LfaArgs &a, const LanArgs 
 __global__ __launch_bounds__(256) void k_lfa_gather(LfaArgs a) { lfa_gather_body<false>(a, LanArgs{}); }
 __global__ __launch_bounds__(256) void k_lfa_gather_lan(LfaArgs a, LanArgs la) { lfa_gather_body<true>(a, la); }
 
-template <bool ONE, bool LAN>
-__device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
-  constexpr uint32_t NC = LAN ? 7 : 5;                                             // alt_flags bits that are counted
+
+// The mode's kernel arguments, and its lane state (FrrProt, spf_frr_common.hip.h).  applies: the mode has a say at this destination
+// (some primary crosses a LAN of S / has members).
+template <FrrProt P> struct LfaProt {};
+template <> struct LfaProt<FrrProt::Lan> { LanArgs la; };
+template <FrrProt P> struct LfaLane {};
+template <> struct LfaLane<FrrProt::Lan> {
+  LanTab lt;
+  uint32_t li0 = LFA_NONE, dL0D = LFA_NONE;                                        // the one primary's LAN and d(L, D)
+  bool applies = false;
+};
+
+template <bool ONE, FrrProt P>
+__device__ __forceinline__ void lfa_body(const LfaArgs &a, const LfaProt<P> &pa) {
+  constexpr bool LAN = P == FrrProt::Lan, SRLG = P == FrrProt::Srlg;
+  constexpr uint32_t NC = P == FrrProt::Plain ? 5 : 7;                             // the five alt_flags bits, then the mode's two counts
   __shared__ uint32_t s_cov[NC];
   __shared__ uint32_t s_tab[ONE ? (FRR_COLS + 1) * 64 : 1];             // the columns, then d(N_k, S)
   __shared__ uint32_t s_m[ONE ? 64 * 64 : 1];
@@ -94,8 +109,9 @@ __device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
   const bool in = valid && D != S && (a.flags[sd] & 1u) && dSD != LFA_NONE;
   uint32_t fl = 0, aslot = LFA_NONE, amet = 0;
   uint64_t cw = 0, nw = 0;                                                         // ONE: the two sets
-  LanTab lt{};
-  if constexpr (LAN) lt = lan_tab(la, pi, K);
+  LfaLane<P> ml;
+  if constexpr (LAN) ml.lt = lan_tab(pa.la, pi, K);
+  if constexpr (SRLG) ml.open(pa, pi, K);
   if (in) {
     const uint64_t *pm = a.mask + sd * W;
     uint32_t np, p0;
@@ -105,17 +121,17 @@ __device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
     if (np == 1) {
       rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
       if (E0 != LFA_NONE) dE0D = a.dist[(size_t)tb.row[p0] * n + D];
+      if constexpr (LAN) {
+        ml.li0 = ml.lt.li[p0];
+        ml.applies = ml.li0 != LFA_NONE;
+        if (ml.applies) ml.dL0D = a.dist[(size_t)ml.lt.lrow[p0] * n + D];
+      }
+      if constexpr (SRLG) ml.one_primary(p0);
+    } else if (np >= 2) {
+      if constexpr (LAN) ml.applies = lan_any_primary(tb, ml.lt, pm);
+      if constexpr (SRLG) ml.any_primary(tb, pm);
     }
-    uint32_t li0 = LFA_NONE, dL0D = LFA_NONE;                                      // LAN: the one primary's LAN and d(L, D)
-    bool lanp = false;                                                             // LAN: some primary crosses a LAN of S
-    if constexpr (LAN) {
-      if (np == 1) {
-        li0 = lt.li[p0];
-        lanp = li0 != LFA_NONE;
-        if (lanp) dL0D = a.dist[(size_t)lt.lrow[p0] * n + D];
-      } else if (np >= 2) lanp = lan_any_primary(tb, lt, pm);
-      if (lanp) fl |= 0x20u;
-    }
+    if constexpr (LAN) { if (ml.applies) fl |= 0x20u; }
     bool have = false, bnode = false, bdown = false;
     uint64_t bsum = 0;
     uint32_t ci = 0;
@@ -128,16 +144,19 @@ __device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
         if (!lfa_less(dND, tb.dns[k], dSD)) continue;                               // loop-free
         if ((tb.cf[k] & 1u) && !a.ignore_overload && tb.nbr[k] != D) continue;       // an overloaded neighbour carries no transit traffic
         bool ok = true, nd = false;
+        const uint32_t rlk = tb.rl[k];
         if (np == 1) {
-          ok = tb.rl[k] != rl0;
+          ok = rlk != rl0;
           if constexpr (LAN) {                                                     // every plain condition holds: now the pseudonode
-            if (ok && lanp && !lfa_less(dND, lt.ml[k * lt.NL + li0], dL0D)) { ok = false; fl |= 0x40u; }
+            if (ok && ml.applies && !lfa_less(dND, ml.lt.ml[k * ml.lt.NL + ml.li0], ml.dL0D)) { ok = false; fl |= 0x40u; }
+          }
+          if constexpr (SRLG) {                                                    // ... now the group
+            if (ok && ml.applies && !ml.safe_one(a, k, rlk, p0, dND, D)) { ok = false; fl |= 0x80u; }
           }
           nd = ok && E0 != LFA_NONE && lfa_less(dND, tb.m[k * K + p0], dE0D);
         } else if (np >= 2) {
           uint32_t n_router = 0;
           bool all = true, lanok = true;
-          const uint32_t rlk = tb.rl[k];
           for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
             uint64_t x = frr_word(tb, pm, w2);
             while (x) {
@@ -149,15 +168,18 @@ __device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
                 all = all && lfa_less(dND, tb.m[k * K + p], a.dist[(size_t)tb.row[p] * n + D]);
               }
               if constexpr (LAN) {
-                if (lanp && lanok) {
-                  const uint32_t j = lt.li[p];
-                  if (j != LFA_NONE) lanok = lfa_less(dND, lt.ml[k * lt.NL + j], a.dist[(size_t)lt.lrow[p] * n + D]);
+                if (ml.applies && lanok) {
+                  const uint32_t j = ml.lt.li[p];
+                  if (j != LFA_NONE) lanok = lfa_less(dND, ml.lt.ml[k * ml.lt.NL + j], a.dist[(size_t)ml.lt.lrow[p] * n + D]);
                 }
               }
             }
           }
           if constexpr (LAN) {
             if (ok && !lanok) { ok = false; fl |= 0x40u; }
+          }
+          if constexpr (SRLG) {
+            if (ok && ml.applies && !ml.safe_ecmp(a, tb, pm, k, rlk, dND, D)) { ok = false; fl |= 0x80u; }
           }
           nd = ok && n_router && all;
         }
@@ -190,12 +212,16 @@ __device__ __forceinline__ void lfa_body(const LfaArgs &a, const LanArgs &la) {
       if (a.node_mask) a.node_mask[od * W + w] = (ONE && w == 0) ? nw : 0ull;
     }
   }
-  frr_cover<NC>(fl, s_cov, a.coverage + (size_t)pi * NC);
+  // coverage: the counted bits of alt_flags as they lie (Lan's two are bits 5 and 6); Srlg: "a primary has members", which is no
+  // bit of alt_flags, and HSPF_LFA_SRLG_REFUSED (bit 7) behind the five
+  uint32_t cv = fl;
+  if constexpr (SRLG) cv = (fl & 0x1Fu) | (ml.applies ? 0x20u : 0u) | ((fl & 0x80u) ? 0x40u : 0u);
+  frr_cover<NC>(cv, s_cov, a.coverage + (size_t)pi * NC);
 }
 
 template <bool ONE>
-__global__ __launch_bounds__(256) void k_lfa(LfaArgs a) { lfa_body<ONE, false>(a, LanArgs{}); }
+__global__ __launch_bounds__(256) void k_lfa(LfaArgs a) { lfa_body<ONE>(a, LfaProt<FrrProt::Plain>{}); }
 template <bool ONE>
-__global__ __launch_bounds__(256) void k_lfa_lan(LfaArgs a, LanArgs la) { lfa_body<ONE, true>(a, la); }
+__global__ __launch_bounds__(256) void k_lfa_lan(LfaArgs a, LfaProt<FrrProt::Lan> pa) { lfa_body<ONE>(a, pa); }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // spf_srlg.hip.h — loop-free alternates and remote-LFA spaces that avoid a shared-risk link group (hspf_lfa_srlg_device,
-// hspf_rlfa_srlg_device; the semantics are written down once, in include/holo_spf_hip.h).  The kernels of spf_lfa.hip.h and
-// spf_rlfa.hip.h are not instantiated a third time: their text is untouched, and what they share (lfa_less, frr_tab, frr_primaries,
-// frr_cover, rlfa_wave_min) is used from here.
+// hspf_rlfa_srlg_device; the semantics are written down once, in include/holo_spf_hip.h).  The local kernel is lfa_body
+// (spf_lfa.hip.h) in the mode FrrProt::Srlg.  The remote kernels are their own: they split the slots differently from k_rlfa_t
+// (spf_rlfa.hip.h), and use what they share with it (lfa_less, frr_tab, frr_primaries, frr_cover, rlfa_wave_min) from here.
 //
 // The member block (written by srlg_stage in spf_frr.hip.h, read here and nowhere else) is a THIRD pair of blocks next to the slot
 // tables and the LAN block.  `stab`:
@@ -17,7 +17,7 @@
 // `sscal` is k_srlg_gather's output, per root at its offset:  d(S, a_i) [NM] | d(N_k, a_i) [K][NM] | d(b_i, N_k) [K][NM]  (LFA_NONE
 // where slot k is no candidate or the vertex is not reached): every term of a crossing that does not depend on the lane.
 //
-// Shape.  k_lfa_srlg<ONE> is k_lfa<ONE> with the member conditions behind every plain one: a candidate that passed them reads
+// Shape.  k_lfa_srlg<ONE> is lfa_body<ONE, Srlg>: the member conditions stand behind every plain one, so a candidate that passed them reads
 // d(b_i, D) of the primary's members — rows the destination's neighbours in the wave read too — and the scalar next to it.
 // A destination whose primaries have no member evaluates no member term.
 // The remote call splits the candidate slots of a root in two:
@@ -96,133 +96,27 @@ __device__ __forceinline__ bool srlg_lfa_safe(const LfaArgs &a, const SrlgTab &s
   return true;
 }
 
-// k_lfa<ONE> (spf_lfa.hip.h) with the member conditions; coverage: the five alt_flags bits, then "a primary has members" and
-// HSPF_LFA_SRLG_REFUSED
+// lfa_body (spf_lfa.hip.h) in the mode FrrProt::Srlg: its arguments, its lane state and the member conditions the body calls
+template <> struct LfaProt<FrrProt::Srlg> { SrlgArgs sa; };
+template <> struct LfaLane<FrrProt::Srlg> {
+  SrlgTab st;
+  bool applies = false;                                                            // some primary has members
+
+  __device__ __forceinline__ void open(const LfaProt<FrrProt::Srlg> &pa, uint32_t pi, uint32_t K) { st = srlg_tab(pa.sa, pi, K); }
+  __device__ __forceinline__ void one_primary(uint32_t p0) { applies = st.sptr[p0 + 1] != st.sptr[p0]; }
+  __device__ __forceinline__ void any_primary(const FrrTab &tb, const uint64_t *pm) {
+    applies = st.T && !frr_all_primaries(tb, pm, [&](uint32_t p) { return st.sptr[p + 1] == st.sptr[p]; });
+  }
+  __device__ __forceinline__ bool safe_one(const LfaArgs &a, uint32_t k, uint32_t rlk, uint32_t p0, uint32_t dND, uint32_t D) const {
+    return srlg_lfa_safe(a, st, k, rlk, p0, dND, D);
+  }
+  __device__ __forceinline__ bool safe_ecmp(const LfaArgs &a, const FrrTab &tb, const uint64_t *pm, uint32_t k, uint32_t rlk, uint32_t dND, uint32_t D) const {
+    return frr_all_primaries(tb, pm, [&](uint32_t p) { return srlg_lfa_safe(a, st, k, rlk, p, dND, D); });
+  }
+};
+
 template <bool ONE>
-__global__ __launch_bounds__(256) void k_lfa_srlg(LfaArgs a, SrlgArgs sa) {
-  constexpr uint32_t NC = 7;
-  __shared__ uint32_t s_cov[NC];
-  __shared__ uint32_t s_tab[ONE ? (FRR_COLS + 1) * 64 : 1];             // the columns, then d(N_k, S)
-  __shared__ uint32_t s_m[ONE ? 64 * 64 : 1];
-  const uint32_t tid = threadIdx.x, pi = blockIdx.y;
-  FrrTab tb = frr_tab(a.tab, a.scal, pi);
-  const uint32_t S = tb.S, K = tb.K, n = a.n, W = a.W, Wk = tb.Wk;
-  if (tid < NC) s_cov[tid] = 0;
-  if constexpr (ONE) {
-    for (uint32_t i = tid; i < FRR_COLS * K; i += 256u) s_tab[i] = tb.cols[i];
-    for (uint32_t i = tid; i < K; i += 256u) s_tab[FRR_COLS * K + i] = tb.dns[i];
-    for (uint32_t i = tid; i < K * K; i += 256u) s_m[i] = tb.m[i];
-    tb = frr_tab_over(S, tb.srow, K, tb.C, s_tab, s_tab + FRR_COLS * K, s_m);
-  }
-  __syncthreads();
-  const SrlgTab st = srlg_tab(sa, pi, K);
-  const uint32_t D = blockIdx.x * LFA_TILE + tid;
-  const bool valid = D < n;
-  const size_t sd = (size_t)tb.srow * n + (valid ? D : 0u);
-  const size_t od = (size_t)pi * n + D;
-  const uint32_t dSD = a.dist[sd];
-  const bool in = valid && D != S && (a.flags[sd] & 1u) && dSD != LFA_NONE;
-  uint32_t fl = 0, cv = 0, aslot = LFA_NONE, amet = 0;
-  uint64_t cw = 0, nw = 0;
-  if (in) {
-    const uint64_t *pm = a.mask + sd * W;
-    uint32_t np, p0;
-    frr_primaries(tb, pm, np, p0);
-    fl = (np ? 0x01u : 0u) | (np >= 2 ? 0x02u : 0u);
-    uint32_t rl0 = LFA_NONE, E0 = LFA_NONE, dE0D = LFA_NONE;
-    bool hasm = false;                                                             // some primary has members
-    if (np == 1) {
-      rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
-      if (E0 != LFA_NONE) dE0D = a.dist[(size_t)tb.row[p0] * n + D];
-      hasm = st.sptr[p0 + 1] != st.sptr[p0];
-    } else if (np >= 2 && st.T) {
-      for (uint32_t w2 = 0; w2 < Wk; ++w2) {
-        uint64_t x = frr_word(tb, pm, w2);
-        while (x) {
-          const uint32_t p = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-          x &= x - 1;
-          hasm = hasm || st.sptr[p + 1] != st.sptr[p];
-        }
-      }
-    }
-    if (hasm) cv |= 0x20u;
-    bool have = false, bnode = false, bdown = false;
-    uint64_t bsum = 0;
-    uint32_t ci = 0;
-    for (uint32_t w = 0; w < Wk; ++w) {
-      if constexpr (!ONE) { cw = 0; nw = 0; }
-      for (; ci < tb.C; ++ci) {
-        const uint32_t k = tb.cl[ci];
-        if ((k >> 6) != w) break;
-        const uint32_t dND = a.dist[(size_t)tb.row[k] * n + D];
-        if (!lfa_less(dND, tb.dns[k], dSD)) continue;
-        if ((tb.cf[k] & 1u) && !a.ignore_overload && tb.nbr[k] != D) continue;
-        bool ok = true, nd = false;
-        const uint32_t rlk = tb.rl[k];
-        if (np == 1) {
-          ok = rlk != rl0;
-          if (ok && hasm && !srlg_lfa_safe(a, st, k, rlk, p0, dND, D)) { ok = false; fl |= 0x80u; }      // every plain condition holds: now the group
-          nd = ok && E0 != LFA_NONE && lfa_less(dND, tb.m[k * K + p0], dE0D);
-        } else if (np >= 2) {
-          uint32_t n_router = 0;
-          bool all = true;
-          for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
-            uint64_t x = frr_word(tb, pm, w2);
-            while (x) {
-              const uint32_t p = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-              x &= x - 1;
-              if (tb.rl[p] == rlk) { ok = false; break; }
-              if (tb.nbr[p] != LFA_NONE) {
-                ++n_router;
-                all = all && lfa_less(dND, tb.m[k * K + p], a.dist[(size_t)tb.row[p] * n + D]);
-              }
-            }
-          }
-          if (ok && hasm) {
-            bool safe = true;
-            for (uint32_t w2 = 0; w2 < Wk && safe; ++w2) {
-              uint64_t x = frr_word(tb, pm, w2);
-              while (x && safe) {
-                const uint32_t p = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-                x &= x - 1;
-                safe = srlg_lfa_safe(a, st, k, rlk, p, dND, D);
-              }
-            }
-            if (!safe) { ok = false; fl |= 0x80u; }
-          }
-          nd = ok && n_router && all;
-        }
-        if (!ok) continue;
-        cw |= 1ull << (k & 63u);
-        if (nd) nw |= 1ull << (k & 63u);
-        if (np == 1) {
-          const uint64_t sum = (uint64_t)tb.cost[k] + dND;
-          if (!have || (nd && !bnode) || (nd == bnode && sum < bsum)) {            // candidates come in ascending slot order
-            have = true; bnode = nd; bsum = sum; aslot = k; bdown = dND < dSD;
-          }
-        }
-      }
-      if constexpr (!ONE) {
-        if (a.cand_mask) a.cand_mask[od * W + w] = cw;
-        if (a.node_mask) a.node_mask[od * W + w] = nw;
-      }
-    }
-    if (have) {
-      fl |= 0x04u | (bnode ? 0x08u : 0u) | (bdown ? 0x10u : 0u);
-      amet = bsum > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)bsum;
-    }
-  }
-  if (valid) {
-    a.alt_slot[od] = aslot; a.alt_metric[od] = amet; a.alt_flags[od] = (uint8_t)fl;
-    const uint32_t w0 = ONE ? 0u : (in ? Wk : 0u);                                 // the words of the sets that the loop above did not write
-    for (uint32_t w = w0; w < W; ++w) {
-      if (a.cand_mask) a.cand_mask[od * W + w] = (ONE && w == 0) ? cw : 0ull;
-      if (a.node_mask) a.node_mask[od * W + w] = (ONE && w == 0) ? nw : 0ull;
-    }
-  }
-  cv |= (fl & 0x1Fu) | ((fl & 0x80u) ? 0x40u : 0u);
-  frr_cover<NC>(cv, s_cov, a.coverage + (size_t)pi * NC);
-}
+__global__ __launch_bounds__(256) void k_lfa_srlg(LfaArgs a, LfaProt<FrrProt::Srlg> pa) { lfa_body<ONE>(a, pa); }
 
 // what every lane of the two remote kernels starts from
 struct RlfaLane { uint32_t v, vv, dSv, rSv; bool valid, elig; };

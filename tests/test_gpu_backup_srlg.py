@@ -165,6 +165,24 @@ def test_a_primary_with_16_members_and_one_with_1(spf_ctx):
     check(spf_ctx, m, need=need)
 
 
+def test_a_primary_with_9_members_takes_the_second_member_stream(spf_ctx):
+    """The hub of 17 again: slot 8 shares a group with 9 links among the neighbours — one more than a stream of the prefix's entries
+    carries, so members 8 .. 15 take their own.  The draw (seed 0) was chosen on the CPU so that the primary refuses something."""
+    g = hub(17, 3)
+    rp, col = g[0], g[1]
+    far = [l for u in range(1, 18) for l in range(int(rp[u]), int(rp[u + 1])) if int(col[l]) != 0]
+    of = {int(rp[0]) + 8: [1]}
+    for l in np.random.default_rng(0).choice(far, 9, replace=False):
+        of.setdefault(int(l), []).append(1)
+    gp, gr = SM.groups_csr(len(col), of)
+    m = SC.Model(g, [0], gp, gr, random_table(np.random.default_rng(5), 18, 70))
+
+    def need(w):
+        assert np.diff(m.mems[0].mem_ptr)[8] == 9
+        assert ((w[0].bk_primary == 8) & (w[0].bk_flags & BS.SRLG_REFUSED != 0)).any() and (w[0].bk_kind == B.ECMP).any()
+    check(spf_ctx, m, need=need)
+
+
 @pytest.mark.parametrize("n_pfx", [255, 256, 300])
 def test_prefix_counts_at_the_tile_edge(spf_ctx, n_pfx):
     g = ring_chords(24, 11, 1, 6, chords=6)
