@@ -91,6 +91,11 @@ class HspfLfaOut(ctypes.Structure):
                 ("cand_mask", ctypes.c_void_p), ("node_mask", ctypes.c_void_p), ("coverage", ctypes.c_void_p)]
 
 
+class HspfLfaEcmpOut(ctypes.Structure):
+    _fields_ = [("ea_ptr", ctypes.c_void_p), ("ea_primary", ctypes.c_void_p), ("ea_slot", ctypes.c_void_p), ("ea_metric", ctypes.c_void_p),
+                ("ea_flags", ctypes.c_void_p), ("ea_coverage", ctypes.c_void_p)]
+
+
 class HspfRlfaOut(ctypes.Structure):
     _fields_ = [("pq_node", ctypes.c_void_p), ("pq_via", ctypes.c_void_p), ("pq_metric", ctypes.c_void_p), ("pq_counts", ctypes.c_void_p),
                 ("space_flags", ctypes.c_void_p), ("space_via", ctypes.c_void_p), ("rl_node", ctypes.c_void_p), ("rl_via", ctypes.c_void_p),
@@ -210,6 +215,9 @@ SYMBOLS = [
     ("hspf_lfa_candidates", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u8p, u32p]),
     ("hspf_lfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfLfaOut)]),
+    ("hspf_lfa_ecmp_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                            ctypes.POINTER(HspfLfaEcmpOut), u64p]),
     # broadcast-link protection (RFC 5286 section 3.3)
     ("hspf_lfa_lan_candidates", ctypes.c_int, [ctypes.POINTER(HspfCsr), ctypes.c_uint32, ctypes.c_uint32, u32p, u32p]),
     ("hspf_lfa_lan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,

@@ -224,6 +224,7 @@ struct hspf_ctx {
   DevBuf lfa_tab, lfa_scal;                          // hspf_lfa_device: the staged per-root slot tables | d(N, S) and d(N, N') of every protected root
   DevBuf lan_tab, lan_scal;                          // hspf_lfa_lan_device: the staged LAN columns | d(N, L) of every protected root
   DevBuf srlg_tab, srlg_scal;                        // hspf_lfa_srlg_device: the staged member tables | d(S, a), d(N, a), d(b, E) of every protected root
+  DevBuf ea_scr;                                     // hspf_lfa_ecmp_device: the tile totals of its count step, scanned in place | the total
   uint32_t *h_ev = nullptr;                          // pinned: the event total, stored by k_events_scan itself
   struct EvState {                                   // the last hspf_routes_events, for hspf_routes_events_rest
     bool valid = false;
@@ -869,7 +870,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->lan_tab, &ctx->lan_scal, &ctx->srlg_tab, &ctx->srlg_scal, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw, &ctx->rnode_part, &ctx->rnode_map, &ctx->tnode_cell})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->lan_tab, &ctx->lan_scal, &ctx->srlg_tab, &ctx->srlg_scal, &ctx->ea_scr, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw, &ctx->rnode_part, &ctx->rnode_map, &ctx->tnode_cell})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -3790,5 +3791,6 @@ int hspf_ancestors_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *ro
 
 }  // extern "C"
 
+#include "spf_lfa_ecmp.hip.h"
 #include "spf_frr.hip.h"
 #include "spf_multi.hip.h"

@@ -1,4 +1,4 @@
-// spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device,
+// spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device, hspf_lfa_ecmp_device,
 // hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_rlfa_node_select_device,
 // hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, hspf_routes_backup_node_device, the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device,
 // and the shared-risk calls hspf_srlg_members, hspf_lfa_srlg_device, hspf_rlfa_srlg_device, hspf_routes_backup_srlg_device.
@@ -469,6 +469,55 @@ int lfa_call(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, u
   });
 }
 
+static_assert(EA_CW == HSPF_LFA_ECMP_COVERAGE_WORDS && HSPF_LFA_EA_PRIMARY == 0x20u, "the fill kernel's coverage width and primary bit are the header's");
+
+// The frame of hspf_lfa_ecmp_device (kernels: spf_lfa_ecmp.hip.h): the checks and the staging of lfa_call, then count -> scan -> fill
+// on the context's stream and ONE synchronisation.  The total arrives in the pinned word k_events_scan stores (h_ev[1]: word 0 is
+// the event stream's).
+int lfa_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                  const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                  const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, uint64_t cap_entries, hspf_lfa_ecmp_out *out_dev,
+                  uint64_t *out_total) {
+  if (!ctx) return HSPF_E_INVAL;
+  return guarded(ctx, [&]() -> int {
+    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
+    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
+    if (!out_dev->ea_ptr || !out_total) return bad("NULL ea_ptr or out_total");
+    if (cap_entries && (!out_dev->ea_primary || !out_dev->ea_slot || !out_dev->ea_metric || !out_dev->ea_flags || !out_dev->ea_coverage))
+      return bad("NULL ea_primary / ea_slot / ea_metric / ea_flags / ea_coverage with cap_entries > 0");
+    int rc;
+    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
+    uint64_t pairs = 0;                                 // an upper bound of the entries: ea_ptr is u32, the scan's carry too
+    for (uint32_t i = 0; i < n_prot; ++i) pairs += (uint64_t)n_vertices * std::max(prot[i].n_slots, 1u);
+    if (pairs >= (1ull << 32)) return bad("n_vertices * max(n_slots, 1), summed over the protected roots, reaches 2^32: split the protect list");
+    (void)hipSetDevice(ctx->device);
+    const uint32_t tiles_x = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    const size_t n_tiles = (size_t)tiles_x * n_prot;
+    if ((rc = ensure(ctx, ctx->ea_scr, (n_tiles + 4) * 4, false))) return rc;
+    if (!ctx->h_ev) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ev, 64, hipHostMallocDefault));
+    uint32_t *d_hev = nullptr;
+    HIPCHK(ctx, hipHostGetDevicePointer((void **)&d_hev, ctx->h_ev, 0));
+    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
+    uint32_t max_k = 0;
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
+    hipStream_t s = ctx->stream;
+    if (out_dev->ea_coverage) HIPCHK(ctx, hipMemsetAsync(out_dev->ea_coverage, 0, (size_t)n_prot * HSPF_LFA_ECMP_COVERAGE_WORDS * 4, s));
+    LfaEcmpArgs a{};
+    a.l = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    a.n_prot = n_prot; a.cap = cap_entries; a.tile = (uint32_t *)ctx->ea_scr.p;
+    a.ea_ptr = out_dev->ea_ptr; a.ea_primary = out_dev->ea_primary; a.ea_slot = out_dev->ea_slot; a.ea_metric = out_dev->ea_metric;
+    a.ea_flags = out_dev->ea_flags; a.ea_coverage = out_dev->ea_coverage;
+    const dim3 grid(tiles_x, n_prot);
+    hipLaunchKernelGGL(k_lfa_ecmp_count, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(1024), 0, s, (uint32_t)n_tiles, a.tile, a.tile + n_tiles, d_hev + 1);
+    if (max_k <= 64) hipLaunchKernelGGL(k_lfa_ecmp_fill<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_lfa_ecmp_fill<false>, grid, dim3(256), 0, s, a);
+    if ((rc = frr_finish(ctx, "k_lfa_ecmp"))) return rc;
+    *out_total = ctx->h_ev[1];
+    return HSPF_OK;
+  });
+}
+
 static_assert(RLFA_CW == HSPF_RLFA_COUNT_WORDS && RLFA_LAN_CW == HSPF_RLFA_LAN_COUNT_WORDS, "the kernels' count widths are the header's");
 
 // the one frame of hspf_rlfa_device (with_lan false, `lan` unread) and hspf_rlfa_lan_device
@@ -567,6 +616,14 @@ int hspf_lfa_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uin
                         const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
   return lfa_call(ctx, "hspf_lfa_lan_device", FrrProt::Lan, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, lan, nullptr, n_prot,
                   lfa_flags, out_dev);
+}
+
+int hspf_lfa_ecmp_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                         const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, uint64_t cap_entries,
+                         hspf_lfa_ecmp_out *out_dev, uint64_t *out_total) {
+  return lfa_ecmp_call(ctx, "hspf_lfa_ecmp_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot, lfa_flags,
+                       cap_entries, out_dev, out_total);
 }
 
 // ---- remote loop-free alternates (include/holo_spf_hip.h "remote loop-free alternates on device"; kernels: spf_rlfa.hip.h) ----

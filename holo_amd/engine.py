@@ -41,6 +41,8 @@ LFA_IGNORE_OVERLOAD = 0x01      # HSPF_LFA_IGNORE_OVERLOAD (lfa_device flags)
 LFA_HAS_PRIMARY, LFA_ECMP, LFA_LINK_PROTECT, LFA_NODE_PROTECT, LFA_DOWNSTREAM = 0x01, 0x02, 0x04, 0x08, 0x10
 LFA_NO_SLOT = 0xFFFFFFFF
 LFA_COVERAGE_WORDS = 5
+LFA_EA_PRIMARY = 0x20           # HSPF_LFA_EA_PRIMARY: ea_flags of lfa_ecmp_device(), the alternate is another primary
+LFA_ECMP_COVERAGE_WORDS = 7
 LFA_LAN_PRIMARY, LFA_LAN_REFUSED = 0x20, 0x40     # HSPF_LFA_LAN_*: alt_flags / bk_flags of the LAN calls
 LFA_LAN_COVERAGE_WORDS = 7
 LFA_LAN_SAFE_REPAIRS = 0x02     # HSPF_LFA_LAN_SAFE_REPAIRS (routes_backup_lan_device flags): tilfa comes from rlfa_lan_device()'s tables
@@ -214,6 +216,29 @@ class LfaResult:
     node_mask: Optional[np.ndarray]   # [P, N, W] u64 or None
     coverage: np.ndarray     # [P, 5] u32; [P, 7] from lfa_lan_device()
     lan: Optional[np.ndarray] = None   # [K] u32 lfa_lan_candidates() of the root (SpfContext.lfa(lan_protect=True))
+
+
+@dataclass
+class LfaEcmpResult:
+    """Per-primary alternates of the ECMP destinations of one lfa_ecmp_device() call: a stream in CSR form over
+    (protected root, destination), the entries of one destination in ascending primary slot order."""
+    ea_ptr: np.ndarray       # [P * N + 1] u32
+    ea_primary: np.ndarray   # [T] u32 the protected primary slot
+    ea_slot: np.ndarray      # [T] u32 its alternate, LFA_NO_SLOT: none
+    ea_metric: np.ndarray    # [T] u32
+    ea_flags: np.ndarray     # [T] u8  LFA_LINK_PROTECT | LFA_NODE_PROTECT | LFA_DOWNSTREAM | LFA_EA_PRIMARY
+    ea_coverage: np.ndarray  # [P, 7] u32
+    n_vertices: int = 0
+
+    @property
+    def total(self) -> int:
+        return len(self.ea_primary)
+
+    def alternates(self, i: int, d: int):
+        """[(primary, slot, metric, flags)] of destination `d` of protected root `i`: empty below two primaries."""
+        k = i * self.n_vertices + d
+        return [(int(self.ea_primary[e]), int(self.ea_slot[e]), int(self.ea_metric[e]), int(self.ea_flags[e]))
+                for e in range(int(self.ea_ptr[k]), int(self.ea_ptr[k + 1]))]
 
 
 def lfa_candidates(row_ptr, col, metric, vflags, root: int, cap: Optional[int] = None) -> LfaCandidates:
@@ -1020,6 +1045,48 @@ class SpfContext:
                 self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], **out)
             self._fetch(host, dev)
         return cand, LfaResult(*host.values(), lan=plan.lan)
+
+    def lfa_ecmp_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
+                        ea_ptr_ptr: int, cap_entries: int = 0, ea_primary_ptr: int = 0, ea_slot_ptr: int = 0, ea_metric_ptr: int = 0,
+                        ea_flags_ptr: int = 0, ea_coverage_ptr: int = 0, lfa_flags: int = 0) -> int:
+        """hspf_lfa_ecmp_device(): per-primary alternates of every destination with two or more primary slots, as a stream in
+        CSR form.  `protect` as for lfa_device(); all `*_ptr` are device pointers: ea_ptr_ptr [P * N + 1] u32, the entry arrays
+        `cap_entries` elements each (0 with cap_entries == 0: ea_ptr and the total alone), ea_coverage_ptr
+        [P, LFA_ECMP_COVERAGE_WORDS] u32.  Returns the total number of entries; when it exceeds cap_entries only ea_ptr was
+        written and the call is to be repeated with larger arrays."""
+        arr, keep = self._protect_array(protect, "lfa_ecmp_device")
+        out = L.HspfLfaEcmpOut(ea_ptr_ptr or None, ea_primary_ptr or None, ea_slot_ptr or None, ea_metric_ptr or None, ea_flags_ptr or None,
+                               ea_coverage_ptr or None)
+        total = ctypes.c_uint64()
+        rc = self.lib.hspf_lfa_ecmp_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                           arr, len(protect), lfa_flags, cap_entries, ctypes.byref(out), ctypes.byref(total))
+        del keep
+        self._check_rc("hspf_lfa_ecmp_device", rc)
+        return int(total.value)
+
+    def lfa_ecmp(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0):
+        """Per-primary alternates of the ECMP destinations of one root, start to finish: the plan and the run of lfa(), then
+        lfa_ecmp_device() twice on those rows — once for ea_ptr and the total, once with arrays of that size.
+        Returns (LfaCandidates, LfaEcmpResult with one protected root)."""
+        plan = self._frr_plan(graph, root)
+        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
+        R, n = len(roots), graph.n
+        protect = [(0, cand, nbr_row)]
+        ptr = np.empty(n + 1, np.uint32)
+        cov = np.zeros((1, LFA_ECMP_COVERAGE_WORDS), np.uint32)
+        with self._dev_buffers(dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, ptr=ptr.nbytes)) as dev:
+            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            tables = (n, R, W, dev["dist"], dev["flags"], dev["mask"], protect)
+            total = self.lfa_ecmp_device(*tables, ea_ptr_ptr=dev["ptr"], lfa_flags=lfa_flags)
+            host = dict(primary=np.empty(total, np.uint32), slot=np.empty(total, np.uint32), metric=np.empty(total, np.uint32),
+                        eflags=np.empty(total, np.uint8))
+            if total:
+                with self._dev_buffers(dict({k: a.nbytes for k, a in host.items()}, cov=cov.nbytes)) as ent:
+                    self.lfa_ecmp_device(*tables, ea_ptr_ptr=dev["ptr"], cap_entries=total, ea_primary_ptr=ent["primary"], ea_slot_ptr=ent["slot"],
+                                         ea_metric_ptr=ent["metric"], ea_flags_ptr=ent["eflags"], ea_coverage_ptr=ent["cov"], lfa_flags=lfa_flags)
+                    self._fetch(dict(host, cov=cov), ent)
+            self._fetch(dict(ptr=ptr), dev)
+        return cand, LfaEcmpResult(ptr, host["primary"], host["slot"], host["metric"], host["eflags"], cov, n_vertices=n)
 
     def rlfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                     protect, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int, rl_via_ptr: int,

@@ -669,8 +669,8 @@ int hspf_ancestors_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *ro
  *   downstream  iff  d(N, D) < d(S, D).
  * Outputs per (S, D):
  *   alt_flags   HSPF_LFA_HAS_PRIMARY   P is not empty
- *               HSPF_LFA_ECMP          popcount(P) >= 2: no alternate is chosen (the other primaries are the alternates); the two
- *                                      sets are still written
+ *               HSPF_LFA_ECMP          popcount(P) >= 2: no alternate is chosen by THIS call (per primary: hspf_lfa_ecmp_device,
+ *                                      below); the two sets are still written
  *               HSPF_LFA_LINK_PROTECT  an alternate was chosen (alt_slot is a member of cand)
  *               HSPF_LFA_NODE_PROTECT  ... and it is a member of node
  *               HSPF_LFA_DOWNSTREAM    ... and it is a downstream neighbour
@@ -728,6 +728,74 @@ typedef struct {                 /* DEVICE pointers                             
 int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                     const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev);
+
+/* ---- per-primary alternates for ECMP destinations (RFC 5286 sections 3.4, 3.6): new symbol, same ABI number ----------------------
+ * hspf_lfa_device stops at a destination with two or more primary slots: it sets HSPF_LFA_ECMP and writes two sets that are safe
+ * against ALL primaries at once.  That is not the answer a RIB needs.  Two primaries behind the same first link of S (two routers on
+ * one LAN) share that link's fate and do not protect each other; two parallel links to one neighbour E protect each other's link
+ * and not the node E; and protection is reported, and a backup installed, PER primary next hop
+ * (frr-protection-available-{link,node,downstream}-type).  hspf_lfa_ecmp_device gives, for every destination with at least two
+ * primary slots and for every one of those primaries, the alternate of that primary and what it protects.
+ *
+ * Inputs.  The forward table set, `prot`, n_prot and lfa_flags exactly as for hspf_lfa_device.  No graph.
+ * Terms as there: S a protected root, D a vertex of S's SPT, D != S, P = the bits of mask_S[D] below n_slots.  The call speaks only
+ * about D with popcount(P) >= 2.  For such a D and a protected primary h in P let E = nbr[h] (may be HSPF_NO_ROOT).  A slot k with
+ * N = nbr[k] is judged by ONE rule whether or not k is itself a primary; every sum is evaluated in 64 bits and a term that is
+ * HSPF_DIST_INF makes its inequality false:
+ *   cand(h)     k != h,  and nbr[k] != HSPF_NO_ROOT,  and d(N, D) < d(N, S) + d(S, D),  and root_link[k] != root_link[h],  and
+ *               (cflags[k] has no NO_TRANSIT, or N == D, or the call passes HSPF_LFA_IGNORE_OVERLOAD);
+ *   node(h)     k is in cand(h), E != HSPF_NO_ROOT, and d(N, D) < d(N, E) + d(E, D)   (N == E makes this false by itself);
+ *   downstream  d(N, D) < d(S, D);
+ *   choice      (section 3.6 in spirit) a member of node(h) before a member of cand(h) only, then a slot that is in P before one
+ *               that is not, then the smaller cost[k] + d(N, D) (64 bits), then the smaller slot index.
+ * A primary with positive costs passes the loop-free inequality by itself; applying it to primaries anyway keeps one rule and is
+ * safe with zero-cost router links.  A primary whose target is a network vertex (nbr == HSPF_NO_ROOT) can be protected; it can
+ * never be an alternate.
+ *
+ * Output: a compact stream in CSR form over (protected root, destination).  DEVICE pointers:
+ *   ea_ptr       u32 [n_prot * n_vertices + 1].  For i * n_vertices + D:  ea_ptr[. + 1] - ea_ptr[.] is popcount(P) when that is at
+ *                least 2, and 0 otherwise (also for D == S and D outside the SPT).  ALWAYS written completely.
+ *   the entries of one D are its primaries in ascending slot order; entry arrays of cap_entries elements each:
+ *   ea_primary   u32  h
+ *   ea_slot      u32  the chosen slot, or HSPF_LFA_NO_SLOT
+ *   ea_metric    u32  cost[k] + d(N, D) saturated at 0xFFFFFFFE, 0 for none
+ *   ea_flags     u8   HSPF_LFA_LINK_PROTECT | HSPF_LFA_NODE_PROTECT | HSPF_LFA_DOWNSTREAM with their alt_flags values, and
+ *                     HSPF_LFA_EA_PRIMARY 0x20: the alternate is another primary of D.  (0x01 and 0x02 mean something else in
+ *                     alt_flags; 0x20 is HSPF_LFA_LAN_PRIMARY only in the outputs of the LAN calls, which this call is not.)
+ *   ea_coverage  u32 [n_prot][HSPF_LFA_ECMP_COVERAGE_WORDS], counted on the device: ECMP destinations | entries | entries with
+ *                an alternate | with a node-protecting one | with a downstream one | whose alternate is a primary | ECMP
+ *                destinations of which EVERY primary has an alternate.
+ * *out_total (HOST): the total number of entries, = ea_ptr[n_prot * n_vertices].
+ *
+ * Capacity.  The caller passes cap_entries and entry arrays of that size.  When the total exceeds cap_entries the call still
+ * returns 0 and writes ea_ptr and *out_total; the entry arrays and ea_coverage are then unspecified, and the caller repeats the
+ * call with larger arrays (the convention of hspf_lfa_candidates and hspf_routes_events: an overflow is not an error).
+ * cap_entries == 0 with NULL entry arrays and NULL ea_coverage asks for ea_ptr and the total alone.
+ * Argument errors — everything hspf_lfa_device rejects; ea_ptr or out_total NULL; an entry array or ea_coverage NULL with
+ * cap_entries > 0; and the host-side bound  sum over the protected roots of n_vertices * max(n_slots, 1) >= 2^32  (the stream is
+ * indexed in 32 bits: split the protect list) — return HSPF_E_INVAL with a text in hspf_last_error that names
+ * hspf_lfa_ecmp_device, before anything is launched.  The staged tables are those of hspf_lfa_device; everything is enqueued on
+ * the context's stream and the call synchronises once at the end.
+ *
+ * From ea_* to a backup next hop per primary next hop: INTEGRATION.md §5s.
+ *
+ * OUT OF SCOPE: ECMP backups per prefix (the follow-up: this call's rule with d_N(p) in place of d(N, D)); the LAN-safe and
+ * SRLG-safe variants of this call; remote or TI-LFA repairs for an ECMP primary that has no alternate; entries for destinations
+ * with a single primary (alt_slot of hspf_lfa_device is that answer). */
+#define HSPF_LFA_EA_PRIMARY            0x20u   /* ea_flags: the alternate is another primary of the destination */
+#define HSPF_LFA_ECMP_COVERAGE_WORDS   7u
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint32_t *ea_ptr;              /* [n_prot * n_vertices + 1]                                                  */
+  uint32_t *ea_primary;          /* [cap_entries]                                                              */
+  uint32_t *ea_slot;             /* [cap_entries]                                                              */
+  uint32_t *ea_metric;           /* [cap_entries]                                                              */
+  uint8_t  *ea_flags;            /* [cap_entries]                                                              */
+  uint32_t *ea_coverage;         /* [n_prot][HSPF_LFA_ECMP_COVERAGE_WORDS]                                     */
+} hspf_lfa_ecmp_out;
+int hspf_lfa_ecmp_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                         const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, uint64_t cap_entries,
+                         hspf_lfa_ecmp_out *out_dev, uint64_t *out_total);
 
 /* ---- broadcast-link protection (RFC 5286 section 3.3) for the alternates and the per-prefix backups: new symbols, same ABI number --
  * When S reaches D across a LAN, what S detects is the loss of its attachment to that LAN, and an alternate must not cross the LAN
@@ -1134,8 +1202,8 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
  *
  * From bk_* to a next hop with a backup and its label stack: INTEGRATION.md §5k.
  *
- * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (the other primaries
- * are the backups; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
+ * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (per vertex:
+ * hspf_lfa_ecmp_device, above; per prefix: not yet; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
  * td_kind; node-protecting remote repairs per prefix are hspf_routes_backup_node_device's, below).  Loop-freeness with respect to a LAN pseudonode is not checked by THIS
  * call: hspf_routes_backup_lan_device ("broadcast-link protection", above) adds it.  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
 #define HSPF_BK_NO_ROUTE       0u
@@ -1410,7 +1478,7 @@ int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, 
  * From bn_* to a next hop with a label stack: INTEGRATION.md §5p.
  *
  * OUT OF SCOPE: LAN pseudonodes as the protected node; LAN-safe release paths (the limitation of the two select calls); ECMP routes
- * (bn_kind 0: the other primaries are the backups); a wave-per-prefix path for prefixes with very many advertisers (one lane walks
+ * (bn_kind 0; per vertex: hspf_lfa_ecmp_device, per prefix: not yet); a wave-per-prefix path for prefixes with very many advertisers (one lane walks
  * one prefix); SRLGs. */
 #define HSPF_BN_LFA            1u             /* bn_kind */
 #define HSPF_BN_PQ             2u

@@ -114,6 +114,18 @@ struct Lfa {
   uint32_t coverage[HSPF_LFA_COVERAGE_WORDS] = {};
 };
 
+// Per-primary alternates of the ECMP destinations (hspf_lfa_ecmp_device) of one protected root on the host: a stream in CSR form
+// over the destinations, the entries of one destination in ascending primary slot order.
+struct LfaEcmp {
+  uint32_t n_vertices = 0;
+  LfaCandidates candidates;
+  std::vector<uint32_t> roots;                          // the SPF roots of the run behind it, as in Lfa
+  std::vector<uint32_t> ea_ptr;                         // [n_vertices + 1]
+  std::vector<uint32_t> ea_primary, ea_slot, ea_metric; // [ea_ptr.back()]
+  std::vector<uint8_t> ea_flags;                        // HSPF_LFA_LINK_PROTECT | _NODE_PROTECT | _DOWNSTREAM | HSPF_LFA_EA_PRIMARY
+  uint32_t ea_coverage[HSPF_LFA_ECMP_COVERAGE_WORDS] = {};
+};
+
 // Remote loop-free alternates (hspf_csr_transpose / hspf_rlfa_device) of one protected root on the host: the LFA result they
 // complete, the PQ node of every slot, the remote alternate of every destination.
 struct Rlfa {
@@ -409,6 +421,59 @@ class Engine {
     r.cand_mask = cm.to_host<uint64_t>((size_t)n * W); r.node_mask = nm.to_host<uint64_t>((size_t)n * W);
     const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
     std::copy(cv.begin(), cv.end(), r.coverage);
+    return r;
+  }
+  // hspf_lfa_ecmp_device on DEVICE tables: per-primary alternates of the destinations with two or more primary slots.  Returns the
+  // total number of entries; when it exceeds cap_entries only ea_ptr was written (repeat with larger arrays).
+  uint64_t lfa_ecmp_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                           const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, uint64_t cap_entries,
+                           hspf_lfa_ecmp_out out_dev) {
+    uint64_t total = 0;
+    const int rc = hspf_lfa_ecmp_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                        lfa_flags, cap_entries, &out_dev, &total);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_ecmp_device (") + hspf_last_error(ctx_) + ")");
+    return total;
+  }
+  // One root start to finish, as lfa(): the same run, then hspf_lfa_ecmp_device twice — for ea_ptr and the total, then with arrays of
+  // that size.  The four vectors must be the CSR `g` was uploaded from.
+  LfaEcmp lfa_ecmp(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                   const std::vector<uint8_t> &vflags, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0) {
+    if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
+      throw Error(HSPF_E_INVAL, "Engine::lfa_ecmp: the CSR is not the one the graph was uploaded from");
+    LfaEcmp r;
+    r.candidates = lfa_candidates(row_ptr, col, metric, vflags, root);
+    const LfaCandidates &c = r.candidates;
+    std::vector<uint32_t> nbrs;
+    for (uint32_t v : c.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
+    std::sort(nbrs.begin(), nbrs.end());
+    nbrs.erase(std::unique(nbrs.begin(), nbrs.end()), nbrs.end());
+    r.roots.push_back(root);
+    r.roots.insert(r.roots.end(), nbrs.begin(), nbrs.end());
+    std::vector<uint32_t> nbr_row(c.nbr.size(), 0u);
+    for (size_t k = 0; k < c.nbr.size(); ++k)
+      if (c.nbr[k] != HSPF_NO_ROOT) nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), c.nbr[k]) - nbrs.begin());
+    const uint32_t n = g.n_vertices(), R = (uint32_t)r.roots.size();
+    const uint32_t W = std::max(mask_words(g, r.roots), ((uint32_t)c.nbr.size() + 63u) / 64u);
+    r.n_vertices = n;
+    const size_t rn = (size_t)R * n;
+    DeviceBuffer dist(ctx_, rn * 4), flags(ctx_, rn * 2), mask(ctx_, rn * 8 * W), ptr(ctx_, ((size_t)n + 1) * 4);
+    hspf_result out{dist.as<uint32_t>(), nullptr, flags.as<uint16_t>(), mask.as<uint64_t>(), W, nullptr};
+    const int rc = hspf_run_device(ctx_, g.raw(), r.roots.data(), R, run_flags, &out);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device (") + hspf_last_error(ctx_) + ")");
+    const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
+    const uint64_t total = lfa_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, 0,
+                                           hspf_lfa_ecmp_out{ptr.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr});
+    if (total) {
+      const size_t t = (size_t)total;
+      DeviceBuffer pri(ctx_, t * 4), slot(ctx_, t * 4), met(ctx_, t * 4), fl(ctx_, t), cov(ctx_, HSPF_LFA_ECMP_COVERAGE_WORDS * 4);
+      lfa_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, total,
+                      hspf_lfa_ecmp_out{ptr.as<uint32_t>(), pri.as<uint32_t>(), slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), cov.as<uint32_t>()});
+      r.ea_primary = pri.to_host<uint32_t>(t); r.ea_slot = slot.to_host<uint32_t>(t); r.ea_metric = met.to_host<uint32_t>(t);
+      r.ea_flags = fl.to_host<uint8_t>(t);
+      const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_ECMP_COVERAGE_WORDS);
+      std::copy(cv.begin(), cv.end(), r.ea_coverage);
+    }
+    r.ea_ptr = ptr.to_host<uint32_t>((size_t)n + 1);
     return r;
   }
   // Remote loop-free alternates (RFC 7490).  csr_transpose: host arithmetic, no device; of a run on the result only `dist`

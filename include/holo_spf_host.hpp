@@ -127,6 +127,16 @@ struct LfaOut {
   std::vector<uint64_t> cand_mask, node_mask;               // [n_protected][n_vertices][mask_words] (empty without with_masks)
   std::vector<uint32_t> coverage;                           // [n_protected][HSPF_LFA_COVERAGE_WORDS] (lfa_lan: HSPF_LFA_LAN_COVERAGE_WORDS)
 };
+// Per-primary alternates of the ECMP destinations (hspf_lfa_ecmp_device) of the same protected roots: a stream in CSR form over
+// (protected root, destination), the entries of one destination in ascending primary slot order.  supported == false: no such call.
+struct LfaEcmpOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_vertices = 0;
+  std::vector<uint32_t> ea_ptr;                             // [n_protected * n_vertices + 1]
+  std::vector<uint32_t> ea_primary, ea_slot, ea_metric;     // [ea_ptr.back()]
+  std::vector<uint8_t> ea_flags;
+  std::vector<uint32_t> ea_coverage;                        // [n_protected][HSPF_LFA_ECMP_COVERAGE_WORDS]
+};
 // Remote loop-free alternates (hspf_rlfa_device) of the same protected roots: PQ nodes per (protected root, slot) and the remote
 // alternate per destination, from the forward DeviceRun and the DeviceRun of the SAME roots on the transposed graph
 // (hspf_csr_transpose).  supported == false: the engine has no such call.
@@ -239,6 +249,9 @@ class Engine {
                                       uint32_t /*lfa_flags*/, const TilfaOut * /*tilfa*/) { return BackupOut{}; }
   // The default: not supported (LfaOut::supported == false).
   virtual LfaOut lfa(DeviceRun &, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) { return LfaOut{}; }
+  // Per primary slot of every destination with two or more of them: its alternate and what that protects (hspf_lfa_ecmp_device).
+  // The default: not supported.
+  virtual LfaEcmpOut lfa_ecmp(DeviceRun &, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/) { return LfaEcmpOut{}; }
   // `reverse_run`: the run of the same roots on the upload of the transposed CSR (the forward run itself on a graph whose
   // costs are symmetric); `lfa`: nullptr, or what lfa() returned for the same protect list.  The default: not supported.
   virtual RlfaOut rlfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
@@ -795,6 +808,45 @@ class HipEngine : public Engine {
   }
   LfaOut lfa(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, bool with_masks) override {
     return lfa_with(run, protect, nullptr, nullptr, lfa_flags, with_masks);
+  }
+  // two calls: ea_ptr and the total, then the entries into arrays of that size
+  LfaEcmpOut lfa_ecmp(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    LfaEcmpOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices;
+    if (protect.empty()) return o;
+    std::vector<hspf_lfa_protect> ps;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("lfa_ecmp: the slot arrays of a protected root differ in length");
+      ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t pb = ((size_t)o.n_protected * o.n_vertices + 1) * 4, cb = (size_t)o.n_protected * HSPF_LFA_ECMP_COVERAGE_WORDS * 4;
+    uint32_t *ptr = (uint32_t *)pool_->dev(pb);
+    hspf_lfa_ecmp_out out{ptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t total = 0;
+    int rc = hspf_lfa_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, 0, &out, &total);
+    const size_t t = (size_t)total;
+    o.ea_ptr.resize(pb / 4); o.ea_primary.resize(t); o.ea_slot.resize(t); o.ea_metric.resize(t); o.ea_flags.resize(t);
+    o.ea_coverage.assign(cb / 4, 0u);
+    bool ok = rc == HSPF_OK;
+    if (ok && t) {
+      uint32_t *pri = (uint32_t *)pool_->dev(t * 4), *slot = (uint32_t *)pool_->dev(t * 4), *met = (uint32_t *)pool_->dev(t * 4), *cov = (uint32_t *)pool_->dev(cb);
+      uint8_t *fl = (uint8_t *)pool_->dev(t);
+      out = hspf_lfa_ecmp_out{ptr, pri, slot, met, fl, cov};
+      rc = hspf_lfa_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, total, &out, &total);
+      ok = rc == HSPF_OK && hipMemcpy(o.ea_primary.data(), pri, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.ea_slot.data(), slot, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.ea_metric.data(), met, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.ea_flags.data(), fl, t, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.ea_coverage.data(), cov, cb, hipMemcpyDeviceToHost) == hipSuccess;
+      pool_->dev_free(pri, t * 4); pool_->dev_free(slot, t * 4); pool_->dev_free(met, t * 4); pool_->dev_free(cov, cb); pool_->dev_free(fl, t);
+    }
+    ok = ok && hipMemcpy(o.ea_ptr.data(), ptr, pb, hipMemcpyDeviceToHost) == hipSuccess;
+    pool_->dev_free(ptr, pb);
+    if (!ok) throw std::runtime_error(std::string("hspf_lfa_ecmp_device: ") + hspf_last_error(ctx_));
+    return o;
   }
   // (backup_routes / backup_routes_lan stay the base's "not supported": a DeviceRoutes does not keep its prefix table, which
   // hspf_routes_backup_device needs; hspf::Engine::routes_backup_device / routes_backup_lan_device take it explicitly.)

@@ -279,6 +279,43 @@ impl Lfa {
     }
 }
 
+/// One entry of `LfaEcmp`: the alternate of one primary slot of an ECMP destination.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct EcmpAlternate {
+    pub primary: u32,
+    /// The chosen slot and `cost[slot] + d(N, D)`; `None`: this primary has no alternate.
+    pub alternate: Option<(u32, u32)>,
+    /// `HSPF_LFA_LINK_PROTECT | HSPF_LFA_NODE_PROTECT | HSPF_LFA_DOWNSTREAM | HSPF_LFA_EA_PRIMARY`
+    pub flags: u8,
+}
+
+/// Per-primary alternates of the ECMP destinations of one `Engine::lfa_ecmp_device` call: a stream in CSR form over
+/// (protected root, destination), the entries of one destination in ascending primary slot order.
+pub struct LfaEcmp {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub ea_ptr: Vec<u32>,
+    pub ea_primary: Vec<u32>,
+    pub ea_slot: Vec<u32>,
+    pub ea_metric: Vec<u32>,
+    pub ea_flags: Vec<u8>,
+    pub ea_coverage: Vec<u32>,
+}
+
+impl LfaEcmp {
+    /// The entries of (protected root `i`, destination `d`): empty unless `d` has two or more primary slots.
+    pub fn alternates(&self, i: usize, d: u32) -> Vec<EcmpAlternate> {
+        let k = i * self.n_vertices as usize + d as usize;
+        (self.ea_ptr[k] as usize..self.ea_ptr[k + 1] as usize)
+            .map(|e| EcmpAlternate {
+                primary: self.ea_primary[e],
+                alternate: (self.ea_slot[e] != sys::HSPF_LFA_NO_SLOT).then(|| (self.ea_slot[e], self.ea_metric[e])),
+                flags: self.ea_flags[e],
+            })
+            .collect()
+    }
+}
+
 /// Remote loop-free alternates (RFC 7490) of the protected roots of one `Engine::rlfa_device` call.  Slots are strided by
 /// `slot_stride` = 64 * mask words per protected root.
 pub struct Rlfa {
@@ -866,6 +903,87 @@ impl Engine {
             node_mask: match &masks { Some(m) => m.1.to_host(cells * w)?, None => Vec::new() },
             coverage: cov.to_host(np * cov_words)?,
         })
+    }
+
+    /// `hspf_lfa_ecmp_device`: for every destination with two or more primary slots and every one of those primaries, the
+    /// alternate of that primary and what it protects (RFC 5286 sections 3.4, 3.6).  `tables` and `protect` as for
+    /// `lfa_device`.  Two calls: the first sizes the stream (`ea_ptr` and the total), the second fills it.
+    pub fn lfa_ecmp_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool) -> Result<LfaEcmp, Error> {
+        let (n, np) = (tables.n_vertices as usize, protect.len());
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "lfa_ecmp_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let cov_words = sys::HSPF_LFA_ECMP_COVERAGE_WORDS as usize;
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
+        let ea_ptr = self.device_alloc((np * n + 1) * 4)?;
+        let mut out = sys::hspf_lfa_ecmp_out {
+            ea_ptr: ea_ptr.p as *mut u32,
+            ea_primary: ptr::null_mut(),
+            ea_slot: ptr::null_mut(),
+            ea_metric: ptr::null_mut(),
+            ea_flags: ptr::null_mut(),
+            ea_coverage: ptr::null_mut(),
+        };
+        let mut total: u64 = 0;
+        let rc = unsafe {
+            sys::hspf_lfa_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, 0, &mut out, &mut total)
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let cap = total as usize;
+        let mut res = LfaEcmp {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            ea_ptr: Vec::new(),
+            ea_primary: Vec::new(),
+            ea_slot: Vec::new(),
+            ea_metric: Vec::new(),
+            ea_flags: Vec::new(),
+            ea_coverage: vec![0; np * cov_words],
+        };
+        if cap == 0 {
+            res.ea_ptr = ea_ptr.to_host(np * n + 1)?;
+            return Ok(res);
+        }
+        let primary = self.device_alloc(cap * 4)?;
+        let slot = self.device_alloc(cap * 4)?;
+        let metric = self.device_alloc(cap * 4)?;
+        let flags = self.device_alloc(cap)?;
+        let cov = self.device_alloc(np * cov_words * 4)?;
+        out.ea_primary = primary.p as *mut u32;
+        out.ea_slot = slot.p as *mut u32;
+        out.ea_metric = metric.p as *mut u32;
+        out.ea_flags = flags.p as *mut u8;
+        out.ea_coverage = cov.p as *mut u32;
+        let rc = unsafe {
+            sys::hspf_lfa_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, total, &mut out, &mut total)
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        res.ea_ptr = ea_ptr.to_host(np * n + 1)?;
+        res.ea_primary = primary.to_host(cap)?;
+        res.ea_slot = slot.to_host(cap)?;
+        res.ea_metric = metric.to_host(cap)?;
+        res.ea_flags = flags.to_host(cap)?;
+        res.ea_coverage = cov.to_host(np * cov_words)?;
+        Ok(res)
     }
 
     /// `hspf_csr_transpose`: the reversed graph (row t lists the sources of t's incoming links by ascending source, then by
