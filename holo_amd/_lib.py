@@ -113,6 +113,11 @@ class HspfBackupOut(ctypes.Structure):
                 ("bk_flags", ctypes.c_void_p), ("bk_cand_mask", ctypes.c_void_p), ("bk_node_mask", ctypes.c_void_p), ("bk_coverage", ctypes.c_void_p)]
 
 
+class HspfBackupEcmpOut(ctypes.Structure):
+    _fields_ = [("eb_ptr", ctypes.c_void_p), ("eb_primary", ctypes.c_void_p), ("eb_kind", ctypes.c_void_p), ("eb_slot", ctypes.c_void_p),
+                ("eb_metric", ctypes.c_void_p), ("eb_flags", ctypes.c_void_p), ("eb_coverage", ctypes.c_void_p)]
+
+
 class HspfRlfaNodeSel(ctypes.Structure):
     _fields_ = [("nq_node", ctypes.c_void_p), ("nq_via", ctypes.c_void_p), ("nq_metric", ctypes.c_void_p), ("nq_count", ctypes.c_void_p)]
 
@@ -260,6 +265,10 @@ SYMBOLS = [
                                                  ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes), ctypes.POINTER(HspfTilfaOut),
                                                  ctypes.POINTER(HspfBackupOut)]),
+    ("hspf_routes_backup_ecmp_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                                      ctypes.c_uint32, ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes),
+                                                      ctypes.POINTER(HspfTilfaOut), ctypes.c_uint64, ctypes.POINTER(HspfBackupEcmpOut), u64p]),
     # node-protecting remote loop-free alternates
     ("hspf_rlfa_node_select_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,

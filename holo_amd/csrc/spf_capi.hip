@@ -224,7 +224,7 @@ struct hspf_ctx {
   DevBuf lfa_tab, lfa_scal;                          // hspf_lfa_device: the staged per-root slot tables | d(N, S) and d(N, N') of every protected root
   DevBuf lan_tab, lan_scal;                          // hspf_lfa_lan_device: the staged LAN columns | d(N, L) of every protected root
   DevBuf srlg_tab, srlg_scal;                        // hspf_lfa_srlg_device: the staged member tables | d(S, a), d(N, a), d(b, E) of every protected root
-  DevBuf ea_scr;                                     // hspf_lfa_ecmp_device: the tile totals of its count step, scanned in place | the total
+  DevBuf ea_scr;                                     // hspf_lfa_ecmp_device, hspf_routes_backup_ecmp_device: the tile totals of the count step, scanned in place | the total
   uint32_t *h_ev = nullptr;                          // pinned: the event total, stored by k_events_scan itself
   struct EvState {                                   // the last hspf_routes_events, for hspf_routes_events_rest
     bool valid = false;

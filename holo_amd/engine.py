@@ -43,6 +43,7 @@ LFA_NO_SLOT = 0xFFFFFFFF
 LFA_COVERAGE_WORDS = 5
 LFA_EA_PRIMARY = 0x20           # HSPF_LFA_EA_PRIMARY: ea_flags of lfa_ecmp_device(), the alternate is another primary
 LFA_ECMP_COVERAGE_WORDS = 7
+BK_ECMP_COVERAGE_WORDS = 8      # HSPF_BK_ECMP_COVERAGE_WORDS: eb_coverage of routes_backup_ecmp_device()
 LFA_LAN_PRIMARY, LFA_LAN_REFUSED = 0x20, 0x40     # HSPF_LFA_LAN_*: alt_flags / bk_flags of the LAN calls
 LFA_LAN_COVERAGE_WORDS = 7
 LFA_LAN_SAFE_REPAIRS = 0x02     # HSPF_LFA_LAN_SAFE_REPAIRS (routes_backup_lan_device flags): tilfa comes from rlfa_lan_device()'s tables
@@ -410,6 +411,30 @@ class TilfaNodeResult:
 
 
 @dataclass
+class BackupEcmpResult:
+    """Per-primary backups of the ECMP prefixes of one routes_backup_ecmp_device() call: a stream in CSR form over
+    (protected root, prefix), the entries of one prefix in ascending primary slot order."""
+    eb_ptr: np.ndarray       # [P * NP + 1] u32
+    eb_primary: np.ndarray   # [T] u32 the protected primary slot
+    eb_kind: np.ndarray      # [T] u8  BK_LFA | BK_NODE | BK_PAIR | BK_NONE
+    eb_slot: np.ndarray      # [T] u32 BK_LFA: the alternate slot; BK_NODE / BK_PAIR: ti_via of the primary; LFA_NO_SLOT otherwise
+    eb_metric: np.ndarray    # [T] u32 BK_LFA: cost to the prefix; BK_NODE / BK_PAIR: the repair's cost to the primary's neighbour
+    eb_flags: np.ndarray     # [T] u8  BK_LFA: LFA_NODE_PROTECT | LFA_DOWNSTREAM | LFA_EA_PRIMARY
+    eb_coverage: np.ndarray  # [P, 8] u32
+    n_prefixes: int = 0
+
+    @property
+    def total(self) -> int:
+        return len(self.eb_primary)
+
+    def entries(self, i: int, p: int):
+        """[(primary, kind, slot, metric, flags)] of prefix `p` of protected root `i`: empty below two primaries."""
+        k = i * self.n_prefixes + p
+        return [(int(self.eb_primary[e]), int(self.eb_kind[e]), int(self.eb_slot[e]), int(self.eb_metric[e]), int(self.eb_flags[e]))
+                for e in range(int(self.eb_ptr[k]), int(self.eb_ptr[k + 1]))]
+
+
+@dataclass
 class BackupRoutes:
     """Per-prefix routes of ONE root with their backups (SpfContext.backup_routes), on the host; one row each."""
     candidates: LfaCandidates
@@ -426,6 +451,7 @@ class BackupRoutes:
     bk_coverage: np.ndarray   # [1, 7] u32; [1, 9] with lan_protect; [1, 10] with srlg
     tilfa: Optional["TilfaResult"] = None      # the per-slot repairs bk_primary indexes (remote=True)
     srlg: Optional["SrlgMembers"] = None       # backup_routes(srlg=...): the members of every slot, rows filled
+    ecmp: Optional["BackupEcmpResult"] = None  # backup_routes(ecmp=True): a backup per primary of every BK_ECMP prefix
     # node_protect=True (hspf_routes_backup_node_device), None otherwise:
     bn_kind: Optional[np.ndarray] = None       # [1, P] u8  BN_* per prefix with exactly one primary, 0 elsewhere
     bn_primary: Optional[np.ndarray] = None    # [1, P] u32 the one primary slot for BN_LFA .. BN_PAIR, LFA_NO_SLOT otherwise
@@ -1315,6 +1341,63 @@ class SpfContext:
                             bk_flags_ptr=bk_flags_ptr, bk_coverage_ptr=bk_coverage_ptr, bk_cand_mask_ptr=bk_cand_mask_ptr,
                             bk_node_mask_ptr=bk_node_mask_ptr, tilfa=tilfa, flags=flags, lfa_flags=lfa_flags, pfx_origin=pfx_origin)
 
+    def routes_backup_ecmp_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
+                                  pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, eb_ptr_ptr: int, cap_entries: int = 0, eb_primary_ptr: int = 0,
+                                  eb_kind_ptr: int = 0, eb_slot_ptr: int = 0, eb_metric_ptr: int = 0, eb_flags_ptr: int = 0, eb_coverage_ptr: int = 0,
+                                  tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> int:
+        """hspf_routes_backup_ecmp_device(): for every prefix whose route has two or more primary slots and every one of those
+        primaries, its backup — an alternate slot that is loop-free with respect to the PREFIX, or the per-link repair of that
+        primary — as a stream in CSR form.  Inputs as for routes_backup_device(); eb_ptr_ptr [P * NP + 1] u32, the entry arrays
+        `cap_entries` elements each (0 with cap_entries == 0: eb_ptr and the total alone), eb_coverage_ptr
+        [P, BK_ECMP_COVERAGE_WORDS] u32.  Returns the total number of entries; when it exceeds cap_entries only eb_ptr was
+        written and the call is to be repeated with larger arrays."""
+        name = "routes_backup_ecmp_device"
+        src = (pfx_ptr, pfx_vertex, pfx_metric)
+        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
+        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
+        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
+        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
+            raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
+        org = None if pfx_origin is None else np.ascontiguousarray(pfx_origin, np.uint32)
+        arr, keep = self._protect_array(protect, name)
+        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags,
+                              None if org is None else _u32(org), None, None, None)
+        r = L.HspfRoutes(*(x or None for x in routes))
+        ti = None
+        if tilfa is not None:
+            ti = L.HspfTilfaOut(tilfa[0] or None, None, None, tilfa[1] or None, None, tilfa[2] or None, None, None, None)
+        out = L.HspfBackupEcmpOut(eb_ptr_ptr or None, eb_primary_ptr or None, eb_kind_ptr or None, eb_slot_ptr or None, eb_metric_ptr or None,
+                                  eb_flags_ptr or None, eb_coverage_ptr or None)
+        total = ctypes.c_uint64()
+        rc = self.lib.hspf_routes_backup_ecmp_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
+                                                     mask_ptr or None, arr, len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r),
+                                                     None if ti is None else ctypes.byref(ti), cap_entries, ctypes.byref(out), ctypes.byref(total))
+        del keep
+        self._check_rc("hspf_" + name, rc)
+        return int(total.value)
+
+    def _backup_ecmp_tail(self, n: int, R: int, W: int, dev: dict, protect, backup, tilfa: bool, lfa_flags: int) -> BackupEcmpResult:
+        """backup_routes(ecmp=True) behind routes_backup_device(), while the tables, the routes and the repairs are on the device: the
+        sizing call, then the filling call with arrays of that size."""
+        NP = len(backup[0]) - 1
+        ptr = np.empty(NP + 1, np.uint32)
+        cov = np.zeros((1, BK_ECMP_COVERAGE_WORDS), np.uint32)
+        kw = dict(routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
+                  tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None, flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags)
+        tables = (n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, backup[0], backup[1], backup[2])
+        with self._dev_buffers(dict(ptr=ptr.nbytes)) as pd:
+            total = self.routes_backup_ecmp_device(*tables, eb_ptr_ptr=pd["ptr"], **kw)
+            host = dict(primary=np.empty(total, np.uint32), kind=np.empty(total, np.uint8), slot=np.empty(total, np.uint32),
+                        metric=np.empty(total, np.uint32), eflags=np.empty(total, np.uint8))
+            if total:
+                with self._dev_buffers(dict({k: a.nbytes for k, a in host.items()}, cov=cov.nbytes)) as ent:
+                    self.routes_backup_ecmp_device(*tables, eb_ptr_ptr=pd["ptr"], cap_entries=total, eb_primary_ptr=ent["primary"],
+                                                   eb_kind_ptr=ent["kind"], eb_slot_ptr=ent["slot"], eb_metric_ptr=ent["metric"],
+                                                   eb_flags_ptr=ent["eflags"], eb_coverage_ptr=ent["cov"], **kw)
+                    self._fetch(dict(host, cov=cov), ent)
+            self._fetch(dict(ptr=ptr), pd)
+        return BackupEcmpResult(ptr, host["primary"], host["kind"], host["slot"], host["metric"], host["eflags"], cov, n_prefixes=NP)
+
     def _routes_backup(self, lans, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                        pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
                        bk_metric_ptr: int, bk_flags_ptr: int, bk_coverage_ptr: int, bk_cand_mask_ptr: int = 0, bk_node_mask_ptr: int = 0,
@@ -1494,7 +1577,7 @@ class SpfContext:
 
     def backup_routes(self, graph: SpfGraph, root: int, prefix_table, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False,
                       remote: bool = True, lan_protect: bool = False, lan_repairs: bool = False, node_protect: bool = False, max_pq: int = 16,
-                      max_pairs: int = 16, srlg: Optional[tuple] = None, srlg_repairs: bool = False) -> BackupRoutes:
+                      max_pairs: int = 16, srlg: Optional[tuple] = None, srlg_repairs: bool = False, ecmp: bool = False) -> BackupRoutes:
         """The routes of one root with their backups, start to finish: run_device() of [root] + its distinct neighbour routers,
         routes_device(), lfa_device() and — with `remote` — rlfa_device() + tilfa_device() (on the transposed graph too unless
         `symmetric`), then routes_backup_device(); only the route and bk_* arrays (and the per-slot repairs) come to the host.
@@ -1510,7 +1593,12 @@ class SpfContext:
         also holds the member endpoints' rows, lfa_srlg_device() and — with `remote` — rlfa_srlg_device() + tilfa_device() take the
         plain calls' places, and routes_backup_srlg_device() writes the backups (bk_coverage has ten words, BackupRoutes.srlg holds
         the members).  srlg_repairs (needs srlg and remote): LFA_SRLG_SAFE_REPAIRS — a primary with members and no alternate takes
-        its per-link repair instead of BK_NONE, unless the repair's forced link is itself a member."""
+        its per-link repair instead of BK_NONE, unless the repair's forced link is itself a member.
+        ecmp (the plain mode only: excludes lan_protect, node_protect and srlg): routes_backup_ecmp_device() runs twice on the same
+        device chain — the sizing call, then the filling call — and BackupRoutes.ecmp holds a backup per primary of every BK_ECMP
+        prefix; every other field is what ecmp=False returns."""
+        if ecmp and (lan_protect or node_protect or srlg is not None):
+            raise ValueError("backup_routes: ecmp excludes lan_protect, node_protect and srlg")
         if srlg is not None and (lan_protect or node_protect):
             raise ValueError("backup_routes: srlg excludes lan_protect and node_protect")
         if srlg_repairs and (srlg is None or not remote):
@@ -1527,7 +1615,7 @@ class SpfContext:
         if srlg is not None:
             return self._backup_srlg(graph, root, tab, srlg[0], srlg[1], run_flags, lfa_flags, symmetric, remote, srlg_repairs)
         return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab, lan_protect=lan_protect,
-                          lan_spaces=lan_repairs, node=(int(max_pq), int(max_pairs)) if node_protect else None)
+                          lan_spaces=lan_repairs, node=(int(max_pq), int(max_pairs)) if node_protect else None, ecmp=ecmp)
 
     def rlfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False, symmetric: bool = False,
              lan_protect: bool = False):
@@ -1547,11 +1635,12 @@ class SpfContext:
         return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True, lan_protect=lan_protect, lan_spaces=lan_protect)
 
     def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None,
-              lan_protect: bool = False, lan_spaces: bool = False, node=None):
+              lan_protect: bool = False, lan_spaces: bool = False, node=None, ecmp: bool = False):
         """The chain behind rlfa(), tilfa() and backup_routes().  backup: None, or (pfx_ptr, pfx_vertex, pfx_metric, flags) — then
         the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`).  lan_spaces
         (with lan_protect): rlfa_lan_device() instead of rlfa_device(), and LFA_LAN_SAFE_REPAIRS for the backups.  node (with backup):
-        None, or (max_pq, max_pairs) of backup_routes(node_protect=True) — then _backup_node_tail() runs on the same rows."""
+        None, or (max_pq, max_pairs) of backup_routes(node_protect=True) — then _backup_node_tail() runs on the same rows.  ecmp (with
+        backup): _backup_ecmp_tail() runs on the same rows."""
         if lan_spaces and (not lan_protect or symmetric):
             raise ValueError("the LAN-safe remote calls need lan_protect and the transposed run (symmetric=False)")
         plan = self._frr_plan(graph, root, lan_protect)
@@ -1620,10 +1709,11 @@ class SpfContext:
                                     flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_LAN_SAFE_REPAIRS if lan_spaces else 0),
                                     **{k + "_ptr": dev[k] for k in bk_names[3:]})
             bn = self._backup_node_tail(graph, run_flags, lfa_flags, backup, dev, protect, R, W, *node) if backup is not None and node else {}
+            eb = self._backup_ecmp_tail(n, R, W, dev, protect, backup, tilfa, lfa_flags) if backup is not None and ecmp else None
             self._fetch(host, dev)
             if backup is not None:
                 return BackupRoutes(cand, *(host[k] for k in bk_names),
-                                    tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None, **bn)
+                                    tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None, ecmp=eb, **bn)
             lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"], lan=plan.lan)
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])

@@ -779,7 +779,7 @@ int hspf_lfa_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_
  *
  * From ea_* to a backup next hop per primary next hop: INTEGRATION.md §5s.
  *
- * OUT OF SCOPE: ECMP backups per prefix (the follow-up: this call's rule with d_N(p) in place of d(N, D)); the LAN-safe and
+ * OUT OF SCOPE: ECMP backups per prefix (hspf_routes_backup_ecmp_device, below: this call's rule with d_N(p) in place of d(N, D)); the LAN-safe and
  * SRLG-safe variants of this call; remote or TI-LFA repairs for an ECMP primary that has no alternate; entries for destinations
  * with a single primary (alt_slot of hspf_lfa_device is that answer). */
 #define HSPF_LFA_EA_PRIMARY            0x20u   /* ea_flags: the alternate is another primary of the destination */
@@ -1203,7 +1203,7 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
  * From bk_* to a next hop with a backup and its label stack: INTEGRATION.md §5k.
  *
  * OUT OF SCOPE: HSPF_PFX_ORDERED tables (OSPFv3's interleaved fold: HSPF_E_INVAL); backups for ECMP routes (per vertex:
- * hspf_lfa_ecmp_device, above; per prefix: not yet; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
+ * hspf_lfa_ecmp_device, above; per prefix: hspf_routes_backup_ecmp_device, below; the two sets are still written); per-prefix Q-spaces (the remote repair is the primary LINK's, as in
  * td_kind; node-protecting remote repairs per prefix are hspf_routes_backup_node_device's, below).  Loop-freeness with respect to a LAN pseudonode is not checked by THIS
  * call: hspf_routes_backup_lan_device ("broadcast-link protection", above) adds it.  One lane walks one prefix: there is no wave-per-prefix path for prefixes with very many advertisers. */
 #define HSPF_BK_NO_ROUTE       0u
@@ -1234,6 +1234,80 @@ int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n
                                   const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
                                   const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
                                   hspf_backup_out *out_dev);
+
+/* ---- per-primary backups for ECMP prefixes (RFC 5286 sections 3.4, 3.6, 6.1): new symbol, same ABI number -------------------------
+ * The four per-prefix calls stop at a route with two or more primary next hops: HSPF_BK_ECMP, the two sets that are safe against
+ * ALL primaries at once, no choice.  In a fat-tree or a meshed core that is most of the RIB.  The per-vertex stream of
+ * hspf_lfa_ecmp_device cannot stand in: a multi-homed prefix can be ECMP through two advertisers whose vertices have one primary
+ * each, and the loop-free inequality has to be held against the neighbour's distance to the PREFIX.  hspf_routes_backup_ecmp_device
+ * gives, for every prefix whose route has at least two primary slots and for every one of those primaries, the backup of that
+ * primary and what it protects: the rule of hspf_lfa_ecmp_device with d_N(p) in place of d(N, D), and the per-link repair of
+ * hspf_routes_backup_device as the fallback.
+ *
+ * Inputs.  Exactly those of hspf_routes_backup_device: the forward table set, `prot`, n_prot, lfa_flags, the HOST prefix table
+ * (HSPF_PFX_SATURATING, HSPF_PFX_LAST_MIN and HSPF_PFX_RESIDENT as there; HSPF_PFX_ORDERED: HSPF_E_INVAL), routes_dev, and
+ * tilfa_dev (NULL: no fallback; only ti_kind, ti_via and ti_metric are read).  cap_entries and out_total follow the convention of
+ * hspf_lfa_ecmp_device.  No graph.
+ * Terms as for hspf_routes_backup_device: S a protected root, p a prefix whose route exists (best_entry != 0xFFFFFFFF), P = the bits
+ * of nexthop_mask[p] below n_slots, d_X(p) the minimum over p's entries with the same saturation rule, d_S(p) = best_metric, read
+ * and not recomputed.  The call speaks only about p with popcount(P) >= 2.  For such a p and a protected primary h in P let
+ * E = nbr[h] (may be HSPF_NO_ROOT).  A slot k with N = nbr[k] is judged by ONE rule whether or not k is itself a primary; every sum
+ * is evaluated in 64 bits and a term that is "not reached" makes its inequality false:
+ *   cand(h)     k != h,  and nbr[k] != HSPF_NO_ROOT,  and d_N(p) < d(N, S) + d_S(p),  and root_link[k] != root_link[h],  and
+ *               (cflags[k] has no HSPF_LFA_C_NO_TRANSIT, or the call passes HSPF_LFA_IGNORE_OVERLOAD, or N's own entry (v == N)
+ *               attains d_N(p): N delivers without transiting, as in hspf_routes_backup_device);
+ *   node(h)     k is in cand(h), E is a router (E != HSPF_NO_ROOT), d_E(p) exists, and d_N(p) < d(N, E) + d_E(p)   (N == E makes
+ *               this false by itself);
+ *   downstream  d_N(p) < d_S(p);
+ *   choice      the rule of hspf_lfa_ecmp_device: a member of node(h) before a member of cand(h) only, then a slot that is in P
+ *               before one that is not, then the smaller cost[k] + d_N(p) (64 bits), then the smaller slot index;
+ *   fallback    no slot chosen for h, tilfa_dev given and ti_kind[h] != HSPF_TILFA_NONE: the per-link repair of h backs up this
+ *               next hop (it delivers to E, and E is a next hop of S towards p: the argument of the one-primary fallback).
+ *
+ * Output: a compact stream in CSR form over (protected root, prefix).  DEVICE pointers:
+ *   eb_ptr       u32 [n_prot * n_prefixes + 1].  For i * n_prefixes + p:  eb_ptr[. + 1] - eb_ptr[.] is popcount(P) when that is at
+ *                least 2, and 0 otherwise (an absent route, a route with fewer than two primaries).  ALWAYS written completely.
+ *   the entries of one p are its primaries in ascending slot order; entry arrays of cap_entries elements each:
+ *   eb_primary   u32  h
+ *   eb_kind      u8   HSPF_BK_LFA a slot was chosen | HSPF_BK_NODE / HSPF_BK_PAIR the one- / two-segment repair of h | HSPF_BK_NONE
+ *   eb_slot      u32  _LFA: the chosen slot; _NODE / _PAIR: ti_via[h] (may be HSPF_RLFA_VIA_SELF); HSPF_LFA_NO_SLOT otherwise
+ *   eb_metric    u32  _LFA: cost[k] + d_N(p) saturated at 0xFFFFFFFE; _NODE / _PAIR: ti_metric[h] — the cost to E, NOT to p; 0
+ *                     otherwise
+ *   eb_flags     u8   _LFA: HSPF_LFA_NODE_PROTECT | HSPF_LFA_DOWNSTREAM | HSPF_LFA_EA_PRIMARY (the backup is another primary of p)
+ *                     with their existing bit values; 0 otherwise
+ *   eb_coverage  u32 [n_prot][HSPF_BK_ECMP_COVERAGE_WORDS], counted on the device: ECMP prefixes | entries | entries of kind _LFA |
+ *                node-protecting entries | downstream entries | entries whose alternate is a primary | repaired entries (_NODE or
+ *                _PAIR) | ECMP prefixes of which EVERY primary has a backup of any kind.
+ * *out_total (HOST): the total number of entries, = eb_ptr[n_prot * n_prefixes].
+ *
+ * Capacity.  When the total exceeds cap_entries the call still returns 0 and writes eb_ptr and *out_total; the entry arrays and
+ * eb_coverage are then unspecified, and the caller repeats the call with larger arrays.  cap_entries == 0 with NULL entry arrays
+ * and NULL eb_coverage asks for eb_ptr and the total alone.
+ * Argument errors — everything hspf_routes_backup_device rejects; eb_ptr or out_total NULL; an entry array or eb_coverage NULL with
+ * cap_entries > 0; and the host-side bound  sum over the protected roots of n_prefixes * max(n_slots, 1) >= 2^32  (the stream is
+ * indexed in 32 bits: split the protect list) — return HSPF_E_INVAL with a text in hspf_last_error that names
+ * hspf_routes_backup_ecmp_device, before anything is launched.  Everything is enqueued on the context's stream and the call
+ * synchronises once at the end.
+ *
+ * From eb_* to a backup per next hop of a prefix: INTEGRATION.md §5t.
+ *
+ * OUT OF SCOPE: the LAN-safe, SRLG-safe and node-protecting-remote variants of this call (hspf_routes_backup_lan_device, _srlg_ and
+ * _node_ still answer HSPF_BK_ECMP with the two sets); per-prefix Q-spaces; HSPF_PFX_ORDERED tables. */
+#define HSPF_BK_ECMP_COVERAGE_WORDS    8u
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint32_t *eb_ptr;              /* [n_prot * n_prefixes + 1]                                                  */
+  uint32_t *eb_primary;          /* [cap_entries]                                                              */
+  uint8_t  *eb_kind;             /* [cap_entries]                                                              */
+  uint32_t *eb_slot;             /* [cap_entries]                                                              */
+  uint32_t *eb_metric;           /* [cap_entries]                                                              */
+  uint8_t  *eb_flags;            /* [cap_entries]                                                              */
+  uint32_t *eb_coverage;         /* [n_prot][HSPF_BK_ECMP_COVERAGE_WORDS]                                      */
+} hspf_backup_ecmp_out;
+int hspf_routes_backup_ecmp_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                   const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *table,
+                                   const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, uint64_t cap_entries,
+                                   hspf_backup_ecmp_out *out_dev, uint64_t *out_total);
 
 /* ---- node-protecting remote loop-free alternates on device (RFC 8102): new symbols, same ABI number -------------------------
  * hspf_rlfa_device protects LINKS: the tunnel to its PQ node, and that node's own path on to the destination, may run straight
@@ -1478,7 +1552,7 @@ int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, 
  * From bn_* to a next hop with a label stack: INTEGRATION.md §5p.
  *
  * OUT OF SCOPE: LAN pseudonodes as the protected node; LAN-safe release paths (the limitation of the two select calls); ECMP routes
- * (bn_kind 0; per vertex: hspf_lfa_ecmp_device, per prefix: not yet); a wave-per-prefix path for prefixes with very many advertisers (one lane walks
+ * (bn_kind 0; per vertex: hspf_lfa_ecmp_device, per prefix: hspf_routes_backup_ecmp_device, plain mode only); a wave-per-prefix path for prefixes with very many advertisers (one lane walks
  * one prefix); SRLGs. */
 #define HSPF_BN_LFA            1u             /* bn_kind */
 #define HSPF_BN_PQ             2u

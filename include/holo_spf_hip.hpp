@@ -181,6 +181,13 @@ struct BackupRoutes {
   std::vector<uint32_t> bk_primary, bk_slot, bk_metric;   // [n_prefixes]
   std::vector<uint64_t> bk_cand_mask, bk_node_mask;       // [n_prefixes][mask_words]
   uint32_t bk_coverage[HSPF_BK_COVERAGE_WORDS] = {};
+  // backup_routes(..., ecmp = true): per primary of every HSPF_BK_ECMP prefix its backup (hspf_routes_backup_ecmp_device), a stream
+  // in CSR form over the prefixes, the entries of one prefix in ascending primary slot order.  Empty otherwise.
+  bool with_ecmp = false;
+  std::vector<uint32_t> eb_ptr;                           // [n_prefixes + 1]
+  std::vector<uint32_t> eb_primary, eb_slot, eb_metric;   // [eb_ptr.back()]
+  std::vector<uint8_t> eb_kind, eb_flags;                 // HSPF_BK_LFA / _NODE / _PAIR / _NONE | HSPF_LFA_NODE_PROTECT | _DOWNSTREAM | HSPF_LFA_EA_PRIMARY
+  uint32_t eb_coverage[HSPF_BK_ECMP_COVERAGE_WORDS] = {};
 };
 
 class Engine;
@@ -635,6 +642,18 @@ class Engine {
                                              lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_device (") + hspf_last_error(ctx_) + ")");
   }
+  // hspf_routes_backup_ecmp_device on the same inputs: per primary of every prefix with two or more primary slots, its backup.
+  // Returns the total number of entries; when it exceeds cap_entries only eb_ptr was written (repeat with larger arrays).
+  uint64_t routes_backup_ecmp_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                                     const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags,
+                                     const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev, uint64_t cap_entries,
+                                     hspf_backup_ecmp_out out_dev) {
+    uint64_t total = 0;
+    const int rc = hspf_routes_backup_ecmp_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                                  (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, cap_entries, &out_dev, &total);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_ecmp_device (") + hspf_last_error(ctx_) + ")");
+    return total;
+  }
   // hspf_routes_backup_lan_device: the same with loop-freeness towards the pseudonodes of the primaries' LANs (`lans` as for
   // lfa_lan_device; bk_coverage has HSPF_BK_LAN_COVERAGE_WORDS words per root).
   void routes_backup_lan_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
@@ -674,12 +693,14 @@ class Engine {
   }
   // One root start to finish: the chain of tilfa() (of lfa() alone without `remote`), hspf_routes_device for the root's row and
   // hspf_routes_backup_device, everything kept on the device in between.  table_flags: HSPF_PFX_SATURATING / HSPF_PFX_LAST_MIN.
+  // ecmp: hspf_routes_backup_ecmp_device runs twice behind it on the same tables (the sizing call, the filling call): eb_* are filled.
   BackupRoutes backup_routes(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
                              const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, const std::vector<uint32_t> &pfx_ptr,
                              const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric, uint32_t table_flags = 0,
-                             uint32_t run_flags = 0, uint32_t lfa_flags = 0, bool symmetric = false, bool remote = true) {
+                             uint32_t run_flags = 0, uint32_t lfa_flags = 0, bool symmetric = false, bool remote = true, bool ecmp = false) {
     if (pfx_ptr.empty() || pfx_vertex.size() != pfx_metric.size()) throw Error(HSPF_E_INVAL, "Engine::backup_routes: malformed prefix table");
     BackupRoutes b;
+    b.with_ecmp = ecmp;
     b.n_prefixes = (uint32_t)pfx_ptr.size() - 1u;
     const hspf_prefix_table t{b.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.data(), pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT,
                               nullptr, nullptr, nullptr, nullptr};
@@ -832,6 +853,23 @@ class Engine {
       bk->bk_cand_mask = cmk.to_host<uint64_t>(np * W); bk->bk_node_mask = nmk.to_host<uint64_t>(np * W);
       const std::vector<uint32_t> c7 = cv7.to_host<uint32_t>(HSPF_BK_COVERAGE_WORDS);
       std::copy(c7.begin(), c7.end(), bk->bk_coverage);
+      if (bk->with_ecmp) {
+        DeviceBuffer ptr(ctx_, (np + 1) * 4);
+        const uint64_t total = routes_backup_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, tr, ro,
+                                                         ti ? &tio : nullptr, 0, hspf_backup_ecmp_out{ptr.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+        if (total) {
+          const size_t t = (size_t)total;
+          DeviceBuffer pri(ctx_, t * 4), knd(ctx_, t), slot(ctx_, t * 4), met(ctx_, t * 4), efl(ctx_, t), cov(ctx_, HSPF_BK_ECMP_COVERAGE_WORDS * 4);
+          routes_backup_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, tr, ro, ti ? &tio : nullptr, total,
+                                    hspf_backup_ecmp_out{ptr.as<uint32_t>(), pri.as<uint32_t>(), knd.as<uint8_t>(), slot.as<uint32_t>(), met.as<uint32_t>(),
+                                                         efl.as<uint8_t>(), cov.as<uint32_t>()});
+          bk->eb_primary = pri.to_host<uint32_t>(t); bk->eb_kind = knd.to_host<uint8_t>(t); bk->eb_slot = slot.to_host<uint32_t>(t);
+          bk->eb_metric = met.to_host<uint32_t>(t); bk->eb_flags = efl.to_host<uint8_t>(t);
+          const std::vector<uint32_t> c8 = cov.to_host<uint32_t>(HSPF_BK_ECMP_COVERAGE_WORDS);
+          std::copy(c8.begin(), c8.end(), bk->eb_coverage);
+        }
+        bk->eb_ptr = ptr.to_host<uint32_t>(np + 1);
+      }
     }
     return r;
   }

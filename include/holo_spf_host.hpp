@@ -202,6 +202,16 @@ struct BackupOut {
   std::vector<uint64_t> bk_cand_mask, bk_node_mask;         // [n_protected][n_prefixes][mask_words]
   std::vector<uint32_t> bk_coverage;                        // [n_protected][HSPF_BK_COVERAGE_WORDS] (backup_routes_srlg: HSPF_BK_SRLG_COVERAGE_WORDS)
 };
+// Per-primary backups of the ECMP prefixes (hspf_routes_backup_ecmp_device) of the same protected roots: a stream in CSR form over
+// (protected root, prefix), the entries of one prefix in ascending primary slot order.  supported == false: no such call.
+struct BackupEcmpOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_prefixes = 0;
+  std::vector<uint32_t> eb_ptr;                             // [n_protected * n_prefixes + 1]
+  std::vector<uint32_t> eb_primary, eb_slot, eb_metric;     // [eb_ptr.back()]
+  std::vector<uint8_t> eb_kind, eb_flags;
+  std::vector<uint32_t> eb_coverage;                        // [n_protected][HSPF_BK_ECMP_COVERAGE_WORDS]
+};
 // Per-prefix node-protecting backups (hspf_routes_backup_node_device) of the same protected roots over the prefix table of a
 // DeviceRoutes: per (protected root, prefix) with one primary the kind (HSPF_BN_*), the primary slot and the chosen repair.
 // supported == false: no such call.
@@ -277,6 +287,13 @@ class Engine {
                                        const std::vector<uint32_t> & /*pfx_vertex*/, const std::vector<uint32_t> & /*pfx_metric*/,
                                        uint32_t /*table_flags*/, const std::vector<LfaProtect> &, const std::vector<Srlg> &, uint32_t /*lfa_flags*/,
                                        const TilfaOut * /*tilfa*/) { return BackupOut{}; }
+  // Per primary slot of every prefix whose route has two or more of them: its backup (hspf_routes_backup_ecmp_device).  `routes`:
+  // what routes_device() wrote for `run` and the prefix table given here again (pfx_* / table_flags: the call reads the
+  // advertisers); `tilfa`: nullptr, or what tilfa() returned for the same protect list.  The default: not supported.
+  virtual BackupEcmpOut backup_routes_ecmp(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<uint32_t> & /*pfx_ptr*/,
+                                           const std::vector<uint32_t> & /*pfx_vertex*/, const std::vector<uint32_t> & /*pfx_metric*/,
+                                           uint32_t /*table_flags*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
+                                           const TilfaOut * /*tilfa*/) { return BackupEcmpOut{}; }
   virtual std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                         const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
                                         uint32_t max_path_metric) = 0;
@@ -1266,6 +1283,75 @@ class HipEngine : public Engine {
       fetch(o.bk_coverage, out.bk_coverage, cb);
     }
     pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    return o;
+  }
+  // two calls: eb_ptr and the total, then the entries into arrays of that size
+  BackupEcmpOut backup_routes_ecmp(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
+                                   const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
+                                   uint32_t lfa_flags, const TilfaOut *tilfa) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rt = static_cast<HipDeviceRoutes &>(routes);
+    BackupEcmpOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes;
+    if (protect.empty()) return o;
+    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
+      throw std::runtime_error("backup_routes_ecmp: the routes are not of this run and prefix table");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("backup_routes_ecmp: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t ps = (size_t)o.n_protected * 64u * r.mask_words;
+    const bool with_ti = tilfa && tilfa->supported;
+    if (with_ti && (tilfa->ti_kind.size() != ps || tilfa->ti_via.size() != ps || tilfa->ti_metric.size() != ps))
+      throw std::runtime_error("backup_routes_ecmp: the TI-LFA result is not of this protect list");
+    const size_t pb = ((size_t)o.n_protected * o.n_prefixes + 1) * 4, cb = (size_t)o.n_protected * HSPF_BK_ECMP_COVERAGE_WORDS * 4;
+    // one block: eb_ptr | eb_coverage | ti_via | ti_metric | ti_kind
+    const size_t head = pb + cb + (with_ti ? ps * 9 : 0);
+    uint8_t *blk = (uint8_t *)pool_->dev(head);
+    uint32_t *ptr = (uint32_t *)blk, *cov = ptr + pb / 4;
+    hspf_tilfa_out ti{};
+    bool ok = true;
+    if (with_ti) {
+      ti.ti_via = cov + cb / 4; ti.ti_metric = ti.ti_via + ps; ti.ti_kind = (uint8_t *)(ti.ti_metric + ps);
+      ok = hipMemcpy(ti.ti_via, tilfa->ti_via.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(ti.ti_metric, tilfa->ti_metric.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(ti.ti_kind, tilfa->ti_kind.data(), ps, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    static const uint32_t zero = 0;
+    const hspf_prefix_table tab{o.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
+                                pfx_metric.empty() ? &zero : pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT};
+    const hspf_routes ro = rt.raw();
+    hspf_backup_ecmp_out out{ptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t total = 0;
+    const char *what = "hipMemcpy of the repairs: ";
+    if (ok) {
+      what = "hspf_routes_backup_ecmp_device: ";
+      ok = hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab, &ro,
+                                          with_ti ? &ti : nullptr, 0, &out, &total) == HSPF_OK;
+    }
+    const size_t t = ok ? (size_t)total : 0;
+    o.eb_ptr.resize(pb / 4); o.eb_primary.resize(t); o.eb_kind.resize(t); o.eb_slot.resize(t); o.eb_metric.resize(t); o.eb_flags.resize(t);
+    o.eb_coverage.assign(cb / 4, 0u);
+    if (ok && t) {
+      // the entries: eb_primary | eb_slot | eb_metric | eb_kind | eb_flags
+      uint8_t *ent = (uint8_t *)pool_->dev(t * 14);
+      out = hspf_backup_ecmp_out{ptr, (uint32_t *)ent, ent + t * 12, (uint32_t *)ent + t, (uint32_t *)ent + 2 * t, ent + t * 13, cov};
+      ok = hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab, &ro,
+                                          with_ti ? &ti : nullptr, total, &out, &total) == HSPF_OK &&
+           hipMemcpy(o.eb_primary.data(), out.eb_primary, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.eb_slot.data(), out.eb_slot, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.eb_metric.data(), out.eb_metric, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.eb_kind.data(), out.eb_kind, t, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.eb_flags.data(), out.eb_flags, t, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(o.eb_coverage.data(), cov, cb, hipMemcpyDeviceToHost) == hipSuccess;
+      pool_->dev_free(ent, t * 14);
+    }
+    ok = ok && hipMemcpy(o.eb_ptr.data(), ptr, pb, hipMemcpyDeviceToHost) == hipSuccess;
+    pool_->dev_free(blk, head);
     if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
     return o;
   }

@@ -531,6 +531,48 @@ impl PrefixTable {
     }
 }
 
+/// One entry of `BackupEcmp`: the backup of one primary slot of an ECMP prefix.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct EcmpBackup {
+    pub primary: u32,
+    /// `HSPF_BK_LFA`, `HSPF_BK_NODE`, `HSPF_BK_PAIR` or `HSPF_BK_NONE`
+    pub kind: u8,
+    /// `HSPF_BK_LFA`: the chosen slot and `cost[slot] + d_N(p)`; `HSPF_BK_NODE` / `HSPF_BK_PAIR`: `ti_via` of the primary and the
+    /// repair's cost to the primary's neighbour; `None`: this primary has no backup.
+    pub backup: Option<(u32, u32)>,
+    /// `HSPF_LFA_NODE_PROTECT | HSPF_LFA_DOWNSTREAM | HSPF_LFA_EA_PRIMARY` for `HSPF_BK_LFA`
+    pub flags: u8,
+}
+
+/// Per-primary backups of the ECMP prefixes of one `Engine::routes_backup_ecmp_device` call: a stream in CSR form over
+/// (protected root, prefix), the entries of one prefix in ascending primary slot order.
+pub struct BackupEcmp {
+    pub n_protected: u32,
+    pub n_prefixes: u32,
+    pub eb_ptr: Vec<u32>,
+    pub eb_primary: Vec<u32>,
+    pub eb_kind: Vec<u8>,
+    pub eb_slot: Vec<u32>,
+    pub eb_metric: Vec<u32>,
+    pub eb_flags: Vec<u8>,
+    pub eb_coverage: Vec<u32>,
+}
+
+impl BackupEcmp {
+    /// The entries of (protected root `i`, prefix `p`): empty unless the route of `p` has two or more primary slots.
+    pub fn entries(&self, i: usize, p: u32) -> Vec<EcmpBackup> {
+        let k = i * self.n_prefixes as usize + p as usize;
+        (self.eb_ptr[k] as usize..self.eb_ptr[k + 1] as usize)
+            .map(|e| EcmpBackup {
+                primary: self.eb_primary[e],
+                kind: self.eb_kind[e],
+                backup: (self.eb_kind[e] as u32 != sys::HSPF_BK_NONE).then(|| (self.eb_slot[e], self.eb_metric[e])),
+                flags: self.eb_flags[e],
+            })
+            .collect()
+    }
+}
+
 /// Per-prefix backup routes of one `routes_backup_device` call, on the host: `[n_protected][n_prefixes]` (the masks with `words`
 /// words per entry), `bk_coverage` `[n_protected][HSPF_BK_COVERAGE_WORDS]`; `bk_kind` holds `HSPF_BK_*`.
 pub struct Backup {
@@ -1524,6 +1566,136 @@ impl Engine {
     pub fn routes_backup_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool,
                                 table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, tilfa: Option<&Tilfa>) -> Result<Backup, Error> {
         self.routes_backup_device_with(tables, protect, None, None, ignore_overload, table, resident, routes, tilfa)
+    }
+
+    /// `hspf_routes_backup_ecmp_device`: for every prefix whose route has two or more primary slots and every one of those
+    /// primaries, its backup — an alternate slot that is loop-free with respect to the PREFIX (the rule of `lfa_ecmp_device` with
+    /// the neighbour's distance to the prefix), or the repair of that primary's link out of `tilfa`.  Inputs as for
+    /// `routes_backup_device`.  Two calls: the first sizes the stream (`eb_ptr` and the total), the second fills it.
+    #[allow(clippy::too_many_arguments)]
+    pub fn routes_backup_ecmp_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool,
+                                     table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, tilfa: Option<&Tilfa>) -> Result<BackupEcmp, Error> {
+        let (np, pf, w) = (protect.len(), table.n_prefixes() as usize, tables.words as usize);
+        if routes.n_prefixes != table.n_prefixes() || routes.words != tables.words {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_ecmp_device: the routes are not of this table set and table".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_ecmp_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let slots = np * 64 * w;
+        let ti = match tilfa {
+            Some(t) if t.ti_kind.len() == slots && t.ti_via.len() == slots && t.ti_metric.len() == slots => {
+                Some((self.device_from(&t.ti_kind)?, self.device_from(&t.ti_via)?, self.device_from(&t.ti_metric)?))
+            }
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_ecmp_device: the TI-LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let ti_raw = ti.as_ref().map(|(k, v, m)| sys::hspf_tilfa_out {
+            ti_kind: k.p as *mut u8,
+            ti_p: ptr::null_mut(),
+            ti_q: ptr::null_mut(),
+            ti_via: v.p as *mut u32,
+            ti_link: ptr::null_mut(),
+            ti_metric: m.p as *mut u32,
+            ti_counts: ptr::null_mut(),
+            td_kind: ptr::null_mut(),
+            td_coverage: ptr::null_mut(),
+        });
+        let mut t = sys::hspf_prefix_table {
+            n_prefixes: table.n_prefixes(),
+            n_entries: table.pfx_vertex.len() as u32,
+            pfx_ptr: table.pfx_ptr.as_ptr(),
+            pfx_vertex: table.pfx_vertex.as_ptr(),
+            pfx_metric: table.pfx_metric.as_ptr(),
+            flags: table.flags | if resident { sys::HSPF_PFX_RESIDENT } else { 0 },
+            pfx_origin: ptr::null(),
+            init_exists: ptr::null(),
+            init_metric: ptr::null(),
+            init_origin: ptr::null(),
+        };
+        let r = sys::hspf_routes {
+            best_metric: routes.best_metric.p as *mut u32,
+            best_entry: routes.best_entry.p as *mut u32,
+            nexthop_mask: routes.nexthop_mask.p as *mut u64,
+        };
+        let cov_words = sys::HSPF_BK_ECMP_COVERAGE_WORDS as usize;
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
+        let ti_ptr = ti_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_out);
+        let eb_ptr = self.device_alloc((np * pf + 1) * 4)?;
+        let mut out = sys::hspf_backup_ecmp_out {
+            eb_ptr: eb_ptr.p as *mut u32,
+            eb_primary: ptr::null_mut(),
+            eb_kind: ptr::null_mut(),
+            eb_slot: ptr::null_mut(),
+            eb_metric: ptr::null_mut(),
+            eb_flags: ptr::null_mut(),
+            eb_coverage: ptr::null_mut(),
+        };
+        let mut total: u64 = 0;
+        let rc = unsafe {
+            sys::hspf_routes_backup_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, 0, &mut out, &mut total)
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let cap = total as usize;
+        let mut res = BackupEcmp {
+            n_protected: np as u32,
+            n_prefixes: table.n_prefixes(),
+            eb_ptr: Vec::new(),
+            eb_primary: Vec::new(),
+            eb_kind: Vec::new(),
+            eb_slot: Vec::new(),
+            eb_metric: Vec::new(),
+            eb_flags: Vec::new(),
+            eb_coverage: vec![0; np * cov_words],
+        };
+        if cap == 0 {
+            res.eb_ptr = eb_ptr.to_host(np * pf + 1)?;
+            return Ok(res);
+        }
+        let primary = self.device_alloc(cap * 4)?;
+        let kind = self.device_alloc(cap)?;
+        let slot = self.device_alloc(cap * 4)?;
+        let metric = self.device_alloc(cap * 4)?;
+        let flags = self.device_alloc(cap)?;
+        let cov = self.device_alloc(np * cov_words * 4)?;
+        out.eb_primary = primary.p as *mut u32;
+        out.eb_kind = kind.p as *mut u8;
+        out.eb_slot = slot.p as *mut u32;
+        out.eb_metric = metric.p as *mut u32;
+        out.eb_flags = flags.p as *mut u8;
+        out.eb_coverage = cov.p as *mut u32;
+        t.flags |= sys::HSPF_PFX_RESIDENT; // the sizing call has just staged the table
+        let rc = unsafe {
+            sys::hspf_routes_backup_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, total, &mut out, &mut total)
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        res.eb_ptr = eb_ptr.to_host(np * pf + 1)?;
+        res.eb_primary = primary.to_host(cap)?;
+        res.eb_kind = kind.to_host(cap)?;
+        res.eb_slot = slot.to_host(cap)?;
+        res.eb_metric = metric.to_host(cap)?;
+        res.eb_flags = flags.to_host(cap)?;
+        res.eb_coverage = cov.to_host(np * cov_words)?;
+        Ok(res)
     }
 
     /// `hspf_routes_backup_srlg_device`: `routes_backup_device` whose alternates neither start on nor cross, on their way to the
