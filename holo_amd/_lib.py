@@ -256,6 +256,11 @@ SYMBOLS = [
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.POINTER(HspfSrlg),
                                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes),
                                                       ctypes.POINTER(HspfTilfaOut), ctypes.POINTER(HspfBackupOut)]),
+    # per-primary SRLG-safe backups of ECMP prefixes
+    ("hspf_routes_backup_ecmp_srlg_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.POINTER(HspfSrlg),
+                                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfPrefixTable), ctypes.POINTER(HspfRoutes),
+                                                           ctypes.POINTER(HspfTilfaOut), ctypes.c_uint64, ctypes.POINTER(HspfBackupEcmpOut), u64p]),
     # two-segment repair paths (TI-LFA, link protection)
     ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,

@@ -27,6 +27,16 @@
 //                         barrier comes from LDS or the arguments: uniform across the workgroup; there is no return in front of one.
 //                         ONE shape: the staged columns and scalars are read through the caches (the K <= 64 copy in LDS of
 //                         k_lfa_ecmp_fill<true> was not built: the LDS goes to the d_N(p) batch).
+// Modes (FrrProt, spf_frr_common.hip.h).  The fill step is ONE body, backup_ecmp_fill_body<P>, in two modes: Plain is
+// k_backup_ecmp_fill as it was; Srlg (hspf_routes_backup_ecmp_srlg_device) is k_backup_ecmp_fill_srlg.  The batch and the walk are
+// the same text; BackupEcmpLane<Srlg> adds what depends on the ENTRY (p, h) alone: the members of slot h — of h, not of all of P —
+// and d_{b_i}(p) of those at most 16 members, computed ONCE per entry in front of the candidate chunks, in k_backup_srlg's two
+// streams of the prefix's entries (members 0 .. 7, 8 .. 15), packed to 33 bits in registers (bks_get / bks_set).  A candidate reads
+// loc, d(N_k, a_i) and w_i of k_srlg_gather's block only after it has passed every plain condition; an entry whose h has no
+// members reads sptr[h], sptr[h + 1] and nothing else of the member block, and streams no advertiser row more than Plain does.
+// Registers, not LDS: next to the d_N(p) batch 256 entries x 16 members x 33 bits would be 17 KB more (37 KB: four workgroups per
+// CU where the registers allow more), the values are private to the lane that made them, and the resource report shows the
+// register form without scratch (profiles/r28_notes.md).  Coverage has three more per-entry words in the mode Srlg.
 // Coverage: the six per-ENTRY counters are summed over a lane's entries with wave ballots into lane j's register, one LDS add per
 // wave; the two per-PREFIX counters are flag bits of lane = p; frr_cover adds those and issues the one atomic per workgroup and
 // counter for all eight.
@@ -36,10 +46,13 @@
 #include <stdint.h>
 
 #include "spf_backup.hip.h"
+#include "spf_backup_srlg.hip.h"
 
 namespace {
 
 constexpr uint32_t EB_CW = 8;                // HSPF_BK_ECMP_COVERAGE_WORDS
+constexpr uint32_t EBS_CW = 11;              // HSPF_BK_ECMP_SRLG_COVERAGE_WORDS
+constexpr uint32_t be_cov_words(FrrProt P) { return P == FrrProt::Srlg ? EBS_CW : EB_CW; }
 constexpr uint32_t BE_SLOTS = 2048;          // d_N(p) values of one batch in LDS (16 KB)
 constexpr uint64_t BE_OWN = 1ull << 62;      // next to a d_N(p) (< 2^33) in LDS: N's own entry attains it
 constexpr uint64_t BE_VAL = (1ull << 40) - 1ull;
@@ -50,6 +63,73 @@ struct BackupEcmpArgs {
   unsigned long long cap;
   uint32_t *tile;                            // [n_prot * tiles_x] tile totals, then offsets | the total
   uint32_t *eb_ptr, *eb_primary; uint8_t *eb_kind; uint32_t *eb_slot, *eb_metric; uint8_t *eb_flags; uint32_t *eb_coverage;
+};
+
+// the fill body's modes (spf_frr_common.hip.h: <Family>Prot<P>, <Family>Lane<P>)
+template <FrrProt P> struct BackupEcmpProt {};
+template <> struct BackupEcmpProt<FrrProt::Srlg> { BackupSrlgArgs s; };
+template <FrrProt P> struct BackupEcmpLane {};
+template <> struct BackupEcmpLane<FrrProt::Srlg> {
+  SrlgTab st;
+  uint32_t s0 = 0, nm = 0;                                               // the members of the entry's h in sidx
+  uint32_t dbl[SRLG_MAXM], dbh = 0xFFFFu;                                // their d_{b_i}(p) (bks_get / bks_set)
+  uint32_t sfl = 0;                                                      // HSPF_BK_SRLG_PRIMARY | _PAIR_REFUSED | HSPF_LFA_SRLG_REFUSED
+
+  __device__ __forceinline__ void open(const BackupEcmpProt<FrrProt::Srlg> &pa, uint32_t pi, uint32_t K) { st = srlg_tab(pa.s.sa, pi, K); }
+  // a new entry (p, h): the members of h and their d_b(p), the prefix's entries lo .. hi streamed once per BKS_MCH members
+  __device__ __forceinline__ void entry(const BackupArgs &a, bool live, uint32_t h, uint32_t lo, uint32_t hi) {
+    s0 = 0; nm = 0; sfl = 0; dbh = 0xFFFFu;
+#pragma unroll
+    for (uint32_t j = 0; j < SRLG_MAXM; ++j) dbl[j] = 0xFFFFFFFFu;
+    if (!live) return;
+    s0 = st.sptr[h];
+    nm = st.sptr[h + 1] - s0;                                            // (at most SRLG_MAXM: the call checked it; every loop over dbl ends at SRLG_MAXM by itself)
+    if (!nm) return;
+    sfl = 0x01u;
+#pragma unroll
+    for (uint32_t m0 = 0; m0 < SRLG_MAXM; m0 += BKS_MCH) {               // (one stream unless h has more than BKS_MCH members)
+      if (m0 >= nm) break;
+      uint32_t hrow[BKS_MCH];
+#pragma unroll
+      for (uint32_t j = 0; j < BKS_MCH; ++j) hrow[j] = m0 + j < nm ? st.hrow[st.sidx[s0 + m0 + j]] : 0u;
+      for (uint32_t e = lo; e < hi; ++e) {
+        const uint32_t v = a.pfx_vertex[e], met = a.pfx_metric[e];
+#pragma unroll
+        for (uint32_t j = 0; j < BKS_MCH; ++j) {
+          if (m0 + j >= nm) break;
+          const uint64_t t = bk_term(a, (size_t)hrow[j] * a.n + v, met);   // (BK_NO_DIST is above every packed value)
+          if (t < bks_get(dbl, dbh, m0 + j)) bks_set(dbl, dbh, m0 + j, t);
+        }
+      }
+    }
+  }
+  // candidate k (root_link rlk, d_{N_k}(p) = d), which has passed every plain condition: no member of h is local to k, none is crossed
+  __device__ __forceinline__ bool safe(uint32_t k, uint32_t rlk, uint64_t d) const {
+    bool ok = true;
+    // (two loops of BKS_MCH: the compiler unrolls a loop with an early exit completely only up to eight iterations, and a loop it
+    // unrolls by a run-time count indexes dbl dynamically — the lane's state would move to scratch, profiles/r25_notes.md)
+#pragma unroll
+    for (uint32_t m0 = 0; m0 < SRLG_MAXM; m0 += BKS_MCH) {
+      if (m0 >= nm) break;
+#pragma unroll
+      for (uint32_t j = 0; j < BKS_MCH; ++j) {
+        if (m0 + j >= nm) break;
+        const uint32_t i = st.sidx[s0 + m0 + j];
+        ok = ok && st.loc[i] != rlk && !bks_cross(d, st.dNa[(size_t)k * st.NM + i], st.cost[i], bks_get(dbl, dbh, m0 + j));
+      }
+    }
+    return ok;
+  }
+  // is the forced adjacency (tp, tl) of h's two-segment repair a member of h?
+  __device__ __forceinline__ bool forced(uint32_t tp, uint32_t tl) const {
+    const uint32_t *pos = srlg_pos(st);
+    bool f = false;
+    for (uint32_t i2 = 0; i2 < nm; ++i2) {
+      const uint32_t i = st.sidx[s0 + i2];
+      f = f || (st.tail[i] == tp && pos[i] == tl);
+    }
+    return f;
+  }
 };
 
 __global__ __launch_bounds__(256) void k_backup_ecmp_count(BackupEcmpArgs a) {
@@ -69,9 +149,12 @@ __global__ __launch_bounds__(256) void k_backup_ecmp_count(BackupEcmpArgs a) {
   if (tid == 0) a.tile[(size_t)pi * gridDim.x + blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) {
+template <FrrProt P>
+__device__ __forceinline__ void backup_ecmp_fill_body(const BackupEcmpArgs &a, const BackupEcmpProt<P> &pa) {
+  constexpr bool SRLG = P == FrrProt::Srlg;
+  constexpr uint32_t CW = be_cov_words(P);
   __shared__ uint64_t s_d[BE_SLOTS];                                     // [prefix of the batch][candidate of the chunk]
-  __shared__ uint32_t s_cov[EB_CW];
+  __shared__ uint32_t s_cov[CW];
   __shared__ uint32_t s_ptr[LFA_TILE + 1];                               // the tile's eb_ptr values, from 0
   __shared__ uint32_t s_scan[GB_BLOCK];
   __shared__ uint16_t s_rank[LFA_TILE];                                  // prefix of the tile -> its place among the tile's ECMP prefixes
@@ -80,8 +163,10 @@ __global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, pi = blockIdx.y;
   const FrrTab tb = frr_tab(a.b.tab, a.b.scal, pi);
   const uint32_t K = tb.K, C = tb.C, W = a.b.W, n_pfx = a.b.n_pfx;
-  if (tid < EB_CW) s_cov[tid] = 0;
+  if (tid < CW) s_cov[tid] = 0;
   s_miss[tid] = 0;
+  BackupEcmpLane<P> ln;
+  if constexpr (SRLG) ln.open(pa, pi, K);
   // the scans inside the tile: counts -> eb_ptr, ECMP bits -> the list
   const uint32_t p_first = blockIdx.x * LFA_TILE;
   const bool valid = p_first + tid < n_pfx;
@@ -106,7 +191,7 @@ __global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) {
   const uint32_t CC = C < BE_SLOTS ? C : BE_SLOTS;                       // candidates per chunk
   const uint32_t B = C ? (BE_SLOTS / CC) : LFA_TILE;                     // prefixes per batch (C == 0: nothing is kept in LDS)
   const bool one_chunk = C <= BE_SLOTS;
-  uint32_t my_cov = 0;                                                   // lane j, 1 <= j <= 6, of a wave: its count of entry bit j
+  uint32_t my_cov = 0;                                                   // lane j, 1 <= j <= 6 (Srlg: and 8 <= j <= 10), of a wave: its count of entry bit j
   for (uint32_t b0 = 0; b0 < todo; b0 += B) {
     const uint32_t nb = todo - b0 < B ? todo - b0 : B;
     const uint32_t e_lo = s_ptr[s_list[b0]], e_hi = s_ptr[s_list[b0 + nb - 1u] + 1u];   // the batch's entries: one range
@@ -143,6 +228,7 @@ __global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) {
         rlh = tb.rl[h]; E = tb.nbr[h];
         if (E != LFA_NONE && !one_chunk) dEp = bk_dist_to_prefix(a.b, tb.row[h], lo, hi);
       }
+      if constexpr (SRLG) ln.entry(a.b, live, h, lo, hi);                // (no barrier inside)
       bool have = false, bnode = false, bprim = false, bdown = false;
       uint64_t bsum = 0;
       uint32_t bslot = LFA_NONE;
@@ -177,6 +263,9 @@ __global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) {
           if (!bk_less(d, tb.dns[k], dSp)) continue;                     // loop-free towards the prefix: ONE rule, a primary or not
           if ((tb.cf[k] & 1u) && !a.b.ignore_overload && !(raw & BE_OWN)) continue;
           if (tb.rl[k] == rlh) continue;                                 // shares the first link's fate
+          if constexpr (SRLG) {                                          // every plain condition holds: now the group of h
+            if (ln.nm && !ln.safe(k, tb.rl[k], d)) { ln.sfl |= 0x80u; continue; }
+          }
           const bool nd = dEp != BK_NO_DIST && bk_less(d, tb.m[k * K + h], dEp);
           const bool pr = (pm[k >> 6] >> (k & 63u)) & 1ull;
           const uint64_t sum = (uint64_t)tb.cost[k] + d;
@@ -195,25 +284,45 @@ __global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) {
         } else if (a.b.ti_kind) {
           const size_t o = (size_t)pi * a.b.stride + h;
           const uint32_t tk = a.b.ti_kind[o];
-          if (tk) { kind = tk == 1u ? 4u : 5u; slot = a.b.ti_via[o]; met = a.b.ti_metric[o]; }
+          bool take = tk != 0;
+          if constexpr (SRLG) {
+            if (ln.nm) {                                                 // h has members: only repairs the caller vouches for
+              take = take && pa.s.repairs;
+              if (take && tk == 2u && ln.forced(pa.s.ti_p[o], pa.s.ti_link[o])) { take = false; ln.sfl |= 0x02u; }
+            }
+          }
+          if (take) { kind = tk == 1u ? 4u : 5u; slot = a.b.ti_via[o]; met = a.b.ti_metric[o]; }
         }
+        if constexpr (SRLG) fl |= ln.sfl;
         const size_t g = (size_t)base + e;                               // < total <= cap
         a.eb_primary[g] = h; a.eb_kind[g] = (uint8_t)kind; a.eb_slot[g] = slot; a.eb_metric[g] = met; a.eb_flags[g] = (uint8_t)fl;
         if (kind == 6u) s_miss[pl] = 1;
         // entry | _LFA | node | downstream | a primary | repaired
         cv = 0x02u | (kind == 3u ? 0x04u : 0u) | (fl & 0x08u) | (fl & 0x10u) | (fl & 0x20u) | ((kind == 4u || kind == 5u) ? 0x40u : 0u);
+        // Srlg: the primary has members | a slot was refused for them | the pair was refused
+        if constexpr (SRLG) cv |= ((fl & 0x01u) << 8) | ((fl & 0x80u) << 2) | ((fl & 0x02u) << 9);
       }
 #pragma unroll
       for (uint32_t j = 1; j <= 6; ++j) {
         const uint32_t c = (uint32_t)__popcll(__ballot((cv >> j) & 1u));
         if (lane == j) my_cov += c;
       }
+      if constexpr (SRLG) {
+#pragma unroll
+        for (uint32_t j = EB_CW; j < CW; ++j) {
+          const uint32_t c = (uint32_t)__popcll(__ballot((cv >> j) & 1u));
+          if (lane == j) my_cov += c;
+        }
+      }
     }
   }
-  if (my_cov) atomicAdd(&s_cov[lane], my_cov);                           // (only lanes 1 .. 6 hold a count)
+  if (my_cov) atomicAdd(&s_cov[lane], my_cov);                           // (only lanes 1 .. 6, Srlg: and 8 .. 10, hold a count)
   __syncthreads();                                                       // s_miss is complete
   const uint32_t dfl = (fill && cnt) ? 0x01u | (s_miss[tid] ? 0u : 0x80u) : 0u;   // ECMP prefix | every primary has a backup
-  frr_cover<EB_CW>(dfl, s_cov, a.eb_coverage + (size_t)pi * EB_CW);
+  frr_cover<CW>(dfl, s_cov, a.eb_coverage + (size_t)pi * CW);
 }
+
+__global__ __launch_bounds__(256) void k_backup_ecmp_fill(BackupEcmpArgs a) { backup_ecmp_fill_body<FrrProt::Plain>(a, BackupEcmpProt<FrrProt::Plain>{}); }
+__global__ __launch_bounds__(256) void k_backup_ecmp_fill_srlg(BackupEcmpArgs a, BackupEcmpProt<FrrProt::Srlg> pa) { backup_ecmp_fill_body<FrrProt::Srlg>(a, pa); }
 
 }  // namespace

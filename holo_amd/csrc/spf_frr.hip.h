@@ -519,14 +519,15 @@ int lfa_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n
   });
 }
 
-static_assert(EB_CW == HSPF_BK_ECMP_COVERAGE_WORDS, "the fill kernel's coverage width is the header's");
+static_assert(be_cov_words(FrrProt::Plain) == HSPF_BK_ECMP_COVERAGE_WORDS && be_cov_words(FrrProt::Srlg) == HSPF_BK_ECMP_SRLG_COVERAGE_WORDS,
+              "the fill kernel's coverage widths are the header's");
 
-// The frame of hspf_routes_backup_ecmp_device (kernels: spf_backup_ecmp.hip.h): the checks and the staging of routes_backup in its
-// plain mode, then count -> scan -> fill on the context's stream and ONE synchronisation, as lfa_ecmp_call (the same scratch and
-// the same pinned word).
-int backup_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+// The one frame of hspf_routes_backup_ecmp_device and hspf_routes_backup_ecmp_srlg_device (kernels: spf_backup_ecmp.hip.h; `srlg`
+// is read in the mode Srlg alone): the checks and the staging of routes_backup in the same mode, then count -> scan -> fill on the
+// context's stream and ONE synchronisation, as lfa_ecmp_call (the same scratch and the same pinned word).
+int backup_ecmp_call(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
-                     const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
+                     const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
                      const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, uint64_t cap_entries, hspf_backup_ecmp_out *out_dev,
                      uint64_t *out_total) {
   if (!ctx) return HSPF_E_INVAL;
@@ -534,10 +535,12 @@ int backup_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_
     auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
     if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
     if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    const bool with_srlg = mode == FrrProt::Srlg;
     if (!out_dev->eb_ptr || !out_total) return bad("NULL eb_ptr or out_total");
     if (cap_entries && (!out_dev->eb_primary || !out_dev->eb_kind || !out_dev->eb_slot || !out_dev->eb_metric || !out_dev->eb_flags || !out_dev->eb_coverage))
       return bad("NULL eb_primary / eb_kind / eb_slot / eb_metric / eb_flags / eb_coverage with cap_entries > 0");
-    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric)) return bad("NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric || (with_srlg && (!tilfa_dev->ti_p || !tilfa_dev->ti_link))))
+      return bad(with_srlg ? "NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev" : "NULL ti_kind / ti_via / ti_metric in tilfa_dev");
     int rc;
     if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
     if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
@@ -546,6 +549,7 @@ int backup_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_
     uint64_t pairs = 0;                                 // an upper bound of the entries: eb_ptr is u32, the scan's carry too
     for (uint32_t i = 0; i < n_prot; ++i) pairs += (uint64_t)t->n_prefixes * std::max(prot[i].n_slots, 1u);
     if (pairs >= (1ull << 32)) return bad("n_prefixes * max(n_slots, 1), summed over the protected roots, reaches 2^32: split the protect list");
+    if (with_srlg && (rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
     if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
     (void)hipSetDevice(ctx->device);
     const uint32_t tiles_x = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
@@ -554,14 +558,18 @@ int backup_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_
     if (!ctx->h_ev) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ev, 64, hipHostMallocDefault));
     uint32_t *d_hev = nullptr;
     HIPCHK(ctx, hipHostGetDevicePointer((void **)&d_hev, ctx->h_ev, 0));
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
+    std::vector<uint32_t> tab, mtab;                    // (live until the synchronisation at the end: the copies read them)
+    uint32_t max_k = 0, max_nms = 0;
+    size_t max_gather = 0;
+    SrlgArgs sa{};
     hipStream_t s = ctx->stream;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) {
+    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
+        (with_srlg && (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms)))) {
       (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
       return rc;
     }
-    if (out_dev->eb_coverage) HIPCHK(ctx, hipMemsetAsync(out_dev->eb_coverage, 0, (size_t)n_prot * HSPF_BK_ECMP_COVERAGE_WORDS * 4, s));
+    const uint32_t coverage_words = with_srlg ? HSPF_BK_ECMP_SRLG_COVERAGE_WORDS : HSPF_BK_ECMP_COVERAGE_WORDS;
+    if (out_dev->eb_coverage) HIPCHK(ctx, hipMemsetAsync(out_dev->eb_coverage, 0, (size_t)n_prot * coverage_words * 4, s));
     if (!t->n_prefixes) {                               // nothing to launch: the one word of eb_ptr
       HIPCHK(ctx, hipMemsetAsync(out_dev->eb_ptr, 0, 4, s));
       HIPCHK(ctx, hipStreamSynchronize(s));
@@ -569,6 +577,7 @@ int backup_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_
       return HSPF_OK;
     }
     const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    if (with_srlg) srlg_gather(ctx, ga, sa, n_prot, max_gather);
     BackupEcmpArgs a{};
     a.b.n = n_vertices; a.b.W = n_mask_words; a.b.ignore_overload = ga.ignore_overload; a.b.stride = 64u * n_mask_words;
     a.b.n_pfx = t->n_prefixes; a.b.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
@@ -576,15 +585,21 @@ int backup_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_
     a.b.tab = ga.tab; a.b.scal = ga.scal;
     a.b.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.b.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.b.pfx_metric = (const uint32_t *)ctx->pf_met.p;
     a.b.best_metric = routes_dev->best_metric; a.b.best_entry = routes_dev->best_entry; a.b.nh_mask = routes_dev->nexthop_mask;
-    if (tilfa_dev) { a.b.ti_kind = tilfa_dev->ti_kind; a.b.ti_via = tilfa_dev->ti_via; a.b.ti_metric = tilfa_dev->ti_metric; }
+    BackupEcmpProt<FrrProt::Srlg> pa{};
+    pa.s.sa = sa; pa.s.repairs = (lfa_flags & HSPF_LFA_SRLG_SAFE_REPAIRS) ? 1u : 0u;
+    if (tilfa_dev) {
+      a.b.ti_kind = tilfa_dev->ti_kind; a.b.ti_via = tilfa_dev->ti_via; a.b.ti_metric = tilfa_dev->ti_metric;
+      pa.s.ti_p = tilfa_dev->ti_p; pa.s.ti_link = tilfa_dev->ti_link;
+    }
     a.n_prot = n_prot; a.cap = cap_entries; a.tile = (uint32_t *)ctx->ea_scr.p;
     a.eb_ptr = out_dev->eb_ptr; a.eb_primary = out_dev->eb_primary; a.eb_kind = out_dev->eb_kind; a.eb_slot = out_dev->eb_slot;
     a.eb_metric = out_dev->eb_metric; a.eb_flags = out_dev->eb_flags; a.eb_coverage = out_dev->eb_coverage;
     const dim3 grid(tiles_x, n_prot);
     hipLaunchKernelGGL(k_backup_ecmp_count, grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(1024), 0, s, (uint32_t)n_tiles, a.tile, a.tile + n_tiles, d_hev + 1);
-    hipLaunchKernelGGL(k_backup_ecmp_fill, grid, dim3(256), 0, s, a);
-    if ((rc = frr_finish(ctx, "k_backup_ecmp"))) return rc;
+    if (with_srlg) hipLaunchKernelGGL(k_backup_ecmp_fill_srlg, grid, dim3(256), 0, s, a, pa);
+    else hipLaunchKernelGGL(k_backup_ecmp_fill, grid, dim3(256), 0, s, a);
+    if ((rc = frr_finish(ctx, with_srlg ? "k_backup_ecmp_srlg" : "k_backup_ecmp"))) return rc;
     *out_total = ctx->h_ev[1];
     return HSPF_OK;
   });
@@ -876,6 +891,16 @@ int hspf_routes_backup_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
                        srlg, n_prot, lfa_flags, table, routes_dev, tilfa_dev, out_dev);
 }
 
+// ---- per-primary SRLG-safe backups of ECMP prefixes (include/holo_spf_hip.h "per-primary SRLG-safe backups for ECMP prefixes"; kernels: spf_backup_ecmp.hip.h) ----
+int hspf_routes_backup_ecmp_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                        const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                        const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                                        const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                        uint64_t cap_entries, hspf_backup_ecmp_out *out_dev, uint64_t *out_total) {
+  return backup_ecmp_call(ctx, "hspf_routes_backup_ecmp_srlg_device", FrrProt::Srlg, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, srlg,
+                          n_prot, lfa_flags, table, routes_dev, tilfa_dev, cap_entries, out_dev, out_total);
+}
+
 // ---- two-segment repair paths (include/holo_spf_hip.h "two-segment repair paths on device"; kernels: spf_tilfa.hip.h) ----
 int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                       const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
@@ -939,7 +964,7 @@ int hspf_routes_backup_ecmp_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
                                    const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *table,
                                    const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, uint64_t cap_entries,
                                    hspf_backup_ecmp_out *out_dev, uint64_t *out_total) {
-  return backup_ecmp_call(ctx, "hspf_routes_backup_ecmp_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot,
+  return backup_ecmp_call(ctx, "hspf_routes_backup_ecmp_device", FrrProt::Plain, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, nullptr, n_prot,
                           lfa_flags, table, routes_dev, tilfa_dev, cap_entries, out_dev, out_total);
 }
 

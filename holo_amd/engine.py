@@ -44,6 +44,7 @@ LFA_COVERAGE_WORDS = 5
 LFA_EA_PRIMARY = 0x20           # HSPF_LFA_EA_PRIMARY: ea_flags of lfa_ecmp_device(), the alternate is another primary
 LFA_ECMP_COVERAGE_WORDS = 7
 BK_ECMP_COVERAGE_WORDS = 8      # HSPF_BK_ECMP_COVERAGE_WORDS: eb_coverage of routes_backup_ecmp_device()
+BK_ECMP_SRLG_COVERAGE_WORDS = 11  # HSPF_BK_ECMP_SRLG_COVERAGE_WORDS: eb_coverage of routes_backup_ecmp_srlg_device()
 LFA_LAN_PRIMARY, LFA_LAN_REFUSED = 0x20, 0x40     # HSPF_LFA_LAN_*: alt_flags / bk_flags of the LAN calls
 LFA_LAN_COVERAGE_WORDS = 7
 LFA_LAN_SAFE_REPAIRS = 0x02     # HSPF_LFA_LAN_SAFE_REPAIRS (routes_backup_lan_device flags): tilfa comes from rlfa_lan_device()'s tables
@@ -1351,7 +1352,34 @@ class SpfContext:
         `cap_entries` elements each (0 with cap_entries == 0: eb_ptr and the total alone), eb_coverage_ptr
         [P, BK_ECMP_COVERAGE_WORDS] u32.  Returns the total number of entries; when it exceeds cap_entries only eb_ptr was
         written and the call is to be repeated with larger arrays."""
-        name = "routes_backup_ecmp_device"
+        return self._routes_backup_ecmp(None, n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr, protect, pfx_ptr, pfx_vertex, pfx_metric,
+                                        routes=routes, eb_ptr_ptr=eb_ptr_ptr, cap_entries=cap_entries, eb_primary_ptr=eb_primary_ptr, eb_kind_ptr=eb_kind_ptr,
+                                        eb_slot_ptr=eb_slot_ptr, eb_metric_ptr=eb_metric_ptr, eb_flags_ptr=eb_flags_ptr, eb_coverage_ptr=eb_coverage_ptr,
+                                        tilfa=tilfa, flags=flags, lfa_flags=lfa_flags, pfx_origin=pfx_origin)
+
+    def routes_backup_ecmp_srlg_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
+                                       srlgs, pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, eb_ptr_ptr: int, cap_entries: int = 0, eb_primary_ptr: int = 0,
+                                       eb_kind_ptr: int = 0, eb_slot_ptr: int = 0, eb_metric_ptr: int = 0, eb_flags_ptr: int = 0, eb_coverage_ptr: int = 0,
+                                       tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> int:
+        """hspf_routes_backup_ecmp_srlg_device(): routes_backup_ecmp_device() whose alternate for a primary h neither starts on nor
+        crosses, on its way to the PREFIX, a link that shares a risk group with h's own first link — the members of h alone count,
+        and another primary in h's group is refused as h's backup.  `srlgs` as for lfa_srlg_device(); the table set holds [root] +
+        neighbour routers + member endpoints.  tilfa = (ti_kind_ptr, ti_via_ptr, ti_metric_ptr, ti_p_ptr, ti_link_ptr), or None; a
+        primary with members takes its per-link repair only under lfa_flags LFA_SRLG_SAFE_REPAIRS, and a pair whose forced link is a
+        member is refused (BK_SRLG_PAIR_REFUSED).  eb_flags carries BK_SRLG_PRIMARY / LFA_SRLG_REFUSED / BK_SRLG_PAIR_REFUSED on an
+        entry of any kind; eb_coverage_ptr: [P, BK_ECMP_SRLG_COVERAGE_WORDS] u32.  Every other argument, the return value and the
+        capacity convention as for routes_backup_ecmp_device()."""
+        return self._routes_backup_ecmp(list(srlgs), n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr, protect, pfx_ptr, pfx_vertex,
+                                        pfx_metric, routes=routes, eb_ptr_ptr=eb_ptr_ptr, cap_entries=cap_entries, eb_primary_ptr=eb_primary_ptr, eb_kind_ptr=eb_kind_ptr,
+                                        eb_slot_ptr=eb_slot_ptr, eb_metric_ptr=eb_metric_ptr, eb_flags_ptr=eb_flags_ptr, eb_coverage_ptr=eb_coverage_ptr,
+                                        tilfa=tilfa, flags=flags, lfa_flags=lfa_flags, pfx_origin=pfx_origin)
+
+    def _routes_backup_ecmp(self, srlgs, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
+                            pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, eb_ptr_ptr: int, cap_entries: int = 0, eb_primary_ptr: int = 0,
+                            eb_kind_ptr: int = 0, eb_slot_ptr: int = 0, eb_metric_ptr: int = 0, eb_flags_ptr: int = 0, eb_coverage_ptr: int = 0,
+                            tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> int:
+        """The body of routes_backup_ecmp_device() (srlgs None) and routes_backup_ecmp_srlg_device()."""
+        name = "routes_backup_ecmp_device" if srlgs is None else "routes_backup_ecmp_srlg_device"
         src = (pfx_ptr, pfx_vertex, pfx_metric)
         pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
         pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
@@ -1360,40 +1388,49 @@ class SpfContext:
             raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
         org = None if pfx_origin is None else np.ascontiguousarray(pfx_origin, np.uint32)
         arr, keep = self._protect_array(protect, name)
+        sarr, skeep = (None, None) if srlgs is None else self._srlg_array(srlgs, protect, name)
         t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags,
                               None if org is None else _u32(org), None, None, None)
         r = L.HspfRoutes(*(x or None for x in routes))
         ti = None
-        if tilfa is not None:
+        if tilfa is not None and srlgs is None:
             ti = L.HspfTilfaOut(tilfa[0] or None, None, None, tilfa[1] or None, None, tilfa[2] or None, None, None, None)
+        elif tilfa is not None:
+            ti = L.HspfTilfaOut(tilfa[0] or None, tilfa[3] or None, None, tilfa[1] or None, tilfa[4] or None, tilfa[2] or None, None, None, None)
         out = L.HspfBackupEcmpOut(eb_ptr_ptr or None, eb_primary_ptr or None, eb_kind_ptr or None, eb_slot_ptr or None, eb_metric_ptr or None,
                                   eb_flags_ptr or None, eb_coverage_ptr or None)
         total = ctypes.c_uint64()
-        rc = self.lib.hspf_routes_backup_ecmp_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
-                                                     mask_ptr or None, arr, len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r),
-                                                     None if ti is None else ctypes.byref(ti), cap_entries, ctypes.byref(out), ctypes.byref(total))
-        del keep
+        head = (self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None, arr)
+        tail = (len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r), None if ti is None else ctypes.byref(ti), cap_entries, ctypes.byref(out),
+                ctypes.byref(total))
+        if srlgs is None:
+            rc = self.lib.hspf_routes_backup_ecmp_device(*head, *tail)
+        else:
+            rc = self.lib.hspf_routes_backup_ecmp_srlg_device(*head, sarr, *tail)
+        del keep, skeep
         self._check_rc("hspf_" + name, rc)
         return int(total.value)
 
-    def _backup_ecmp_tail(self, n: int, R: int, W: int, dev: dict, protect, backup, tilfa: bool, lfa_flags: int) -> BackupEcmpResult:
+    def _backup_ecmp_tail(self, n: int, R: int, W: int, dev: dict, protect, backup, tilfa: bool, lfa_flags: int, srlgs=None) -> BackupEcmpResult:
         """backup_routes(ecmp=True) behind routes_backup_device(), while the tables, the routes and the repairs are on the device: the
-        sizing call, then the filling call with arrays of that size."""
+        sizing call, then the filling call with arrays of that size.  srlgs (backup_routes(ecmp=True, srlg=...), behind
+        routes_backup_srlg_device()): routes_backup_ecmp_srlg_device() with these members; eb_coverage has eleven words."""
         NP = len(backup[0]) - 1
         ptr = np.empty(NP + 1, np.uint32)
-        cov = np.zeros((1, BK_ECMP_COVERAGE_WORDS), np.uint32)
+        cov = np.zeros((1, BK_ECMP_COVERAGE_WORDS if srlgs is None else BK_ECMP_SRLG_COVERAGE_WORDS), np.uint32)
+        ti_names = ("ti_kind", "ti_via", "ti_metric") + (() if srlgs is None else ("ti_p", "ti_link"))
         kw = dict(routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
-                  tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None, flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags)
-        tables = (n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, backup[0], backup[1], backup[2])
+                  tilfa=tuple(dev[k] for k in ti_names) if tilfa else None, flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags)
+        tables = (srlgs, n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, backup[0], backup[1], backup[2])
         with self._dev_buffers(dict(ptr=ptr.nbytes)) as pd:
-            total = self.routes_backup_ecmp_device(*tables, eb_ptr_ptr=pd["ptr"], **kw)
+            total = self._routes_backup_ecmp(*tables, eb_ptr_ptr=pd["ptr"], **kw)
             host = dict(primary=np.empty(total, np.uint32), kind=np.empty(total, np.uint8), slot=np.empty(total, np.uint32),
                         metric=np.empty(total, np.uint32), eflags=np.empty(total, np.uint8))
             if total:
                 with self._dev_buffers(dict({k: a.nbytes for k, a in host.items()}, cov=cov.nbytes)) as ent:
-                    self.routes_backup_ecmp_device(*tables, eb_ptr_ptr=pd["ptr"], cap_entries=total, eb_primary_ptr=ent["primary"],
-                                                   eb_kind_ptr=ent["kind"], eb_slot_ptr=ent["slot"], eb_metric_ptr=ent["metric"],
-                                                   eb_flags_ptr=ent["eflags"], eb_coverage_ptr=ent["cov"], **kw)
+                    self._routes_backup_ecmp(*tables, eb_ptr_ptr=pd["ptr"], cap_entries=total, eb_primary_ptr=ent["primary"],
+                                             eb_kind_ptr=ent["kind"], eb_slot_ptr=ent["slot"], eb_metric_ptr=ent["metric"],
+                                             eb_flags_ptr=ent["eflags"], eb_coverage_ptr=ent["cov"], **kw)
                     self._fetch(dict(host, cov=cov), ent)
             self._fetch(dict(ptr=ptr), pd)
         return BackupEcmpResult(ptr, host["primary"], host["kind"], host["slot"], host["metric"], host["eflags"], cov, n_prefixes=NP)
@@ -1472,9 +1509,10 @@ class SpfContext:
         self._check_rc("hspf_" + name, rc)
 
     def _backup_srlg(self, graph: SpfGraph, root: int, tab, grp_ptr, grp, run_flags: int, lfa_flags: int, symmetric: bool, remote: bool,
-                     srlg_repairs: bool) -> BackupRoutes:
+                     srlg_repairs: bool, ecmp: bool = False) -> BackupRoutes:
         """backup_routes(srlg=...): on a run that also holds the member endpoints' rows, _srlg_chain() with `remote` (only the
-        per-slot repairs come to the host), then routes_device() and routes_backup_srlg_device()."""
+        per-slot repairs come to the host), then routes_device() and routes_backup_srlg_device(); with `ecmp`, _backup_ecmp_tail()
+        with the members on the same rows."""
         plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
         cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
         R, n, NP = len(roots), graph.n, len(tab[0]) - 1
@@ -1503,8 +1541,12 @@ class SpfContext:
                                            tilfa=tuple(dev[k] for k in ("ti_kind", "ti_via", "ti_metric", "ti_p", "ti_link")) if remote else None,
                                            flags=tab[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_SRLG_SAFE_REPAIRS if srlg_repairs else 0),
                                            **{k + "_ptr": dev[k] for k in bk_names[3:]})
+            eb = None
+            if ecmp:
+                eb = self._backup_ecmp_tail(n, R, W, dev, protect, tab, remote, lfa_flags | (LFA_SRLG_SAFE_REPAIRS if srlg_repairs else 0), srlgs=[mem])
             self._fetch(host, dev)
-        return BackupRoutes(cand, *(host[k] for k in bk_names), tilfa=TilfaResult(*(host[k] for k in self._TI_NAMES)) if remote else None, srlg=mem)
+        return BackupRoutes(cand, *(host[k] for k in bk_names), tilfa=TilfaResult(*(host[k] for k in self._TI_NAMES)) if remote else None, srlg=mem,
+                            ecmp=eb)
 
     def routes_backup_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                                   pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, ydist_ptr: int, y_roots, bn_kind_ptr: int, bn_primary_ptr: int,
@@ -1594,11 +1636,13 @@ class SpfContext:
         plain calls' places, and routes_backup_srlg_device() writes the backups (bk_coverage has ten words, BackupRoutes.srlg holds
         the members).  srlg_repairs (needs srlg and remote): LFA_SRLG_SAFE_REPAIRS — a primary with members and no alternate takes
         its per-link repair instead of BK_NONE, unless the repair's forced link is itself a member.
-        ecmp (the plain mode only: excludes lan_protect, node_protect and srlg): routes_backup_ecmp_device() runs twice on the same
-        device chain — the sizing call, then the filling call — and BackupRoutes.ecmp holds a backup per primary of every BK_ECMP
-        prefix; every other field is what ecmp=False returns."""
-        if ecmp and (lan_protect or node_protect or srlg is not None):
-            raise ValueError("backup_routes: ecmp excludes lan_protect, node_protect and srlg")
+        ecmp (excludes lan_protect and node_protect): routes_backup_ecmp_device() runs twice on the same device chain — the sizing
+        call, then the filling call — and BackupRoutes.ecmp holds a backup per primary of every BK_ECMP prefix; every other field
+        is what ecmp=False returns.  With srlg, routes_backup_ecmp_srlg_device() takes its place behind the srlg chain: every
+        primary's backup avoids that primary's own groups (eb_coverage has eleven words), and both BackupRoutes.srlg and
+        BackupRoutes.ecmp are filled."""
+        if ecmp and (lan_protect or node_protect):
+            raise ValueError("backup_routes: ecmp excludes lan_protect and node_protect")
         if srlg is not None and (lan_protect or node_protect):
             raise ValueError("backup_routes: srlg excludes lan_protect and node_protect")
         if srlg_repairs and (srlg is None or not remote):
@@ -1613,7 +1657,7 @@ class SpfContext:
             tab = (prefix_table.pfx_ptr, prefix_table.pfx_vertex, prefix_table.pfx_metric, int(getattr(prefix_table, "flags", 0)))
         tab = tuple(np.ascontiguousarray(a, np.uint32) for a in tab[:3]) + (int(tab[3]) & ~PFX_RESIDENT,)
         if srlg is not None:
-            return self._backup_srlg(graph, root, tab, srlg[0], srlg[1], run_flags, lfa_flags, symmetric, remote, srlg_repairs)
+            return self._backup_srlg(graph, root, tab, srlg[0], srlg[1], run_flags, lfa_flags, symmetric, remote, srlg_repairs, ecmp)
         return self._rlfa(graph, root, run_flags, lfa_flags, remote, symmetric or not remote, remote, backup=tab, lan_protect=lan_protect,
                           lan_spaces=lan_repairs, node=(int(max_pq), int(max_pairs)) if node_protect else None, ecmp=ecmp)
 

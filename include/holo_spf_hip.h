@@ -1291,8 +1291,9 @@ int hspf_routes_backup_lan_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n
  *
  * From eb_* to a backup per next hop of a prefix: INTEGRATION.md §5t.
  *
- * OUT OF SCOPE: the LAN-safe, SRLG-safe and node-protecting-remote variants of this call (hspf_routes_backup_lan_device, _srlg_ and
- * _node_ still answer HSPF_BK_ECMP with the two sets); per-prefix Q-spaces; HSPF_PFX_ORDERED tables. */
+ * OUT OF SCOPE: the LAN-safe and node-protecting-remote variants of this call (hspf_routes_backup_lan_device, _srlg_ and
+ * _node_ still answer HSPF_BK_ECMP with the two sets; the SRLG-safe variant is hspf_routes_backup_ecmp_srlg_device, below);
+ * per-prefix Q-spaces; HSPF_PFX_ORDERED tables. */
 #define HSPF_BK_ECMP_COVERAGE_WORDS    8u
 typedef struct {                 /* DEVICE pointers                                                            */
   uint32_t *eb_ptr;              /* [n_prot * n_prefixes + 1]                                                  */
@@ -1617,7 +1618,8 @@ int hspf_routes_backup_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
  *
  * From bk_* to a next hop when SRLGs are configured: INTEGRATION.md §5r.
  *
- * OUT OF SCOPE: SRLGs combined with the LAN inequalities (a LAN primary is treated as by hspf_routes_backup_device); SRLGs combined
+ * OUT OF SCOPE: a choice for ECMP routes (HSPF_BK_ECMP and the two sets here; per primary and against that primary's own group:
+ * hspf_routes_backup_ecmp_srlg_device, below); SRLGs combined with the LAN inequalities (a LAN primary is treated as by hspf_routes_backup_device); SRLGs combined
  * with node-protecting backups (hspf_routes_backup_node_device); per-prefix Q-spaces (the remote repair is the primary LINK's);
  * HSPF_PFX_ORDERED tables (HSPF_E_INVAL); group tables in the fuzz_frr run of tools/gpu_fuzz.py (existing seeds keep their meaning).
  */
@@ -1631,6 +1633,53 @@ int hspf_routes_backup_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
                                    const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
                                    const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
                                    hspf_backup_out *out_dev);
+
+/* ---- per-primary SRLG-safe backups for ECMP prefixes on device: new symbol, same ABI number ------------------------------------
+ * hspf_routes_backup_srlg_device stops at a route with two or more primaries (HSPF_BK_ECMP, no choice);
+ * hspf_routes_backup_ecmp_device chooses per primary but knows no groups, and its tie order prefers another primary: two
+ * equal-cost uplinks in one conduit are handed to each other, and one cut takes both.  hspf_routes_backup_ecmp_srlg_device is
+ * everything hspf_routes_backup_ecmp_device is ("per-primary backups for ECMP prefixes", above), with the following on top.
+ *
+ * Inputs.  Those of hspf_routes_backup_ecmp_device, plus `srlg` parallel to `prot` exactly as in hspf_routes_backup_srlg_device
+ * (at most HSPF_SRLG_MAX_MEMBERS members per slot; batch and root list [S] ++ neighbour routers ++ member endpoints).  tilfa_dev:
+ * NULL, or the hspf_tilfa_out for the same `prot`; ti_kind, ti_via, ti_metric AND ti_p, ti_link are required when it is given.
+ * For a prefix p with popcount(P) >= 2 and a protected primary h in P let M(h) be the members of slot h.  The members of h ALONE
+ * count: the entry protects h's link, and its risk group is h's; the members of the other primaries play no part.
+ *   crosses_p(N_k, i) as for hspf_routes_backup_srlg_device: d(N_k, a_i) is finite, d_{b_i}(p) exists, and
+ *                     d_{N_k}(p) >= d(N_k, a_i) + w_i + d_{b_i}(p)  (64 bits; HSPF_PFX_SATURATING as there).  An unreachable member
+ *                     refuses nothing.
+ *   cand(h)           additionally, for every member i in M(h): i is not local to k (not (tail_i == S and pos_i == root_link[k])),
+ *                     and crosses_p(N_k, i) is false.  The rule is the same whether or not k is itself a primary: a primary whose
+ *                     own first link is in h's group is refused as a backup of h.
+ *   node(h), downstream and the choice (node, then primary, then sum, then slot) are unchanged, over the narrowed cand(h).
+ *   fallback          no slot chosen for h.  h without members: the plain call's.  h with members: the per-link repair is taken
+ *                     only under HSPF_LFA_SRLG_SAFE_REPAIRS; then HSPF_TILFA_NODE gives HSPF_BK_NODE, and HSPF_TILFA_PAIR gives
+ *                     HSPF_BK_PAIR unless (ti_p[h], ti_link[h]) equals (tail_i, pos_i) of a member of h: then the entry is
+ *                     HSPF_BK_NONE with HSPF_BK_SRLG_PAIR_REFUSED.
+ * eb_flags gains three bits, on an entry of ANY kind (0x08 / 0x10 / 0x20 keep their meaning):
+ *   HSPF_BK_SRLG_PRIMARY       (0x01) h has at least one member
+ *   HSPF_LFA_SRLG_REFUSED      (0x80) some slot met every condition of the plain cand(h) and failed only a member condition
+ *   HSPF_BK_SRLG_PAIR_REFUSED  (0x02) as above
+ * eb_coverage is [n_prot][HSPF_BK_ECMP_SRLG_COVERAGE_WORDS]: the eight words of the plain call (word 7 still counts the prefixes
+ * of which every primary has a backup of any kind) | entries with HSPF_BK_SRLG_PRIMARY | with HSPF_LFA_SRLG_REFUSED | with
+ * HSPF_BK_SRLG_PAIR_REFUSED.  eb_ptr, *out_total and the capacity convention are exactly the plain call's: they depend on the
+ * routes alone.
+ * With every mem_ptr all zero every shared output equals hspf_routes_backup_ecmp_device's bit for bit, words 8 .. 10 are 0, and
+ * HSPF_LFA_SRLG_SAFE_REPAIRS has no effect.
+ * Argument errors — everything hspf_routes_backup_ecmp_device rejects, everything hspf_lfa_srlg_device rejects in `srlg` (17
+ * members on a slot among them), ti_p or ti_link NULL when tilfa_dev is given, HSPF_PFX_ORDERED — return HSPF_E_INVAL with a text
+ * that names hspf_routes_backup_ecmp_srlg_device, before anything is launched.
+ *
+ * From eb_* to a backup per next hop when SRLGs are configured: INTEGRATION.md §5u.
+ *
+ * OUT OF SCOPE: the per-vertex twin (hspf_lfa_ecmp_device with groups); LAN-safe and node-protecting-remote ECMP variants; SRLGs
+ * combined with the LAN inequalities; group tables in the fuzz_frr run of tools/gpu_fuzz.py. */
+#define HSPF_BK_ECMP_SRLG_COVERAGE_WORDS  11u
+int hspf_routes_backup_ecmp_srlg_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                                        const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                                        const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+                                        const hspf_prefix_table *table, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                        uint64_t cap_entries, hspf_backup_ecmp_out *out_dev, uint64_t *out_total);
 
 /* ---- several GPUs --------------------------------------------------------------------------
  * SPF roots are independent units over a read-only graph: the graph is replicated on every GPU, whole 64-root

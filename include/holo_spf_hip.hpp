@@ -654,6 +654,20 @@ class Engine {
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_ecmp_device (") + hspf_last_error(ctx_) + ")");
     return total;
   }
+  // hspf_routes_backup_ecmp_srlg_device: routes_backup_ecmp_device whose alternate for a primary h neither starts on nor crosses, on
+  // its way to the prefix, a member of h's OWN shared-risk group (`srlgs` as for lfa_srlg_device; HSPF_LFA_SRLG_SAFE_REPAIRS in
+  // lfa_flags vouches for tilfa_dev, whose ti_p / ti_link are read too; eb_coverage has HSPF_BK_ECMP_SRLG_COVERAGE_WORDS words per root).
+  uint64_t routes_backup_ecmp_srlg_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
+                                          const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_srlg> &srlgs,
+                                          uint32_t lfa_flags, const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev,
+                                          uint64_t cap_entries, hspf_backup_ecmp_out out_dev) {
+    if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "routes_backup_ecmp_srlg_device: one hspf_srlg per protected root");
+    uint64_t total = 0;
+    const int rc = hspf_routes_backup_ecmp_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
+                                                       (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, cap_entries, &out_dev, &total);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_ecmp_srlg_device (") + hspf_last_error(ctx_) + ")");
+    return total;
+  }
   // hspf_routes_backup_lan_device: the same with loop-freeness towards the pseudonodes of the primaries' LANs (`lans` as for
   // lfa_lan_device; bk_coverage has HSPF_BK_LAN_COVERAGE_WORDS words per root).
   void routes_backup_lan_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,

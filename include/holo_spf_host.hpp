@@ -294,6 +294,14 @@ class Engine {
                                            const std::vector<uint32_t> & /*pfx_vertex*/, const std::vector<uint32_t> & /*pfx_metric*/,
                                            uint32_t /*table_flags*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                                            const TilfaOut * /*tilfa*/) { return BackupEcmpOut{}; }
+  // backup_routes_ecmp() against shared-risk link groups (hspf_routes_backup_ecmp_srlg_device): per primary h an alternate that
+  // avoids h's own groups; srlgs[i] belongs to protect[i] and the run holds the members' endpoints' rows, as for backup_routes_srlg();
+  // HSPF_LFA_SRLG_SAFE_REPAIRS in lfa_flags vouches for `tilfa`, whose ti_p / ti_link are read too.  eb_coverage has
+  // HSPF_BK_ECMP_SRLG_COVERAGE_WORDS words per root.  The default: not supported.
+  virtual BackupEcmpOut backup_routes_ecmp_srlg(DeviceRun & /*run*/, DeviceRoutes & /*routes*/, const std::vector<uint32_t> & /*pfx_ptr*/,
+                                                const std::vector<uint32_t> & /*pfx_vertex*/, const std::vector<uint32_t> & /*pfx_metric*/,
+                                                uint32_t /*table_flags*/, const std::vector<LfaProtect> &, const std::vector<Srlg> &,
+                                                uint32_t /*lfa_flags*/, const TilfaOut * /*tilfa*/) { return BackupEcmpOut{}; }
   virtual std::unique_ptr<Graph> upload(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col,
                                         const std::vector<uint32_t> &metric, const std::vector<uint8_t> &vflags,
                                         uint32_t max_path_metric) = 0;
@@ -1290,6 +1298,17 @@ class HipEngine : public Engine {
   BackupEcmpOut backup_routes_ecmp(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
                                    const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
                                    uint32_t lfa_flags, const TilfaOut *tilfa) override {
+    return backup_routes_ecmp_with(run, routes, pfx_ptr, pfx_vertex, pfx_metric, table_flags, protect, nullptr, lfa_flags, tilfa);
+  }
+  BackupEcmpOut backup_routes_ecmp_srlg(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
+                                        const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
+                                        const std::vector<Srlg> &srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) override {
+    return backup_routes_ecmp_with(run, routes, pfx_ptr, pfx_vertex, pfx_metric, table_flags, protect, &srlgs, lfa_flags, tilfa);
+  }
+  // the frame of backup_routes_ecmp() (srlgs nullptr) and backup_routes_ecmp_srlg()
+  BackupEcmpOut backup_routes_ecmp_with(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
+                                        const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
+                                        const std::vector<Srlg> *srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) {
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rt = static_cast<HipDeviceRoutes &>(routes);
     BackupEcmpOut o;
@@ -1304,20 +1323,29 @@ class HipEngine : public Engine {
         throw std::runtime_error("backup_routes_ecmp: the slot arrays of a protected root differ in length");
       pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
     }
+    std::vector<hspf_srlg> ss;
+    if (srlgs) ss = srlg_raw("backup_routes_ecmp_srlg: ", protect, *srlgs);
     const size_t ps = (size_t)o.n_protected * 64u * r.mask_words;
     const bool with_ti = tilfa && tilfa->supported;
-    if (with_ti && (tilfa->ti_kind.size() != ps || tilfa->ti_via.size() != ps || tilfa->ti_metric.size() != ps))
+    if (with_ti && (tilfa->ti_kind.size() != ps || tilfa->ti_via.size() != ps || tilfa->ti_metric.size() != ps ||
+                    (srlgs && (tilfa->ti_p.size() != ps || tilfa->ti_link.size() != ps))))
       throw std::runtime_error("backup_routes_ecmp: the TI-LFA result is not of this protect list");
-    const size_t pb = ((size_t)o.n_protected * o.n_prefixes + 1) * 4, cb = (size_t)o.n_protected * HSPF_BK_ECMP_COVERAGE_WORDS * 4;
-    // one block: eb_ptr | eb_coverage | ti_via | ti_metric | ti_kind
-    const size_t head = pb + cb + (with_ti ? ps * 9 : 0);
+    const size_t pb = ((size_t)o.n_protected * o.n_prefixes + 1) * 4;
+    const size_t cb = (size_t)o.n_protected * (srlgs ? HSPF_BK_ECMP_SRLG_COVERAGE_WORDS : HSPF_BK_ECMP_COVERAGE_WORDS) * 4;
+    // one block: eb_ptr | eb_coverage | ti_via | ti_metric | (with groups: ti_p | ti_link |) ti_kind
+    const size_t head = pb + cb + (with_ti ? ps * (srlgs ? 17 : 9) : 0);
     uint8_t *blk = (uint8_t *)pool_->dev(head);
     uint32_t *ptr = (uint32_t *)blk, *cov = ptr + pb / 4;
     hspf_tilfa_out ti{};
     bool ok = true;
     if (with_ti) {
       ti.ti_via = cov + cb / 4; ti.ti_metric = ti.ti_via + ps; ti.ti_kind = (uint8_t *)(ti.ti_metric + ps);
-      ok = hipMemcpy(ti.ti_via, tilfa->ti_via.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
+      if (srlgs) {
+        ti.ti_p = ti.ti_metric + ps; ti.ti_link = ti.ti_p + ps; ti.ti_kind = (uint8_t *)(ti.ti_link + ps);
+        ok = hipMemcpy(ti.ti_p, tilfa->ti_p.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(ti.ti_link, tilfa->ti_link.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess;
+      }
+      ok = ok && hipMemcpy(ti.ti_via, tilfa->ti_via.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
            hipMemcpy(ti.ti_metric, tilfa->ti_metric.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
            hipMemcpy(ti.ti_kind, tilfa->ti_kind.data(), ps, hipMemcpyHostToDevice) == hipSuccess;
     }
@@ -1328,10 +1356,15 @@ class HipEngine : public Engine {
     hspf_backup_ecmp_out out{ptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t total = 0;
     const char *what = "hipMemcpy of the repairs: ";
+    auto call = [&](uint64_t cap) {
+      return (srlgs ? hspf_routes_backup_ecmp_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), ss.data(), o.n_protected,
+                                                          lfa_flags, &tab, &ro, with_ti ? &ti : nullptr, cap, &out, &total)
+                    : hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab,
+                                                     &ro, with_ti ? &ti : nullptr, cap, &out, &total)) == HSPF_OK;
+    };
     if (ok) {
-      what = "hspf_routes_backup_ecmp_device: ";
-      ok = hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab, &ro,
-                                          with_ti ? &ti : nullptr, 0, &out, &total) == HSPF_OK;
+      what = srlgs ? "hspf_routes_backup_ecmp_srlg_device: " : "hspf_routes_backup_ecmp_device: ";
+      ok = call(0);
     }
     const size_t t = ok ? (size_t)total : 0;
     o.eb_ptr.resize(pb / 4); o.eb_primary.resize(t); o.eb_kind.resize(t); o.eb_slot.resize(t); o.eb_metric.resize(t); o.eb_flags.resize(t);
@@ -1340,8 +1373,7 @@ class HipEngine : public Engine {
       // the entries: eb_primary | eb_slot | eb_metric | eb_kind | eb_flags
       uint8_t *ent = (uint8_t *)pool_->dev(t * 14);
       out = hspf_backup_ecmp_out{ptr, (uint32_t *)ent, ent + t * 12, (uint32_t *)ent + t, (uint32_t *)ent + 2 * t, ent + t * 13, cov};
-      ok = hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab, &ro,
-                                          with_ti ? &ti : nullptr, total, &out, &total) == HSPF_OK &&
+      ok = call(total) &&
            hipMemcpy(o.eb_primary.data(), out.eb_primary, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(o.eb_slot.data(), out.eb_slot, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
            hipMemcpy(o.eb_metric.data(), out.eb_metric, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&

@@ -1575,7 +1575,28 @@ impl Engine {
     #[allow(clippy::too_many_arguments)]
     pub fn routes_backup_ecmp_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], ignore_overload: bool,
                                      table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>, tilfa: Option<&Tilfa>) -> Result<BackupEcmp, Error> {
+        self.routes_backup_ecmp_device_with(tables, protect, None, ignore_overload, table, resident, routes, tilfa)
+    }
+
+    /// `hspf_routes_backup_ecmp_srlg_device`: `routes_backup_ecmp_device` whose alternate for a primary h neither starts on nor
+    /// crosses, on its way to the PREFIX, a member of h's own shared-risk group — the members of h alone count, and another primary
+    /// in h's group is refused as h's backup.  `srlgs` as for `lfa_srlg_device` (the tables hold the member endpoints' rows);
+    /// `safe_repairs` is `HSPF_LFA_SRLG_SAFE_REPAIRS`.  `eb_flags` carries `HSPF_BK_SRLG_PRIMARY`, `HSPF_LFA_SRLG_REFUSED` and
+    /// `HSPF_BK_SRLG_PAIR_REFUSED` on an entry of any kind; `eb_coverage` has `HSPF_BK_ECMP_SRLG_COVERAGE_WORDS` words per root.
+    #[allow(clippy::too_many_arguments)]
+    pub fn routes_backup_ecmp_srlg_device(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], srlgs: &[&SrlgMembers],
+                                          ignore_overload: bool, safe_repairs: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
+                                          tilfa: Option<&Tilfa>) -> Result<BackupEcmp, Error> {
+        self.routes_backup_ecmp_device_with(tables, protect, Some((srlgs, safe_repairs)), ignore_overload, table, resident, routes, tilfa)
+    }
+
+    /// The frame of `routes_backup_ecmp_device` (`srlg` None) and `routes_backup_ecmp_srlg_device`.
+    #[allow(clippy::too_many_arguments)]
+    fn routes_backup_ecmp_device_with(&self, tables: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])], srlg: Option<(&[&SrlgMembers], bool)>,
+                                      ignore_overload: bool, table: &PrefixTable, resident: bool, routes: &DeviceRoutes<'_>,
+                                      tilfa: Option<&Tilfa>) -> Result<BackupEcmp, Error> {
         let (np, pf, w) = (protect.len(), table.n_prefixes() as usize, tables.words as usize);
+        let srlg_raw = match srlg { Some((m, _)) => Some(Self::srlg_raw("routes_backup_ecmp_srlg_device", protect, m)?), None => None };
         if routes.n_prefixes != table.n_prefixes() || routes.words != tables.words {
             return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_ecmp_device: the routes are not of this table set and table".into() });
         }
@@ -1604,12 +1625,18 @@ impl Engine {
             Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_ecmp_device: the TI-LFA result is not of this protect list".into() }),
             None => None,
         };
+        // the SRLG call also reads the forced adjacency of a pair
+        let ti_pl = match (tilfa, srlg) {
+            (Some(t), Some(_)) if t.ti_p.len() == slots && t.ti_link.len() == slots => Some((self.device_from(&t.ti_p)?, self.device_from(&t.ti_link)?)),
+            (Some(_), Some(_)) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "routes_backup_ecmp_srlg_device: the TI-LFA result is not of this protect list".into() }),
+            _ => None,
+        };
         let ti_raw = ti.as_ref().map(|(k, v, m)| sys::hspf_tilfa_out {
             ti_kind: k.p as *mut u8,
-            ti_p: ptr::null_mut(),
+            ti_p: ti_pl.as_ref().map_or(ptr::null_mut(), |x| x.0.p as *mut u32),
             ti_q: ptr::null_mut(),
             ti_via: v.p as *mut u32,
-            ti_link: ptr::null_mut(),
+            ti_link: ti_pl.as_ref().map_or(ptr::null_mut(), |x| x.1.p as *mut u32),
             ti_metric: m.p as *mut u32,
             ti_counts: ptr::null_mut(),
             td_kind: ptr::null_mut(),
@@ -1632,8 +1659,9 @@ impl Engine {
             best_entry: routes.best_entry.p as *mut u32,
             nexthop_mask: routes.nexthop_mask.p as *mut u64,
         };
-        let cov_words = sys::HSPF_BK_ECMP_COVERAGE_WORDS as usize;
-        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 };
+        let cov_words = if srlg.is_some() { sys::HSPF_BK_ECMP_SRLG_COVERAGE_WORDS } else { sys::HSPF_BK_ECMP_COVERAGE_WORDS } as usize;
+        let lfa_flags = if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 }
+            | if matches!(srlg, Some((_, true))) { sys::HSPF_LFA_SRLG_SAFE_REPAIRS } else { 0 };
         let (dist, flags_in, mask) = (tables.dist.p as *const u32, tables.flags.p as *const u16, tables.mask.p as *const u64);
         let ti_ptr = ti_raw.as_ref().map_or(ptr::null(), |x| x as *const sys::hspf_tilfa_out);
         let eb_ptr = self.device_alloc((np * pf + 1) * 4)?;
@@ -1648,7 +1676,10 @@ impl Engine {
         };
         let mut total: u64 = 0;
         let rc = unsafe {
-            sys::hspf_routes_backup_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, 0, &mut out, &mut total)
+            match &srlg_raw {
+                None => sys::hspf_routes_backup_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, 0, &mut out, &mut total),
+                Some(m) => sys::hspf_routes_backup_ecmp_srlg_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), m.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, 0, &mut out, &mut total),
+            }
         };
         if rc != sys::HSPF_OK {
             return Err(self.err(rc));
@@ -1683,7 +1714,10 @@ impl Engine {
         out.eb_coverage = cov.p as *mut u32;
         t.flags |= sys::HSPF_PFX_RESIDENT; // the sizing call has just staged the table
         let rc = unsafe {
-            sys::hspf_routes_backup_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, total, &mut out, &mut total)
+            match &srlg_raw {
+                None => sys::hspf_routes_backup_ecmp_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, total, &mut out, &mut total),
+                Some(m) => sys::hspf_routes_backup_ecmp_srlg_device(self.ctx, tables.n_vertices, tables.n_roots, tables.words, dist, flags_in, mask, raw.as_ptr(), m.as_ptr(), np as u32, lfa_flags, &t, &r, ti_ptr, total, &mut out, &mut total),
+            }
         };
         if rc != sys::HSPF_OK {
             return Err(self.err(rc));
