@@ -9,14 +9,19 @@
 // wave-uniform (scalar registers), only v differs between lanes.  Nothing that scales with K or with the number of advertisers
 // lives in registers.  d_E(p) of the one primary is computed once, in front of the chunks; an ECMP prefix (whose sets are
 // written, no slot is chosen) streams its entries again per chunk and primary.
-//   k_backup       everything but the counts.
-//   k_backup_cov_t<P>   the coverage of every protection mode P (FrrProt, spf_frr_common.hip.h): a wave counts the kinds of its
+// ONE body, backup_body<FrrProt P> (the modes: spf_frr_common.hip.h): the route and primaries prologue, the chunked stream of d_N(p)
+// with the own bits, the word flush of the two sets, the loop-free and the overload test, the walk over the primaries of an ECMP
+// prefix, the pick rule and the epilogue that chooses between the alternate and the per-link repair stand here once.  A mode adds
+// BackupProt<P>, its kernel arguments, and BackupLane<P>, its lane state with four hooks (below, in front of the body).
+//   k_backup       Plain: everything but the counts.
+//   k_backup_lan   Lan (hspf_routes_backup_lan_device): d_L(p) of the one primary's LAN is computed once next to d_E(p); a candidate
+//                  that has passed every plain condition is then held against d(N, L) + d_L(p); the per-link repair is taken for a
+//                  point-to-point primary, and for a LAN primary only under HSPF_LFA_LAN_SAFE_REPAIRS (the caller's word that the
+//                  repairs come from hspf_rlfa_lan_device's tables).
+//   k_backup_srlg  Srlg (hspf_routes_backup_srlg_device): spf_backup_srlg.hip.h.
+//   k_backup_cov_t<P>   the coverage of every protection mode P: a wave counts the kinds of its
 //                  prefixes, and the mode's bits of bk_flags, with ballots (grid-stride over the tiles of one protected root),
 //                  then one vector atomic add per wave and word.
-// The LAN variant (hspf_routes_backup_lan_device) is k_backup_lan, a further instantiation of the same body: d_L(p) of the one
-// primary's LAN is computed once next to d_E(p); a candidate that has passed every plain
-// condition is then held against d(N, L) + d_L(p); the per-link repair is taken for a point-to-point primary, and for a LAN
-// primary only under HSPF_LFA_LAN_SAFE_REPAIRS (the caller's word that the repairs come from hspf_rlfa_lan_device's tables).
 // There is no wave-per-prefix path: a prefix with very many advertisers is walked by ONE lane and holds its wave back.
 #pragma once
 
@@ -33,7 +38,7 @@ constexpr uint32_t BK_KINDS = 7;                   // HSPF_BK_*
 
 struct BackupArgs {
   uint32_t n, W, ignore_overload, stride;                                  // stride = 64 * W slots per protected root
-  uint32_t n_pfx, sat, lan_repairs, pad1;                                   // lan_repairs: HSPF_LFA_LAN_SAFE_REPAIRS (k_backup_lan)
+  uint32_t n_pfx, sat, pad0, pad1;
   const uint32_t *dist; const uint16_t *flags;                             // the table set
   const uint32_t *tab, *scal;                                              // as LfaArgs (staged by the call, gathered by k_lfa_gather)
   const uint32_t *pfx_ptr, *pfx_vertex, *pfx_metric;                       // the staged prefix table
@@ -73,8 +78,66 @@ __device__ __forceinline__ bool bk_less(uint64_t x, uint32_t b, uint64_t c) {
   return x != BK_NO_DIST && b != LFA_NONE && x < (uint64_t)b + c;
 }
 
-template <bool LAN>
-__device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &la) {
+// The mode's kernel arguments and its lane state (FrrProt, spf_frr_common.hip.h).  A lane has four hooks into backup_body:
+//   open        in front of the chunks: the mode's view of the root, what it keeps about the primaries of the prefix;
+//   one         one primary, candidate k (root_link rlk, d_{N_k}(p) = d) has passed every plain condition: may it stay?
+//   ecmp        the same behind the walk over two or more primaries;
+//   may_repair / repair / flags   the epilogue: may the per-link repair be looked at, may the one found (kind tk, at o) be taken,
+//               and the mode's bits of bk_flags.
+// STREAMS_DE: open() computes d_E(p) of the one primary in a stream of its own (Srlg: next to the members' rows).
+// The Srlg specialisations stand in spf_backup_srlg.hip.h, next to the member lane they use.
+template <FrrProt P> struct BackupProt {};
+template <> struct BackupProt<FrrProt::Lan> { LanArgs la; uint32_t lan_repairs, pad; };   // lan_repairs: HSPF_LFA_LAN_SAFE_REPAIRS
+template <FrrProt P> struct BackupLane {
+  static constexpr bool STREAMS_DE = false;
+  __device__ __forceinline__ void open(const BackupArgs &, const BackupProt<P> &, const FrrTab &, uint32_t, const uint64_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t &) {}
+  __device__ __forceinline__ bool one(uint32_t, uint32_t, uint64_t) { return true; }
+  __device__ __forceinline__ bool ecmp(const BackupArgs &, const FrrTab &, const uint64_t *, uint32_t, uint32_t, uint64_t, uint32_t, uint32_t) { return true; }
+  __device__ __forceinline__ bool may_repair(const BackupProt<P> &) const { return true; }
+  __device__ __forceinline__ bool repair(const BackupProt<P> &, size_t, uint32_t) { return true; }
+  __device__ __forceinline__ uint32_t flags() const { return 0u; }
+};
+// Lan: d_L(p) of the one primary's LAN is computed once, in front of the chunks; a candidate is held against d(N, L) + d_L(p)
+template <> struct BackupLane<FrrProt::Lan> {
+  static constexpr bool STREAMS_DE = false;
+  LanTab lt;
+  uint32_t li0 = LFA_NONE, lfl = 0;                                                // the one primary's LAN; HSPF_LFA_LAN_PRIMARY | _REFUSED
+  uint64_t dL0p = BK_NO_DIST;
+  bool lanp = false;                                                               // some primary crosses a LAN of S
+
+  __device__ __forceinline__ void open(const BackupArgs &a, const BackupProt<FrrProt::Lan> &pa, const FrrTab &tb, uint32_t pi, const uint64_t *pm,
+                                       uint32_t np, uint32_t p0, uint32_t lo, uint32_t hi, uint64_t &) {
+    lt = lan_tab(pa.la, pi, tb.K);
+    if (np == 1) {
+      li0 = lt.li[p0];
+      lanp = li0 != LFA_NONE;
+      if (lanp) dL0p = bk_dist_to_prefix(a, lt.lrow[p0], lo, hi);
+    } else if (np >= 2) lanp = lan_any_primary(tb, lt, pm);
+    if (lanp) lfl |= 0x20u;
+  }
+  __device__ __forceinline__ bool one(uint32_t k, uint32_t, uint64_t d) {
+    if (!lanp || (dL0p != BK_NO_DIST && bk_less(d, lt.ml[k * lt.NL + li0], dL0p))) return true;
+    lfl |= 0x40u;
+    return false;
+  }
+  __device__ __forceinline__ bool ecmp(const BackupArgs &a, const FrrTab &tb, const uint64_t *pm, uint32_t k, uint32_t, uint64_t d, uint32_t lo, uint32_t hi) {
+    if (!lanp) return true;
+    const bool ok = frr_all_primaries(tb, pm, [&](uint32_t q) {
+      const uint32_t j = lt.li[q];
+      if (j == LFA_NONE) return true;
+      const uint64_t dLp = bk_dist_to_prefix(a, lt.lrow[q], lo, hi);
+      return dLp != BK_NO_DIST && bk_less(d, lt.ml[k * lt.NL + j], dLp);
+    });
+    if (!ok) lfl |= 0x40u;
+    return ok;
+  }
+  __device__ __forceinline__ bool may_repair(const BackupProt<FrrProt::Lan> &pa) const { return !lanp || pa.lan_repairs; }   // (a LAN primary: only repairs the caller vouches for)
+  __device__ __forceinline__ bool repair(const BackupProt<FrrProt::Lan> &, size_t, uint32_t) { return true; }
+  __device__ __forceinline__ uint32_t flags() const { return lfl; }
+};
+
+template <FrrProt P>
+__device__ __forceinline__ void backup_body(const BackupArgs &a, const BackupProt<P> &pa) {
   const uint32_t pi = blockIdx.y;
   const FrrTab tb = frr_tab(a.tab, a.scal, pi);
   const uint32_t K = tb.K, C = tb.C, n = a.n, W = a.W, Wk = tb.Wk;
@@ -93,21 +156,10 @@ __device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &
   uint64_t dE0p = BK_NO_DIST;
   if (np == 1) {
     rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
-    if (E0 != LFA_NONE) dE0p = bk_dist_to_prefix(a, tb.row[p0], lo, hi);
+    if (!BackupLane<P>::STREAMS_DE && E0 != LFA_NONE) dE0p = bk_dist_to_prefix(a, tb.row[p0], lo, hi);
   }
-  LanTab lt{};
-  uint32_t li0 = LFA_NONE, lfl = 0;                                                // LAN: the one primary's LAN; the two LAN bits
-  uint64_t dL0p = BK_NO_DIST;
-  bool lanp = false;                                                               // LAN: some primary crosses a LAN of S
-  if constexpr (LAN) {
-    lt = lan_tab(la, pi, K);
-    if (np == 1) {
-      li0 = lt.li[p0];
-      lanp = li0 != LFA_NONE;
-      if (lanp) dL0p = bk_dist_to_prefix(a, lt.lrow[p0], lo, hi);
-    } else if (np >= 2) lanp = lan_any_primary(tb, lt, pm);
-    if (lanp) lfl |= 0x20u;
-  }
+  BackupLane<P> ln;
+  ln.open(a, pa, tb, pi, pm, np, p0, lo, hi, dE0p);
   bool have = false, bnode = false, bdown = false;
   uint64_t bsum = 0, cw = 0, nw = 0;
   uint32_t aslot = LFA_NONE, wi = 0;                                               // wi: the word of the sets that cw / nw stand for
@@ -144,17 +196,14 @@ __device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &
       if (!bk_less(d, tb.dns[k], dSp)) continue;                                   // loop-free with respect to the prefix
       if ((tb.cf[k] & 1u) && !a.ignore_overload && !((own >> j) & 1u)) continue;   // an overloaded neighbour carries no transit traffic
       bool ok, nd = false;
+      const uint32_t rlk = tb.rl[k];
       if (np == 1) {
-        ok = tb.rl[k] != rl0;                                                      // (k == p0 has p0's root_link)
-        if constexpr (LAN) {                                                       // every plain condition holds: now the pseudonode
-          if (ok && lanp && !(dL0p != BK_NO_DIST && bk_less(d, lt.ml[k * lt.NL + li0], dL0p))) { ok = false; lfl |= 0x40u; }
-        }
+        ok = rlk != rl0 && ln.one(k, rlk, d);                                      // (k == p0 has p0's root_link); then the mode
         nd = ok && E0 != LFA_NONE && dE0p != BK_NO_DIST && bk_less(d, tb.m[k * K + p0], dE0p);
       } else {
         ok = !((pm[k >> 6] >> (k & 63u)) & 1ull);
         uint32_t n_router = 0;
-        bool all = true, lanok = true;
-        const uint32_t rlk = tb.rl[k];
+        bool all = true;
         for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
           uint64_t x = frr_word(tb, pm, w2);
           while (x) {
@@ -168,20 +217,9 @@ __device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &
                 all = dEp != BK_NO_DIST && bk_less(d, tb.m[k * K + q], dEp);
               }
             }
-            if constexpr (LAN) {
-              if (lanp && lanok) {
-                const uint32_t j = lt.li[q];
-                if (j != LFA_NONE) {
-                  const uint64_t dLp = bk_dist_to_prefix(a, lt.lrow[q], lo, hi);
-                  lanok = dLp != BK_NO_DIST && bk_less(d, lt.ml[k * lt.NL + j], dLp);
-                }
-              }
-            }
           }
         }
-        if constexpr (LAN) {
-          if (ok && !lanok) { ok = false; lfl |= 0x40u; }
-        }
+        ok = ok && ln.ecmp(a, tb, pm, k, rlk, d, lo, hi);
         nd = ok && n_router && all;
       }
       if (!ok) continue;
@@ -207,18 +245,18 @@ __device__ __forceinline__ void backup_body(const BackupArgs &a, const LanArgs &
       kind = 3u; slot = aslot;
       met = bsum > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)bsum;
       fl = (bnode ? 0x08u : 0u) | (bdown ? 0x10u : 0u);
-    } else if (a.ti_kind && !(LAN && lanp && !a.lan_repairs)) {                             // (a LAN primary: only repairs the caller vouches for)
+    } else if (a.ti_kind && ln.may_repair(pa)) {
       const size_t o = (size_t)pi * a.stride + p0;
       const uint32_t tk = a.ti_kind[o];
-      if (tk) { kind = tk == 1u ? 4u : 5u; slot = a.ti_via[o]; met = a.ti_metric[o]; }
+      if (tk && ln.repair(pa, o, tk)) { kind = tk == 1u ? 4u : 5u; slot = a.ti_via[o]; met = a.ti_metric[o]; }
     }
   }
-  if constexpr (LAN) fl |= lfl;
+  fl |= ln.flags();
   a.bk_kind[oo] = (uint8_t)kind; a.bk_primary[oo] = prim; a.bk_slot[oo] = slot; a.bk_metric[oo] = met; a.bk_flags[oo] = (uint8_t)fl;
 }
 
-__global__ __launch_bounds__(256) void k_backup(BackupArgs a) { backup_body<false>(a, LanArgs{}); }
-__global__ __launch_bounds__(256) void k_backup_lan(BackupArgs a, LanArgs la) { backup_body<true>(a, la); }
+__global__ __launch_bounds__(256) void k_backup(BackupArgs a) { backup_body(a, BackupProt<FrrProt::Plain>{}); }
+__global__ __launch_bounds__(256) void k_backup_lan(BackupArgs a, BackupProt<FrrProt::Lan> pa) { backup_body(a, pa); }
 
 // coverage[pi][]: the seven kinds, then the prefixes with one bit of bk_flags each:
 //   Lan   HSPF_LFA_LAN_PRIMARY, HSPF_LFA_LAN_REFUSED;   Srlg   HSPF_BK_SRLG_PRIMARY, HSPF_LFA_SRLG_REFUSED, HSPF_BK_SRLG_PAIR_REFUSED

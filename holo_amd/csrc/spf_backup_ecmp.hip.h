@@ -30,8 +30,9 @@
 // Modes (FrrProt, spf_frr_common.hip.h).  The fill step is ONE body, backup_ecmp_fill_body<P>, in two modes: Plain is
 // k_backup_ecmp_fill as it was; Srlg (hspf_routes_backup_ecmp_srlg_device) is k_backup_ecmp_fill_srlg.  The batch and the walk are
 // the same text; BackupEcmpLane<Srlg> adds what depends on the ENTRY (p, h) alone: the members of slot h — of h, not of all of P —
-// and d_{b_i}(p) of those at most 16 members, computed ONCE per entry in front of the candidate chunks, in k_backup_srlg's two
-// streams of the prefix's entries (members 0 .. 7, 8 .. 15), packed to 33 bits in registers (bks_get / bks_set).  A candidate reads
+// and d_{b_i}(p) of those at most 16 members, computed ONCE per entry in front of the candidate chunks.  The lane is BkMembers
+// (spf_backup_srlg.hip.h), the member lane of k_backup_srlg: its two streams of the prefix's entries (members 0 .. 7, 8 .. 15), its
+// member test and its forced-adjacency test; the values are packed to 33 bits in registers.  A candidate reads
 // loc, d(N_k, a_i) and w_i of k_srlg_gather's block only after it has passed every plain condition; an entry whose h has no
 // members reads sptr[h], sptr[h + 1] and nothing else of the member block, and streams no advertiser row more than Plain does.
 // Registers, not LDS: next to the d_N(p) batch 256 entries x 16 members x 33 bits would be 17 KB more (37 KB: four workgroups per
@@ -70,65 +71,14 @@ template <FrrProt P> struct BackupEcmpProt {};
 template <> struct BackupEcmpProt<FrrProt::Srlg> { BackupSrlgArgs s; };
 template <FrrProt P> struct BackupEcmpLane {};
 template <> struct BackupEcmpLane<FrrProt::Srlg> {
-  SrlgTab st;
-  uint32_t s0 = 0, nm = 0;                                               // the members of the entry's h in sidx
-  uint32_t dbl[SRLG_MAXM], dbh = 0xFFFFu;                                // their d_{b_i}(p) (bks_get / bks_set)
+  BkMembers mb;                                                          // the members of the entry's h (spf_backup_srlg.hip.h)
   uint32_t sfl = 0;                                                      // HSPF_BK_SRLG_PRIMARY | _PAIR_REFUSED | HSPF_LFA_SRLG_REFUSED
 
-  __device__ __forceinline__ void open(const BackupEcmpProt<FrrProt::Srlg> &pa, uint32_t pi, uint32_t K) { st = srlg_tab(pa.s.sa, pi, K); }
-  // a new entry (p, h): the members of h and their d_b(p), the prefix's entries lo .. hi streamed once per BKS_MCH members
+  __device__ __forceinline__ void open(const BackupEcmpProt<FrrProt::Srlg> &pa, uint32_t pi, uint32_t K) { mb.st = srlg_tab(pa.s.sa, pi, K); }
+  // a new entry (p, h)
   __device__ __forceinline__ void entry(const BackupArgs &a, bool live, uint32_t h, uint32_t lo, uint32_t hi) {
-    s0 = 0; nm = 0; sfl = 0; dbh = 0xFFFFu;
-#pragma unroll
-    for (uint32_t j = 0; j < SRLG_MAXM; ++j) dbl[j] = 0xFFFFFFFFu;
-    if (!live) return;
-    s0 = st.sptr[h];
-    nm = st.sptr[h + 1] - s0;                                            // (at most SRLG_MAXM: the call checked it; every loop over dbl ends at SRLG_MAXM by itself)
-    if (!nm) return;
-    sfl = 0x01u;
-#pragma unroll
-    for (uint32_t m0 = 0; m0 < SRLG_MAXM; m0 += BKS_MCH) {               // (one stream unless h has more than BKS_MCH members)
-      if (m0 >= nm) break;
-      uint32_t hrow[BKS_MCH];
-#pragma unroll
-      for (uint32_t j = 0; j < BKS_MCH; ++j) hrow[j] = m0 + j < nm ? st.hrow[st.sidx[s0 + m0 + j]] : 0u;
-      for (uint32_t e = lo; e < hi; ++e) {
-        const uint32_t v = a.pfx_vertex[e], met = a.pfx_metric[e];
-#pragma unroll
-        for (uint32_t j = 0; j < BKS_MCH; ++j) {
-          if (m0 + j >= nm) break;
-          const uint64_t t = bk_term(a, (size_t)hrow[j] * a.n + v, met);   // (BK_NO_DIST is above every packed value)
-          if (t < bks_get(dbl, dbh, m0 + j)) bks_set(dbl, dbh, m0 + j, t);
-        }
-      }
-    }
-  }
-  // candidate k (root_link rlk, d_{N_k}(p) = d), which has passed every plain condition: no member of h is local to k, none is crossed
-  __device__ __forceinline__ bool safe(uint32_t k, uint32_t rlk, uint64_t d) const {
-    bool ok = true;
-    // (two loops of BKS_MCH: the compiler unrolls a loop with an early exit completely only up to eight iterations, and a loop it
-    // unrolls by a run-time count indexes dbl dynamically — the lane's state would move to scratch, profiles/r25_notes.md)
-#pragma unroll
-    for (uint32_t m0 = 0; m0 < SRLG_MAXM; m0 += BKS_MCH) {
-      if (m0 >= nm) break;
-#pragma unroll
-      for (uint32_t j = 0; j < BKS_MCH; ++j) {
-        if (m0 + j >= nm) break;
-        const uint32_t i = st.sidx[s0 + m0 + j];
-        ok = ok && st.loc[i] != rlk && !bks_cross(d, st.dNa[(size_t)k * st.NM + i], st.cost[i], bks_get(dbl, dbh, m0 + j));
-      }
-    }
-    return ok;
-  }
-  // is the forced adjacency (tp, tl) of h's two-segment repair a member of h?
-  __device__ __forceinline__ bool forced(uint32_t tp, uint32_t tl) const {
-    const uint32_t *pos = srlg_pos(st);
-    bool f = false;
-    for (uint32_t i2 = 0; i2 < nm; ++i2) {
-      const uint32_t i = st.sidx[s0 + i2];
-      f = f || (st.tail[i] == tp && pos[i] == tl);
-    }
-    return f;
+    if (live) mb.stream(a, h, lo, hi); else mb.clear();
+    sfl = mb.nm ? 0x01u : 0u;
   }
 };
 
@@ -264,7 +214,7 @@ __device__ __forceinline__ void backup_ecmp_fill_body(const BackupEcmpArgs &a, c
           if ((tb.cf[k] & 1u) && !a.b.ignore_overload && !(raw & BE_OWN)) continue;
           if (tb.rl[k] == rlh) continue;                                 // shares the first link's fate
           if constexpr (SRLG) {                                          // every plain condition holds: now the group of h
-            if (ln.nm && !ln.safe(k, tb.rl[k], d)) { ln.sfl |= 0x80u; continue; }
+            if (ln.mb.nm && !ln.mb.safe(k, tb.rl[k], d)) { ln.sfl |= 0x80u; continue; }
           }
           const bool nd = dEp != BK_NO_DIST && bk_less(d, tb.m[k * K + h], dEp);
           const bool pr = (pm[k >> 6] >> (k & 63u)) & 1ull;
@@ -286,9 +236,9 @@ __device__ __forceinline__ void backup_ecmp_fill_body(const BackupEcmpArgs &a, c
           const uint32_t tk = a.b.ti_kind[o];
           bool take = tk != 0;
           if constexpr (SRLG) {
-            if (ln.nm) {                                                 // h has members: only repairs the caller vouches for
+            if (ln.mb.nm) {                                              // h has members: only repairs the caller vouches for
               take = take && pa.s.repairs;
-              if (take && tk == 2u && ln.forced(pa.s.ti_p[o], pa.s.ti_link[o])) { take = false; ln.sfl |= 0x02u; }
+              if (take && tk == 2u && ln.mb.forced(pa.s.ti_p[o], pa.s.ti_link[o])) { take = false; ln.sfl |= 0x02u; }
             }
           }
           if (take) { kind = tk == 1u ? 4u : 5u; slot = a.b.ti_via[o]; met = a.b.ti_metric[o]; }

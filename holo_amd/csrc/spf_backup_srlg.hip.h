@@ -1,28 +1,26 @@
 // spf_backup_srlg.hip.h — per-prefix backup routes that avoid the shared-risk link groups of the primaries
-// (hspf_routes_backup_srlg_device; the semantics are written down once, in include/holo_spf_hip.h).  The kernels of
-// spf_backup.hip.h and spf_srlg.hip.h are not instantiated again: their text is untouched, and what they share (BackupArgs,
-// bk_term, bk_dist_to_prefix, bk_less, srlg_tab, frr_tab, frr_primaries) is used from here.  (k_backup_srlg is still a copy of
-// backup_body with the member conditions in it: as an instantiation of one body over FrrProt it lost the registers of d_{b_i}(p)
-// to scratch, profiles/r25_notes.md.)
+// (hspf_routes_backup_srlg_device; the semantics are written down once, in include/holo_spf_hip.h).  k_backup_srlg is
+// backup_body (spf_backup.hip.h) in the mode FrrProt::Srlg: this file holds the mode's arguments, its lane state with the four
+// hooks the body calls, and BkMembers, the member lane that the per-primary ECMP fill (spf_backup_ecmp.hip.h) uses as well.
 //
 // Staged blocks.  The slot tables and the prefix table are those of hspf_routes_backup_device; the member block is srlg_stage's
 // (spf_srlg.hip.h), with ONE column appended behind `loc`:  pos [NM], the member's position within its tail's row.  No offset that
-// srlg_tab reads moves; the column is reached through srlg_pos() below, which srlg_stage shares its two constants with.  d(N_k, a_i) and the members' costs come from the block that
-// k_srlg_gather fills.
+// srlg_tab reads moves; the column is reached through srlg_pos() below, which srlg_stage shares its two constants with.
+// d(N_k, a_i) and the members' costs come from the block that k_srlg_gather fills.
 //
-// Shape.  k_backup_srlg is k_backup — lane = prefix, 256 prefixes per workgroup, blockIdx.y = the protected root, candidate slots
-// in chunks of BK_CH with d_N(p) in registers — with the member conditions behind every plain one.
-//   one primary   d_{b_i}(p) of the primary's members is computed next to d_E(p), in front of the chunks, in ONE stream of the
-//                 prefix's entries: per entry (v, m) one gather dist[head_row_i][v] per member; a primary with more than BKS_MCH
-//                 members takes a second stream for members 8 .. 15.  All HSPF_SRLG_MAX_MEMBERS values stay in registers, packed
-//                 to 33 bits (16 low words and one word of high bits; a sum is at most 0x1FFFFFFFD, so 0x1FFFFFFFF stands for
-//                 "no advertiser reached").  As 16 x u64 next to 16 head rows the kernel took 147 VGPRs, in this form 131: one
-//                 wave per SIMD fewer than k_backup.  With amdgpu_waves_per_eu(4) the compiler fits it into 104 VGPRs without
-//                 scratch (profiles/r23_notes.md has the resource reports).  A candidate reads
-//                 loc, d(N_k, a_i) and w_i only after it has passed every plain condition; a prefix whose primary has no member
-//                 evaluates no member term and streams nothing more than k_backup does.
-//   ECMP          sets only: a candidate that passed the plain conditions re-streams the entries per primary and member, as the
-//                 plain kernel re-streams them per primary.
+// BkMembers: what a lane keeps about the members of ONE primary h.
+//   stream   d_{b_i}(p) of h's members in ONE stream of the prefix's entries: per entry (v, m) one gather dist[head_row_i][v] per
+//            member; an h with more than BKS_MCH members takes a second stream for members 8 .. 15.  The per-prefix kernel folds
+//            d_E(p) of a router primary into the first stream.  All HSPF_SRLG_MAX_MEMBERS values stay in registers, packed to 33
+//            bits (16 low words in ONE 16-lane vector and one word of high bits; a sum is at most 0x1FFFFFFFD, so 0x1FFFFFFFF
+//            stands for "no advertiser reached").  An h without members streams nothing (the kernel: nothing beyond d_E(p)).
+//   safe     a candidate that has passed every plain condition against the members: none local to it, none crossed.  A loop to
+//            the number of members: as a vector the values are indexed by a run-time count without leaving the registers (as an
+//            array inside the lane's struct they went to scratch, and unrolled 16 times per slot of a chunk the kernel no longer
+//            fitted four waves: profiles/r29_notes.md has both reports).  loc, d(N_k, a_i) and w_i are read only here.
+//   forced   is the forced adjacency of a two-segment repair a member of h?
+// The ECMP sets of the per-prefix kernel (two or more primaries, no slot is chosen) keep no values: bks_safe_stream re-streams
+// the entries per primary and member, as the plain kernel re-streams them per primary; bks_member_ok is the one test of both.
 //   k_backup_cov_srlg   k_backup_cov_t<Srlg> (spf_backup.hip.h), ten words.
 #pragma once
 
@@ -57,212 +55,133 @@ __device__ __forceinline__ bool bks_cross(uint64_t dNp, uint32_t dNa, uint32_t w
 }
 
 // d_{b_i}(p) in 33 bits: the low word, and bit j of `hi` for member j
-__device__ __forceinline__ uint64_t bks_get(const uint32_t (&lo)[SRLG_MAXM], uint32_t hi, uint32_t j) { return (uint64_t)lo[j] | ((uint64_t)((hi >> j) & 1u) << 32); }
-__device__ __forceinline__ void bks_set(uint32_t (&lo)[SRLG_MAXM], uint32_t &hi, uint32_t j, uint64_t x) {
+typedef uint32_t bks_lo_t __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ uint64_t bks_get(const bks_lo_t &lo, uint32_t hi, uint32_t j) { return (uint64_t)lo[j] | ((uint64_t)((hi >> j) & 1u) << 32); }
+__device__ __forceinline__ void bks_set(bks_lo_t &lo, uint32_t &hi, uint32_t j, uint64_t x) {
   lo[j] = (uint32_t)x; hi = (hi & ~(1u << j)) | ((uint32_t)(x >> 32) << j);
 }
 
-// candidate k (root_link rlk, d_{N_k}(p) = d) against the members of primary q, their d_{b_i}(p) streamed here (the ECMP path)
+// member i against candidate k (root_link rlk, d_{N_k}(p) = d): it is not local to k and k's path to p does not cross it.
+// dbp() yields d_{b_i}(p); it is asked only for a member that N_k reaches.
+template <class F>
+__device__ __forceinline__ bool bks_member_ok(const SrlgTab &st, uint32_t i, uint32_t k, uint32_t rlk, uint64_t d, F &&dbp) {
+  if (st.loc[i] == rlk) return false;
+  const uint32_t dNa = st.dNa[(size_t)k * st.NM + i];
+  return dNa == LFA_NONE || !bks_cross(d, dNa, st.cost[i], dbp());
+}
+
+// candidate k against the members of primary q, their d_{b_i}(p) streamed here (the ECMP sets of the per-prefix kernel)
 __device__ __forceinline__ bool bks_safe_stream(const BackupArgs &a, const SrlgTab &st, uint32_t k, uint32_t rlk, uint32_t q, uint64_t d,
                                                 uint32_t lo, uint32_t hi) {
   const uint32_t x1 = st.sptr[q + 1];
   for (uint32_t x = st.sptr[q]; x < x1; ++x) {
     const uint32_t i = st.sidx[x];
-    if (st.loc[i] == rlk) return false;
-    const uint32_t dNa = st.dNa[(size_t)k * st.NM + i];
-    if (dNa == LFA_NONE) continue;
-    if (bks_cross(d, dNa, st.cost[i], bk_dist_to_prefix(a, st.hrow[i], lo, hi))) return false;
+    if (!bks_member_ok(st, i, k, rlk, d, [&] { return bk_dist_to_prefix(a, st.hrow[i], lo, hi); })) return false;
   }
   return true;
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_backup_srlg(BackupArgs a, BackupSrlgArgs b) {
-  const uint32_t pi = blockIdx.y;
-  const FrrTab tb = frr_tab(a.tab, a.scal, pi);
-  const uint32_t K = tb.K, C = tb.C, n = a.n, W = a.W, Wk = tb.Wk;
-  const uint32_t p = blockIdx.x * LFA_TILE + threadIdx.x;
-  if (p >= a.n_pfx) return;                                                        // (no barrier below)
-  const SrlgTab st = srlg_tab(b.sa, pi, K);
-  const size_t oi = (size_t)tb.srow * a.n_pfx + p, oo = (size_t)pi * a.n_pfx + p;
-  const uint32_t lo = a.pfx_ptr[p], hi = a.pfx_ptr[p + 1];
-  const bool route = a.best_entry[oi] != LFA_NONE;
-  const uint64_t dSp = a.best_metric[oi];
-  const uint64_t *pm = a.nh_mask + oi * W;
-  uint32_t np = 0, p0 = 0;
-  if (route) frr_primaries(tb, pm, np, p0);
-  uint32_t kind = !route ? 0u : np == 0 ? 1u : np >= 2 ? 2u : 6u;
-  const bool sets = kind >= 2;                                                     // the two sets are evaluated and written
-  uint32_t rl0 = LFA_NONE, E0 = LFA_NONE, s0 = 0, nm0 = 0;                         // s0, nm0: the one primary's members in sidx
-  uint64_t dE0p = BK_NO_DIST;
-  uint32_t dbl[SRLG_MAXM], dbh = 0xFFFFu;                                          // d_{b_i}(p) of the one primary's members (bks_get / bks_set)
-  bool hasm = false;                                                               // some primary has members
-  if (np == 1) {
-    rl0 = tb.rl[p0]; E0 = tb.nbr[p0];
-    s0 = st.sptr[p0]; nm0 = st.sptr[p0 + 1] - s0;
-    nm0 = nm0 > SRLG_MAXM ? SRLG_MAXM : nm0;                                       // (the call checked it: the bound of the register array)
-    hasm = nm0 != 0;
-    // d_E(p) and the members' d_b(p): the entries streamed once
-    const size_t ebase = (size_t)tb.row[p0] * n;
-#pragma unroll
-    for (uint32_t j = 0; j < SRLG_MAXM; ++j) dbl[j] = 0xFFFFFFFFu;
-    if (E0 != LFA_NONE || hasm) {
-#pragma unroll
-      for (uint32_t m0 = 0; m0 < SRLG_MAXM; m0 += BKS_MCH) {                       // (one stream unless the primary has more than BKS_MCH members)
-        if (m0 && m0 >= nm0) break;
-        uint32_t hrow[BKS_MCH];
-#pragma unroll
-        for (uint32_t j = 0; j < BKS_MCH; ++j) hrow[j] = m0 + j < nm0 ? st.hrow[st.sidx[s0 + m0 + j]] : 0u;
-        for (uint32_t e = lo; e < hi; ++e) {
-          const uint32_t v = a.pfx_vertex[e], met = a.pfx_metric[e];
-          if (!m0 && E0 != LFA_NONE) { const uint64_t t = bk_term(a, ebase + v, met); dE0p = t < dE0p ? t : dE0p; }
-#pragma unroll
-          for (uint32_t j = 0; j < BKS_MCH; ++j) {
-            if (m0 + j >= nm0) break;
-            const uint64_t t = bk_term(a, (size_t)hrow[j] * n + v, met);           // (BK_NO_DIST is above every packed value)
-            if (t < bks_get(dbl, dbh, m0 + j)) bks_set(dbl, dbh, m0 + j, t);
-          }
-        }
-      }
-    }
-  } else {
+// What a lane keeps about the members of ONE primary h: where they stand in sidx, and their d_{b_i}(p), at most SRLG_MAXM values
+// packed to 33 bits in registers.  Used by the one-primary path of k_backup_srlg and, per entry (p, h), by k_backup_ecmp_fill_srlg.
+struct BkMembers {
+  SrlgTab st;
+  uint32_t s0 = 0, nm = 0;                                                         // the members of h: sidx[s0 .. s0 + nm)
+  bks_lo_t dbl; uint32_t dbh = 0xFFFFu;                                            // their d_{b_i}(p) (bks_get / bks_set)
+
+  __device__ __forceinline__ void clear() {
+    s0 = 0; nm = 0; dbh = 0xFFFFu;
 #pragma unroll
     for (uint32_t j = 0; j < SRLG_MAXM; ++j) dbl[j] = 0xFFFFFFFFu;
   }
-  if (np >= 2 && st.T) {
-    for (uint32_t w2 = 0; w2 < Wk; ++w2) {
-      uint64_t x = frr_word(tb, pm, w2);
-      while (x) {
-        const uint32_t q = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-        x &= x - 1;
-        hasm = hasm || st.sptr[q + 1] != st.sptr[q];
-      }
-    }
-  }
-  uint32_t sfl = (sets && hasm) ? 0x01u : 0u;                                      // HSPF_BK_SRLG_PRIMARY | _PAIR_REFUSED | HSPF_LFA_SRLG_REFUSED
-  bool have = false, bnode = false, bdown = false;
-  uint64_t bsum = 0, cw = 0, nw = 0;
-  uint32_t aslot = LFA_NONE, wi = 0;                                               // wi: the word of the sets that cw / nw stand for
-  for (uint32_t c0 = 0; c0 < C; c0 += BK_CH) {
-    // d_N(p) of the chunk's neighbours: the entries streamed once; own bit j: N_j's own entry attains d_{N_j}(p)
-    uint64_t dNp[BK_CH];
-    uint32_t own = 0;
+  // the members of h and their d_b(p): the prefix's entries lo .. hi streamed once per BKS_MCH member head rows.  With `extra` the
+  // first stream also takes the minimum over row erow into dE (d_E(p) of a router primary).  Nothing is streamed for an h without
+  // members unless `extra` asks for the row.
+  template <class Args>
+  __device__ __forceinline__ void stream(const Args &a, uint32_t h, uint32_t lo, uint32_t hi, bool extra = false, uint32_t erow = 0, uint64_t *dE = nullptr) {
+    clear();
+    s0 = st.sptr[h];
+    nm = st.sptr[h + 1] - s0;
+    nm = nm > SRLG_MAXM ? SRLG_MAXM : nm;                                          // (the call checked it: the bound of dbl)
+    if (!nm && !extra) return;
+    const size_t ebase = (size_t)erow * a.n;
 #pragma unroll
-    for (uint32_t j = 0; j < BK_CH; ++j) dNp[j] = BK_NO_DIST;
-    if (sets)
+    for (uint32_t m0 = 0; m0 < SRLG_MAXM; m0 += BKS_MCH) {                         // (one stream unless h has more than BKS_MCH members)
+      if (m0 && m0 >= nm) break;
+      uint32_t hrow[BKS_MCH];
+#pragma unroll
+      for (uint32_t j = 0; j < BKS_MCH; ++j) hrow[j] = m0 + j < nm ? st.hrow[st.sidx[s0 + m0 + j]] : 0u;
       for (uint32_t e = lo; e < hi; ++e) {
         const uint32_t v = a.pfx_vertex[e], met = a.pfx_metric[e];
+        if (!m0 && extra) { const uint64_t t = bk_term(a, ebase + v, met); *dE = t < *dE ? t : *dE; }
 #pragma unroll
-        for (uint32_t j = 0; j < BK_CH; ++j) {
-          if (c0 + j >= C) break;
-          const uint32_t k = tb.cl[c0 + j];
-          const uint64_t t = bk_term(a, (size_t)tb.row[k] * n + v, met);
-          const bool mine = v == tb.nbr[k];
-          if (t < dNp[j]) { dNp[j] = t; own = (own & ~(1u << j)) | ((mine ? 1u : 0u) << j); }
-          else if (t == dNp[j] && mine && t != BK_NO_DIST) own |= 1u << j;
-        }
-      }
-#pragma unroll
-    for (uint32_t j = 0; j < BK_CH; ++j) {
-      if (c0 + j >= C) break;
-      const uint32_t k = tb.cl[c0 + j];                                            // ascending, the same for every lane
-      while (wi < (k >> 6)) {                                                      // the words in front of slot k are complete
-        if (a.cand_mask) a.cand_mask[oo * W + wi] = cw;
-        if (a.node_mask) a.node_mask[oo * W + wi] = nw;
-        cw = 0; nw = 0; ++wi;
-      }
-      if (!sets) continue;
-      const uint64_t d = dNp[j];
-      if (!bk_less(d, tb.dns[k], dSp)) continue;                                   // loop-free with respect to the prefix
-      if ((tb.cf[k] & 1u) && !a.ignore_overload && !((own >> j) & 1u)) continue;   // an overloaded neighbour carries no transit traffic
-      bool ok, nd = false;
-      const uint32_t rlk = tb.rl[k];
-      if (np == 1) {
-        ok = rlk != rl0;                                                           // (k == p0 has p0's root_link)
-        if (ok && hasm) {                                                          // every plain condition holds: now the group
-          bool safe = true;
-#pragma unroll
-          for (uint32_t i2 = 0; i2 < SRLG_MAXM; ++i2) {
-            if (i2 >= nm0) break;
-            const uint32_t i = st.sidx[s0 + i2];
-            safe = safe && st.loc[i] != rlk && !bks_cross(d, st.dNa[(size_t)k * st.NM + i], st.cost[i], bks_get(dbl, dbh, i2));
-          }
-          if (!safe) { ok = false; sfl |= 0x80u; }
-        }
-        nd = ok && E0 != LFA_NONE && dE0p != BK_NO_DIST && bk_less(d, tb.m[k * K + p0], dE0p);
-      } else {
-        ok = !((pm[k >> 6] >> (k & 63u)) & 1ull);
-        uint32_t n_router = 0;
-        bool all = true;
-        for (uint32_t w2 = 0; w2 < Wk && ok; ++w2) {
-          uint64_t x = frr_word(tb, pm, w2);
-          while (x) {
-            const uint32_t q = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-            x &= x - 1;
-            if (tb.rl[q] == rlk) { ok = false; break; }
-            if (tb.nbr[q] != LFA_NONE) {
-              ++n_router;
-              if (all) {
-                const uint64_t dEp = bk_dist_to_prefix(a, tb.row[q], lo, hi);
-                all = dEp != BK_NO_DIST && bk_less(d, tb.m[k * K + q], dEp);
-              }
-            }
-          }
-        }
-        if (ok && hasm) {
-          bool safe = true;
-          for (uint32_t w2 = 0; w2 < Wk && safe; ++w2) {
-            uint64_t x = frr_word(tb, pm, w2);
-            while (x && safe) {
-              const uint32_t q = w2 * 64u + (uint32_t)__ffsll((unsigned long long)x) - 1u;
-              x &= x - 1;
-              safe = bks_safe_stream(a, st, k, rlk, q, d, lo, hi);
-            }
-          }
-          if (!safe) { ok = false; sfl |= 0x80u; }
-        }
-        nd = ok && n_router && all;
-      }
-      if (!ok) continue;
-      cw |= 1ull << (k & 63u);
-      if (nd) nw |= 1ull << (k & 63u);
-      if (np == 1) {
-        const uint64_t sum = (uint64_t)tb.cost[k] + d;
-        if (!have || (nd && !bnode) || (nd == bnode && sum < bsum)) {              // ascending slot order: a tie keeps the smaller slot
-          have = true; bnode = nd; bsum = sum; aslot = k; bdown = d < dSp;
+        for (uint32_t j = 0; j < BKS_MCH; ++j) {
+          if (m0 + j >= nm) break;
+          const uint64_t t = bk_term(a, (size_t)hrow[j] * a.n + v, met);           // (BK_NO_DIST is above every packed value)
+          if (t < bks_get(dbl, dbh, m0 + j)) bks_set(dbl, dbh, m0 + j, t);
         }
       }
     }
   }
-  for (; wi < W; ++wi) {                                                           // the last word with candidates, and what lies behind
-    if (a.cand_mask) a.cand_mask[oo * W + wi] = cw;
-    if (a.node_mask) a.node_mask[oo * W + wi] = nw;
-    cw = 0; nw = 0;
+  // candidate k (root_link rlk, d_{N_k}(p) = d), which has passed every plain condition: no member of h is local to k, none is crossed
+  __device__ __forceinline__ bool safe(uint32_t k, uint32_t rlk, uint64_t d) const {
+    bool ok = true;
+    // (a loop to nm, not an unrolled one: dbl is a vector, which the compiler indexes by a run-time count in registers.  The 128
+    // unrolled tests of a chunk — as two loops of BKS_MCH — cost k_backup_srlg its fourth wave, profiles/r29_notes.md)
+    for (uint32_t i2 = 0; i2 < nm && ok; ++i2) ok = bks_member_ok(st, st.sidx[s0 + i2], k, rlk, d, [&] { return bks_get(dbl, dbh, i2); });
+    return ok;
   }
-  uint32_t prim = LFA_NONE, slot = LFA_NONE, met = 0, fl = 0;
-  if (np == 1) {
-    prim = p0;
-    if (have) {
-      kind = 3u; slot = aslot;
-      met = bsum > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)bsum;
-      fl = (bnode ? 0x08u : 0u) | (bdown ? 0x10u : 0u);
-    } else if (a.ti_kind && !(hasm && !b.repairs)) {                               // (a primary with members: only repairs the caller vouches for)
-      const size_t o = (size_t)pi * a.stride + p0;
-      const uint32_t tk = a.ti_kind[o];
-      bool forced = false;                                                         // the pair's forced adjacency is a member of the primary
-      if (tk == 2u && hasm) {
-        const uint32_t tp = b.ti_p[o], tl = b.ti_link[o];
-        const uint32_t *pos = srlg_pos(st);
-        for (uint32_t i2 = 0; i2 < nm0; ++i2) {
-          const uint32_t i = st.sidx[s0 + i2];
-          forced = forced || (st.tail[i] == tp && pos[i] == tl);
-        }
-      }
-      if (forced) sfl |= 0x02u;
-      else if (tk) { kind = tk == 1u ? 4u : 5u; slot = a.ti_via[o]; met = a.ti_metric[o]; }
+  // is the forced adjacency (tp, tl) of h's two-segment repair a member of h?
+  __device__ __forceinline__ bool forced(uint32_t tp, uint32_t tl) const {
+    const uint32_t *pos = srlg_pos(st);
+    bool f = false;
+    for (uint32_t i2 = 0; i2 < nm; ++i2) {
+      const uint32_t i = st.sidx[s0 + i2];
+      f = f || (st.tail[i] == tp && pos[i] == tl);
     }
+    return f;
   }
-  fl |= sfl;
-  a.bk_kind[oo] = (uint8_t)kind; a.bk_primary[oo] = prim; a.bk_slot[oo] = slot; a.bk_metric[oo] = met; a.bk_flags[oo] = (uint8_t)fl;
-}
+};
+
+// backup_body (spf_backup.hip.h) in the mode FrrProt::Srlg: its arguments, its lane state and the hooks the body calls
+template <> struct BackupProt<FrrProt::Srlg> { BackupSrlgArgs s; };
+template <> struct BackupLane<FrrProt::Srlg> {
+  static constexpr bool STREAMS_DE = true;
+  BkMembers mb;                                                                    // the one primary's
+  uint32_t sfl = 0;                                                                // HSPF_BK_SRLG_PRIMARY | _PAIR_REFUSED | HSPF_LFA_SRLG_REFUSED
+  bool hasm = false;                                                               // some primary has members
+
+  __device__ __forceinline__ void open(const BackupArgs &a, const BackupProt<FrrProt::Srlg> &pa, const FrrTab &tb, uint32_t pi, const uint64_t *pm,
+                                       uint32_t np, uint32_t p0, uint32_t lo, uint32_t hi, uint64_t &dE0p) {
+    mb.st = srlg_tab(pa.s.sa, pi, tb.K);
+    if (np == 1) {                                                                 // d_E(p) and the members' d_b(p): the entries streamed once
+      mb.stream(a, p0, lo, hi, tb.nbr[p0] != LFA_NONE, tb.row[p0], &dE0p);
+      hasm = mb.nm != 0;
+    } else {
+      mb.clear();
+      if (np >= 2) hasm = mb.st.T && !frr_all_primaries(tb, pm, [&](uint32_t q) { return mb.st.sptr[q + 1] == mb.st.sptr[q]; });
+    }
+    if (hasm) sfl = 0x01u;
+  }
+  __device__ __forceinline__ bool one(uint32_t k, uint32_t rlk, uint64_t d) {
+    if (!hasm || mb.safe(k, rlk, d)) return true;
+    sfl |= 0x80u;
+    return false;
+  }
+  __device__ __forceinline__ bool ecmp(const BackupArgs &a, const FrrTab &tb, const uint64_t *pm, uint32_t k, uint32_t rlk, uint64_t d, uint32_t lo, uint32_t hi) {
+    if (!hasm || frr_all_primaries(tb, pm, [&](uint32_t q) { return bks_safe_stream(a, mb.st, k, rlk, q, d, lo, hi); })) return true;
+    sfl |= 0x80u;
+    return false;
+  }
+  __device__ __forceinline__ bool may_repair(const BackupProt<FrrProt::Srlg> &pa) const { return !hasm || pa.s.repairs; }   // (a primary with members: only repairs the caller vouches for)
+  // a pair whose forced adjacency is a member of the primary is refused
+  __device__ __forceinline__ bool repair(const BackupProt<FrrProt::Srlg> &pa, size_t o, uint32_t tk) {
+    if (!(tk == 2u && hasm && mb.forced(pa.s.ti_p[o], pa.s.ti_link[o]))) return true;
+    sfl |= 0x02u;
+    return false;
+  }
+  __device__ __forceinline__ uint32_t flags() const { return sfl; }
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_backup_srlg(BackupArgs a, BackupProt<FrrProt::Srlg> pa) { backup_body(a, pa); }
 
 }  // namespace

@@ -392,7 +392,6 @@ int routes_backup(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertic
     BackupArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
     a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
-    a.lan_repairs = (with_lan && (lfa_flags & HSPF_LFA_LAN_SAFE_REPAIRS)) ? 1u : 0u;
     a.dist = dist_dev; a.flags = flags_dev;
     a.tab = ga.tab; a.scal = ga.scal;
     a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
@@ -408,10 +407,10 @@ int routes_backup(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertic
     const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
     const dim3 grid(n_tiles, n_prot), cgrid(std::min(n_tiles, 64u), n_prot);
     if (with_lan) {
-      hipLaunchKernelGGL(k_backup_lan, grid, dim3(256), 0, s, a, la);
+      hipLaunchKernelGGL(k_backup_lan, grid, dim3(256), 0, s, a, BackupProt<FrrProt::Lan>{la, (lfa_flags & HSPF_LFA_LAN_SAFE_REPAIRS) ? 1u : 0u, 0u});
       hipLaunchKernelGGL(k_backup_cov_lan, cgrid, dim3(256), 0, s, a);
     } else if (with_srlg) {
-      hipLaunchKernelGGL(k_backup_srlg, grid, dim3(256), 0, s, a, b);
+      hipLaunchKernelGGL(k_backup_srlg, grid, dim3(256), 0, s, a, BackupProt<FrrProt::Srlg>{b});
       hipLaunchKernelGGL(k_backup_cov_srlg, cgrid, dim3(256), 0, s, a);
     } else {
       hipLaunchKernelGGL(k_backup, grid, dim3(256), 0, s, a);

@@ -115,8 +115,8 @@ __device__ __forceinline__ bool frr_all_primaries(const FrrTab &t, const uint64_
 //   <Family>Lane<P>   what a lane keeps for the mode next to the body's own state (empty for Plain), with the mode's conditions
 //                     as members where they are more than a line;
 // selected with `if constexpr`: an instantiation holds nothing of another mode.  The Srlg specialisations stand in spf_srlg.hip.h,
-// next to the member block they read, and the Srlg kernels are instantiated there.  (Folded so far: lfa_body in spf_lfa.hip.h and
-// k_backup_cov_t in spf_backup.hip.h; k_backup_srlg is still its own body, see spf_backup_srlg.hip.h.)
+// next to the member block they read, and the Srlg kernels are instantiated there.  (Folded: lfa_body in spf_lfa.hip.h, backup_body and
+// k_backup_cov_t in spf_backup.hip.h, backup_ecmp_fill_body in spf_backup_ecmp.hip.h.)
 enum class FrrProt { Plain, Lan, Srlg };
 
 // the LAN block of the call (both NULL in a call without one), and the view of one protected root over it
