@@ -1,12 +1,17 @@
-// spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h): hspf_lfa_candidates, hspf_lfa_device, hspf_lfa_ecmp_device,
-// hspf_csr_transpose, hspf_rlfa_device, hspf_rlfa_lan_device, hspf_tilfa_device, hspf_routes_backup_device, hspf_routes_backup_ecmp_device, hspf_rlfa_node_select_device,
-// hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device, hspf_routes_backup_node_device, the broadcast-link calls hspf_lfa_lan_candidates, hspf_lfa_lan_device, hspf_routes_backup_lan_device,
-// and the shared-risk calls hspf_srlg_members, hspf_lfa_srlg_device, hspf_rlfa_srlg_device, hspf_routes_backup_srlg_device.
-// Included by spf_capi.hip (one TU).
+// spf_frr.hip.h — host side of the fast-reroute calls of the C ABI (include/holo_spf_hip.h).  Included by spf_capi.hip (one TU).
+//   host arithmetic:       hspf_lfa_candidates, hspf_lfa_lan_candidates, hspf_csr_transpose, hspf_srlg_members
+//   alternates:            hspf_lfa_device, hspf_lfa_lan_device, hspf_lfa_srlg_device (lfa_call); hspf_lfa_ecmp_device (lfa_ecmp_call)
+//   remote alternates:     hspf_rlfa_device, hspf_rlfa_lan_device, hspf_rlfa_srlg_device (rlfa_call)
+//   two-segment repairs:   hspf_tilfa_device
+//   per-prefix backups:    hspf_routes_backup_device, hspf_routes_backup_lan_device, hspf_routes_backup_srlg_device (routes_backup);
+//                          hspf_routes_backup_ecmp_device, hspf_routes_backup_ecmp_srlg_device (backup_ecmp_call)
+//   node protection:       hspf_rlfa_node_select_device, hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device,
+//                          hspf_routes_backup_node_device
 //
-// The device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and
-// one frame: argument checks, lfa_stage, k_lfa_gather where the kernels need the per-root scalars, the call's own kernels,
-// frr_finish.  `fn` names the calling entry point in hspf_last_error.
+// The 18 device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and one
+// frame, FrrCall: its checks, stage(), the call's memsets, gather() where the kernels need the per-root scalars, the call's own
+// kernels, finish().  A call that leaves any other way drains the stream in the frame's destructor.  `fn` names the calling entry
+// point in hspf_last_error.
 #pragma once
 
 #include <unordered_map>
@@ -26,20 +31,8 @@ namespace {
 
 int frr_bad(hspf_ctx *ctx, const char *fn, const std::string &what) { ctx->last_error = std::string(fn) + ": " + what; return HSPF_E_INVAL; }
 
-int frr_check_dims(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, uint32_t n_prot) {
-  if (n_vertices == 0 || n_rows == 0 || n_mask_words == 0 || n_prot == 0 || n_prot > 65535u || n_mask_words > (1u << 20))
-    return frr_bad(ctx, fn, "n_vertices, n_rows, n_mask_words or n_prot out of range");
-  return HSPF_OK;
-}
-
-int frr_check_graph(hspf_ctx *ctx, const char *fn, const hspf_graph *g, uint32_t n_vertices) {
-  if (g->invalid) return frr_bad(ctx, fn, "the graph is invalid after a failed hspf_graph_patch (free it and upload again)");
-  if (g->n != n_vertices) return frr_bad(ctx, fn, "n_vertices is not the graph's");
-  return HSPF_OK;
-}
-
 // The checks of the protected roots, and the staged block (its layout: spf_frr_common.hip.h) copied to ctx->lfa_tab on the context's
-// stream, with ctx->lfa_scal sized for k_lfa_gather.  `tab` is the copy's source: it lives until the caller has synchronised.
+// stream, with ctx->lfa_scal sized for k_lfa_gather.  `tab` is the copy's source: the frame's (FrrCall), which outlives the copy.
 int lfa_stage(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const hspf_lfa_protect *prot,
                      uint32_t n_prot, std::vector<uint32_t> &tab, uint32_t *out_max_k) {
   auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
@@ -87,21 +80,6 @@ int lfa_stage(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_row
   return HSPF_OK;
 }
 
-// k_lfa_gather on the staged block: d(N_k, S) and d(N_k, N_p) of every protected root.  Returns the arguments it launched with
-// (hspf_lfa_device goes on with them).
-LfaArgs frr_gather(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words, uint32_t lfa_flags, const uint32_t *dist_dev,
-                   const uint16_t *flags_dev, const uint64_t *mask_dev, uint32_t n_prot, uint32_t max_k) {
-  LfaArgs a{};
-  a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
-  a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev;
-  a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (uint32_t *)ctx->lfa_scal.p;
-  if (max_k) {
-    const uint32_t gx = (uint32_t)std::min<size_t>(((size_t)max_k * ((size_t)max_k + 1) + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_lfa_gather, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a);
-  }
-  return a;
-}
-
 // The LAN columns of a LAN call, checked: before anything is staged or launched.
 int lan_check(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const hspf_lfa_protect *prot,
               const hspf_lfa_lan *lan, uint32_t n_prot) {
@@ -120,7 +98,7 @@ int lan_check(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_row
 }
 
 // The LAN block (its layout: spf_frr_common.hip.h) copied to ctx->lan_tab on the context's stream, with ctx->lan_scal sized for
-// k_lfa_gather_lan.  After lan_check and lfa_stage.  `ltab` is the copy's source: it lives until the caller has synchronised.
+// k_lfa_gather_lan.  After lan_check and lfa_stage.  `ltab` is the copy's source: the frame's.
 int lan_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, std::vector<uint32_t> &ltab,
               LanArgs *out, size_t *out_max_gather) {
   ltab.assign((size_t)n_prot * LAN_HDR_WORDS, 0u);
@@ -159,20 +137,6 @@ int lan_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, const
   return HSPF_OK;
 }
 
-// k_lfa_gather_lan on the two staged blocks: what frr_gather leaves, and d(N_k, L) of every protected root
-LfaArgs frr_gather_lan(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_mask_words, uint32_t lfa_flags, const uint32_t *dist_dev,
-                       const uint16_t *flags_dev, const uint64_t *mask_dev, uint32_t n_prot, size_t max_gather, const LanArgs &la) {
-  LfaArgs a{};
-  a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
-  a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev;
-  a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (uint32_t *)ctx->lfa_scal.p;
-  if (max_gather) {
-    const uint32_t gx = (uint32_t)std::min<size_t>((max_gather + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_lfa_gather_lan, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a, la);
-  }
-  return a;
-}
-
 static_assert(SRLG_MAXM == HSPF_SRLG_MAX_MEMBERS && RLFA_SRLG_CW == HSPF_RLFA_SRLG_COUNT_WORDS, "the kernels' member bound and count width are the header's");
 
 // The member columns of an SRLG call, checked: before anything is staged or launched.  Every index a kernel dereferences is held
@@ -201,7 +165,7 @@ int srlg_check(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_ro
 }
 
 // The member block (its layout: spf_srlg.hip.h; behind its six member columns a seventh, pos [NM], that only k_backup_srlg reads)
-// copied to ctx->srlg_tab on the context's stream, with ctx->srlg_scal sized for k_srlg_gather.  After srlg_check and lfa_stage.  `stab` is the copy's source: it lives until the caller has synchronised.
+// copied to ctx->srlg_tab on the context's stream, with ctx->srlg_scal sized for k_srlg_gather.  After srlg_check and lfa_stage.  `stab` is the copy's source: the frame's.
 int srlg_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, std::vector<uint32_t> &stab,
                SrlgArgs *out, size_t *out_max_gather, uint32_t *out_max_nms) {
   stab.assign((size_t)n_prot * SRLG_HDR_WORDS, 0u);
@@ -257,16 +221,9 @@ int srlg_stage(hspf_ctx *ctx, const char *fn, const hspf_lfa_protect *prot, cons
   return HSPF_OK;
 }
 
-// k_srlg_gather on the staged blocks, behind frr_gather
-void srlg_gather(hspf_ctx *ctx, const LfaArgs &a, const SrlgArgs &sa, uint32_t n_prot, size_t max_gather) {
-  if (!max_gather) return;
-  const uint32_t gx = (uint32_t)std::min<size_t>((max_gather + 255) / 256, 1024);
-  hipLaunchKernelGGL(k_srlg_gather, dim3(gx, n_prot), dim3(256), 0, ctx->stream, a, sa);
-}
-
 // The graph's two-way flags, one byte per link in the order of the device's raw CSR, copied to ctx->tilfa_tw on the context's stream
-// (hspf_tilfa_device, hspf_tilfa_node_select_device).  The host mirror's pool is in that order unless a patch moved rows; then `tw`
-// is the copy's source: it lives until the caller has synchronised.
+// (hspf_tilfa_device, hspf_tilfa_node_select_device).  The host mirror's pool is in that order unless a patch moved rows; then `tw`,
+// the frame's, is the copy's source.
 int tw_stage(hspf_ctx *ctx, const char *fn, const hspf_graph *g, std::vector<uint8_t> &tw) {
   auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
   const uint32_t e = g->e;
@@ -285,15 +242,6 @@ int tw_stage(hspf_ctx *ctx, const char *fn, const hspf_graph *g, std::vector<uin
     tw_src = tw.data();
   } else if (g->twoway.size() < e) return bad("the graph's host mirror and its link count disagree");
   if (e) HIPCHK(ctx, hipMemcpyAsync(ctx->tilfa_tw.p, tw_src, e, hipMemcpyHostToDevice, ctx->stream));
-  return HSPF_OK;
-}
-
-// the end of a call: a launch error is reported under the name of its kernels; then the stream is drained
-int frr_finish(hspf_ctx *ctx, const char *kernels) {
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) { ctx->last_error = std::string(kernels) + ": " + hipGetErrorString(le); return HSPF_E_HIP; }
-  hipStream_t s = ctx->stream;
-  HIPCHK(ctx, hipStreamSynchronize(s));
   return HSPF_OK;
 }
 
@@ -344,6 +292,198 @@ int lfa_walk(const hspf_csr *csr, uint32_t root, uint32_t *out_total_slots, F &&
 static_assert(bk_cov_words(FrrProt::Plain) == HSPF_BK_COVERAGE_WORDS && bk_cov_words(FrrProt::Lan) == HSPF_BK_LAN_COVERAGE_WORDS &&
               bk_cov_words(FrrProt::Srlg) == HSPF_BK_SRLG_COVERAGE_WORDS, "the coverage kernel's widths are the header's");
 
+// ---- the frame of a device call ----------------------------------------------------------------------------------------------
+// One FrrCall per call, declared inside the guarded() lambda.  It holds the call's common arguments, the shared checks, and every
+// host block whose copy to the device the call enqueues (the candidate tables, the LAN or member block, the two-way bytes) with
+// what staging them yields for the launches.  A call reads top to bottom: checks -> stage -> memsets -> arguments -> launches ->
+// finish().  Every other way out behind the first enqueue — a return, a HIPCHK, an exception on its way to guarded() — passes
+// the destructor, which drains the stream: no copy is left reading a block of the frame, or of the caller, that is gone.
+struct FrrCall {
+  hspf_ctx *const ctx; const char *const fn;
+  const uint32_t n, R, W;                               // n_vertices, n_rows, n_mask_words
+  const uint32_t *const dist; const uint16_t *const flags; const uint64_t *const mask;
+  const hspf_lfa_protect *const prot; const uint32_t n_prot;
+  size_t stride = 0, n_slots = 0;                       // 64 * W, n_prot * stride (check_slots)
+  std::vector<uint32_t> tab, mtab;                      // sources of the staged copies: the candidate tables, the LAN or member block
+  std::vector<uint8_t> tw;                              // the same: the two-way bytes where a patch moved rows
+  uint32_t max_k = 0, max_nms = 0;
+  size_t max_gather = 0;
+  LanArgs la{};
+  SrlgArgs sa{};
+  uint32_t tiles_x = 0; size_t n_tiles = 0; uint32_t *d_total = nullptr;      // the CSR stream of the ECMP calls (stream_open)
+  uint32_t *ymap = nullptr; uint32_t n_yrows = 0;       // the listed nodes' vertex -> row map (node_map)
+  bool enqueued = false, finished = false;
+
+  FrrCall(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev,
+          const uint16_t *flags_dev, const uint64_t *mask_dev, const hspf_lfa_protect *prot, uint32_t n_prot)
+      : ctx(ctx), fn(fn), n(n_vertices), R(n_rows), W(n_mask_words), dist(dist_dev), flags(flags_dev), mask(mask_dev), prot(prot), n_prot(n_prot) {}
+  FrrCall(const FrrCall &) = delete;
+  ~FrrCall() { if (enqueued && !finished) (void)hipStreamSynchronize(ctx->stream); }
+
+  // -- checks: nothing is staged, written or launched before the last of them
+  int bad(const std::string &what) const { return frr_bad(ctx, fn, what); }
+  // the tables, prot and out; `more`: the call's further pointers, which `what` names with them
+  int check_ptrs(const void *out, bool more = true, const char *what = "NULL table, prot or out pointer") const {
+    return (!more || !dist || !flags || !mask || !prot || !out) ? bad(what) : HSPF_OK;
+  }
+  int check_dims() const {
+    if (n == 0 || R == 0 || W == 0 || n_prot == 0 || n_prot > 65535u || W > (1u << 20)) return bad("n_vertices, n_rows, n_mask_words or n_prot out of range");
+    return HSPF_OK;
+  }
+  int check_graph(const hspf_graph *g) const {
+    if (g->invalid) return bad("the graph is invalid after a failed hspf_graph_patch (free it and upload again)");
+    return g->n != n ? bad("n_vertices is not the graph's") : HSPF_OK;
+  }
+  int check_twoway(const hspf_graph *g) const { return g->twoway.size() != g->col.size() ? bad("the graph holds no two-way flags") : HSPF_OK; }
+  int check_slots() {                                   // after check_dims
+    stride = (size_t)64 * W; n_slots = (size_t)n_prot * stride;
+    return n_slots > (1u << 28) ? bad("n_prot * 64 * n_mask_words out of range") : HSPF_OK;
+  }
+  int check_routes(const hspf_routes *r) const {
+    return (!r->best_metric || !r->best_entry || !r->nexthop_mask) ? bad("NULL best_metric / best_entry / nexthop_mask") : HSPF_OK;
+  }
+  int check_prefix_table(const hspf_prefix_table *t) const {      // (the entries: stage_prefix_table)
+    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
+    return (t->flags & HSPF_PFX_ORDERED) ? bad("HSPF_PFX_ORDERED tables are out of scope") : HSPF_OK;
+  }
+  int check_tilfa(FrrProt mode, const hspf_tilfa_out *ti) const {
+    const bool srlg = mode == FrrProt::Srlg;            // its repairs are walked: the forced adjacency is read too
+    if (ti && (!ti->ti_kind || !ti->ti_via || !ti->ti_metric || (srlg && (!ti->ti_p || !ti->ti_link))))
+      return bad(srlg ? "NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev" : "NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    return HSPF_OK;
+  }
+  // a selection struct and its list length; `where`: "" for the call that writes it, " in sel_dev" ... for one that reads it
+  int check_rn_sel(const hspf_rlfa_node_sel *q, uint32_t max_pq, const char *where) const {
+    if (!q->nq_node || !q->nq_via || !q->nq_metric || !q->nq_count) return bad(std::string("NULL nq_node / nq_via / nq_metric / nq_count") + where);
+    return (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) ? bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ") : HSPF_OK;
+  }
+  int check_tn_sel(const hspf_tilfa_node_sel *q, uint32_t max_pairs, const char *where) const {
+    if (!q->tq_q || !q->tq_p || !q->tq_link || !q->tq_via || !q->tq_metric || !q->tq_count)
+      return bad(std::string("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count") + where);
+    return (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) ? bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS") : HSPF_OK;
+  }
+  int check_y_roots(const uint32_t *y_roots, uint32_t n_y) const {      // after check_dims
+    if (n_y == 0) return bad("n_yrows is 0");
+    for (uint32_t i = 0; i < n_y; ++i)
+      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
+    return HSPF_OK;
+  }
+  // the mode's columns (`lan` is read in the mode Lan alone, `srlg` in the mode Srlg alone; so in stage)
+  int check_mode(FrrProt mode, const hspf_lfa_lan *lan, const hspf_srlg *srlg) const {
+    if (mode == FrrProt::Lan) return lan_check(ctx, fn, n, R, W, prot, lan, n_prot);
+    return mode == FrrProt::Srlg ? srlg_check(ctx, fn, n, R, W, prot, srlg, n_prot) : HSPF_OK;
+  }
+  // the entries an ECMP call can emit, bounded: its ptr array is u32, the scan's carry too (`items`: what n_items counts)
+  int check_pairs(uint32_t n_items, const char *items) const {
+    uint64_t pairs = 0;
+    for (uint32_t i = 0; i < n_prot; ++i) pairs += (uint64_t)n_items * std::max(prot[i].n_slots, 1u);
+    return pairs >= (1ull << 32) ? bad(std::string(items) + " * max(n_slots, 1), summed over the protected roots, reaches 2^32: split the protect list") : HSPF_OK;
+  }
+
+  // -- staging: from here on the stream may hold copies out of this frame
+  hipStream_t stream() { enqueued = true; return ctx->stream; }
+  int stage_prefix_table(const hspf_prefix_table *t) { enqueued = true; return pfx_table_stage(ctx, fn, n, t); }
+  // lfa_stage (with the checks of the protected roots), then the mode's block.  After check_mode.
+  int stage(FrrProt mode, const hspf_lfa_lan *lan, const hspf_srlg *srlg) {
+    enqueued = true;
+    int rc;
+    if ((rc = lfa_stage(ctx, fn, n, R, W, prot, n_prot, tab, &max_k))) return rc;
+    if (mode == FrrProt::Lan) return lan_stage(ctx, fn, prot, lan, n_prot, mtab, &la, &max_gather);
+    return mode == FrrProt::Srlg ? srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms) : HSPF_OK;
+  }
+  int stage_twoway(const hspf_graph *g) { enqueued = true; return tw_stage(ctx, fn, g, tw); }
+  // The vertex -> row map of the listed nodes (after check_y_roots): ctx->rnode_map sized and cleared, the list copied behind it
+  // (the caller's: it lives through the call).  launch_node_map() fills the map; a frame's own memsets may stand between the two.
+  int node_map(const uint32_t *y_roots, uint32_t n_y) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->rnode_map, ((size_t)n + n_y) * 4, false))) return rc;
+    hipStream_t s = stream();
+    ymap = (uint32_t *)ctx->rnode_map.p; n_yrows = n_y;
+    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n * 4, s));
+    HIPCHK(ctx, hipMemcpyAsync(ymap + n, y_roots, (size_t)n_y * 4, hipMemcpyHostToDevice, s));
+    return HSPF_OK;
+  }
+  void launch_node_map() {
+    RnodeDestArgs m{};                                  // k_rlfa_nmap reads n, the root list and the map
+    m.n = n; m.yroots = ymap + n; m.n_yrows = n_yrows; m.ymap = ymap;
+    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, ctx->stream, m);
+  }
+
+  // -- launches
+  // The gather of the mode on the staged blocks: d(N_k, S) and d(N_k, N_p) of every protected root (k_lfa_gather), in the mode Lan
+  // with d(N_k, L) (k_lfa_gather_lan), in the mode Srlg followed by the members' distances (k_srlg_gather).  Returns the arguments
+  // it launched with (lfa_call goes on with them).
+  LfaArgs gather(FrrProt mode, uint32_t lfa_flags) {
+    LfaArgs a{};
+    a.n = n; a.W = W; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u;
+    a.dist = dist; a.flags = flags; a.mask = mask;
+    a.tab = (const uint32_t *)ctx->lfa_tab.p; a.scal = (uint32_t *)ctx->lfa_scal.p;
+    auto grid = [&](size_t work) { return dim3((uint32_t)std::min<size_t>((work + 255) / 256, 1024), n_prot); };
+    if (mode == FrrProt::Lan) {
+      if (max_gather) hipLaunchKernelGGL(k_lfa_gather_lan, grid(max_gather), dim3(256), 0, ctx->stream, a, la);
+    } else if (max_k) {
+      hipLaunchKernelGGL(k_lfa_gather, grid((size_t)max_k * ((size_t)max_k + 1)), dim3(256), 0, ctx->stream, a);
+    }
+    if (mode == FrrProt::Srlg && max_gather) hipLaunchKernelGGL(k_srlg_gather, grid(max_gather), dim3(256), 0, ctx->stream, a, sa);
+    return a;
+  }
+  // The CSR stream of the ECMP calls, before anything is staged: the tile scratch of n_items per protected root and the pinned word
+  // the total arrives in (h_ev[1]: word 0 is the event stream's).  After check_pairs.
+  int stream_open(uint32_t n_items) {
+    (void)hipSetDevice(ctx->device);
+    tiles_x = (n_items + LFA_TILE - 1) / LFA_TILE; n_tiles = (size_t)tiles_x * n_prot;
+    int rc;
+    if ((rc = ensure(ctx, ctx->ea_scr, (n_tiles + 4) * 4, false))) return rc;
+    if (!ctx->h_ev) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ev, 64, hipHostMallocDefault));
+    HIPCHK(ctx, hipHostGetDevicePointer((void **)&d_total, ctx->h_ev, 0));
+    ++d_total;
+    return HSPF_OK;
+  }
+  uint32_t *tile() const { return (uint32_t *)ctx->ea_scr.p; }
+  // ... and its end: count(grid) -> k_events_scan -> fill(grid), ONE synchronisation, the total
+  template <class Count, class Fill>
+  int stream_close(Count &&count, Fill &&fill, const char *kernels, uint64_t *out_total) {
+    const dim3 grid(tiles_x, n_prot);
+    count(grid);
+    hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(1024), 0, ctx->stream, (uint32_t)n_tiles, tile(), tile() + n_tiles, d_total);
+    fill(grid);
+    int rc;
+    if ((rc = finish(kernels))) return rc;
+    *out_total = ctx->h_ev[1];
+    return HSPF_OK;
+  }
+  // The end of a call: a launch error is reported under the name of its kernels (nullptr: nothing was launched); then the stream
+  // is drained.
+  int finish(const char *kernels) {
+    const hipError_t le = kernels ? hipGetLastError() : hipSuccess;
+    if (le != hipSuccess) { ctx->last_error = std::string(kernels) + ": " + hipGetErrorString(le); return HSPF_E_HIP; }
+    finished = true;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return HSPF_OK;
+  }
+};
+
+// What the per-prefix backup kernels of both families read: the table set, the staged tables and scalars, the staged prefix table,
+// the routes, the repairs of tilfa_dev; in `b` what the mode Srlg adds (the member block, the forced adjacency, the repairs flag).
+// The outputs are the caller's to fill in.
+BackupArgs backup_args(const FrrCall &f, const LfaArgs &ga, uint32_t lfa_flags, const hspf_prefix_table *t, const hspf_routes *routes_dev,
+                       const hspf_tilfa_out *tilfa_dev, BackupSrlgArgs *b) {
+  BackupArgs a{};
+  a.n = f.n; a.W = f.W; a.ignore_overload = ga.ignore_overload; a.stride = 64u * f.W;
+  a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
+  a.dist = f.dist; a.flags = f.flags;
+  a.tab = ga.tab; a.scal = ga.scal;
+  a.pfx_ptr = (const uint32_t *)f.ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)f.ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)f.ctx->pf_met.p;
+  a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
+  *b = BackupSrlgArgs{};
+  b->sa = f.sa; b->repairs = (lfa_flags & HSPF_LFA_SRLG_SAFE_REPAIRS) ? 1u : 0u;
+  if (tilfa_dev) {
+    a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric;
+    b->ti_p = tilfa_dev->ti_p; b->ti_link = tilfa_dev->ti_link;
+  }
+  return a;
+}
+
 // The one frame of hspf_routes_backup_device, hspf_routes_backup_lan_device and hspf_routes_backup_srlg_device: `lan` is read in
 // the mode Lan alone, `srlg` in the mode Srlg alone.
 int routes_backup(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
@@ -352,71 +492,34 @@ int routes_backup(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertic
                   const hspf_prefix_table *t, const hspf_routes *routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const bool with_lan = mode == FrrProt::Lan, with_srlg = mode == FrrProt::Srlg;
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
-    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
-    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
-      return bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
-    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric || (with_srlg && (!tilfa_dev->ti_p || !tilfa_dev->ti_link))))
-      return bad(with_srlg ? "NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev" : "NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    FrrCall f(ctx, fn, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
-    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
-    if (with_srlg && (rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
-    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
-    std::vector<uint32_t> tab, mtab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0, max_nms = 0;
-    size_t max_gather = 0;
-    LanArgs la{};
-    SrlgArgs sa{};
-    hipStream_t s = ctx->stream;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
-        (with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, mtab, &la, &max_gather))) ||
-        (with_srlg && (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms)))) {
-      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
-      return rc;
-    }
-    const uint32_t coverage_words = with_lan ? HSPF_BK_LAN_COVERAGE_WORDS : with_srlg ? HSPF_BK_SRLG_COVERAGE_WORDS : HSPF_BK_COVERAGE_WORDS;
-    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * coverage_words * 4, s));
-    if (!t->n_prefixes) {                               // nothing to launch
-      HIPCHK(ctx, hipStreamSynchronize(s));
-      return HSPF_OK;
-    }
-    const LfaArgs ga = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
-                                : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    if (with_srlg) srlg_gather(ctx, ga, sa, n_prot, max_gather);
-    BackupArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = 64u * n_mask_words;
-    a.n_pfx = t->n_prefixes; a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
-    a.dist = dist_dev; a.flags = flags_dev;
-    a.tab = ga.tab; a.scal = ga.scal;
-    a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
-    a.best_metric = routes_dev->best_metric; a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
-    BackupSrlgArgs b{};
-    b.sa = sa; b.repairs = (lfa_flags & HSPF_LFA_SRLG_SAFE_REPAIRS) ? 1u : 0u;
-    if (tilfa_dev) {
-      a.ti_kind = tilfa_dev->ti_kind; a.ti_via = tilfa_dev->ti_via; a.ti_metric = tilfa_dev->ti_metric;
-      b.ti_p = tilfa_dev->ti_p; b.ti_link = tilfa_dev->ti_link;
-    }
+    if ((rc = f.check_ptrs(out_dev, t && routes_dev, "NULL table, prot, prefix table, routes or out pointer")) || (rc = f.check_routes(routes_dev))) return rc;
+    if (!out_dev->bk_kind || !out_dev->bk_primary || !out_dev->bk_slot || !out_dev->bk_metric || !out_dev->bk_flags || !out_dev->bk_coverage)
+      return f.bad("NULL bk_kind / bk_primary / bk_slot / bk_metric / bk_flags / bk_coverage");
+    if ((rc = f.check_tilfa(mode, tilfa_dev)) || (rc = f.check_dims()) || (rc = f.check_prefix_table(t)) || (rc = f.check_slots()) ||
+        (rc = f.check_mode(mode, lan, srlg)) || (rc = f.stage_prefix_table(t)) || (rc = f.stage(mode, lan, srlg))) return rc;
+    hipStream_t s = f.stream();
+    HIPCHK(ctx, hipMemsetAsync(out_dev->bk_coverage, 0, (size_t)n_prot * bk_cov_words(mode) * 4, s));
+    if (!t->n_prefixes) return f.finish(nullptr);       // nothing to launch
+    const LfaArgs ga = f.gather(mode, lfa_flags);
+    BackupSrlgArgs b;
+    BackupArgs a = backup_args(f, ga, lfa_flags, t, routes_dev, tilfa_dev, &b);
     a.bk_kind = out_dev->bk_kind; a.bk_primary = out_dev->bk_primary; a.bk_slot = out_dev->bk_slot; a.bk_metric = out_dev->bk_metric;
     a.bk_flags = out_dev->bk_flags; a.cand_mask = out_dev->bk_cand_mask; a.node_mask = out_dev->bk_node_mask; a.coverage = out_dev->bk_coverage;
     const uint32_t n_tiles = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
     const dim3 grid(n_tiles, n_prot), cgrid(std::min(n_tiles, 64u), n_prot);
-    if (with_lan) {
-      hipLaunchKernelGGL(k_backup_lan, grid, dim3(256), 0, s, a, BackupProt<FrrProt::Lan>{la, (lfa_flags & HSPF_LFA_LAN_SAFE_REPAIRS) ? 1u : 0u, 0u});
+    if (mode == FrrProt::Lan) {
+      hipLaunchKernelGGL(k_backup_lan, grid, dim3(256), 0, s, a, BackupProt<FrrProt::Lan>{f.la, (lfa_flags & HSPF_LFA_LAN_SAFE_REPAIRS) ? 1u : 0u, 0u});
       hipLaunchKernelGGL(k_backup_cov_lan, cgrid, dim3(256), 0, s, a);
-    } else if (with_srlg) {
+    } else if (mode == FrrProt::Srlg) {
       hipLaunchKernelGGL(k_backup_srlg, grid, dim3(256), 0, s, a, BackupProt<FrrProt::Srlg>{b});
       hipLaunchKernelGGL(k_backup_cov_srlg, cgrid, dim3(256), 0, s, a);
     } else {
       hipLaunchKernelGGL(k_backup, grid, dim3(256), 0, s, a);
       hipLaunchKernelGGL(k_backup_cov, cgrid, dim3(256), 0, s, a);
     }
-    return frr_finish(ctx, with_lan ? "k_backup_lan" : with_srlg ? "k_backup_srlg" : "k_backup");
+    return f.finish(mode == FrrProt::Lan ? "k_backup_lan" : mode == FrrProt::Srlg ? "k_backup_srlg" : "k_backup");
   });
 }
 
@@ -426,95 +529,62 @@ int lfa_call(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, u
              const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, hspf_lfa_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const bool with_lan = mode == FrrProt::Lan, with_srlg = mode == FrrProt::Srlg;
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    FrrCall f(ctx, fn, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
-    if (with_srlg && (rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
-    std::vector<uint32_t> tab, mtab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0, max_nms = 0;
-    size_t max_gather = 0;
-    LanArgs la{};
-    SrlgArgs sa{};
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, mtab, &la, &max_gather))) ||
-        (with_srlg && (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms)))) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      return rc;
-    }
-    const uint32_t coverage_words = with_lan ? HSPF_LFA_LAN_COVERAGE_WORDS : with_srlg ? HSPF_LFA_SRLG_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
+    if ((rc = f.check_ptrs(out_dev))) return rc;
+    if (!out_dev->alt_slot || !out_dev->alt_metric || !out_dev->alt_flags || !out_dev->coverage) return f.bad("NULL alt_slot / alt_metric / alt_flags / coverage");
+    if ((rc = f.check_dims()) || (rc = f.check_mode(mode, lan, srlg)) || (rc = f.stage(mode, lan, srlg))) return rc;
+    hipStream_t s = f.stream();
+    const uint32_t coverage_words = mode == FrrProt::Lan ? HSPF_LFA_LAN_COVERAGE_WORDS : mode == FrrProt::Srlg ? HSPF_LFA_SRLG_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
     HIPCHK(ctx, hipMemsetAsync(out_dev->coverage, 0, (size_t)n_prot * coverage_words * 4, s));
-    LfaArgs a = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
-                         : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    if (with_srlg) srlg_gather(ctx, a, sa, n_prot, max_gather);
+    LfaArgs a = f.gather(mode, lfa_flags);
     a.alt_slot = out_dev->alt_slot; a.alt_metric = out_dev->alt_metric; a.alt_flags = out_dev->alt_flags;
     a.cand_mask = out_dev->cand_mask; a.node_mask = out_dev->node_mask; a.coverage = out_dev->coverage;
     const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot);
-    const bool one = max_k <= 64;                       // every root's slots fit one mask word: the tables go to LDS
-    if (with_lan) {
-      if (one) hipLaunchKernelGGL(k_lfa_lan<true>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Lan>{la});
-      else hipLaunchKernelGGL(k_lfa_lan<false>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Lan>{la});
-    } else if (with_srlg) {
-      if (one) hipLaunchKernelGGL(k_lfa_srlg<true>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Srlg>{sa});
-      else hipLaunchKernelGGL(k_lfa_srlg<false>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Srlg>{sa});
+    const bool one = f.max_k <= 64;                     // every root's slots fit one mask word: the tables go to LDS
+    if (mode == FrrProt::Lan) {
+      if (one) hipLaunchKernelGGL(k_lfa_lan<true>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Lan>{f.la});
+      else hipLaunchKernelGGL(k_lfa_lan<false>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Lan>{f.la});
+    } else if (mode == FrrProt::Srlg) {
+      if (one) hipLaunchKernelGGL(k_lfa_srlg<true>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Srlg>{f.sa});
+      else hipLaunchKernelGGL(k_lfa_srlg<false>, grid, dim3(256), 0, s, a, LfaProt<FrrProt::Srlg>{f.sa});
     } else {
       if (one) hipLaunchKernelGGL(k_lfa<true>, grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL(k_lfa<false>, grid, dim3(256), 0, s, a);
     }
-    return frr_finish(ctx, with_lan ? "k_lfa_lan" : with_srlg ? "k_lfa_srlg" : "k_lfa");
+    return f.finish(mode == FrrProt::Lan ? "k_lfa_lan" : mode == FrrProt::Srlg ? "k_lfa_srlg" : "k_lfa");
   });
 }
 
 static_assert(EA_CW == HSPF_LFA_ECMP_COVERAGE_WORDS && HSPF_LFA_EA_PRIMARY == 0x20u, "the fill kernel's coverage width and primary bit are the header's");
 
-// The frame of hspf_lfa_ecmp_device (kernels: spf_lfa_ecmp.hip.h): the checks and the staging of lfa_call, then count -> scan -> fill
-// on the context's stream and ONE synchronisation.  The total arrives in the pinned word k_events_scan stores (h_ev[1]: word 0 is
-// the event stream's).
+// The frame of hspf_lfa_ecmp_device (kernels: spf_lfa_ecmp.hip.h): the checks and the staging of lfa_call, then the frame's CSR stream
 int lfa_ecmp_call(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                   const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                   const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, uint64_t cap_entries, hspf_lfa_ecmp_out *out_dev,
                   uint64_t *out_total) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!out_dev->ea_ptr || !out_total) return bad("NULL ea_ptr or out_total");
-    if (cap_entries && (!out_dev->ea_primary || !out_dev->ea_slot || !out_dev->ea_metric || !out_dev->ea_flags || !out_dev->ea_coverage))
-      return bad("NULL ea_primary / ea_slot / ea_metric / ea_flags / ea_coverage with cap_entries > 0");
+    FrrCall f(ctx, fn, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    uint64_t pairs = 0;                                 // an upper bound of the entries: ea_ptr is u32, the scan's carry too
-    for (uint32_t i = 0; i < n_prot; ++i) pairs += (uint64_t)n_vertices * std::max(prot[i].n_slots, 1u);
-    if (pairs >= (1ull << 32)) return bad("n_vertices * max(n_slots, 1), summed over the protected roots, reaches 2^32: split the protect list");
-    (void)hipSetDevice(ctx->device);
-    const uint32_t tiles_x = (n_vertices + LFA_TILE - 1) / LFA_TILE;
-    const size_t n_tiles = (size_t)tiles_x * n_prot;
-    if ((rc = ensure(ctx, ctx->ea_scr, (n_tiles + 4) * 4, false))) return rc;
-    if (!ctx->h_ev) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ev, 64, hipHostMallocDefault));
-    uint32_t *d_hev = nullptr;
-    HIPCHK(ctx, hipHostGetDevicePointer((void **)&d_hev, ctx->h_ev, 0));
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
+    if ((rc = f.check_ptrs(out_dev))) return rc;
+    if (!out_dev->ea_ptr || !out_total) return f.bad("NULL ea_ptr or out_total");
+    if (cap_entries && (!out_dev->ea_primary || !out_dev->ea_slot || !out_dev->ea_metric || !out_dev->ea_flags || !out_dev->ea_coverage))
+      return f.bad("NULL ea_primary / ea_slot / ea_metric / ea_flags / ea_coverage with cap_entries > 0");
+    if ((rc = f.check_dims()) || (rc = f.check_pairs(n_vertices, "n_vertices")) || (rc = f.stream_open(n_vertices)) ||
+        (rc = f.stage(FrrProt::Plain, nullptr, nullptr))) return rc;
+    hipStream_t s = f.stream();
     if (out_dev->ea_coverage) HIPCHK(ctx, hipMemsetAsync(out_dev->ea_coverage, 0, (size_t)n_prot * HSPF_LFA_ECMP_COVERAGE_WORDS * 4, s));
     LfaEcmpArgs a{};
-    a.l = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    a.n_prot = n_prot; a.cap = cap_entries; a.tile = (uint32_t *)ctx->ea_scr.p;
+    a.l = f.gather(FrrProt::Plain, lfa_flags);
+    a.n_prot = n_prot; a.cap = cap_entries; a.tile = f.tile();
     a.ea_ptr = out_dev->ea_ptr; a.ea_primary = out_dev->ea_primary; a.ea_slot = out_dev->ea_slot; a.ea_metric = out_dev->ea_metric;
     a.ea_flags = out_dev->ea_flags; a.ea_coverage = out_dev->ea_coverage;
-    const dim3 grid(tiles_x, n_prot);
-    hipLaunchKernelGGL(k_lfa_ecmp_count, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(1024), 0, s, (uint32_t)n_tiles, a.tile, a.tile + n_tiles, d_hev + 1);
-    if (max_k <= 64) hipLaunchKernelGGL(k_lfa_ecmp_fill<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_lfa_ecmp_fill<false>, grid, dim3(256), 0, s, a);
-    if ((rc = frr_finish(ctx, "k_lfa_ecmp"))) return rc;
-    *out_total = ctx->h_ev[1];
-    return HSPF_OK;
+    return f.stream_close([&](dim3 grid) { hipLaunchKernelGGL(k_lfa_ecmp_count, grid, dim3(256), 0, s, a); },
+                          [&](dim3 grid) {
+                            if (f.max_k <= 64) hipLaunchKernelGGL(k_lfa_ecmp_fill<true>, grid, dim3(256), 0, s, a);
+                            else hipLaunchKernelGGL(k_lfa_ecmp_fill<false>, grid, dim3(256), 0, s, a);
+                          }, "k_lfa_ecmp", out_total);
   });
 }
 
@@ -522,8 +592,8 @@ static_assert(be_cov_words(FrrProt::Plain) == HSPF_BK_ECMP_COVERAGE_WORDS && be_
               "the fill kernel's coverage widths are the header's");
 
 // The one frame of hspf_routes_backup_ecmp_device and hspf_routes_backup_ecmp_srlg_device (kernels: spf_backup_ecmp.hip.h; `srlg`
-// is read in the mode Srlg alone): the checks and the staging of routes_backup in the same mode, then count -> scan -> fill on the
-// context's stream and ONE synchronisation, as lfa_ecmp_call (the same scratch and the same pinned word).
+// is read in the mode Srlg alone): the checks, the staging and the arguments of routes_backup in the same mode, then the frame's
+// CSR stream as lfa_ecmp_call (the same scratch and the same pinned word).
 int backup_ecmp_call(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                      const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags, const hspf_prefix_table *t,
@@ -531,134 +601,87 @@ int backup_ecmp_call(hspf_ctx *ctx, const char *fn, FrrProt mode, uint32_t n_ver
                      uint64_t *out_total) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
-    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
-    const bool with_srlg = mode == FrrProt::Srlg;
-    if (!out_dev->eb_ptr || !out_total) return bad("NULL eb_ptr or out_total");
-    if (cap_entries && (!out_dev->eb_primary || !out_dev->eb_kind || !out_dev->eb_slot || !out_dev->eb_metric || !out_dev->eb_flags || !out_dev->eb_coverage))
-      return bad("NULL eb_primary / eb_kind / eb_slot / eb_metric / eb_flags / eb_coverage with cap_entries > 0");
-    if (tilfa_dev && (!tilfa_dev->ti_kind || !tilfa_dev->ti_via || !tilfa_dev->ti_metric || (with_srlg && (!tilfa_dev->ti_p || !tilfa_dev->ti_link))))
-      return bad(with_srlg ? "NULL ti_kind / ti_via / ti_metric / ti_p / ti_link in tilfa_dev" : "NULL ti_kind / ti_via / ti_metric in tilfa_dev");
+    FrrCall f(ctx, fn, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
-    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    uint64_t pairs = 0;                                 // an upper bound of the entries: eb_ptr is u32, the scan's carry too
-    for (uint32_t i = 0; i < n_prot; ++i) pairs += (uint64_t)t->n_prefixes * std::max(prot[i].n_slots, 1u);
-    if (pairs >= (1ull << 32)) return bad("n_prefixes * max(n_slots, 1), summed over the protected roots, reaches 2^32: split the protect list");
-    if (with_srlg && (rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
-    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
-    (void)hipSetDevice(ctx->device);
-    const uint32_t tiles_x = (t->n_prefixes + LFA_TILE - 1) / LFA_TILE;
-    const size_t n_tiles = (size_t)tiles_x * n_prot;
-    if ((rc = ensure(ctx, ctx->ea_scr, (n_tiles + 4) * 4, false))) return rc;
-    if (!ctx->h_ev) HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ev, 64, hipHostMallocDefault));
-    uint32_t *d_hev = nullptr;
-    HIPCHK(ctx, hipHostGetDevicePointer((void **)&d_hev, ctx->h_ev, 0));
-    std::vector<uint32_t> tab, mtab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0, max_nms = 0;
-    size_t max_gather = 0;
-    SrlgArgs sa{};
-    hipStream_t s = ctx->stream;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
-        (with_srlg && (rc = srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms)))) {
-      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
-      return rc;
-    }
-    const uint32_t coverage_words = with_srlg ? HSPF_BK_ECMP_SRLG_COVERAGE_WORDS : HSPF_BK_ECMP_COVERAGE_WORDS;
-    if (out_dev->eb_coverage) HIPCHK(ctx, hipMemsetAsync(out_dev->eb_coverage, 0, (size_t)n_prot * coverage_words * 4, s));
+    if ((rc = f.check_ptrs(out_dev, t && routes_dev, "NULL table, prot, prefix table, routes or out pointer")) || (rc = f.check_routes(routes_dev))) return rc;
+    if (!out_dev->eb_ptr || !out_total) return f.bad("NULL eb_ptr or out_total");
+    if (cap_entries && (!out_dev->eb_primary || !out_dev->eb_kind || !out_dev->eb_slot || !out_dev->eb_metric || !out_dev->eb_flags || !out_dev->eb_coverage))
+      return f.bad("NULL eb_primary / eb_kind / eb_slot / eb_metric / eb_flags / eb_coverage with cap_entries > 0");
+    if ((rc = f.check_tilfa(mode, tilfa_dev)) || (rc = f.check_dims()) || (rc = f.check_prefix_table(t)) || (rc = f.check_slots()) ||
+        (rc = f.check_pairs(t->n_prefixes, "n_prefixes")) || (rc = f.check_mode(mode, nullptr, srlg)) || (rc = f.stage_prefix_table(t)) ||
+        (rc = f.stream_open(t->n_prefixes)) || (rc = f.stage(mode, nullptr, srlg))) return rc;
+    hipStream_t s = f.stream();
+    if (out_dev->eb_coverage) HIPCHK(ctx, hipMemsetAsync(out_dev->eb_coverage, 0, (size_t)n_prot * be_cov_words(mode) * 4, s));
     if (!t->n_prefixes) {                               // nothing to launch: the one word of eb_ptr
       HIPCHK(ctx, hipMemsetAsync(out_dev->eb_ptr, 0, 4, s));
-      HIPCHK(ctx, hipStreamSynchronize(s));
+      if ((rc = f.finish(nullptr))) return rc;
       *out_total = 0;
       return HSPF_OK;
     }
-    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    if (with_srlg) srlg_gather(ctx, ga, sa, n_prot, max_gather);
+    const LfaArgs ga = f.gather(mode, lfa_flags);
     BackupEcmpArgs a{};
-    a.b.n = n_vertices; a.b.W = n_mask_words; a.b.ignore_overload = ga.ignore_overload; a.b.stride = 64u * n_mask_words;
-    a.b.n_pfx = t->n_prefixes; a.b.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u;
-    a.b.dist = dist_dev; a.b.flags = flags_dev;
-    a.b.tab = ga.tab; a.b.scal = ga.scal;
-    a.b.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.b.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.b.pfx_metric = (const uint32_t *)ctx->pf_met.p;
-    a.b.best_metric = routes_dev->best_metric; a.b.best_entry = routes_dev->best_entry; a.b.nh_mask = routes_dev->nexthop_mask;
     BackupEcmpProt<FrrProt::Srlg> pa{};
-    pa.s.sa = sa; pa.s.repairs = (lfa_flags & HSPF_LFA_SRLG_SAFE_REPAIRS) ? 1u : 0u;
-    if (tilfa_dev) {
-      a.b.ti_kind = tilfa_dev->ti_kind; a.b.ti_via = tilfa_dev->ti_via; a.b.ti_metric = tilfa_dev->ti_metric;
-      pa.s.ti_p = tilfa_dev->ti_p; pa.s.ti_link = tilfa_dev->ti_link;
-    }
-    a.n_prot = n_prot; a.cap = cap_entries; a.tile = (uint32_t *)ctx->ea_scr.p;
+    a.b = backup_args(f, ga, lfa_flags, t, routes_dev, tilfa_dev, &pa.s);
+    a.n_prot = n_prot; a.cap = cap_entries; a.tile = f.tile();
     a.eb_ptr = out_dev->eb_ptr; a.eb_primary = out_dev->eb_primary; a.eb_kind = out_dev->eb_kind; a.eb_slot = out_dev->eb_slot;
     a.eb_metric = out_dev->eb_metric; a.eb_flags = out_dev->eb_flags; a.eb_coverage = out_dev->eb_coverage;
-    const dim3 grid(tiles_x, n_prot);
-    hipLaunchKernelGGL(k_backup_ecmp_count, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(1024), 0, s, (uint32_t)n_tiles, a.tile, a.tile + n_tiles, d_hev + 1);
-    if (with_srlg) hipLaunchKernelGGL(k_backup_ecmp_fill_srlg, grid, dim3(256), 0, s, a, pa);
-    else hipLaunchKernelGGL(k_backup_ecmp_fill, grid, dim3(256), 0, s, a);
-    if ((rc = frr_finish(ctx, with_srlg ? "k_backup_ecmp_srlg" : "k_backup_ecmp"))) return rc;
-    *out_total = ctx->h_ev[1];
-    return HSPF_OK;
+    return f.stream_close([&](dim3 grid) { hipLaunchKernelGGL(k_backup_ecmp_count, grid, dim3(256), 0, s, a); },
+                          [&](dim3 grid) {
+                            if (mode == FrrProt::Srlg) hipLaunchKernelGGL(k_backup_ecmp_fill_srlg, grid, dim3(256), 0, s, a, pa);
+                            else hipLaunchKernelGGL(k_backup_ecmp_fill, grid, dim3(256), 0, s, a);
+                          }, mode == FrrProt::Srlg ? "k_backup_ecmp_srlg" : "k_backup_ecmp", out_total);
   });
 }
 
 static_assert(RLFA_CW == HSPF_RLFA_COUNT_WORDS && RLFA_LAN_CW == HSPF_RLFA_LAN_COUNT_WORDS, "the kernels' count widths are the header's");
 
-// the one frame of hspf_rlfa_device (with_lan false, `lan` unread) and hspf_rlfa_lan_device
-int rlfa_call(hspf_ctx *ctx, const char *fn, bool with_lan, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+// The one frame of hspf_rlfa_device, hspf_rlfa_lan_device and hspf_rlfa_srlg_device (`lan`, `srlg`: as routes_backup)
+int rlfa_call(hspf_ctx *ctx, const char *fn, FrrProt mode, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
               const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
-              const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
-              hspf_rlfa_out *out_dev) {
+              const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
+              const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
-    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
-      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
+    FrrCall f(ctx, fn, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
-    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
-    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if (with_lan && (rc = lan_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, lan, n_prot))) return rc;
-    std::vector<uint32_t> tab, ltab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0;
-    size_t max_gather = 0;
-    LanArgs la{};
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((with_lan && (rc = lan_stage(ctx, fn, prot, lan, n_prot, ltab, &la, &max_gather))) || (rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      return rc;
-    }
-    const uint32_t count_words = with_lan ? HSPF_RLFA_LAN_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS;
-    const uint32_t coverage_words = with_lan ? HSPF_RLFA_LAN_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
-    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * count_words * 4, s));
+    if ((rc = f.check_ptrs(out_dev, g && rdist_dev, "NULL graph, table, prot or out pointer"))) return rc;
+    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
+      return f.bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
+    if ((rc = f.check_dims()) || (rc = f.check_graph(g)) || (rc = f.check_slots()) || (rc = f.check_mode(mode, lan, srlg)) ||
+        (rc = f.stage(mode, lan, srlg)) || (rc = ensure(ctx, ctx->rlfa_key, f.n_slots * 8, false))) return rc;
+    hipStream_t s = f.stream();
+    const bool with_lan = mode == FrrProt::Lan, with_srlg = mode == FrrProt::Srlg;
+    const uint32_t count_words = with_lan ? HSPF_RLFA_LAN_COUNT_WORDS : with_srlg ? HSPF_RLFA_SRLG_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS;
+    const uint32_t coverage_words = with_lan ? HSPF_RLFA_LAN_COVERAGE_WORDS : with_srlg ? HSPF_RLFA_SRLG_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
+    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, f.n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, f.n_slots * count_words * 4, s));
     HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * coverage_words * 4, s));
-    const LfaArgs ga = with_lan ? frr_gather_lan(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_gather, la)
-                                : frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
+    const LfaArgs ga = f.gather(mode, lfa_flags);
     RlfaArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)stride;
+    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)f.stride;
     a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
     a.tab = ga.tab; a.scal = ga.scal;
     a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
     a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
     a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
     a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
-    const dim3 grid((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), fgrid((uint32_t)((n_slots + 255) / 256));
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    const dim3 grid(n_tiles, n_prot), fgrid((uint32_t)((f.n_slots + 255) / 256));
     if (with_lan) {
-      hipLaunchKernelGGL(k_rlfa_lan, grid, dim3(256), 0, s, a, RlfaLan<true>{la});
-      hipLaunchKernelGGL(k_rlfa_final_lan, fgrid, dim3(256), 0, s, a, n_prot, RlfaLan<true>{la});
-      hipLaunchKernelGGL(k_rlfa_dest_lan, grid, dim3(256), 0, s, a, RlfaLan<true>{la});
+      hipLaunchKernelGGL(k_rlfa_lan, grid, dim3(256), 0, s, a, RlfaLan<true>{f.la});
+      hipLaunchKernelGGL(k_rlfa_final_lan, fgrid, dim3(256), 0, s, a, n_prot, RlfaLan<true>{f.la});
+      hipLaunchKernelGGL(k_rlfa_dest_lan, grid, dim3(256), 0, s, a, RlfaLan<true>{f.la});
+    } else if (with_srlg) {
+      hipLaunchKernelGGL(k_rlfa_srlg, grid, dim3(256), 0, s, a, f.sa);
+      if (f.max_nms) hipLaunchKernelGGL(k_rlfa_srlg_slot, dim3(n_tiles, std::min(f.max_nms, 65535u), n_prot), dim3(256), 0, s, a, f.sa);
+      hipLaunchKernelGGL(k_rlfa_srlg_final, fgrid, dim3(256), 0, s, a, n_prot, f.sa);
+      hipLaunchKernelGGL(k_rlfa_srlg_dest, grid, dim3(256), 0, s, a, f.sa);
     } else {
       hipLaunchKernelGGL(k_rlfa, grid, dim3(256), 0, s, a, RlfaLan<false>{});
       hipLaunchKernelGGL(k_rlfa_final, fgrid, dim3(256), 0, s, a, n_prot, RlfaLan<false>{});
       hipLaunchKernelGGL(k_rlfa_dest, grid, dim3(256), 0, s, a, RlfaLan<false>{});
     }
-    return frr_finish(ctx, with_lan ? "k_rlfa_lan" : "k_rlfa");
+    return f.finish(with_lan ? "k_rlfa_lan" : with_srlg ? "k_rlfa_srlg" : "k_rlfa");
   });
 }
 
@@ -740,16 +763,16 @@ int hspf_rlfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, ui
                      const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                      const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                      hspf_rlfa_out *out_dev) {
-  return rlfa_call(ctx, "hspf_rlfa_device", false, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, nullptr, n_prot,
-                   lfa_flags, alt_flags_in_dev, out_dev);
+  return rlfa_call(ctx, "hspf_rlfa_device", FrrProt::Plain, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, nullptr,
+                   nullptr, n_prot, lfa_flags, alt_flags_in_dev, out_dev);
 }
 
 int hspf_rlfa_lan_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
                          const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                          const hspf_lfa_protect *prot, const hspf_lfa_lan *lan, uint32_t n_prot, uint32_t lfa_flags,
                          const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev) {
-  return rlfa_call(ctx, "hspf_rlfa_lan_device", true, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, lan, n_prot,
-                   lfa_flags, alt_flags_in_dev, out_dev);
+  return rlfa_call(ctx, "hspf_rlfa_lan_device", FrrProt::Lan, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, lan,
+                   nullptr, n_prot, lfa_flags, alt_flags_in_dev, out_dev);
 }
 
 // ---- shared-risk link groups (include/holo_spf_hip.h "SRLG-safe alternates and remote-LFA spaces"; kernels: spf_srlg.hip.h) ----
@@ -834,50 +857,8 @@ int hspf_rlfa_srlg_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertice
                           const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                           const hspf_lfa_protect *prot, const hspf_srlg *srlg, uint32_t n_prot, uint32_t lfa_flags,
                           const uint8_t *alt_flags_in_dev, hspf_rlfa_out *out_dev) {
-  if (!ctx) return HSPF_E_INVAL;
-  return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_rlfa_srlg_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
-    if (!out_dev->pq_node || !out_dev->pq_via || !out_dev->pq_metric || !out_dev->pq_counts || !out_dev->rl_node || !out_dev->rl_via || !out_dev->rl_coverage)
-      return bad("NULL pq_node / pq_via / pq_metric / pq_counts / rl_node / rl_via / rl_coverage");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
-    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
-    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if ((rc = srlg_check(ctx, fn, n_vertices, n_rows, n_mask_words, prot, srlg, n_prot))) return rc;
-    std::vector<uint32_t> tab, stab;                    // (live until the synchronisation at the end: the copies read them)
-    uint32_t max_k = 0, max_nms = 0;
-    size_t max_gather = 0;
-    SrlgArgs sa{};
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = srlg_stage(ctx, fn, prot, srlg, n_prot, stab, &sa, &max_gather, &max_nms)) || (rc = ensure(ctx, ctx->rlfa_key, n_slots * 8, false))) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      return rc;
-    }
-    HIPCHK(ctx, hipMemsetAsync(ctx->rlfa_key.p, 0xFF, n_slots * 8, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->pq_counts, 0, n_slots * HSPF_RLFA_SRLG_COUNT_WORDS * 4, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->rl_coverage, 0, (size_t)n_prot * HSPF_RLFA_SRLG_COVERAGE_WORDS * 4, s));
-    const LfaArgs ga = frr_gather(ctx, n_vertices, n_mask_words, lfa_flags, dist_dev, flags_dev, mask_dev, n_prot, max_k);
-    srlg_gather(ctx, ga, sa, n_prot, max_gather);
-    RlfaArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.ignore_overload = ga.ignore_overload; a.stride = (uint32_t)stride;
-    a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev; a.vf = (const uint8_t *)g->d_vflags;
-    a.tab = ga.tab; a.scal = ga.scal;
-    a.alt_in = alt_flags_in_dev; a.key = (unsigned long long *)ctx->rlfa_key.p;
-    a.pq_node = out_dev->pq_node; a.pq_via = out_dev->pq_via; a.pq_metric = out_dev->pq_metric; a.pq_counts = out_dev->pq_counts;
-    a.space_flags = out_dev->space_flags; a.space_via = out_dev->space_via;
-    a.rl_node = out_dev->rl_node; a.rl_via = out_dev->rl_via; a.rl_cov = out_dev->rl_coverage;
-    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
-    const dim3 grid(n_tiles, n_prot), fgrid((uint32_t)((n_slots + 255) / 256));
-    hipLaunchKernelGGL(k_rlfa_srlg, grid, dim3(256), 0, s, a, sa);
-    if (max_nms) hipLaunchKernelGGL(k_rlfa_srlg_slot, dim3(n_tiles, std::min(max_nms, 65535u), n_prot), dim3(256), 0, s, a, sa);
-    hipLaunchKernelGGL(k_rlfa_srlg_final, fgrid, dim3(256), 0, s, a, n_prot, sa);
-    hipLaunchKernelGGL(k_rlfa_srlg_dest, grid, dim3(256), 0, s, a, sa);
-    return frr_finish(ctx, "k_rlfa_srlg");
-  });
+  return rlfa_call(ctx, "hspf_rlfa_srlg_device", FrrProt::Srlg, g, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, prot, nullptr,
+                   srlg, n_prot, lfa_flags, alt_flags_in_dev, out_dev);
 }
 
 // ---- per-prefix backups with shared-risk link groups (include/holo_spf_hip.h "per-prefix SRLG-safe backups"; kernels: spf_backup_srlg.hip.h) ----
@@ -908,32 +889,23 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
   if (!ctx) return HSPF_E_INVAL;
   (void)lfa_flags;                                      // (eligibility and the overload rule are in the space tables)
   return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_tilfa_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!g || !dist_dev || !flags_dev || !mask_dev || !rdist_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
-    if (!space_flags_dev || !space_via_dev) return bad("NULL space_flags / space_via (the tables of hspf_rlfa_device are required)");
+    FrrCall f(ctx, "hspf_tilfa_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
+    int rc;
+    if ((rc = f.check_ptrs(out_dev, g && rdist_dev, "NULL graph, table, prot or out pointer"))) return rc;
+    if (!space_flags_dev || !space_via_dev) return f.bad("NULL space_flags / space_via (the tables of hspf_rlfa_device are required)");
     if (!out_dev->ti_kind || !out_dev->ti_p || !out_dev->ti_q || !out_dev->ti_via || !out_dev->ti_link || !out_dev->ti_metric || !out_dev->ti_counts ||
         !out_dev->td_kind || !out_dev->td_coverage)
-      return bad("NULL ti_kind / ti_p / ti_q / ti_via / ti_link / ti_metric / ti_counts / td_kind / td_coverage");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
-    if (n_vertices > 0x7FFFFFFFu) return bad("n_vertices does not fit the selection key");
-    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
-    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if (g->twoway.size() != g->col.size()) return bad("the graph holds no two-way flags");
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    std::vector<uint8_t> tw;                            // (the same)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    if ((rc = ensure(ctx, ctx->tilfa_key, n_slots * 8, false))) return rc;
-    if ((rc = tw_stage(ctx, fn, g, tw))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(ctx->tilfa_key.p, 0xFF, n_slots * 8, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->ti_counts, 0, n_slots * HSPF_TILFA_COUNT_WORDS * 4, s));
+      return f.bad("NULL ti_kind / ti_p / ti_q / ti_via / ti_link / ti_metric / ti_counts / td_kind / td_coverage");
+    if ((rc = f.check_dims()) || (rc = f.check_graph(g))) return rc;
+    if (n_vertices > 0x7FFFFFFFu) return f.bad("n_vertices does not fit the selection key");
+    if ((rc = f.check_slots()) || (rc = f.check_twoway(g)) || (rc = f.stage(FrrProt::Plain, nullptr, nullptr)) ||
+        (rc = ensure(ctx, ctx->tilfa_key, f.n_slots * 8, false)) || (rc = f.stage_twoway(g))) return rc;
+    hipStream_t s = f.stream();
+    HIPCHK(ctx, hipMemsetAsync(ctx->tilfa_key.p, 0xFF, f.n_slots * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->ti_counts, 0, f.n_slots * HSPF_TILFA_COUNT_WORDS * 4, s));
     HIPCHK(ctx, hipMemsetAsync(out_dev->td_coverage, 0, (size_t)n_prot * HSPF_TILFA_COVERAGE_WORDS * 4, s));
     TilfaArgs a{};
-    a.n = n_vertices; a.W = n_mask_words; a.stride = (uint32_t)stride;
+    a.n = n_vertices; a.W = n_mask_words; a.stride = (uint32_t)f.stride;
     a.dist = dist_dev; a.rdist = rdist_dev; a.flags = flags_dev; a.mask = mask_dev;
     a.tab = (const uint32_t *)ctx->lfa_tab.p; a.alt_in = alt_flags_in_dev;
     a.sflags = space_flags_dev; a.svia = space_via_dev;
@@ -942,10 +914,10 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
     a.ti_kind = out_dev->ti_kind; a.ti_p = out_dev->ti_p; a.ti_q = out_dev->ti_q; a.ti_via = out_dev->ti_via; a.ti_link = out_dev->ti_link;
     a.ti_metric = out_dev->ti_metric; a.ti_counts = out_dev->ti_counts; a.td_kind = out_dev->td_kind; a.td_cov = out_dev->td_coverage;
     const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
-    if (max_k) hipLaunchKernelGGL(k_tilfa, dim3(n_tiles, std::min(max_k, 65535u), n_prot), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_tilfa_final, dim3((uint32_t)((n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
+    if (f.max_k) hipLaunchKernelGGL(k_tilfa, dim3(n_tiles, std::min(f.max_k, 65535u), n_prot), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_tilfa_final, dim3((uint32_t)((f.n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
     hipLaunchKernelGGL(k_tilfa_dest, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_tilfa");
+    return f.finish("k_tilfa");
   });
 }
 
@@ -984,34 +956,26 @@ int hspf_rlfa_node_select_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_
                                  uint32_t max_pq, hspf_rlfa_node_sel *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_rlfa_node_select_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!space_flags_dev) return bad("NULL space_flags (the table of hspf_rlfa_device is required)");
-    if (!out_dev->nq_node || !out_dev->nq_via || !out_dev->nq_metric || !out_dev->nq_count) return bad("NULL nq_node / nq_via / nq_metric / nq_count");
-    if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) return bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
+    FrrCall f(ctx, "hspf_rlfa_node_select_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
-    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    if ((rc = f.check_ptrs(out_dev))) return rc;
+    if (!space_flags_dev) return f.bad("NULL space_flags (the table of hspf_rlfa_device is required)");
+    if ((rc = f.check_rn_sel(out_dev, max_pq, "")) || (rc = f.check_dims()) || (rc = f.check_slots()) || (rc = f.stage(FrrProt::Plain, nullptr, nullptr))) return rc;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE, max_k = f.max_k;
     const size_t part_keys = (size_t)n_prot * max_k * n_tiles * max_pq;      // one list per workgroup
-    if (part_keys > ((size_t)1 << 30)) { ctx->last_error = std::string(fn) + ": the partial lists of this call need more than 8 GiB of scratch"; return HSPF_E_NOMEM; }
+    if (part_keys > ((size_t)1 << 30)) { ctx->last_error = std::string(f.fn) + ": the partial lists of this call need more than 8 GiB of scratch"; return HSPF_E_NOMEM; }
     if ((rc = ensure(ctx, ctx->rnode_part, std::max<size_t>(part_keys, 1) * 8, false))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(out_dev->nq_count, 0, n_slots * 4, s));
+    hipStream_t s = f.stream();
+    HIPCHK(ctx, hipMemsetAsync(out_dev->nq_count, 0, f.n_slots * 4, s));
     RnodeSelArgs a{};
-    a.n = n_vertices; a.stride = (uint32_t)stride; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u; a.max_pq = max_pq;
+    a.n = n_vertices; a.stride = (uint32_t)f.stride; a.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u; a.max_pq = max_pq;
     a.max_k = max_k; a.n_tiles = n_tiles;
     a.dist = dist_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p; a.sflags = space_flags_dev;
     a.part = (unsigned long long *)ctx->rnode_part.p;
     a.nq_node = out_dev->nq_node; a.nq_via = out_dev->nq_via; a.nq_metric = out_dev->nq_metric; a.nq_count = out_dev->nq_count;
     if (max_k) hipLaunchKernelGGL(k_rlfa_nsel, dim3(n_tiles, std::min(max_k, 65535u), n_prot), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_rlfa_nsel_final, dim3((uint32_t)stride, n_prot), dim3(64), 0, s, a);
-    return frr_finish(ctx, "k_rlfa_nsel");
+    hipLaunchKernelGGL(k_rlfa_nsel_final, dim3((uint32_t)f.stride, n_prot), dim3(64), 0, s, a);
+    return f.finish("k_rlfa_nsel");
   });
 }
 
@@ -1023,40 +987,28 @@ int hspf_rlfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, u
                           const uint8_t *alt_flags_in_dev, hspf_rlfa_node_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_rlfa_node_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!ydist_dev || !y_roots || !sel_dev) return bad("NULL ydist, y_roots or sel pointer");
-    if (!sel_dev->nq_node || !sel_dev->nq_via || !sel_dev->nq_metric || !sel_dev->nq_count) return bad("NULL nq_node / nq_via / nq_metric / nq_count in sel_dev");
-    if (!out_dev->nd_kind || !out_dev->nd_node || !out_dev->nd_via || !out_dev->nd_metric || !out_dev->nd_coverage)
-      return bad("NULL nd_kind / nd_node / nd_via / nd_metric / nd_coverage");
-    if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) return bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
-    if (n_yrows == 0) return bad("n_yrows is 0");
+    FrrCall f(ctx, "hspf_rlfa_node_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    for (uint32_t i = 0; i < n_yrows; ++i)
-      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n_vertices) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    if ((rc = ensure(ctx, ctx->rnode_map, ((size_t)n_vertices + n_yrows) * 4, false))) return rc;
-    hipStream_t s = ctx->stream;
-    uint32_t *ymap = (uint32_t *)ctx->rnode_map.p, *yroots = ymap + n_vertices;
-    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n_vertices * 4, s));
-    HIPCHK(ctx, hipMemcpyAsync(yroots, y_roots, (size_t)n_yrows * 4, hipMemcpyHostToDevice, s));      // (the caller's: it lives through the call)
+    if ((rc = f.check_ptrs(out_dev))) return rc;
+    if (!ydist_dev || !y_roots || !sel_dev) return f.bad("NULL ydist, y_roots or sel pointer");
+    if ((rc = f.check_rn_sel(sel_dev, max_pq, " in sel_dev"))) return rc;
+    if (!out_dev->nd_kind || !out_dev->nd_node || !out_dev->nd_via || !out_dev->nd_metric || !out_dev->nd_coverage)
+      return f.bad("NULL nd_kind / nd_node / nd_via / nd_metric / nd_coverage");
+    if ((rc = f.check_dims()) || (rc = f.check_slots()) || (rc = f.check_y_roots(y_roots, n_yrows)) || (rc = f.stage(FrrProt::Plain, nullptr, nullptr)) ||
+        (rc = f.node_map(y_roots, n_yrows))) return rc;
+    hipStream_t s = f.stream();
     HIPCHK(ctx, hipMemsetAsync(out_dev->nd_coverage, 0, (size_t)n_prot * HSPF_NP_COVERAGE_WORDS * 4, s));
     RnodeDestArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.stride = 64u * n_mask_words; a.max_pq = max_pq;
     a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p;
-    a.ydist = ydist_dev; a.yroots = yroots; a.n_yrows = n_yrows; a.ymap = ymap;
+    a.ydist = ydist_dev; a.yroots = f.ymap + n_vertices; a.n_yrows = n_yrows; a.ymap = f.ymap;
     a.nq_node = sel_dev->nq_node; a.nq_via = sel_dev->nq_via; a.nq_metric = sel_dev->nq_metric; a.nq_count = sel_dev->nq_count;
     a.alt_in = alt_flags_in_dev;
     a.nd_kind = out_dev->nd_kind; a.nd_node = out_dev->nd_node; a.nd_via = out_dev->nd_via; a.nd_metric = out_dev->nd_metric;
     a.nd_set = out_dev->nd_set; a.nd_cov = out_dev->nd_coverage;
-    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, a);
+    f.launch_node_map();
     hipLaunchKernelGGL(k_rlfa_ndest, dim3((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_rlfa_ndest");
+    return f.finish("k_rlfa_ndest");
   });
 }
 
@@ -1070,41 +1022,26 @@ int hspf_tilfa_node_select_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n
                                   uint32_t max_pairs, hspf_tilfa_node_sel *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_tilfa_node_select_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!g || !dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL graph, table, prot or out pointer");
-    if (!space_flags_dev) return bad("NULL space_flags (the table of hspf_rlfa_device is required)");
-    if (!out_dev->tq_q || !out_dev->tq_p || !out_dev->tq_link || !out_dev->tq_via || !out_dev->tq_metric || !out_dev->tq_count)
-      return bad("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count");
-    if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) return bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
+    FrrCall f(ctx, "hspf_tilfa_node_select_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((rc = frr_check_graph(ctx, fn, g, n_vertices))) return rc;
-    const size_t stride = (size_t)64 * n_mask_words, n_slots = (size_t)n_prot * stride;
-    if (n_slots > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    if (g->twoway.size() != g->col.size()) return bad("the graph holds no two-way flags");
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    std::vector<uint8_t> tw;                            // (the same)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    if ((rc = f.check_ptrs(out_dev, g, "NULL graph, table, prot or out pointer"))) return rc;
+    if (!space_flags_dev) return f.bad("NULL space_flags (the table of hspf_rlfa_device is required)");
+    if ((rc = f.check_tn_sel(out_dev, max_pairs, "")) || (rc = f.check_dims()) || (rc = f.check_graph(g)) || (rc = f.check_slots()) ||
+        (rc = f.check_twoway(g)) || (rc = f.stage(FrrProt::Plain, nullptr, nullptr))) return rc;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE, max_k = f.max_k;
     const size_t cells = (size_t)n_prot * max_k * n_vertices;                  // one per (root, candidate, vertex): not tiled
     const size_t part_keys = (size_t)n_prot * max_k * n_tiles * max_pairs;     // one list per workgroup
     if (cells > ((size_t)1 << 30)) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      ctx->last_error = std::string(fn) + ": the cells of this call (8 bytes x slots x n_vertices per protected root) need more than 8 GiB of scratch: split prot";
+      ctx->last_error = std::string(f.fn) + ": the cells of this call (8 bytes x slots x n_vertices per protected root) need more than 8 GiB of scratch: split prot";
       return HSPF_E_NOMEM;
     }
     if ((rc = ensure(ctx, ctx->tnode_cell, std::max<size_t>(cells, 1) * 8, false)) ||
-        (rc = ensure(ctx, ctx->rnode_part, std::max<size_t>(part_keys, 1) * 8, false)) || (rc = tw_stage(ctx, fn, g, tw))) {
-      (void)hipStreamSynchronize(s);
-      return rc;
-    }
+        (rc = ensure(ctx, ctx->rnode_part, std::max<size_t>(part_keys, 1) * 8, false)) || (rc = f.stage_twoway(g))) return rc;
+    hipStream_t s = f.stream();
     HIPCHK(ctx, hipMemsetAsync(ctx->tnode_cell.p, 0xFF, std::max<size_t>(cells, 1) * 8, s));
-    HIPCHK(ctx, hipMemsetAsync(out_dev->tq_count, 0, n_slots * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->tq_count, 0, f.n_slots * 4, s));
     TnSelArgs a{};
-    a.r.n = n_vertices; a.r.stride = (uint32_t)stride; a.r.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u; a.r.max_pq = max_pairs;
+    a.r.n = n_vertices; a.r.stride = (uint32_t)f.stride; a.r.ignore_overload = (lfa_flags & HSPF_LFA_IGNORE_OVERLOAD) ? 1u : 0u; a.r.max_pq = max_pairs;
     a.r.max_k = max_k; a.r.n_tiles = n_tiles;
     a.r.dist = dist_dev; a.r.tab = (const uint32_t *)ctx->lfa_tab.p; a.r.sflags = space_flags_dev;
     a.r.part = (unsigned long long *)ctx->rnode_part.p;
@@ -1117,8 +1054,8 @@ int hspf_tilfa_node_select_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n
       hipLaunchKernelGGL(k_tn_link, grid, dim3(256), 0, s, a);
       hipLaunchKernelGGL(k_tn_sel, grid, dim3(256), 0, s, a);
     }
-    hipLaunchKernelGGL(k_tn_sel_final, dim3((uint32_t)stride, n_prot), dim3(64), 0, s, a);
-    return frr_finish(ctx, "k_tn_link");
+    hipLaunchKernelGGL(k_tn_sel_final, dim3((uint32_t)f.stride, n_prot), dim3(64), 0, s, a);
+    return f.finish("k_tn_link");
   });
 }
 
@@ -1130,47 +1067,29 @@ int hspf_tilfa_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t n_rows, 
                            const uint8_t *alt_flags_in_dev, const uint8_t *nd_kind_in_dev, hspf_tilfa_node_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_tilfa_node_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !out_dev) return bad("NULL table, prot or out pointer");
-    if (!ydist_dev || !y_roots || !sel_dev) return bad("NULL ydist, y_roots or sel pointer");
-    if (!sel_dev->tq_q || !sel_dev->tq_p || !sel_dev->tq_link || !sel_dev->tq_via || !sel_dev->tq_metric || !sel_dev->tq_count)
-      return bad("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count in sel_dev");
-    if (!out_dev->tn_kind || !out_dev->tn_p || !out_dev->tn_q || !out_dev->tn_link || !out_dev->tn_via || !out_dev->tn_metric || !out_dev->tn_coverage)
-      return bad("NULL tn_kind / tn_p / tn_q / tn_link / tn_via / tn_metric / tn_coverage");
-    if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) return bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
-    if (n_yrows == 0) return bad("n_yrows is 0");
+    FrrCall f(ctx, "hspf_tilfa_node_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
     int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    for (uint32_t i = 0; i < n_yrows; ++i)
-      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n_vertices) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = ensure(ctx, ctx->rnode_map, ((size_t)n_vertices + n_yrows) * 4, false))) {
-      (void)hipStreamSynchronize(s);                    // (lfa_stage's copy reads `tab`)
-      return rc;
-    }
-    uint32_t *ymap = (uint32_t *)ctx->rnode_map.p, *yroots = ymap + n_vertices;
-    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n_vertices * 4, s));
-    HIPCHK(ctx, hipMemcpyAsync(yroots, y_roots, (size_t)n_yrows * 4, hipMemcpyHostToDevice, s));      // (the caller's: it lives through the call)
+    if ((rc = f.check_ptrs(out_dev))) return rc;
+    if (!ydist_dev || !y_roots || !sel_dev) return f.bad("NULL ydist, y_roots or sel pointer");
+    if ((rc = f.check_tn_sel(sel_dev, max_pairs, " in sel_dev"))) return rc;
+    if (!out_dev->tn_kind || !out_dev->tn_p || !out_dev->tn_q || !out_dev->tn_link || !out_dev->tn_via || !out_dev->tn_metric || !out_dev->tn_coverage)
+      return f.bad("NULL tn_kind / tn_p / tn_q / tn_link / tn_via / tn_metric / tn_coverage");
+    if ((rc = f.check_dims()) || (rc = f.check_slots()) || (rc = f.check_y_roots(y_roots, n_yrows)) || (rc = f.stage(FrrProt::Plain, nullptr, nullptr)) ||
+        (rc = f.node_map(y_roots, n_yrows))) return rc;
+    hipStream_t s = f.stream();
     HIPCHK(ctx, hipMemsetAsync(out_dev->tn_coverage, 0, (size_t)n_prot * HSPF_TN_COVERAGE_WORDS * 4, s));
-    RnodeDestArgs m{};                                  // k_rlfa_nmap reads n, the root list and the map
-    m.n = n_vertices; m.yroots = yroots; m.n_yrows = n_yrows; m.ymap = ymap;
     TnDestArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.stride = 64u * n_mask_words; a.max_pairs = max_pairs;
     a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p;
-    a.ydist = ydist_dev; a.ymap = ymap;
+    a.ydist = ydist_dev; a.ymap = f.ymap;
     a.tq_q = sel_dev->tq_q; a.tq_p = sel_dev->tq_p; a.tq_link = sel_dev->tq_link; a.tq_via = sel_dev->tq_via; a.tq_metric = sel_dev->tq_metric;
     a.tq_count = sel_dev->tq_count;
     a.alt_in = alt_flags_in_dev; a.nd_in = nd_kind_in_dev;
     a.tn_kind = out_dev->tn_kind; a.tn_p = out_dev->tn_p; a.tn_q = out_dev->tn_q; a.tn_link = out_dev->tn_link; a.tn_via = out_dev->tn_via;
     a.tn_metric = out_dev->tn_metric; a.tn_set = out_dev->tn_set; a.tn_cov = out_dev->tn_coverage;
-    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, m);
+    f.launch_node_map();
     hipLaunchKernelGGL(k_tn_dest, dim3((n_vertices + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_tn_dest");
+    return f.finish("k_tn_dest");
   });
 }
 
@@ -1190,60 +1109,30 @@ int hspf_routes_backup_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
                                    const hspf_backup_out *bk_in_dev, hspf_backup_node_out *out_dev) {
   if (!ctx) return HSPF_E_INVAL;
   return guarded(ctx, [&]() -> int {
-    const char *fn = "hspf_routes_backup_node_device";
-    auto bad = [&](const std::string &what) { return frr_bad(ctx, fn, what); };
-    if (!dist_dev || !flags_dev || !mask_dev || !prot || !t || !routes_dev || !out_dev) return bad("NULL table, prot, prefix table, routes or out pointer");
-    if (!routes_dev->best_metric || !routes_dev->best_entry || !routes_dev->nexthop_mask) return bad("NULL best_metric / best_entry / nexthop_mask");
+    FrrCall f(ctx, "hspf_routes_backup_node_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
+    int rc;
+    if ((rc = f.check_ptrs(out_dev, t && routes_dev, "NULL table, prot, prefix table, routes or out pointer")) || (rc = f.check_routes(routes_dev))) return rc;
     if (!out_dev->bn_kind || !out_dev->bn_primary || !out_dev->bn_p || !out_dev->bn_q || !out_dev->bn_link || !out_dev->bn_via || !out_dev->bn_metric ||
         !out_dev->bn_coverage)
-      return bad("NULL bn_kind / bn_primary / bn_p / bn_q / bn_link / bn_via / bn_metric / bn_coverage");
-    if (!ydist_dev || !y_roots) return bad("NULL ydist or y_roots pointer");
-    if (!rn_sel_dev && !tn_sel_dev) return bad("NULL rn_sel_dev and tn_sel_dev (at least one list is required)");
-    if (rn_sel_dev) {
-      if (!rn_sel_dev->nq_node || !rn_sel_dev->nq_via || !rn_sel_dev->nq_metric || !rn_sel_dev->nq_count)
-        return bad("NULL nq_node / nq_via / nq_metric / nq_count in rn_sel_dev");
-      if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) return bad("max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
-    }
-    if (tn_sel_dev) {
-      if (!tn_sel_dev->tq_q || !tn_sel_dev->tq_p || !tn_sel_dev->tq_link || !tn_sel_dev->tq_via || !tn_sel_dev->tq_metric || !tn_sel_dev->tq_count)
-        return bad("NULL tq_q / tq_p / tq_link / tq_via / tq_metric / tq_count in tn_sel_dev");
-      if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) return bad("max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
-    }
-    if (bk_in_dev && (!bk_in_dev->bk_kind || !bk_in_dev->bk_flags)) return bad("NULL bk_kind / bk_flags in bk_in_dev");
-    if (n_yrows == 0) return bad("n_yrows is 0");
-    int rc;
-    if ((rc = frr_check_dims(ctx, fn, n_vertices, n_rows, n_mask_words, n_prot))) return rc;
-    if (!t->pfx_ptr || (t->n_entries && (!t->pfx_vertex || !t->pfx_metric))) return bad("NULL pfx_ptr / pfx_vertex / pfx_metric");
-    if (t->flags & HSPF_PFX_ORDERED) return bad("HSPF_PFX_ORDERED tables are out of scope");
-    if ((size_t)n_prot * 64 * n_mask_words > (1u << 28)) return bad("n_prot * 64 * n_mask_words out of range");
-    for (uint32_t i = 0; i < n_yrows; ++i)
-      if (y_roots[i] != HSPF_NO_ROOT && y_roots[i] >= n_vertices) return bad("y_roots entry " + std::to_string(i) + " >= n_vertices");
-    if ((rc = pfx_table_stage(ctx, fn, n_vertices, t))) return rc;
-    std::vector<uint32_t> tab;                          // (lives until the synchronisation at the end: the copy reads it)
-    uint32_t max_k = 0;
-    hipStream_t s = ctx->stream;
-    if ((rc = lfa_stage(ctx, fn, n_vertices, n_rows, n_mask_words, prot, n_prot, tab, &max_k)) ||
-        (rc = ensure(ctx, ctx->rnode_map, ((size_t)n_vertices + n_yrows) * 4, false))) {
-      (void)hipStreamSynchronize(s);                    // (the table's copies read caller-owned host memory)
+      return f.bad("NULL bn_kind / bn_primary / bn_p / bn_q / bn_link / bn_via / bn_metric / bn_coverage");
+    if (!ydist_dev || !y_roots) return f.bad("NULL ydist or y_roots pointer");
+    if (!rn_sel_dev && !tn_sel_dev) return f.bad("NULL rn_sel_dev and tn_sel_dev (at least one list is required)");
+    if ((rn_sel_dev && (rc = f.check_rn_sel(rn_sel_dev, max_pq, " in rn_sel_dev"))) || (tn_sel_dev && (rc = f.check_tn_sel(tn_sel_dev, max_pairs, " in tn_sel_dev"))))
       return rc;
-    }
+    if (bk_in_dev && (!bk_in_dev->bk_kind || !bk_in_dev->bk_flags)) return f.bad("NULL bk_kind / bk_flags in bk_in_dev");
+    if ((rc = f.check_dims()) || (rc = f.check_prefix_table(t)) || (rc = f.check_slots()) || (rc = f.check_y_roots(y_roots, n_yrows)) ||
+        (rc = f.stage_prefix_table(t)) || (rc = f.stage(FrrProt::Plain, nullptr, nullptr))) return rc;
+    hipStream_t s = f.stream();
     HIPCHK(ctx, hipMemsetAsync(out_dev->bn_coverage, 0, (size_t)n_prot * HSPF_BN_COVERAGE_WORDS * 4, s));
-    if (!t->n_prefixes) {                               // nothing to launch
-      HIPCHK(ctx, hipStreamSynchronize(s));
-      return HSPF_OK;
-    }
-    uint32_t *ymap = (uint32_t *)ctx->rnode_map.p, *yroots = ymap + n_vertices;
-    HIPCHK(ctx, hipMemsetAsync(ymap, 0xFF, (size_t)n_vertices * 4, s));
-    HIPCHK(ctx, hipMemcpyAsync(yroots, y_roots, (size_t)n_yrows * 4, hipMemcpyHostToDevice, s));      // (the caller's: it lives through the call)
-    RnodeDestArgs m{};                                  // k_rlfa_nmap reads n, the root list and the map
-    m.n = n_vertices; m.yroots = yroots; m.n_yrows = n_yrows; m.ymap = ymap;
+    if (!t->n_prefixes) return f.finish(nullptr);       // nothing to launch
+    if ((rc = f.node_map(y_roots, n_yrows))) return rc;
     BackupNodeArgs a{};
     a.n = n_vertices; a.W = n_mask_words; a.stride = 64u * n_mask_words; a.n_pfx = t->n_prefixes;
     a.sat = (t->flags & HSPF_PFX_SATURATING) ? 1u : 0u; a.max_pq = rn_sel_dev ? max_pq : 0u; a.max_pairs = tn_sel_dev ? max_pairs : 0u;
     a.dist = dist_dev; a.flags = flags_dev; a.tab = (const uint32_t *)ctx->lfa_tab.p;
     a.pfx_ptr = (const uint32_t *)ctx->pf_ptr.p; a.pfx_vertex = (const uint32_t *)ctx->pf_vtx.p; a.pfx_metric = (const uint32_t *)ctx->pf_met.p;
     a.best_entry = routes_dev->best_entry; a.nh_mask = routes_dev->nexthop_mask;
-    a.ydist = ydist_dev; a.ymap = ymap;
+    a.ydist = ydist_dev; a.ymap = f.ymap;
     if (rn_sel_dev) { a.nq_node = rn_sel_dev->nq_node; a.nq_via = rn_sel_dev->nq_via; a.nq_metric = rn_sel_dev->nq_metric; a.nq_count = rn_sel_dev->nq_count; }
     if (tn_sel_dev) {
       a.tq_q = tn_sel_dev->tq_q; a.tq_p = tn_sel_dev->tq_p; a.tq_link = tn_sel_dev->tq_link; a.tq_via = tn_sel_dev->tq_via;
@@ -1253,9 +1142,9 @@ int hspf_routes_backup_node_device(hspf_ctx *ctx, uint32_t n_vertices, uint32_t 
     a.bn_kind = out_dev->bn_kind; a.bn_primary = out_dev->bn_primary; a.bn_p = out_dev->bn_p; a.bn_q = out_dev->bn_q; a.bn_link = out_dev->bn_link;
     a.bn_via = out_dev->bn_via; a.bn_metric = out_dev->bn_metric; a.bn_set_pq = out_dev->bn_set_pq; a.bn_set_pair = out_dev->bn_set_pair;
     a.bn_cov = out_dev->bn_coverage;
-    hipLaunchKernelGGL(k_rlfa_nmap, dim3((n_yrows + 255) / 256), dim3(256), 0, s, m);
+    f.launch_node_map();
     hipLaunchKernelGGL(k_backup_node, dim3((t->n_prefixes + LFA_TILE - 1) / LFA_TILE, n_prot), dim3(256), 0, s, a);
-    return frr_finish(ctx, "k_backup_node");
+    return f.finish("k_backup_node");
   });
 }
 
