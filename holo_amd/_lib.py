@@ -29,6 +29,10 @@ class HspfResult(ctypes.Structure):
                 ("pop_rank", ctypes.c_void_p)]
 
 
+class HspfFailure(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("arg", ctypes.c_uint32)]
+
+
 class HspfStats(ctypes.Structure):
     _fields_ = [("n_roots", ctypes.c_uint32), ("n_batches", ctypes.c_uint32),
                 ("n_relax_launches", ctypes.c_uint32), ("n_dag_launches", ctypes.c_uint32),
@@ -178,6 +182,11 @@ SYMBOLS = [
     ("hspf_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfResult)]),
     ("hspf_run_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfResult)]),
     ("hspf_get_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HspfStats)]),
+    # failure scenarios: one (root, failure) per row
+    ("hspf_run_failures", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, ctypes.POINTER(HspfFailure), ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.POINTER(HspfResult)]),
+    ("hspf_run_failures_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, ctypes.POINTER(HspfFailure), ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.POINTER(HspfResult)]),
     ("hspf_run_device_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.POINTER(HspfResult), u64p]),
     ("hspf_wait", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HspfStats)]),

@@ -236,6 +236,8 @@ struct hspf_ctx {
   DevBuf gb_kx;                                                 // hspf_graph_upload_keyed: keys, ranks, resolved targets
   DevBuf gb, gb_delta, gb_hub, giant_part;                      // graph build scratch, patch delta, hub-mode sort buffers
   DevBuf leaf_jobs;                                             // run_classes: the rows derived for leaf roots (LeafRootJob)
+  DevBuf fail_lanes, fail_flag;                                 // hspf_run_failures*: FailDev::pos | vtx of the pass, its flag bytes
+  std::vector<uint32_t> hb_fail;                                // ... and the host side of the first
   uint32_t hub_deg = HUB_DEG;                       // HSPF_HUB_DEG env: rows with more links than this -> graph build from sorted keys
   uint64_t tw_host_max = UINT64_MAX;                // HSPF_TW_HOST_MAX env: row entries a structural patch may scan to keep the two-way mirror itself (unset: max(4096, links / 32))
   BuildInfo *h_info = nullptr;     // pinned
@@ -442,7 +444,14 @@ void launch_dag(dim3 grid, hipStream_t s, GraphDev g, const uint32_t *dist, uint
                 const uint32_t *roots, SlotTabs tabs, uint32_t nn, uint32_t io, int *changed, int sweep,
                 uint32_t epoch, uint32_t *lf, uint32_t hc, uint32_t *act) {
   hipLaunchKernelGGL((k_dag<W, GS>), grid, dim3(256), 0, s, g, dist, hv, mask, roots, tabs, nn, io, changed,
-                     sweep, epoch, lf, hc, act);
+                     sweep, epoch, lf, hc, act, FailNone{});
+}
+template <int W, bool GS = false>
+void launch_dag_fail(dim3 grid, hipStream_t s, GraphDev g, const uint32_t *dist, uint32_t *hv, uint64_t *mask,
+                     const uint32_t *roots, SlotTabs tabs, uint32_t nn, uint32_t io, int *changed, int sweep,
+                     uint32_t epoch, uint32_t *lf, uint32_t hc, uint32_t *act, FailDev fd) {
+  hipLaunchKernelGGL((k_dag<W, GS, true>), grid, dim3(256), 0, s, g, dist, hv, mask, roots, tabs, nn, io, changed,
+                     sweep, epoch, lf, hc, act, fd);
 }
 template <int W>
 void launch_emit(dim3 grid, hipStream_t s, uint32_t n, uint32_t nr, const uint32_t *dist, const uint32_t *hv,
@@ -870,7 +879,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->lan_tab, &ctx->lan_scal, &ctx->srlg_tab, &ctx->srlg_scal, &ctx->ea_scr, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw, &ctx->rnode_part, &ctx->rnode_map, &ctx->tnode_cell})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->fail_lanes, &ctx->fail_flag, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->lan_tab, &ctx->lan_scal, &ctx->srlg_tab, &ctx->srlg_scal, &ctx->ea_scr, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw, &ctx->rnode_part, &ctx->rnode_map, &ctx->tnode_cell})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -1552,7 +1561,7 @@ static int copy_to_host(hspf_ctx *ctx, void *dst, const void *src_dev, size_t by
 
 static int run_impl(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, uint32_t n_roots, uint32_t run_flags,
                     hspf_result *out, bool host_out, const uint32_t *row_map = nullptr, uint32_t total_rows = 0,
-                    bool no_fused = false, PackedReq *pk = nullptr);
+                    bool no_fused = false, PackedReq *pk = nullptr, const hspf_failure *fail = nullptr);
 
 }  // extern "C"  (the pass below has a member template)
 
@@ -1564,6 +1573,8 @@ struct Run {
   // the call
   hspf_ctx *ctx; const hspf_graph *g; const uint32_t *roots; uint32_t n_roots, run_flags; hspf_result *out; bool host_out;
   const uint32_t *row_map; uint32_t total_rows; bool no_fused; PackedReq *pk; uint32_t n;
+  const hspf_failure *fail = nullptr;                                // hspf_run_failures*: one failure per root (validated by the entry point); two-phase path only
+  FailDev fdv{};
   hspf_stats &st;                                                    // ctx->stats
   std::vector<uint32_t> &tab_ptr, &tab_vtx, &tab_base;               // slot tables of the roots (host)
   Run(hspf_ctx *c, const hspf_graph *gr, const uint32_t *r, uint32_t nr, uint32_t fl, hspf_result *o, bool ho, const uint32_t *rm, uint32_t tr, bool nf, PackedReq *p)
@@ -1700,7 +1711,7 @@ int Run::choose_state() {
   // 17-24 slots: the 8-byte state with a wider mask field and correspondingly fewer hop bits (32 - M); a root farther
   // than that many router hops from something raises LF_OVERFLOW and the run is redone on the two-phase path.
   const uint32_t fused_max_slots = g->wide24_bad ? 16u : 24u;
-  fused = !no_fused && max_slots <= fused_max_slots && n < (1u << 23) && !(ctx->variant & 1u);
+  fused = !no_fused && !fail && max_slots <= fused_max_slots && n < (1u << 23) && !(ctx->variant & 1u);
   const uint32_t Mw = std::max(16u, max_slots);
   fp_wide = FusedParams{0u, Mw, Mw == 16u ? 0xFFFFu : (1u << (32u - Mw)) - 1u, 0xFFFFFFFFu, g->max_path_metric, 0xFFFFFFFFu,
                       g->hopcount_like ? 1u : 0u, 0xFFFFFFFFu};
@@ -1905,7 +1916,7 @@ int Run::init_state() {
   // (the leaf is popped AFTER its parent, against the static (distance, index) order), the emit's derivation gives the right
   // triple but cannot raise LF_DYN any more (the status bits were read before it), and the caller would be told the order
   // is static (round 6: tests/test_gpu_fuzz.py, zero-metric instances, seed 5058).
-  use_fw = !fused && !(ctx->variant & 64u) && (!g->hopcount_like || W <= 4);
+  use_fw = !fused && !fail && !(ctx->variant & 64u) && (!g->hopcount_like || W <= 4);
   defer = use_fw && g->n_leaf != 0 && g->max_path_metric != HSPF_DIST_INF && !g->hopcount_like && g->n_zero_rows == 0;
   HIPCHK(ctx, hipEventRecord(ctx->ev[0], s));
   if (fused) {
@@ -1927,6 +1938,24 @@ int Run::init_state() {
     HIPCHK(ctx, hipMemsetAsync(d_dist, 0xFF, rows * 4, s));
     HIPCHK(ctx, hipMemsetAsync(d_hv, 0, rows * 4, s));
     hipLaunchKernelGGL(k_init_roots, dim3((L + 255) / 256), dim3(256), 0, s, n, d_dist, d_roots, L);
+    if (fail) {
+      // Scenario run: the lanes' failures as two words per lane, and the per-batch marks that send a chunk of links to the
+      // slow side of the sweeps (k_init_fail).  Leaves are not deferred on this path: they take part in the fixed point
+      // like any other row, so a leaf behind the failed link or the excluded vertex needs nothing of its own.
+      std::vector<uint32_t> &hf = ctx->hb_fail;
+      hf.assign((size_t)2 * L, HSPF_DIST_INF);
+      for (uint32_t r = 0; r < n_roots; ++r) {
+        if (roots[r] == HSPF_NO_ROOT) continue;
+        if (fail[r].kind == HSPF_FAIL_ROOT_LINK) hf[r] = fail[r].arg;
+        else if (fail[r].kind == HSPF_FAIL_VERTEX) hf[(size_t)L + r] = fail[r].arg;
+      }
+      if ((rc = ensure(ctx, ctx->fail_lanes, (size_t)2 * L * 4, false))) return rc;
+      if ((rc = ensure(ctx, ctx->fail_flag, (size_t)B * n, false))) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->fail_lanes.p, hf.data(), (size_t)2 * L * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(ctx, hipMemsetAsync(ctx->fail_flag.p, 0, (size_t)B * n, s));
+      fdv = FailDev{(const uint32_t *)ctx->fail_lanes.p, (const uint32_t *)ctx->fail_lanes.p + L, (const uint8_t *)ctx->fail_flag.p};
+      hipLaunchKernelGGL(k_init_fail, dim3((L + 255) / 256), dim3(256), 0, s, n, (const uint32_t *)d_roots, fdv.pos, fdv.vtx, (uint8_t *)ctx->fail_flag.p, L);
+    }
   }
 
   const uint32_t vblocks = (n + VPB - 1) / VPB;
@@ -2478,10 +2507,15 @@ int Run::path_wide() {
   } else {
   uint32_t n_relax = 0;
   rc = run_phase(ctx->est_relax, 0u, [&](uint32_t sweep) {
-    if (g->max_path_metric == HSPF_DIST_INF)
-      hipLaunchKernelGGL((k_relax<true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf);
+    if (fail) {
+      if (g->max_path_metric == HSPF_DIST_INF)
+        hipLaunchKernelGGL((k_relax<true, true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, fdv);
+      else
+        hipLaunchKernelGGL((k_relax<false, true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, fdv);
+    } else if (g->max_path_metric == HSPF_DIST_INF)
+      hipLaunchKernelGGL((k_relax<true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, FailNone{});
     else
-      hipLaunchKernelGGL((k_relax<false>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf);
+      hipLaunchKernelGGL((k_relax<false>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, FailNone{});
   }, n_relax, []() {});
   if (rc) return rc;
   ctx->est_relax = n_relax + 1;
@@ -2498,7 +2532,14 @@ int Run::path_wide() {
       hipLaunchKernelGGL(k_rebase, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_hv, rows);
       epoch = 2;
     }
-    switch (W) {
+    if (fail) switch (W) {
+      case 1: launch_dag_fail<1, true>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
+      case 2: launch_dag_fail<2>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
+      case 4: launch_dag_fail<4>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
+      case 8: launch_dag_fail<8>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
+      default: launch_dag_fail<16>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
+    }
+    else switch (W) {
       case 1: launch_dag<1, true>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
       case 2: launch_dag<2>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
       case 4: launch_dag<4>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
@@ -2689,6 +2730,7 @@ int Run::exact_roots() {
   for (uint32_t r = 0; r < n_roots; ++r) {
     if (roots[r] == HSPF_NO_ROOT) continue;
     const uint32_t lf = ctx->h_lane_flags[r];
+    if (fail) { if (forced || (lf & (LF_NEED_EXACT | LF_DYN))) ex.push_back(r); continue; }      // scenario runs: the sequential kernel with the same exclusion, not k_repair
     if (forced || (lf & LF_NEED_EXACT) || ((run_flags & HSPF_RUN_POP_RANK) && !want_rank)) ex.push_back(r);
     else if (want_rank) dy.push_back(r);
     else if (lf & LF_DYN) {
@@ -2721,7 +2763,9 @@ int Run::exact_roots() {
     if ((rc = ensure(ctx, ctx->ex_pos, ex.size() * (size_t)n * 4))) return rc;
     a.root_list = (const uint32_t *)ctx->ex_list.p + dy.size();
     a.heap = (uint32_t *)ctx->ex_heap.p; a.pos = (uint32_t *)ctx->ex_pos.p;
-    hipLaunchKernelGGL(k_exact, dim3((a.n_exact + 63) / 64), dim3(64), 0, s, a);
+    a.fail_pos = fdv.pos; a.fail_vtx = fdv.vtx;
+    if (fail) hipLaunchKernelGGL(k_exact_fail, dim3((a.n_exact + 63) / 64), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_exact, dim3((a.n_exact + 63) / 64), dim3(64), 0, s, a);
   }
   if ((run_flags & HSPF_RUN_POP_RANK) && d_rank) {
     // pop_rank of padding roots
@@ -2816,7 +2860,7 @@ extern "C" {
 
 static int run_impl(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, uint32_t n_roots, uint32_t run_flags,
                     hspf_result *out, bool host_out, const uint32_t *row_map, uint32_t total_rows,
-                    bool no_fused, PackedReq *pk) {
+                    bool no_fused, PackedReq *pk, const hspf_failure *fail) {
   // packed results (hspf_run_packed*): `out` is not read; host_out says whether pk->dst is host memory
   hspf_result pk_none{};
   if (pk) { out = &pk_none; host_out = pk->host; }
@@ -2883,7 +2927,7 @@ static int run_impl(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, u
         if (out->vflags_out) part.vflags_out = out->vflags_out + o;
         if (out->first_hop_mask) part.first_hop_mask = out->first_hop_mask + o * out->n_mask_words;
         if (out->pop_rank) part.pop_rank = out->pop_rank + o;
-        const int rc = run_impl(ctx, g, roots + off, nr, run_flags, &part, host_out, row_map ? row_map + off : nullptr, total_rows, no_fused);
+        const int rc = run_impl(ctx, g, roots + off, nr, run_flags, &part, host_out, row_map ? row_map + off : nullptr, total_rows, no_fused, nullptr, fail ? fail + off : nullptr);
         if (rc) return rc;
         const hspf_stats &p = ctx->stats;
         acc.n_roots += p.n_roots; acc.n_batches += p.n_batches; acc.n_relax_launches += p.n_relax_launches;
@@ -2898,6 +2942,7 @@ static int run_impl(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, u
     }
   }
   Run run(ctx, g, roots, n_roots, run_flags, out, host_out, row_map, total_rows, no_fused, pk);
+  run.fail = fail;
   return run.go();
 }
 
@@ -3092,6 +3137,45 @@ int hspf_run(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, uint32_t
 
 int hspf_run_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, uint32_t n_roots, uint32_t run_flags, hspf_result *out_device) {
   return guarded(ctx, [&]() { return run_classes(ctx, g, roots, n_roots, run_flags, out_device, false); });
+}
+
+// ---- failure scenarios: row r = the run of roots[r] with fail[r] applied (include/holo_spf_hip.h) ----
+// Everything is checked before anything is launched; the pass itself is run_impl's two-phase path with the FAIL kernels.
+static int run_failures(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, const hspf_failure *fail, uint32_t n_rows,
+                        uint32_t run_flags, hspf_result *out, bool host_out, const char *call) {
+  if (!ctx) return HSPF_E_INVAL;
+  auto bad = [&](const std::string &what) { ctx->last_error = std::string(call) + ": " + what; return HSPF_E_INVAL; };
+  if (!g || !roots || !fail || !out || n_rows == 0 || !out->dist) return bad("null argument or no rows");
+  if (g->invalid) return bad("the graph is invalid after a failed hspf_graph_patch (free it and upload again)");
+  if (run_flags & (HSPF_RUN_POP_RANK | HSPF_RUN_COUNT_ROWS)) return bad("HSPF_RUN_POP_RANK / HSPF_RUN_COUNT_ROWS are not accepted");
+  for (uint32_t r = 0; r < n_rows; ++r) {
+    const uint32_t root = roots[r];
+    if (root == HSPF_NO_ROOT) continue;
+    const std::string row = "row " + std::to_string(r) + ": ";
+    if (root >= g->n) return bad(row + "root out of range");
+    switch (fail[r].kind) {
+      case HSPF_FAIL_NONE: break;
+      case HSPF_FAIL_ROOT_LINK:
+        if (fail[r].arg >= g->rlen[root]) return bad(row + "link position " + std::to_string(fail[r].arg) + " beyond the root's row of " + std::to_string(g->rlen[root]) + " links");
+        break;
+      case HSPF_FAIL_VERTEX:
+        if (fail[r].arg >= g->n) return bad(row + "excluded vertex out of range");
+        if (fail[r].arg == root) return bad(row + "the excluded vertex is the root");
+        break;
+      default: return bad(row + "unknown failure kind " + std::to_string(fail[r].kind));
+    }
+  }
+  return run_impl(ctx, g, roots, n_rows, run_flags, out, host_out, nullptr, 0, true, nullptr, fail);
+}
+
+int hspf_run_failures(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, const hspf_failure *fail, uint32_t n_rows,
+                      uint32_t run_flags, hspf_result *out) {
+  return guarded(ctx, [&]() { return run_failures(ctx, g, roots, fail, n_rows, run_flags, out, true, "hspf_run_failures"); });
+}
+
+int hspf_run_failures_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, const hspf_failure *fail, uint32_t n_rows,
+                             uint32_t run_flags, hspf_result *out_device) {
+  return guarded(ctx, [&]() { return run_failures(ctx, g, roots, fail, n_rows, run_flags, out_device, false, "hspf_run_failures_device"); });
 }
 
 // ---- packed results (ABI 7) ---------------------------------------------------------------------

@@ -218,12 +218,34 @@ constexpr int NGRP = 64 / GRP;
 
 // Distance relaxation sweep.  grid = (ceil8(ceil(n / VPB)), n_batches), block = 256.
 // MAXINF: max_path_metric == 0xFFFFFFFF (OSPF): u32 saturation must be detected.
-template <bool MAXINF>
+// FAIL (hspf_run_failures*): every lane may carry ONE failure of its own — a link of its root's row that is not used, or a
+// vertex that is not in its SPT (FailDev).  The test sits on the rare side, next to has_nt: a 64-link chunk takes it only
+// when one of its sources is marked in the batch's flag bytes (a root of the batch with a failed link, or an excluded
+// vertex of the batch — k_init_fail), and then a link costs two compares against per-lane registers.  The excluded
+// vertex's own row is never written in its lane (it stays INF), so nothing leaves it either.  The FAIL == false instantiations
+// are the code of k_relax / k_dag / k_exact as it was; their last argument is an empty struct (FailArg).
+struct FailDev {
+  const uint32_t *pos;     // [batches * 64] failed position inside the lane's root row; INF: none
+  const uint32_t *vtx;     // [batches * 64] excluded vertex of the lane; INF: none
+  const uint8_t *flag;     // [batches][n]   1: a source the chunk test has to look at (see above)
+};
+
+struct FailNone {};       // the last kernel argument of the FAIL == false instantiations: nothing
+template <bool FAIL> struct FailArg { using type = FailNone; };
+template <> struct FailArg<true> { using type = FailDev; };
+__device__ __forceinline__ uint32_t fail_pos(const FailDev &fd, uint32_t slot) { return fd.pos[slot]; }
+__device__ __forceinline__ uint32_t fail_vtx(const FailDev &fd, uint32_t slot) { return fd.vtx[slot]; }
+__device__ __forceinline__ const uint8_t *fail_flags(const FailDev &fd, size_t off) { return fd.flag + off; }
+__device__ __forceinline__ uint32_t fail_pos(const FailNone &, uint32_t) { return INF; }
+__device__ __forceinline__ uint32_t fail_vtx(const FailNone &, uint32_t) { return INF; }
+__device__ __forceinline__ const uint8_t *fail_flags(const FailNone &, size_t) { return nullptr; }
+
+template <bool MAXINF, bool FAIL = false>
 __global__ __launch_bounds__(256) void k_relax(GraphDev g, uint32_t *__restrict__ dist,
                                                const uint32_t *__restrict__ roots,
                                                uint32_t maxpath, uint32_t ignore_ovl,
                                                int *changed, int sweep,
-                                               uint32_t *lane_flags) {
+                                               uint32_t *lane_flags, typename FailArg<FAIL>::type fd) {
   if (sweep > 0 && changed[sweep - 1] == 0) return;      // converged in an earlier launch
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -235,6 +257,8 @@ __global__ __launch_bounds__(256) void k_relax(GraphDev g, uint32_t *__restrict_
   const uint32_t *__restrict__ in_src = g.in_src;
   const uint32_t *__restrict__ in_w = g.in_w;
   const uint32_t my_root = roots[batch * 64 + lane];
+  const uint32_t my_fpos = fail_pos(fd, batch * 64 + lane), my_fvtx = fail_vtx(fd, batch * 64 + lane);
+  const uint8_t *FF = fail_flags(fd, (size_t)batch * n);
   uint32_t *D = dist + (size_t)batch * n * 64;
   const uint32_t lane4 = lane * 4u;
   // row bounds of the VPW vertices of this wave: one vector load, lanes 0..VPW
@@ -255,6 +279,8 @@ __global__ __launch_bounds__(256) void k_relax(GraphDev g, uint32_t *__restrict_
       // overload gating is rare: only rows that list an overloaded source take the slow path
       const bool has_nt = !ignore_ovl && __ballot((sv & SRC_NO_TRANSIT) != 0) != 0ull;
       if (!has_nt) sv &= SRC_MASK;
+      const bool has_fl = FAIL && __ballot(lane < cnt && FF[sv & SRC_MASK] != 0) != 0ull;
+      const uint32_t fv = (has_fl && lane < cnt) ? g.in_fpos[eb + lane] : 0u;
 #pragma unroll
       for (int gi = 0; gi < NGRP; ++gi) {
         if (cnt <= (uint32_t)(gi * GRP)) break;
@@ -272,6 +298,10 @@ __global__ __launch_bounds__(256) void k_relax(GraphDev g, uint32_t *__restrict_
             const uint32_t sw = rdlane(sv, gi * GRP + k);
             if ((sw & SRC_NO_TRANSIT) && (sw & SRC_MASK) != my_root) d = INF;
           }
+          if (FAIL && has_fl) {                                   // uniform
+            const uint32_t u = rdlane(sv, gi * GRP + k) & SRC_MASK;
+            if (u == my_fvtx || (u == my_root && rdlane(fv, gi * GRP + k) == my_fpos)) d = INF;
+          }
           const uint32_t c = add_sat(d, w);                       // INF stays INF
           if (MAXINF && c == INF && d != INF && w != INF) sat = true;   // genuine u32 saturation
           best = min(best, c);        // candidates above max_path_metric are rejected at the end
@@ -279,13 +309,25 @@ __global__ __launch_bounds__(256) void k_relax(GraphDev g, uint32_t *__restrict_
       }
     }
     // min over all candidates: if the smallest exceeds max_path_metric, every one does
-    if (best < d_old && best <= maxpath) {
+    if (best < d_old && best <= maxpath && !(FAIL && v == my_fvtx)) {
       D[(size_t)v * 64 + lane] = best;
       any = true;
     }
   }
   if (__ballot(any) != 0ull && lane == 0) changed[sweep] = 1;
   if (MAXINF && sat) atomicOr(&lane_flags[batch * 64 + lane], LF_NEED_EXACT);
+}
+
+// Marks of a scenario run (FailDev::flag, zeroed by the caller): the roots that have a failed link and the excluded
+// vertices, per batch.  Lanes that mark the same byte store the same value.
+__global__ void k_init_fail(uint32_t n, const uint32_t *roots, const uint32_t *pos, const uint32_t *vtx, uint8_t *flag, uint32_t n_lanes) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_lanes) return;
+  const uint32_t r = roots[i];
+  if (r == INF) return;
+  uint8_t *F = flag + (size_t)(i >> 6) * n;
+  if (pos[i] != INF) F[r] = 1;
+  if (vtx[i] != INF) F[vtx[i]] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -297,13 +339,16 @@ __global__ __launch_bounds__(256) void k_relax(GraphDev g, uint32_t *__restrict_
 // In-links of a row are stored by (cost descending, source ascending) — graph_build.hip.h, kb_rank —, so among the
 // tight links the first one in row order has the smallest parent distance and, on ties, the smallest parent index:
 // the earliest-popped tight parent (first discoverer).
-template <int W, bool GS>
+// FAIL: as in k_relax.  The excluded vertex has distance INF in its lane and can be nobody's tight parent; the failed
+// link of the root CAN look tight (a parallel link, or another path, of the same length), so it is taken out here too —
+// which is also what keeps its slot bit clear.
+template <int W, bool GS, bool FAIL = false>
 __global__ __launch_bounds__(256) void k_dag(GraphDev g, const uint32_t *__restrict__ dist,
                                              uint32_t *__restrict__ hv, uint64_t *__restrict__ mask,
                                              const uint32_t *__restrict__ roots, SlotTabs tabs,
                                              uint32_t net_nexthops, uint32_t ignore_ovl,
                                              int *changed, int sweep, uint32_t epoch,
-                                             uint32_t *lane_flags, uint32_t hc, uint32_t *__restrict__ act) {
+                                             uint32_t *lane_flags, uint32_t hc, uint32_t *__restrict__ act, typename FailArg<FAIL>::type fd) {
   // links per group = neighbour rows requested together: more for narrow masks (a 100-link row of a fat-tree switch is
   // 2 dependent round trips per group), fewer for wide ones (2 * DG * W mask registers)
   constexpr int DG = W <= 2 ? 8 : (W <= 4 ? 4 : 2);
@@ -320,6 +365,8 @@ __global__ __launch_bounds__(256) void k_dag(GraphDev g, const uint32_t *__restr
   const uint32_t *__restrict__ in_w = g.in_w;
   const uint32_t root_slot = batch * 64 + lane;
   const uint32_t my_root = roots[root_slot];
+  const uint32_t my_fpos = fail_pos(fd, root_slot), my_fvtx = fail_vtx(fd, root_slot);
+  const uint8_t *FF = fail_flags(fd, (size_t)batch * n);
   const uint32_t *D = dist + (size_t)batch * n * 64;
   uint32_t *H = hv + (size_t)batch * n * 64;
   uint64_t *M = mask + (size_t)batch * n * 64 * W;
@@ -359,6 +406,8 @@ __global__ __launch_bounds__(256) void k_dag(GraphDev g, const uint32_t *__restr
         uint32_t wv = lane < cnt ? in_w[eb + lane] : 1u;
         const bool has_nt = !ignore_ovl && __ballot((sv & SRC_NO_TRANSIT) != 0) != 0ull;
         if (!has_nt) sv &= SRC_MASK;
+        const bool has_fl = FAIL && __ballot(lane < cnt && FF[sv & SRC_MASK] != 0) != 0ull;
+        const uint32_t fv = (has_fl && lane < cnt) ? g.in_fpos[eb + lane] : 0u;
         // A zero-cost link from a HIGHER-numbered source is never a static-order parent; padding
         // lanes likewise: rewrite both as (own row, cost 1), which can never be tight.  Exception:
         // hop-count-like graphs (see fused_row_any): there the FIRST tight one of them, in row order
@@ -384,6 +433,10 @@ __global__ __launch_bounds__(256) void k_dag(GraphDev g, const uint32_t *__restr
             if (has_nt) {
               const uint32_t sw = rdlane(sv, gi * DG + k);
               if ((sw & SRC_NO_TRANSIT) && (sw & SRC_MASK) != my_root) d = INF;
+            }
+            if (FAIL && has_fl) {                                 // uniform
+              const uint32_t u = rdlane(sv, gi * DG + k) & SRC_MASK;
+              if (u == my_fvtx || (u == my_root && rdlane(fv, gi * DG + k) == my_fpos)) d = INF;
             }
             // tight parent (d + w == dv without saturation; dv != INF for `need` lanes)
             tight[k] = need && d != INF && add_sat(d, w) == dv;
@@ -3180,6 +3233,7 @@ struct ExactArgs {
   uint32_t *pop_rank;          // may be null
   const uint32_t *row_map;     // output row of root index ri (null: ri itself)
   uint32_t *heap; uint32_t *pos;   // [n_exact][n]
+  const uint32_t *fail_pos, *fail_vtx;   // scenario runs (k_exact_fail): FailDev::pos / vtx, indexed like roots[]
 };
 
 __device__ __forceinline__ bool ex_less(const uint32_t *dist, uint32_t a, uint32_t b) {
@@ -3187,7 +3241,10 @@ __device__ __forceinline__ bool ex_less(const uint32_t *dist, uint32_t a, uint32
   return da < db || (da == db && a < b);
 }
 
-__global__ void k_exact(ExactArgs a) {
+// FAIL: the root's failed link and every link INTO the excluded vertex are skipped; the excluded vertex is then never
+// labelled, never popped, and no link out of it is walked.
+template <bool FAIL>
+__device__ __forceinline__ void exact_body(const ExactArgs &a) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= a.n_exact) return;
   const uint32_t ri = a.root_list[t];
@@ -3208,6 +3265,7 @@ __global__ void k_exact(ExactArgs a) {
     for (uint32_t k = 0; k < W; ++k) mask[(size_t)i * W + k] = 0;
   }
   if (root == INF) return;
+  const uint32_t my_fpos = FAIL ? a.fail_pos[ri] : INF, my_fvtx = FAIL ? a.fail_vtx[ri] : INF;
   uint32_t hn = 0, popped = 0;
   dist[root] = 0; heap[0] = root; pos[root] = 0; hn = 1;
   while (hn) {
@@ -3238,6 +3296,7 @@ __global__ void k_exact(ExactArgs a) {
     for (uint32_t k = a.g.out_ptr[v]; k < a.g.out_ptr[v + 1]; ++k) {
       const uint32_t tv = a.g.out_dst[k];
       if (flags[tv] & 1) continue;                      // already on the SPT
+      if (FAIL && (tv == my_fvtx || (v == root && a.g.out_fpos[k] == my_fpos))) continue;
       const uint64_t c64 = (uint64_t)dvv + a.g.out_w[k];
       const uint32_t d = c64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c64;
       if (d > a.maxpath) continue;
@@ -3274,6 +3333,8 @@ __global__ void k_exact(ExactArgs a) {
     }
   }
 }
+__global__ void k_exact(ExactArgs a) { exact_body<false>(a); }
+__global__ void k_exact_fail(ExactArgs a) { exact_body<true>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // Route derivation (prefix attachment): one thread per (root, prefix).  Consecutive threads take

@@ -79,6 +79,8 @@ TN_COVERAGE_WORDS = 6
 BN_LFA, BN_PQ, BN_LAST_HOP, BN_NONE, BN_PAIR = 1, 2, 3, 4, 5                # HSPF_BN_* (bn_kind)
 BN_COVERAGE_WORDS = 6
 
+FAIL_NONE, FAIL_ROOT_LINK, FAIL_VERTEX = 0, 1, 2     # HSPF_FAIL_*: kind of a run_failures() row
+
 RF_IN_SPT = 0x0001
 RF_EXACT = 0x0002
 DIST_INF = 0xFFFFFFFF
@@ -785,6 +787,58 @@ class SpfContext:
         if rc != 0:
             raise HspfError(rc, "hspf_run_device", self.last_error())
         return self.stats()
+
+    @staticmethod
+    def _failure_array(failures, n_rows: int):
+        """(kind, arg) pairs -> the hspf_failure array of a run_failures call."""
+        f = np.ascontiguousarray(failures, dtype=np.uint32).reshape(-1, 2)
+        if len(f) != n_rows:
+            raise ValueError("one (kind, arg) failure per root")
+        return f, f.ctypes.data_as(ctypes.POINTER(L.HspfFailure))
+
+    def run_failures_device(self, graph: SpfGraph, roots: Sequence[int], failures, run_flags: int = 0, *, dist_ptr: int,
+                            hops_ptr: int = 0, flags_ptr: int = 0, mask_ptr: int = 0, mask_words: int = 1) -> dict:
+        """hspf_run_failures_device(): row r = the run of roots[r] with failures[r] = (FAIL_*, arg) applied, on the
+        untouched graph; results stay in HBM at the given device pointers.  Returns the stats of the run."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        f, fp = self._failure_array(failures, len(roots))
+        res = L.HspfResult(dist_ptr or None, hops_ptr or None, flags_ptr or None, mask_ptr or None, mask_words, None)
+        rc = self.lib.hspf_run_failures_device(self.handle, graph.handle, _u32(roots), fp, len(roots), run_flags, ctypes.byref(res))
+        if rc != 0:
+            raise HspfError(rc, "hspf_run_failures_device", self.last_error())
+        return self.stats()
+
+    def run_failures(self, graph: SpfGraph, roots: Sequence[int], failures, run_flags: int = 0, *, want_mask: bool = True,
+                     mask_words: Optional[int] = None) -> SpfResult:
+        """hspf_run_failures(): as run_failures_device(), results in host numpy arrays."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        f, fp = self._failure_array(failures, len(roots))
+        R, n = len(roots), graph.n
+        W = mask_words or graph.mask_words(roots)
+        dist = np.empty((R, n), np.uint32)
+        hops = np.empty((R, n), np.uint16)
+        flags = np.empty((R, n), np.uint16)
+        mask = np.empty((R, n, W), np.uint64) if want_mask else None
+        res = L.HspfResult(dist.ctypes.data, hops.ctypes.data, flags.ctypes.data, mask.ctypes.data if want_mask else None, W, None)
+        rc = self.lib.hspf_run_failures(self.handle, graph.handle, _u32(roots), fp, R, run_flags, ctypes.byref(res))
+        if rc != 0:
+            raise HspfError(rc, "hspf_run_failures", self.last_error())
+        return SpfResult(dist, hops, flags, mask, None, self.stats())
+
+    def post_convergence(self, graph: SpfGraph, root: int, run_flags: int = 0, *, node: bool = False):
+        """The post-convergence trees of one router: one row per candidate slot e of lfa_candidates(root) — the root's SPT
+        with link root_link[e] failed, or with node=True with the neighbour nbr[e] taken out.  Returns (candidates, slots,
+        SpfResult): row i belongs to slot slots[i].  The rows come from ONE run_failures() call."""
+        cand = lfa_candidates(graph.row_ptr, graph.col, graph.metric, graph.vflags, root)
+        slots = np.flatnonzero(cand.nbr != NO_ROOT).astype(np.uint32)
+        if len(slots) == 0:
+            n = graph.n
+            return cand, slots, SpfResult(np.empty((0, n), np.uint32), np.empty((0, n), np.uint16), np.empty((0, n), np.uint16),
+                                          np.empty((0, n, 1), np.uint64), None, {})
+        fails = np.empty((len(slots), 2), np.uint32)
+        fails[:, 0] = FAIL_VERTEX if node else FAIL_ROOT_LINK
+        fails[:, 1] = cand.nbr[slots] if node else cand.root_link[slots]
+        return cand, slots, self.run_failures(graph, np.full(len(slots), root, np.uint32), fails, run_flags)
 
     def run_device_async(self, graph: SpfGraph, roots: Sequence[int], run_flags: int, *, dist_ptr: int,
                          hops_ptr: int = 0, flags_ptr: int = 0, mask_ptr: int = 0, mask_words: int = 1) -> int:

@@ -325,6 +325,51 @@ int hspf_run_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, u
                     uint32_t run_flags, hspf_result *out_device);
 int hspf_get_stats(const hspf_ctx *ctx, hspf_stats *out);
 
+/* ---- failure scenarios: the SPT a root has AFTER a failure, one scenario per row ---------- */
+/*
+ * Row r is the run of roots[r] on the graph with fail[r] applied; the graph itself is not touched, so any number of
+ * scenarios — every link of a router under link failure, every neighbour under node failure — are ONE batch of one run
+ * ("lane = root": a scenario is a lane whose root happens to repeat).  This is the post-convergence tree: the yardstick of
+ * the fast-reroute calls below (hspf_tilfa_device's "the best total is the SPF distance S -> E with the protected link
+ * removed" is dist[E] of the HSPF_FAIL_ROOT_LINK row of that link) and the input of what they leave out of scope.
+ *
+ * Everything is as hspf_run_device defines it — distances, hop counts, HSPF_RF_*, the first-hop mask and its slot
+ * numbering (positions count ALL links of the root's row as passed: no slot moves because a link failed), max_path_metric,
+ * overload, HSPF_RUN_NET_NEXTHOPS, HSPF_RUN_IGNORE_OVERLOAD, n_mask_words as hspf_mask_words gives it for `roots` — except:
+ *   HSPF_FAIL_NONE       nothing: the row equals hspf_run_device's row of that root.
+ *   HSPF_FAIL_ROOT_LINK  arg = position j of a link in the ROOT's row of the caller's CSR: that link is not used in this row.
+ *                        Only that direction matters for the root's own SPT (the root's distance is 0 and never improved);
+ *                        parallel links to the same neighbour stay, and the two-way check of every other link is unaffected
+ *                        (the neighbour still lists the root).  A link that did not survive the two-way check changes
+ *                        nothing.  The slot bit of j is never set.  j >= the row's length: HSPF_E_INVAL.
+ *   HSPF_FAIL_VERTEX     arg = a vertex X != root: X is not in this row's SPT (dist HSPF_DIST_INF, hops 0, flags 0, mask 0)
+ *                        and no link out of X is used.  X may be a router or a network vertex (a LAN failure).  X == root
+ *                        or X >= n: HSPF_E_INVAL.
+ * roots[r] == HSPF_NO_ROOT gives an empty SPT as always; its failure is not looked at.  The same root may appear in any
+ * number of rows.  Argument errors (also an unknown kind, HSPF_RUN_POP_RANK, HSPF_RUN_COUNT_ROWS) return HSPF_E_INVAL before
+ * anything is launched — hspf_get_stats still shows the previous run — with a text in hspf_last_error that names the call.
+ *
+ * Engine path: scenario runs take ONE path, the two-phase fixed point (distances, then hops and masks over the tight-link
+ * DAG) with the failure test on the rare side of its sweeps, whatever the number of slots; leaves take part in the fixed
+ * point instead of being derived in the emit.  Roots whose pop order is dynamic under the failure (zero-cost plateaus) or
+ * whose sums saturate u32 are redone by the sequential kernel with the same exclusion (HSPF_RF_EXACT in their rows): slow
+ * and correct.  OUT OF SCOPE: packed words and the asynchronous / ticket forms; failures of links that are not the root's;
+ * more than one failure per row.
+ */
+#define HSPF_FAIL_NONE      0u   /* the row is a plain run of its root                                   */
+#define HSPF_FAIL_ROOT_LINK 1u   /* arg = position j of a link in the ROOT's row of the caller's CSR     */
+#define HSPF_FAIL_VERTEX    2u   /* arg = a vertex index X != root                                        */
+typedef struct {
+  uint32_t kind;            /* HSPF_FAIL_*                                                 */
+  uint32_t arg;             /* the link position or the vertex, as the kind says           */
+} hspf_failure;
+/* roots and fail are host arrays of n_rows entries; out_dev holds DEVICE pointers (n_rows rows), as for hspf_run_device. */
+int hspf_run_failures_device(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, const hspf_failure *fail,
+                             uint32_t n_rows, uint32_t run_flags, hspf_result *out_dev);
+/* ... and with host buffers, as hspf_run. */
+int hspf_run_failures(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, const hspf_failure *fail,
+                      uint32_t n_rows, uint32_t run_flags, hspf_result *out_host);
+
 /* ---- asynchronous runs (ABI 6) ----------------------------------------------------------- */
 /*
  * The reference runs ONE SPF at a time per instance thread (holo-protocol/src/lib.rs:427-430), but an SPF event holds

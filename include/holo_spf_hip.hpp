@@ -303,6 +303,33 @@ class Engine {
     return t;
   }
 
+  // Failure scenarios: row r = the run of roots[r] with failures[r] applied (HSPF_FAIL_*), the graph untouched; everything else
+  // as run().  run_failures_device writes to DEVICE pointers sized for roots.size() rows and returns the run's statistics.
+  Tables run_failures(const Graph &g, const std::vector<uint32_t> &roots, const std::vector<hspf_failure> &failures, uint32_t run_flags = 0) {
+    if (failures.size() != roots.size()) throw Error(HSPF_E_INVAL, "run_failures: one hspf_failure per root");
+    Tables t;
+    t.n_roots = (uint32_t)roots.size();
+    t.n_vertices = g.n_vertices();
+    t.mask_words = mask_words(g, roots);
+    const size_t rn = (size_t)t.n_roots * t.n_vertices;
+    t.dist.resize(rn); t.hops.resize(rn); t.flags.resize(rn); t.mask.resize(rn * t.mask_words);
+    hspf_result out{t.dist.data(), t.hops.data(), t.flags.data(), t.mask.data(), t.mask_words, nullptr};
+    const int rc = hspf_run_failures(ctx_, g.raw(), roots.data(), failures.data(), t.n_roots, run_flags, &out);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_failures (") + hspf_last_error(ctx_) + ")");
+    hspf_get_stats(ctx_, &t.stats);
+    return t;
+  }
+  hspf_stats run_failures_device(const Graph &g, const std::vector<uint32_t> &roots, const std::vector<hspf_failure> &failures, uint32_t run_flags,
+                                 const hspf_result &out_device) {
+    if (failures.size() != roots.size()) throw Error(HSPF_E_INVAL, "run_failures_device: one hspf_failure per root");
+    hspf_result out = out_device;
+    const int rc = hspf_run_failures_device(ctx_, g.raw(), roots.data(), failures.data(), (uint32_t)roots.size(), run_flags, &out);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_failures_device (") + hspf_last_error(ctx_) + ")");
+    hspf_stats st{};
+    hspf_get_stats(ctx_, &st);
+    return st;
+  }
+
   // ABI 7: packed results — a quarter of hspf_run's bytes over the bus.  `reuse`: a PackedTables of an earlier run whose
   // buffer is taken over when it is large enough.  Throws Error with code HSPF_E_NO_PACKED when the run's results do not
   // fit packed words (more than 24 first-hop slots): the caller then uses run().

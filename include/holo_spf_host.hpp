@@ -30,6 +30,7 @@ struct Tables {                       // row-major [root][vertex] results of one
   std::vector<uint64_t> mask;
 };
 struct SlotTable { std::vector<uint32_t> vertex, base; uint32_t total = 0; };
+struct Failure { uint32_t kind = HSPF_FAIL_NONE, arg = 0; };   // one row of run_failures(): hspf_failure
 
 class Graph {                         // one uploaded graph (device resident for the product engine)
  public:
@@ -313,6 +314,12 @@ class Engine {
                                               const std::vector<uint32_t> &, const std::vector<uint8_t> &, uint32_t, std::vector<uint32_t> &,
                                               std::vector<uint32_t> &, std::vector<uint32_t> &, std::vector<uint32_t> &, std::vector<uint8_t> &) { return nullptr; }
   virtual Tables run(Graph &g, const std::vector<uint32_t> &roots, uint32_t run_flags) = 0;
+  // Failure scenarios (hspf_run_failures): row r = the run of roots[r] with failures[r] applied, the graph untouched; mask_words as
+  // for run() on `roots`.  The default: not supported (an engine without the call; run_failures_sequential() below is the loop
+  // itself for a caller that holds the CSR).
+  virtual Tables run_failures(Graph &, const std::vector<uint32_t> & /*roots*/, const std::vector<Failure> & /*failures*/, uint32_t /*run_flags*/) {
+    throw std::runtime_error("run_failures: not supported by this engine");
+  }
   virtual SlotTable slot_table(Graph &g, uint32_t root) = 0;
   // whole rows replaced (hspf_graph_patch): vertices strictly ascending, rows[i] = (col, metric) of vertices[i]
   virtual void patch(Graph &g, const std::vector<uint32_t> &vertices,
@@ -404,6 +411,102 @@ inline void splice_rows(std::vector<uint32_t> &row_ptr, std::vector<uint32_t> &c
   copy_stretch(n);
   nrp[n] = (uint32_t)out;
   row_ptr.swap(nrp); col.swap(ncol); metric.swap(nmet);
+}
+
+// The host twin of hspf_run_failures: the sequential SPF loop on the caller's CSR with the two skips — the
+// root's failed link, and every link into the excluded vertex (which is then never labelled, never popped, never expanded).  Pops in
+// (distance, vertex) order; flags are HSPF_RF_IN_SPT alone.  Throws std::invalid_argument where the C call returns HSPF_E_INVAL.
+inline Tables run_failures_sequential(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                                      const std::vector<uint8_t> &vflags, uint32_t max_path_metric, const std::vector<uint32_t> &roots,
+                                      const std::vector<Failure> &failures, uint32_t run_flags) {
+  const uint32_t n = (uint32_t)vflags.size(), R = (uint32_t)roots.size();
+  if (failures.size() != roots.size()) throw std::invalid_argument("run_failures: one failure per root");
+  if (run_flags & (HSPF_RUN_POP_RANK | HSPF_RUN_COUNT_ROWS)) throw std::invalid_argument("run_failures: HSPF_RUN_POP_RANK / HSPF_RUN_COUNT_ROWS are not accepted");
+  for (uint32_t r = 0; r < R; ++r) {
+    if (roots[r] == HSPF_NO_ROOT) continue;
+    if (roots[r] >= n) throw std::invalid_argument("run_failures: root out of range");
+    const Failure &f = failures[r];
+    if (f.kind == HSPF_FAIL_ROOT_LINK) { if (f.arg >= row_ptr[roots[r] + 1] - row_ptr[roots[r]]) throw std::invalid_argument("run_failures: link position beyond the root's row"); }
+    else if (f.kind == HSPF_FAIL_VERTEX) { if (f.arg >= n || f.arg == roots[r]) throw std::invalid_argument("run_failures: excluded vertex out of range or the root"); }
+    else if (f.kind != HSPF_FAIL_NONE) throw std::invalid_argument("run_failures: unknown failure kind");
+  }
+  // the two-way check, once: link k of u's row is kept when its target lists u
+  std::vector<uint8_t> twoway(col.size(), 0);
+  for (uint32_t u = 0; u < n; ++u)
+    for (uint32_t k = row_ptr[u]; k < row_ptr[u + 1]; ++k) {
+      const uint32_t t = col[k];
+      for (uint32_t k2 = row_ptr[t]; k2 < row_ptr[t + 1] && !twoway[k]; ++k2) twoway[k] = col[k2] == u;
+    }
+  // slot bases of a root: H = [root] ++ networks reached through networks only, over kept links in row order
+  std::vector<uint32_t> base(n);
+  auto slots_of = [&](uint32_t root) {
+    std::fill(base.begin(), base.end(), 0xFFFFFFFFu);
+    std::vector<uint32_t> q{root};
+    base[root] = 0;
+    uint32_t total = row_ptr[root + 1] - row_ptr[root];
+    for (size_t qi = 0; qi < q.size(); ++qi)
+      for (uint32_t k = row_ptr[q[qi]]; k < row_ptr[q[qi] + 1]; ++k) {
+        const uint32_t t = col[k];
+        if (!twoway[k] || !(vflags[t] & HSPF_VF_NETWORK) || base[t] != 0xFFFFFFFFu) continue;
+        base[t] = total; total += row_ptr[t + 1] - row_ptr[t];
+        q.push_back(t);
+      }
+    return total;
+  };
+  Tables t;
+  t.n_roots = R; t.n_vertices = n; t.mask_words = 1;
+  for (uint32_t r = 0; r < R; ++r) if (roots[r] != HSPF_NO_ROOT) t.mask_words = std::max(t.mask_words, (slots_of(roots[r]) + 63u) / 64u);
+  const uint32_t W = t.mask_words;
+  const size_t rn = (size_t)R * n;
+  t.dist.assign(rn, HSPF_DIST_INF); t.hops.assign(rn, 0); t.flags.assign(rn, 0); t.mask.assign(rn * W, 0);
+  for (uint32_t r = 0; r < R; ++r) {
+    const uint32_t root = roots[r];
+    if (root == HSPF_NO_ROOT) continue;
+    const uint32_t fpos = failures[r].kind == HSPF_FAIL_ROOT_LINK ? failures[r].arg : 0xFFFFFFFFu;
+    const uint32_t fvtx = failures[r].kind == HSPF_FAIL_VERTEX ? failures[r].arg : 0xFFFFFFFFu;
+    slots_of(root);
+    uint32_t *dist = t.dist.data() + (size_t)r * n;
+    uint16_t *hops = t.hops.data() + (size_t)r * n, *flags = t.flags.data() + (size_t)r * n;
+    uint64_t *mask = t.mask.data() + (size_t)r * n * W;
+    std::map<std::pair<uint32_t, uint32_t>, char> cand;            // (distance, vertex): the reference's ordered candidate list
+    dist[root] = 0; cand[{0u, root}] = 1;
+    while (!cand.empty()) {
+      const uint32_t v = cand.begin()->first.second;
+      cand.erase(cand.begin());
+      flags[v] = HSPF_RF_IN_SPT;
+      const uint8_t vf = vflags[v];
+      const uint16_t vh = hops[v];
+      if (vf & HSPF_VF_NO_EXPAND) continue;
+      if (vh != 0 && !(vf & HSPF_VF_NETWORK) && !(run_flags & HSPF_RUN_IGNORE_OVERLOAD) && (vf & HSPF_VF_NO_TRANSIT)) continue;
+      for (uint32_t k = row_ptr[v]; k < row_ptr[v + 1]; ++k) {
+        if (!twoway[k]) continue;
+        const uint32_t tv = col[k];
+        if (flags[tv] & HSPF_RF_IN_SPT) continue;
+        if (tv == fvtx || (v == root && k - row_ptr[v] == fpos)) continue;      // the two skips
+        const uint64_t s64 = (uint64_t)dist[v] + metric[k];
+        const uint32_t d = s64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)s64;
+        if (d > max_path_metric) continue;
+        const bool on_cand = cand.count({dist[tv], tv}) != 0;
+        if (on_cand && d > dist[tv]) continue;
+        if (!on_cand || d < dist[tv]) {
+          if (on_cand) cand.erase({dist[tv], tv});
+          dist[tv] = d;
+          hops[tv] = (vflags[tv] & HSPF_VF_NETWORK) ? vh : (uint16_t)(vh == 0xFFFFu ? 0xFFFFu : vh + 1u);
+          std::fill(mask + (size_t)tv * W, mask + (size_t)(tv + 1) * W, 0ull);
+          cand[{d, tv}] = 1;
+        }
+        if (vh == 0) {
+          if (!(vflags[tv] & HSPF_VF_NETWORK) || (run_flags & HSPF_RUN_NET_NEXTHOPS)) {
+            const uint32_t sl = base[v] + (k - row_ptr[v]);
+            mask[(size_t)tv * W + sl / 64u] |= 1ull << (sl % 64u);
+          }
+        } else {
+          for (uint32_t w = 0; w < W; ++w) mask[(size_t)tv * W + w] |= mask[(size_t)v * W + w];
+        }
+      }
+    }
+  }
+  return t;
 }
 
 // ---- addresses and prefixes (BTreeMap<IpNetwork, _> / BTreeMap<IpAddr, _> order) -----------------------------------
@@ -698,6 +801,23 @@ class HipEngine : public Engine {
     return t;
   }
   bool use_packed = true;              // false: hspf_run for every run (the A/B of tests and of the end-to-end timing)
+  Tables run_failures(Graph &gr, const std::vector<uint32_t> &roots, const std::vector<Failure> &failures, uint32_t run_flags) override {
+    hspf_graph *g = static_cast<HipGraph &>(gr).g;
+    if (failures.size() != roots.size()) throw std::runtime_error("run_failures: one failure per root");
+    Tables t;
+    t.n_roots = (uint32_t)roots.size();
+    t.n_vertices = hspf_graph_n_vertices(g);
+    int rc = hspf_mask_words(ctx_, g, roots.data(), t.n_roots, &t.mask_words);
+    if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_mask_words: ") + hspf_last_error(ctx_));
+    const size_t rn = (size_t)t.n_roots * t.n_vertices;
+    t.dist.resize(rn); t.hops.resize(rn); t.flags.resize(rn); t.mask.resize(rn * t.mask_words);
+    std::vector<hspf_failure> ff;
+    for (const Failure &f : failures) ff.push_back(hspf_failure{f.kind, f.arg});
+    hspf_result out{t.dist.data(), t.hops.data(), t.flags.data(), t.mask.data(), t.mask_words, nullptr};
+    rc = hspf_run_failures(ctx_, g, roots.data(), ff.data(), t.n_roots, run_flags, &out);
+    if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_run_failures: ") + hspf_last_error(ctx_));
+    return t;
+  }
   SlotTable slot_table(Graph &gr, uint32_t root) override {
     hspf_graph *g = static_cast<HipGraph &>(gr).g;
     SlotTable st;

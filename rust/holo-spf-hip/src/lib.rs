@@ -2228,6 +2228,33 @@ impl Engine {
         Ok(Tables { n_roots: roots.len() as u32, n_vertices: g.n, repr: Repr::Full { words, dist, hops, flags, mask } })
     }
 
+    /// `hspf_mask_words` + `hspf_run_failures`: `run_failures_device` with the four arrays in host vectors.
+    pub fn run_failures(&self, g: &Graph<'_>, roots: &[u32], failures: &[sys::hspf_failure], run_flags: u32) -> Result<Tables<'_>, Error> {
+        if failures.len() != roots.len() {
+            return Err(self.err(sys::HSPF_E_INVAL));
+        }
+        let mut words = 0u32;
+        let rc = unsafe { sys::hspf_mask_words(self.ctx, g.g, roots.as_ptr(), roots.len() as u32, &mut words) };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let cells = roots.len() * g.n as usize;
+        let (mut dist, mut hops, mut flags, mut mask) = (vec![0u32; cells], vec![0u16; cells], vec![0u16; cells], vec![0u64; cells * words as usize]);
+        let mut out = sys::hspf_result {
+            dist: dist.as_mut_ptr(),
+            hops: hops.as_mut_ptr(),
+            vflags_out: flags.as_mut_ptr(),
+            first_hop_mask: mask.as_mut_ptr(),
+            n_mask_words: words,
+            pop_rank: ptr::null_mut(),
+        };
+        let rc = unsafe { sys::hspf_run_failures(self.ctx, g.g, roots.as_ptr(), failures.as_ptr(), roots.len() as u32, run_flags, &mut out) };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(Tables { n_roots: roots.len() as u32, n_vertices: g.n, repr: Repr::Full { words, dist, hops, flags, mask } })
+    }
+
     /// `hspf_run_device`: the tables stay in HBM (input of `routes_device` / `ancestors_device`).
     pub fn run_device(&self, g: &Graph<'_>, roots: &[u32], run_flags: u32) -> Result<DeviceTables<'_>, Error> {
         let mut words = 0u32;
@@ -2254,6 +2281,43 @@ impl Engine {
             pop_rank: ptr::null_mut(),
         };
         let rc = unsafe { sys::hspf_run_device(self.ctx, g.g, roots.as_ptr(), roots.len() as u32, run_flags, &mut out) };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(t)
+    }
+
+    /// `hspf_run_failures_device`: row r is the run of `roots[r]` with `failures[r]` applied (`HSPF_FAIL_ROOT_LINK`: a position in
+    /// the root's own row; `HSPF_FAIL_VERTEX`: a vertex other than the root), the graph untouched — the post-convergence trees of
+    /// a router's links and neighbours in one batch.  The tables stay in HBM like `run_device`'s.
+    pub fn run_failures_device(&self, g: &Graph<'_>, roots: &[u32], failures: &[sys::hspf_failure], run_flags: u32) -> Result<DeviceTables<'_>, Error> {
+        if failures.len() != roots.len() {
+            return Err(self.err(sys::HSPF_E_INVAL));
+        }
+        let mut words = 0u32;
+        let rc = unsafe { sys::hspf_mask_words(self.ctx, g.g, roots.as_ptr(), roots.len() as u32, &mut words) };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        let cells = roots.len() * g.n as usize;
+        let t = DeviceTables {
+            n_roots: roots.len() as u32,
+            n_vertices: g.n,
+            words,
+            dist: self.device_alloc(cells * 4)?,
+            hops: self.device_alloc(cells * 2)?,
+            flags: self.device_alloc(cells * 2)?,
+            mask: self.device_alloc(cells * 8 * words as usize)?,
+        };
+        let mut out = sys::hspf_result {
+            dist: t.dist.p as *mut u32,
+            hops: t.hops.p as *mut u16,
+            vflags_out: t.flags.p as *mut u16,
+            first_hop_mask: t.mask.p as *mut u64,
+            n_mask_words: words,
+            pop_rank: ptr::null_mut(),
+        };
+        let rc = unsafe { sys::hspf_run_failures_device(self.ctx, g.g, roots.as_ptr(), failures.as_ptr(), roots.len() as u32, run_flags, &mut out) };
         if rc != sys::HSPF_OK {
             return Err(self.err(rc));
         }
