@@ -131,6 +131,12 @@ class HspfRlfaNodeOut(ctypes.Structure):
                 ("nd_set", ctypes.c_void_p), ("nd_coverage", ctypes.c_void_p)]
 
 
+class HspfTilfaPcOut(ctypes.Structure):
+    _fields_ = [("tp_kind", ctypes.c_void_p), ("tp_p", ctypes.c_void_p), ("tp_via", ctypes.c_void_p), ("tp_q", ctypes.c_void_p),
+                ("tp_n_adj", ctypes.c_void_p), ("tp_hop_pos", ctypes.c_void_p), ("tp_hop_head", ctypes.c_void_p), ("tp_metric", ctypes.c_void_p),
+                ("tp_flags", ctypes.c_void_p), ("tp_coverage", ctypes.c_void_p)]
+
+
 class HspfTilfaNodeSel(ctypes.Structure):
     _fields_ = [("tq_q", ctypes.c_void_p), ("tq_p", ctypes.c_void_p), ("tq_link", ctypes.c_void_p), ("tq_via", ctypes.c_void_p),
                 ("tq_metric", ctypes.c_void_p), ("tq_count", ctypes.c_void_p)]
@@ -274,6 +280,11 @@ SYMBOLS = [
     ("hspf_tilfa_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
                                          ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfTilfaOut)]),
+    # TI-LFA repairs along the post-convergence path
+    ("hspf_tilfa_pc_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                            u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HspfTilfaPcOut)]),
     # per-prefix backup routes
     ("hspf_routes_backup_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.POINTER(HspfLfaProtect), ctypes.c_uint32, ctypes.c_uint32,

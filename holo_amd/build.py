@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libholo_spf_hip.so")
 SOURCES = ["spf_capi.hip", "hub_sort.hip"]
 DEPS = ["spf_capi.hip", "spf_kernels.hip.h", "spf_repair.hip.h", "spf_frr.hip.h", "spf_frr_common.hip.h", "spf_lfa.hip.h", "spf_lfa_ecmp.hip.h", "spf_rlfa.hip.h",
-        "spf_tilfa.hip.h", "spf_backup.hip.h", "spf_backup_ecmp.hip.h", "spf_rlfa_node.hip.h", "spf_tilfa_node.hip.h", "spf_backup_node.hip.h", "spf_srlg.hip.h", "spf_backup_srlg.hip.h", "graph_build.hip.h", "graph_patch.hip.h", "spf_multi.hip.h", "hub_sort.hip", "hub_sort.h",
+        "spf_tilfa.hip.h", "spf_tilfa_pc.hip.h", "spf_backup.hip.h", "spf_backup_ecmp.hip.h", "spf_rlfa_node.hip.h", "spf_tilfa_node.hip.h", "spf_backup_node.hip.h", "spf_srlg.hip.h", "spf_backup_srlg.hip.h", "graph_build.hip.h", "graph_patch.hip.h", "spf_multi.hip.h", "hub_sort.hip", "hub_sort.h",
         os.path.join("..", "..", "include", "holo_spf_hip.h")]
 
 

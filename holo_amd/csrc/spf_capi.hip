@@ -218,6 +218,7 @@ struct hspf_ctx {
   DevBuf evs_scr, evs_rec;
   DevBuf rlfa_key;                                   // hspf_rlfa_device: the selection keys, one u64 per (protected root, slot)
   DevBuf tilfa_key, tilfa_tw;                        // hspf_tilfa_device: its selection keys | the graph's two-way flags, one byte per link
+  DevBuf tipc_tab;                                   // hspf_tilfa_pc_device: the staged rows of pc_dist per (protected root, slot), their scratch indices, the list of pairs
   DevBuf rnode_part, rnode_map;                      // hspf_rlfa_node_*: the workgroups' partial lists | vertex -> PQ-node row, then the staged root list
   DevBuf tnode_cell;                                 // hspf_tilfa_node_select_device: the cheapest way into q, one u64 per (protected root, candidate, vertex); the
                                                      // partial lists, the row map and the two-way flags are rnode_part / rnode_map / tilfa_tw
@@ -879,7 +880,7 @@ void hspf_shutdown(hspf_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf *b : {&ctx->dist, &ctx->hv, &ctx->mask, &ctx->lane_flags, &ctx->changed,
                     &ctx->st64, &ctx->stamp, &ctx->hnb, &ctx->o_dist, &ctx->o_hops, &ctx->o_flags,
-                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->fail_lanes, &ctx->fail_flag, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->lan_tab, &ctx->lan_scal, &ctx->srlg_tab, &ctx->srlg_scal, &ctx->ea_scr, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw, &ctx->rnode_part, &ctx->rnode_map, &ctx->tnode_cell})
+                    &ctx->o_mask, &ctx->o_rank, &ctx->ex_list, &ctx->ex_heap, &ctx->ex_pos, &ctx->rp_rank, &ctx->dyn_part, &ctx->rp_trace, &ctx->rp_z, &ctx->rp_ord, &ctx->rp_work, &ctx->rp_status, &ctx->pf_ptr, &ctx->pf_vtx, &ctx->pf_met, &ctx->pf_org, &ctx->gb_kx, &ctx->gb, &ctx->gb_pa, &ctx->gb_delta, &ctx->gb_hub, &ctx->giant_part, &ctx->leaf_jobs, &ctx->fail_lanes, &ctx->fail_flag, &ctx->kcnt, &ctx->pack, &ctx->evs_scr, &ctx->evs_rec, &ctx->swcnt, &ctx->o_pack, &ctx->pk_flag, &ctx->xcd_ctl, &ctx->lfa_tab, &ctx->lfa_scal, &ctx->lan_tab, &ctx->lan_scal, &ctx->srlg_tab, &ctx->srlg_scal, &ctx->ea_scr, &ctx->rlfa_key, &ctx->tilfa_key, &ctx->tilfa_tw, &ctx->tipc_tab, &ctx->rnode_part, &ctx->rnode_map, &ctx->tnode_cell})
     release(*b);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   for (auto &e : ctx->ev_stage) if (e) (void)hipEventDestroy(e);

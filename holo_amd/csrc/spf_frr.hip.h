@@ -3,12 +3,13 @@
 //   alternates:            hspf_lfa_device, hspf_lfa_lan_device, hspf_lfa_srlg_device (lfa_call); hspf_lfa_ecmp_device (lfa_ecmp_call)
 //   remote alternates:     hspf_rlfa_device, hspf_rlfa_lan_device, hspf_rlfa_srlg_device (rlfa_call)
 //   two-segment repairs:   hspf_tilfa_device
+//   post-convergence path: hspf_tilfa_pc_device
 //   per-prefix backups:    hspf_routes_backup_device, hspf_routes_backup_lan_device, hspf_routes_backup_srlg_device (routes_backup);
 //                          hspf_routes_backup_ecmp_device, hspf_routes_backup_ecmp_srlg_device (backup_ecmp_call)
 //   node protection:       hspf_rlfa_node_select_device, hspf_rlfa_node_device, hspf_tilfa_node_select_device, hspf_tilfa_node_device,
 //                          hspf_routes_backup_node_device
 //
-// The 18 device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and one
+// The 19 device calls share one staged structure — the candidate tables of the protected roots (spf_frr_common.hip.h) — and one
 // frame, FrrCall: its checks, stage(), the call's memsets, gather() where the kernels need the per-root scalars, the call's own
 // kernels, finish().  A call that leaves any other way drains the stream in the frame's destructor.  `fn` names the calling entry
 // point in hspf_last_error.
@@ -19,6 +20,7 @@
 #include "spf_lfa.hip.h"
 #include "spf_rlfa.hip.h"
 #include "spf_tilfa.hip.h"
+#include "spf_tilfa_pc.hip.h"
 #include "spf_backup.hip.h"
 #include "spf_rlfa_node.hip.h"
 #include "spf_tilfa_node.hip.h"
@@ -304,7 +306,7 @@ struct FrrCall {
   const uint32_t *const dist; const uint16_t *const flags; const uint64_t *const mask;
   const hspf_lfa_protect *const prot; const uint32_t n_prot;
   size_t stride = 0, n_slots = 0;                       // 64 * W, n_prot * stride (check_slots)
-  std::vector<uint32_t> tab, mtab;                      // sources of the staged copies: the candidate tables, the LAN or member block
+  std::vector<uint32_t> tab, mtab;                      // sources of the staged copies: the candidate tables; the LAN or member block (hspf_tilfa_pc_device: its row block)
   std::vector<uint8_t> tw;                              // the same: the two-way bytes where a patch moved rows
   uint32_t max_k = 0, max_nms = 0;
   size_t max_gather = 0;
@@ -312,13 +314,17 @@ struct FrrCall {
   SrlgArgs sa{};
   uint32_t tiles_x = 0; size_t n_tiles = 0; uint32_t *d_total = nullptr;      // the CSR stream of the ECMP calls (stream_open)
   uint32_t *ymap = nullptr; uint32_t n_yrows = 0;       // the listed nodes' vertex -> row map (node_map)
+  void *owned = nullptr;                                // device scratch of this call alone (scratch): released with the frame
   bool enqueued = false, finished = false;
 
   FrrCall(hspf_ctx *ctx, const char *fn, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev,
           const uint16_t *flags_dev, const uint64_t *mask_dev, const hspf_lfa_protect *prot, uint32_t n_prot)
       : ctx(ctx), fn(fn), n(n_vertices), R(n_rows), W(n_mask_words), dist(dist_dev), flags(flags_dev), mask(mask_dev), prot(prot), n_prot(n_prot) {}
   FrrCall(const FrrCall &) = delete;
-  ~FrrCall() { if (enqueued && !finished) (void)hipStreamSynchronize(ctx->stream); }
+  ~FrrCall() {
+    if (enqueued && !finished) (void)hipStreamSynchronize(ctx->stream);
+    if (owned) (void)hipFree(owned);
+  }
 
   // -- checks: nothing is staged, written or launched before the last of them
   int bad(const std::string &what) const { return frr_bad(ctx, fn, what); }
@@ -392,6 +398,14 @@ struct FrrCall {
     return mode == FrrProt::Srlg ? srlg_stage(ctx, fn, prot, srlg, n_prot, mtab, &sa, &max_gather, &max_nms) : HSPF_OK;
   }
   int stage_twoway(const hspf_graph *g) { enqueued = true; return tw_stage(ctx, fn, g, tw); }
+  // Scratch that the call sizes and the frame releases (one per call): too large to stay with the context.  Nothing is enqueued
+  // on it yet when this fails; the destructor frees it behind the drained stream.
+  int scratch(size_t bytes, void **out) {
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipMalloc(&owned, std::max<size_t>(bytes, 8)));
+    *out = owned;
+    return HSPF_OK;
+  }
   // The vertex -> row map of the listed nodes (after check_y_roots): ctx->rnode_map sized and cleared, the list copied behind it
   // (the caller's: it lives through the call).  launch_node_map() fills the map; a frame's own memsets may stand between the two.
   int node_map(const uint32_t *y_roots, uint32_t n_y) {
@@ -918,6 +932,74 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
     hipLaunchKernelGGL(k_tilfa_final, dim3((uint32_t)((f.n_slots + 255) / 256)), dim3(256), 0, s, a, n_prot);
     hipLaunchKernelGGL(k_tilfa_dest, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
     return f.finish("k_tilfa");
+  });
+}
+
+// ---- TI-LFA along the post-convergence path (include/holo_spf_hip.h "repairs along the post-convergence path"; kernels: spf_tilfa_pc.hip.h) ----
+static_assert(TIPC_MAX_ADJ == HSPF_TIPC_MAX_ADJ && TIPC_COV == HSPF_TIPC_COVERAGE_WORDS && TIPC_LFA == HSPF_TIPC_D_LFA && TIPC_REPAIR == HSPF_TIPC_D_REPAIR &&
+              TIPC_NONE == HSPF_TIPC_D_NONE && TIPC_LONG == HSPF_TIPC_D_LONG && TIPC_LAN == HSPF_TIPC_D_LAN && TIPC_WALK == HSPF_TIPC_D_WALK &&
+              TIPC_F_ON_PC == HSPF_TIPC_ON_PC && TIPC_F_P_IS_ROOT == HSPF_TIPC_P_IS_ROOT && TIPC_F_Q_IS_DEST == HSPF_TIPC_Q_IS_DEST &&
+              TIPC_SRC_NT == hspf::SRC_NO_TRANSIT && TIPC_SRC_MASK == hspf::SRC_MASK, "the kernels' constants are the header's and the graph's");
+
+int hspf_tilfa_pc_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                         const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                         const uint8_t *space_flags_dev, const uint32_t *space_via_dev, const uint32_t *pc_dist_dev, uint32_t n_pc_rows,
+                         const uint32_t *pc_row, uint32_t run_flags, uint32_t max_walk, hspf_tilfa_pc_out *out_dev) {
+  if (!ctx) return HSPF_E_INVAL;
+  (void)lfa_flags;                                      // (eligibility and the overload rule of the spaces are in the space tables)
+  return guarded(ctx, [&]() -> int {
+    FrrCall f(ctx, "hspf_tilfa_pc_device", n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, prot, n_prot);
+    int rc;
+    if ((rc = f.check_ptrs(out_dev, g && rdist_dev, "NULL graph, table, prot or out pointer"))) return rc;
+    if (!space_flags_dev || !space_via_dev) return f.bad("NULL space_flags / space_via (the tables of hspf_rlfa_device are required)");
+    if (!pc_dist_dev || !pc_row) return f.bad("NULL pc_dist / pc_row (the rows of hspf_run_failures_device are required)");
+    if (!out_dev->tp_kind || !out_dev->tp_p || !out_dev->tp_via || !out_dev->tp_q || !out_dev->tp_n_adj || !out_dev->tp_hop_pos || !out_dev->tp_hop_head ||
+        !out_dev->tp_metric || !out_dev->tp_flags || !out_dev->tp_coverage)
+      return f.bad("NULL tp_kind / tp_p / tp_via / tp_q / tp_n_adj / tp_hop_pos / tp_hop_head / tp_metric / tp_flags / tp_coverage");
+    if ((rc = f.check_dims()) || (rc = f.check_graph(g))) return rc;
+    if (max_walk == 0 || max_walk > 65535u) return f.bad("max_walk outside 1 .. 65535");
+    if ((rc = f.check_slots())) return rc;
+    // the rows: given for candidate slots only, inside pc_dist; the staged block prow | pidx | plist
+    std::vector<uint32_t> &pt = f.mtab;
+    pt.assign(2 * f.n_slots, LFA_NONE);
+    for (uint32_t i = 0; i < n_prot; ++i) {
+      const hspf_lfa_protect &p = prot[i];
+      const std::string who = "protected root " + std::to_string(i) + ": ";
+      if (p.n_slots > f.stride) return f.bad(who + "n_slots > 64 * n_mask_words");      // (before nbr is read that far)
+      if (p.n_slots && !p.nbr) return f.bad(who + "NULL slot array");
+      for (uint32_t e = 0; e < f.stride; ++e) {
+        const size_t s = (size_t)i * f.stride + e;
+        const uint32_t r = pc_row[s];
+        if (r == HSPF_NO_ROOT) continue;
+        if (e >= p.n_slots || p.nbr[e] == HSPF_NO_ROOT) return f.bad(who + "pc_row given for slot " + std::to_string(e) + ", which is no candidate");
+        if (r >= n_pc_rows) return f.bad(who + "pc_row of slot " + std::to_string(e) + " >= n_pc_rows");
+        pt[s] = r; pt[f.n_slots + s] = (uint32_t)(pt.size() - 2 * f.n_slots); pt.push_back((uint32_t)s);
+      }
+    }
+    const size_t n_pairs = pt.size() - 2 * f.n_slots;
+    void *par = nullptr;
+    if ((rc = f.stage(FrrProt::Plain, nullptr, nullptr)) || (rc = ensure(ctx, ctx->tipc_tab, pt.size() * 4, false)) ||
+        (rc = f.scratch(n_pairs * n_vertices * sizeof(uint2), &par))) return rc;
+    hipStream_t s = f.stream();
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tipc_tab.p, pt.data(), pt.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(out_dev->tp_coverage, 0, (size_t)n_prot * HSPF_TIPC_COVERAGE_WORDS * 4, s));
+    TipcArgs a{};
+    a.n = n_vertices; a.W = n_mask_words; a.stride = (uint32_t)f.stride; a.ignore_overload = (run_flags & HSPF_RUN_IGNORE_OVERLOAD) ? 1u : 0u;
+    a.max_walk = max_walk; a.n_pairs = (uint32_t)n_pairs;
+    a.dist = dist_dev; a.flags = flags_dev; a.mask = mask_dev;
+    a.tab = (const uint32_t *)ctx->lfa_tab.p; a.alt_in = alt_flags_in_dev;
+    a.sflags = space_flags_dev; a.svia = space_via_dev; a.pc_dist = pc_dist_dev;
+    a.prow = (const uint32_t *)ctx->tipc_tab.p; a.pidx = a.prow + f.n_slots; a.plist = a.pidx + f.n_slots;
+    a.in_ptr = g->d_in_ptr; a.in_src = g->d_in_src; a.in_w = g->d_in_w; a.in_fpos = g->d_in_fpos; a.vflags = g->d_vflags;
+    a.par = (uint2 *)par;
+    a.tp_kind = out_dev->tp_kind; a.tp_n_adj = out_dev->tp_n_adj; a.tp_flags = out_dev->tp_flags; a.tp_p = out_dev->tp_p; a.tp_via = out_dev->tp_via;
+    a.tp_q = out_dev->tp_q; a.tp_hop_pos = out_dev->tp_hop_pos; a.tp_hop_head = out_dev->tp_hop_head; a.tp_metric = out_dev->tp_metric;
+    a.tp_cov = out_dev->tp_coverage;
+    const uint32_t n_tiles = (n_vertices + LFA_TILE - 1) / LFA_TILE;
+    if (n_pairs) hipLaunchKernelGGL(k_tipc_parent, dim3(n_tiles, (uint32_t)std::min<size_t>(n_pairs, 65535)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_tipc_walk, dim3(n_tiles, n_prot), dim3(256), 0, s, a);
+    return f.finish("k_tipc_walk");
   });
 }
 

@@ -67,6 +67,10 @@ TILFA_NONE, TILFA_NODE, TILFA_PAIR = 0, 1, 2                                  # 
 TILFA_D_LFA, TILFA_D_NODE, TILFA_D_PAIR, TILFA_D_NONE = 1, 2, 3, 4            # HSPF_TILFA_D_*: td_kind
 TILFA_COUNT_WORDS = 2
 TILFA_COVERAGE_WORDS = 5
+TIPC_MAX_ADJ = 4                                                              # HSPF_TIPC_MAX_ADJ
+TIPC_D_LFA, TIPC_D_REPAIR, TIPC_D_NONE, TIPC_D_LONG, TIPC_D_LAN, TIPC_D_WALK = 1, 2, 3, 4, 5, 6      # HSPF_TIPC_D_*: tp_kind
+TIPC_ON_PC, TIPC_P_IS_ROOT, TIPC_Q_IS_DEST = 0x01, 0x02, 0x04                 # HSPF_TIPC_*: tp_flags
+TIPC_COVERAGE_WORDS = 12
 BK_NO_ROUTE, BK_LOCAL, BK_ECMP, BK_LFA, BK_NODE, BK_PAIR, BK_NONE = 0, 1, 2, 3, 4, 5, 6      # HSPF_BK_*: bk_kind
 BK_COVERAGE_WORDS = 7
 BK_LAN_COVERAGE_WORDS = 9
@@ -368,6 +372,37 @@ class TilfaResult:
     ti_counts: np.ndarray    # [P, S, 2] u32 single nodes | usable (p, link) pairs
     td_kind: np.ndarray      # [P, N] u8  TILFA_D_* per destination with exactly one primary, 0 elsewhere
     td_coverage: np.ndarray  # [P, 5] u32
+
+
+@dataclass
+class TilfaPcResult:
+    """TI-LFA repairs along the post-convergence path of the protected roots of one tilfa_pc_device() call, on the host."""
+    tp_kind: np.ndarray      # [P, N] u8  TIPC_D_* per destination with exactly one primary, 0 elsewhere
+    tp_p: np.ndarray         # [P, N] u32, NO_ROOT: none
+    tp_via: np.ndarray       # [P, N] u32, RLFA_VIA_SELF or a slot; LFA_NO_SLOT: none, or p is the root
+    tp_q: np.ndarray         # [P, N] u32
+    tp_n_adj: np.ndarray     # [P, N] u8  0 .. TIPC_MAX_ADJ
+    tp_hop_pos: np.ndarray   # [P, N, 4] u32 position of the link in its tail's row, in the order p -> q
+    tp_hop_head: np.ndarray  # [P, N, 4] u32
+    tp_metric: np.ndarray    # [P, N] u32
+    tp_flags: np.ndarray     # [P, N] u8  TIPC_ON_PC | TIPC_P_IS_ROOT | TIPC_Q_IS_DEST
+    tp_coverage: np.ndarray  # [P, 12] u32
+
+    def segments(self, d: int, i: int = 0):
+        """The repair of destination d of protected root i: (via, p, [(tail, pos, head), ...], q) — the Node-SID of p out of `via`
+        (LFA_NO_SLOT: p is the root, no node segment), the Adj-SID of every listed link, then q's own path.  None unless
+        TIPC_D_REPAIR."""
+        if self.tp_kind[i, d] != TIPC_D_REPAIR:
+            return None
+        p, hops, tail = int(self.tp_p[i, d]), [], int(self.tp_p[i, d])
+        for h in range(int(self.tp_n_adj[i, d])):
+            head = int(self.tp_hop_head[i, d, h])
+            hops.append((tail, int(self.tp_hop_pos[i, d, h]), head))
+            tail = head
+        return int(self.tp_via[i, d]), p, hops, int(self.tp_q[i, d])
+
+
+TILFA_PC_FIELDS = ("tp_kind", "tp_p", "tp_via", "tp_q", "tp_n_adj", "tp_hop_pos", "tp_hop_head", "tp_metric", "tp_flags", "tp_coverage")
 
 
 @dataclass
@@ -1381,6 +1416,27 @@ class SpfContext:
         del keep
         self._check_rc("hspf_tilfa_device", rc)
 
+    def tilfa_pc_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
+                        protect, *, space_flags_ptr: int, space_via_ptr: int, pc_dist_ptr: int, n_pc_rows: int, pc_row, max_walk: int = 256,
+                        run_flags: int = 0, tp_kind_ptr: int, tp_p_ptr: int, tp_via_ptr: int, tp_q_ptr: int, tp_n_adj_ptr: int, tp_hop_pos_ptr: int,
+                        tp_hop_head_ptr: int, tp_metric_ptr: int, tp_flags_ptr: int, tp_coverage_ptr: int, alt_flags_in_ptr: int = 0,
+                        lfa_flags: int = 0) -> None:
+        """hspf_tilfa_pc_device(): per destination with one primary slot the repair that follows its post-convergence path — the
+        rows `pc_dist_ptr` [n_pc_rows, n] of a run_failures_device() on `graph`, pc_row [len(protect), 64 * mask_words] (host) naming
+        the row of each slot's FAIL_ROOT_LINK scenario (NO_ROOT: none).  The other inputs are tilfa_device()'s; run_flags are the
+        failure run's.  All `*_ptr` are device pointers."""
+        arr, keep = self._protect_array(protect, "tilfa_pc_device")
+        rows = None if pc_row is None else np.ascontiguousarray(pc_row, dtype=np.uint32)
+        if rows is not None and rows.size != len(protect) * 64 * mask_words:
+            raise ValueError("tilfa_pc_device: pc_row holds 64 * mask_words entries per protected root")
+        out = L.HspfTilfaPcOut(tp_kind_ptr or None, tp_p_ptr or None, tp_via_ptr or None, tp_q_ptr or None, tp_n_adj_ptr or None, tp_hop_pos_ptr or None,
+                               tp_hop_head_ptr or None, tp_metric_ptr or None, tp_flags_ptr or None, tp_coverage_ptr or None)
+        rc = self.lib.hspf_tilfa_pc_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                           rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None,
+                                           space_via_ptr or None, pc_dist_ptr or None, n_pc_rows, None if rows is None else _u32(rows), run_flags, max_walk, ctypes.byref(out))
+        del keep
+        self._check_rc("hspf_tilfa_pc_device", rc)
+
     def routes_backup_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                              pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
                              bk_metric_ptr: int, bk_flags_ptr: int, bk_coverage_ptr: int, bk_cand_mask_ptr: int = 0, bk_node_mask_ptr: int = 0,
@@ -1732,13 +1788,20 @@ class SpfContext:
         Against shared-risk link groups: tilfa_srlg()."""
         return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True, lan_protect=lan_protect, lan_spaces=lan_protect)
 
+    def tilfa_pc(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False, max_walk: int = 256):
+        """TI-LFA repairs along the post-convergence path of one root, start to finish: the chain of tilfa(), ONE
+        run_failures_device() with the FAIL_ROOT_LINK scenario of every candidate slot, then tilfa_pc_device() on those rows and
+        the same space tables; nothing leaves the device before the end.  Returns what tilfa() returns plus a TilfaPcResult."""
+        return self._rlfa(graph, root, run_flags, lfa_flags, True, symmetric, True, pc=max_walk)
+
     def _rlfa(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool, backup=None,
-              lan_protect: bool = False, lan_spaces: bool = False, node=None, ecmp: bool = False):
+              lan_protect: bool = False, lan_spaces: bool = False, node=None, ecmp: bool = False, pc=None):
         """The chain behind rlfa(), tilfa() and backup_routes().  backup: None, or (pfx_ptr, pfx_vertex, pfx_metric, flags) — then
         the routes and their backups are derived on the same rows (the remote calls are skipped unless `tilfa`).  lan_spaces
         (with lan_protect): rlfa_lan_device() instead of rlfa_device(), and LFA_LAN_SAFE_REPAIRS for the backups.  node (with backup):
         None, or (max_pq, max_pairs) of backup_routes(node_protect=True) — then _backup_node_tail() runs on the same rows.  ecmp (with
-        backup): _backup_ecmp_tail() runs on the same rows."""
+        backup): _backup_ecmp_tail() runs on the same rows.  pc (with tilfa): None, or max_walk of tilfa_pc() — then the failure rows of
+        the candidate slots and tilfa_pc_device() follow tilfa_device()."""
         if lan_spaces and (not lan_protect or symmetric):
             raise ValueError("the LAN-safe remote calls need lan_protect and the transposed run (symmetric=False)")
         plan = self._frr_plan(graph, root, lan_protect)
@@ -1764,8 +1827,15 @@ class SpfContext:
                           bk_kind=((1, NP), np.uint8), bk_primary=((1, NP), np.uint32), bk_slot=((1, NP), np.uint32), bk_metric=((1, NP), np.uint32),
                           bk_flags=((1, NP), np.uint8), bk_cand_mask=((1, NP, W), np.uint64), bk_node_mask=((1, NP, W), np.uint64),
                           bk_coverage=((1, BK_LAN_COVERAGE_WORDS if lan_protect else BK_COVERAGE_WORDS), np.uint32))
+        pc_slots = np.flatnonzero(cand.nbr != NO_ROOT).astype(np.uint32) if pc is not None else None
+        if pc is not None:
+            A = TIPC_MAX_ADJ
+            shapes.update(tp_kind=((1, n), np.uint8), tp_p=((1, n), np.uint32), tp_via=((1, n), np.uint32), tp_q=((1, n), np.uint32),
+                          tp_n_adj=((1, n), np.uint8), tp_hop_pos=((1, n, A), np.uint32), tp_hop_head=((1, n, A), np.uint32),
+                          tp_metric=((1, n), np.uint32), tp_flags=((1, n), np.uint8), tp_coverage=((1, TIPC_COVERAGE_WORDS), np.uint32))
         host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
+        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n,
+                     pc_dist=4 * len(pc_slots) * n if pc is not None else 0)
         sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
         with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
             self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
@@ -1798,6 +1868,16 @@ class SpfContext:
                 self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
                                   space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
                                   **{k + "_ptr": dev[k] for k in ti_names})
+            if pc is not None:
+                pc_row = np.full((1, S), NO_ROOT, np.uint32)
+                pc_row[0, pc_slots] = np.arange(len(pc_slots), dtype=np.uint32)
+                if len(pc_slots):
+                    fails = np.stack([np.full(len(pc_slots), FAIL_ROOT_LINK, np.uint32), cand.root_link[pc_slots].astype(np.uint32)], axis=1)
+                    self.run_failures_device(graph, np.full(len(pc_slots), root, np.uint32), fails, run_flags, dist_ptr=dev["pc_dist"])
+                self.tilfa_pc_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
+                                     space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], pc_dist_ptr=dev["pc_dist"] or dev["dist"],
+                                     n_pc_rows=len(pc_slots), pc_row=pc_row, max_walk=pc, run_flags=run_flags, alt_flags_in_ptr=dev["aflags"],
+                                     lfa_flags=lfa_flags, **{k + "_ptr": dev[k] for k in TILFA_PC_FIELDS})
             if backup is not None:
                 self.routes_device(n, 1, W, dev["dist"], dev["flags"], dev["mask"], backup[0], backup[1], backup[2], flags=backup[3],
                                    best_metric_ptr=dev["best_metric"], best_entry_ptr=dev["best_entry"], nexthop_mask_ptr=dev["nexthop_mask"])
@@ -1815,6 +1895,8 @@ class SpfContext:
             lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"], lan=plan.lan)
             rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
                             host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
+            if pc is not None:
+                return cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names)), TilfaPcResult(*(host[k] for k in TILFA_PC_FIELDS))
             return (cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, lfa, rl)
 
     def rlfa_node_select_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,

@@ -1167,8 +1167,9 @@ int hspf_rlfa_srlg_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertice
  *
  * OUT OF SCOPE: adjacencies across a LAN pseudonode (p -> network vertex -> q is not offered: q must be a router in p's own
  * row); node protection (one-segment node-protecting repairs: hspf_rlfa_node_device, below; two-segment ones:
- * hspf_tilfa_node_select_device / hspf_tilfa_node_device, below that); segment lists longer than two; post-convergence-path
- * selection among equal-cost repairs. */
+ * hspf_tilfa_node_select_device / hspf_tilfa_node_device, below that); repairs that end at the destination instead of at E,
+ * follow its post-convergence path, or need more than one adjacency (hspf_tilfa_pc_device, below: per destination, up to
+ * HSPF_TIPC_MAX_ADJ adjacencies). */
 #define HSPF_TILFA_NONE           0u            /* ti_kind */
 #define HSPF_TILFA_NODE           1u
 #define HSPF_TILFA_PAIR           2u
@@ -1193,6 +1194,108 @@ int hspf_tilfa_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, u
                       const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
                       const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                       const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out *out_dev);
+
+/* ---- TI-LFA repairs along the post-convergence path (link protection): new symbol, same ABI number ---------------------------
+ * hspf_tilfa_device repairs a LINK: its segment list ends at the far router E, whatever the destination, and it offers one
+ * adjacency at most.  The TI-LFA draft asks for the repair of each DESTINATION to follow the path that destination has after
+ * convergence.  hspf_tilfa_pc_device walks that path — the row hspf_run_failures_device gives for the failed link — from D up to
+ * S and cuts it into: a Node-SID, up to HSPF_TIPC_MAX_ADJ Adj-SIDs, and D's own shortest path from there.
+ *
+ * Inputs.  Everything hspf_tilfa_device takes, with the same meaning (`g` the FORWARD graph; space_flags_dev / space_via_dev
+ * REQUIRED), and
+ *   pc_dist_dev [n_pc_rows][n_vertices]  DEVICE: the `dist` table of an hspf_run_failures_device call on `g`.
+ *   pc_row [n_prot][stride]              HOST, u32: for slot e of protected root i the row of pc_dist_dev that holds
+ *                                        {HSPF_FAIL_ROOT_LINK, root_link[e]} of that root; HSPF_NO_ROOT: no row.
+ *   run_flags                            those the failure run was given; only HSPF_RUN_IGNORE_OVERLOAD is looked at.
+ *   max_walk                             1 .. 65535: the vertices a walk may visit.
+ *
+ * Per protected root S and destination D != S in S's SPT with exactly ONE primary slot e (the population of td_kind);
+ * c = cost[e], pc = row pc_row[e].  Every sum is evaluated in 64 bits; totals saturate at 0xFFFFFFFE as ti_metric.
+ *   parent(v)   for v != S with pc[v] != HSPF_DIST_INF: among the links (u -> v, cost w, position j in u's row of the caller's
+ *               CSR) the scenario run itself uses — they survive the two-way check and u has no HSPF_VF_NO_EXPAND (the device
+ *               graph's in-link arrays hold exactly those, also after hspf_graph_patch); u is a network, or S, or has no
+ *               HSPF_VF_NO_TRANSIT, or run_flags has HSPF_RUN_IGNORE_OVERLOAD; the link is not the failed one (u == S and
+ *               j == root_link[e]); and it is tight, pc[u] + w == pc[v] — the one with the smallest (u, j).
+ *   walk        cur = D, q = D, an empty gap list.  At each cur, in this order:
+ *                 1. cur has HSPF_RLFA_ELIGIBLE and _IN_Q in space_flags[e]: q = cur, the gap list is emptied.
+ *                 2. cur has _ELIGIBLE, _IN_P or _IN_XP, and a release point (space_via[e][cur] != HSPF_LFA_NO_SLOT): p = cur, stop.
+ *                 3. cur == S: p = S, no node segment, stop.
+ *                 4. the hop (position j of parent(cur)'s row, head cur) goes to the FRONT of the gap list; cur = parent(cur).
+ *               A walk that has visited max_walk vertices without stopping is HSPF_TIPC_D_WALK: tight links of cost 0 that form a
+ *               cycle are the one way to get there on a row of the failure run, and the cap makes that outcome deterministic.
+ *   repair      the Node-SID of p sent out of via = space_via[e][p] exactly as ti_via is; the Adj-SIDs of the recorded links
+ *               p -> ... -> q; from q the packet follows q's own shortest path to D.
+ * Why the last part is safe: q is in Q(e) or q == D.  e is a primary of D, so d(S, D) = c + d(E, D).  A shortest path q -> D over
+ * the failed link would cost d(q, S) + c + d(E, D); Q(e) says d(q, E) < d(q, S) + c, so that is more than d(q, E) + d(E, D),
+ * which is at least d(q, D): no shortest path of q to D crosses the link.  (q == D: the path is empty.)  The first part is
+ * hspf_rlfa_device's P / XP inequality, the middle part is forced link by link and never the failed link.
+ *
+ * Outputs (DEVICE pointers, [n_prot][n_vertices] unless stated; "none" is HSPF_NO_ROOT / HSPF_LFA_NO_SLOT / 0 as elsewhere):
+ *   tp_kind u8    0 outside the population, else
+ *                 HSPF_TIPC_D_LFA     the given alt_flags have HSPF_LFA_LINK_PROTECT; the vertex is not walked
+ *                 HSPF_TIPC_D_REPAIR  a repair was found
+ *                 HSPF_TIPC_D_NONE    the slot is no candidate, has no row, or pc[D] is HSPF_DIST_INF (also: a vertex on the walk
+ *                                     has no parent, which a row of that link never shows)
+ *                 HSPF_TIPC_D_LONG    the walk stopped with more than HSPF_TIPC_MAX_ADJ hops between p and q
+ *                 HSPF_TIPC_D_LAN     not _D_LONG, and a vertex strictly between p and q carries HSPF_VF_NETWORK
+ *                 HSPF_TIPC_D_WALK    see above
+ *   for HSPF_TIPC_D_REPAIR, "none" otherwise:
+ *   tp_p, tp_via, tp_q        tp_via is HSPF_LFA_NO_SLOT for p == S (no node segment)
+ *   tp_n_adj u8               the recorded hops, 0 .. HSPF_TIPC_MAX_ADJ
+ *   tp_hop_pos / tp_hop_head  [n_prot][n_vertices][HSPF_TIPC_MAX_ADJ], in the order p -> q: the position of the link in its
+ *                             tail's row, and its head; the tail of hop 0 is p, of hop i the head of hop i - 1; the head of the
+ *                             last hop is q.  Unused entries HSPF_LFA_NO_SLOT / HSPF_NO_ROOT.
+ *   tp_metric                 rel(p) + pc[D] - pc[p], saturated; rel(p) rebuilt from the via as hspf_tilfa_device does, rel(S) = 0,
+ *                             pc[S] = 0
+ *   tp_flags u8               HSPF_TIPC_ON_PC rel(p) == pc[p]: the repair costs exactly the post-convergence distance |
+ *                             HSPF_TIPC_P_IS_ROOT | HSPF_TIPC_Q_IS_DEST
+ *   tp_coverage [n_prot][12]  counted on the device: the population | the six classes in the order of their values | the
+ *                             _D_REPAIR destinations with tp_n_adj = 0, 1, 2, 3, 4
+ * Argument errors — what hspf_tilfa_device rejects, NULL pc_dist_dev / pc_row, a pc_row entry given for a slot that is no
+ * candidate (or >= n_slots), a row >= n_pc_rows, max_walk outside 1 .. 65535 — return HSPF_E_INVAL with a text in hspf_last_error
+ * that names hspf_tilfa_pc_device, before anything is launched.  The call sizes its own scratch (8 bytes per vertex and slot
+ * with a row, released before it returns), enqueues everything on the context's stream and synchronises once at the end.
+ *
+ * From a result to a label stack: INTEGRATION.md §5w.
+ *
+ * LAN PRIMARIES.  For a slot behind a pseudonode (root_link[e] leads to a network vertex) the failed link is S's link onto the
+ * LAN, but the P / XP sets of hspf_rlfa_device are relative to E: the release path S -> p may run over that link to ANOTHER
+ * router of the LAN (the limitation hspf_rlfa_device states; hspf_rlfa_lan_device removes it for its own outputs).  Such a
+ * _D_REPAIR is safe against the failure of E's attachment, not of S's link onto the LAN; it shows as tp_metric < pc[D].  The
+ * adjacencies and q's tail end are safe either way.  A caller that protects the LAN link itself must not install these
+ * (INTEGRATION.md 5w).
+ *
+ * OUT OF SCOPE: node protection (HSPF_FAIL_VERTEX rows); SRLG- and LAN-safe tables (the call reads whatever space tables it is
+ * given, but the walk knows of one failed link only); destinations with several primaries (ECMP); per-prefix mapping;
+ * adjacencies across a pseudonode (_D_LAN, as hspf_tilfa_device); packed and asynchronous forms. */
+#define HSPF_TIPC_MAX_ADJ        4u
+#define HSPF_TIPC_D_LFA          1u            /* tp_kind */
+#define HSPF_TIPC_D_REPAIR       2u
+#define HSPF_TIPC_D_NONE         3u
+#define HSPF_TIPC_D_LONG         4u
+#define HSPF_TIPC_D_LAN          5u
+#define HSPF_TIPC_D_WALK         6u
+#define HSPF_TIPC_ON_PC          0x01u         /* tp_flags */
+#define HSPF_TIPC_P_IS_ROOT      0x02u
+#define HSPF_TIPC_Q_IS_DEST      0x04u
+#define HSPF_TIPC_COVERAGE_WORDS 12u
+typedef struct {                 /* DEVICE pointers                                                            */
+  uint8_t  *tp_kind;             /* [n_prot][n_vertices]                                                       */
+  uint32_t *tp_p;                /* [n_prot][n_vertices]                                                       */
+  uint32_t *tp_via;              /* [n_prot][n_vertices]                                                       */
+  uint32_t *tp_q;                /* [n_prot][n_vertices]                                                       */
+  uint8_t  *tp_n_adj;            /* [n_prot][n_vertices]                                                       */
+  uint32_t *tp_hop_pos;          /* [n_prot][n_vertices][HSPF_TIPC_MAX_ADJ]                                    */
+  uint32_t *tp_hop_head;         /* [n_prot][n_vertices][HSPF_TIPC_MAX_ADJ]                                    */
+  uint32_t *tp_metric;           /* [n_prot][n_vertices]                                                       */
+  uint8_t  *tp_flags;            /* [n_prot][n_vertices]                                                       */
+  uint32_t *tp_coverage;         /* [n_prot][HSPF_TIPC_COVERAGE_WORDS]                                         */
+} hspf_tilfa_pc_out;
+int hspf_tilfa_pc_device(hspf_ctx *ctx, const hspf_graph *g, uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words,
+                         const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev, const uint32_t *rdist_dev,
+                         const hspf_lfa_protect *prot, uint32_t n_prot, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                         const uint8_t *space_flags_dev, const uint32_t *space_via_dev, const uint32_t *pc_dist_dev, uint32_t n_pc_rows,
+                         const uint32_t *pc_row, uint32_t run_flags, uint32_t max_walk, hspf_tilfa_pc_out *out_dev);
 
 /* ---- per-prefix backup routes on device (RFC 5286 section 6.1): new symbol, same ABI number --------------------------------
  * hspf_lfa_device, hspf_rlfa_device and hspf_tilfa_device protect VERTICES and LINKS; what a RIB installs, and what

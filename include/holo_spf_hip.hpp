@@ -599,6 +599,18 @@ class Engine {
                                      (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, &out_dev);
     if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_device (") + hspf_last_error(ctx_) + ")");
   }
+  // hspf_tilfa_pc_device on DEVICE tables: those of tilfa_device, and pc_dist_dev [n_pc_rows][n_vertices] — the dist of a
+  // run_failures_device on `g` — with pc_row [protect.size()][64 * n_mask_words] (host) naming each slot's row (HSPF_NO_ROOT: none).
+  void tilfa_pc_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
+                       const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
+                       const uint8_t *space_flags_dev, const uint32_t *space_via_dev, const uint32_t *pc_dist_dev, uint32_t n_pc_rows,
+                       const std::vector<uint32_t> &pc_row, uint32_t run_flags, uint32_t max_walk, hspf_tilfa_pc_out out_dev) {
+    if (pc_row.size() != protect.size() * 64u * n_mask_words) throw Error(HSPF_E_INVAL, "tilfa_pc_device: pc_row holds 64 * n_mask_words entries per protected root");
+    const int rc = hspf_tilfa_pc_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                                        (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, pc_dist_dev, n_pc_rows,
+                                        pc_row.data(), run_flags, max_walk, &out_dev);
+    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_pc_device (") + hspf_last_error(ctx_) + ")");
+  }
   // One root start to finish: rlfa() with the space tables, everything kept on the device, then hspf_tilfa_device on the same rows.
   Tilfa tilfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
               const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,

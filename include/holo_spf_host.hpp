@@ -163,6 +163,31 @@ struct TilfaOut {
   std::vector<uint8_t> td_kind;                             // [n_protected][n_vertices] HSPF_TILFA_D_*
   std::vector<uint32_t> td_coverage;                        // [n_protected][HSPF_TILFA_COVERAGE_WORDS]
 };
+// TI-LFA repairs along the post-convergence path (hspf_tilfa_pc_device) of the same protected roots: per destination with one
+// primary slot the Node-SID, the adjacencies and the class, from the forward DeviceRun, the space tables of rlfa(..., with_spaces =
+// true) and the dist rows of run_failures() for the slots' links.  supported == false: no such call.
+struct TilfaPcOut {
+  bool supported = false;
+  uint32_t n_protected = 0, n_vertices = 0;
+  std::vector<uint8_t> tp_kind, tp_n_adj, tp_flags;         // [n_protected][n_vertices] HSPF_TIPC_D_* | 0 .. HSPF_TIPC_MAX_ADJ | HSPF_TIPC_*
+  std::vector<uint32_t> tp_p, tp_via, tp_q, tp_metric;      // [n_protected][n_vertices]
+  std::vector<uint32_t> tp_hop_pos, tp_hop_head;            // [n_protected][n_vertices][HSPF_TIPC_MAX_ADJ], in the order p -> q
+  std::vector<uint32_t> tp_coverage;                        // [n_protected][HSPF_TIPC_COVERAGE_WORDS]
+  struct Hop { uint32_t tail, pos, head; };
+  // the repair of destination d of protected root i: false unless HSPF_TIPC_D_REPAIR; via == HSPF_LFA_NO_SLOT: p is the root
+  bool segments(uint32_t i, uint32_t d, uint32_t &via, uint32_t &p, std::vector<Hop> &hops, uint32_t &q) const {
+    const size_t c = (size_t)i * n_vertices + d;
+    hops.clear();
+    if (i >= n_protected || d >= n_vertices || tp_kind[c] != HSPF_TIPC_D_REPAIR) return false;
+    via = tp_via[c]; p = tp_p[c]; q = tp_q[c];
+    uint32_t tail = p;
+    for (uint32_t h = 0; h < tp_n_adj[c] && h < HSPF_TIPC_MAX_ADJ; ++h) {
+      hops.push_back(Hop{tail, tp_hop_pos[c * HSPF_TIPC_MAX_ADJ + h], tp_hop_head[c * HSPF_TIPC_MAX_ADJ + h]});
+      tail = hops.back().head;
+    }
+    return true;
+  }
+};
 // Node-protecting remote loop-free alternates (RFC 8102: hspf_rlfa_node_select_device, one run over the listed nodes,
 // hspf_rlfa_node_device) of the same protected roots: per (protected root, slot) the cheapest max_pq PQ nodes whose release path
 // avoids the neighbour behind the slot, and per destination the cheapest of them whose own path avoids it too, from the forward
@@ -251,6 +276,12 @@ class Engine {
   // `rlfa`: what rlfa() returned for the same protect list WITH its space tables; `gr` is the forward graph.  The default: not supported.
   virtual TilfaOut tilfa(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
                          const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/) { return TilfaOut{}; }
+  // tilfa()'s inputs, and `pc_dist` [n_pc_rows][n_vertices]: the dist rows of run_failures() on `gr`; pc_row [n_protected][64 *
+  // mask_words]: per slot the row of its {HSPF_FAIL_ROOT_LINK, root_link} scenario, HSPF_NO_ROOT for none; run_flags: that run's.
+  // The default: not supported (tilfa_pc_sequential() below is the loop an engine that holds its CSR can answer with).
+  virtual TilfaPcOut tilfa_pc(Graph &, DeviceRun & /*run*/, DeviceRun & /*reverse_run*/, const std::vector<LfaProtect> &, uint32_t /*lfa_flags*/,
+                              const LfaOut * /*lfa*/, const RlfaOut & /*rlfa*/, const std::vector<uint32_t> & /*pc_dist*/, uint32_t /*n_pc_rows*/,
+                              const std::vector<uint32_t> & /*pc_row*/, uint32_t /*run_flags*/, uint32_t /*max_walk*/) { return TilfaPcOut{}; }
   // lfa() / backup_routes() with loop-freeness towards the pseudonodes of the primaries' LANs; lans[i] belongs to protect[i], the
   // run holds the SPTs rooted at the LANs too.  The defaults: not supported.
   virtual LfaOut lfa_lan(DeviceRun &, const std::vector<LfaProtect> &, const std::vector<LfaLan> &, uint32_t /*lfa_flags*/, bool /*with_masks*/) {
@@ -411,6 +442,114 @@ inline void splice_rows(std::vector<uint32_t> &row_ptr, std::vector<uint32_t> &c
   copy_stretch(n);
   nrp[n] = (uint32_t)out;
   row_ptr.swap(nrp); col.swap(ncol); metric.swap(nmet);
+}
+
+// The host twin of hspf_tilfa_pc_device: the rule of include/holo_spf_hip.h ("repairs along the post-convergence path") as a
+// sequential loop on the caller's CSR.  `fwd`: the forward tables of the run the protect list indexes (dist, flags, mask); space_flags /
+// space_via [n_protected][64 * mask_words][n]; alt_flags: nullptr or [n_protected][n]; pc_dist / pc_row / run_flags / max_walk as
+// the call's.  Parents are found per visited vertex with a scan of the whole CSR's in-links built once: O(links) memory, no device.
+inline TilfaPcOut tilfa_pc_sequential(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                                      const std::vector<uint8_t> &vflags, const Tables &fwd, const std::vector<LfaProtect> &protect,
+                                      const std::vector<uint8_t> &space_flags, const std::vector<uint32_t> &space_via, const std::vector<uint8_t> *alt_flags,
+                                      const std::vector<uint32_t> &pc_dist, uint32_t n_pc_rows, const std::vector<uint32_t> &pc_row, uint32_t run_flags,
+                                      uint32_t max_walk) {
+  const uint32_t n = fwd.n_vertices, W = fwd.mask_words, A = HSPF_TIPC_MAX_ADJ;
+  const size_t stride = (size_t)64 * W, np = protect.size();
+  if (row_ptr.size() != (size_t)n + 1 || vflags.size() != n) throw std::invalid_argument("tilfa_pc: the CSR is not of the tables' size");
+  if (max_walk == 0 || max_walk > 65535u) throw std::invalid_argument("tilfa_pc: max_walk outside 1 .. 65535");
+  if (space_flags.size() != np * stride * n || space_via.size() != np * stride * n || pc_row.size() != np * stride || pc_dist.size() != (size_t)n_pc_rows * n ||
+      (alt_flags && alt_flags->size() != np * n))
+    throw std::invalid_argument("tilfa_pc: an input array is not of this protect list");
+  for (size_t i = 0; i < np; ++i)
+    for (size_t e = 0; e < stride; ++e) {
+      const uint32_t r = pc_row[i * stride + e];
+      if (r == HSPF_NO_ROOT) continue;
+      if (e >= protect[i].nbr.size() || protect[i].nbr[e] == HSPF_NO_ROOT) throw std::invalid_argument("tilfa_pc: pc_row given for a slot that is no candidate");
+      if (r >= n_pc_rows) throw std::invalid_argument("tilfa_pc: pc_row >= n_pc_rows");
+    }
+  // the links a run uses whatever its root: two-way, the source without HSPF_VF_NO_EXPAND; per target (source, position, cost)
+  struct In { uint32_t u, j, w; };
+  std::vector<std::vector<In>> into(n);
+  auto lists = [&](uint32_t t, uint32_t u) { for (uint32_t k = row_ptr[t]; k < row_ptr[t + 1]; ++k) if (col[k] == u) return true; return false; };
+  for (uint32_t u = 0; u < n; ++u) {
+    if (vflags[u] & HSPF_VF_NO_EXPAND) continue;
+    for (uint32_t k = row_ptr[u]; k < row_ptr[u + 1]; ++k)
+      if (col[k] < n && lists(col[k], u)) into[col[k]].push_back(In{u, k - row_ptr[u], metric[k]});
+  }
+  const bool ign = (run_flags & HSPF_RUN_IGNORE_OVERLOAD) != 0;
+  TilfaPcOut o;
+  o.supported = true; o.n_protected = (uint32_t)np; o.n_vertices = n;
+  o.tp_kind.assign(np * n, 0); o.tp_n_adj.assign(np * n, 0); o.tp_flags.assign(np * n, 0);
+  o.tp_p.assign(np * n, HSPF_NO_ROOT); o.tp_via.assign(np * n, HSPF_LFA_NO_SLOT); o.tp_q.assign(np * n, HSPF_NO_ROOT); o.tp_metric.assign(np * n, 0);
+  o.tp_hop_pos.assign(np * n * A, HSPF_LFA_NO_SLOT); o.tp_hop_head.assign(np * n * A, HSPF_NO_ROOT);
+  o.tp_coverage.assign(np * HSPF_TIPC_COVERAGE_WORDS, 0);
+  for (size_t i = 0; i < np; ++i) {
+    const LfaProtect &pr = protect[i];
+    const uint32_t S = pr.root_vertex, K = (uint32_t)pr.nbr.size();
+    const uint32_t *dS = fwd.dist.data() + (size_t)pr.root_row * n;
+    uint32_t *cov = o.tp_coverage.data() + i * HSPF_TIPC_COVERAGE_WORDS;
+    for (uint32_t D = 0; D < n; ++D) {
+      const size_t sd = (size_t)pr.root_row * n + D, od = i * n + D;
+      if (D == S || !(fwd.flags[sd] & 1u) || dS[D] == HSPF_DIST_INF) continue;
+      uint32_t nprim = 0, e = 0;
+      for (uint32_t k = 0; k < K; ++k)
+        if ((fwd.mask[sd * W + k / 64] >> (k % 64)) & 1u) { if (!nprim) e = k; ++nprim; }
+      if (nprim != 1) continue;
+      uint32_t cls;
+      std::vector<std::pair<uint32_t, uint32_t>> gap;              // (position, head) in the order of recording: q first
+      uint32_t p = HSPF_NO_ROOT, q = D, via = HSPF_LFA_NO_SLOT;
+      uint64_t rel = 0;
+      const size_t si = i * stride + e;
+      const uint32_t *pc = pc_row[si] != HSPF_NO_ROOT ? pc_dist.data() + (size_t)pc_row[si] * n : nullptr;
+      if (alt_flags && ((*alt_flags)[od] & HSPF_LFA_LINK_PROTECT)) cls = HSPF_TIPC_D_LFA;
+      else if (pr.nbr[e] == HSPF_NO_ROOT || !pc || pc[D] == HSPF_DIST_INF) cls = HSPF_TIPC_D_NONE;
+      else {
+        const uint8_t *sf = space_flags.data() + si * n;
+        const uint32_t *sv = space_via.data() + si * n;
+        const uint32_t fpos = pr.root_link[e];
+        bool lan = false;
+        uint32_t cur = D;
+        cls = HSPF_TIPC_D_WALK;
+        for (uint32_t step = 0; step < max_walk; ++step) {
+          const uint8_t f = sf[cur];
+          if ((f & HSPF_RLFA_ELIGIBLE) && (f & HSPF_RLFA_IN_Q)) { q = cur; gap.clear(); lan = false; }
+          if ((f & HSPF_RLFA_ELIGIBLE) && (f & (HSPF_RLFA_IN_P | HSPF_RLFA_IN_XP)) && (sv[cur] == HSPF_RLFA_VIA_SELF || sv[cur] < K)) {
+            p = cur; via = sv[cur];
+            rel = via == HSPF_RLFA_VIA_SELF ? (uint64_t)dS[cur] : (uint64_t)pr.cost[via] + fwd.dist[(size_t)pr.nbr_row[via] * n + cur];
+            cls = HSPF_TIPC_D_REPAIR;
+            break;
+          }
+          if (cur == S) { p = S; rel = 0; cls = HSPF_TIPC_D_REPAIR; break; }
+          uint32_t bu = HSPF_NO_ROOT, bj = HSPF_NO_ROOT;
+          for (const In &l : into[cur]) {
+            if (!ign && (vflags[l.u] & HSPF_VF_NO_TRANSIT) && !(vflags[l.u] & HSPF_VF_NETWORK) && l.u != S) continue;
+            if (l.u == S && l.j == fpos) continue;
+            if (pc[l.u] == HSPF_DIST_INF || (uint64_t)pc[l.u] + l.w != pc[cur]) continue;
+            if (l.u < bu || (l.u == bu && l.j < bj)) { bu = l.u; bj = l.j; }
+          }
+          if (bu == HSPF_NO_ROOT) { cls = HSPF_TIPC_D_NONE; break; }
+          if (!gap.empty() && (vflags[cur] & HSPF_VF_NETWORK)) lan = true;
+          gap.emplace_back(bj, cur);
+          cur = bu;
+        }
+        if (cls == HSPF_TIPC_D_REPAIR) cls = gap.size() > A ? HSPF_TIPC_D_LONG : lan ? HSPF_TIPC_D_LAN : HSPF_TIPC_D_REPAIR;
+        if (cls == HSPF_TIPC_D_REPAIR) {
+          const uint32_t pcp = p == S ? 0u : pc[p];
+          const uint64_t t = rel + pc[D] - pcp;
+          o.tp_p[od] = p; o.tp_via[od] = via; o.tp_q[od] = q; o.tp_n_adj[od] = (uint8_t)gap.size();
+          o.tp_metric[od] = (uint32_t)std::min<uint64_t>(t, 0xFFFFFFFEull);
+          o.tp_flags[od] = (uint8_t)((rel == pcp ? HSPF_TIPC_ON_PC : 0u) | (p == S ? HSPF_TIPC_P_IS_ROOT : 0u) | (q == D ? HSPF_TIPC_Q_IS_DEST : 0u));
+          for (size_t h = 0; h < gap.size(); ++h) {
+            o.tp_hop_pos[od * A + h] = gap[gap.size() - 1 - h].first; o.tp_hop_head[od * A + h] = gap[gap.size() - 1 - h].second;
+          }
+          ++cov[7 + gap.size()];
+        }
+      }
+      o.tp_kind[od] = (uint8_t)cls;
+      ++cov[0]; ++cov[cls];
+    }
+  }
+  return o;
 }
 
 // The host twin of hspf_run_failures: the sequential SPF loop on the caller's CSR with the two skips — the
@@ -1189,6 +1328,61 @@ class HipEngine : public Engine {
     }
     pool_->dev_free(blk, total);
     if (!ok) throw std::runtime_error(std::string("hspf_tilfa_device: ") + hspf_last_error(ctx_));
+    return o;
+  }
+  TilfaPcOut tilfa_pc(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
+                      const RlfaOut &rl, const std::vector<uint32_t> &pc_dist, uint32_t n_pc_rows, const std::vector<uint32_t> &pc_row, uint32_t run_flags,
+                      uint32_t max_walk) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rr = static_cast<HipDeviceRun &>(reverse_run);
+    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error("tilfa_pc: the two runs differ in shape");
+    TilfaPcOut o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices;
+    if (protect.empty()) return o;
+    const size_t stride = (size_t)64 * r.mask_words;
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * stride, sp = ps * o.n_vertices, pcw = (size_t)n_pc_rows * o.n_vertices;
+    if (rl.space_flags.size() != sp || rl.space_via.size() != sp) throw std::runtime_error("tilfa_pc: the RLFA result holds no space tables of this protect list");
+    if (pc_row.size() != ps || pc_dist.size() != pcw) throw std::runtime_error("tilfa_pc: pc_row or pc_dist is not of this protect list");
+    std::vector<hspf_lfa_protect> pr;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error("tilfa_pc: the slot arrays of a protected root differ in length");
+      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    const size_t cb = (size_t)o.n_protected * HSPF_TIPC_COVERAGE_WORDS, A = HSPF_TIPC_MAX_ADJ;
+    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
+    // one block: tp_p | tp_via | tp_q | tp_metric | tp_hop_pos | tp_hop_head | tp_coverage | space_via | pc_dist | tp_kind | tp_n_adj | tp_flags | space_flags | alt_flags
+    const size_t words = pn * 4 + pn * A * 2 + cb + sp + std::max<size_t>(pcw, 1), total = words * 4 + pn * 3 + sp + (with_alt ? pn : 0);
+    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    uint32_t *w = (uint32_t *)blk;
+    hspf_tilfa_pc_out out{};
+    out.tp_p = w; w += pn; out.tp_via = w; w += pn; out.tp_q = w; w += pn; out.tp_metric = w; w += pn;
+    out.tp_hop_pos = w; w += pn * A; out.tp_hop_head = w; w += pn * A; out.tp_coverage = w; w += cb;
+    uint32_t *sv = w; w += sp;
+    uint32_t *pcd = w; w += std::max<size_t>(pcw, 1);
+    uint8_t *b = (uint8_t *)w;
+    out.tp_kind = b; b += pn; out.tp_n_adj = b; b += pn; out.tp_flags = b; b += pn;
+    uint8_t *sf = b; b += sp;
+    uint8_t *alt = with_alt ? b : nullptr;
+    bool ok = hipMemcpy(sv, rl.space_via.data(), sp * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
+              (pcw == 0 || hipMemcpy(pcd, pc_dist.data(), pcw * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
+    const int rc = ok ? hspf_tilfa_pc_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(),
+                                             o.n_protected, lfa_flags, alt, sf, sv, pcd, n_pc_rows, pc_row.data(), run_flags, max_walk, &out) : HSPF_E_HIP;
+    auto fetch = [&](auto &vec, const void *src, size_t count) {
+      vec.resize(count);
+      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
+    };
+    ok = ok && rc == HSPF_OK;
+    if (ok) {
+      fetch(o.tp_kind, out.tp_kind, pn); fetch(o.tp_n_adj, out.tp_n_adj, pn); fetch(o.tp_flags, out.tp_flags, pn); fetch(o.tp_p, out.tp_p, pn);
+      fetch(o.tp_via, out.tp_via, pn); fetch(o.tp_q, out.tp_q, pn); fetch(o.tp_metric, out.tp_metric, pn); fetch(o.tp_hop_pos, out.tp_hop_pos, pn * A);
+      fetch(o.tp_hop_head, out.tp_hop_head, pn * A); fetch(o.tp_coverage, out.tp_coverage, cb);
+    }
+    pool_->dev_free(blk, total);
+    if (!ok) throw std::runtime_error(std::string("hspf_tilfa_pc_device: ") + hspf_last_error(ctx_));
     return o;
   }
   RlfaNodeOut rlfa_node(Graph &gr, DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t run_flags, uint32_t lfa_flags, const LfaOut *lfa,

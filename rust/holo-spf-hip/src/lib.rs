@@ -364,6 +364,46 @@ pub struct Tilfa {
     pub td_coverage: Vec<u32>,
 }
 
+/// What `tilfa_pc_device` returns: per (protected root, destination) the repair along the post-convergence path
+/// (`hspf_tilfa_pc_device`).  Arrays are `[n_protected][n_vertices]`, the hop arrays with
+/// `HSPF_TIPC_MAX_ADJ` entries per destination.
+#[derive(Debug, Clone)]
+pub struct TilfaPc {
+    pub n_protected: u32,
+    pub n_vertices: u32,
+    pub tp_kind: Vec<u8>,
+    pub tp_p: Vec<u32>,
+    pub tp_via: Vec<u32>,
+    pub tp_q: Vec<u32>,
+    pub tp_n_adj: Vec<u8>,
+    pub tp_hop_pos: Vec<u32>,
+    pub tp_hop_head: Vec<u32>,
+    pub tp_metric: Vec<u32>,
+    pub tp_flags: Vec<u8>,
+    pub tp_coverage: Vec<u32>,
+}
+
+impl TilfaPc {
+    /// The repair of destination `d` of protected root `i`: `(via, p, [(tail, position, head)], q)` — the Node-SID of `p` out of
+    /// `via` (`HSPF_LFA_NO_SLOT`: `p` is the root, no node segment), the Adj-SID of every listed link, then `q`'s own path.
+    /// `None` unless `HSPF_TIPC_D_REPAIR`.
+    pub fn segments(&self, i: usize, d: usize) -> Option<(u32, u32, Vec<(u32, u32, u32)>, u32)> {
+        let c = i * self.n_vertices as usize + d;
+        if i >= self.n_protected as usize || d >= self.n_vertices as usize || self.tp_kind[c] as u32 != sys::HSPF_TIPC_D_REPAIR {
+            return None;
+        }
+        let a = sys::HSPF_TIPC_MAX_ADJ as usize;
+        let mut tail = self.tp_p[c];
+        let mut hops = Vec::with_capacity(self.tp_n_adj[c] as usize);
+        for h in 0..(self.tp_n_adj[c] as usize).min(a) {
+            let head = self.tp_hop_head[c * a + h];
+            hops.push((tail, self.tp_hop_pos[c * a + h], head));
+            tail = head;
+        }
+        Some((self.tp_via[c], self.tp_p[c], hops, self.tp_q[c]))
+    }
+}
+
 impl Tilfa {
     /// The repair of (protected root `i`, slot `e`): (via, p, forced link of p's row or `None` for a single node, total),
     /// `None` when there is none.  The segment list is the Node-SID of p, then the Adj-SID of that link.
@@ -1269,6 +1309,113 @@ impl Engine {
             ti_counts: ti_counts.to_host(slots * sys::HSPF_TILFA_COUNT_WORDS as usize)?,
             td_kind: td_kind.to_host(cells)?,
             td_coverage: td_cov.to_host(np * sys::HSPF_TILFA_COVERAGE_WORDS as usize)?,
+        })
+    }
+
+    /// `hspf_tilfa_pc_device`: per destination with one primary slot the repair that follows its post-convergence path.  `g`,
+    /// `tables`, `reverse`, `protect`, `lfa`, `rlfa` as for `tilfa_device`; `pc`: the tables of a `run_failures_device` on `g`;
+    /// `pc_row[i * 64 * words + e]`: the row of `pc` with `{HSPF_FAIL_ROOT_LINK, root_link[e]}` of protected root `i`, or
+    /// `HSPF_NO_ROOT`; `run_flags`: those of that run; `max_walk`: 1 ..= 65535.
+    #[allow(clippy::too_many_arguments)]
+    pub fn tilfa_pc_device(&self, g: &Graph<'_>, tables: &DeviceTables<'_>, reverse: &DeviceTables<'_>, protect: &[(u32, &LfaCandidates, &[u32])],
+                           ignore_overload: bool, lfa: Option<&Lfa>, rlfa: &Rlfa, pc: &DeviceTables<'_>, pc_row: &[u32], run_flags: u32,
+                           max_walk: u32) -> Result<TilfaPc, Error> {
+        let (n, np) = (tables.n_vertices as usize, protect.len());
+        let stride = 64 * tables.words as usize;
+        if reverse.n_vertices != tables.n_vertices || reverse.n_roots != tables.n_roots || pc.n_vertices != tables.n_vertices || pc_row.len() != np * stride {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_pc_device: the table sets or pc_row differ in shape".into() });
+        }
+        let mut raw = Vec::with_capacity(np);
+        for (root_row, c, nbr_row) in protect {
+            let k = c.nbr.len();
+            if nbr_row.len() != k || c.cost.len() != k || c.root_link.len() != k || c.cflags.len() != k {
+                return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_pc_device: the slot arrays of a protected root differ in length".into() });
+            }
+            raw.push(sys::hspf_lfa_protect {
+                root_vertex: c.root,
+                root_row: *root_row,
+                n_slots: k as u32,
+                nbr: c.nbr.as_ptr(),
+                nbr_row: nbr_row.as_ptr(),
+                cost: c.cost.as_ptr(),
+                root_link: c.root_link.as_ptr(),
+                cflags: c.cflags.as_ptr(),
+            });
+        }
+        let (slots, cells, adj) = (np * stride, np * n, sys::HSPF_TIPC_MAX_ADJ as usize);
+        if rlfa.space_flags.len() != slots * n || rlfa.space_via.len() != slots * n {
+            return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_pc_device: the RLFA result holds no space tables of this protect list".into() });
+        }
+        let sp_flags = self.device_from(&rlfa.space_flags)?;
+        let sp_via = self.device_from(&rlfa.space_via)?;
+        let alt = match lfa {
+            Some(l) if l.alt_flags.len() == cells => Some(self.device_from(&l.alt_flags)?),
+            Some(_) => return Err(Error { code: sys::HSPF_E_INVAL, detail: "tilfa_pc_device: the LFA result is not of this protect list".into() }),
+            None => None,
+        };
+        let tp_kind = self.device_alloc(cells)?;
+        let tp_p = self.device_alloc(cells * 4)?;
+        let tp_via = self.device_alloc(cells * 4)?;
+        let tp_q = self.device_alloc(cells * 4)?;
+        let tp_n_adj = self.device_alloc(cells)?;
+        let tp_hop_pos = self.device_alloc(cells * adj * 4)?;
+        let tp_hop_head = self.device_alloc(cells * adj * 4)?;
+        let tp_metric = self.device_alloc(cells * 4)?;
+        let tp_flags = self.device_alloc(cells)?;
+        let tp_cov = self.device_alloc(np * sys::HSPF_TIPC_COVERAGE_WORDS as usize * 4)?;
+        let mut out = sys::hspf_tilfa_pc_out {
+            tp_kind: tp_kind.p as *mut u8,
+            tp_p: tp_p.p as *mut u32,
+            tp_via: tp_via.p as *mut u32,
+            tp_q: tp_q.p as *mut u32,
+            tp_n_adj: tp_n_adj.p as *mut u8,
+            tp_hop_pos: tp_hop_pos.p as *mut u32,
+            tp_hop_head: tp_hop_head.p as *mut u32,
+            tp_metric: tp_metric.p as *mut u32,
+            tp_flags: tp_flags.p as *mut u8,
+            tp_coverage: tp_cov.p as *mut u32,
+        };
+        let rc = unsafe {
+            sys::hspf_tilfa_pc_device(
+                self.ctx,
+                g.g,
+                tables.n_vertices,
+                tables.n_roots,
+                tables.words,
+                tables.dist.p as *const u32,
+                tables.flags.p as *const u16,
+                tables.mask.p as *const u64,
+                reverse.dist.p as *const u32,
+                raw.as_ptr(),
+                np as u32,
+                if ignore_overload { sys::HSPF_LFA_IGNORE_OVERLOAD } else { 0 },
+                alt.as_ref().map_or(ptr::null(), |a| a.p as *const u8),
+                sp_flags.p as *const u8,
+                sp_via.p as *const u32,
+                pc.dist.p as *const u32,
+                pc.n_roots,
+                pc_row.as_ptr(),
+                run_flags,
+                max_walk,
+                &mut out,
+            )
+        };
+        if rc != sys::HSPF_OK {
+            return Err(self.err(rc));
+        }
+        Ok(TilfaPc {
+            n_protected: np as u32,
+            n_vertices: tables.n_vertices,
+            tp_kind: tp_kind.to_host(cells)?,
+            tp_p: tp_p.to_host(cells)?,
+            tp_via: tp_via.to_host(cells)?,
+            tp_q: tp_q.to_host(cells)?,
+            tp_n_adj: tp_n_adj.to_host(cells)?,
+            tp_hop_pos: tp_hop_pos.to_host(cells * adj)?,
+            tp_hop_head: tp_hop_head.to_host(cells * adj)?,
+            tp_metric: tp_metric.to_host(cells)?,
+            tp_flags: tp_flags.to_host(cells)?,
+            tp_coverage: tp_cov.to_host(np * sys::HSPF_TIPC_COVERAGE_WORDS as usize)?,
         })
     }
 
