@@ -1660,8 +1660,6 @@ int Run::prepare() {
   if ((run_flags & HSPF_RUN_POP_RANK) && !out->pop_rank) { ctx->last_error = "HSPF_RUN_POP_RANK without pop_rank buffer"; return HSPF_E_INVAL; }
   B = (n_roots + 63) / 64; L = B * 64;
   s = ctx->stream;
-  st = hspf_stats{};
-  st.n_roots = n_roots; st.n_batches = B;
   t_entry = std::chrono::steady_clock::now();      // hspf_stats::dbg[2..3]: host time of the call (us)
   pf = ctx->prefill;      // what the previous run left for this one; whoever does not take it loses it
   ctx->prefill.valid = false;
@@ -1696,6 +1694,8 @@ int Run::prepare() {
     return HSPF_E_TOO_MANY_SLOTS;
   }
   if (need_words > 16) { ctx->last_error = "more than 1024 first-hop slots"; return HSPF_E_TOO_MANY_SLOTS; }
+  st = hspf_stats{};                                           // only now: a call refused above leaves the statistics of the last run
+  st.n_roots = n_roots; st.n_batches = B;
   W = round_words(need_words);
   out_words = want_mask ? out->n_mask_words : W;
   st.n_mask_words = need_words;

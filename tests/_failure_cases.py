@@ -5,8 +5,10 @@ every link of its row retargeted to n.  The retargeted links fail the two-way ch
 columns 0 .. n-1 of the oracle's row are what the engine must deliver bit for bit.
 
 A case is (graph, max_path_metric, roots, failures, run_flags, check): `check(ref, plain)` asserts on the ORACLE's rows that the branch
-the case names is taken (ref: the failure rows, plain: the same roots without failures).  `widen` gives the root more than 64 slots."""
-from dataclasses import dataclass
+the case names is taken (ref: the failure rows, plain: the same roots without failures).  `widen` gives the root more than 64 slots;
+`Case.at(extra)` is the case with `extra` spokes at its first root (WORDS: 130, 300, 520, 960 spokes -> 3, 5, 9, 16 mask words, the
+engine's kernel widths 4, 8, 16, 16), and Ref.extra / Ref.front tell a check how many spokes the root has and where they stand."""
+from dataclasses import dataclass, replace
 from typing import Callable
 
 import numpy as np
@@ -36,15 +38,21 @@ def both(n, und):
     return rows
 
 
-def widen(rows, vf, S, extra=66, cost=9):
-    """`extra` single-homed routers behind S, their links appended to S's row: S gets more than 64 slots, nothing else moves."""
+WORDS = {130: 3, 300: 5, 520: 9, 960: 16}     # spokes of Case.at() -> mask words needed (the roots of the case list have 1 .. 20 slots of their own)
+
+
+def widen(rows, vf, S, extra=66, cost=9, front=False):
+    """`extra` single-homed routers behind S, their links appended to S's row: S gets more than 64 slots, nothing else moves.
+    front: the spokes' links stand BEFORE S's own links instead, whose positions (and slots) move up by `extra`."""
     rows = [list(r) for r in rows]
     vf = list(vf)
+    spokes = []
     for _ in range(extra):
         v = len(rows)
         rows.append([(S, cost)])
-        rows[S].append((v, cost))
+        spokes.append((v, cost))
         vf.append(0)
+    rows[S] = spokes + rows[S] if front else rows[S] + spokes
     return rows, vf
 
 
@@ -101,6 +109,8 @@ class Ref:
     flags: np.ndarray
     mask: np.ndarray
     pop_rank: np.ndarray
+    extra: int = 0               # spokes at the case's first root (run_check sets both)
+    front: bool = False          # ... standing before the root's own links
 
 
 def reference(graph, maxp, roots, fails, run_flags=0, W=None) -> Ref:
@@ -151,10 +161,24 @@ class Case:
     flags: int
     check: Callable
     exact: bool = False          # the rows must come from the sequential kernel (stats n_exact_roots > 0)
+    spoke_cost: int = 9          # cost of the widening spokes (1 on hop-count-like graphs, which they must not leave)
+    front: bool = False          # at(): the spokes stand before the root's own links
+    extra: int = 0               # spokes already added by at()
+    hopcount: bool = False       # the graph is hop-count-like, spokes included
+    words: dict = None           # {spokes: mask words needed} of a case that does not start at one word (default: WORDS)
 
     def graph(self, wide=False):
-        rows, vf = (widen(self.rows, self.vf, self.roots[0]) if wide else (self.rows, self.vf))
+        rows, vf = (widen(self.rows, self.vf, self.roots[0], cost=self.spoke_cost) if wide else (self.rows, self.vf))
         return csr(rows, vf)
+
+    def at(self, extra):
+        """The case with `extra` spokes at its first root.  With `front` they come first in the root's row, and the HSPF_FAIL_ROOT_LINK
+        positions of that root move up with its own links."""
+        assert self.extra == 0
+        S = self.roots[0]
+        rows, vf = widen(self.rows, self.vf, S, extra, self.spoke_cost, self.front)
+        fails = [(k, a + extra) if (self.front and k == ROOT_LINK and r == S) else (k, a) for r, (k, a) in zip(self.roots, self.fails)]
+        return replace(self, rows=rows, vf=vf, fails=fails, extra=extra)
 
 
 def bit(ref, r, v, slot):
@@ -249,13 +273,112 @@ def _cases():
     rows = [[(3, 10), (4, 10)], [(3, 10)], [(4, 10)], [(0, 0), (1, 0)], [(0, 0), (2, 0)]]
 
     def chk15(f, p):
-        own = 2 if f.mask.shape[2] == 1 else 68
+        own = 2 + f.extra
         for r in (0, 1):
             assert p.dist[r, 1] == 10 and f.dist[r, 1] == INF and f.dist[r, 2] == 10 and f.dist[r, 4] == 10
             assert bit(f, r, 2, own + 3) and not bit(f, r, 2, own + 1) and bit(p, r, 2, own + 3) and bit(p, r, 1, own + 1)
         assert f.dist[0, 3] == INF and f.dist[1, 3] == INF
     C["two_lans"] = Case(rows, [0, 0, 0, NET, NET], INF, [0, 0], [(ROOT_LINK, 0), (VERTEX, 3)], 0, chk15)
+    # 16: the ring of case 1 with the spokes of at() standing FIRST in the root's row: the failed link 0 -> 1 and the detour 0 -> 5 then
+    # have the two highest slots of the root, both in the top mask word (960 spokes: slots 960 and 961, word 15)
+    def chk16(f, p):
+        fs = f.extra if f.front else 0
+        ds = fs + 1
+        if f.front:
+            assert f.extra >= 64 and fs // 64 == ds // 64 == f.mask.shape[2] - 1
+        assert p.dist[0, 1] == 1 and bit(p, 0, 1, fs) and f.dist[0, 1] == 5
+        assert any(bit(f, 0, v, ds) for v in range(1, 6)) and not any(bit(f, 0, v, fs) for v in range(f.dist.shape[1]))
+    C["high_slot_detour"] = Case(ring, [0] * 6, INF, [0], [(ROOT_LINK, 0)], 0, chk16, front=True)
+    # 17: the giant row of case 14 with the failures far down it: S = 301 hangs on routers 130 (at 5) and 290 (at 30), whose links into
+    # the pseudonode stand at in-row positions 129 and 289 (the third and the fifth 64-link chunk).  (Router 302 belongs to case 20.)
+    g17 = _giant_far()
+    C["giant_row_far"] = Case(g17[0], g17[1], INF, [301, 301, 301], [(ROOT_LINK, 0), (VERTEX, 130), (VERTEX, 0)], 0, lambda f, p: _chk_far(f, p, 0))
+    # 18: a root's failed link far down a ROUTER's in-row (no pseudonode: the root keeps two slots).  Hub 0 with routers 1 .. 70 at 5;
+    # S = 70 also reaches the hub through 71 (2 + 3): with S's own link to the hub failed (position 1 of its row, position 69 of the
+    # hub's in-row, the second chunk) the hub is still 5 away and the failed link looks tight; the link 64 places before it in the
+    # in-row (router 6's) has position 0 in ITS row
+    rows = [[(r, 5) for r in range(1, 71)] + [(71, 3)]] + [[(0, 5)] for _ in range(70)] + [[(70, 2), (0, 3)]]
+    rows[70] = [(71, 2), (0, 5)]
+
+    def chk18(f, p):
+        assert p.dist[0, 0] == 5 and bit(p, 0, 0, 0) and bit(p, 0, 0, 1)
+        assert f.dist[0, 0] == 5 and bit(f, 0, 0, 0) and not bit(f, 0, 0, 1) and f.dist[0, 1] == 10 and not bit(f, 0, 1, 1)
+    C["hub_far_link"] = Case(rows, [0] * 72, INF, [70], [(ROOT_LINK, 1)], 0, chk18)
+    assert in_row(csr(rows), 0)[69] == (70, 1) and in_row(csr(rows), 0)[5] == (6, 0)
+    # 19: a hop-count-like graph (LANs 0, 1, 2 numbered below their routers 3 .. 8; router -> LAN 0, LAN -> router 1).  S = 3 and R = 4
+    # share the LANs 0 and 1, router 6 is on LAN 0 only; 5 and 8 (LANs 1 and 2) are both one hop away, so both their links are tight
+    # zero-cost in-links of LAN 2 from higher-numbered sources, and the first, 5's, is its only parent (7 is behind LAN 2).
+    # Rows: nothing failed; S's link into LAN 0 (its parent becomes R's link); R excluded; LAN 0 excluded; 5 excluded (8's link takes over)
+    rows = [[(3, 1), (4, 1), (6, 1)], [(3, 1), (4, 1), (5, 1), (8, 1)], [(5, 1), (8, 1), (7, 1)],
+            [(0, 0), (1, 0)], [(0, 0), (1, 0)], [(1, 0), (2, 0)], [(0, 0)], [(2, 0)], [(1, 0), (2, 0)]]
+
+    def chk19(f, p):
+        a, b, c, d, e = range(5)
+        own = 2 + f.extra
+        s5, s8 = own + 3 + 2, own + 3 + 3                                 # slots of LAN 1's links to 5 and to 8 (LAN 0's three come first)
+        assert f.dist[a].tolist()[:9] == [0, 0, 1, 0, 1, 1, 1, 2, 1] and np.array_equal(f.dist[a], p.dist[a]) and np.array_equal(f.mask[a], p.mask[a])
+        assert f.dist[b, 0] == 1 and f.flags[b, 0] == 1 and f.hops[a, 0] == 0 and f.hops[b, 0] == 1 and f.dist[b, 6] == 2
+        assert bit(f, b, 6, own + 3 + 1) and not bit(f, b, 6, own + 2) and bit(f, a, 6, own + 2)   # 6: through LAN 1's link to R, not LAN 0's to 6
+        assert f.dist[c, 4] == INF and f.dist[c, 0] == 0 and f.dist[d, 0] == INF and f.dist[d, 6] == INF and f.dist[d, 4] == 1
+        assert bit(f, a, 7, s5) and not bit(f, a, 7, s8) and bit(f, a, 2, s5) and not bit(f, a, 2, s8)   # LAN 2 and 7: the first parent only
+        assert f.dist[e, 5] == INF and f.dist[e, 2] == 1 and f.dist[e, 7] == 2 and bit(f, e, 7, s8) and not bit(f, e, 7, s5)
+    C["hopcount_lan_first_parent"] = Case(rows, [NET] * 3 + [0] * 6, INF, [3] * 5, [(NONE, 0), (ROOT_LINK, 0), (VERTEX, 4), (VERTEX, 0), (VERTEX, 5)], 0,
+                                          chk19, spoke_cost=1, hopcount=True)
     return C
+
+
+def in_row(graph, t):
+    """[(source, position in the source's row)] of the links into t in the engine's in-row order: cost descending, source ascending,
+    position ascending (two-way links only)."""
+    rp, col, met, _ = graph
+    out = []
+    for u in range(len(rp) - 1):
+        for k in range(int(rp[u]), int(rp[u + 1])):
+            if int(col[k]) == t and u in col[rp[t]:rp[t + 1]]:
+                out.append((-int(met[k]), u, k - int(rp[u])))
+    return [(u, j) for _, u, j in sorted(out)]
+
+
+def _giant_far():
+    n_r = 300
+    rows = [[(r, 0) for r in range(1, n_r + 1)]] + [[(0, 10)] for _ in range(n_r)] + [[(130, 5), (290, 30)]]
+    rows[130].append((301, 5))
+    rows[290].append((301, 30))
+    # router 302 behind 280 (at 3) and on the LAN (at 7): 280 reaches the LAN at 10 both ways
+    rows.append([(280, 3), (0, 7)])
+    rows[280] = [(302, 3), (0, 10)]
+    rows[0].append((302, 0))
+    g = csr(rows)
+    pos = in_row(g, 0)
+    assert pos[129] == (130, 0) and pos[289] == (290, 0) and pos[279] == (280, 1) and pos[279 - 256] == (24, 0) and len(pos) == 301
+    return rows, [NET] + [0] * 302
+
+
+def _chk_far(f, p, r0):
+    a, b, c = r0, r0 + 1, r0 + 2
+    assert p.dist[a, 0] == 15 and p.dist[a, 300] == 15 and bit(p, a, 300, 0)
+    assert f.dist[a, 290] == 30 and f.dist[a, 0] == 40 and f.dist[a, 130] == 40 and f.dist[a, 300] == 40 and bit(f, a, 300, 1) and not bit(f, a, 300, 0)
+    assert f.dist[b, 130] == INF and f.dist[b, 0] == 40 and f.dist[b, 300] == 40
+    assert f.dist[c, 0] == INF and f.dist[c, 130] == 5 and f.dist[c, 290] == 30 and (f.dist[c, :303] != INF).sum() == 3
+
+
+def _wide_cases():
+    """Cases whose first root needs more than one mask word before any widening: not part of CASES, whose every case runs at one word."""
+    # 20: case 17's graph with a root that is itself a router of the 301-router LAN: M = 280, in-row position 279 (the fifth chunk), its
+    # link into the LAN at position 1 of its row while the in-link 256 places earlier (router 24's) has position 0.  M reaches the
+    # LAN at 10 directly and through 302 (3 + 7): with its own link failed the LAN keeps its distance, the failed link looks tight,
+    # and everything behind the LAN moves from the LAN's own slots to slot 0 (M -> 302).  Then 302 excluded, and case 17's three rows.
+    rows, vf = _giant_far()
+
+    def chk20(f, p):
+        own = 2 + f.extra
+        assert p.dist[0, 0] == 10 and p.hops[0, 0] == 0 and bit(p, 0, 1, own + 0) and not bit(p, 0, 1, 0)
+        assert f.dist[0, 0] == 10 and f.hops[0, 0] == 1 and bit(f, 0, 1, 0) and not bit(f, 0, 1, own + 0) and f.dist[0, 1] == 10
+        assert not any(bit(f, 0, v, 1) for v in range(f.dist.shape[1]))
+        assert f.dist[1, 302] == INF and f.dist[1, 0] == 10 and f.hops[1, 0] == 0
+        _chk_far(f, p, 2)
+    fails = [(ROOT_LINK, 1), (VERTEX, 302), (ROOT_LINK, 0), (VERTEX, 130), (VERTEX, 0)]
+    return {"giant_row_member": Case(rows, vf, INF, [280, 280, 301, 301, 301], fails, 0, chk20, words={0: 5, 130: 7, 300: 10, 520: 13})}
 
 
 def _fail():
@@ -263,14 +386,72 @@ def _fail():
 
 
 CASES = _cases()
+WIDE_CASES = _wide_cases()
 
 
-def run_check(case: Case, wide: bool):
-    """The oracle's rows of a case, after asserting that its branch is taken; returns (graph, ref)."""
+def hopcount_random(seed) -> Case:
+    """A seeded hop-count-like graph of 20 to 60 vertices — LANs first, so that each is numbered below its routers; every router on one
+    to three of them, on odd seeds with some point-to-point links at 1 — with every link and every neighbour (mostly LANs) of three
+    router roots.  Every root has at most 40 slots: 280 spokes at the first bring the run to five mask words."""
+    r = np.random.default_rng(7700 + seed)
+    n = int(r.integers(20, 61))
+    k = max(3, n // 4)
+    rows = [[] for _ in range(n)]
+    for v in range(k, n):
+        for l in r.choice(k, int(r.integers(1, 4)), replace=False).tolist():
+            rows[v].append((l, 0))
+            rows[l].append((v, 1))
+    if seed % 2:
+        for _ in range(n // 4):
+            a, b = (int(x) for x in r.integers(k, n, 2))
+            if a != b and all(t != b for t, _ in rows[a]):
+                rows[a].append((b, 1))
+                rows[b].append((a, 1))
+    vf = [NET] * k + [0] * (n - k)
+    graph = csr(rows, vf)
+    roots, fails = [], []
+    for S in r.choice(np.arange(k, n), 3, replace=False).tolist():
+        sc = all_scenarios(graph, S)
+        roots += [S] * len(sc)
+        fails += sc
+    return Case(rows, vf, INF, roots, fails, 0, lambda f, p: None, spoke_cost=1, hopcount=True, words={0: 1, 280: 5})
+
+
+def is_hopcount_like(graph):
+    """The engine's hop-count shape, restated on the CSR: every link that survives the two-way check costs 0 into a network — and
+    then comes from a higher-numbered router — and 1 into a router; some network has such a link."""
+    rp, col, met, vf = graph
+    net_in = False
+    for u in range(len(vf)):
+        for k in range(int(rp[u]), int(rp[u + 1])):
+            t = int(col[k])
+            if u not in col[rp[t]:rp[t + 1]]:
+                continue
+            if vf[t] & NET:
+                if met[k] != 0 or (vf[u] & NET) or u <= t:
+                    return False
+                net_in = True
+            elif met[k] != 1:
+                return False
+    return net_in
+
+
+def run_check(case: Case, wide: bool = False, extra=None):
+    """The oracle's rows of a case, after asserting that its branch is taken; returns (graph, ref).  extra: the case at(extra), whose
+    roots and failures the caller takes from at(extra) too; the oracle must need WORDS[extra] mask words."""
+    from oracle import graph_oracle as go
+    assert not (wide and extra is not None)
+    if extra is not None:
+        case = case.at(extra)
     g = case.graph(wide)
     ref = reference(g, case.maxp, case.roots, case.fails, case.flags)
     plain = reference(g, case.maxp, case.roots, [(NONE, 0)] * len(case.roots), case.flags)
-    assert ref.mask.shape[2] == (2 if wide else 1)
+    need = go.mask_words(g[0], g[1], g[2], g[3], np.asarray(case.roots, np.uint32))
+    want = (2 if wide else (case.words or {0: 1})[0]) if extra is None else (case.words or WORDS)[extra]
+    assert need == ref.mask.shape[2] == want, (need, ref.mask.shape, want)
+    assert is_hopcount_like(g) == case.hopcount
+    for x in (ref, plain):
+        x.extra, x.front = (66 if wide else 0) if extra is None else extra, extra is not None and case.front
     case.check(ref, plain)
     return g, ref
 
@@ -321,6 +502,31 @@ def driver_files(tmp_path, names=("ring", "parallel_unequal", "lan_link", "lan_e
             p = tmp_path / f"failures_{name}_{int(wide)}.txt"
             write_case_file(p, g, c.maxp, c.roots, c.fails, c.flags, ref)
             files.append(str(p))
+    return files
+
+
+EXTRAS = sorted(WORDS)
+HOPCOUNT_SEEDS = range(20)
+
+
+def wide_runs():
+    """(id, base case, spokes or None) of everything beyond the two legacy widths: every case of CASES at the four widths of WORDS,
+    the cases of WIDE_CASES as they are and at the widths that keep them within 16 words, the seeded hop-count-like graphs at one
+    word and at five."""
+    runs = [(f"{name}-{e}", CASES[name], e) for name in sorted(CASES) for e in EXTRAS]
+    runs += [(f"{name}-{e}", c, e or None) for name, c in sorted(WIDE_CASES.items()) for e in sorted(c.words)]
+    runs += [(f"hopcount_random{seed}-{e}", hopcount_random(seed), e or None) for seed in HOPCOUNT_SEEDS for e in (0, 280)]
+    return runs
+
+
+def driver_files_wide(tmp_path):
+    files = []
+    for rid, c, e in wide_runs():
+        g, ref = run_check(c, extra=e)
+        cw = c.at(e) if e is not None else c
+        p = tmp_path / f"failures_{rid}.txt"
+        write_case_file(p, g, cw.maxp, cw.roots, cw.fails, cw.flags, ref)
+        files.append(str(p))
     return files
 
 

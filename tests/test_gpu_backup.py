@@ -56,6 +56,7 @@ class Device:
         r = dict(best_metric=torch.full((tab.R, NP), 7, dtype=torch.int32, device="cuda:0"), best_entry=torch.full((tab.R, NP), 7, dtype=torch.int32, device="cuda:0"),
                  nexthop_mask=torch.full((tab.R, NP, tab.W), 7, dtype=torch.int64, device="cuda:0"))
         a = arrays or (t.ptr, t.vertex, t.metric)
+        torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
         self.ctx.routes_device(tab.n, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), *a, flags=t.flags if flags is None else flags,
                                **{k + "_ptr": x.data_ptr() for k, x in r.items()})
         for i, rr in enumerate(self.model.root_row):
@@ -79,6 +80,7 @@ class Device:
             ti = [torch.from_numpy(np.stack([getattr(x, k) for x in tm]).view(np.uint8 if k == "ti_kind" else np.int32)).to("cuda:0") for k in ("ti_kind", "ti_via", "ti_metric")]
             assert ti[0].shape == (P, S)
         a = arrays or (t.ptr, t.vertex, t.metric)
+        torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
         self.ctx.routes_backup_device(tab.n, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), protect or self.protect, *a,
                                       routes=tuple(r[k].data_ptr() for k in ("best_metric", "best_entry", "nexthop_mask")),
                                       tilfa=None if ti is None else tuple(x.data_ptr() for x in ti), flags=t.flags if flags is None else flags, lfa_flags=lfa_flags,

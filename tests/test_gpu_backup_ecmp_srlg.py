@@ -61,6 +61,7 @@ def run(d, t, lfa_flags=0, tilfa=None, cap=None, routes=None, srlgs=None, flags=
     pri, slot, met = (torch.full((cap + 3,), SENTINEL, dtype=torch.int32, device="cuda:0") for _ in range(3))
     kind, fl = (torch.full((cap + 3,), 7, dtype=torch.uint8, device="cuda:0") for _ in range(2))
     cov = torch.full((P, BES.COVERAGE_WORDS), 7, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     total = d.ctx.routes_backup_ecmp_srlg_device(*args, eb_ptr_ptr=ptr.data_ptr(), cap_entries=cap, eb_primary_ptr=pri.data_ptr(), eb_kind_ptr=kind.data_ptr(),
                                                  eb_slot_ptr=slot.data_ptr(), eb_metric_ptr=met.data_ptr(), eb_flags_ptr=fl.data_ptr(),
                                                  eb_coverage_ptr=cov.data_ptr(), **kw)

@@ -43,6 +43,7 @@ class NodeDevice(Device):
         real = sorted({int(v) for v in y_roots if v != NONE})
         if real:
             rows = torch.full((len(real), tab.n), 7, dtype=torch.int32, device="cuda:0")
+            torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
             self.ctx.run_device(tab.G, np.array(real, np.uint32), run_flags, dist_ptr=rows.data_ptr())
             for i, v in enumerate(y_roots):
                 if v != NONE:
@@ -68,6 +69,7 @@ class NodeDevice(Device):
         tn = [_dev(np.stack([getattr(w.tn, k) for w in wants])) for k in TQ] if with_tn else None
         bk = [_dev(np.stack([getattr(w.bk, k) for w in wants])) for k in ("bk_kind", "bk_flags")] if with_bk else None
         a = arrays or (t.ptr, t.vertex, t.metric)
+        torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
         self.ctx.routes_backup_node_device(tab.n, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), protect or self.protect, *a,
                                            routes=tuple(r[k].data_ptr() for k in ("best_metric", "best_entry", "nexthop_mask")), ydist_ptr=yd.data_ptr(),
                                            y_roots=y_roots, rn_sel=None if rn is None else tuple(x.data_ptr() for x in rn),

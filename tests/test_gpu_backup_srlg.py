@@ -44,6 +44,7 @@ class Device:
         tab, NP = self.tab, t.n
         r = dict(best_metric=torch.full((tab.R, NP), 7, dtype=torch.int32, device="cuda:0"), best_entry=torch.full((tab.R, NP), 7, dtype=torch.int32, device="cuda:0"),
                  nexthop_mask=torch.full((tab.R, NP, tab.W), 7, dtype=torch.int64, device="cuda:0"))
+        torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
         self.ctx.routes_device(tab.n, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), t.ptr, t.vertex, t.metric, flags=t.flags,
                                **{k + "_ptr": x.data_ptr() for k, x in r.items()})
         for i, rr in enumerate(self.model.root_row):
@@ -76,6 +77,7 @@ class Device:
         args = (tab.n, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), self.protect)
         kw = dict(routes=tuple(r[k].data_ptr() for k in ("best_metric", "best_entry", "nexthop_mask")), flags=t.flags, lfa_flags=lfa_flags,
                   **{k + "_ptr": x.data_ptr() for k, x in out.items()})
+        torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
         if plain:
             self.ctx.routes_backup_device(*args, t.ptr, t.vertex, t.metric, tilfa=None if ti is None else tuple(x.data_ptr() for x in ti[:3]), **kw)
         else:

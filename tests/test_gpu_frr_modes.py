@@ -65,6 +65,7 @@ def run_backup_srlg(ctx, h, t, routes, lfa_flags):
     shapes = dict(bk_kind=(1, NP), bk_primary=(1, NP), bk_slot=(1, NP), bk_metric=(1, NP), bk_flags=(1, NP), bk_cand_mask=(1, NP, tab.W),
                   bk_node_mask=(1, NP, tab.W), bk_coverage=(1, 10))
     out = {k: torch.full(sh, 7, dtype=_torch_dt(OUT[k]), device="cuda:0") for k, sh in shapes.items()}
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.routes_backup_srlg_device(tab.n, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), h.protect, h.srlgs, t.ptr, t.vertex,
                                   t.metric, tilfa=None, routes=routes, flags=t.flags, lfa_flags=lfa_flags, **{k + "_ptr": x.data_ptr() for k, x in out.items()})
     return {k: x.cpu().numpy().view(OUT[k]) for k, x in out.items()}

@@ -122,6 +122,7 @@ def run_lfa(ctx, tab, protect, lfa_flags=0, masks=True):
     cov = torch.full((P, 5), 7, dtype=torch.int32, device=dev)
     cm = torch.full((P, n, W), 7, dtype=torch.int64, device=dev) if masks else None
     nm = torch.full((P, n, W), 7, dtype=torch.int64, device=dev) if masks else None
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.lfa_device(n, tab.R, W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), protect, alt_slot_ptr=slot.data_ptr(),
                    alt_metric_ptr=metric.data_ptr(), alt_flags_ptr=fl.data_ptr(), coverage_ptr=cov.data_ptr(),
                    cand_mask_ptr=cm.data_ptr() if masks else 0, node_mask_ptr=nm.data_ptr() if masks else 0, lfa_flags=lfa_flags)

@@ -33,6 +33,7 @@ def run_ecmp(ctx, tab, protect, lfa_flags=0, cap=None):
     pri, slot, met = (torch.full((cap + 3,), SENTINEL, dtype=torch.int32, device=dev) for _ in range(3))
     fl = torch.full((cap + 3,), 7, dtype=torch.uint8, device=dev)
     cov = torch.full((P, EM.COVERAGE_WORDS), 7, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     total = ctx.lfa_ecmp_device(*args, ea_ptr_ptr=ptr.data_ptr(), cap_entries=cap, ea_primary_ptr=pri.data_ptr(), ea_slot_ptr=slot.data_ptr(),
                                 ea_metric_ptr=met.data_ptr(), ea_flags_ptr=fl.data_ptr(), ea_coverage_ptr=cov.data_ptr(), lfa_flags=lfa_flags)
     h = lambda t, dt: t.cpu().numpy().view(dt)      # noqa: E731

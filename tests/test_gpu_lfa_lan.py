@@ -38,6 +38,7 @@ def run_lfa(ctx, tab, protect, lans, lfa_flags=0, masks=True, plain=False):
     kw = dict(alt_slot_ptr=slot.data_ptr(), alt_metric_ptr=metric.data_ptr(), alt_flags_ptr=fl.data_ptr(), coverage_ptr=cov.data_ptr(),
               cand_mask_ptr=cm.data_ptr() if masks else 0, node_mask_ptr=nm.data_ptr() if masks else 0, lfa_flags=lfa_flags)
     args = (n, tab.R, W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), protect)
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     if plain:
         ctx.lfa_device(*args, **kw)
     else:
@@ -69,6 +70,7 @@ def run_backup(ctx, tab, protect, lans, pt, lfa_flags=0, masks=True, plain=False
     kw = {k + "_ptr": (0 if v is None else v.data_ptr()) for k, v in out.items()}
     call = ctx.routes_backup_device if plain else ctx.routes_backup_lan_device
     args = (n, tab.R, W, *tabs, protect) + (() if plain else (lans,)) + (pt.ptr, pt.vertex, pt.metric)
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     call(*args, routes=(bm.data_ptr(), be.data_ptr(), nh.data_ptr()), tilfa=ti, flags=pt.flags | (8 if resident else 0), lfa_flags=lfa_flags, **kw)
     dt = dict(bk_kind=np.uint8, bk_primary=np.uint32, bk_slot=np.uint32, bk_metric=np.uint32, bk_flags=np.uint8, bk_cand_mask=np.uint64,
               bk_node_mask=np.uint64, bk_coverage=np.uint32)

@@ -147,6 +147,7 @@ def run_rlfa(ctx, tab, protect, lfa_flags=0, spaces=True, alt_flags=None, rdist=
              rl_coverage=full((P, 4), torch.int32))
     alt = torch.from_numpy(np.ascontiguousarray(alt_flags)).to(dev) if alt_flags is not None else None
     ptr = lambda x: 0 if x is None else x.data_ptr()      # noqa: E731
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.rlfa_device(tab.G, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(),
                     (tab.rdist if rdist is None else rdist).data_ptr(), protect, pq_node_ptr=ptr(t["pq_node"]), pq_via_ptr=ptr(t["pq_via"]),
                     pq_metric_ptr=ptr(t["pq_metric"]), pq_counts_ptr=ptr(t["pq_counts"]), rl_node_ptr=ptr(t["rl_node"]), rl_via_ptr=ptr(t["rl_via"]),

@@ -45,6 +45,7 @@ def run_rlfa_lan(ctx, tab, protect, lans, lfa_flags=0, spaces=True, alt_flags=No
              rl_coverage=full((P, 6), torch.int32))
     alt = torch.from_numpy(np.ascontiguousarray(alt_flags)).to(dev) if alt_flags is not None else None
     ptr = lambda x: 0 if x is None else x.data_ptr()      # noqa: E731
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.rlfa_lan_device(tab.G, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), tab.rdist.data_ptr(), protect, lans,
                         pq_node_ptr=ptr(t["pq_node"]), pq_via_ptr=ptr(t["pq_via"]), pq_metric_ptr=ptr(t["pq_metric"]), pq_counts_ptr=ptr(t["pq_counts"]),
                         rl_node_ptr=ptr(t["rl_node"]), rl_via_ptr=ptr(t["rl_via"]), rl_coverage_ptr=ptr(t["rl_coverage"]),
@@ -61,6 +62,7 @@ def run_tilfa_on(ctx, tab, protect, dev_tables, alt, lfa_flags=0):
     t = dict(ti_kind=full((P, S), torch.uint8), ti_p=full((P, S), torch.int32), ti_q=full((P, S), torch.int32), ti_via=full((P, S), torch.int32),
              ti_link=full((P, S), torch.int32), ti_metric=full((P, S), torch.int32), ti_counts=full((P, S, 2), torch.int32),
              td_kind=full((P, n), torch.uint8), td_coverage=full((P, 5), torch.int32))
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.tilfa_device(tab.G, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), tab.rdist.data_ptr(), protect,
                      space_flags_ptr=dev_tables["space_flags"].data_ptr(), space_via_ptr=dev_tables["space_via"].data_ptr(),
                      alt_flags_in_ptr=0 if alt is None else alt.data_ptr(), lfa_flags=lfa_flags, **{k + "_ptr": v.data_ptr() for k, v in t.items()})

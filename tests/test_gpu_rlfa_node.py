@@ -53,11 +53,12 @@ def run_node(ctx, tab, protect, y_roots, run_flags=0, lfa_flags=0, alt_flags=Non
     alt = torch.from_numpy(np.ascontiguousarray(alt_flags)).to(dev) if alt_flags is not None else None
     ap = 0 if alt is None else alt.data_ptr()
     fwd = (tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr())
+    ydist = full((len(y_roots), n), torch.int32)
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the calls on the context's
     ctx.rlfa_device(tab.G, tab.R, tab.W, *fwd, tab.rdist.data_ptr(), protect, alt_flags_in_ptr=ap, lfa_flags=lfa_flags,
                     **{k + "_ptr": x.data_ptr() for k, x in r.items()})
     ctx.rlfa_node_select_device(n, tab.R, tab.W, *fwd, protect, space_flags_ptr=r["space_flags"].data_ptr(), max_pq=max_pq, lfa_flags=lfa_flags,
                                 **{k + "_ptr": x.data_ptr() for k, x in s.items()})
-    ydist = full((len(y_roots), n), torch.int32)
     ctx.run_device(tab.G, y_roots, run_flags, dist_ptr=ydist.data_ptr())
     ctx.rlfa_node_device(n, tab.R, tab.W, *fwd, protect, ydist_ptr=ydist.data_ptr(), y_roots=y_roots, sel=tuple(s[k].data_ptr() for k in SEL),
                          max_pq=max_pq, alt_flags_in_ptr=ap, **{k + "_ptr": 0 if x is None else x.data_ptr() for k, x in d.items()})

@@ -39,6 +39,7 @@ def run_lfa_srlg(ctx, tab, protect, srlgs, lfa_flags=0, masks=True):
              cand_mask=full((P, n, W), torch.int64) if masks else None, node_mask=full((P, n, W), torch.int64) if masks else None,
              coverage=full((P, 7), torch.int32))
     ptr = lambda x: 0 if x is None else x.data_ptr()      # noqa: E731
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.lfa_srlg_device(n, tab.R, W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), protect, srlgs, alt_slot_ptr=ptr(t["alt_slot"]),
                         alt_metric_ptr=ptr(t["alt_metric"]), alt_flags_ptr=ptr(t["alt_flags"]), coverage_ptr=ptr(t["coverage"]),
                         cand_mask_ptr=ptr(t["cand_mask"]), node_mask_ptr=ptr(t["node_mask"]), lfa_flags=lfa_flags)
@@ -57,6 +58,7 @@ def run_rlfa_srlg(ctx, tab, protect, srlgs, lfa_flags=0, spaces=True, alt_flags=
              rl_coverage=full((P, 6), torch.int32))
     alt = torch.from_numpy(np.ascontiguousarray(alt_flags)).to(dev) if alt_flags is not None else None
     ptr = lambda x: 0 if x is None else x.data_ptr()      # noqa: E731
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.rlfa_srlg_device(tab.G, tab.R, tab.W, tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(),
                          (tab.rdist if rdist is None else rdist).data_ptr(), protect, srlgs,
                          pq_node_ptr=ptr(t["pq_node"]), pq_via_ptr=ptr(t["pq_via"]), pq_metric_ptr=ptr(t["pq_metric"]), pq_counts_ptr=ptr(t["pq_counts"]),

@@ -46,6 +46,7 @@ def run_tilfa(ctx, tab, protect, lfa_flags=0, alt_flags=None, fill=7):
     alt = torch.from_numpy(np.ascontiguousarray(alt_flags)).to(dev) if alt_flags is not None else None
     ap = 0 if alt is None else alt.data_ptr()
     tables = (tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), tab.rdist.data_ptr())
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.rlfa_device(tab.G, tab.R, tab.W, *tables, protect, alt_flags_in_ptr=ap, lfa_flags=lfa_flags, **{k + "_ptr": x.data_ptr() for k, x in r.items()})
     ctx.tilfa_device(tab.G, tab.R, tab.W, *tables, protect, space_flags_ptr=r["space_flags"].data_ptr(), space_via_ptr=r["space_via"].data_ptr(),
                      alt_flags_in_ptr=ap, lfa_flags=lfa_flags, **{k + "_ptr": x.data_ptr() for k, x in t.items()})

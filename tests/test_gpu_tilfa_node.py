@@ -103,11 +103,12 @@ def run_tn(ctx, tab, protect, y_roots, run_flags=0, lfa_flags=0, alt_flags=None,
     alt, ndk = up(alt_flags), up(nd_kind)
     ptr = lambda x: 0 if x is None else x.data_ptr()      # noqa: E731
     fwd = (tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr())
+    ydist = full((len(y_roots), n), torch.int32)
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the calls on the context's
     ctx.rlfa_device(tab.G, tab.R, tab.W, *fwd, tab.rdist.data_ptr(), protect, alt_flags_in_ptr=ptr(alt), lfa_flags=lfa_flags,
                     **{k + "_ptr": x.data_ptr() for k, x in r.items()})
     ctx.tilfa_node_select_device(tab.G, tab.R, tab.W, *fwd, protect, space_flags_ptr=r["space_flags"].data_ptr(), max_pairs=max_pairs, lfa_flags=lfa_flags,
                                  **{k + "_ptr": x.data_ptr() for k, x in s.items()})
-    ydist = full((len(y_roots), n), torch.int32)
     ctx.run_device(tab.G, y_roots, run_flags, dist_ptr=ydist.data_ptr())
     ctx.tilfa_node_device(n, tab.R, tab.W, *fwd, protect, ydist_ptr=ydist.data_ptr(), y_roots=y_roots, sel=tuple(s[k].data_ptr() for k in SEL),
                           max_pairs=max_pairs, alt_flags_in_ptr=ptr(alt), nd_kind_in_ptr=ptr(ndk), **{k + "_ptr": ptr(x) for k, x in d.items()})

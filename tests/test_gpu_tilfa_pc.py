@@ -49,6 +49,7 @@ def run_pc(ctx, tab, protect, wants, run_flags=0, lfa_flags=0, alt_flags=None, m
     alt = torch.from_numpy(np.ascontiguousarray(alt_flags)).to(dev) if alt_flags is not None else None
     ap = 0 if alt is None else alt.data_ptr()
     tables = (tab.dist.data_ptr(), tab.flags.data_ptr(), tab.mask.data_ptr(), tab.rdist.data_ptr())
+    torch.cuda.synchronize()                                   # the fills run on torch's stream, the call on the context's
     ctx.rlfa_device(tab.G, tab.R, tab.W, *tables, protect, alt_flags_in_ptr=ap, lfa_flags=lfa_flags, **{k + "_ptr": x.data_ptr() for k, x in r.items()})
     hr = host(r)
     roots, fails, pc_row = [], [], np.full((NP, S), 0xFFFFFFFF, np.uint32)

@@ -106,6 +106,60 @@ def test_every_case_takes_the_branch_it_names(name, wide):
     F.run_check(F.CASES[name], wide)
 
 
+@pytest.mark.parametrize("extra", F.EXTRAS)
+@pytest.mark.parametrize("name", sorted(F.CASES))
+def test_every_case_takes_its_branch_at_every_width(name, extra):
+    """130, 300, 520 and 960 spokes at the case's first root: the oracle needs 3, 5, 9 and 16 mask words (run_check asserts it) and
+    every case's own check still holds."""
+    from oracle import graph_oracle as go
+    go.build()
+    F.run_check(F.CASES[name], extra=extra)
+
+
+@pytest.mark.parametrize("name,extra", [(n, e) for n, c in sorted(F.WIDE_CASES.items()) for e in sorted(c.words)])
+def test_the_wide_only_cases_take_their_branch(name, extra):
+    from oracle import graph_oracle as go
+    go.build()
+    c = F.WIDE_CASES[name]
+    g, ref = F.run_check(c, extra=extra or None)
+    assert ref.mask.shape[2] == c.words[extra] > 1
+
+
+def test_the_case_list_has_the_new_branches_and_one_word_bases():
+    """The cases the wide GPU tests lean on are there; every case of CASES fits one mask word unwidened with at most 20 slots (what
+    the table F.WORDS assumes), the hop-count-like ones are hop-count-like and the others are not (run_check asserts both)."""
+    assert {"high_slot_detour", "giant_row_far", "hub_far_link", "hopcount_lan_first_parent"} <= set(F.CASES) and "giant_row_member" in F.WIDE_CASES
+    assert F.CASES["high_slot_detour"].front and F.CASES["hopcount_lan_first_parent"].hopcount
+    for name, c in F.CASES.items():
+        g = c.graph()
+        assert max(F.slot_bases(g, int(r))[1] for r in c.roots) <= 20, name
+        assert F.is_hopcount_like(g) == c.hopcount and F.is_hopcount_like(c.at(130).graph()) == c.hopcount, name
+    top = F.CASES["high_slot_detour"].at(960)
+    assert top.fails == [(F.ROOT_LINK, 960)] and top.graph()[1][960:962].tolist() == [1, 5]
+
+
+def test_the_hopcount_sweep_is_hopcount_like_and_sees_failures_bite():
+    """Non-vacuity of the seeded hop-count-like graphs of tests/test_gpu_failures_wide.py, on the CPU oracle: all 20 have the shape,
+    20 to 60 vertices and three router roots; failures of network vertices occur in every graph, and nearly every row differs from
+    the plain row of its root."""
+    from oracle import graph_oracle as go
+    go.build()
+    rows = nets = bite = 0
+    for seed in F.HOPCOUNT_SEEDS:
+        c = F.hopcount_random(seed)
+        g = c.graph()
+        assert F.is_hopcount_like(g) and 20 <= len(c.vf) <= 60 and len(set(c.roots)) == 3 and not any(c.vf[r] & F.NET for r in c.roots)
+        ref = F.reference(g, c.maxp, c.roots, c.fails)
+        plain = F.reference(g, c.maxp, c.roots, [(F.NONE, 0)] * len(c.roots))
+        assert ref.mask.shape[2] == 1
+        k = sum(1 for kind, a in c.fails if kind == F.VERTEX and c.vf[a] & F.NET)
+        assert k >= 3
+        nets += k
+        rows += len(c.roots)
+        bite += sum(F._differs(ref, plain, r) for r in range(len(c.roots)))
+    assert rows >= 200 and nets >= 100 and bite >= rows * 9 // 10, (rows, nets, bite)
+
+
 def test_the_protocol_sweep_patches_half_and_sees_failures_bite():
     """Non-vacuity of the protocol sweep of tests/test_gpu_failures.py, on the CPU oracle: about half of its 40 graphs really lose
     a link to the patch, and in most graphs a failure row differs from the plain row of its root."""
@@ -149,3 +203,17 @@ def test_driver_cpu_legs_reproduce_the_oracle_rows(tmp_path, engine):
     m = LINE.search(out.stdout)
     assert out.returncode == 0 and m, out.stdout + out.stderr
     assert int(m.group(1)) == len(files) and int(m.group(2)) >= len(files) + 129 and int(m.group(3)) == 0
+
+
+@pytest.mark.parametrize("engine", ["host", "oracle"])
+def test_driver_cpu_legs_at_every_width_and_on_hopcount_graphs(tmp_path, engine):
+    """The host twin and the model on F.wide_runs(): every case at 3, 5, 9 and 16 mask words, the wide-only cases, the seeded
+    hop-count-like graphs at one word and at five."""
+    _build_driver()
+    files = F.driver_files_wide(tmp_path)
+    assert len(files) == 4 * len(F.CASES) + 4 + 2 * len(F.HOPCOUNT_SEEDS)
+    out = subprocess.run([DRIVER, "--engine", engine, "--oracle-so", os.path.join(ROOT, "oracle", "liboracle_spf.so")] + files,
+                         capture_output=True, text=True, timeout=300)
+    m = LINE.search(out.stdout)
+    assert out.returncode == 0 and m, out.stdout[-2000:] + out.stderr[-2000:]
+    assert int(m.group(1)) == len(files) and int(m.group(2)) >= 2 * len(files) and int(m.group(3)) == 0
