@@ -699,6 +699,75 @@ class SpfGraph:
             pass
 
 
+# ---- the fast-reroute chains of SpfContext: the names and shapes of what they keep on the device ---------------------------
+
+TILFA_FIELDS = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")     # TilfaResult, HspfTilfaOut
+BACKUP_FIELDS = ("best_metric", "best_entry", "nexthop_mask", "bk_kind", "bk_primary", "bk_slot", "bk_metric", "bk_flags", "bk_cand_mask",
+                 "bk_node_mask", "bk_coverage")                      # BackupRoutes: the three of routes_device(), then HspfBackupOut
+_TILFA_IN = ("ti_kind", "ti_via", "ti_metric", "ti_p", "ti_link")    # `tilfa` of the per-prefix backup calls: the first three, all five for SRLG
+_SRLG_WIDTHS = dict(lfa_cov=LFA_SRLG_COVERAGE_WORDS, pq_counts=RLFA_SRLG_COUNT_WORDS, rl_cov=RLFA_SRLG_COVERAGE_WORDS)
+
+
+def _frr_shapes(*groups, n: int = 0, S: int = 0, NP: int = 0, W: int = 0, M: int = 0, lfa_cov: int = LFA_COVERAGE_WORDS,
+                pq_counts: int = RLFA_COUNT_WORDS, rl_cov: int = RLFA_COVERAGE_WORDS, bk_cov: int = BK_COVERAGE_WORDS, masks=None) -> dict:
+    """{name: (shape, dtype)} of what the calls of a chain write for ONE protected root, group by group in the order given (a group
+    that is False or None is skipped).  n vertices, S = 64 * mask words slots, NP prefixes, W mask words, M list entries per slot;
+    the coverage and count widths are the plain calls' unless given.  masks (group "lfa"): None — no mask entries, False — entries of
+    None (no buffer, pointer 0), True — the two tables."""
+    u8, u32, u64 = np.uint8, np.uint32, np.uint64
+
+    def cols(shape, names, bytes_=()):
+        return {k: (shape, u8 if k in bytes_ else u32) for k in names}
+    table = {
+        "lfa": lambda: dict(cols((1, n), ("slot", "metric", "aflags"), ("aflags",)),
+                            **({} if masks is None else dict.fromkeys(("cm", "nm"), ((1, n, W), u64) if masks else None)), cov=((1, lfa_cov), u32)),
+        "rlfa": lambda: dict(cols((1, S), ("pq_node", "pq_via", "pq_metric")), pq_counts=((1, S, pq_counts), u32),
+                             **cols((1, n), ("rl_node", "rl_via")), rl_cov=((1, rl_cov), u32)),
+        "spaces": lambda: cols((1, S, n), ("sp_flags", "sp_via"), ("sp_flags",)),
+        "tilfa": lambda: dict(cols((1, S), TILFA_FIELDS[:6], ("ti_kind",)), ti_counts=((1, S, TILFA_COUNT_WORDS), u32), td_kind=((1, n), u8),
+                              td_coverage=((1, TILFA_COVERAGE_WORDS), u32)),
+        "tilfa_pc": lambda: dict(cols((1, n), TILFA_PC_FIELDS[:-1], ("tp_kind", "tp_n_adj", "tp_flags")), tp_hop_pos=((1, n, TIPC_MAX_ADJ), u32),
+                                 tp_hop_head=((1, n, TIPC_MAX_ADJ), u32), tp_coverage=((1, TIPC_COVERAGE_WORDS), u32)),
+        "backup": lambda: dict(cols((1, NP), BACKUP_FIELDS[:-1], ("bk_kind", "bk_flags")),
+                               **dict.fromkeys(("nexthop_mask", "bk_cand_mask", "bk_node_mask"), ((1, NP, W), u64)), bk_coverage=((1, bk_cov), u32)),
+        "rn_sel": lambda: dict(cols((1, S, M), ("nq_node", "nq_via", "nq_metric")), nq_count=((1, S), u32)),
+        "tn_sel": lambda: dict(cols((1, S, M), ("tq_q", "tq_p", "tq_link", "tq_via", "tq_metric")), tq_count=((1, S), u32)),
+        "nd": lambda: dict(cols((1, n), ("nd_kind", "nd_node", "nd_via", "nd_metric", "nd_set"), ("nd_kind",)), nd_coverage=((1, NP_COVERAGE_WORDS), u32)),
+        "tn": lambda: dict(cols((1, n), ("tn_kind", "tn_p", "tn_q", "tn_link", "tn_via", "tn_metric", "tn_set"), ("tn_kind",)),
+                           tn_coverage=((1, TN_COVERAGE_WORDS), u32)),
+        "bn": lambda: dict(cols((1, NP), ("bn_kind", "bn_primary", "bn_p", "bn_q", "bn_link", "bn_via", "bn_metric", "bn_set_pq", "bn_set_pair"), ("bn_kind",)),
+                           bn_coverage=((1, BN_COVERAGE_WORDS), u32)),
+    }
+    out = {}
+    for g in groups:
+        if g:
+            out.update(table[g]())
+    return out
+
+
+def _empty(shapes: dict) -> dict:
+    """Host arrays for the entries of _frr_shapes()."""
+    return {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
+
+
+def _dev_bytes(shapes: dict) -> dict:
+    """Device buffer sizes for the entries of _frr_shapes(): never 0, so that every pointer of the chain is non-null."""
+    return {k: max(int(np.prod(sh)) * np.dtype(dt).itemsize, 8) for k, (sh, dt) in shapes.items()}
+
+
+def _ref(struct):
+    return None if struct is None else ctypes.byref(struct)
+
+
+def _lfa_result(host: dict, lan=None) -> LfaResult:
+    return LfaResult(host["slot"], host["metric"], host["aflags"], host.get("cm"), host.get("nm"), host["cov"], lan=lan)
+
+
+def _rlfa_result(host: dict) -> RlfaResult:
+    return RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"), host.get("sp_via"),
+                      host["rl_node"], host["rl_via"], host["rl_cov"])
+
+
 class SpfContext:
     """One engine context: device, HIP stream, scratch (hspf_ctx).  One thread at a time."""
 
@@ -1044,6 +1113,30 @@ class SpfContext:
                                       cols[4].ctypes.data_as(L.u8p))
         return arr, keep
 
+    @staticmethod
+    def _out(struct, **ptrs):
+        """An out or sel struct of device pointers from its field names (a wrapper's keyword without `_ptr`): 0 becomes NULL, and
+        so does every field that is not named."""
+        return struct(**{k: v or None for k, v in ptrs.items()})
+
+    def _frr_call(self, name: str, tables, protect, tail, *, graph=None, rdist_ptr=None, lans=None, srlgs=None) -> None:
+        """The one way into the library for the fast-reroute calls: hspf_<name>(ctx[, graph], n_vertices, n_rows, mask_words, dist,
+        flags, mask[, rdist], protect array[, LAN or SRLG array], len(protect), *tail).  tables = (n_vertices, n_rows, mask_words,
+        dist_ptr, flags_ptr, mask_ptr); graph: the calls that scan the graph's links take its handle in front of n_vertices;
+        rdist_ptr: None for the calls that have no such argument (0: a NULL one).  The numpy columns behind the arrays live until the call is over."""
+        n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr = tables
+        arr, keep = self._protect_array(protect, name)
+        side = []
+        if lans is not None:
+            side.append(self._lan_array(lans, protect, name))
+        if srlgs is not None:
+            side.append(self._srlg_array(srlgs, protect, name))
+        rc = getattr(self.lib, "hspf_" + name)(self.handle, *(() if graph is None else (graph.handle,)), n_vertices, n_rows, mask_words,
+                                               dist_ptr or None, flags_ptr or None, mask_ptr or None,
+                                               *(() if rdist_ptr is None else (rdist_ptr or None,)), arr, *(a for a, _ in side), len(protect), *tail)
+        del keep, side
+        self._check_rc("hspf_" + name, rc)
+
     def lfa_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                    alt_slot_ptr: int, alt_metric_ptr: int, alt_flags_ptr: int, coverage_ptr: int, cand_mask_ptr: int = 0,
                    node_mask_ptr: int = 0, lfa_flags: int = 0) -> None:
@@ -1051,12 +1144,9 @@ class SpfContext:
         `protect`: a list of (root_row, LfaCandidates, nbr_row) — nbr_row[k] = table row of the SPT rooted at
         candidates.nbr[k] (ignored where the slot is no candidate).  All `*_ptr` are device pointers; cand_mask_ptr /
         node_mask_ptr may be 0."""
-        arr, keep = self._protect_array(protect, "lfa_device")
-        out = L.HspfLfaOut(alt_slot_ptr or None, alt_metric_ptr or None, alt_flags_ptr or None, cand_mask_ptr or None, node_mask_ptr or None,
-                           coverage_ptr or None)
-        rc = self.lib.hspf_lfa_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                      arr, len(protect), lfa_flags, ctypes.byref(out))
-        self._check_rc("hspf_lfa_device", rc)
+        out = self._out(L.HspfLfaOut, alt_slot=alt_slot_ptr, alt_metric=alt_metric_ptr, alt_flags=alt_flags_ptr, cand_mask=cand_mask_ptr,
+                        node_mask=node_mask_ptr, coverage=coverage_ptr)
+        self._frr_call("lfa_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect, (lfa_flags, ctypes.byref(out)))
 
     @staticmethod
     def _lan_array(lans, protect, who: str):
@@ -1079,14 +1169,10 @@ class SpfContext:
         """hspf_lfa_lan_device(): lfa_device() with loop-freeness towards the pseudonode of every primary's LAN (RFC 5286
         section 3.3).  `lans`: per protected root (lan, lan_row) — lfa_lan_candidates() and, where lan[k] is a vertex, the table
         row of the SPT rooted at it.  coverage_ptr: [P, LFA_LAN_COVERAGE_WORDS] u32."""
-        arr, keep = self._protect_array(protect, "lfa_lan_device")
-        larr, lkeep = self._lan_array(lans, protect, "lfa_lan_device")
-        out = L.HspfLfaOut(alt_slot_ptr or None, alt_metric_ptr or None, alt_flags_ptr or None, cand_mask_ptr or None, node_mask_ptr or None,
-                           coverage_ptr or None)
-        rc = self.lib.hspf_lfa_lan_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                          arr, larr, len(protect), lfa_flags, ctypes.byref(out))
-        del keep, lkeep
-        self._check_rc("hspf_lfa_lan_device", rc)
+        out = self._out(L.HspfLfaOut, alt_slot=alt_slot_ptr, alt_metric=alt_metric_ptr, alt_flags=alt_flags_ptr, cand_mask=cand_mask_ptr,
+                        node_mask=node_mask_ptr, coverage=coverage_ptr)
+        self._frr_call("lfa_lan_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect, (lfa_flags, ctypes.byref(out)),
+                       lans=lans)
 
     def _check_rc(self, name: str, rc: int) -> None:
         if rc != 0:
@@ -1137,30 +1223,71 @@ class SpfContext:
         roots = np.concatenate([roots, lans]).astype(np.uint32)
         return FrrPlan(cand, roots, nbr_row, max(graph.mask_words(roots), (cand.n_slots + 63) // 64), lan, lan_row)
 
+    @contextlib.contextmanager
+    def _frr_tables(self, graph: SpfGraph, plan: FrrPlan, run_flags: int, sizes: dict, *, transposed: bool):
+        """What every one-root chain starts with: device buffers for the table set of the plan's roots (dist / flags / mask, and
+        rdist when `transposed`) and for `sizes`, run_device() of those roots, and — when `transposed` — the same run on the
+        transposed graph (csr_transpose, uploaded after the forward run, freed when the chain ends).  Yields (dev, tables, rdist,
+        protect): dev = {name: pointer}, tables = (n, R, W, dist, flags, mask), rdist = the forward dist unless `transposed`."""
+        R, n, W = len(plan.roots), graph.n, plan.mask_words
+        with self._dev_buffers(dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=4 * R * n if transposed else 0, **sizes)) as dev, \
+                contextlib.ExitStack() as cleanup:
+            self.run_device(graph, plan.roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
+            if transposed:
+                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
+                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
+                cleanup.callback(GT.free)
+                self.run_device(GT, plan.roots, run_flags, dist_ptr=dev["rdist"])
+            yield dev, (n, R, W, dev["dist"], dev["flags"], dev["mask"]), dev["rdist"] if transposed else dev["dist"], [(0, plan.cand, plan.nbr_row)]
+
+    def _frr_steps(self, graph: SpfGraph, tables, rdist: int, protect, dev: dict, lfa_flags: int, *, lfa_lans=None, rlfa_lans=None, srlgs=None,
+                   remote: bool = True, tilfa: bool = False) -> None:
+        """The calls of a chain behind _frr_tables(), everything left on the device in `dev` (buffers named as in _frr_shapes()): the
+        LFA call, with `remote` the remote-LFA call on its alt_flags (the space tables where `dev` has them), with `tilfa`
+        tilfa_device() on those tables.  lfa_lans / rlfa_lans / srlgs: the LAN or SRLG call takes the plain one's place."""
+        out = dict(alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"],
+                   cand_mask_ptr=dev.get("cm", 0), node_mask_ptr=dev.get("nm", 0), lfa_flags=lfa_flags)
+        if srlgs is not None:
+            self.lfa_srlg_device(*tables, protect, srlgs, **out)
+        elif lfa_lans is not None:
+            self.lfa_lan_device(*tables, protect, lfa_lans, **out)
+        else:
+            self.lfa_device(*tables, protect, **out)
+        if not remote:
+            return
+        gtables = (graph, *tables[1:], rdist, protect)
+        out = dict(pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
+                   rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"], space_flags_ptr=dev.get("sp_flags", 0),
+                   space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags)
+        if srlgs is not None:
+            self.rlfa_srlg_device(*gtables, srlgs, **out)
+        elif rlfa_lans is not None:
+            self.rlfa_lan_device(*gtables, rlfa_lans, **out)
+        else:
+            self.rlfa_device(*gtables, **out)
+        if tilfa:
+            self.tilfa_device(*gtables, space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"],
+                              lfa_flags=lfa_flags, **{k + "_ptr": dev[k] for k in TILFA_FIELDS})
+
+    def _lfa(self, graph: SpfGraph, plan: FrrPlan, run_flags: int, lfa_flags: int, want_masks: bool, cov_words: int, **side) -> LfaResult:
+        """The chain of lfa() and lfa_srlg(): the run of the plan's roots, the LFA call (side: lfa_lans or srlgs of _frr_steps()), the
+        five arrays and the coverage on the host."""
+        shapes = _frr_shapes("lfa", n=graph.n, W=plan.mask_words, lfa_cov=cov_words, masks=want_masks)
+        host = {k: np.empty(*sh) if sh else None for k, sh in shapes.items()}
+        with self._frr_tables(graph, plan, run_flags, {k: 0 if a is None else a.nbytes for k, a in host.items()}, transposed=False) as (
+                dev, tables, rdist, protect):
+            self._frr_steps(graph, tables, rdist, protect, dev, lfa_flags, remote=False, **side)
+            self._fetch(host, dev)
+        return _lfa_result(host, plan.lan)
+
     def lfa(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, want_masks: bool = True, lan_protect: bool = False):
         """Backup next hops of one root, start to finish: the candidate table of `root`, ONE run_device() for
         [root] + its distinct neighbour routers, lfa_device() on those rows, the five arrays and the coverage on the host.
         Returns (LfaCandidates, LfaResult with one row).  The SPT tables never leave the device.  lan_protect: the run also holds
         the SPTs of the root's LANs and lfa_lan_device() takes lfa_device()'s place (seven coverage words, `lan` filled)."""
         plan = self._frr_plan(graph, root, lan_protect)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n = len(roots), graph.n
-        masks = ((1, n, W), np.uint64) if want_masks else None
-        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cm=masks, nm=masks,
-                      cov=((1, LFA_LAN_COVERAGE_WORDS if lan_protect else LFA_COVERAGE_WORDS), np.uint32))
-        host = {k: np.empty(*sh) if sh else None for k, sh in shapes.items()}
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W)
-        sizes.update({k: 0 if a is None else a.nbytes for k, a in host.items()})
-        with self._dev_buffers(sizes) as dev:
-            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-            out = dict(alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"],
-                       cand_mask_ptr=dev["cm"], node_mask_ptr=dev["nm"], lfa_flags=lfa_flags)
-            if lan_protect:
-                self.lfa_lan_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], plan.lans, **out)
-            else:
-                self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], **out)
-            self._fetch(host, dev)
-        return cand, LfaResult(*host.values(), lan=plan.lan)
+        return plan.cand, self._lfa(graph, plan, run_flags, lfa_flags, want_masks, LFA_LAN_COVERAGE_WORDS if lan_protect else LFA_COVERAGE_WORDS,
+                                    lfa_lans=plan.lans if lan_protect else None)
 
     def lfa_ecmp_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                         ea_ptr_ptr: int, cap_entries: int = 0, ea_primary_ptr: int = 0, ea_slot_ptr: int = 0, ea_metric_ptr: int = 0,
@@ -1170,14 +1297,11 @@ class SpfContext:
         `cap_entries` elements each (0 with cap_entries == 0: ea_ptr and the total alone), ea_coverage_ptr
         [P, LFA_ECMP_COVERAGE_WORDS] u32.  Returns the total number of entries; when it exceeds cap_entries only ea_ptr was
         written and the call is to be repeated with larger arrays."""
-        arr, keep = self._protect_array(protect, "lfa_ecmp_device")
-        out = L.HspfLfaEcmpOut(ea_ptr_ptr or None, ea_primary_ptr or None, ea_slot_ptr or None, ea_metric_ptr or None, ea_flags_ptr or None,
-                               ea_coverage_ptr or None)
+        out = self._out(L.HspfLfaEcmpOut, ea_ptr=ea_ptr_ptr, ea_primary=ea_primary_ptr, ea_slot=ea_slot_ptr, ea_metric=ea_metric_ptr,
+                        ea_flags=ea_flags_ptr, ea_coverage=ea_coverage_ptr)
         total = ctypes.c_uint64()
-        rc = self.lib.hspf_lfa_ecmp_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                           arr, len(protect), lfa_flags, cap_entries, ctypes.byref(out), ctypes.byref(total))
-        del keep
-        self._check_rc("hspf_lfa_ecmp_device", rc)
+        self._frr_call("lfa_ecmp_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, cap_entries, ctypes.byref(out), ctypes.byref(total)))
         return int(total.value)
 
     def lfa_ecmp(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0):
@@ -1185,24 +1309,21 @@ class SpfContext:
         lfa_ecmp_device() twice on those rows — once for ea_ptr and the total, once with arrays of that size.
         Returns (LfaCandidates, LfaEcmpResult with one protected root)."""
         plan = self._frr_plan(graph, root)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n = len(roots), graph.n
-        protect = [(0, cand, nbr_row)]
+        n = graph.n
         ptr = np.empty(n + 1, np.uint32)
         cov = np.zeros((1, LFA_ECMP_COVERAGE_WORDS), np.uint32)
-        with self._dev_buffers(dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, ptr=ptr.nbytes)) as dev:
-            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-            tables = (n, R, W, dev["dist"], dev["flags"], dev["mask"], protect)
-            total = self.lfa_ecmp_device(*tables, ea_ptr_ptr=dev["ptr"], lfa_flags=lfa_flags)
+        with self._frr_tables(graph, plan, run_flags, dict(ptr=ptr.nbytes), transposed=False) as (dev, tables, _, protect):
+            total = self.lfa_ecmp_device(*tables, protect, ea_ptr_ptr=dev["ptr"], lfa_flags=lfa_flags)
             host = dict(primary=np.empty(total, np.uint32), slot=np.empty(total, np.uint32), metric=np.empty(total, np.uint32),
                         eflags=np.empty(total, np.uint8))
             if total:
                 with self._dev_buffers(dict({k: a.nbytes for k, a in host.items()}, cov=cov.nbytes)) as ent:
-                    self.lfa_ecmp_device(*tables, ea_ptr_ptr=dev["ptr"], cap_entries=total, ea_primary_ptr=ent["primary"], ea_slot_ptr=ent["slot"],
-                                         ea_metric_ptr=ent["metric"], ea_flags_ptr=ent["eflags"], ea_coverage_ptr=ent["cov"], lfa_flags=lfa_flags)
+                    self.lfa_ecmp_device(*tables, protect, ea_ptr_ptr=dev["ptr"], cap_entries=total, ea_primary_ptr=ent["primary"],
+                                         ea_slot_ptr=ent["slot"], ea_metric_ptr=ent["metric"], ea_flags_ptr=ent["eflags"], ea_coverage_ptr=ent["cov"],
+                                         lfa_flags=lfa_flags)
                     self._fetch(dict(host, cov=cov), ent)
             self._fetch(dict(ptr=ptr), dev)
-        return cand, LfaEcmpResult(ptr, host["primary"], host["slot"], host["metric"], host["eflags"], cov, n_vertices=n)
+        return plan.cand, LfaEcmpResult(ptr, host["primary"], host["slot"], host["metric"], host["eflags"], cov, n_vertices=n)
 
     def rlfa_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                     protect, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int, rl_via_ptr: int,
@@ -1211,13 +1332,10 @@ class SpfContext:
         primary, from the forward table set of a run_device() and `rdist_ptr`, the dist of the same roots on the transposed
         graph (the forward dist itself on a symmetric-cost graph).  `protect` as for lfa_device(); all `*_ptr` are device
         pointers, the slot arrays are strided by 64 * mask_words; space_*_ptr / alt_flags_in_ptr may be 0."""
-        arr, keep = self._protect_array(protect, "rlfa_device")
-        out = L.HspfRlfaOut(pq_node_ptr or None, pq_via_ptr or None, pq_metric_ptr or None, pq_counts_ptr or None, space_flags_ptr or None,
-                            space_via_ptr or None, rl_node_ptr or None, rl_via_ptr or None, rl_coverage_ptr or None)
-        rc = self.lib.hspf_rlfa_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                       rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_rlfa_device", rc)
+        out = self._out(L.HspfRlfaOut, pq_node=pq_node_ptr, pq_via=pq_via_ptr, pq_metric=pq_metric_ptr, pq_counts=pq_counts_ptr,
+                        space_flags=space_flags_ptr, space_via=space_via_ptr, rl_node=rl_node_ptr, rl_via=rl_via_ptr, rl_coverage=rl_coverage_ptr)
+        self._frr_call("rlfa_device", (graph.n, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, alt_flags_in_ptr or None, ctypes.byref(out)), graph=graph, rdist_ptr=rdist_ptr or 0)
 
     def rlfa_lan_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                         protect, lans, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int,
@@ -1227,15 +1345,10 @@ class SpfContext:
         `lans` as for lfa_lan_device(); both table sets come from the run [root] + neighbour routers + LANs, and `rdist_ptr` is
         ALWAYS the dist of that list on the transposed graph (a pseudonode's links cost 0 one way: the forward dist is no
         substitute).  pq_counts_ptr: [P, S, RLFA_LAN_COUNT_WORDS] u32, rl_coverage_ptr: [P, RLFA_LAN_COVERAGE_WORDS] u32."""
-        arr, keep = self._protect_array(protect, "rlfa_lan_device")
-        larr, lkeep = self._lan_array(lans, protect, "rlfa_lan_device")
-        out = L.HspfRlfaOut(pq_node_ptr or None, pq_via_ptr or None, pq_metric_ptr or None, pq_counts_ptr or None, space_flags_ptr or None,
-                            space_via_ptr or None, rl_node_ptr or None, rl_via_ptr or None, rl_coverage_ptr or None)
-        rc = self.lib.hspf_rlfa_lan_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
-                                           mask_ptr or None, rdist_ptr or None, arr, larr, len(protect), lfa_flags, alt_flags_in_ptr or None,
-                                           ctypes.byref(out))
-        del keep, lkeep
-        self._check_rc("hspf_rlfa_lan_device", rc)
+        out = self._out(L.HspfRlfaOut, pq_node=pq_node_ptr, pq_via=pq_via_ptr, pq_metric=pq_metric_ptr, pq_counts=pq_counts_ptr,
+                        space_flags=space_flags_ptr, space_via=space_via_ptr, rl_node=rl_node_ptr, rl_via=rl_via_ptr, rl_coverage=rl_coverage_ptr)
+        self._frr_call("rlfa_lan_device", (graph.n, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, alt_flags_in_ptr or None, ctypes.byref(out)), graph=graph, rdist_ptr=rdist_ptr or 0, lans=lans)
 
     @staticmethod
     def _srlg_array(srlgs, protect, who: str):
@@ -1265,14 +1378,10 @@ class SpfContext:
         """hspf_lfa_srlg_device(): lfa_device() whose alternates neither start on nor cross a link that shares a risk group with a
         primary's first link.  `srlgs`: per protected root a SrlgMembers with tail_row / head_row filled (the rows of the SPTs
         rooted at the members' endpoints).  coverage_ptr: [P, LFA_SRLG_COVERAGE_WORDS] u32."""
-        arr, keep = self._protect_array(protect, "lfa_srlg_device")
-        sarr, skeep = self._srlg_array(srlgs, protect, "lfa_srlg_device")
-        out = L.HspfLfaOut(alt_slot_ptr or None, alt_metric_ptr or None, alt_flags_ptr or None, cand_mask_ptr or None, node_mask_ptr or None,
-                           coverage_ptr or None)
-        rc = self.lib.hspf_lfa_srlg_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                           arr, sarr, len(protect), lfa_flags, ctypes.byref(out))
-        del keep, skeep
-        self._check_rc("hspf_lfa_srlg_device", rc)
+        out = self._out(L.HspfLfaOut, alt_slot=alt_slot_ptr, alt_metric=alt_metric_ptr, alt_flags=alt_flags_ptr, cand_mask=cand_mask_ptr,
+                        node_mask=node_mask_ptr, coverage=coverage_ptr)
+        self._frr_call("lfa_srlg_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect, (lfa_flags, ctypes.byref(out)),
+                       srlgs=srlgs)
 
     def rlfa_srlg_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                          protect, srlgs, *, pq_node_ptr: int, pq_via_ptr: int, pq_metric_ptr: int, pq_counts_ptr: int, rl_node_ptr: int,
@@ -1281,15 +1390,10 @@ class SpfContext:
         """hspf_rlfa_srlg_device(): rlfa_device() with P, extended P and Q narrowed to the vertices whose paths cross no member of
         the slot's risk group.  `srlgs` as for lfa_srlg_device(); both table sets come from the run [root] + neighbour routers +
         member endpoints.  pq_counts_ptr: [P, S, RLFA_SRLG_COUNT_WORDS] u32, rl_coverage_ptr: [P, RLFA_SRLG_COVERAGE_WORDS] u32."""
-        arr, keep = self._protect_array(protect, "rlfa_srlg_device")
-        sarr, skeep = self._srlg_array(srlgs, protect, "rlfa_srlg_device")
-        out = L.HspfRlfaOut(pq_node_ptr or None, pq_via_ptr or None, pq_metric_ptr or None, pq_counts_ptr or None, space_flags_ptr or None,
-                            space_via_ptr or None, rl_node_ptr or None, rl_via_ptr or None, rl_coverage_ptr or None)
-        rc = self.lib.hspf_rlfa_srlg_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
-                                            mask_ptr or None, rdist_ptr or None, arr, sarr, len(protect), lfa_flags, alt_flags_in_ptr or None,
-                                            ctypes.byref(out))
-        del keep, skeep
-        self._check_rc("hspf_rlfa_srlg_device", rc)
+        out = self._out(L.HspfRlfaOut, pq_node=pq_node_ptr, pq_via=pq_via_ptr, pq_metric=pq_metric_ptr, pq_counts=pq_counts_ptr,
+                        space_flags=space_flags_ptr, space_via=space_via_ptr, rl_node=rl_node_ptr, rl_via=rl_via_ptr, rl_coverage=rl_coverage_ptr)
+        self._frr_call("rlfa_srlg_device", (graph.n, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, alt_flags_in_ptr or None, ctypes.byref(out)), graph=graph, rdist_ptr=rdist_ptr or 0, srlgs=srlgs)
 
     def _srlg_plan(self, graph: SpfGraph, root: int, grp_ptr, grp):
         """_frr_plan() for the SRLG calls: the distinct member endpoints that are not yet roots are appended to the run, and the
@@ -1308,21 +1412,7 @@ class SpfContext:
         the members' endpoints, lfa_srlg_device() on those rows.  Returns (LfaCandidates, SrlgMembers, LfaResult with seven
         coverage words)."""
         plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n = len(roots), graph.n
-        masks = ((1, n, W), np.uint64) if want_masks else None
-        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cm=masks, nm=masks,
-                      cov=((1, LFA_SRLG_COVERAGE_WORDS), np.uint32))
-        host = {k: np.empty(*sh) if sh else None for k, sh in shapes.items()}
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W)
-        sizes.update({k: 0 if a is None else a.nbytes for k, a in host.items()})
-        with self._dev_buffers(sizes) as dev:
-            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-            self.lfa_srlg_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], [(0, cand, nbr_row)], [mem], alt_slot_ptr=dev["slot"],
-                                 alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], cand_mask_ptr=dev["cm"],
-                                 node_mask_ptr=dev["nm"], lfa_flags=lfa_flags)
-            self._fetch(host, dev)
-        return cand, mem, LfaResult(*host.values())
+        return plan.cand, mem, self._lfa(graph, plan, run_flags, lfa_flags, want_masks, LFA_SRLG_COVERAGE_WORDS, srlgs=[mem])
 
     def rlfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int = 0, *, lfa_flags: int = 0, want_spaces: bool = False,
                   symmetric: bool = False):
@@ -1331,67 +1421,17 @@ class SpfContext:
         Returns (LfaCandidates, SrlgMembers, LfaResult without masks, RlfaResult)."""
         return self._rlfa_srlg(graph, root, grp_ptr, grp, run_flags, lfa_flags, want_spaces, symmetric, False)
 
-    _TI_NAMES = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
-
-    @staticmethod
-    def _srlg_shapes(n: int, S: int, want_spaces: bool, tilfa: bool) -> dict:
-        """{name: (shape, dtype)} of what _srlg_chain() writes for one protected root."""
-        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8), cov=((1, LFA_SRLG_COVERAGE_WORDS), np.uint32),
-                      pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
-                      pq_counts=((1, S, RLFA_SRLG_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32), rl_via=((1, n), np.uint32),
-                      rl_cov=((1, RLFA_SRLG_COVERAGE_WORDS), np.uint32))
-        if want_spaces or tilfa:
-            shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
-        if tilfa:
-            shapes.update(ti_kind=((1, S), np.uint8), ti_p=((1, S), np.uint32), ti_q=((1, S), np.uint32), ti_via=((1, S), np.uint32),
-                          ti_link=((1, S), np.uint32), ti_metric=((1, S), np.uint32), ti_counts=((1, S, TILFA_COUNT_WORDS), np.uint32),
-                          td_kind=((1, n), np.uint8), td_coverage=((1, TILFA_COVERAGE_WORDS), np.uint32))
-        return shapes
-
-    def _srlg_chain(self, graph: SpfGraph, plan: FrrPlan, mem: SrlgMembers, run_flags: int, lfa_flags: int, symmetric: bool, tilfa: bool, dev: dict,
-                    cleanup) -> list:
-        """The device side rlfa_srlg(), tilfa_srlg() and backup_routes(srlg=...) share, everything left on the device in the buffers
-        of _srlg_shapes() (`dev`, next to dist / flags / mask / rdist): run_device() of the plan's roots (on the transposed graph too
-        unless `symmetric`), lfa_srlg_device(), rlfa_srlg_device() and — with `tilfa` — tilfa_device() on the safe tables.  Returns
-        the protect list."""
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n = len(roots), graph.n
-        self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-        if not symmetric:
-            trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
-            GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
-            cleanup.callback(GT.free)
-            self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
-        rdist = dev["dist"] if symmetric else dev["rdist"]
-        protect = [(0, cand, nbr_row)]
-        self.lfa_srlg_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, [mem], alt_slot_ptr=dev["slot"],
-                             alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
-        self.rlfa_srlg_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, [mem], pq_node_ptr=dev["pq_node"],
-                              pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
-                              rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
-                              space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
-                              lfa_flags=lfa_flags)
-        if tilfa:
-            self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], rdist, protect, space_flags_ptr=dev["sp_flags"],
-                              space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
-                              **{k + "_ptr": dev[k] for k in self._TI_NAMES})
-        return protect
-
     def _rlfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int, lfa_flags: int, want_spaces: bool, symmetric: bool, tilfa: bool):
         """The chain behind rlfa_srlg() and tilfa_srlg() (tilfa: tilfa_device() runs on the safe tables, its TilfaResult is appended;
         a TILFA_PAIR's forced link is NOT checked against the members: compare (ti_p, ti_link) with the slot's (tail, pos) list)."""
         plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
-        cand, R, n, W = plan.cand, len(plan.roots), graph.n, plan.mask_words
-        host = {k: np.empty(sh, dt) for k, (sh, dt) in self._srlg_shapes(n, 64 * W, want_spaces, tilfa).items()}
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n)
-        sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
-        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
-            self._srlg_chain(graph, plan, mem, run_flags, lfa_flags, symmetric, tilfa, dev, cleanup)
+        shapes = _frr_shapes("lfa", "rlfa", (want_spaces or tilfa) and "spaces", tilfa and "tilfa", n=graph.n, S=64 * plan.mask_words, **_SRLG_WIDTHS)
+        host = _empty(shapes)
+        with self._frr_tables(graph, plan, run_flags, _dev_bytes(shapes), transposed=not symmetric) as (dev, tables, rdist, protect):
+            self._frr_steps(graph, tables, rdist, protect, dev, lfa_flags, srlgs=[mem], tilfa=tilfa)
             self._fetch(host, dev)
-        lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
-        rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"), host.get("sp_via"),
-                        host["rl_node"], host["rl_via"], host["rl_cov"])
-        return (cand, mem, lfa, rl, TilfaResult(*(host[k] for k in self._TI_NAMES))) if tilfa else (cand, mem, lfa, rl)
+        res = (plan.cand, mem, _lfa_result(host), _rlfa_result(host))
+        return res + (TilfaResult(*(host[k] for k in TILFA_FIELDS)),) if tilfa else res
 
     def tilfa_srlg(self, graph: SpfGraph, root: int, grp_ptr, grp, run_flags: int = 0, *, lfa_flags: int = 0, symmetric: bool = False):
         """tilfa() against shared-risk link groups: rlfa_srlg() with everything kept on the device, then tilfa_device() on the safe
@@ -1407,14 +1447,11 @@ class SpfContext:
         P-space plus one forced adjacency into the Q-space, from the tables of a run_device(), `rdist_ptr` and the space tables
         rlfa_device() wrote for the same `protect` and lfa_flags (both required).  `graph` is the FORWARD graph: its links are
         scanned.  All `*_ptr` are device pointers, the slot arrays are strided by 64 * mask_words; alt_flags_in_ptr may be 0."""
-        arr, keep = self._protect_array(protect, "tilfa_device")
-        out = L.HspfTilfaOut(ti_kind_ptr or None, ti_p_ptr or None, ti_q_ptr or None, ti_via_ptr or None, ti_link_ptr or None, ti_metric_ptr or None,
-                             ti_counts_ptr or None, td_kind_ptr or None, td_coverage_ptr or None)
-        rc = self.lib.hspf_tilfa_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                        rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None,
-                                        space_via_ptr or None, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_tilfa_device", rc)
+        out = self._out(L.HspfTilfaOut, ti_kind=ti_kind_ptr, ti_p=ti_p_ptr, ti_q=ti_q_ptr, ti_via=ti_via_ptr, ti_link=ti_link_ptr,
+                        ti_metric=ti_metric_ptr, ti_counts=ti_counts_ptr, td_kind=td_kind_ptr, td_coverage=td_coverage_ptr)
+        self._frr_call("tilfa_device", (graph.n, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None, space_via_ptr or None, ctypes.byref(out)),
+                       graph=graph, rdist_ptr=rdist_ptr or 0)
 
     def tilfa_pc_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, rdist_ptr: int,
                         protect, *, space_flags_ptr: int, space_via_ptr: int, pc_dist_ptr: int, n_pc_rows: int, pc_row, max_walk: int = 256,
@@ -1425,17 +1462,15 @@ class SpfContext:
         rows `pc_dist_ptr` [n_pc_rows, n] of a run_failures_device() on `graph`, pc_row [len(protect), 64 * mask_words] (host) naming
         the row of each slot's FAIL_ROOT_LINK scenario (NO_ROOT: none).  The other inputs are tilfa_device()'s; run_flags are the
         failure run's.  All `*_ptr` are device pointers."""
-        arr, keep = self._protect_array(protect, "tilfa_pc_device")
         rows = None if pc_row is None else np.ascontiguousarray(pc_row, dtype=np.uint32)
         if rows is not None and rows.size != len(protect) * 64 * mask_words:
             raise ValueError("tilfa_pc_device: pc_row holds 64 * mask_words entries per protected root")
-        out = L.HspfTilfaPcOut(tp_kind_ptr or None, tp_p_ptr or None, tp_via_ptr or None, tp_q_ptr or None, tp_n_adj_ptr or None, tp_hop_pos_ptr or None,
-                               tp_hop_head_ptr or None, tp_metric_ptr or None, tp_flags_ptr or None, tp_coverage_ptr or None)
-        rc = self.lib.hspf_tilfa_pc_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                           rdist_ptr or None, arr, len(protect), lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None,
-                                           space_via_ptr or None, pc_dist_ptr or None, n_pc_rows, None if rows is None else _u32(rows), run_flags, max_walk, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_tilfa_pc_device", rc)
+        out = self._out(L.HspfTilfaPcOut, tp_kind=tp_kind_ptr, tp_p=tp_p_ptr, tp_via=tp_via_ptr, tp_q=tp_q_ptr, tp_n_adj=tp_n_adj_ptr,
+                        tp_hop_pos=tp_hop_pos_ptr, tp_hop_head=tp_hop_head_ptr, tp_metric=tp_metric_ptr, tp_flags=tp_flags_ptr,
+                        tp_coverage=tp_coverage_ptr)
+        self._frr_call("tilfa_pc_device", (graph.n, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, alt_flags_in_ptr or None, space_flags_ptr or None, space_via_ptr or None, pc_dist_ptr or None, n_pc_rows,
+                        None if rows is None else _u32(rows), run_flags, max_walk, ctypes.byref(out)), graph=graph, rdist_ptr=rdist_ptr or 0)
 
     def routes_backup_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                              pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
@@ -1484,12 +1519,10 @@ class SpfContext:
                                         eb_slot_ptr=eb_slot_ptr, eb_metric_ptr=eb_metric_ptr, eb_flags_ptr=eb_flags_ptr, eb_coverage_ptr=eb_coverage_ptr,
                                         tilfa=tilfa, flags=flags, lfa_flags=lfa_flags, pfx_origin=pfx_origin)
 
-    def _routes_backup_ecmp(self, srlgs, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
-                            pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, eb_ptr_ptr: int, cap_entries: int = 0, eb_primary_ptr: int = 0,
-                            eb_kind_ptr: int = 0, eb_slot_ptr: int = 0, eb_metric_ptr: int = 0, eb_flags_ptr: int = 0, eb_coverage_ptr: int = 0,
-                            tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> int:
-        """The body of routes_backup_ecmp_device() (srlgs None) and routes_backup_ecmp_srlg_device()."""
-        name = "routes_backup_ecmp_device" if srlgs is None else "routes_backup_ecmp_srlg_device"
+    @staticmethod
+    def _pfx_args(name: str, pfx_ptr, pfx_vertex, pfx_metric, flags: int, pfx_origin=None):
+        """The hspf_prefix_table of a per-prefix backup call from host numpy, and the arrays it points into (to be kept alive for
+        the call)."""
         src = (pfx_ptr, pfx_vertex, pfx_metric)
         pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
         pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
@@ -1497,29 +1530,40 @@ class SpfContext:
         if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
             raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
         org = None if pfx_origin is None else np.ascontiguousarray(pfx_origin, np.uint32)
-        arr, keep = self._protect_array(protect, name)
-        sarr, skeep = (None, None) if srlgs is None else self._srlg_array(srlgs, protect, name)
         t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags,
                               None if org is None else _u32(org), None, None, None)
+        return t, (pfx_ptr, pfx_vertex, pfx_metric, org)
+
+    @staticmethod
+    def _tilfa_in(tilfa):
+        """`tilfa` of the per-prefix backup calls — None, (ti_kind_ptr, ti_via_ptr, ti_metric_ptr), or those three and (ti_p_ptr,
+        ti_link_ptr) for the SRLG calls — as the hspf_tilfa_out the library reads."""
+        return None if tilfa is None else SpfContext._out(L.HspfTilfaOut, **dict(zip(_TILFA_IN, tilfa)))
+
+    def _routes_backup_ecmp(self, srlgs, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
+                            pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, eb_ptr_ptr: int, cap_entries: int = 0, eb_primary_ptr: int = 0,
+                            eb_kind_ptr: int = 0, eb_slot_ptr: int = 0, eb_metric_ptr: int = 0, eb_flags_ptr: int = 0, eb_coverage_ptr: int = 0,
+                            tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> int:
+        """The body of routes_backup_ecmp_device() (srlgs None) and routes_backup_ecmp_srlg_device()."""
+        name = "routes_backup_ecmp_device" if srlgs is None else "routes_backup_ecmp_srlg_device"
+        t, keep = self._pfx_args(name, pfx_ptr, pfx_vertex, pfx_metric, flags, pfx_origin)
         r = L.HspfRoutes(*(x or None for x in routes))
-        ti = None
-        if tilfa is not None and srlgs is None:
-            ti = L.HspfTilfaOut(tilfa[0] or None, None, None, tilfa[1] or None, None, tilfa[2] or None, None, None, None)
-        elif tilfa is not None:
-            ti = L.HspfTilfaOut(tilfa[0] or None, tilfa[3] or None, None, tilfa[1] or None, tilfa[4] or None, tilfa[2] or None, None, None, None)
-        out = L.HspfBackupEcmpOut(eb_ptr_ptr or None, eb_primary_ptr or None, eb_kind_ptr or None, eb_slot_ptr or None, eb_metric_ptr or None,
-                                  eb_flags_ptr or None, eb_coverage_ptr or None)
+        ti = self._tilfa_in(tilfa)
+        out = self._out(L.HspfBackupEcmpOut, eb_ptr=eb_ptr_ptr, eb_primary=eb_primary_ptr, eb_kind=eb_kind_ptr, eb_slot=eb_slot_ptr,
+                        eb_metric=eb_metric_ptr, eb_flags=eb_flags_ptr, eb_coverage=eb_coverage_ptr)
         total = ctypes.c_uint64()
-        head = (self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None, arr)
-        tail = (len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r), None if ti is None else ctypes.byref(ti), cap_entries, ctypes.byref(out),
-                ctypes.byref(total))
-        if srlgs is None:
-            rc = self.lib.hspf_routes_backup_ecmp_device(*head, *tail)
-        else:
-            rc = self.lib.hspf_routes_backup_ecmp_srlg_device(*head, sarr, *tail)
-        del keep, skeep
-        self._check_rc("hspf_" + name, rc)
+        self._frr_call(name, (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, ctypes.byref(t), ctypes.byref(r), _ref(ti), cap_entries, ctypes.byref(out), ctypes.byref(total)), srlgs=srlgs)
+        del keep
         return int(total.value)
+
+    @staticmethod
+    def _backup_kw(dev: dict, backup, tilfa: bool, lfa_flags: int, srlg: bool) -> dict:
+        """What every per-prefix backup call of a chain takes from the device: the routes routes_device() wrote, the per-slot repairs
+        of tilfa_device() with `tilfa` (five pointers for the SRLG calls), and the table as the resident one."""
+        return dict(routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
+                    tilfa=tuple(dev[k] for k in (_TILFA_IN if srlg else _TILFA_IN[:3])) if tilfa else None, flags=backup[3] | PFX_RESIDENT,
+                    lfa_flags=lfa_flags)
 
     def _backup_ecmp_tail(self, n: int, R: int, W: int, dev: dict, protect, backup, tilfa: bool, lfa_flags: int, srlgs=None) -> BackupEcmpResult:
         """backup_routes(ecmp=True) behind routes_backup_device(), while the tables, the routes and the repairs are on the device: the
@@ -1528,9 +1572,7 @@ class SpfContext:
         NP = len(backup[0]) - 1
         ptr = np.empty(NP + 1, np.uint32)
         cov = np.zeros((1, BK_ECMP_COVERAGE_WORDS if srlgs is None else BK_ECMP_SRLG_COVERAGE_WORDS), np.uint32)
-        ti_names = ("ti_kind", "ti_via", "ti_metric") + (() if srlgs is None else ("ti_p", "ti_link"))
-        kw = dict(routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
-                  tilfa=tuple(dev[k] for k in ti_names) if tilfa else None, flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags)
+        kw = self._backup_kw(dev, backup, tilfa, lfa_flags, srlgs is not None)
         tables = (srlgs, n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, backup[0], backup[1], backup[2])
         with self._dev_buffers(dict(ptr=ptr.nbytes)) as pd:
             total = self._routes_backup_ecmp(*tables, eb_ptr_ptr=pd["ptr"], **kw)
@@ -1548,34 +1590,17 @@ class SpfContext:
     def _routes_backup(self, lans, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                        pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, bk_kind_ptr: int, bk_primary_ptr: int, bk_slot_ptr: int,
                        bk_metric_ptr: int, bk_flags_ptr: int, bk_coverage_ptr: int, bk_cand_mask_ptr: int = 0, bk_node_mask_ptr: int = 0,
-                       tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None) -> None:
-        """The body of routes_backup_device() (lans None) and routes_backup_lan_device()."""
-        name = "routes_backup_device" if lans is None else "routes_backup_lan_device"
-        src = (pfx_ptr, pfx_vertex, pfx_metric)
-        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
-        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
-        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
-        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
-            raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
-        org = None if pfx_origin is None else np.ascontiguousarray(pfx_origin, np.uint32)
-        arr, keep = self._protect_array(protect, name)
-        larr, lkeep = (None, None) if lans is None else self._lan_array(lans, protect, name)
-        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags,
-                              None if org is None else _u32(org), None, None, None)
+                       tilfa: Optional[tuple] = None, flags: int = 0, lfa_flags: int = 0, pfx_origin=None, srlgs=None) -> None:
+        """The body of routes_backup_device() (lans and srlgs None), routes_backup_lan_device() and routes_backup_srlg_device()."""
+        name = "routes_backup_lan_device" if lans is not None else "routes_backup_device" if srlgs is None else "routes_backup_srlg_device"
+        t, keep = self._pfx_args(name, pfx_ptr, pfx_vertex, pfx_metric, flags, pfx_origin)
         r = L.HspfRoutes(*(x or None for x in routes))
-        ti = None
-        if tilfa is not None:
-            ti = L.HspfTilfaOut(tilfa[0] or None, None, None, tilfa[1] or None, None, tilfa[2] or None, None, None, None)
-        out = L.HspfBackupOut(bk_kind_ptr or None, bk_primary_ptr or None, bk_slot_ptr or None, bk_metric_ptr or None, bk_flags_ptr or None,
-                              bk_cand_mask_ptr or None, bk_node_mask_ptr or None, bk_coverage_ptr or None)
-        head = (self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None, arr)
-        tail = (len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r), None if ti is None else ctypes.byref(ti), ctypes.byref(out))
-        if lans is None:
-            rc = self.lib.hspf_routes_backup_device(*head, *tail)
-        else:
-            rc = self.lib.hspf_routes_backup_lan_device(*head, larr, *tail)
-        del keep, lkeep
-        self._check_rc("hspf_" + name, rc)
+        ti = self._tilfa_in(tilfa)
+        out = self._out(L.HspfBackupOut, bk_kind=bk_kind_ptr, bk_primary=bk_primary_ptr, bk_slot=bk_slot_ptr, bk_metric=bk_metric_ptr,
+                        bk_flags=bk_flags_ptr, bk_cand_mask=bk_cand_mask_ptr, bk_node_mask=bk_node_mask_ptr, bk_coverage=bk_coverage_ptr)
+        self._frr_call(name, (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, ctypes.byref(t), ctypes.byref(r), _ref(ti), ctypes.byref(out)), lans=lans, srlgs=srlgs)
+        del keep
 
     def routes_backup_lan_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, lans,
                                  pfx_ptr, pfx_vertex, pfx_metric, **kw) -> None:
@@ -1596,67 +1621,41 @@ class SpfContext:
         caller's word that `tilfa` comes from rlfa_srlg_device()'s tables), and a pair whose forced link is a member is refused
         (BK_SRLG_PAIR_REFUSED).  bk_coverage_ptr: [P, BK_SRLG_COVERAGE_WORDS] u32; every other argument as for
         routes_backup_device()."""
-        name = "routes_backup_srlg_device"
-        src = (pfx_ptr, pfx_vertex, pfx_metric)
-        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
-        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
-        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
-        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
-            raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
-        arr, keep = self._protect_array(protect, name)
-        sarr, skeep = self._srlg_array(srlgs, protect, name)
-        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags, None, None, None, None)
-        r = L.HspfRoutes(*(x or None for x in routes))
-        ti = None
-        if tilfa is not None:
-            ti = L.HspfTilfaOut(tilfa[0] or None, tilfa[3] or None, None, tilfa[1] or None, tilfa[4] or None, tilfa[2] or None, None, None, None)
-        out = L.HspfBackupOut(bk_kind_ptr or None, bk_primary_ptr or None, bk_slot_ptr or None, bk_metric_ptr or None, bk_flags_ptr or None,
-                              bk_cand_mask_ptr or None, bk_node_mask_ptr or None, bk_coverage_ptr or None)
-        rc = self.lib.hspf_routes_backup_srlg_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
-                                                     mask_ptr or None, arr, sarr, len(protect), lfa_flags, ctypes.byref(t), ctypes.byref(r),
-                                                     None if ti is None else ctypes.byref(ti), ctypes.byref(out))
-        del keep, skeep
-        self._check_rc("hspf_" + name, rc)
+        self._routes_backup(None, n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr, protect, pfx_ptr, pfx_vertex, pfx_metric,
+                            routes=routes, bk_kind_ptr=bk_kind_ptr, bk_primary_ptr=bk_primary_ptr, bk_slot_ptr=bk_slot_ptr, bk_metric_ptr=bk_metric_ptr,
+                            bk_flags_ptr=bk_flags_ptr, bk_coverage_ptr=bk_coverage_ptr, bk_cand_mask_ptr=bk_cand_mask_ptr,
+                            bk_node_mask_ptr=bk_node_mask_ptr, tilfa=tilfa, flags=flags, lfa_flags=lfa_flags, srlgs=list(srlgs))
+
+    def _backup_step(self, tables, protect, dev: dict, backup, tilfa: bool, lfa_flags: int, *, lans=None, srlgs=None) -> None:
+        """The routes of a chain's root and their backups, left on the device in the buffers of _frr_shapes("backup"): routes_device()
+        on the root's own row, then routes_backup_device() — or, with `lans` / `srlgs`, its LAN / SRLG variant — with the per-slot
+        repairs of tilfa_device() when `tilfa` says they are in `dev`."""
+        n, _, W, dist, flags, mask = tables
+        self.routes_device(n, 1, W, dist, flags, mask, backup[0], backup[1], backup[2], flags=backup[3], best_metric_ptr=dev["best_metric"],
+                           best_entry_ptr=dev["best_entry"], nexthop_mask_ptr=dev["nexthop_mask"])
+        self._routes_backup(lans, *tables, protect, backup[0], backup[1], backup[2], srlgs=srlgs,
+                            **self._backup_kw(dev, backup, tilfa, lfa_flags, srlgs is not None), **{k + "_ptr": dev[k] for k in BACKUP_FIELDS[3:]})
 
     def _backup_srlg(self, graph: SpfGraph, root: int, tab, grp_ptr, grp, run_flags: int, lfa_flags: int, symmetric: bool, remote: bool,
                      srlg_repairs: bool, ecmp: bool = False) -> BackupRoutes:
-        """backup_routes(srlg=...): on a run that also holds the member endpoints' rows, _srlg_chain() with `remote` (only the
-        per-slot repairs come to the host), then routes_device() and routes_backup_srlg_device(); with `ecmp`, _backup_ecmp_tail()
-        with the members on the same rows."""
+        """backup_routes(srlg=...): on a run that also holds the member endpoints' rows, the SRLG calls of _frr_steps() with `remote`
+        (only the per-slot repairs come to the host), then routes_device() and routes_backup_srlg_device(); with `ecmp`,
+        _backup_ecmp_tail() with the members on the same rows."""
         plan, mem = self._srlg_plan(graph, root, grp_ptr, grp)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n, NP = len(roots), graph.n, len(tab[0]) - 1
-        shapes = dict(best_metric=((1, NP), np.uint32), best_entry=((1, NP), np.uint32), nexthop_mask=((1, NP, W), np.uint64),
-                      bk_kind=((1, NP), np.uint8), bk_primary=((1, NP), np.uint32), bk_slot=((1, NP), np.uint32), bk_metric=((1, NP), np.uint32),
-                      bk_flags=((1, NP), np.uint8), bk_cand_mask=((1, NP, W), np.uint64), bk_node_mask=((1, NP, W), np.uint64),
-                      bk_coverage=((1, BK_SRLG_COVERAGE_WORDS), np.uint32))
-        bk_names = tuple(shapes)
-        chain = self._srlg_shapes(n, 64 * W, True, True) if remote else {}
-        shapes.update({k: chain[k] for k in self._TI_NAMES if remote})
-        host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric or not remote else 4 * R * n)
-        sizes.update({k: max(int(np.prod(sh)) * np.dtype(dt).itemsize, 8) for k, (sh, dt) in chain.items()})      # (what stays on the device)
-        sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
-        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
-            tables = (dev["dist"], dev["flags"], dev["mask"])
+        n, R, W = graph.n, len(plan.roots), plan.mask_words
+        chain = _frr_shapes("lfa", "rlfa", "spaces", "tilfa", n=n, S=64 * W, **_SRLG_WIDTHS) if remote else {}      # (what stays on the device)
+        shapes = dict(_frr_shapes("backup", NP=len(tab[0]) - 1, W=W, bk_cov=BK_SRLG_COVERAGE_WORDS), **{k: chain[k] for k in TILFA_FIELDS if remote})
+        host = _empty(shapes)
+        lfa_flags_bk = lfa_flags | (LFA_SRLG_SAFE_REPAIRS if srlg_repairs else 0)
+        with self._frr_tables(graph, plan, run_flags, {**_dev_bytes(chain), **_dev_bytes(shapes)}, transposed=remote and not symmetric) as (
+                dev, tables, rdist, protect):
             if remote:
-                protect = self._srlg_chain(graph, plan, mem, run_flags, lfa_flags, symmetric, True, dev, cleanup)
-            else:
-                self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-                protect = [(0, cand, nbr_row)]
-            self.routes_device(n, 1, W, *tables, tab[0], tab[1], tab[2], flags=tab[3], best_metric_ptr=dev["best_metric"],
-                               best_entry_ptr=dev["best_entry"], nexthop_mask_ptr=dev["nexthop_mask"])
-            self.routes_backup_srlg_device(n, R, W, *tables, protect, [mem], tab[0], tab[1], tab[2],
-                                           routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
-                                           tilfa=tuple(dev[k] for k in ("ti_kind", "ti_via", "ti_metric", "ti_p", "ti_link")) if remote else None,
-                                           flags=tab[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_SRLG_SAFE_REPAIRS if srlg_repairs else 0),
-                                           **{k + "_ptr": dev[k] for k in bk_names[3:]})
-            eb = None
-            if ecmp:
-                eb = self._backup_ecmp_tail(n, R, W, dev, protect, tab, remote, lfa_flags | (LFA_SRLG_SAFE_REPAIRS if srlg_repairs else 0), srlgs=[mem])
+                self._frr_steps(graph, tables, rdist, protect, dev, lfa_flags, srlgs=[mem], tilfa=True)
+            self._backup_step(tables, protect, dev, tab, remote, lfa_flags_bk, srlgs=[mem])
+            eb = self._backup_ecmp_tail(n, R, W, dev, protect, tab, remote, lfa_flags_bk, srlgs=[mem]) if ecmp else None
             self._fetch(host, dev)
-        return BackupRoutes(cand, *(host[k] for k in bk_names), tilfa=TilfaResult(*(host[k] for k in self._TI_NAMES)) if remote else None, srlg=mem,
-                            ecmp=eb)
+        return BackupRoutes(plan.cand, *(host[k] for k in BACKUP_FIELDS), tilfa=TilfaResult(*(host[k] for k in TILFA_FIELDS)) if remote else None,
+                            srlg=mem, ecmp=eb)
 
     def routes_backup_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect,
                                   pfx_ptr, pfx_vertex, pfx_metric, *, routes: tuple, ydist_ptr: int, y_roots, bn_kind_ptr: int, bn_primary_ptr: int,
@@ -1669,60 +1668,51 @@ class SpfContext:
         (host array; NO_ROOT entries are skipped); rn_sel = the four pointers of rlfa_node_select_device() with max_pq, tn_sel = the
         six of tilfa_node_select_device() with max_pairs (at least one of the two); bk_in = (bk_kind_ptr, bk_flags_ptr) of
         routes_backup_device(), or None.  The two set pointers may be 0."""
-        name = "routes_backup_node_device"
-        src = (pfx_ptr, pfx_vertex, pfx_metric)
-        pfx_ptr = np.ascontiguousarray(pfx_ptr, np.uint32)
-        pfx_vertex = np.ascontiguousarray(pfx_vertex, np.uint32)
-        pfx_metric = np.ascontiguousarray(pfx_metric, np.uint32)
-        if flags & PFX_RESIDENT and any(a is not b for a, b in zip(src, (pfx_ptr, pfx_vertex, pfx_metric))):
-            raise ValueError(name + ": PFX_RESIDENT needs the caller's own contiguous uint32 arrays (a conversion made a copy)")
-        arr, keep = self._protect_array(protect, name)
+        t, keep = self._pfx_args("routes_backup_node_device", pfx_ptr, pfx_vertex, pfx_metric, flags)
         yr = np.ascontiguousarray(y_roots, np.uint32)
-        t = L.HspfPrefixTable(len(pfx_ptr) - 1, len(pfx_vertex), _u32(pfx_ptr), _u32(pfx_vertex), _u32(pfx_metric), flags, None, None, None, None)
         r = L.HspfRoutes(*(x or None for x in routes))
         rn = None if rn_sel is None else L.HspfRlfaNodeSel(*(x or None for x in rn_sel))
         tn = None if tn_sel is None else L.HspfTilfaNodeSel(*(x or None for x in tn_sel))
-        bk = None if bk_in is None else L.HspfBackupOut(bk_in[0] or None, None, None, None, bk_in[1] or None, None, None, None)
-        out = L.HspfBackupNodeOut(bn_kind_ptr or None, bn_primary_ptr or None, bn_p_ptr or None, bn_q_ptr or None, bn_link_ptr or None,
-                                  bn_via_ptr or None, bn_metric_ptr or None, bn_set_pq_ptr or None, bn_set_pair_ptr or None, bn_coverage_ptr or None)
-        ref = lambda x: None if x is None else ctypes.byref(x)      # noqa: E731
-        rc = self.lib.hspf_routes_backup_node_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
-                                                     mask_ptr or None, arr, len(protect), ctypes.byref(t), ctypes.byref(r), ydist_ptr or None,
-                                                     _u32(yr) if len(yr) else None, len(yr), ref(rn), max_pq, ref(tn), max_pairs, ref(bk),
-                                                     ctypes.byref(out))
+        bk = None if bk_in is None else self._out(L.HspfBackupOut, bk_kind=bk_in[0], bk_flags=bk_in[1])
+        out = self._out(L.HspfBackupNodeOut, bn_kind=bn_kind_ptr, bn_primary=bn_primary_ptr, bn_p=bn_p_ptr, bn_q=bn_q_ptr, bn_link=bn_link_ptr,
+                        bn_via=bn_via_ptr, bn_metric=bn_metric_ptr, bn_set_pq=bn_set_pq_ptr, bn_set_pair=bn_set_pair_ptr, bn_coverage=bn_coverage_ptr)
+        self._frr_call("routes_backup_node_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (ctypes.byref(t), ctypes.byref(r), ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), _ref(rn), max_pq, _ref(tn),
+                        max_pairs, _ref(bk), ctypes.byref(out)))
         del keep
-        self._check_rc("hspf_" + name, rc)
 
-    def _backup_node_tail(self, graph: SpfGraph, run_flags: int, lfa_flags: int, backup, dev, protect, R: int, W: int, max_pq: int, max_pairs: int):
+    @contextlib.contextmanager
+    def _y_run(self, graph: SpfGraph, listed, run_flags: int):
+        """The SPTs of the nodes a select call listed: yields (y_roots, ydist_ptr) — the ascending union of `listed` without NO_ROOT
+        and the `dist` of ONE run_device() over it, freed on exit.  Where no list holds a node, one NO_ROOT padding row keeps the
+        arguments of the call that follows valid, and nothing is run."""
+        listed = np.asarray(listed).ravel()
+        y_roots = np.unique(listed[listed != NO_ROOT]).astype(np.uint32)
+        if len(y_roots) == 0:
+            y_roots = np.array([NO_ROOT], np.uint32)
+        with self._dev_buffers(dict(ydist=4 * len(y_roots) * graph.n)) as ydev:
+            if y_roots[0] != NO_ROOT:
+                self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
+            yield y_roots, ydev["ydist"]
+
+    def _backup_node_tail(self, graph: SpfGraph, run_flags: int, lfa_flags: int, backup, dev: dict, tables, protect, max_pq: int, max_pairs: int):
         """backup_routes(node_protect=True) while the tables, the space_flags, the routes and bk_* are on the device: the two select
         calls, ONE run_device() over the ascending union of the listed PQ nodes and q's, routes_backup_node_device().  Returns the
         bn_* arrays on the host."""
-        n, S, NP = graph.n, 64 * W, len(backup[0]) - 1
-        tables = (dev["dist"], dev["flags"], dev["mask"])
-        rn = {k: np.empty((1, S, max_pq), np.uint32) for k in ("nq_node", "nq_via", "nq_metric")}
-        rn["nq_count"] = np.empty((1, S), np.uint32)
-        tn = {k: np.empty((1, S, max_pairs), np.uint32) for k in ("tq_q", "tq_p", "tq_link", "tq_via", "tq_metric")}
-        tn["tq_count"] = np.empty((1, S), np.uint32)
-        bn = dict(bn_kind=np.empty((1, NP), np.uint8),
-                  **{k: np.empty((1, NP), np.uint32) for k in ("bn_primary", "bn_p", "bn_q", "bn_link", "bn_via", "bn_metric", "bn_set_pq", "bn_set_pair")},
-                  bn_coverage=np.empty((1, BN_COVERAGE_WORDS), np.uint32))
-        with self._dev_buffers({k: max(a.nbytes, 8) for k, a in dict(rn, **tn, **bn).items()}) as ndev:
-            self.rlfa_node_select_device(n, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pq=max_pq, lfa_flags=lfa_flags,
+        S = 64 * tables[2]
+        shapes = [_frr_shapes("rn_sel", S=S, M=max_pq), _frr_shapes("tn_sel", S=S, M=max_pairs), _frr_shapes("bn", NP=len(backup[0]) - 1)]
+        rn, tn, bn = (_empty(sh) for sh in shapes)
+        with self._dev_buffers(_dev_bytes({**shapes[0], **shapes[1], **shapes[2]})) as ndev:
+            self.rlfa_node_select_device(*tables, protect, space_flags_ptr=dev["sp_flags"], max_pq=max_pq, lfa_flags=lfa_flags,
                                          **{k + "_ptr": ndev[k] for k in rn})
-            self.tilfa_node_select_device(graph, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pairs=max_pairs, lfa_flags=lfa_flags,
+            self.tilfa_node_select_device(graph, *tables[1:], protect, space_flags_ptr=dev["sp_flags"], max_pairs=max_pairs, lfa_flags=lfa_flags,
                                           **{k + "_ptr": ndev[k] for k in tn})
             self._fetch(dict(nq_node=rn["nq_node"], tq_q=tn["tq_q"]), ndev)
-            listed = np.concatenate([rn["nq_node"].ravel(), tn["tq_q"].ravel()])
-            y_roots = np.unique(listed[listed != NO_ROOT]).astype(np.uint32)
-            if len(y_roots) == 0:                       # no list holds a node: one padding row keeps the call's arguments valid
-                y_roots = np.array([NO_ROOT], np.uint32)
-            with self._dev_buffers(dict(ydist=4 * len(y_roots) * n)) as ydev:
-                if y_roots[0] != NO_ROOT:
-                    self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
-                self.routes_backup_node_device(n, R, W, *tables, protect, backup[0], backup[1], backup[2],
-                                               routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]), ydist_ptr=ydev["ydist"],
-                                               y_roots=y_roots, rn_sel=tuple(ndev[k] for k in rn), max_pq=max_pq, tn_sel=tuple(ndev[k] for k in tn),
-                                               max_pairs=max_pairs, bk_in=(dev["bk_kind"], dev["bk_flags"]), flags=backup[3] | PFX_RESIDENT,
+            with self._y_run(graph, np.concatenate([rn["nq_node"].ravel(), tn["tq_q"].ravel()]), run_flags) as (y_roots, ydist):
+                self.routes_backup_node_device(*tables, protect, backup[0], backup[1], backup[2],
+                                               routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]), ydist_ptr=ydist, y_roots=y_roots,
+                                               rn_sel=tuple(ndev[k] for k in rn), max_pq=max_pq, tn_sel=tuple(ndev[k] for k in tn), max_pairs=max_pairs,
+                                               bk_in=(dev["bk_kind"], dev["bk_flags"]), flags=backup[3] | PFX_RESIDENT,
                                                **{k + "_ptr": ndev[k] for k in bn})
                 self._fetch(bn, ndev)
         return bn
@@ -1805,99 +1795,50 @@ class SpfContext:
         if lan_spaces and (not lan_protect or symmetric):
             raise ValueError("the LAN-safe remote calls need lan_protect and the transposed run (symmetric=False)")
         plan = self._frr_plan(graph, root, lan_protect)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n, S = len(roots), graph.n, 64 * W
-        shapes = dict(slot=((1, n), np.uint32), metric=((1, n), np.uint32), aflags=((1, n), np.uint8),
-                      cov=((1, LFA_LAN_COVERAGE_WORDS if lan_protect else LFA_COVERAGE_WORDS), np.uint32),
-                      pq_node=((1, S), np.uint32), pq_via=((1, S), np.uint32), pq_metric=((1, S), np.uint32),
-                      pq_counts=((1, S, RLFA_LAN_COUNT_WORDS if lan_spaces else RLFA_COUNT_WORDS), np.uint32), rl_node=((1, n), np.uint32),
-                      rl_via=((1, n), np.uint32), rl_cov=((1, RLFA_LAN_COVERAGE_WORDS if lan_spaces else RLFA_COVERAGE_WORDS), np.uint32))
-        if want_spaces:
-            shapes.update(sp_flags=((1, S, n), np.uint8), sp_via=((1, S, n), np.uint32))
-        ti_names = ("ti_kind", "ti_p", "ti_q", "ti_via", "ti_link", "ti_metric", "ti_counts", "td_kind", "td_coverage")
-        if tilfa:
-            shapes.update(ti_kind=((1, S), np.uint8), ti_p=((1, S), np.uint32), ti_q=((1, S), np.uint32), ti_via=((1, S), np.uint32),
-                          ti_link=((1, S), np.uint32), ti_metric=((1, S), np.uint32), ti_counts=((1, S, TILFA_COUNT_WORDS), np.uint32),
-                          td_kind=((1, n), np.uint8), td_coverage=((1, TILFA_COVERAGE_WORDS), np.uint32))
-        bk_names = ("best_metric", "best_entry", "nexthop_mask", "bk_kind", "bk_primary", "bk_slot", "bk_metric", "bk_flags", "bk_cand_mask",
-                    "bk_node_mask", "bk_coverage")
-        if backup is not None:
-            NP = len(backup[0]) - 1
-            shapes.update(best_metric=((1, NP), np.uint32), best_entry=((1, NP), np.uint32), nexthop_mask=((1, NP, W), np.uint64),
-                          bk_kind=((1, NP), np.uint8), bk_primary=((1, NP), np.uint32), bk_slot=((1, NP), np.uint32), bk_metric=((1, NP), np.uint32),
-                          bk_flags=((1, NP), np.uint8), bk_cand_mask=((1, NP, W), np.uint64), bk_node_mask=((1, NP, W), np.uint64),
-                          bk_coverage=((1, BK_LAN_COVERAGE_WORDS if lan_protect else BK_COVERAGE_WORDS), np.uint32))
+        cand, W = plan.cand, plan.mask_words
+        n, S = graph.n, 64 * W
+        shapes = _frr_shapes("lfa", "rlfa", want_spaces and "spaces", tilfa and "tilfa", backup is not None and "backup", pc is not None and "tilfa_pc",
+                             n=n, S=S, W=W, NP=len(backup[0]) - 1 if backup is not None else 0,
+                             lfa_cov=LFA_LAN_COVERAGE_WORDS if lan_protect else LFA_COVERAGE_WORDS,
+                             pq_counts=RLFA_LAN_COUNT_WORDS if lan_spaces else RLFA_COUNT_WORDS,
+                             rl_cov=RLFA_LAN_COVERAGE_WORDS if lan_spaces else RLFA_COVERAGE_WORDS,
+                             bk_cov=BK_LAN_COVERAGE_WORDS if lan_protect else BK_COVERAGE_WORDS)
+        host = _empty(shapes)
+        remote = backup is None or tilfa
+        if not remote:                                  # backup_routes(remote=False): nothing writes the remote arrays, nothing reads them
+            for k in _frr_shapes("rlfa"):
+                del host[k]
         pc_slots = np.flatnonzero(cand.nbr != NO_ROOT).astype(np.uint32) if pc is not None else None
-        if pc is not None:
-            A = TIPC_MAX_ADJ
-            shapes.update(tp_kind=((1, n), np.uint8), tp_p=((1, n), np.uint32), tp_via=((1, n), np.uint32), tp_q=((1, n), np.uint32),
-                          tp_n_adj=((1, n), np.uint8), tp_hop_pos=((1, n, A), np.uint32), tp_hop_head=((1, n, A), np.uint32),
-                          tp_metric=((1, n), np.uint32), tp_flags=((1, n), np.uint8), tp_coverage=((1, TIPC_COVERAGE_WORDS), np.uint32))
-        host = {k: np.empty(sh, dt) for k, (sh, dt) in shapes.items()}
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n,
-                     pc_dist=4 * len(pc_slots) * n if pc is not None else 0)
-        sizes.update({k: max(a.nbytes, 8) for k, a in host.items()})
-        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
-            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-            if not symmetric:
-                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
-                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
-                cleanup.callback(GT.free)
-                self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
-            protect = [(0, cand, nbr_row)]
-            if lan_protect:
-                self.lfa_lan_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, plan.lans, alt_slot_ptr=dev["slot"],
-                                    alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
-            else:
-                self.lfa_device(n, R, W, dev["dist"], dev["flags"], dev["mask"], protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"],
-                                alt_flags_ptr=dev["aflags"], coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
-            if backup is None or tilfa:
-                tabs = (graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect)
-                out = dict(pq_node_ptr=dev["pq_node"], pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"],
-                           rl_node_ptr=dev["rl_node"], rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"],
-                           space_flags_ptr=dev.get("sp_flags", 0), space_via_ptr=dev.get("sp_via", 0), alt_flags_in_ptr=dev["aflags"],
-                           lfa_flags=lfa_flags)
-                if lan_spaces:
-                    self.rlfa_lan_device(*tabs, plan.lans, **out)
-                else:
-                    self.rlfa_device(*tabs, **out)
-            else:                                       # backup_routes(remote=False): nothing wrote the remote arrays, nothing reads them
-                for k in ("pq_node", "pq_via", "pq_metric", "pq_counts", "rl_node", "rl_via", "rl_cov"):
-                    del host[k]
-            if tilfa:
-                self.tilfa_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
-                                  space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
-                                  **{k + "_ptr": dev[k] for k in ti_names})
+        sizes = dict(pc_dist=4 * len(pc_slots) * n if pc is not None else 0, **_dev_bytes(shapes))
+        with self._frr_tables(graph, plan, run_flags, sizes, transposed=not symmetric) as (dev, tables, rdist, protect):
+            self._frr_steps(graph, tables, rdist, protect, dev, lfa_flags, lfa_lans=plan.lans if lan_protect else None,
+                            rlfa_lans=plan.lans if lan_spaces else None, remote=remote, tilfa=tilfa)
             if pc is not None:
                 pc_row = np.full((1, S), NO_ROOT, np.uint32)
                 pc_row[0, pc_slots] = np.arange(len(pc_slots), dtype=np.uint32)
                 if len(pc_slots):
                     fails = np.stack([np.full(len(pc_slots), FAIL_ROOT_LINK, np.uint32), cand.root_link[pc_slots].astype(np.uint32)], axis=1)
                     self.run_failures_device(graph, np.full(len(pc_slots), root, np.uint32), fails, run_flags, dist_ptr=dev["pc_dist"])
-                self.tilfa_pc_device(graph, R, W, dev["dist"], dev["flags"], dev["mask"], dev["dist"] if symmetric else dev["rdist"], protect,
-                                     space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"], pc_dist_ptr=dev["pc_dist"] or dev["dist"],
-                                     n_pc_rows=len(pc_slots), pc_row=pc_row, max_walk=pc, run_flags=run_flags, alt_flags_in_ptr=dev["aflags"],
-                                     lfa_flags=lfa_flags, **{k + "_ptr": dev[k] for k in TILFA_PC_FIELDS})
+                self.tilfa_pc_device(graph, *tables[1:], rdist, protect, space_flags_ptr=dev["sp_flags"], space_via_ptr=dev["sp_via"],
+                                     pc_dist_ptr=dev["pc_dist"] or dev["dist"], n_pc_rows=len(pc_slots), pc_row=pc_row, max_walk=pc,
+                                     run_flags=run_flags, alt_flags_in_ptr=dev["aflags"], lfa_flags=lfa_flags,
+                                     **{k + "_ptr": dev[k] for k in TILFA_PC_FIELDS})
+            bn, eb = {}, None
             if backup is not None:
-                self.routes_device(n, 1, W, dev["dist"], dev["flags"], dev["mask"], backup[0], backup[1], backup[2], flags=backup[3],
-                                   best_metric_ptr=dev["best_metric"], best_entry_ptr=dev["best_entry"], nexthop_mask_ptr=dev["nexthop_mask"])
-                self._routes_backup(plan.lans if lan_protect else None, n, R, W, dev["dist"], dev["flags"], dev["mask"], protect,
-                                    backup[0], backup[1], backup[2], routes=(dev["best_metric"], dev["best_entry"], dev["nexthop_mask"]),
-                                    tilfa=(dev["ti_kind"], dev["ti_via"], dev["ti_metric"]) if tilfa else None,
-                                    flags=backup[3] | PFX_RESIDENT, lfa_flags=lfa_flags | (LFA_LAN_SAFE_REPAIRS if lan_spaces else 0),
-                                    **{k + "_ptr": dev[k] for k in bk_names[3:]})
-            bn = self._backup_node_tail(graph, run_flags, lfa_flags, backup, dev, protect, R, W, *node) if backup is not None and node else {}
-            eb = self._backup_ecmp_tail(n, R, W, dev, protect, backup, tilfa, lfa_flags) if backup is not None and ecmp else None
+                self._backup_step(tables, protect, dev, backup, tilfa, lfa_flags | (LFA_LAN_SAFE_REPAIRS if lan_spaces else 0),
+                                  lans=plan.lans if lan_protect else None)
+                if node:
+                    bn = self._backup_node_tail(graph, run_flags, lfa_flags, backup, dev, tables, protect, *node)
+                if ecmp:
+                    eb = self._backup_ecmp_tail(*tables[:3], dev, protect, backup, tilfa, lfa_flags)
             self._fetch(host, dev)
-            if backup is not None:
-                return BackupRoutes(cand, *(host[k] for k in bk_names),
-                                    tilfa=TilfaResult(*(host[k] for k in ti_names)) if tilfa else None, ecmp=eb, **bn)
-            lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"], lan=plan.lan)
-            rl = RlfaResult(host["pq_node"], host["pq_via"], host["pq_metric"], host["pq_counts"], host.get("sp_flags"),
-                            host.get("sp_via"), host["rl_node"], host["rl_via"], host["rl_cov"])
-            if pc is not None:
-                return cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names)), TilfaPcResult(*(host[k] for k in TILFA_PC_FIELDS))
-            return (cand, lfa, rl, TilfaResult(*(host[k] for k in ti_names))) if tilfa else (cand, lfa, rl)
+        ti = TilfaResult(*(host[k] for k in TILFA_FIELDS)) if tilfa else None
+        if backup is not None:
+            return BackupRoutes(cand, *(host[k] for k in BACKUP_FIELDS), tilfa=ti, ecmp=eb, **bn)
+        res = (cand, _lfa_result(host, plan.lan), _rlfa_result(host))
+        if pc is not None:
+            return res + (ti, TilfaPcResult(*(host[k] for k in TILFA_PC_FIELDS)))
+        return res + (ti,) if tilfa else res
 
     def rlfa_node_select_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                                 space_flags_ptr: int, max_pq: int, nq_node_ptr: int, nq_via_ptr: int, nq_metric_ptr: int, nq_count_ptr: int,
@@ -1905,12 +1846,9 @@ class SpfContext:
         """hspf_rlfa_node_select_device(): per (protected root, slot) the cheapest `max_pq` link-protecting PQ nodes whose release
         path avoids the neighbour behind the slot, from the tables of a run_device() and the space_flags rlfa_device() wrote for the
         same `protect` and lfa_flags.  All `*_ptr` are device pointers; the lists are [P][64 * mask_words][max_pq]."""
-        arr, keep = self._protect_array(protect, "rlfa_node_select_device")
-        out = L.HspfRlfaNodeSel(nq_node_ptr or None, nq_via_ptr or None, nq_metric_ptr or None, nq_count_ptr or None)
-        rc = self.lib.hspf_rlfa_node_select_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                                   arr, len(protect), lfa_flags, space_flags_ptr or None, max_pq, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_rlfa_node_select_device", rc)
+        out = self._out(L.HspfRlfaNodeSel, nq_node=nq_node_ptr, nq_via=nq_via_ptr, nq_metric=nq_metric_ptr, nq_count=nq_count_ptr)
+        self._frr_call("rlfa_node_select_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, space_flags_ptr or None, max_pq, ctypes.byref(out)))
 
     def rlfa_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                          ydist_ptr: int, y_roots, sel: tuple, max_pq: int, nd_kind_ptr: int, nd_node_ptr: int, nd_via_ptr: int,
@@ -1919,16 +1857,13 @@ class SpfContext:
         primary's neighbour.  ydist_ptr: `dist` [len(y_roots)][n] of a forward run_device() of `y_roots` (host array; NO_ROOT
         entries are skipped); sel = (nq_node_ptr, nq_via_ptr, nq_metric_ptr, nq_count_ptr) of rlfa_node_select_device() with the
         same max_pq.  nd_set_ptr / alt_flags_in_ptr may be 0."""
-        arr, keep = self._protect_array(protect, "rlfa_node_device")
         yr = np.ascontiguousarray(y_roots, np.uint32)
         se = L.HspfRlfaNodeSel(*(x or None for x in sel))
-        out = L.HspfRlfaNodeOut(nd_kind_ptr or None, nd_node_ptr or None, nd_via_ptr or None, nd_metric_ptr or None, nd_set_ptr or None,
-                                nd_coverage_ptr or None)
-        rc = self.lib.hspf_rlfa_node_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                            arr, len(protect), ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), ctypes.byref(se), max_pq,
-                                            alt_flags_in_ptr or None, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_rlfa_node_device", rc)
+        out = self._out(L.HspfRlfaNodeOut, nd_kind=nd_kind_ptr, nd_node=nd_node_ptr, nd_via=nd_via_ptr, nd_metric=nd_metric_ptr, nd_set=nd_set_ptr,
+                        nd_coverage=nd_coverage_ptr)
+        self._frr_call("rlfa_node_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), ctypes.byref(se), max_pq, alt_flags_in_ptr or None,
+                        ctypes.byref(out)))
 
     def rlfa_node(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, max_pq: int = 16, symmetric: bool = False):
         """Node-protecting remote alternates of one root, start to finish: run_device() of [root] + its distinct neighbour routers
@@ -1938,53 +1873,26 @@ class SpfContext:
         return self._rlfa_node(graph, root, run_flags, lfa_flags, max_pq, symmetric)[0]
 
     def _rlfa_node(self, graph: SpfGraph, root: int, run_flags: int, lfa_flags: int, max_pq: int, symmetric: bool, tail=None):
-        """The chain of rlfa_node().  tail(dev, tables, protect, R, W): what tilfa_node() goes on with while the tables, the
+        """The chain of rlfa_node().  tail(dev, tables, protect): what tilfa_node() goes on with while the tables, the
         space_flags (dev["sp_flags"]), the alt_flags (dev["aflags"]) and nd_kind (dev["nd_kind"]) are on the device.  Returns
         (RlfaNodeResult, what `tail` returned)."""
         plan = self._frr_plan(graph, root)
-        cand, roots, nbr_row, W = plan.cand, plan.roots, plan.nbr_row, plan.mask_words
-        R, n, S, M = len(roots), graph.n, 64 * W, int(max_pq)
-        host = dict(slot=np.empty((1, n), np.uint32), metric=np.empty((1, n), np.uint32), aflags=np.empty((1, n), np.uint8),
-                    cov=np.empty((1, LFA_COVERAGE_WORDS), np.uint32))
-        sel = dict(nq_node=np.empty((1, S, M), np.uint32), nq_via=np.empty((1, S, M), np.uint32), nq_metric=np.empty((1, S, M), np.uint32),
-                   nq_count=np.empty((1, S), np.uint32))
-        nd = dict(nd_kind=np.empty((1, n), np.uint8), nd_node=np.empty((1, n), np.uint32), nd_via=np.empty((1, n), np.uint32),
-                  nd_metric=np.empty((1, n), np.uint32), nd_set=np.empty((1, n), np.uint32), nd_coverage=np.empty((1, NP_COVERAGE_WORDS), np.uint32))
-        sizes = dict(dist=4 * R * n, flags=2 * R * n, mask=8 * R * n * W, rdist=0 if symmetric else 4 * R * n, sp_flags=S * n,
-                     pq_node=4 * S, pq_via=4 * S, pq_metric=4 * S, pq_counts=4 * S * RLFA_COUNT_WORDS, rl_node=4 * n, rl_via=4 * n,
-                     rl_cov=4 * RLFA_COVERAGE_WORDS)
-        for d in (host, sel, nd):
-            sizes.update({k: max(a.nbytes, 8) for k, a in d.items()})
-        with self._dev_buffers(sizes) as dev, contextlib.ExitStack() as cleanup:
-            tables = (dev["dist"], dev["flags"], dev["mask"])
-            self.run_device(graph, roots, run_flags, dist_ptr=dev["dist"], flags_ptr=dev["flags"], mask_ptr=dev["mask"], mask_words=W)
-            if not symmetric:
-                trp, tcol, tmet = csr_transpose(graph.row_ptr, graph.col, graph.metric, graph.vflags)
-                GT = self.upload(trp, tcol, tmet, graph.vflags, graph.max_path_metric)
-                cleanup.callback(GT.free)
-                self.run_device(GT, roots, run_flags, dist_ptr=dev["rdist"])
-            protect = [(0, cand, nbr_row)]
-            self.lfa_device(n, R, W, *tables, protect, alt_slot_ptr=dev["slot"], alt_metric_ptr=dev["metric"], alt_flags_ptr=dev["aflags"],
-                            coverage_ptr=dev["cov"], lfa_flags=lfa_flags)
-            self.rlfa_device(graph, R, W, *tables, dev["dist"] if symmetric else dev["rdist"], protect, pq_node_ptr=dev["pq_node"],
-                             pq_via_ptr=dev["pq_via"], pq_metric_ptr=dev["pq_metric"], pq_counts_ptr=dev["pq_counts"], rl_node_ptr=dev["rl_node"],
-                             rl_via_ptr=dev["rl_via"], rl_coverage_ptr=dev["rl_cov"], space_flags_ptr=dev["sp_flags"], alt_flags_in_ptr=dev["aflags"],
-                             lfa_flags=lfa_flags)
-            self.rlfa_node_select_device(n, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pq=M, lfa_flags=lfa_flags,
+        n, S, M = graph.n, 64 * plan.mask_words, int(max_pq)
+        only_dev = dict(sp_flags=_frr_shapes("spaces", n=n, S=S)["sp_flags"], **_frr_shapes("rlfa", n=n, S=S))      # (never fetched)
+        shapes = [_frr_shapes("lfa", n=n), _frr_shapes("rn_sel", S=S, M=M), _frr_shapes("nd", n=n)]
+        host, sel, nd = (_empty(sh) for sh in shapes)
+        with self._frr_tables(graph, plan, run_flags, _dev_bytes({**only_dev, **shapes[0], **shapes[1], **shapes[2]}), transposed=not symmetric) as (
+                dev, tables, rdist, protect):
+            self._frr_steps(graph, tables, rdist, protect, dev, lfa_flags)
+            self.rlfa_node_select_device(*tables, protect, space_flags_ptr=dev["sp_flags"], max_pq=M, lfa_flags=lfa_flags,
                                          **{k + "_ptr": dev[k] for k in sel})
             self._fetch(dict(host, **sel), dev)
-            y_roots = np.unique(sel["nq_node"][sel["nq_node"] != NO_ROOT]).astype(np.uint32)
-            if len(y_roots) == 0:                       # no list holds a node: one padding row keeps the test's arguments valid
-                y_roots = np.array([NO_ROOT], np.uint32)
-            with self._dev_buffers(dict(ydist=4 * len(y_roots) * n)) as ydev:
-                if y_roots[0] != NO_ROOT:
-                    self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
-                self.rlfa_node_device(n, R, W, *tables, protect, ydist_ptr=ydev["ydist"], y_roots=y_roots, sel=tuple(dev[k] for k in sel),
-                                      max_pq=M, alt_flags_in_ptr=dev["aflags"], **{k + "_ptr": dev[k] for k in nd})
+            with self._y_run(graph, sel["nq_node"], run_flags) as (y_roots, ydist):
+                self.rlfa_node_device(*tables, protect, ydist_ptr=ydist, y_roots=y_roots, sel=tuple(dev[k] for k in sel), max_pq=M,
+                                      alt_flags_in_ptr=dev["aflags"], **{k + "_ptr": dev[k] for k in nd})
                 self._fetch(nd, dev)
-            more = tail(dev, tables, protect, R, W) if tail else None
-        lfa = LfaResult(host["slot"], host["metric"], host["aflags"], None, None, host["cov"])
-        return RlfaNodeResult(*sel.values(), y_roots, *nd.values(), candidates=cand, lfa=lfa), more
+            more = tail(dev, tables, protect) if tail else None
+        return RlfaNodeResult(*sel.values(), y_roots, *nd.values(), candidates=plan.cand, lfa=_lfa_result(host)), more
 
     def tilfa_node_select_device(self, graph: SpfGraph, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                                  space_flags_ptr: int, max_pairs: int, tq_q_ptr: int, tq_p_ptr: int, tq_link_ptr: int, tq_via_ptr: int,
@@ -1993,12 +1901,10 @@ class SpfContext:
         adjacency p -> q enters from a node p of the extended P-space whose release path avoids the neighbour behind the slot, from
         the tables of a run_device(), the links of `graph` (the FORWARD graph) and the space_flags rlfa_device() wrote for the same
         `protect` and lfa_flags.  All `*_ptr` are device pointers; the lists are [P][64 * mask_words][max_pairs]."""
-        arr, keep = self._protect_array(protect, "tilfa_node_select_device")
-        out = L.HspfTilfaNodeSel(tq_q_ptr or None, tq_p_ptr or None, tq_link_ptr or None, tq_via_ptr or None, tq_metric_ptr or None, tq_count_ptr or None)
-        rc = self.lib.hspf_tilfa_node_select_device(self.handle, graph.handle, graph.n, n_rows, mask_words, dist_ptr or None, flags_ptr or None,
-                                                    mask_ptr or None, arr, len(protect), lfa_flags, space_flags_ptr or None, max_pairs, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_tilfa_node_select_device", rc)
+        out = self._out(L.HspfTilfaNodeSel, tq_q=tq_q_ptr, tq_p=tq_p_ptr, tq_link=tq_link_ptr, tq_via=tq_via_ptr, tq_metric=tq_metric_ptr,
+                        tq_count=tq_count_ptr)
+        self._frr_call("tilfa_node_select_device", (graph.n, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (lfa_flags, space_flags_ptr or None, max_pairs, ctypes.byref(out)), graph=graph)
 
     def tilfa_node_device(self, n_vertices: int, n_rows: int, mask_words: int, dist_ptr: int, flags_ptr: int, mask_ptr: int, protect, *,
                           ydist_ptr: int, y_roots, sel: tuple, max_pairs: int, tn_kind_ptr: int, tn_p_ptr: int, tn_q_ptr: int, tn_link_ptr: int,
@@ -2009,16 +1915,13 @@ class SpfContext:
         entries are skipped); sel = (tq_q_ptr, tq_p_ptr, tq_link_ptr, tq_via_ptr, tq_metric_ptr, tq_count_ptr) of
         tilfa_node_select_device() with the same max_pairs.  tn_set_ptr / alt_flags_in_ptr / nd_kind_in_ptr (the nd_kind of
         rlfa_node_device()) may be 0."""
-        arr, keep = self._protect_array(protect, "tilfa_node_device")
         yr = np.ascontiguousarray(y_roots, np.uint32)
         se = L.HspfTilfaNodeSel(*(x or None for x in sel))
-        out = L.HspfTilfaNodeOut(tn_kind_ptr or None, tn_p_ptr or None, tn_q_ptr or None, tn_link_ptr or None, tn_via_ptr or None, tn_metric_ptr or None,
-                                 tn_set_ptr or None, tn_coverage_ptr or None)
-        rc = self.lib.hspf_tilfa_node_device(self.handle, n_vertices, n_rows, mask_words, dist_ptr or None, flags_ptr or None, mask_ptr or None,
-                                             arr, len(protect), ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), ctypes.byref(se), max_pairs,
-                                             alt_flags_in_ptr or None, nd_kind_in_ptr or None, ctypes.byref(out))
-        del keep
-        self._check_rc("hspf_tilfa_node_device", rc)
+        out = self._out(L.HspfTilfaNodeOut, tn_kind=tn_kind_ptr, tn_p=tn_p_ptr, tn_q=tn_q_ptr, tn_link=tn_link_ptr, tn_via=tn_via_ptr,
+                        tn_metric=tn_metric_ptr, tn_set=tn_set_ptr, tn_coverage=tn_coverage_ptr)
+        self._frr_call("tilfa_node_device", (n_vertices, n_rows, mask_words, dist_ptr, flags_ptr, mask_ptr), protect,
+                       (ydist_ptr or None, _u32(yr) if len(yr) else None, len(yr), ctypes.byref(se), max_pairs, alt_flags_in_ptr or None,
+                        nd_kind_in_ptr or None, ctypes.byref(out)))
 
     def tilfa_node(self, graph: SpfGraph, root: int, run_flags: int = 0, *, lfa_flags: int = 0, max_pq: int = 16, max_pairs: int = 16,
                    symmetric: bool = False):
@@ -2028,25 +1931,16 @@ class SpfContext:
         TilfaNodeResult with one row; its `rlfa_node` is what rlfa_node() returns."""
         n, M = graph.n, int(max_pairs)
 
-        def tail(dev, tables, protect, R, W):
-            S = 64 * W
-            sel = {k: np.empty((1, S, M), np.uint32) for k in ("tq_q", "tq_p", "tq_link", "tq_via", "tq_metric")}
-            sel["tq_count"] = np.empty((1, S), np.uint32)
-            tn = dict(tn_kind=np.empty((1, n), np.uint8), **{k: np.empty((1, n), np.uint32) for k in ("tn_p", "tn_q", "tn_link", "tn_via", "tn_metric", "tn_set")},
-                      tn_coverage=np.empty((1, TN_COVERAGE_WORDS), np.uint32))
-            with self._dev_buffers({k: max(a.nbytes, 8) for k, a in dict(sel, **tn).items()}) as tdev:
-                self.tilfa_node_select_device(graph, R, W, *tables, protect, space_flags_ptr=dev["sp_flags"], max_pairs=M, lfa_flags=lfa_flags,
+        def tail(dev, tables, protect):
+            shapes = [_frr_shapes("tn_sel", S=64 * tables[2], M=M), _frr_shapes("tn", n=n)]
+            sel, tn = (_empty(sh) for sh in shapes)
+            with self._dev_buffers(_dev_bytes({**shapes[0], **shapes[1]})) as tdev:
+                self.tilfa_node_select_device(graph, *tables[1:], protect, space_flags_ptr=dev["sp_flags"], max_pairs=M, lfa_flags=lfa_flags,
                                               **{k + "_ptr": tdev[k] for k in sel})
                 self._fetch(sel, tdev)
-                y_roots = np.unique(sel["tq_q"][sel["tq_q"] != NO_ROOT]).astype(np.uint32)
-                if len(y_roots) == 0:                   # no list holds a q: one padding row keeps the second call's arguments valid
-                    y_roots = np.array([NO_ROOT], np.uint32)
-                with self._dev_buffers(dict(ydist=4 * len(y_roots) * n)) as ydev:
-                    if y_roots[0] != NO_ROOT:
-                        self.run_device(graph, y_roots, run_flags, dist_ptr=ydev["ydist"])
-                    self.tilfa_node_device(n, R, W, *tables, protect, ydist_ptr=ydev["ydist"], y_roots=y_roots, sel=tuple(tdev[k] for k in sel),
-                                           max_pairs=M, alt_flags_in_ptr=dev["aflags"], nd_kind_in_ptr=dev["nd_kind"],
-                                           **{k + "_ptr": tdev[k] for k in tn})
+                with self._y_run(graph, sel["tq_q"], run_flags) as (y_roots, ydist):
+                    self.tilfa_node_device(*tables, protect, ydist_ptr=ydist, y_roots=y_roots, sel=tuple(tdev[k] for k in sel), max_pairs=M,
+                                           alt_flags_in_ptr=dev["aflags"], nd_kind_in_ptr=dev["nd_kind"], **{k + "_ptr": tdev[k] for k in tn})
                     self._fetch(tn, tdev)
             return sel, y_roots, tn
 
