@@ -264,8 +264,7 @@ class Engine {
     hspf_csr csr{(uint32_t)vflags.size(), (uint32_t)col.size(), row_ptr.data(), col.data(), metric.data(), vflags.data(),
                  max_path_metric};
     hspf_graph *g = nullptr;
-    const int rc = hspf_graph_upload(ctx_, &csr, &g);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_graph_upload (") + hspf_last_error(ctx_) + ")");
+    check(hspf_graph_upload(ctx_, &csr, &g), "hspf_graph_upload");
     return Graph(holder_, g);
   }
 
@@ -297,8 +296,7 @@ class Engine {
     if (run_flags & HSPF_RUN_POP_RANK) t.pop_rank.resize(rn);
     hspf_result out{t.dist.data(), t.hops.data(), t.flags.data(), t.mask.data(), t.mask_words,
                     t.pop_rank.empty() ? nullptr : t.pop_rank.data()};
-    const int rc = hspf_run(ctx_, g.raw(), roots.data(), t.n_roots, run_flags, &out);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run (") + hspf_last_error(ctx_) + ")");
+    check(hspf_run(ctx_, g.raw(), roots.data(), t.n_roots, run_flags, &out), "hspf_run");
     hspf_get_stats(ctx_, &t.stats);
     return t;
   }
@@ -314,8 +312,7 @@ class Engine {
     const size_t rn = (size_t)t.n_roots * t.n_vertices;
     t.dist.resize(rn); t.hops.resize(rn); t.flags.resize(rn); t.mask.resize(rn * t.mask_words);
     hspf_result out{t.dist.data(), t.hops.data(), t.flags.data(), t.mask.data(), t.mask_words, nullptr};
-    const int rc = hspf_run_failures(ctx_, g.raw(), roots.data(), failures.data(), t.n_roots, run_flags, &out);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_failures (") + hspf_last_error(ctx_) + ")");
+    check(hspf_run_failures(ctx_, g.raw(), roots.data(), failures.data(), t.n_roots, run_flags, &out), "hspf_run_failures");
     hspf_get_stats(ctx_, &t.stats);
     return t;
   }
@@ -323,8 +320,7 @@ class Engine {
                                  const hspf_result &out_device) {
     if (failures.size() != roots.size()) throw Error(HSPF_E_INVAL, "run_failures_device: one hspf_failure per root");
     hspf_result out = out_device;
-    const int rc = hspf_run_failures_device(ctx_, g.raw(), roots.data(), failures.data(), (uint32_t)roots.size(), run_flags, &out);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_failures_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_run_failures_device(ctx_, g.raw(), roots.data(), failures.data(), (uint32_t)roots.size(), run_flags, &out), "hspf_run_failures_device");
     hspf_stats st{};
     hspf_get_stats(ctx_, &st);
     return st;
@@ -341,8 +337,7 @@ class Engine {
     if (reuse && reuse->words.size() >= need) t.words = std::move(reuse->words);
     else t.words = PinnedBuffer(ctx_, need);
     t.root_status.assign(t.n_roots, 0);
-    const int rc = hspf_run_packed(ctx_, g.raw(), roots.data(), t.n_roots, run_flags, t.words.data(), t.words.size(), &t.layout, t.root_status.data());
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_packed (") + hspf_last_error(ctx_) + ")");
+    check(hspf_run_packed(ctx_, g.raw(), roots.data(), t.n_roots, run_flags, t.words.data(), t.words.size(), &t.layout, t.root_status.data()), "hspf_run_packed");
     hspf_get_stats(ctx_, &t.stats);
     return t;
   }
@@ -352,14 +347,12 @@ class Engine {
   // wait(ticket) has returned.  Results are bit-identical to hspf_run_device's.
   uint64_t run_device_async(const Graph &g, const std::vector<uint32_t> &roots, uint32_t run_flags, const hspf_result &out_device) {
     uint64_t ticket = 0;
-    const int rc = hspf_run_device_async(ctx_, g.raw(), roots.data(), (uint32_t)roots.size(), run_flags, &out_device, &ticket);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device_async (") + hspf_last_error(ctx_) + ")");
+    check(hspf_run_device_async(ctx_, g.raw(), roots.data(), (uint32_t)roots.size(), run_flags, &out_device, &ticket), "hspf_run_device_async");
     return ticket;
   }
   hspf_stats wait(uint64_t ticket) {
     hspf_stats st{};
-    const int rc = hspf_wait(ctx_, ticket, &st);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_wait (") + hspf_last_error(ctx_) + ")");
+    check(hspf_wait(ctx_, ticket, &st), "hspf_wait");
     return st;
   }
   // The route event stream (hspf_routes_events): every (root, prefix) pair of two DEVICE table sets whose action is not
@@ -372,11 +365,9 @@ class Engine {
     if (records.size() < 1024u * stride) records.resize(1024u * stride);
     const uint32_t cap = (uint32_t)std::min<size_t>(records.size() / stride, 0xFFFFFFFFu);
     uint32_t total = 0;
-    int rc = hspf_routes_events(ctx_, n_roots, n_prefixes, n_mask_words, &old_dev, &new_dev, with_silent ? HSPF_EV_SILENT : 0u, cap, records.data(), &total);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_events (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_events(ctx_, n_roots, n_prefixes, n_mask_words, &old_dev, &new_dev, with_silent ? HSPF_EV_SILENT : 0u, cap, records.data(), &total), "hspf_routes_events");
     records.resize((size_t)total * stride);
-    if (total > cap && (rc = hspf_routes_events_rest(ctx_, cap, total - cap, records.data() + (size_t)cap * stride)) != HSPF_OK)
-      throw Error(rc, std::string("hspf_routes_events_rest (") + hspf_last_error(ctx_) + ")");
+    if (total > cap) check(hspf_routes_events_rest(ctx_, cap, total - cap, records.data() + (size_t)cap * stride), "hspf_routes_events_rest");
     return total;
   }
   // Loop-free alternates (RFC 5286).  lfa_candidates: host arithmetic on the caller's CSR, no device.
@@ -394,9 +385,8 @@ class Engine {
   // hspf_lfa_device on DEVICE tables of a previous run (several protected roots may share them).
   void lfa_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
                   const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, hspf_lfa_out out_dev) {
-    const int rc = hspf_lfa_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
-                                   lfa_flags, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_lfa_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                          lfa_flags, &out_dev), "hspf_lfa_device");
   }
   // Broadcast-link protection (RFC 5286 section 3.3).  lfa_lan_candidates: per slot the LAN behind its first link (host arithmetic);
   // lfa_lan_device: lfa_device with loop-freeness towards those pseudonodes; `lans[i]` belongs to `protect[i]`, coverage has
@@ -414,9 +404,8 @@ class Engine {
                       const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_lfa_lan> &lans, uint32_t lfa_flags,
                       hspf_lfa_out out_dev) {
     if (lans.size() != protect.size()) throw Error(HSPF_E_INVAL, "lfa_lan_device: one hspf_lfa_lan per protected root");
-    const int rc = hspf_lfa_lan_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), lans.data(),
-                                       (uint32_t)protect.size(), lfa_flags, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_lan_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_lfa_lan_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), lans.data(),
+                              (uint32_t)protect.size(), lfa_flags, &out_dev), "hspf_lfa_lan_device");
   }
   // One root start to finish: candidates, ONE run for [root] ++ its distinct neighbour routers with the tables left in HBM,
   // the alternates evaluated there, the five arrays and the coverage on the host.  The four vectors must be the CSR `g` was
@@ -424,37 +413,9 @@ class Engine {
   // checked here (HSPF_E_INVAL); rows that differ give alternates of a graph that does not exist.
   Lfa lfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
           const std::vector<uint8_t> &vflags, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0) {
-    if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
-      throw Error(HSPF_E_INVAL, "Engine::lfa: the CSR is not the one the graph was uploaded from");
     Lfa r;
-    r.candidates = lfa_candidates(row_ptr, col, metric, vflags, root);
-    const LfaCandidates &c = r.candidates;
-    std::vector<uint32_t> nbrs;
-    for (uint32_t v : c.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
-    std::sort(nbrs.begin(), nbrs.end());
-    nbrs.erase(std::unique(nbrs.begin(), nbrs.end()), nbrs.end());
-    r.roots.push_back(root);
-    r.roots.insert(r.roots.end(), nbrs.begin(), nbrs.end());
-    std::vector<uint32_t> nbr_row(c.nbr.size(), 0u);
-    for (size_t k = 0; k < c.nbr.size(); ++k)
-      if (c.nbr[k] != HSPF_NO_ROOT) nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), c.nbr[k]) - nbrs.begin());
-    const uint32_t n = g.n_vertices(), R = (uint32_t)r.roots.size();
-    const uint32_t W = std::max(mask_words(g, r.roots), ((uint32_t)c.nbr.size() + 63u) / 64u);
-    r.n_vertices = n; r.mask_words = W;
-    const size_t rn = (size_t)R * n;
-    DeviceBuffer dist(ctx_, rn * 4), flags(ctx_, rn * 2), mask(ctx_, rn * 8 * W);
-    DeviceBuffer slot(ctx_, (size_t)n * 4), met(ctx_, (size_t)n * 4), fl(ctx_, n), cm(ctx_, (size_t)n * 8 * W), nm(ctx_, (size_t)n * 8 * W),
-        cov(ctx_, HSPF_LFA_COVERAGE_WORDS * 4);
-    hspf_result out{dist.as<uint32_t>(), nullptr, flags.as<uint16_t>(), mask.as<uint64_t>(), W, nullptr};
-    const int rc = hspf_run_device(ctx_, g.raw(), r.roots.data(), R, run_flags, &out);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device (") + hspf_last_error(ctx_) + ")");
-    const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
-    lfa_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags,
-               hspf_lfa_out{slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), cm.as<uint64_t>(), nm.as<uint64_t>(), cov.as<uint32_t>()});
-    r.alt_slot = slot.to_host<uint32_t>(n); r.alt_metric = met.to_host<uint32_t>(n); r.alt_flags = fl.to_host<uint8_t>(n);
-    r.cand_mask = cm.to_host<uint64_t>((size_t)n * W); r.node_mask = nm.to_host<uint64_t>((size_t)n * W);
-    const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
-    std::copy(cv.begin(), cv.end(), r.coverage);
+    Chain c = chain_head("Engine::lfa", g, row_ptr, col, metric, vflags, root, run_flags, lfa_flags, r.candidates, r.roots);
+    lfa_step(c, r, true);
     return r;
   }
   // hspf_lfa_ecmp_device on DEVICE tables: per-primary alternates of the destinations with two or more primary slots.  Returns the
@@ -463,51 +424,31 @@ class Engine {
                            const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, uint64_t cap_entries,
                            hspf_lfa_ecmp_out out_dev) {
     uint64_t total = 0;
-    const int rc = hspf_lfa_ecmp_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
-                                        lfa_flags, cap_entries, &out_dev, &total);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_ecmp_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_lfa_ecmp_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                               lfa_flags, cap_entries, &out_dev, &total), "hspf_lfa_ecmp_device");
     return total;
   }
   // One root start to finish, as lfa(): the same run, then hspf_lfa_ecmp_device twice — for ea_ptr and the total, then with arrays of
   // that size.  The four vectors must be the CSR `g` was uploaded from.
   LfaEcmp lfa_ecmp(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
                    const std::vector<uint8_t> &vflags, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0) {
-    if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
-      throw Error(HSPF_E_INVAL, "Engine::lfa_ecmp: the CSR is not the one the graph was uploaded from");
     LfaEcmp r;
-    r.candidates = lfa_candidates(row_ptr, col, metric, vflags, root);
-    const LfaCandidates &c = r.candidates;
-    std::vector<uint32_t> nbrs;
-    for (uint32_t v : c.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
-    std::sort(nbrs.begin(), nbrs.end());
-    nbrs.erase(std::unique(nbrs.begin(), nbrs.end()), nbrs.end());
-    r.roots.push_back(root);
-    r.roots.insert(r.roots.end(), nbrs.begin(), nbrs.end());
-    std::vector<uint32_t> nbr_row(c.nbr.size(), 0u);
-    for (size_t k = 0; k < c.nbr.size(); ++k)
-      if (c.nbr[k] != HSPF_NO_ROOT) nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), c.nbr[k]) - nbrs.begin());
-    const uint32_t n = g.n_vertices(), R = (uint32_t)r.roots.size();
-    const uint32_t W = std::max(mask_words(g, r.roots), ((uint32_t)c.nbr.size() + 63u) / 64u);
-    r.n_vertices = n;
-    const size_t rn = (size_t)R * n;
-    DeviceBuffer dist(ctx_, rn * 4), flags(ctx_, rn * 2), mask(ctx_, rn * 8 * W), ptr(ctx_, ((size_t)n + 1) * 4);
-    hspf_result out{dist.as<uint32_t>(), nullptr, flags.as<uint16_t>(), mask.as<uint64_t>(), W, nullptr};
-    const int rc = hspf_run_device(ctx_, g.raw(), r.roots.data(), R, run_flags, &out);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device (") + hspf_last_error(ctx_) + ")");
-    const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
-    const uint64_t total = lfa_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, 0,
+    const Chain c = chain_head("Engine::lfa_ecmp", g, row_ptr, col, metric, vflags, root, run_flags, lfa_flags, r.candidates, r.roots);
+    const size_t n = c.n;
+    r.n_vertices = c.n;
+    DeviceBuffer ptr(ctx_, (n + 1) * 4);
+    const uint64_t total = lfa_ecmp_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), c.protect(), lfa_flags, 0,
                                            hspf_lfa_ecmp_out{ptr.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr});
     if (total) {
       const size_t t = (size_t)total;
       DeviceBuffer pri(ctx_, t * 4), slot(ctx_, t * 4), met(ctx_, t * 4), fl(ctx_, t), cov(ctx_, HSPF_LFA_ECMP_COVERAGE_WORDS * 4);
-      lfa_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, total,
+      lfa_ecmp_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), c.protect(), lfa_flags, total,
                       hspf_lfa_ecmp_out{ptr.as<uint32_t>(), pri.as<uint32_t>(), slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), cov.as<uint32_t>()});
       r.ea_primary = pri.to_host<uint32_t>(t); r.ea_slot = slot.to_host<uint32_t>(t); r.ea_metric = met.to_host<uint32_t>(t);
       r.ea_flags = fl.to_host<uint8_t>(t);
-      const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_ECMP_COVERAGE_WORDS);
-      std::copy(cv.begin(), cv.end(), r.ea_coverage);
+      words_to_host(cov, r.ea_coverage);
     }
-    r.ea_ptr = ptr.to_host<uint32_t>((size_t)n + 1);
+    r.ea_ptr = ptr.to_host<uint32_t>(n + 1);
     return r;
   }
   // Remote loop-free alternates (RFC 7490).  csr_transpose: host arithmetic, no device; of a run on the result only `dist`
@@ -526,9 +467,8 @@ class Engine {
   void rlfa_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                    const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                    hspf_rlfa_out out_dev) {
-    const int rc = hspf_rlfa_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
-                                    (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_rlfa_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                           (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev), "hspf_rlfa_device");
   }
   // hspf_rlfa_lan_device: rlfa_device with P, extended P and Q loop-free towards the pseudonode of every slot's LAN.  `lans[i]`
   // belongs to `protect[i]`; both table sets come from the run [S] ++ neighbour routers ++ LANs, rdist_dev ALWAYS from the transposed
@@ -537,9 +477,8 @@ class Engine {
                        const uint64_t *mask_dev, const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect,
                        const std::vector<hspf_lfa_lan> &lans, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev, hspf_rlfa_out out_dev) {
     if (lans.size() != protect.size()) throw Error(HSPF_E_INVAL, "rlfa_lan_device: one hspf_lfa_lan per protected root");
-    const int rc = hspf_rlfa_lan_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
-                                        lans.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_lan_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_rlfa_lan_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                               lans.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev), "hspf_rlfa_lan_device");
   }
   // Shared-risk link groups.  srlg_members: host arithmetic, no device (hspf_srlg_members): per first-hop slot of `root` the other
   // links that share a group id with the link of the root's row the slot stands behind; tail_row / head_row are the caller's to fill.
@@ -568,9 +507,8 @@ class Engine {
                        const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const std::vector<hspf_srlg> &srlgs,
                        uint32_t lfa_flags, hspf_lfa_out out_dev) {
     if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "lfa_srlg_device: one hspf_srlg per protected root");
-    const int rc = hspf_lfa_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
-                                        (uint32_t)protect.size(), lfa_flags, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_lfa_srlg_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_lfa_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
+                               (uint32_t)protect.size(), lfa_flags, &out_dev), "hspf_lfa_srlg_device");
   }
   // hspf_rlfa_srlg_device: rlfa_device with P, extended P and Q narrowed by the members of every slot's group; both table sets come
   // from the run [S] ++ neighbour routers ++ member endpoints; pq_counts has HSPF_RLFA_SRLG_COUNT_WORDS words per slot, rl_coverage
@@ -579,9 +517,8 @@ class Engine {
                         const uint64_t *mask_dev, const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect,
                         const std::vector<hspf_srlg> &srlgs, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev, hspf_rlfa_out out_dev) {
     if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "rlfa_srlg_device: one hspf_srlg per protected root");
-    const int rc = hspf_rlfa_srlg_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
-                                         srlgs.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_srlg_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_rlfa_srlg_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                                srlgs.data(), (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, &out_dev), "hspf_rlfa_srlg_device");
   }
   // One root start to finish, as lfa(): ONE run of [root] ++ its neighbour routers on `g` and one on the upload of its transpose
   // (skipped when `symmetric` says every link has its reverse at the same cost), hspf_lfa_device, hspf_rlfa_device, results on
@@ -589,15 +526,17 @@ class Engine {
   Rlfa rlfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
             const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
             bool symmetric = false, bool with_spaces = false) {
-    return rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, with_spaces, nullptr, nullptr, nullptr);
+    Rlfa r;
+    Chain c = rlfa_head(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, r);
+    remote_step(c, r, with_spaces);
+    return r;
   }
   // hspf_tilfa_device on DEVICE tables: those of rlfa_device plus the space tables it wrote (required); `g` is the FORWARD graph.
   void tilfa_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev, const uint64_t *mask_dev,
                     const uint32_t *rdist_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const uint8_t *alt_flags_in_dev,
                     const uint8_t *space_flags_dev, const uint32_t *space_via_dev, hspf_tilfa_out out_dev) {
-    const int rc = hspf_tilfa_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
-                                     (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_tilfa_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                            (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, &out_dev), "hspf_tilfa_device");
   }
   // hspf_tilfa_pc_device on DEVICE tables: those of tilfa_device, and pc_dist_dev [n_pc_rows][n_vertices] — the dist of a
   // run_failures_device on `g` — with pc_row [protect.size()][64 * n_mask_words] (host) naming each slot's row (HSPF_NO_ROOT: none).
@@ -606,17 +545,18 @@ class Engine {
                        const uint8_t *space_flags_dev, const uint32_t *space_via_dev, const uint32_t *pc_dist_dev, uint32_t n_pc_rows,
                        const std::vector<uint32_t> &pc_row, uint32_t run_flags, uint32_t max_walk, hspf_tilfa_pc_out out_dev) {
     if (pc_row.size() != protect.size() * 64u * n_mask_words) throw Error(HSPF_E_INVAL, "tilfa_pc_device: pc_row holds 64 * n_mask_words entries per protected root");
-    const int rc = hspf_tilfa_pc_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
-                                        (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, pc_dist_dev, n_pc_rows,
-                                        pc_row.data(), run_flags, max_walk, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_pc_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_tilfa_pc_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, rdist_dev, protect.data(),
+                               (uint32_t)protect.size(), lfa_flags, alt_flags_in_dev, space_flags_dev, space_via_dev, pc_dist_dev, n_pc_rows,
+                               pc_row.data(), run_flags, max_walk, &out_dev), "hspf_tilfa_pc_device");
   }
   // One root start to finish: rlfa() with the space tables, everything kept on the device, then hspf_tilfa_device on the same rows.
   Tilfa tilfa(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
               const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags = 0, uint32_t lfa_flags = 0,
               bool symmetric = false) {
     Tilfa t;
-    t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, &t, nullptr, nullptr);
+    Chain c = rlfa_head(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, t.rlfa);
+    remote_step(c, t.rlfa, true);
+    two_segment_step(c, t);
     return t;
   }
   // hspf_rlfa_node_select_device on DEVICE tables: the table set and protect list of lfa_device and the space_flags rlfa_device
@@ -624,9 +564,8 @@ class Engine {
   void rlfa_node_select_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
                                const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags,
                                const uint8_t *space_flags_dev, uint32_t max_pq, hspf_rlfa_node_sel out_dev) {
-    const int rc = hspf_rlfa_node_select_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
-                                                (uint32_t)protect.size(), lfa_flags, space_flags_dev, max_pq, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_node_select_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_rlfa_node_select_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                       (uint32_t)protect.size(), lfa_flags, space_flags_dev, max_pq, &out_dev), "hspf_rlfa_node_select_device");
   }
   // hspf_rlfa_node_device on DEVICE tables: ydist_dev is the dist of a forward run of y_roots (host list: the caller's choice among
   // the listed nodes), sel_dev what rlfa_node_select_device wrote with the same max_pq.
@@ -634,18 +573,16 @@ class Engine {
                         const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const uint32_t *ydist_dev,
                         const std::vector<uint32_t> &y_roots, const hspf_rlfa_node_sel &sel_dev, uint32_t max_pq, const uint8_t *alt_flags_in_dev,
                         hspf_rlfa_node_out out_dev) {
-    const int rc = hspf_rlfa_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
-                                         ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pq, alt_flags_in_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_rlfa_node_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_rlfa_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pq, alt_flags_in_dev, &out_dev), "hspf_rlfa_node_device");
   }
   // hspf_tilfa_node_select_device on DEVICE tables: the table set and protect list of lfa_device, the FORWARD graph and the
   // space_flags rlfa_device wrote for them; the lists are [protect.size()][64 * n_mask_words][max_pairs].
   void tilfa_node_select_device(const Graph &g, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
                                 const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags,
                                 const uint8_t *space_flags_dev, uint32_t max_pairs, hspf_tilfa_node_sel out_dev) {
-    const int rc = hspf_tilfa_node_select_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
-                                                 (uint32_t)protect.size(), lfa_flags, space_flags_dev, max_pairs, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_node_select_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_tilfa_node_select_device(ctx_, g.raw(), g.n_vertices(), n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                        (uint32_t)protect.size(), lfa_flags, space_flags_dev, max_pairs, &out_dev), "hspf_tilfa_node_select_device");
   }
   // hspf_tilfa_node_device on DEVICE tables: ydist_dev is the dist of a forward run of y_roots (host list: the caller's choice among
   // the listed q's), sel_dev what tilfa_node_select_device wrote with the same max_pairs; nd_kind_in_dev: the nd_kind of
@@ -654,9 +591,8 @@ class Engine {
                          const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, const uint32_t *ydist_dev,
                          const std::vector<uint32_t> &y_roots, const hspf_tilfa_node_sel &sel_dev, uint32_t max_pairs, const uint8_t *alt_flags_in_dev,
                          const uint8_t *nd_kind_in_dev, hspf_tilfa_node_out out_dev) {
-    const int rc = hspf_tilfa_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
-                                          ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pairs, alt_flags_in_dev, nd_kind_in_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_tilfa_node_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_tilfa_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                 ydist_dev, y_roots.data(), (uint32_t)y_roots.size(), &sel_dev, max_pairs, alt_flags_in_dev, nd_kind_in_dev, &out_dev), "hspf_tilfa_node_device");
   }
   // One root start to finish: rlfa() with the space tables, everything kept on the device, then the node-protecting remote LFA
   // (select, ONE run over the union of the listed PQ nodes, evaluate) and the two-segment node-protecting repairs (select, ONE run
@@ -669,7 +605,9 @@ class Engine {
     if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) throw Error(HSPF_E_INVAL, "Engine::tilfa_node: max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
     TilfaNode t;
     t.max_pq = max_pq; t.max_pairs = max_pairs;
-    t.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, true, nullptr, nullptr, nullptr, &t);
+    Chain c = rlfa_head(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric, t.rlfa);
+    remote_step(c, t.rlfa, true);
+    node_steps(c, t);
     return t;
   }
   // hspf_routes_backup_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the routes
@@ -677,9 +615,8 @@ class Engine {
   void routes_backup_device(uint32_t n_vertices, uint32_t n_rows, uint32_t n_mask_words, const uint32_t *dist_dev, const uint16_t *flags_dev,
                             const uint64_t *mask_dev, const std::vector<hspf_lfa_protect> &protect, uint32_t lfa_flags, const hspf_prefix_table &table,
                             const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev, hspf_backup_out out_dev) {
-    const int rc = hspf_routes_backup_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
-                                             lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_backup_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), (uint32_t)protect.size(),
+                                    lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev), "hspf_routes_backup_device");
   }
   // hspf_routes_backup_ecmp_device on the same inputs: per primary of every prefix with two or more primary slots, its backup.
   // Returns the total number of entries; when it exceeds cap_entries only eb_ptr was written (repeat with larger arrays).
@@ -688,9 +625,8 @@ class Engine {
                                      const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev, uint64_t cap_entries,
                                      hspf_backup_ecmp_out out_dev) {
     uint64_t total = 0;
-    const int rc = hspf_routes_backup_ecmp_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
-                                                  (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, cap_entries, &out_dev, &total);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_ecmp_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_backup_ecmp_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                         (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, cap_entries, &out_dev, &total), "hspf_routes_backup_ecmp_device");
     return total;
   }
   // hspf_routes_backup_ecmp_srlg_device: routes_backup_ecmp_device whose alternate for a primary h neither starts on nor crosses, on
@@ -702,9 +638,8 @@ class Engine {
                                           uint64_t cap_entries, hspf_backup_ecmp_out out_dev) {
     if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "routes_backup_ecmp_srlg_device: one hspf_srlg per protected root");
     uint64_t total = 0;
-    const int rc = hspf_routes_backup_ecmp_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
-                                                       (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, cap_entries, &out_dev, &total);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_ecmp_srlg_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_backup_ecmp_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
+                                              (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, cap_entries, &out_dev, &total), "hspf_routes_backup_ecmp_srlg_device");
     return total;
   }
   // hspf_routes_backup_lan_device: the same with loop-freeness towards the pseudonodes of the primaries' LANs (`lans` as for
@@ -714,9 +649,8 @@ class Engine {
                                 uint32_t lfa_flags, const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev,
                                 hspf_backup_out out_dev) {
     if (lans.size() != protect.size()) throw Error(HSPF_E_INVAL, "routes_backup_lan_device: one hspf_lfa_lan per protected root");
-    const int rc = hspf_routes_backup_lan_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), lans.data(),
-                                                 (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_lan_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_backup_lan_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), lans.data(),
+                                        (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev), "hspf_routes_backup_lan_device");
   }
   // hspf_routes_backup_srlg_device: routes_backup_device whose alternates neither start on nor cross, on their way to the prefix, a
   // member of a primary's shared-risk group (`srlgs` as for lfa_srlg_device; HSPF_LFA_SRLG_SAFE_REPAIRS in lfa_flags vouches for
@@ -726,9 +660,8 @@ class Engine {
                                  uint32_t lfa_flags, const hspf_prefix_table &table, const hspf_routes &routes_dev, const hspf_tilfa_out *tilfa_dev,
                                  hspf_backup_out out_dev) {
     if (srlgs.size() != protect.size()) throw Error(HSPF_E_INVAL, "routes_backup_srlg_device: one hspf_srlg per protected root");
-    const int rc = hspf_routes_backup_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
-                                                  (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_srlg_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_backup_srlg_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(), srlgs.data(),
+                                         (uint32_t)protect.size(), lfa_flags, &table, &routes_dev, tilfa_dev, &out_dev), "hspf_routes_backup_srlg_device");
   }
   // hspf_routes_backup_node_device on DEVICE tables: the table set and protect list of lfa_device, the HOST prefix table and the
   // routes hspf_routes_device wrote for it, ydist_dev the dist of a forward run of y_roots (host list: the caller's choice among the
@@ -739,10 +672,9 @@ class Engine {
                                  const hspf_routes &routes_dev, const uint32_t *ydist_dev, const std::vector<uint32_t> &y_roots,
                                  const hspf_rlfa_node_sel *rn_sel_dev, uint32_t max_pq, const hspf_tilfa_node_sel *tn_sel_dev, uint32_t max_pairs,
                                  const hspf_backup_out *bk_in_dev, hspf_backup_node_out out_dev) {
-    const int rc = hspf_routes_backup_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
-                                                  (uint32_t)protect.size(), &table, &routes_dev, ydist_dev, y_roots.data(), (uint32_t)y_roots.size(),
-                                                  rn_sel_dev, max_pq, tn_sel_dev, max_pairs, bk_in_dev, &out_dev);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_backup_node_device (") + hspf_last_error(ctx_) + ")");
+    check(hspf_routes_backup_node_device(ctx_, n_vertices, n_rows, n_mask_words, dist_dev, flags_dev, mask_dev, protect.data(),
+                                         (uint32_t)protect.size(), &table, &routes_dev, ydist_dev, y_roots.data(), (uint32_t)y_roots.size(),
+                                         rn_sel_dev, max_pq, tn_sel_dev, max_pairs, bk_in_dev, &out_dev), "hspf_routes_backup_node_device");
   }
   // One root start to finish: the chain of tilfa() (of lfa() alone without `remote`), hspf_routes_device for the root's row and
   // hspf_routes_backup_device, everything kept on the device in between.  table_flags: HSPF_PFX_SATURATING / HSPF_PFX_LAST_MIN.
@@ -757,8 +689,13 @@ class Engine {
     b.n_prefixes = (uint32_t)pfx_ptr.size() - 1u;
     const hspf_prefix_table t{b.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.data(), pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT,
                               nullptr, nullptr, nullptr, nullptr};
-    b.tilfa.rlfa = rlfa_impl(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric || !remote, remote,
-                             remote ? &b.tilfa : nullptr, &b, &t);
+    // without `remote` nothing reads the remote LFA or the reverse run: both are skipped
+    Chain c = rlfa_head(g, row_ptr, col, metric, vflags, max_path_metric, root, run_flags, lfa_flags, symmetric || !remote, b.tilfa.rlfa);
+    if (remote) {
+      remote_step(c, b.tilfa.rlfa, true);
+      two_segment_step(c, b.tilfa);
+    }
+    backup_step(c, b, t);
     return b;
   }
   void wait_all() { (void)hspf_wait_all(ctx_); }
@@ -769,162 +706,201 @@ class Engine {
   }
 
  private:
-  // rlfa(); with `ti` the two-segment step runs on the same device tables before anything is freed; with `bk` the routes of `table`
-  // and their backups are derived there too (without `ti` the remote-LFA call is skipped: nothing reads it); with `tn` (and the
-  // space tables) the two node-protecting pairs of calls run there, each with its own run over the union of its lists
-  Rlfa rlfa_impl(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
-                 const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags, uint32_t lfa_flags,
-                 bool symmetric, bool with_spaces, Tilfa *ti, BackupRoutes *bk, const hspf_prefix_table *table, TilfaNode *tn = nullptr) {
+  void check(int rc, const char *call) const {
+    if (rc != HSPF_OK) throw Error(rc, std::string(call) + " (" + hspf_last_error(ctx_) + ")");
+  }
+  template <size_t N> static void words_to_host(const DeviceBuffer &b, uint32_t (&dst)[N]) {      // a coverage array
+    const std::vector<uint32_t> v = b.to_host<uint32_t>(N);
+    std::copy(v.begin(), v.end(), dst);
+  }
+  // The device tables the steps of a one-root chain share.  The head fills the first line — the forward run of [root] ++ its
+  // distinct neighbour routers, left in HBM — and the one protected root over it; every step leaves what a later one reads.
+  struct Chain {
+    const Graph *g = nullptr;
+    const LfaCandidates *cand = nullptr;
+    uint32_t n = 0, R = 0, W = 1, S = 64, run_flags = 0, lfa_flags = 0;
+    std::vector<uint32_t> nbr_row;
+    DeviceBuffer dist, flags, mask;     // chain_head
+    DeviceBuffer rdist;                 // rlfa_head: the dist of the same roots on the transposed graph (not read where the costs are symmetric)
+    DeviceBuffer alt_flags;             // lfa_step
+    DeviceBuffer sp_flags, sp_via;      // remote_step
+    DeviceBuffer ti_kind, ti_via, ti_metric;   // two_segment_step
+    bool repairs = false;               // ... has run
+    bool symmetric = false;
+    uint32_t *d() const { return dist.as<uint32_t>(); }
+    uint16_t *f() const { return flags.as<uint16_t>(); }
+    uint64_t *m() const { return mask.as<uint64_t>(); }
+    const uint32_t *rd() const { return symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(); }
+    std::vector<hspf_lfa_protect> protect() const {
+      return {hspf_lfa_protect{cand->root, 0u, (uint32_t)cand->nbr.size(), cand->nbr.data(), nbr_row.data(), cand->cost.data(), cand->root_link.data(),
+                               cand->cflags.data()}};
+    }
+  };
+  // The head of every chain: the CSR held against the graph (`who` names the caller in the message), the candidate table into `cand`,
+  // [root] ++ its sorted distinct neighbour routers into `roots` with the row of every slot's neighbour, the mask width, the run.
+  Chain chain_head(const char *who, const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                   const std::vector<uint8_t> &vflags, uint32_t root, uint32_t run_flags, uint32_t lfa_flags, LfaCandidates &cand, std::vector<uint32_t> &roots) {
     if (vflags.size() != g.n_vertices() || row_ptr.size() != vflags.size() + 1 || col.size() != g.n_links() || metric.size() != col.size())
-      throw Error(HSPF_E_INVAL, "Engine::rlfa: the CSR is not the one the graph was uploaded from");
-    Rlfa r;
-    r.lfa.candidates = lfa_candidates(row_ptr, col, metric, vflags, root);
-    const LfaCandidates &c = r.lfa.candidates;
+      throw Error(HSPF_E_INVAL, std::string(who) + ": the CSR is not the one the graph was uploaded from");
+    cand = lfa_candidates(row_ptr, col, metric, vflags, root);
     std::vector<uint32_t> nbrs;
-    for (uint32_t v : c.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
+    for (uint32_t v : cand.nbr) if (v != HSPF_NO_ROOT) nbrs.push_back(v);
     std::sort(nbrs.begin(), nbrs.end());
     nbrs.erase(std::unique(nbrs.begin(), nbrs.end()), nbrs.end());
-    r.lfa.roots.push_back(root);
-    r.lfa.roots.insert(r.lfa.roots.end(), nbrs.begin(), nbrs.end());
-    std::vector<uint32_t> nbr_row(c.nbr.size(), 0u);
-    for (size_t k = 0; k < c.nbr.size(); ++k)
-      if (c.nbr[k] != HSPF_NO_ROOT) nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), c.nbr[k]) - nbrs.begin());
-    const uint32_t n = g.n_vertices(), R = (uint32_t)r.lfa.roots.size();
-    const uint32_t W = std::max(mask_words(g, r.lfa.roots), ((uint32_t)c.nbr.size() + 63u) / 64u), S = 64u * W;
-    r.lfa.n_vertices = n; r.lfa.mask_words = W; r.slot_stride = S;
-    const size_t rn = (size_t)R * n, sn = with_spaces ? (size_t)S * n : 0;
-    DeviceBuffer dist(ctx_, rn * 4), flags(ctx_, rn * 2), mask(ctx_, rn * 8 * W), rdist(ctx_, symmetric ? 0 : rn * 4);
-    DeviceBuffer slot(ctx_, (size_t)n * 4), met(ctx_, (size_t)n * 4), fl(ctx_, n), cov(ctx_, HSPF_LFA_COVERAGE_WORDS * 4);
-    DeviceBuffer pq_node(ctx_, S * 4), pq_via(ctx_, S * 4), pq_metric(ctx_, S * 4), pq_counts(ctx_, (size_t)S * 4 * HSPF_RLFA_COUNT_WORDS),
-        sp_flags(ctx_, sn), sp_via(ctx_, sn * 4), rl_node(ctx_, (size_t)n * 4), rl_via(ctx_, (size_t)n * 4), rl_cov(ctx_, HSPF_RLFA_COVERAGE_WORDS * 4);
-    hspf_result out{dist.as<uint32_t>(), nullptr, flags.as<uint16_t>(), mask.as<uint64_t>(), W, nullptr};
-    int rc = hspf_run_device(ctx_, g.raw(), r.lfa.roots.data(), R, run_flags, &out);
-    if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device (") + hspf_last_error(ctx_) + ")");
+    roots.push_back(root);
+    roots.insert(roots.end(), nbrs.begin(), nbrs.end());
+    Chain c;
+    c.g = &g; c.cand = &cand; c.run_flags = run_flags; c.lfa_flags = lfa_flags;
+    c.nbr_row.assign(cand.nbr.size(), 0u);
+    for (size_t k = 0; k < cand.nbr.size(); ++k)
+      if (cand.nbr[k] != HSPF_NO_ROOT) c.nbr_row[k] = 1u + (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), cand.nbr[k]) - nbrs.begin());
+    c.n = g.n_vertices(); c.R = (uint32_t)roots.size();
+    c.W = std::max(mask_words(g, roots), ((uint32_t)cand.nbr.size() + 63u) / 64u); c.S = 64u * c.W;
+    const size_t rn = (size_t)c.R * c.n;
+    c.dist = DeviceBuffer(ctx_, rn * 4); c.flags = DeviceBuffer(ctx_, rn * 2); c.mask = DeviceBuffer(ctx_, rn * 8 * c.W);
+    hspf_result out{c.d(), nullptr, c.f(), c.m(), c.W, nullptr};
+    check(hspf_run_device(ctx_, g.raw(), roots.data(), c.R, run_flags, &out), "hspf_run_device");
+    return c;
+  }
+  // The LFA step: hspf_lfa_device over the head's run; the masks only for lfa() itself.  alt_flags stay for the steps behind it.
+  void lfa_step(Chain &c, Lfa &r, bool with_masks) {
+    const size_t n = c.n, nw = with_masks ? n * c.W : 0;
+    r.n_vertices = c.n; r.mask_words = c.W;
+    DeviceBuffer slot(ctx_, n * 4), met(ctx_, n * 4), cm, nm, cov(ctx_, HSPF_LFA_COVERAGE_WORDS * 4);
+    c.alt_flags = DeviceBuffer(ctx_, n);
+    if (with_masks) { cm = DeviceBuffer(ctx_, nw * 8); nm = DeviceBuffer(ctx_, nw * 8); }
+    lfa_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), c.protect(), c.lfa_flags,
+               hspf_lfa_out{slot.as<uint32_t>(), met.as<uint32_t>(), c.alt_flags.as<uint8_t>(), cm.as<uint64_t>(), nm.as<uint64_t>(), cov.as<uint32_t>()});
+    r.alt_slot = slot.to_host<uint32_t>(n); r.alt_metric = met.to_host<uint32_t>(n); r.alt_flags = c.alt_flags.to_host<uint8_t>(n);
+    if (with_masks) { r.cand_mask = cm.to_host<uint64_t>(nw); r.node_mask = nm.to_host<uint64_t>(nw); }
+    words_to_host(cov, r.coverage);
+  }
+  // The head of the remote chains (all say Engine::rlfa): chain_head, the run of the same roots on the upload of the transposed CSR —
+  // skipped when `symmetric` — and the LFA step.
+  Chain rlfa_head(const Graph &g, const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, const std::vector<uint32_t> &metric,
+                  const std::vector<uint8_t> &vflags, uint32_t max_path_metric, uint32_t root, uint32_t run_flags, uint32_t lfa_flags, bool symmetric, Rlfa &r) {
+    Chain c = chain_head("Engine::rlfa", g, row_ptr, col, metric, vflags, root, run_flags, lfa_flags, r.lfa.candidates, r.lfa.roots);
+    r.slot_stride = c.S;
+    c.symmetric = symmetric;
+    c.rdist = DeviceBuffer(ctx_, symmetric ? 0 : (size_t)c.R * c.n * 4);
     if (!symmetric) {
       const Transposed t = csr_transpose(row_ptr, col, metric, vflags);
       Graph gt = upload(t.row_ptr, t.col, t.metric, vflags, max_path_metric);
-      hspf_result rout{rdist.as<uint32_t>(), nullptr, nullptr, nullptr, 1, nullptr};
-      rc = hspf_run_device(ctx_, gt.raw(), r.lfa.roots.data(), R, run_flags, &rout);
-      if (rc != HSPF_OK) throw Error(rc, std::string("hspf_run_device on the transposed graph (") + hspf_last_error(ctx_) + ")");
+      hspf_result rout{c.rdist.as<uint32_t>(), nullptr, nullptr, nullptr, 1, nullptr};
+      check(hspf_run_device(ctx_, gt.raw(), r.lfa.roots.data(), c.R, run_flags, &rout), "hspf_run_device on the transposed graph");
     }
-    const hspf_lfa_protect p{root, 0u, (uint32_t)c.nbr.size(), c.nbr.data(), nbr_row.data(), c.cost.data(), c.root_link.data(), c.cflags.data()};
-    lfa_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags,
-               hspf_lfa_out{slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), nullptr, nullptr, cov.as<uint32_t>()});
-    const bool remote = !bk || ti;
-    if (remote)
-    rlfa_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(), {p},
-                lfa_flags, fl.as<uint8_t>(),
+    lfa_step(c, r.lfa, false);
+    return c;
+  }
+  // The remote step: hspf_rlfa_device; the space tables, when asked for, stay for the steps behind it.
+  void remote_step(Chain &c, Rlfa &r, bool with_spaces) {
+    const size_t n = c.n, S = c.S, sn = with_spaces ? S * n : 0;
+    DeviceBuffer pq_node(ctx_, S * 4), pq_via(ctx_, S * 4), pq_metric(ctx_, S * 4), pq_counts(ctx_, S * 4 * HSPF_RLFA_COUNT_WORDS), rl_node(ctx_, n * 4),
+        rl_via(ctx_, n * 4), rl_cov(ctx_, HSPF_RLFA_COVERAGE_WORDS * 4);
+    c.sp_flags = DeviceBuffer(ctx_, sn); c.sp_via = DeviceBuffer(ctx_, sn * 4);
+    rlfa_device(*c.g, c.R, c.W, c.d(), c.f(), c.m(), c.rd(), c.protect(), c.lfa_flags, c.alt_flags.as<uint8_t>(),
                 hspf_rlfa_out{pq_node.as<uint32_t>(), pq_via.as<uint32_t>(), pq_metric.as<uint32_t>(), pq_counts.as<uint32_t>(),
-                              with_spaces ? sp_flags.as<uint8_t>() : nullptr, with_spaces ? sp_via.as<uint32_t>() : nullptr, rl_node.as<uint32_t>(),
+                              with_spaces ? c.sp_flags.as<uint8_t>() : nullptr, with_spaces ? c.sp_via.as<uint32_t>() : nullptr, rl_node.as<uint32_t>(),
                               rl_via.as<uint32_t>(), rl_cov.as<uint32_t>()});
-    r.lfa.alt_slot = slot.to_host<uint32_t>(n); r.lfa.alt_metric = met.to_host<uint32_t>(n); r.lfa.alt_flags = fl.to_host<uint8_t>(n);
-    const std::vector<uint32_t> cv = cov.to_host<uint32_t>(HSPF_LFA_COVERAGE_WORDS);
-    std::copy(cv.begin(), cv.end(), r.lfa.coverage);
-    if (remote) {
     r.pq_node = pq_node.to_host<uint32_t>(S); r.pq_via = pq_via.to_host<uint32_t>(S); r.pq_metric = pq_metric.to_host<uint32_t>(S);
-    r.pq_counts = pq_counts.to_host<uint32_t>((size_t)S * HSPF_RLFA_COUNT_WORDS);
-    if (with_spaces) { r.space_flags = sp_flags.to_host<uint8_t>(sn); r.space_via = sp_via.to_host<uint32_t>(sn); }
+    r.pq_counts = pq_counts.to_host<uint32_t>(S * HSPF_RLFA_COUNT_WORDS);
+    if (with_spaces) { r.space_flags = c.sp_flags.to_host<uint8_t>(sn); r.space_via = c.sp_via.to_host<uint32_t>(sn); }
     r.rl_node = rl_node.to_host<uint32_t>(n); r.rl_via = rl_via.to_host<uint32_t>(n);
-    const std::vector<uint32_t> rc4 = rl_cov.to_host<uint32_t>(HSPF_RLFA_COVERAGE_WORDS);
-    std::copy(rc4.begin(), rc4.end(), r.rl_coverage);
+    words_to_host(rl_cov, r.rl_coverage);
+  }
+  // The two-segment step: hspf_tilfa_device on the space tables; kind, via and metric of every slot stay for the backup step.
+  void two_segment_step(Chain &c, Tilfa &t) {
+    const size_t n = c.n, S = c.S;
+    c.ti_kind = DeviceBuffer(ctx_, S); c.ti_via = DeviceBuffer(ctx_, S * 4); c.ti_metric = DeviceBuffer(ctx_, S * 4);
+    c.repairs = true;
+    DeviceBuffer tp(ctx_, S * 4), tq(ctx_, S * 4), tl(ctx_, S * 4), tc(ctx_, S * 4 * HSPF_TILFA_COUNT_WORDS), dk(ctx_, n), dc(ctx_, HSPF_TILFA_COVERAGE_WORDS * 4);
+    tilfa_device(*c.g, c.R, c.W, c.d(), c.f(), c.m(), c.rd(), c.protect(), c.lfa_flags, c.alt_flags.as<uint8_t>(), c.sp_flags.as<uint8_t>(), c.sp_via.as<uint32_t>(),
+                 hspf_tilfa_out{c.ti_kind.as<uint8_t>(), tp.as<uint32_t>(), tq.as<uint32_t>(), c.ti_via.as<uint32_t>(), tl.as<uint32_t>(), c.ti_metric.as<uint32_t>(),
+                                tc.as<uint32_t>(), dk.as<uint8_t>(), dc.as<uint32_t>()});
+    t.ti_kind = c.ti_kind.to_host<uint8_t>(S); t.ti_p = tp.to_host<uint32_t>(S); t.ti_q = tq.to_host<uint32_t>(S);
+    t.ti_via = c.ti_via.to_host<uint32_t>(S); t.ti_link = tl.to_host<uint32_t>(S); t.ti_metric = c.ti_metric.to_host<uint32_t>(S);
+    t.ti_counts = tc.to_host<uint32_t>(S * HSPF_TILFA_COUNT_WORDS); t.td_kind = dk.to_host<uint8_t>(n);
+    words_to_host(dc, t.td_coverage);
+  }
+  // The ascending union of the vertices a select call listed into `y`, and their rows (dist only) on the forward graph; one padding
+  // row keeps the arguments of the evaluate call valid where no list holds a vertex.
+  DeviceBuffer rows_of(const Chain &c, const std::vector<uint32_t> &listed, std::vector<uint32_t> &y) {
+    for (uint32_t v : listed) if (v != HSPF_NO_ROOT) y.push_back(v);
+    std::sort(y.begin(), y.end());
+    y.erase(std::unique(y.begin(), y.end()), y.end());
+    const bool none = y.empty();
+    if (none) y.push_back(HSPF_NO_ROOT);
+    DeviceBuffer ydist(ctx_, y.size() * (size_t)c.n * 4);
+    if (none) return ydist;
+    hspf_result yout{ydist.as<uint32_t>(), nullptr, nullptr, nullptr, 1, nullptr};
+    check(hspf_run_device(ctx_, c.g->raw(), y.data(), (uint32_t)y.size(), c.run_flags, &yout), "hspf_run_device over the listed vertices");
+    return ydist;
+  }
+  // The node-protecting pair: the remote LFA (select, the rows of the listed PQ nodes, evaluate), then the two-segment repairs
+  // (select, the rows of the listed q's, evaluate with the nd_kind of the first); both read the space tables.
+  void node_steps(Chain &c, TilfaNode &t) {
+    const size_t n = c.n, S = c.S, SQ = S * t.max_pq, SP = S * t.max_pairs;
+    const std::vector<hspf_lfa_protect> p = c.protect();
+    DeviceBuffer qn(ctx_, SQ * 4), qv(ctx_, SQ * 4), qm(ctx_, SQ * 4), qc(ctx_, S * 4);
+    const hspf_rlfa_node_sel nsel{qn.as<uint32_t>(), qv.as<uint32_t>(), qm.as<uint32_t>(), qc.as<uint32_t>()};
+    rlfa_node_select_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), p, c.lfa_flags, c.sp_flags.as<uint8_t>(), t.max_pq, nsel);
+    t.nq_node = qn.to_host<uint32_t>(SQ); t.nq_via = qv.to_host<uint32_t>(SQ); t.nq_metric = qm.to_host<uint32_t>(SQ); t.nq_count = qc.to_host<uint32_t>(S);
+    const DeviceBuffer ydn = rows_of(c, t.nq_node, t.pq_roots);
+    DeviceBuffer dk(ctx_, n), dn(ctx_, n * 4), dv(ctx_, n * 4), dm(ctx_, n * 4), dc(ctx_, HSPF_NP_COVERAGE_WORDS * 4);
+    rlfa_node_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), p, ydn.as<uint32_t>(), t.pq_roots, nsel, t.max_pq, c.alt_flags.as<uint8_t>(),
+                     hspf_rlfa_node_out{dk.as<uint8_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(), dm.as<uint32_t>(), nullptr, dc.as<uint32_t>()});
+    t.nd_kind = dk.to_host<uint8_t>(n); t.nd_node = dn.to_host<uint32_t>(n); t.nd_via = dv.to_host<uint32_t>(n); t.nd_metric = dm.to_host<uint32_t>(n);
+    words_to_host(dc, t.nd_coverage);
+    DeviceBuffer tq(ctx_, SP * 4), tp(ctx_, SP * 4), tl(ctx_, SP * 4), tvi(ctx_, SP * 4), tme(ctx_, SP * 4), tc(ctx_, S * 4);
+    const hspf_tilfa_node_sel tsel{tq.as<uint32_t>(), tp.as<uint32_t>(), tl.as<uint32_t>(), tvi.as<uint32_t>(), tme.as<uint32_t>(), tc.as<uint32_t>()};
+    tilfa_node_select_device(*c.g, c.R, c.W, c.d(), c.f(), c.m(), p, c.lfa_flags, c.sp_flags.as<uint8_t>(), t.max_pairs, tsel);
+    t.tq_q = tq.to_host<uint32_t>(SP); t.tq_p = tp.to_host<uint32_t>(SP); t.tq_link = tl.to_host<uint32_t>(SP);
+    t.tq_via = tvi.to_host<uint32_t>(SP); t.tq_metric = tme.to_host<uint32_t>(SP); t.tq_count = tc.to_host<uint32_t>(S);
+    const DeviceBuffer ydq = rows_of(c, t.tq_q, t.y_roots);
+    DeviceBuffer ek(ctx_, n), ep(ctx_, n * 4), eq(ctx_, n * 4), el(ctx_, n * 4), ev(ctx_, n * 4), em(ctx_, n * 4), es(ctx_, n * 4), ec(ctx_, HSPF_TN_COVERAGE_WORDS * 4);
+    tilfa_node_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), p, ydq.as<uint32_t>(), t.y_roots, tsel, t.max_pairs, c.alt_flags.as<uint8_t>(), dk.as<uint8_t>(),
+                      hspf_tilfa_node_out{ek.as<uint8_t>(), ep.as<uint32_t>(), eq.as<uint32_t>(), el.as<uint32_t>(), ev.as<uint32_t>(), em.as<uint32_t>(),
+                                          es.as<uint32_t>(), ec.as<uint32_t>()});
+    t.tn_kind = ek.to_host<uint8_t>(n); t.tn_p = ep.to_host<uint32_t>(n); t.tn_q = eq.to_host<uint32_t>(n); t.tn_link = el.to_host<uint32_t>(n);
+    t.tn_via = ev.to_host<uint32_t>(n); t.tn_metric = em.to_host<uint32_t>(n); t.tn_set = es.to_host<uint32_t>(n);
+    words_to_host(ec, t.tn_coverage);
+  }
+  // The routes-and-backup step: hspf_routes_device for the root's row, hspf_routes_backup_device on it (with the repairs of the
+  // two-segment step where it ran), and behind them — with_ecmp — hspf_routes_backup_ecmp_device twice: the sizing call, the filling call.
+  void backup_step(Chain &c, BackupRoutes &b, const hspf_prefix_table &table) {
+    const size_t np = table.n_prefixes, nz = std::max<size_t>(np, 1), W = c.W;
+    const std::vector<hspf_lfa_protect> p = c.protect();
+    DeviceBuffer bm(ctx_, nz * 4), be(ctx_, nz * 4), nh(ctx_, nz * 8 * W), kk(ctx_, nz), pp(ctx_, nz * 4), ss(ctx_, nz * 4), mm(ctx_, nz * 4), ff(ctx_, nz),
+        cmk(ctx_, nz * 8 * W), nmk(ctx_, nz * 8 * W), cv(ctx_, HSPF_BK_COVERAGE_WORDS * 4);
+    hspf_routes ro{bm.as<uint32_t>(), be.as<uint32_t>(), nh.as<uint64_t>()};
+    check(hspf_routes_device(ctx_, c.n, 1, c.W, c.d(), c.f(), c.m(), &table, &ro), "hspf_routes_device");
+    hspf_prefix_table tr = table;
+    tr.flags |= HSPF_PFX_RESIDENT;                      // the arrays hspf_routes_device has just staged
+    const hspf_tilfa_out tio{c.ti_kind.as<uint8_t>(), nullptr, nullptr, c.ti_via.as<uint32_t>(), nullptr, c.ti_metric.as<uint32_t>(), nullptr, nullptr, nullptr};
+    const hspf_tilfa_out *ti = c.repairs ? &tio : nullptr;
+    routes_backup_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), p, c.lfa_flags, tr, ro, ti,
+                         hspf_backup_out{kk.as<uint8_t>(), pp.as<uint32_t>(), ss.as<uint32_t>(), mm.as<uint32_t>(), ff.as<uint8_t>(), cmk.as<uint64_t>(),
+                                         nmk.as<uint64_t>(), cv.as<uint32_t>()});
+    b.best_metric = bm.to_host<uint32_t>(np); b.best_entry = be.to_host<uint32_t>(np); b.nexthop_mask = nh.to_host<uint64_t>(np * W);
+    b.bk_kind = kk.to_host<uint8_t>(np); b.bk_primary = pp.to_host<uint32_t>(np); b.bk_slot = ss.to_host<uint32_t>(np);
+    b.bk_metric = mm.to_host<uint32_t>(np); b.bk_flags = ff.to_host<uint8_t>(np);
+    b.bk_cand_mask = cmk.to_host<uint64_t>(np * W); b.bk_node_mask = nmk.to_host<uint64_t>(np * W);
+    words_to_host(cv, b.bk_coverage);
+    if (!b.with_ecmp) return;
+    DeviceBuffer ptr(ctx_, (np + 1) * 4);
+    const uint64_t total = routes_backup_ecmp_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), p, c.lfa_flags, tr, ro, ti, 0,
+                                                     hspf_backup_ecmp_out{ptr.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+    if (total) {
+      const size_t t = (size_t)total;
+      DeviceBuffer pri(ctx_, t * 4), knd(ctx_, t), slot(ctx_, t * 4), met(ctx_, t * 4), efl(ctx_, t), cov(ctx_, HSPF_BK_ECMP_COVERAGE_WORDS * 4);
+      routes_backup_ecmp_device(c.n, c.R, c.W, c.d(), c.f(), c.m(), p, c.lfa_flags, tr, ro, ti, total,
+                                hspf_backup_ecmp_out{ptr.as<uint32_t>(), pri.as<uint32_t>(), knd.as<uint8_t>(), slot.as<uint32_t>(), met.as<uint32_t>(),
+                                                     efl.as<uint8_t>(), cov.as<uint32_t>()});
+      b.eb_primary = pri.to_host<uint32_t>(t); b.eb_kind = knd.to_host<uint8_t>(t); b.eb_slot = slot.to_host<uint32_t>(t);
+      b.eb_metric = met.to_host<uint32_t>(t); b.eb_flags = efl.to_host<uint8_t>(t);
+      words_to_host(cov, b.eb_coverage);
     }
-    DeviceBuffer kind(ctx_, ti ? S : 0), tv(ctx_, ti ? S * 4 : 0), tm(ctx_, ti ? S * 4 : 0);
-    if (ti) {
-      DeviceBuffer tp(ctx_, S * 4), tq(ctx_, S * 4), tl(ctx_, S * 4),
-          tc(ctx_, (size_t)S * 4 * HSPF_TILFA_COUNT_WORDS), dk(ctx_, n), dc(ctx_, HSPF_TILFA_COVERAGE_WORDS * 4);
-      tilfa_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), symmetric ? dist.as<uint32_t>() : rdist.as<uint32_t>(), {p},
-                   lfa_flags, fl.as<uint8_t>(), sp_flags.as<uint8_t>(), sp_via.as<uint32_t>(),
-                   hspf_tilfa_out{kind.as<uint8_t>(), tp.as<uint32_t>(), tq.as<uint32_t>(), tv.as<uint32_t>(), tl.as<uint32_t>(), tm.as<uint32_t>(),
-                                  tc.as<uint32_t>(), dk.as<uint8_t>(), dc.as<uint32_t>()});
-      ti->ti_kind = kind.to_host<uint8_t>(S); ti->ti_p = tp.to_host<uint32_t>(S); ti->ti_q = tq.to_host<uint32_t>(S);
-      ti->ti_via = tv.to_host<uint32_t>(S); ti->ti_link = tl.to_host<uint32_t>(S); ti->ti_metric = tm.to_host<uint32_t>(S);
-      ti->ti_counts = tc.to_host<uint32_t>((size_t)S * HSPF_TILFA_COUNT_WORDS); ti->td_kind = dk.to_host<uint8_t>(n);
-      const std::vector<uint32_t> c5 = dc.to_host<uint32_t>(HSPF_TILFA_COVERAGE_WORDS);
-      std::copy(c5.begin(), c5.end(), ti->td_coverage);
-    }
-    if (tn) {
-      // the ascending union of the vertices a select call listed, its rows (dist only) on the forward graph; one padding row keeps the
-      // arguments of the evaluate call valid where no list holds a vertex
-      auto rows_of = [&](const std::vector<uint32_t> &listed, std::vector<uint32_t> &y, DeviceBuffer &ydist) {
-        for (uint32_t v : listed) if (v != HSPF_NO_ROOT) y.push_back(v);
-        std::sort(y.begin(), y.end());
-        y.erase(std::unique(y.begin(), y.end()), y.end());
-        const bool none = y.empty();
-        if (none) y.push_back(HSPF_NO_ROOT);
-        ydist = DeviceBuffer(ctx_, y.size() * (size_t)n * 4);
-        if (none) return;
-        hspf_result yout{ydist.as<uint32_t>(), nullptr, nullptr, nullptr, 1, nullptr};
-        const int yrc = hspf_run_device(ctx_, g.raw(), y.data(), (uint32_t)y.size(), run_flags, &yout);
-        if (yrc != HSPF_OK) throw Error(yrc, std::string("hspf_run_device over the listed vertices (") + hspf_last_error(ctx_) + ")");
-      };
-      const size_t SQ = (size_t)S * tn->max_pq, SP = (size_t)S * tn->max_pairs;
-      DeviceBuffer qn(ctx_, SQ * 4), qv(ctx_, SQ * 4), qm(ctx_, SQ * 4), qc(ctx_, S * 4), ydn(ctx_, 0);
-      const hspf_rlfa_node_sel nsel{qn.as<uint32_t>(), qv.as<uint32_t>(), qm.as<uint32_t>(), qc.as<uint32_t>()};
-      rlfa_node_select_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, sp_flags.as<uint8_t>(), tn->max_pq, nsel);
-      tn->nq_node = qn.to_host<uint32_t>(SQ); tn->nq_via = qv.to_host<uint32_t>(SQ); tn->nq_metric = qm.to_host<uint32_t>(SQ);
-      tn->nq_count = qc.to_host<uint32_t>(S);
-      rows_of(tn->nq_node, tn->pq_roots, ydn);
-      DeviceBuffer dk(ctx_, n), dn(ctx_, (size_t)n * 4), dv(ctx_, (size_t)n * 4), dm(ctx_, (size_t)n * 4), dc(ctx_, HSPF_NP_COVERAGE_WORDS * 4);
-      rlfa_node_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, ydn.as<uint32_t>(), tn->pq_roots, nsel, tn->max_pq,
-                       fl.as<uint8_t>(), hspf_rlfa_node_out{dk.as<uint8_t>(), dn.as<uint32_t>(), dv.as<uint32_t>(), dm.as<uint32_t>(), nullptr, dc.as<uint32_t>()});
-      tn->nd_kind = dk.to_host<uint8_t>(n); tn->nd_node = dn.to_host<uint32_t>(n); tn->nd_via = dv.to_host<uint32_t>(n); tn->nd_metric = dm.to_host<uint32_t>(n);
-      const std::vector<uint32_t> c5 = dc.to_host<uint32_t>(HSPF_NP_COVERAGE_WORDS);
-      std::copy(c5.begin(), c5.end(), tn->nd_coverage);
-      DeviceBuffer tq(ctx_, SP * 4), tp(ctx_, SP * 4), tl(ctx_, SP * 4), tvi(ctx_, SP * 4), tme(ctx_, SP * 4), tc(ctx_, S * 4), ydq(ctx_, 0);
-      const hspf_tilfa_node_sel tsel{tq.as<uint32_t>(), tp.as<uint32_t>(), tl.as<uint32_t>(), tvi.as<uint32_t>(), tme.as<uint32_t>(), tc.as<uint32_t>()};
-      tilfa_node_select_device(g, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, sp_flags.as<uint8_t>(), tn->max_pairs, tsel);
-      tn->tq_q = tq.to_host<uint32_t>(SP); tn->tq_p = tp.to_host<uint32_t>(SP); tn->tq_link = tl.to_host<uint32_t>(SP);
-      tn->tq_via = tvi.to_host<uint32_t>(SP); tn->tq_metric = tme.to_host<uint32_t>(SP); tn->tq_count = tc.to_host<uint32_t>(S);
-      rows_of(tn->tq_q, tn->y_roots, ydq);
-      DeviceBuffer ek(ctx_, n), ep(ctx_, (size_t)n * 4), eq(ctx_, (size_t)n * 4), el(ctx_, (size_t)n * 4), ev(ctx_, (size_t)n * 4), em(ctx_, (size_t)n * 4),
-          es(ctx_, (size_t)n * 4), ec(ctx_, HSPF_TN_COVERAGE_WORDS * 4);
-      tilfa_node_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, ydq.as<uint32_t>(), tn->y_roots, tsel, tn->max_pairs,
-                        fl.as<uint8_t>(), dk.as<uint8_t>(),
-                        hspf_tilfa_node_out{ek.as<uint8_t>(), ep.as<uint32_t>(), eq.as<uint32_t>(), el.as<uint32_t>(), ev.as<uint32_t>(), em.as<uint32_t>(),
-                                            es.as<uint32_t>(), ec.as<uint32_t>()});
-      tn->tn_kind = ek.to_host<uint8_t>(n); tn->tn_p = ep.to_host<uint32_t>(n); tn->tn_q = eq.to_host<uint32_t>(n); tn->tn_link = el.to_host<uint32_t>(n);
-      tn->tn_via = ev.to_host<uint32_t>(n); tn->tn_metric = em.to_host<uint32_t>(n); tn->tn_set = es.to_host<uint32_t>(n);
-      const std::vector<uint32_t> c6 = ec.to_host<uint32_t>(HSPF_TN_COVERAGE_WORDS);
-      std::copy(c6.begin(), c6.end(), tn->tn_coverage);
-    }
-    if (bk) {
-      const size_t np = table->n_prefixes, nz = std::max<size_t>(np, 1);
-      DeviceBuffer bm(ctx_, nz * 4), be(ctx_, nz * 4), nh(ctx_, nz * 8 * W), kk(ctx_, nz), pp(ctx_, nz * 4), ss(ctx_, nz * 4), mm(ctx_, nz * 4), ff(ctx_, nz),
-          cmk(ctx_, nz * 8 * W), nmk(ctx_, nz * 8 * W), cv7(ctx_, HSPF_BK_COVERAGE_WORDS * 4);
-      hspf_routes ro{bm.as<uint32_t>(), be.as<uint32_t>(), nh.as<uint64_t>()};
-      rc = hspf_routes_device(ctx_, n, 1, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), table, &ro);
-      if (rc != HSPF_OK) throw Error(rc, std::string("hspf_routes_device (") + hspf_last_error(ctx_) + ")");
-      hspf_prefix_table tr = *table;
-      tr.flags |= HSPF_PFX_RESIDENT;                      // the arrays hspf_routes_device has just staged
-      const hspf_tilfa_out tio{kind.as<uint8_t>(), nullptr, nullptr, tv.as<uint32_t>(), nullptr, tm.as<uint32_t>(), nullptr, nullptr, nullptr};
-      routes_backup_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, tr, ro, ti ? &tio : nullptr,
-                           hspf_backup_out{kk.as<uint8_t>(), pp.as<uint32_t>(), ss.as<uint32_t>(), mm.as<uint32_t>(), ff.as<uint8_t>(), cmk.as<uint64_t>(),
-                                           nmk.as<uint64_t>(), cv7.as<uint32_t>()});
-      bk->best_metric = bm.to_host<uint32_t>(np); bk->best_entry = be.to_host<uint32_t>(np); bk->nexthop_mask = nh.to_host<uint64_t>(np * W);
-      bk->bk_kind = kk.to_host<uint8_t>(np); bk->bk_primary = pp.to_host<uint32_t>(np); bk->bk_slot = ss.to_host<uint32_t>(np);
-      bk->bk_metric = mm.to_host<uint32_t>(np); bk->bk_flags = ff.to_host<uint8_t>(np);
-      bk->bk_cand_mask = cmk.to_host<uint64_t>(np * W); bk->bk_node_mask = nmk.to_host<uint64_t>(np * W);
-      const std::vector<uint32_t> c7 = cv7.to_host<uint32_t>(HSPF_BK_COVERAGE_WORDS);
-      std::copy(c7.begin(), c7.end(), bk->bk_coverage);
-      if (bk->with_ecmp) {
-        DeviceBuffer ptr(ctx_, (np + 1) * 4);
-        const uint64_t total = routes_backup_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, tr, ro,
-                                                         ti ? &tio : nullptr, 0, hspf_backup_ecmp_out{ptr.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
-        if (total) {
-          const size_t t = (size_t)total;
-          DeviceBuffer pri(ctx_, t * 4), knd(ctx_, t), slot(ctx_, t * 4), met(ctx_, t * 4), efl(ctx_, t), cov(ctx_, HSPF_BK_ECMP_COVERAGE_WORDS * 4);
-          routes_backup_ecmp_device(n, R, W, dist.as<uint32_t>(), flags.as<uint16_t>(), mask.as<uint64_t>(), {p}, lfa_flags, tr, ro, ti ? &tio : nullptr, total,
-                                    hspf_backup_ecmp_out{ptr.as<uint32_t>(), pri.as<uint32_t>(), knd.as<uint8_t>(), slot.as<uint32_t>(), met.as<uint32_t>(),
-                                                         efl.as<uint8_t>(), cov.as<uint32_t>()});
-          bk->eb_primary = pri.to_host<uint32_t>(t); bk->eb_kind = knd.to_host<uint8_t>(t); bk->eb_slot = slot.to_host<uint32_t>(t);
-          bk->eb_metric = met.to_host<uint32_t>(t); bk->eb_flags = efl.to_host<uint8_t>(t);
-          const std::vector<uint32_t> c8 = cov.to_host<uint32_t>(HSPF_BK_ECMP_COVERAGE_WORDS);
-          std::copy(c8.begin(), c8.end(), bk->eb_coverage);
-        }
-        bk->eb_ptr = ptr.to_host<uint32_t>(np + 1);
-      }
-    }
-    return r;
+    b.eb_ptr = ptr.to_host<uint32_t>(np + 1);
   }
   std::shared_ptr<CtxHolder> holder_;
   hspf_ctx *ctx_ = nullptr;

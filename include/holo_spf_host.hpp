@@ -776,6 +776,40 @@ class HipPool {
  private:
   std::map<size_t, std::vector<void *>> dev_, pin_;
 };
+// One device request from the pool, handed back when the scope ends — the way out an exception takes included.
+class HipLease {
+ public:
+  HipLease(HipPool &pool, size_t bytes, bool wanted = true) : pool_(pool), bytes_(bytes), p_(wanted ? pool.dev(bytes) : nullptr) {}
+  HipLease(const HipLease &) = delete;
+  HipLease &operator=(const HipLease &) = delete;
+  ~HipLease() { pool_.dev_free(p_, bytes_); }
+  template <typename T> T *as() const { return static_cast<T *>(p_); }
+ private:
+  HipPool &pool_;
+  size_t bytes_;
+  void *p_;
+};
+// A cursor over one device block: arrays in the order they are asked for (64-bit arrays first, then words, then bytes: every
+// array stays aligned), host vectors copied in and out, and in `ok` whether every copy went through (after the first that did
+// not, the rest are skipped).  Without a block it is the copies and their flag alone.
+class DevCursor {
+ public:
+  DevCursor() = default;
+  explicit DevCursor(const HipLease &block) : at_(block.as<uint8_t>()) {}
+  explicit DevCursor(void *block) : at_(static_cast<uint8_t *>(block)) {}
+  template <typename T> T *take(size_t count) { T *p = reinterpret_cast<T *>(at_); at_ += count * sizeof(T); return p; }
+  template <typename T> void upload(T *dst, const std::vector<T> &src) {
+    ok = ok && (src.empty() || hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
+  }
+  template <typename T> T *put(const std::vector<T> &src) { T *dst = take<T>(src.size()); upload(dst, src); return dst; }
+  template <typename T> void fetch(std::vector<T> &vec, const T *src, size_t count) {
+    vec.resize(count);
+    ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess);
+  }
+  bool ok = true;
+ private:
+  uint8_t *at_ = nullptr;
+};
 class HipDeviceRun : public DeviceRun {             // dist / hops / flags / masks of one run in device buffers of the engine's pool
  public:
   explicit HipDeviceRun(std::shared_ptr<HipPool> pool) : pool_(std::move(pool)) {}
@@ -997,9 +1031,7 @@ class HipEngine : public Engine {
     if (P == 0) return o;
     uint32_t *bm = (uint32_t *)pool_->dev(rp * 4), *be = (uint32_t *)pool_->dev(rp * 4);
     uint64_t *nm = (uint64_t *)pool_->dev(rp * 8 * r.mask_words);
-    static const uint32_t zero = 0;
-    hspf_prefix_table tab{P, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
-                          pfx_metric.empty() ? &zero : pfx_metric.data(), flags};
+    const hspf_prefix_table tab = prefix_table(pfx_ptr, pfx_vertex, pfx_metric, flags);
     hspf_routes ro{bm, be, nm};
     const int rc = hspf_routes_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, &tab, &ro);
     bool ok = rc == HSPF_OK && hipMemcpy(o.best_metric.data(), bm, rp * 4, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -1016,9 +1048,7 @@ class HipEngine : public Engine {
     o->n_roots = r.n_roots; o->n_prefixes = (uint32_t)pfx_ptr.size() - 1; o->mask_words = r.mask_words;
     if (!o->alloc()) throw std::runtime_error("hipMalloc of the route tables failed");
     if (o->n_prefixes == 0) return o;
-    static const uint32_t zero = 0;
-    hspf_prefix_table tab{o->n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
-                          pfx_metric.empty() ? &zero : pfx_metric.data(), flags};
+    const hspf_prefix_table tab = prefix_table(pfx_ptr, pfx_vertex, pfx_metric, flags);
     hspf_routes ro = o->raw();
     const int rc = hspf_routes_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, &tab, &ro);
     if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_routes_device: ") + hspf_last_error(ctx_));
@@ -1050,10 +1080,7 @@ class HipEngine : public Engine {
     auto &o = static_cast<HipDeviceRoutes &>(rib_set);
     auto &r = static_cast<HipDeviceRun &>(run);
     if (pfx_ptr.size() <= 1) return;
-    static const uint32_t zero = 0;
-    hspf_prefix_table tab{(uint32_t)pfx_ptr.size() - 1, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
-                          pfx_metric.empty() ? &zero : pfx_metric.data(), HSPF_PFX_SATURATING | HSPF_PFX_ORDERED, pfx_origin.empty() ? &zero : pfx_origin.data(),
-                          nullptr, nullptr, nullptr};
+    const hspf_prefix_table tab = prefix_table(pfx_ptr, pfx_vertex, pfx_metric, HSPF_PFX_SATURATING | HSPF_PFX_ORDERED, &pfx_origin);
     const hspf_rib_device rib{o.n_prefixes, o.mask_words, o.bm, o.be, o.nm, o.org};
     const int rc = hspf_rib_fold_device(ctx_, r.n_vertices, r.mask_words, r.dist, r.flags, r.mask, &tab, prefix_map.data(), area_index, word_offset, &rib);
     if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_rib_fold_device: ") + hspf_last_error(ctx_));
@@ -1074,8 +1101,9 @@ class HipEngine : public Engine {
       if (hipMalloc(&diff_, need) != hipSuccess) throw std::runtime_error("hipMalloc of the diff scratch failed");
       diff_cap_ = need;
     }
-    uint32_t *changed = (uint32_t *)diff_, *cptr = changed + rp;
-    uint8_t *action = (uint8_t *)(cptr + b.n_roots + 1);
+    DevCursor c(diff_);
+    uint32_t *changed = c.take<uint32_t>(rp), *cptr = c.take<uint32_t>((size_t)b.n_roots + 1);
+    uint8_t *action = c.take<uint8_t>(rp);
     hspf_routes ro = a.raw(), rn = b.raw();
     int rc = hspf_routes_diff_device(ctx_, b.n_roots, b.n_prefixes, b.mask_words, &ro, &rn, action, changed, cptr);
     if (rc != HSPF_OK) throw std::runtime_error(std::string("hspf_routes_diff_device: ") + hspf_last_error(ctx_));
@@ -1090,57 +1118,142 @@ class HipEngine : public Engine {
     }
     return out;
   }
-  LfaOut lfa(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, bool with_masks) override {
-    return lfa_with(run, protect, nullptr, nullptr, lfa_flags, with_masks);
-  }
-  // two calls: ea_ptr and the total, then the entries into arrays of that size
-  LfaEcmpOut lfa_ecmp(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags) override {
-    auto &r = static_cast<HipDeviceRun &>(run);
-    LfaEcmpOut o;
+ private:
+  // ---- what the fast-reroute calls below share ---------------------------------------------------------------------------
+  [[noreturn]] void fail(const char *what) const { throw std::runtime_error(std::string(what) + hspf_last_error(ctx_)); }
+  // the head of a result: per protected root over the vertices of a run, or over the prefixes of a routes set
+  template <typename Out> static Out head(const std::vector<LfaProtect> &protect, const HipDeviceRun &r) {
+    Out o;
     o.supported = true;
     o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices;
-    if (protect.empty()) return o;
-    std::vector<hspf_lfa_protect> ps;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("lfa_ecmp: the slot arrays of a protected root differ in length");
-      ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
-    const size_t pb = ((size_t)o.n_protected * o.n_vertices + 1) * 4, cb = (size_t)o.n_protected * HSPF_LFA_ECMP_COVERAGE_WORDS * 4;
-    uint32_t *ptr = (uint32_t *)pool_->dev(pb);
-    hspf_lfa_ecmp_out out{ptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t total = 0;
-    int rc = hspf_lfa_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, 0, &out, &total);
-    const size_t t = (size_t)total;
-    o.ea_ptr.resize(pb / 4); o.ea_primary.resize(t); o.ea_slot.resize(t); o.ea_metric.resize(t); o.ea_flags.resize(t);
-    o.ea_coverage.assign(cb / 4, 0u);
-    bool ok = rc == HSPF_OK;
-    if (ok && t) {
-      uint32_t *pri = (uint32_t *)pool_->dev(t * 4), *slot = (uint32_t *)pool_->dev(t * 4), *met = (uint32_t *)pool_->dev(t * 4), *cov = (uint32_t *)pool_->dev(cb);
-      uint8_t *fl = (uint8_t *)pool_->dev(t);
-      out = hspf_lfa_ecmp_out{ptr, pri, slot, met, fl, cov};
-      rc = hspf_lfa_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, total, &out, &total);
-      ok = rc == HSPF_OK && hipMemcpy(o.ea_primary.data(), pri, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.ea_slot.data(), slot, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.ea_metric.data(), met, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.ea_flags.data(), fl, t, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.ea_coverage.data(), cov, cb, hipMemcpyDeviceToHost) == hipSuccess;
-      pool_->dev_free(pri, t * 4); pool_->dev_free(slot, t * 4); pool_->dev_free(met, t * 4); pool_->dev_free(cov, cb); pool_->dev_free(fl, t);
-    }
-    ok = ok && hipMemcpy(o.ea_ptr.data(), ptr, pb, hipMemcpyDeviceToHost) == hipSuccess;
-    pool_->dev_free(ptr, pb);
-    if (!ok) throw std::runtime_error(std::string("hspf_lfa_ecmp_device: ") + hspf_last_error(ctx_));
     return o;
   }
-  // (backup_routes / backup_routes_lan stay the base's "not supported": a DeviceRoutes does not keep its prefix table, which
-  // hspf_routes_backup_device needs; hspf::Engine::routes_backup_device / routes_backup_lan_device take it explicitly.)
-  LfaOut lfa_lan(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans, uint32_t lfa_flags, bool with_masks) override {
-    if (lans.size() != protect.size()) throw std::runtime_error("lfa_lan: one LfaLan per protected root");
-    return lfa_with(run, protect, &lans, nullptr, lfa_flags, with_masks);
+  template <typename Out> static Out head(const std::vector<LfaProtect> &protect, const HipDeviceRoutes &rt) {
+    Out o;
+    o.supported = true;
+    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes;
+    return o;
   }
-  LfaOut lfa_srlg(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<Srlg> &srlgs, uint32_t lfa_flags, bool with_masks) override {
-    return lfa_with(run, protect, nullptr, &srlgs, lfa_flags, with_masks);
+  static void same_shape(const std::string &who, const HipDeviceRun &r, const HipDeviceRun &rr) {
+    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error(who + "the two runs differ in shape");
   }
+  static void routes_of_run(const std::string &who, const HipDeviceRun &r, const HipDeviceRoutes &rt, const std::vector<uint32_t> &pfx_ptr,
+                            const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric) {
+    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
+      throw std::runtime_error(who + "the routes are not of this run and prefix table");
+  }
+  // the hspf_lfa_protect / hspf_lfa_lan array of a call (and srlg_raw, below: the hspf_srlg array), the lengths held to the slot
+  // arrays; lans: one per protected root, which the caller has checked
+  static std::vector<hspf_lfa_protect> protect_raw(const std::string &who, const std::vector<LfaProtect> &protect) {
+    std::vector<hspf_lfa_protect> out;
+    for (const LfaProtect &p : protect) {
+      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
+        throw std::runtime_error(who + "the slot arrays of a protected root differ in length");
+      out.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
+    }
+    return out;
+  }
+  static std::vector<hspf_lfa_lan> lan_raw(const std::string &who, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans) {
+    std::vector<hspf_lfa_lan> out;
+    for (size_t i = 0; i < lans.size(); ++i) {
+      const LfaLan &l = lans[i];
+      if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error(who + "lan / lan_row differ in length from the slot arrays");
+      out.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
+    }
+    return out;
+  }
+  // a prefix table from the caller's vectors; an empty one is stood in for by one zero, the C call wants non-NULL pointers
+  static hspf_prefix_table prefix_table(const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric,
+                                        uint32_t flags, const std::vector<uint32_t> *pfx_origin = nullptr) {
+    static const uint32_t zero = 0;
+    auto data = [](const std::vector<uint32_t> &v) { return v.empty() ? &zero : v.data(); };
+    return hspf_prefix_table{(uint32_t)pfx_ptr.size() - 1, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), data(pfx_vertex), data(pfx_metric), flags,
+                             pfx_origin ? data(*pfx_origin) : nullptr, nullptr, nullptr, nullptr};
+  }
+  // ... given AGAIN to a backup call, which reads the advertisers from it: nothing of it is resident for that call
+  static hspf_prefix_table given_table(const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric,
+                                       uint32_t table_flags) {
+    return prefix_table(pfx_ptr, pfx_vertex, pfx_metric, table_flags & ~HSPF_PFX_RESIDENT);
+  }
+  // the alt_flags of lfa() for the same protect list, where given: pn bytes at the end of the call's block
+  static bool has_alt(const LfaOut *lfa, size_t pn) { return lfa && lfa->supported && lfa->alt_flags.size() == pn; }
+  static uint8_t *put_alt(DevCursor &c, const LfaOut *lfa, size_t pn) { return has_alt(lfa, pn) ? c.put(lfa->alt_flags) : nullptr; }
+  // the per-slot repairs of tilfa() a backup call falls back on (with_links: ti_p and ti_link are read too), where given — those
+  // of another protect list are an error: 9 bytes per slot of the call's block, 17 with the links, ti_kind behind the words
+  static bool has_tilfa(const std::string &who, const TilfaOut *t, size_t ps, bool with_links) {
+    if (!t || !t->supported) return false;
+    if (t->ti_kind.size() != ps || t->ti_via.size() != ps || t->ti_metric.size() != ps || (with_links && (t->ti_p.size() != ps || t->ti_link.size() != ps)))
+      throw std::runtime_error(who + "the TI-LFA result is not of this protect list");
+    return true;
+  }
+  static hspf_tilfa_out put_tilfa(DevCursor &c, const TilfaOut &t, bool with_links) {
+    hspf_tilfa_out ti{};
+    ti.ti_via = c.put(t.ti_via); ti.ti_metric = c.put(t.ti_metric);
+    if (with_links) { ti.ti_p = c.put(t.ti_p); ti.ti_link = c.put(t.ti_link); }
+    ti.ti_kind = c.put(t.ti_kind);
+    return ti;
+  }
+  // the rows a node-protecting call reads: the ascending union of the vertices the lists name — where they name none, one padding
+  // row keeps the arguments of that call valid (true: it is padding) — and their dist on the forward graph
+  static bool y_union(std::vector<uint32_t> &y, const std::vector<uint32_t> *a, const std::vector<uint32_t> *b = nullptr) {
+    for (const std::vector<uint32_t> *l : {a, b})
+      if (l) for (uint32_t v : *l) if (v != HSPF_NO_ROOT) y.push_back(v);
+    std::sort(y.begin(), y.end());
+    y.erase(std::unique(y.begin(), y.end()), y.end());
+    const bool none = y.empty();
+    if (none) y.push_back(HSPF_NO_ROOT);
+    return none;
+  }
+  void y_run(Graph &gr, const std::vector<uint32_t> &y, bool none, uint32_t run_flags, uint32_t *ydist, const char *what) {
+    if (none) return;
+    hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
+    if (hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, y.data(), (uint32_t)y.size(), run_flags, &yres) != HSPF_OK) fail(what);
+  }
+  // the frame of rlfa() (lans == srlgs == nullptr: hspf_rlfa_device), rlfa_lan() (hspf_rlfa_lan_device) and rlfa_srlg()
+  // (hspf_rlfa_srlg_device)
+  RlfaOut rlfa_with(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans,
+                    const std::vector<Srlg> *srlgs, uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) {
+    const uint32_t nw = lans ? HSPF_RLFA_LAN_COUNT_WORDS : srlgs ? HSPF_RLFA_SRLG_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS;
+    const uint32_t cw = lans ? HSPF_RLFA_LAN_COVERAGE_WORDS : srlgs ? HSPF_RLFA_SRLG_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
+    const char *fn = lans ? "hspf_rlfa_lan_device: " : srlgs ? "hspf_rlfa_srlg_device: " : "hspf_rlfa_device: ";
+    const std::string who = lans ? "rlfa_lan: " : srlgs ? "rlfa_srlg: " : "rlfa: ";
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rr = static_cast<HipDeviceRun &>(reverse_run);
+    same_shape(who, r, rr);
+    RlfaOut o = head<RlfaOut>(protect, r);
+    o.slot_stride = 64u * r.mask_words;
+    if (protect.empty()) return o;
+    const std::vector<hspf_lfa_protect> pr = protect_raw(who, protect);
+    std::vector<hspf_lfa_lan> ls;
+    if (lans) ls = lan_raw(who, protect, *lans);
+    std::vector<hspf_srlg> ss;
+    if (srlgs) ss = srlg_raw(who, protect, *srlgs);
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = with_spaces ? ps * o.n_vertices : 0;
+    const size_t cb = (size_t)o.n_protected * cw;
+    // one block: pq_node | pq_via | pq_metric | pq_counts | rl_node | rl_via | rl_coverage | space_via | space_flags | alt_flags
+    HipLease blk(*pool_, (ps * (3 + nw) + pn * 2 + cb + sp) * 4 + sp + (has_alt(lfa, pn) ? pn : 0));
+    DevCursor c(blk);
+    hspf_rlfa_out out{};
+    out.pq_node = c.take<uint32_t>(ps); out.pq_via = c.take<uint32_t>(ps); out.pq_metric = c.take<uint32_t>(ps); out.pq_counts = c.take<uint32_t>(ps * nw);
+    out.rl_node = c.take<uint32_t>(pn); out.rl_via = c.take<uint32_t>(pn); out.rl_coverage = c.take<uint32_t>(cb);
+    if (with_spaces) { out.space_via = c.take<uint32_t>(sp); out.space_flags = c.take<uint8_t>(sp); }
+    const uint8_t *alt = put_alt(c, lfa, pn);
+    hspf_graph *g = static_cast<HipGraph &>(gr).g;
+    const int rc = !c.ok ? HSPF_E_HIP
+                 : lans ? hspf_rlfa_lan_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(), ls.data(),
+                                               o.n_protected, lfa_flags, alt, &out)
+                 : srlgs ? hspf_rlfa_srlg_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(), ss.data(),
+                                                 o.n_protected, lfa_flags, alt, &out)
+                        : hspf_rlfa_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(), o.n_protected,
+                                           lfa_flags, alt, &out);
+    if (rc != HSPF_OK) fail(fn);
+    c.fetch(o.pq_node, out.pq_node, ps); c.fetch(o.pq_via, out.pq_via, ps); c.fetch(o.pq_metric, out.pq_metric, ps); c.fetch(o.pq_counts, out.pq_counts, ps * nw);
+    c.fetch(o.rl_node, out.rl_node, pn); c.fetch(o.rl_via, out.rl_via, pn); c.fetch(o.rl_coverage, out.rl_coverage, cb);
+    if (with_spaces) { c.fetch(o.space_via, out.space_via, sp); c.fetch(o.space_flags, out.space_flags, sp); }
+    if (!c.ok) fail(fn);
+    return o;
+  }
+ public:
   // the hspf_srlg array of an SRLG call, its lengths held to the slot arrays
   static std::vector<hspf_srlg> srlg_raw(const std::string &who, const std::vector<LfaProtect> &protect, const std::vector<Srlg> &srlgs) {
     if (srlgs.size() != protect.size()) throw std::runtime_error(who + "one Srlg per protected root");
@@ -1155,50 +1268,126 @@ class HipEngine : public Engine {
     }
     return out;
   }
-  // the frame of lfa() (lans == srlgs == nullptr: hspf_lfa_device), lfa_lan() (hspf_lfa_lan_device) and lfa_srlg() (hspf_lfa_srlg_device)
+  // the frame of lfa() (lans == srlgs == nullptr: hspf_lfa_device), lfa_lan() (hspf_lfa_lan_device) and lfa_srlg() (hspf_lfa_srlg_device);
+  // one pool request per array
   LfaOut lfa_with(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans, const std::vector<Srlg> *srlgs,
                   uint32_t lfa_flags, bool with_masks) {
     auto &r = static_cast<HipDeviceRun &>(run);
     const uint32_t cw = lans ? HSPF_LFA_LAN_COVERAGE_WORDS : srlgs ? HSPF_LFA_SRLG_COVERAGE_WORDS : HSPF_LFA_COVERAGE_WORDS;
     const char *fn = lans ? "hspf_lfa_lan_device: " : srlgs ? "hspf_lfa_srlg_device: " : "hspf_lfa_device: ";
-    LfaOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.mask_words = r.mask_words;
+    LfaOut o = head<LfaOut>(protect, r);
+    o.mask_words = r.mask_words;
     if (protect.empty()) return o;
-    std::vector<hspf_lfa_protect> ps;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("lfa: the slot arrays of a protected root differ in length");
-      ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
+    const std::vector<hspf_lfa_protect> ps = protect_raw("lfa: ", protect);
     std::vector<hspf_lfa_lan> ls;
-    for (size_t i = 0; lans && i < lans->size(); ++i) {
-      const LfaLan &l = (*lans)[i];
-      if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error("lfa_lan: lan / lan_row differ in length from the slot arrays");
-      ls.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
-    }
+    if (lans) ls = lan_raw("lfa_lan: ", protect, *lans);
     std::vector<hspf_srlg> ss;
     if (srlgs) ss = srlg_raw("lfa_srlg: ", protect, *srlgs);
-    const size_t pn = (size_t)o.n_protected * o.n_vertices, mb = with_masks ? pn * 8 * o.mask_words : 0, cb = (size_t)o.n_protected * cw * 4;
-    uint32_t *slot = (uint32_t *)pool_->dev(pn * 4), *met = (uint32_t *)pool_->dev(pn * 4), *cov = (uint32_t *)pool_->dev(cb);
-    uint8_t *fl = (uint8_t *)pool_->dev(pn);
-    uint64_t *cm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr, *nm = with_masks ? (uint64_t *)pool_->dev(mb) : nullptr;
-    hspf_lfa_out out{slot, met, fl, cm, nm, cov};
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, pw = pn * o.mask_words, cb = (size_t)o.n_protected * cw;
+    HipLease slot(*pool_, pn * 4), met(*pool_, pn * 4), cov(*pool_, cb * 4), fl(*pool_, pn), cm(*pool_, pw * 8, with_masks), nm(*pool_, pw * 8, with_masks);
+    hspf_lfa_out out{slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), cm.as<uint64_t>(), nm.as<uint64_t>(), cov.as<uint32_t>()};
     const int rc = lans ? hspf_lfa_lan_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), ls.data(), o.n_protected, lfa_flags, &out)
                  : srlgs ? hspf_lfa_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), ss.data(), o.n_protected, lfa_flags, &out)
                         : hspf_lfa_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, &out);
-    o.alt_slot.resize(pn); o.alt_metric.resize(pn); o.alt_flags.resize(pn); o.coverage.resize((size_t)o.n_protected * cw);
-    if (with_masks) { o.cand_mask.resize(pn * o.mask_words); o.node_mask.resize(pn * o.mask_words); }
-    const bool ok = rc == HSPF_OK && hipMemcpy(o.alt_slot.data(), slot, pn * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(o.alt_metric.data(), met, pn * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(o.alt_flags.data(), fl, pn, hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(o.coverage.data(), cov, cb, hipMemcpyDeviceToHost) == hipSuccess &&
-                    (!with_masks || (hipMemcpy(o.cand_mask.data(), cm, mb, hipMemcpyDeviceToHost) == hipSuccess &&
-                                     hipMemcpy(o.node_mask.data(), nm, mb, hipMemcpyDeviceToHost) == hipSuccess));
-    pool_->dev_free(slot, pn * 4); pool_->dev_free(met, pn * 4); pool_->dev_free(cov, cb); pool_->dev_free(fl, pn);
-    if (with_masks) { pool_->dev_free(cm, mb); pool_->dev_free(nm, mb); }
-    if (!ok) throw std::runtime_error(std::string(fn) + hspf_last_error(ctx_));
+    if (rc != HSPF_OK) fail(fn);
+    DevCursor c;
+    c.fetch(o.alt_slot, out.alt_slot, pn); c.fetch(o.alt_metric, out.alt_metric, pn); c.fetch(o.alt_flags, out.alt_flags, pn); c.fetch(o.coverage, out.coverage, cb);
+    if (with_masks) { c.fetch(o.cand_mask, out.cand_mask, pw); c.fetch(o.node_mask, out.node_mask, pw); }
+    if (!c.ok) fail(fn);
     return o;
+  }
+  // the frame of backup_routes_ecmp() (srlgs nullptr) and backup_routes_ecmp_srlg().  Two calls: eb_ptr and the total, then the
+  // entries into arrays of that size
+  BackupEcmpOut backup_routes_ecmp_with(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
+                                        const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
+                                        const std::vector<Srlg> *srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    auto &rt = static_cast<HipDeviceRoutes &>(routes);
+    BackupEcmpOut o = head<BackupEcmpOut>(protect, rt);
+    if (protect.empty()) return o;
+    routes_of_run("backup_routes_ecmp: ", r, rt, pfx_ptr, pfx_vertex, pfx_metric);
+    const std::vector<hspf_lfa_protect> pr = protect_raw("backup_routes_ecmp: ", protect);
+    std::vector<hspf_srlg> ss;
+    if (srlgs) ss = srlg_raw("backup_routes_ecmp_srlg: ", protect, *srlgs);
+    const size_t ps = (size_t)o.n_protected * 64u * r.mask_words;
+    const bool with_links = srlgs != nullptr, with_ti = has_tilfa("backup_routes_ecmp: ", tilfa, ps, with_links);
+    const size_t pb = (size_t)o.n_protected * o.n_prefixes + 1;
+    const size_t cb = (size_t)o.n_protected * (srlgs ? HSPF_BK_ECMP_SRLG_COVERAGE_WORDS : HSPF_BK_ECMP_COVERAGE_WORDS);
+    // one block: eb_ptr | eb_coverage | ti_via | ti_metric | (with groups: ti_p | ti_link |) ti_kind
+    HipLease blk(*pool_, (pb + cb) * 4 + (with_ti ? ps * (with_links ? 17 : 9) : 0));
+    DevCursor c(blk);
+    hspf_backup_ecmp_out out{};
+    out.eb_ptr = c.take<uint32_t>(pb);
+    uint32_t *cov = c.take<uint32_t>(cb);
+    hspf_tilfa_out ti{};
+    if (with_ti) ti = put_tilfa(c, *tilfa, with_links);
+    if (!c.ok) fail("hipMemcpy of the repairs: ");
+    const char *what = srlgs ? "hspf_routes_backup_ecmp_srlg_device: " : "hspf_routes_backup_ecmp_device: ";
+    const hspf_prefix_table tab = given_table(pfx_ptr, pfx_vertex, pfx_metric, table_flags);
+    const hspf_routes ro = rt.raw();
+    uint64_t total = 0;
+    auto call = [&](uint64_t cap) {
+      const int rc = srlgs ? hspf_routes_backup_ecmp_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), ss.data(), o.n_protected,
+                                                                 lfa_flags, &tab, &ro, with_ti ? &ti : nullptr, cap, &out, &total)
+                           : hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab,
+                                                            &ro, with_ti ? &ti : nullptr, cap, &out, &total);
+      if (rc != HSPF_OK) fail(what);
+    };
+    call(0);
+    const size_t t = (size_t)total;
+    o.eb_coverage.assign(cb, 0u);
+    if (t) {
+      // the entries: eb_primary | eb_slot | eb_metric | eb_kind | eb_flags
+      HipLease ent(*pool_, t * 14);
+      DevCursor e(ent);
+      out.eb_primary = e.take<uint32_t>(t); out.eb_slot = e.take<uint32_t>(t); out.eb_metric = e.take<uint32_t>(t); out.eb_kind = e.take<uint8_t>(t);
+      out.eb_flags = e.take<uint8_t>(t); out.eb_coverage = cov;
+      call(total);
+      c.fetch(o.eb_primary, out.eb_primary, t); c.fetch(o.eb_slot, out.eb_slot, t); c.fetch(o.eb_metric, out.eb_metric, t); c.fetch(o.eb_kind, out.eb_kind, t);
+      c.fetch(o.eb_flags, out.eb_flags, t); c.fetch(o.eb_coverage, out.eb_coverage, cb);
+    }
+    c.fetch(o.eb_ptr, out.eb_ptr, pb);
+    if (!c.ok) fail(what);
+    return o;
+  }
+  LfaOut lfa(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, bool with_masks) override {
+    return lfa_with(run, protect, nullptr, nullptr, lfa_flags, with_masks);
+  }
+  // two calls: ea_ptr and the total, then the entries into arrays of that size; one pool request per array
+  LfaEcmpOut lfa_ecmp(DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags) override {
+    auto &r = static_cast<HipDeviceRun &>(run);
+    LfaEcmpOut o = head<LfaEcmpOut>(protect, r);
+    if (protect.empty()) return o;
+    const std::vector<hspf_lfa_protect> ps = protect_raw("lfa_ecmp: ", protect);
+    const size_t pb = (size_t)o.n_protected * o.n_vertices + 1, cb = (size_t)o.n_protected * HSPF_LFA_ECMP_COVERAGE_WORDS;
+    const char *what = "hspf_lfa_ecmp_device: ";
+    HipLease ptr(*pool_, pb * 4);
+    hspf_lfa_ecmp_out out{ptr.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t total = 0;
+    if (hspf_lfa_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, 0, &out, &total) != HSPF_OK) fail(what);
+    const size_t t = (size_t)total;
+    DevCursor c;
+    o.ea_coverage.assign(cb, 0u);
+    if (t) {
+      HipLease pri(*pool_, t * 4), slot(*pool_, t * 4), met(*pool_, t * 4), cov(*pool_, cb * 4), fl(*pool_, t);
+      out = hspf_lfa_ecmp_out{ptr.as<uint32_t>(), pri.as<uint32_t>(), slot.as<uint32_t>(), met.as<uint32_t>(), fl.as<uint8_t>(), cov.as<uint32_t>()};
+      if (hspf_lfa_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, ps.data(), o.n_protected, lfa_flags, total, &out, &total) != HSPF_OK)
+        fail(what);
+      c.fetch(o.ea_primary, out.ea_primary, t); c.fetch(o.ea_slot, out.ea_slot, t); c.fetch(o.ea_metric, out.ea_metric, t); c.fetch(o.ea_flags, out.ea_flags, t);
+      c.fetch(o.ea_coverage, out.ea_coverage, cb);
+    }
+    c.fetch(o.ea_ptr, out.ea_ptr, pb);
+    if (!c.ok) fail(what);
+    return o;
+  }
+  // (backup_routes / backup_routes_lan stay the base's "not supported": a DeviceRoutes does not keep its prefix table, which
+  // hspf_routes_backup_device needs; hspf::Engine::routes_backup_device / routes_backup_lan_device take it explicitly.)
+  LfaOut lfa_lan(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> &lans, uint32_t lfa_flags, bool with_masks) override {
+    if (lans.size() != protect.size()) throw std::runtime_error("lfa_lan: one LfaLan per protected root");
+    return lfa_with(run, protect, &lans, nullptr, lfa_flags, with_masks);
+  }
+  LfaOut lfa_srlg(DeviceRun &run, const std::vector<LfaProtect> &protect, const std::vector<Srlg> &srlgs, uint32_t lfa_flags, bool with_masks) override {
+    return lfa_with(run, protect, nullptr, &srlgs, lfa_flags, with_masks);
   }
   RlfaOut rlfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
                bool with_spaces) override {
@@ -1213,121 +1402,35 @@ class HipEngine : public Engine {
                     uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) override {
     return rlfa_with(gr, run, reverse_run, protect, nullptr, &srlgs, lfa_flags, lfa, with_spaces);
   }
- private:
-  // the frame of rlfa() (lans == srlgs == nullptr: hspf_rlfa_device), rlfa_lan() (hspf_rlfa_lan_device) and rlfa_srlg()
-  // (hspf_rlfa_srlg_device)
-  RlfaOut rlfa_with(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, const std::vector<LfaLan> *lans,
-                    const std::vector<Srlg> *srlgs, uint32_t lfa_flags, const LfaOut *lfa, bool with_spaces) {
-    const uint32_t nw = lans ? HSPF_RLFA_LAN_COUNT_WORDS : srlgs ? HSPF_RLFA_SRLG_COUNT_WORDS : HSPF_RLFA_COUNT_WORDS;
-    const uint32_t cw = lans ? HSPF_RLFA_LAN_COVERAGE_WORDS : srlgs ? HSPF_RLFA_SRLG_COVERAGE_WORDS : HSPF_RLFA_COVERAGE_WORDS;
-    const char *fn = lans ? "hspf_rlfa_lan_device: " : srlgs ? "hspf_rlfa_srlg_device: " : "hspf_rlfa_device: ";
-    const std::string who = lans ? "rlfa_lan: " : srlgs ? "rlfa_srlg: " : "rlfa: ";
-    auto &r = static_cast<HipDeviceRun &>(run);
-    auto &rr = static_cast<HipDeviceRun &>(reverse_run);
-    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error(who + "the two runs differ in shape");
-    RlfaOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words;
-    if (protect.empty()) return o;
-    std::vector<hspf_lfa_protect> ps;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error(who + "the slot arrays of a protected root differ in length");
-      ps.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
-    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps4 = (size_t)o.n_protected * o.slot_stride * 4, sp = with_spaces ? (size_t)o.n_protected * o.slot_stride * o.n_vertices : 0;
-    std::vector<hspf_lfa_lan> ls;
-    for (size_t i = 0; lans && i < lans->size(); ++i) {
-      const LfaLan &l = (*lans)[i];
-      if (l.lan.size() != protect[i].nbr.size() || l.lan_row.size() != protect[i].nbr.size()) throw std::runtime_error("rlfa_lan: lan / lan_row differ in length from the slot arrays");
-      ls.push_back(hspf_lfa_lan{l.lan.data(), l.lan_row.data()});
-    }
-    std::vector<hspf_srlg> ss;
-    if (srlgs) ss = srlg_raw(who, protect, *srlgs);
-    const size_t cb = (size_t)o.n_protected * cw * 4;
-    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
-    // one block: pq_node | pq_via | pq_metric | pq_counts | rl_node | rl_via | rl_coverage | space_via | space_flags | alt_flags
-    const size_t total = ps4 * 3 + ps4 * nw + pn * 8 + cb + sp * 5 + (with_alt ? pn : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
-    uint32_t *w = (uint32_t *)blk;
-    hspf_rlfa_out out{};
-    out.pq_node = w; w += ps4 / 4; out.pq_via = w; w += ps4 / 4; out.pq_metric = w; w += ps4 / 4; out.pq_counts = w; w += ps4 / 4 * nw;
-    out.rl_node = w; w += pn; out.rl_via = w; w += pn; out.rl_coverage = w; w += cb / 4;
-    if (with_spaces) { out.space_via = w; w += sp; out.space_flags = (uint8_t *)w; }
-    uint8_t *alt = with_alt ? (uint8_t *)w + sp : nullptr;
-    bool ok = !with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess;
-    hspf_graph *g = static_cast<HipGraph &>(gr).g;
-    const int rc = !ok ? HSPF_E_HIP
-                 : lans ? hspf_rlfa_lan_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), ls.data(),
-                                               o.n_protected, lfa_flags, alt, &out)
-                 : srlgs ? hspf_rlfa_srlg_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), ss.data(),
-                                                 o.n_protected, lfa_flags, alt, &out)
-                        : hspf_rlfa_device(ctx_, g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, ps.data(), o.n_protected,
-                                           lfa_flags, alt, &out);
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
-    ok = ok && rc == HSPF_OK;
-    if (ok) {
-      fetch(o.pq_node, out.pq_node, ps4 / 4); fetch(o.pq_via, out.pq_via, ps4 / 4); fetch(o.pq_metric, out.pq_metric, ps4 / 4);
-      fetch(o.pq_counts, out.pq_counts, ps4 / 4 * nw); fetch(o.rl_node, out.rl_node, pn); fetch(o.rl_via, out.rl_via, pn);
-      fetch(o.rl_coverage, out.rl_coverage, cb / 4);
-      if (with_spaces) { fetch(o.space_via, out.space_via, sp); fetch(o.space_flags, out.space_flags, sp); }
-    }
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string(fn) + hspf_last_error(ctx_));
-    return o;
-  }
- public:
   TilfaOut tilfa(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
                  const RlfaOut &rl) override {
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rr = static_cast<HipDeviceRun &>(reverse_run);
-    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error("tilfa: the two runs differ in shape");
-    TilfaOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words;
+    same_shape("tilfa: ", r, rr);
+    TilfaOut o = head<TilfaOut>(protect, r);
+    o.slot_stride = 64u * r.mask_words;
     if (protect.empty()) return o;
     const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = ps * o.n_vertices;
     if (rl.space_flags.size() != sp || rl.space_via.size() != sp) throw std::runtime_error("tilfa: the RLFA result holds no space tables of this protect list");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("tilfa: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
+    const std::vector<hspf_lfa_protect> pr = protect_raw("tilfa: ", protect);
     const size_t cb = (size_t)o.n_protected * HSPF_TILFA_COVERAGE_WORDS;
-    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
     // one block: ti_p | ti_q | ti_via | ti_link | ti_metric | ti_counts | td_coverage | space_via | ti_kind | td_kind | space_flags | alt_flags
-    const size_t words = ps * 5 + ps * HSPF_TILFA_COUNT_WORDS + cb + sp, total = words * 4 + ps + pn + sp + (with_alt ? pn : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
-    uint32_t *w = (uint32_t *)blk;
+    HipLease blk(*pool_, (ps * 5 + ps * HSPF_TILFA_COUNT_WORDS + cb + sp) * 4 + ps + pn + sp + (has_alt(lfa, pn) ? pn : 0));
+    DevCursor c(blk);
     hspf_tilfa_out out{};
-    out.ti_p = w; w += ps; out.ti_q = w; w += ps; out.ti_via = w; w += ps; out.ti_link = w; w += ps; out.ti_metric = w; w += ps;
-    out.ti_counts = w; w += ps * HSPF_TILFA_COUNT_WORDS; out.td_coverage = w; w += cb;
-    uint32_t *sv = w; w += sp;
-    uint8_t *b = (uint8_t *)w;
-    out.ti_kind = b; b += ps; out.td_kind = b; b += pn;
-    uint8_t *sf = b; b += sp;
-    uint8_t *alt = with_alt ? b : nullptr;
-    bool ok = hipMemcpy(sv, rl.space_via.data(), sp * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
-              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
-    const int rc = ok ? hspf_tilfa_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(),
-                                          o.n_protected, lfa_flags, alt, sf, sv, &out) : HSPF_E_HIP;
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
-    ok = ok && rc == HSPF_OK;
-    if (ok) {
-      fetch(o.ti_kind, out.ti_kind, ps); fetch(o.ti_p, out.ti_p, ps); fetch(o.ti_q, out.ti_q, ps); fetch(o.ti_via, out.ti_via, ps);
-      fetch(o.ti_link, out.ti_link, ps); fetch(o.ti_metric, out.ti_metric, ps); fetch(o.ti_counts, out.ti_counts, ps * HSPF_TILFA_COUNT_WORDS);
-      fetch(o.td_kind, out.td_kind, pn); fetch(o.td_coverage, out.td_coverage, cb);
-    }
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string("hspf_tilfa_device: ") + hspf_last_error(ctx_));
+    out.ti_p = c.take<uint32_t>(ps); out.ti_q = c.take<uint32_t>(ps); out.ti_via = c.take<uint32_t>(ps); out.ti_link = c.take<uint32_t>(ps);
+    out.ti_metric = c.take<uint32_t>(ps); out.ti_counts = c.take<uint32_t>(ps * HSPF_TILFA_COUNT_WORDS); out.td_coverage = c.take<uint32_t>(cb);
+    const uint32_t *sv = c.put(rl.space_via);
+    out.ti_kind = c.take<uint8_t>(ps); out.td_kind = c.take<uint8_t>(pn);
+    const uint8_t *sf = c.put(rl.space_flags), *alt = put_alt(c, lfa, pn);
+    const char *what = "hspf_tilfa_device: ";
+    if (!c.ok || hspf_tilfa_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(), o.n_protected,
+                                   lfa_flags, alt, sf, sv, &out) != HSPF_OK)
+      fail(what);
+    c.fetch(o.ti_kind, out.ti_kind, ps); c.fetch(o.ti_p, out.ti_p, ps); c.fetch(o.ti_q, out.ti_q, ps); c.fetch(o.ti_via, out.ti_via, ps);
+    c.fetch(o.ti_link, out.ti_link, ps); c.fetch(o.ti_metric, out.ti_metric, ps); c.fetch(o.ti_counts, out.ti_counts, ps * HSPF_TILFA_COUNT_WORDS);
+    c.fetch(o.td_kind, out.td_kind, pn); c.fetch(o.td_coverage, out.td_coverage, cb);
+    if (!c.ok) fail(what);
     return o;
   }
   TilfaPcOut tilfa_pc(Graph &gr, DeviceRun &run, DeviceRun &reverse_run, const std::vector<LfaProtect> &protect, uint32_t lfa_flags, const LfaOut *lfa,
@@ -1335,211 +1438,115 @@ class HipEngine : public Engine {
                       uint32_t max_walk) override {
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rr = static_cast<HipDeviceRun &>(reverse_run);
-    if (rr.n_vertices != r.n_vertices || rr.n_roots != r.n_roots) throw std::runtime_error("tilfa_pc: the two runs differ in shape");
-    TilfaPcOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices;
+    same_shape("tilfa_pc: ", r, rr);
+    TilfaPcOut o = head<TilfaPcOut>(protect, r);
     if (protect.empty()) return o;
-    const size_t stride = (size_t)64 * r.mask_words;
-    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * stride, sp = ps * o.n_vertices, pcw = (size_t)n_pc_rows * o.n_vertices;
+    const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * 64u * r.mask_words, sp = ps * o.n_vertices, pcw = (size_t)n_pc_rows * o.n_vertices;
     if (rl.space_flags.size() != sp || rl.space_via.size() != sp) throw std::runtime_error("tilfa_pc: the RLFA result holds no space tables of this protect list");
     if (pc_row.size() != ps || pc_dist.size() != pcw) throw std::runtime_error("tilfa_pc: pc_row or pc_dist is not of this protect list");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("tilfa_pc: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
+    const std::vector<hspf_lfa_protect> pr = protect_raw("tilfa_pc: ", protect);
     const size_t cb = (size_t)o.n_protected * HSPF_TIPC_COVERAGE_WORDS, A = HSPF_TIPC_MAX_ADJ;
-    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
     // one block: tp_p | tp_via | tp_q | tp_metric | tp_hop_pos | tp_hop_head | tp_coverage | space_via | pc_dist | tp_kind | tp_n_adj | tp_flags | space_flags | alt_flags
-    const size_t words = pn * 4 + pn * A * 2 + cb + sp + std::max<size_t>(pcw, 1), total = words * 4 + pn * 3 + sp + (with_alt ? pn : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
-    uint32_t *w = (uint32_t *)blk;
+    HipLease blk(*pool_, (pn * 4 + pn * A * 2 + cb + sp + std::max<size_t>(pcw, 1)) * 4 + pn * 3 + sp + (has_alt(lfa, pn) ? pn : 0));
+    DevCursor c(blk);
     hspf_tilfa_pc_out out{};
-    out.tp_p = w; w += pn; out.tp_via = w; w += pn; out.tp_q = w; w += pn; out.tp_metric = w; w += pn;
-    out.tp_hop_pos = w; w += pn * A; out.tp_hop_head = w; w += pn * A; out.tp_coverage = w; w += cb;
-    uint32_t *sv = w; w += sp;
-    uint32_t *pcd = w; w += std::max<size_t>(pcw, 1);
-    uint8_t *b = (uint8_t *)w;
-    out.tp_kind = b; b += pn; out.tp_n_adj = b; b += pn; out.tp_flags = b; b += pn;
-    uint8_t *sf = b; b += sp;
-    uint8_t *alt = with_alt ? b : nullptr;
-    bool ok = hipMemcpy(sv, rl.space_via.data(), sp * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
-              (pcw == 0 || hipMemcpy(pcd, pc_dist.data(), pcw * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
-    const int rc = ok ? hspf_tilfa_pc_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(),
-                                             o.n_protected, lfa_flags, alt, sf, sv, pcd, n_pc_rows, pc_row.data(), run_flags, max_walk, &out) : HSPF_E_HIP;
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
-    ok = ok && rc == HSPF_OK;
-    if (ok) {
-      fetch(o.tp_kind, out.tp_kind, pn); fetch(o.tp_n_adj, out.tp_n_adj, pn); fetch(o.tp_flags, out.tp_flags, pn); fetch(o.tp_p, out.tp_p, pn);
-      fetch(o.tp_via, out.tp_via, pn); fetch(o.tp_q, out.tp_q, pn); fetch(o.tp_metric, out.tp_metric, pn); fetch(o.tp_hop_pos, out.tp_hop_pos, pn * A);
-      fetch(o.tp_hop_head, out.tp_hop_head, pn * A); fetch(o.tp_coverage, out.tp_coverage, cb);
-    }
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string("hspf_tilfa_pc_device: ") + hspf_last_error(ctx_));
+    out.tp_p = c.take<uint32_t>(pn); out.tp_via = c.take<uint32_t>(pn); out.tp_q = c.take<uint32_t>(pn); out.tp_metric = c.take<uint32_t>(pn);
+    out.tp_hop_pos = c.take<uint32_t>(pn * A); out.tp_hop_head = c.take<uint32_t>(pn * A); out.tp_coverage = c.take<uint32_t>(cb);
+    const uint32_t *sv = c.put(rl.space_via);
+    uint32_t *pcd = c.take<uint32_t>(std::max<size_t>(pcw, 1));
+    c.upload(pcd, pc_dist);
+    out.tp_kind = c.take<uint8_t>(pn); out.tp_n_adj = c.take<uint8_t>(pn); out.tp_flags = c.take<uint8_t>(pn);
+    const uint8_t *sf = c.put(rl.space_flags), *alt = put_alt(c, lfa, pn);
+    const char *what = "hspf_tilfa_pc_device: ";
+    if (!c.ok || hspf_tilfa_pc_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, rr.dist, pr.data(), o.n_protected,
+                                      lfa_flags, alt, sf, sv, pcd, n_pc_rows, pc_row.data(), run_flags, max_walk, &out) != HSPF_OK)
+      fail(what);
+    c.fetch(o.tp_kind, out.tp_kind, pn); c.fetch(o.tp_n_adj, out.tp_n_adj, pn); c.fetch(o.tp_flags, out.tp_flags, pn); c.fetch(o.tp_p, out.tp_p, pn);
+    c.fetch(o.tp_via, out.tp_via, pn); c.fetch(o.tp_q, out.tp_q, pn); c.fetch(o.tp_metric, out.tp_metric, pn); c.fetch(o.tp_hop_pos, out.tp_hop_pos, pn * A);
+    c.fetch(o.tp_hop_head, out.tp_hop_head, pn * A); c.fetch(o.tp_coverage, out.tp_coverage, cb);
+    if (!c.ok) fail(what);
     return o;
   }
   RlfaNodeOut rlfa_node(Graph &gr, DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t run_flags, uint32_t lfa_flags, const LfaOut *lfa,
                         const RlfaOut &rl, uint32_t max_pq) override {
     auto &r = static_cast<HipDeviceRun &>(run);
-    RlfaNodeOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words; o.max_pq = max_pq;
+    RlfaNodeOut o = head<RlfaNodeOut>(protect, r);
+    o.slot_stride = 64u * r.mask_words; o.max_pq = max_pq;
     if (protect.empty()) return o;
     if (max_pq == 0 || max_pq > HSPF_RLFA_NODE_MAX_PQ) throw std::runtime_error("rlfa_node: max_pq outside 1 .. HSPF_RLFA_NODE_MAX_PQ");
     const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = ps * o.n_vertices, pm = ps * max_pq;
     if (rl.space_flags.size() != sp) throw std::runtime_error("rlfa_node: the RLFA result holds no space tables of this protect list");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("rlfa_node: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
+    const std::vector<hspf_lfa_protect> pr = protect_raw("rlfa_node: ", protect);
     const size_t cb = (size_t)o.n_protected * HSPF_NP_COVERAGE_WORDS;
-    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
     // one block: nq_node | nq_via | nq_metric | nq_count | nd_node | nd_via | nd_metric | nd_set | nd_coverage | nd_kind | space_flags | alt_flags
-    const size_t words = pm * 3 + ps + pn * 4 + cb, total = words * 4 + pn + sp + (with_alt ? pn : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
-    uint32_t *w = (uint32_t *)blk;
+    HipLease blk(*pool_, (pm * 3 + ps + pn * 4 + cb) * 4 + pn + sp + (has_alt(lfa, pn) ? pn : 0));
+    DevCursor c(blk);
     hspf_rlfa_node_sel sel{};
     hspf_rlfa_node_out out{};
-    sel.nq_node = w; w += pm; sel.nq_via = w; w += pm; sel.nq_metric = w; w += pm; sel.nq_count = w; w += ps;
-    out.nd_node = w; w += pn; out.nd_via = w; w += pn; out.nd_metric = w; w += pn; out.nd_set = w; w += pn; out.nd_coverage = w; w += cb;
-    uint8_t *b = (uint8_t *)w;
-    out.nd_kind = b; b += pn;
-    uint8_t *sf = b; b += sp;
-    uint8_t *alt = with_alt ? b : nullptr;
-    bool ok = hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
-              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
+    sel.nq_node = c.take<uint32_t>(pm); sel.nq_via = c.take<uint32_t>(pm); sel.nq_metric = c.take<uint32_t>(pm); sel.nq_count = c.take<uint32_t>(ps);
+    out.nd_node = c.take<uint32_t>(pn); out.nd_via = c.take<uint32_t>(pn); out.nd_metric = c.take<uint32_t>(pn); out.nd_set = c.take<uint32_t>(pn);
+    out.nd_coverage = c.take<uint32_t>(cb);
+    out.nd_kind = c.take<uint8_t>(pn);
+    const uint8_t *sf = c.put(rl.space_flags), *alt = put_alt(c, lfa, pn);
     const char *what = "hspf_rlfa_node_select_device: ";
-    int rc = ok ? hspf_rlfa_node_select_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, sf,
-                                               max_pq, &sel) : HSPF_E_HIP;
-    ok = ok && rc == HSPF_OK;
-    uint32_t *ydist = nullptr;
-    size_t ybytes = 0;
-    if (ok) {
-      fetch(o.nq_node, sel.nq_node, pm); fetch(o.nq_via, sel.nq_via, pm); fetch(o.nq_metric, sel.nq_metric, pm); fetch(o.nq_count, sel.nq_count, ps);
-    }
-    if (ok) {
-      for (uint32_t v : o.nq_node) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
-      std::sort(o.y_roots.begin(), o.y_roots.end());
-      o.y_roots.erase(std::unique(o.y_roots.begin(), o.y_roots.end()), o.y_roots.end());
-      const bool none = o.y_roots.empty();
-      if (none) o.y_roots.push_back(HSPF_NO_ROOT);        // one padding row keeps the arguments of the second call valid
-      ybytes = o.y_roots.size() * (size_t)o.n_vertices * 4;
-      ydist = (uint32_t *)pool_->dev(ybytes);
-      if (!none) {
-        what = "hspf_run_device (the PQ-node rows): ";
-        hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
-        rc = hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, o.y_roots.data(), (uint32_t)o.y_roots.size(), run_flags, &yres);
-        ok = rc == HSPF_OK;
-      }
-      if (ok) {
-        what = "hspf_rlfa_node_device: ";
-        rc = hspf_rlfa_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, ydist, o.y_roots.data(),
-                                   (uint32_t)o.y_roots.size(), &sel, max_pq, alt, &out);
-        ok = rc == HSPF_OK;
-      }
-      if (ok) {
-        fetch(o.nd_kind, out.nd_kind, pn); fetch(o.nd_node, out.nd_node, pn); fetch(o.nd_via, out.nd_via, pn); fetch(o.nd_metric, out.nd_metric, pn);
-        fetch(o.nd_set, out.nd_set, pn); fetch(o.nd_coverage, out.nd_coverage, cb);
-      }
-    }
-    if (ydist) pool_->dev_free(ydist, ybytes);
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    if (!c.ok || hspf_rlfa_node_select_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, sf, max_pq,
+                                              &sel) != HSPF_OK)
+      fail(what);
+    c.fetch(o.nq_node, sel.nq_node, pm); c.fetch(o.nq_via, sel.nq_via, pm); c.fetch(o.nq_metric, sel.nq_metric, pm); c.fetch(o.nq_count, sel.nq_count, ps);
+    if (!c.ok) fail(what);
+    const bool none = y_union(o.y_roots, &o.nq_node);
+    HipLease ydist(*pool_, o.y_roots.size() * (size_t)o.n_vertices * 4);
+    y_run(gr, o.y_roots, none, run_flags, ydist.as<uint32_t>(), "hspf_run_device (the PQ-node rows): ");
+    what = "hspf_rlfa_node_device: ";
+    if (hspf_rlfa_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, ydist.as<uint32_t>(), o.y_roots.data(),
+                              (uint32_t)o.y_roots.size(), &sel, max_pq, alt, &out) != HSPF_OK)
+      fail(what);
+    c.fetch(o.nd_kind, out.nd_kind, pn); c.fetch(o.nd_node, out.nd_node, pn); c.fetch(o.nd_via, out.nd_via, pn); c.fetch(o.nd_metric, out.nd_metric, pn);
+    c.fetch(o.nd_set, out.nd_set, pn); c.fetch(o.nd_coverage, out.nd_coverage, cb);
+    if (!c.ok) fail(what);
     return o;
   }
   TilfaNodeOut tilfa_node(Graph &gr, DeviceRun &run, const std::vector<LfaProtect> &protect, uint32_t run_flags, uint32_t lfa_flags, const LfaOut *lfa,
                           const RlfaOut &rl, const RlfaNodeOut *node, uint32_t max_pairs) override {
     auto &r = static_cast<HipDeviceRun &>(run);
-    TilfaNodeOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_vertices = r.n_vertices; o.slot_stride = 64u * r.mask_words; o.max_pairs = max_pairs;
+    TilfaNodeOut o = head<TilfaNodeOut>(protect, r);
+    o.slot_stride = 64u * r.mask_words; o.max_pairs = max_pairs;
     if (protect.empty()) return o;
     if (max_pairs == 0 || max_pairs > HSPF_TILFA_NODE_MAX_PAIRS) throw std::runtime_error("tilfa_node: max_pairs outside 1 .. HSPF_TILFA_NODE_MAX_PAIRS");
     const size_t pn = (size_t)o.n_protected * o.n_vertices, ps = (size_t)o.n_protected * o.slot_stride, sp = ps * o.n_vertices, pm = ps * max_pairs;
     if (rl.space_flags.size() != sp) throw std::runtime_error("tilfa_node: the RLFA result holds no space tables of this protect list");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("tilfa_node: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
+    const std::vector<hspf_lfa_protect> pr = protect_raw("tilfa_node: ", protect);
     const size_t cb = (size_t)o.n_protected * HSPF_TN_COVERAGE_WORDS;
-    const bool with_alt = lfa && lfa->supported && lfa->alt_flags.size() == pn;
     const bool with_nd = node && node->supported && node->nd_kind.size() == pn;
     // one block: tq_q | tq_p | tq_link | tq_via | tq_metric | tq_count | tn_p | tn_q | tn_link | tn_via | tn_metric | tn_set | tn_coverage | tn_kind |
     // space_flags | alt_flags | nd_kind
-    const size_t words = pm * 5 + ps + pn * 6 + cb, total = words * 4 + pn + sp + (with_alt ? pn : 0) + (with_nd ? pn : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
-    uint32_t *w = (uint32_t *)blk;
+    HipLease blk(*pool_, (pm * 5 + ps + pn * 6 + cb) * 4 + pn + sp + (has_alt(lfa, pn) ? pn : 0) + (with_nd ? pn : 0));
+    DevCursor c(blk);
     hspf_tilfa_node_sel sel{};
     hspf_tilfa_node_out out{};
-    sel.tq_q = w; w += pm; sel.tq_p = w; w += pm; sel.tq_link = w; w += pm; sel.tq_via = w; w += pm; sel.tq_metric = w; w += pm; sel.tq_count = w; w += ps;
-    out.tn_p = w; w += pn; out.tn_q = w; w += pn; out.tn_link = w; w += pn; out.tn_via = w; w += pn; out.tn_metric = w; w += pn; out.tn_set = w; w += pn;
-    out.tn_coverage = w; w += cb;
-    uint8_t *b = (uint8_t *)w;
-    out.tn_kind = b; b += pn;
-    uint8_t *sf = b; b += sp;
-    uint8_t *alt = with_alt ? b : nullptr;
-    if (with_alt) b += pn;
-    uint8_t *ndk = with_nd ? b : nullptr;
-    bool ok = hipMemcpy(sf, rl.space_flags.data(), sp, hipMemcpyHostToDevice) == hipSuccess &&
-              (!with_alt || hipMemcpy(alt, lfa->alt_flags.data(), pn, hipMemcpyHostToDevice) == hipSuccess) &&
-              (!with_nd || hipMemcpy(ndk, node->nd_kind.data(), pn, hipMemcpyHostToDevice) == hipSuccess);
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
+    sel.tq_q = c.take<uint32_t>(pm); sel.tq_p = c.take<uint32_t>(pm); sel.tq_link = c.take<uint32_t>(pm); sel.tq_via = c.take<uint32_t>(pm);
+    sel.tq_metric = c.take<uint32_t>(pm); sel.tq_count = c.take<uint32_t>(ps);
+    out.tn_p = c.take<uint32_t>(pn); out.tn_q = c.take<uint32_t>(pn); out.tn_link = c.take<uint32_t>(pn); out.tn_via = c.take<uint32_t>(pn);
+    out.tn_metric = c.take<uint32_t>(pn); out.tn_set = c.take<uint32_t>(pn); out.tn_coverage = c.take<uint32_t>(cb);
+    out.tn_kind = c.take<uint8_t>(pn);
+    const uint8_t *sf = c.put(rl.space_flags), *alt = put_alt(c, lfa, pn), *ndk = with_nd ? c.put(node->nd_kind) : nullptr;
     const char *what = "hspf_tilfa_node_select_device: ";
-    int rc = ok ? hspf_tilfa_node_select_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(),
-                                                o.n_protected, lfa_flags, sf, max_pairs, &sel) : HSPF_E_HIP;
-    ok = ok && rc == HSPF_OK;
-    uint32_t *ydist = nullptr;
-    size_t ybytes = 0;
-    if (ok) {
-      fetch(o.tq_q, sel.tq_q, pm); fetch(o.tq_p, sel.tq_p, pm); fetch(o.tq_link, sel.tq_link, pm); fetch(o.tq_via, sel.tq_via, pm);
-      fetch(o.tq_metric, sel.tq_metric, pm); fetch(o.tq_count, sel.tq_count, ps);
-    }
-    if (ok) {
-      for (uint32_t v : o.tq_q) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
-      std::sort(o.y_roots.begin(), o.y_roots.end());
-      o.y_roots.erase(std::unique(o.y_roots.begin(), o.y_roots.end()), o.y_roots.end());
-      const bool none = o.y_roots.empty();
-      if (none) o.y_roots.push_back(HSPF_NO_ROOT);        // one padding row keeps the arguments of the second call valid
-      ybytes = o.y_roots.size() * (size_t)o.n_vertices * 4;
-      ydist = (uint32_t *)pool_->dev(ybytes);
-      if (!none) {
-        what = "hspf_run_device (the q rows): ";
-        hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
-        rc = hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, o.y_roots.data(), (uint32_t)o.y_roots.size(), run_flags, &yres);
-        ok = rc == HSPF_OK;
-      }
-      if (ok) {
-        what = "hspf_tilfa_node_device: ";
-        rc = hspf_tilfa_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, ydist, o.y_roots.data(),
-                                    (uint32_t)o.y_roots.size(), &sel, max_pairs, alt, ndk, &out);
-        ok = rc == HSPF_OK;
-      }
-      if (ok) {
-        fetch(o.tn_kind, out.tn_kind, pn); fetch(o.tn_p, out.tn_p, pn); fetch(o.tn_q, out.tn_q, pn); fetch(o.tn_link, out.tn_link, pn);
-        fetch(o.tn_via, out.tn_via, pn); fetch(o.tn_metric, out.tn_metric, pn); fetch(o.tn_set, out.tn_set, pn); fetch(o.tn_coverage, out.tn_coverage, cb);
-      }
-    }
-    if (ydist) pool_->dev_free(ydist, ybytes);
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    if (!c.ok || hspf_tilfa_node_select_device(ctx_, static_cast<HipGraph &>(gr).g, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(),
+                                               o.n_protected, lfa_flags, sf, max_pairs, &sel) != HSPF_OK)
+      fail(what);
+    c.fetch(o.tq_q, sel.tq_q, pm); c.fetch(o.tq_p, sel.tq_p, pm); c.fetch(o.tq_link, sel.tq_link, pm); c.fetch(o.tq_via, sel.tq_via, pm);
+    c.fetch(o.tq_metric, sel.tq_metric, pm); c.fetch(o.tq_count, sel.tq_count, ps);
+    if (!c.ok) fail(what);
+    const bool none = y_union(o.y_roots, &o.tq_q);
+    HipLease ydist(*pool_, o.y_roots.size() * (size_t)o.n_vertices * 4);
+    y_run(gr, o.y_roots, none, run_flags, ydist.as<uint32_t>(), "hspf_run_device (the q rows): ");
+    what = "hspf_tilfa_node_device: ";
+    if (hspf_tilfa_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, ydist.as<uint32_t>(), o.y_roots.data(),
+                               (uint32_t)o.y_roots.size(), &sel, max_pairs, alt, ndk, &out) != HSPF_OK)
+      fail(what);
+    c.fetch(o.tn_kind, out.tn_kind, pn); c.fetch(o.tn_p, out.tn_p, pn); c.fetch(o.tn_q, out.tn_q, pn); c.fetch(o.tn_link, out.tn_link, pn);
+    c.fetch(o.tn_via, out.tn_via, pn); c.fetch(o.tn_metric, out.tn_metric, pn); c.fetch(o.tn_set, out.tn_set, pn); c.fetch(o.tn_coverage, out.tn_coverage, cb);
+    if (!c.ok) fail(what);
     return o;
   }
   BackupOut backup_routes_srlg(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
@@ -1547,68 +1554,37 @@ class HipEngine : public Engine {
                                const std::vector<Srlg> &srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) override {
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rt = static_cast<HipDeviceRoutes &>(routes);
-    BackupOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes; o.mask_words = r.mask_words;
+    BackupOut o = head<BackupOut>(protect, rt);
+    o.mask_words = r.mask_words;
     if (protect.empty()) return o;
-    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
-      throw std::runtime_error("backup_routes_srlg: the routes are not of this run and prefix table");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("backup_routes_srlg: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
+    routes_of_run("backup_routes_srlg: ", r, rt, pfx_ptr, pfx_vertex, pfx_metric);
+    const std::vector<hspf_lfa_protect> pr = protect_raw("backup_routes_srlg: ", protect);
     const std::vector<hspf_srlg> ss = srlg_raw("backup_routes_srlg: ", protect, srlgs);
     const size_t ps = (size_t)o.n_protected * 64u * r.mask_words, pp = (size_t)o.n_protected * o.n_prefixes, pw = pp * r.mask_words;
-    const bool with_ti = tilfa && tilfa->supported;
-    if (with_ti && (tilfa->ti_kind.size() != ps || tilfa->ti_via.size() != ps || tilfa->ti_metric.size() != ps || tilfa->ti_p.size() != ps || tilfa->ti_link.size() != ps))
-      throw std::runtime_error("backup_routes_srlg: the TI-LFA result is not of this protect list");
+    const bool with_ti = has_tilfa("backup_routes_srlg: ", tilfa, ps, true);
     const size_t cb = (size_t)o.n_protected * HSPF_BK_SRLG_COVERAGE_WORDS;
-    // one block: bk_cand_mask | bk_node_mask | bk_primary | bk_slot | bk_metric | bk_coverage | ti_via | ti_metric | ti_p | ti_link | bk_kind | bk_flags | ti_kind
-    const size_t total = pw * 16 + pp * 12 + cb * 4 + (with_ti ? ps * 17 : 0) + pp * 2;
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
+    // one block: bk_cand_mask | bk_node_mask | bk_primary | bk_slot | bk_metric | bk_coverage | ti_via | ti_metric | ti_p | ti_link | ti_kind | bk_kind | bk_flags
+    HipLease blk(*pool_, pw * 16 + pp * 12 + cb * 4 + (with_ti ? ps * 17 : 0) + pp * 2);
+    DevCursor c(blk);
     hspf_backup_out out{};
-    out.bk_cand_mask = (uint64_t *)blk; out.bk_node_mask = out.bk_cand_mask + pw;
-    uint32_t *w = (uint32_t *)(out.bk_node_mask + pw);
-    out.bk_primary = w; w += pp; out.bk_slot = w; w += pp; out.bk_metric = w; w += pp; out.bk_coverage = w; w += cb;
+    out.bk_cand_mask = c.take<uint64_t>(pw); out.bk_node_mask = c.take<uint64_t>(pw);
+    out.bk_primary = c.take<uint32_t>(pp); out.bk_slot = c.take<uint32_t>(pp); out.bk_metric = c.take<uint32_t>(pp); out.bk_coverage = c.take<uint32_t>(cb);
     hspf_tilfa_out ti{};
-    bool ok = true;
-    auto put = [&](uint32_t *&dst, const std::vector<uint32_t> &src) {
-      dst = w; w += src.size();
-      ok = ok && (src.empty() || hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
-    };
-    if (with_ti) { put(ti.ti_via, tilfa->ti_via); put(ti.ti_metric, tilfa->ti_metric); put(ti.ti_p, tilfa->ti_p); put(ti.ti_link, tilfa->ti_link); }
-    uint8_t *b = (uint8_t *)w;
-    out.bk_kind = b; b += pp; out.bk_flags = b; b += pp;
-    if (with_ti) {
-      ti.ti_kind = b;
-      ok = ok && hipMemcpy(ti.ti_kind, tilfa->ti_kind.data(), ps, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    const char *what = "hipMemcpy of the repairs: ";
-    if (ok) {
-      what = "hspf_routes_backup_srlg_device: ";
-      static const uint32_t zero = 0;
-      const hspf_prefix_table tab{o.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
-                                  pfx_metric.empty() ? &zero : pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT};
-      const hspf_routes ro = rt.raw();
-      ok = hspf_routes_backup_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), ss.data(), o.n_protected, lfa_flags,
-                                          &tab, &ro, with_ti ? &ti : nullptr, &out) == HSPF_OK;
-    }
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
-    if (ok) {
-      fetch(o.bk_kind, out.bk_kind, pp); fetch(o.bk_flags, out.bk_flags, pp); fetch(o.bk_primary, out.bk_primary, pp); fetch(o.bk_slot, out.bk_slot, pp);
-      fetch(o.bk_metric, out.bk_metric, pp); fetch(o.bk_cand_mask, out.bk_cand_mask, pw); fetch(o.bk_node_mask, out.bk_node_mask, pw);
-      fetch(o.bk_coverage, out.bk_coverage, cb);
-    }
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    if (with_ti) ti = put_tilfa(c, *tilfa, true);
+    out.bk_kind = c.take<uint8_t>(pp); out.bk_flags = c.take<uint8_t>(pp);
+    if (!c.ok) fail("hipMemcpy of the repairs: ");
+    const char *what = "hspf_routes_backup_srlg_device: ";
+    const hspf_prefix_table tab = given_table(pfx_ptr, pfx_vertex, pfx_metric, table_flags);
+    const hspf_routes ro = rt.raw();
+    if (hspf_routes_backup_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), ss.data(), o.n_protected, lfa_flags, &tab, &ro,
+                                       with_ti ? &ti : nullptr, &out) != HSPF_OK)
+      fail(what);
+    c.fetch(o.bk_kind, out.bk_kind, pp); c.fetch(o.bk_flags, out.bk_flags, pp); c.fetch(o.bk_primary, out.bk_primary, pp); c.fetch(o.bk_slot, out.bk_slot, pp);
+    c.fetch(o.bk_metric, out.bk_metric, pp); c.fetch(o.bk_cand_mask, out.bk_cand_mask, pw); c.fetch(o.bk_node_mask, out.bk_node_mask, pw);
+    c.fetch(o.bk_coverage, out.bk_coverage, cb);
+    if (!c.ok) fail(what);
     return o;
   }
-  // two calls: eb_ptr and the total, then the entries into arrays of that size
   BackupEcmpOut backup_routes_ecmp(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
                                    const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
                                    uint32_t lfa_flags, const TilfaOut *tilfa) override {
@@ -1619,100 +1595,15 @@ class HipEngine : public Engine {
                                         const std::vector<Srlg> &srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) override {
     return backup_routes_ecmp_with(run, routes, pfx_ptr, pfx_vertex, pfx_metric, table_flags, protect, &srlgs, lfa_flags, tilfa);
   }
-  // the frame of backup_routes_ecmp() (srlgs nullptr) and backup_routes_ecmp_srlg()
-  BackupEcmpOut backup_routes_ecmp_with(DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr, const std::vector<uint32_t> &pfx_vertex,
-                                        const std::vector<uint32_t> &pfx_metric, uint32_t table_flags, const std::vector<LfaProtect> &protect,
-                                        const std::vector<Srlg> *srlgs, uint32_t lfa_flags, const TilfaOut *tilfa) {
-    auto &r = static_cast<HipDeviceRun &>(run);
-    auto &rt = static_cast<HipDeviceRoutes &>(routes);
-    BackupEcmpOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes;
-    if (protect.empty()) return o;
-    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
-      throw std::runtime_error("backup_routes_ecmp: the routes are not of this run and prefix table");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("backup_routes_ecmp: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
-    std::vector<hspf_srlg> ss;
-    if (srlgs) ss = srlg_raw("backup_routes_ecmp_srlg: ", protect, *srlgs);
-    const size_t ps = (size_t)o.n_protected * 64u * r.mask_words;
-    const bool with_ti = tilfa && tilfa->supported;
-    if (with_ti && (tilfa->ti_kind.size() != ps || tilfa->ti_via.size() != ps || tilfa->ti_metric.size() != ps ||
-                    (srlgs && (tilfa->ti_p.size() != ps || tilfa->ti_link.size() != ps))))
-      throw std::runtime_error("backup_routes_ecmp: the TI-LFA result is not of this protect list");
-    const size_t pb = ((size_t)o.n_protected * o.n_prefixes + 1) * 4;
-    const size_t cb = (size_t)o.n_protected * (srlgs ? HSPF_BK_ECMP_SRLG_COVERAGE_WORDS : HSPF_BK_ECMP_COVERAGE_WORDS) * 4;
-    // one block: eb_ptr | eb_coverage | ti_via | ti_metric | (with groups: ti_p | ti_link |) ti_kind
-    const size_t head = pb + cb + (with_ti ? ps * (srlgs ? 17 : 9) : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(head);
-    uint32_t *ptr = (uint32_t *)blk, *cov = ptr + pb / 4;
-    hspf_tilfa_out ti{};
-    bool ok = true;
-    if (with_ti) {
-      ti.ti_via = cov + cb / 4; ti.ti_metric = ti.ti_via + ps; ti.ti_kind = (uint8_t *)(ti.ti_metric + ps);
-      if (srlgs) {
-        ti.ti_p = ti.ti_metric + ps; ti.ti_link = ti.ti_p + ps; ti.ti_kind = (uint8_t *)(ti.ti_link + ps);
-        ok = hipMemcpy(ti.ti_p, tilfa->ti_p.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(ti.ti_link, tilfa->ti_link.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess;
-      }
-      ok = ok && hipMemcpy(ti.ti_via, tilfa->ti_via.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
-           hipMemcpy(ti.ti_metric, tilfa->ti_metric.data(), ps * 4, hipMemcpyHostToDevice) == hipSuccess &&
-           hipMemcpy(ti.ti_kind, tilfa->ti_kind.data(), ps, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    static const uint32_t zero = 0;
-    const hspf_prefix_table tab{o.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
-                                pfx_metric.empty() ? &zero : pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT};
-    const hspf_routes ro = rt.raw();
-    hspf_backup_ecmp_out out{ptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t total = 0;
-    const char *what = "hipMemcpy of the repairs: ";
-    auto call = [&](uint64_t cap) {
-      return (srlgs ? hspf_routes_backup_ecmp_srlg_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), ss.data(), o.n_protected,
-                                                          lfa_flags, &tab, &ro, with_ti ? &ti : nullptr, cap, &out, &total)
-                    : hspf_routes_backup_ecmp_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, lfa_flags, &tab,
-                                                     &ro, with_ti ? &ti : nullptr, cap, &out, &total)) == HSPF_OK;
-    };
-    if (ok) {
-      what = srlgs ? "hspf_routes_backup_ecmp_srlg_device: " : "hspf_routes_backup_ecmp_device: ";
-      ok = call(0);
-    }
-    const size_t t = ok ? (size_t)total : 0;
-    o.eb_ptr.resize(pb / 4); o.eb_primary.resize(t); o.eb_kind.resize(t); o.eb_slot.resize(t); o.eb_metric.resize(t); o.eb_flags.resize(t);
-    o.eb_coverage.assign(cb / 4, 0u);
-    if (ok && t) {
-      // the entries: eb_primary | eb_slot | eb_metric | eb_kind | eb_flags
-      uint8_t *ent = (uint8_t *)pool_->dev(t * 14);
-      out = hspf_backup_ecmp_out{ptr, (uint32_t *)ent, ent + t * 12, (uint32_t *)ent + t, (uint32_t *)ent + 2 * t, ent + t * 13, cov};
-      ok = call(total) &&
-           hipMemcpy(o.eb_primary.data(), out.eb_primary, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.eb_slot.data(), out.eb_slot, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.eb_metric.data(), out.eb_metric, t * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.eb_kind.data(), out.eb_kind, t, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.eb_flags.data(), out.eb_flags, t, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(o.eb_coverage.data(), cov, cb, hipMemcpyDeviceToHost) == hipSuccess;
-      pool_->dev_free(ent, t * 14);
-    }
-    ok = ok && hipMemcpy(o.eb_ptr.data(), ptr, pb, hipMemcpyDeviceToHost) == hipSuccess;
-    pool_->dev_free(blk, head);
-    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
-    return o;
-  }
   BackupNodeOut backup_routes_node(Graph &gr, DeviceRun &run, DeviceRoutes &routes, const std::vector<uint32_t> &pfx_ptr,
                                    const std::vector<uint32_t> &pfx_vertex, const std::vector<uint32_t> &pfx_metric, uint32_t table_flags,
                                    const std::vector<LfaProtect> &protect, uint32_t run_flags, const RlfaNodeOut *node, const TilfaNodeOut *pairs,
                                    const BackupOut *backup) override {
     auto &r = static_cast<HipDeviceRun &>(run);
     auto &rt = static_cast<HipDeviceRoutes &>(routes);
-    BackupNodeOut o;
-    o.supported = true;
-    o.n_protected = (uint32_t)protect.size(); o.n_prefixes = rt.n_prefixes;
+    BackupNodeOut o = head<BackupNodeOut>(protect, rt);
     if (protect.empty()) return o;
-    if (pfx_ptr.size() != (size_t)rt.n_prefixes + 1 || pfx_vertex.size() != pfx_metric.size() || rt.mask_words != r.mask_words)
-      throw std::runtime_error("backup_routes_node: the routes are not of this run and prefix table");
+    routes_of_run("backup_routes_node: ", r, rt, pfx_ptr, pfx_vertex, pfx_metric);
     const size_t ps = (size_t)o.n_protected * 64u * r.mask_words, pp = (size_t)o.n_protected * o.n_prefixes;
     const bool with_rn = node && node->supported, with_tn = pairs && pairs->supported, with_bk = backup && backup->supported;
     if (!with_rn && !with_tn) throw std::runtime_error("backup_routes_node: at least one of the two lists is required");
@@ -1724,78 +1615,41 @@ class HipEngine : public Engine {
       throw std::runtime_error("backup_routes_node: the TI-LFA-node result is not of this protect list");
     if (with_bk && (backup->bk_kind.size() != pp || backup->bk_flags.size() != pp))
       throw std::runtime_error("backup_routes_node: the backup result is not of this protect list and table");
-    std::vector<hspf_lfa_protect> pr;
-    for (const LfaProtect &p : protect) {
-      if (p.nbr_row.size() != p.nbr.size() || p.cost.size() != p.nbr.size() || p.root_link.size() != p.nbr.size() || p.cflags.size() != p.nbr.size())
-        throw std::runtime_error("backup_routes_node: the slot arrays of a protected root differ in length");
-      pr.push_back(hspf_lfa_protect{p.root_vertex, p.root_row, (uint32_t)p.nbr.size(), p.nbr.data(), p.nbr_row.data(), p.cost.data(), p.root_link.data(), p.cflags.data()});
-    }
-    if (with_rn) for (uint32_t v : node->nq_node) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
-    if (with_tn) for (uint32_t v : pairs->tq_q) if (v != HSPF_NO_ROOT) o.y_roots.push_back(v);
-    std::sort(o.y_roots.begin(), o.y_roots.end());
-    o.y_roots.erase(std::unique(o.y_roots.begin(), o.y_roots.end()), o.y_roots.end());
-    const bool none = o.y_roots.empty();
-    if (none) o.y_roots.push_back(HSPF_NO_ROOT);          // one padding row keeps the arguments of the call valid
+    const std::vector<hspf_lfa_protect> pr = protect_raw("backup_routes_node: ", protect);
+    const bool none = y_union(o.y_roots, with_rn ? &node->nq_node : nullptr, with_tn ? &pairs->tq_q : nullptr);
     const size_t cb = (size_t)o.n_protected * HSPF_BN_COVERAGE_WORDS, yw = o.y_roots.size() * (size_t)r.n_vertices;
     // one block: the lists (nq_node | nq_via | nq_metric | nq_count | tq_q | tq_p | tq_link | tq_via | tq_metric | tq_count) | bn_primary .. bn_set_pair |
     // bn_coverage | ydist | bn_kind | bk_kind | bk_flags
-    const size_t words = pq * 3 + (with_rn ? ps : 0) + pm * 5 + (with_tn ? ps : 0) + pp * 8 + cb + yw, total = words * 4 + pp + (with_bk ? 2 * pp : 0);
-    uint8_t *blk = (uint8_t *)pool_->dev(total);
-    uint32_t *w = (uint32_t *)blk;
+    HipLease blk(*pool_, (pq * 3 + (with_rn ? ps : 0) + pm * 5 + (with_tn ? ps : 0) + pp * 8 + cb + yw) * 4 + pp + (with_bk ? 2 * pp : 0));
+    DevCursor c(blk);
     hspf_rlfa_node_sel rn{};
     hspf_tilfa_node_sel tn{};
     hspf_backup_node_out out{};
-    bool ok = true;
-    auto put = [&](uint32_t *&dst, const std::vector<uint32_t> &src) {
-      dst = w; w += src.size();
-      ok = ok && (src.empty() || hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
-    };
-    if (with_rn) { put(rn.nq_node, node->nq_node); put(rn.nq_via, node->nq_via); put(rn.nq_metric, node->nq_metric); put(rn.nq_count, node->nq_count); }
+    if (with_rn) { rn.nq_node = c.put(node->nq_node); rn.nq_via = c.put(node->nq_via); rn.nq_metric = c.put(node->nq_metric); rn.nq_count = c.put(node->nq_count); }
     if (with_tn) {
-      put(tn.tq_q, pairs->tq_q); put(tn.tq_p, pairs->tq_p); put(tn.tq_link, pairs->tq_link); put(tn.tq_via, pairs->tq_via); put(tn.tq_metric, pairs->tq_metric);
-      put(tn.tq_count, pairs->tq_count);
+      tn.tq_q = c.put(pairs->tq_q); tn.tq_p = c.put(pairs->tq_p); tn.tq_link = c.put(pairs->tq_link); tn.tq_via = c.put(pairs->tq_via);
+      tn.tq_metric = c.put(pairs->tq_metric); tn.tq_count = c.put(pairs->tq_count);
     }
-    out.bn_primary = w; w += pp; out.bn_p = w; w += pp; out.bn_q = w; w += pp; out.bn_link = w; w += pp; out.bn_via = w; w += pp; out.bn_metric = w; w += pp;
-    out.bn_set_pq = w; w += pp; out.bn_set_pair = w; w += pp; out.bn_coverage = w; w += cb;
-    uint32_t *ydist = w; w += yw;
-    uint8_t *b = (uint8_t *)w;
-    out.bn_kind = b; b += pp;
+    out.bn_primary = c.take<uint32_t>(pp); out.bn_p = c.take<uint32_t>(pp); out.bn_q = c.take<uint32_t>(pp); out.bn_link = c.take<uint32_t>(pp);
+    out.bn_via = c.take<uint32_t>(pp); out.bn_metric = c.take<uint32_t>(pp); out.bn_set_pq = c.take<uint32_t>(pp); out.bn_set_pair = c.take<uint32_t>(pp);
+    out.bn_coverage = c.take<uint32_t>(cb);
+    uint32_t *ydist = c.take<uint32_t>(yw);
+    out.bn_kind = c.take<uint8_t>(pp);
     hspf_backup_out bk{};
-    if (with_bk) {
-      bk.bk_kind = b; b += pp; bk.bk_flags = b;
-      ok = ok && (pp == 0 || (hipMemcpy(bk.bk_kind, backup->bk_kind.data(), pp, hipMemcpyHostToDevice) == hipSuccess &&
-                              hipMemcpy(bk.bk_flags, backup->bk_flags.data(), pp, hipMemcpyHostToDevice) == hipSuccess));
-    }
-    const char *what = "hipMemcpy of the lists: ";
-    int rc = ok ? HSPF_OK : HSPF_E_HIP;
-    if (ok && !none) {
-      what = "hspf_run_device (the rows of the listed nodes): ";
-      hspf_result yres{ydist, nullptr, nullptr, nullptr, 1, nullptr};
-      rc = hspf_run_device(ctx_, static_cast<HipGraph &>(gr).g, o.y_roots.data(), (uint32_t)o.y_roots.size(), run_flags, &yres);
-      ok = rc == HSPF_OK;
-    }
-    if (ok) {
-      what = "hspf_routes_backup_node_device: ";
-      static const uint32_t zero = 0;
-      const hspf_prefix_table tab{o.n_prefixes, (uint32_t)pfx_vertex.size(), pfx_ptr.data(), pfx_vertex.empty() ? &zero : pfx_vertex.data(),
-                                  pfx_metric.empty() ? &zero : pfx_metric.data(), table_flags & ~HSPF_PFX_RESIDENT};
-      const hspf_routes ro = rt.raw();
-      rc = hspf_routes_backup_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, &tab, &ro, ydist,
-                                          o.y_roots.data(), (uint32_t)o.y_roots.size(), with_rn ? &rn : nullptr, with_rn ? node->max_pq : 0u,
-                                          with_tn ? &tn : nullptr, with_tn ? pairs->max_pairs : 0u, with_bk ? &bk : nullptr, &out);
-      ok = rc == HSPF_OK;
-    }
-    auto fetch = [&](auto &vec, const void *src, size_t count) {
-      vec.resize(count);
-      ok = ok && (count == 0 || hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost) == hipSuccess);
-    };
-    if (ok) {
-      fetch(o.bn_kind, out.bn_kind, pp); fetch(o.bn_primary, out.bn_primary, pp); fetch(o.bn_p, out.bn_p, pp); fetch(o.bn_q, out.bn_q, pp);
-      fetch(o.bn_link, out.bn_link, pp); fetch(o.bn_via, out.bn_via, pp); fetch(o.bn_metric, out.bn_metric, pp); fetch(o.bn_set_pq, out.bn_set_pq, pp);
-      fetch(o.bn_set_pair, out.bn_set_pair, pp); fetch(o.bn_coverage, out.bn_coverage, cb);
-    }
-    pool_->dev_free(blk, total);
-    if (!ok) throw std::runtime_error(std::string(what) + hspf_last_error(ctx_));
+    if (with_bk) { bk.bk_kind = c.put(backup->bk_kind); bk.bk_flags = c.put(backup->bk_flags); }
+    if (!c.ok) fail("hipMemcpy of the lists: ");
+    y_run(gr, o.y_roots, none, run_flags, ydist, "hspf_run_device (the rows of the listed nodes): ");
+    const char *what = "hspf_routes_backup_node_device: ";
+    const hspf_prefix_table tab = given_table(pfx_ptr, pfx_vertex, pfx_metric, table_flags);
+    const hspf_routes ro = rt.raw();
+    if (hspf_routes_backup_node_device(ctx_, r.n_vertices, r.n_roots, r.mask_words, r.dist, r.flags, r.mask, pr.data(), o.n_protected, &tab, &ro, ydist, o.y_roots.data(),
+                                       (uint32_t)o.y_roots.size(), with_rn ? &rn : nullptr, with_rn ? node->max_pq : 0u, with_tn ? &tn : nullptr,
+                                       with_tn ? pairs->max_pairs : 0u, with_bk ? &bk : nullptr, &out) != HSPF_OK)
+      fail(what);
+    c.fetch(o.bn_kind, out.bn_kind, pp); c.fetch(o.bn_primary, out.bn_primary, pp); c.fetch(o.bn_p, out.bn_p, pp); c.fetch(o.bn_q, out.bn_q, pp);
+    c.fetch(o.bn_link, out.bn_link, pp); c.fetch(o.bn_via, out.bn_via, pp); c.fetch(o.bn_metric, out.bn_metric, pp); c.fetch(o.bn_set_pq, out.bn_set_pq, pp);
+    c.fetch(o.bn_set_pair, out.bn_set_pair, pp); c.fetch(o.bn_coverage, out.bn_coverage, cb);
+    if (!c.ok) fail(what);
     return o;
   }
   RouteEvents routes_events(DeviceRoutes &old_set, DeviceRoutes &new_set, bool with_silent) override {
