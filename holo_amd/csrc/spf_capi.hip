@@ -26,6 +26,7 @@
 #include <thread>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace hspf;
@@ -267,7 +268,18 @@ struct hspf_ctx {
   size_t h_lane_cap = 0;
   uint32_t est_relax = 12, est_dag = 12, est_fused = 12, est_fw = 12;   // launch-ahead estimates (adapted run to run)
   bool est_seen = false;                   // est_fused comes from a run of this context (not the initial guess)
-  uint32_t variant = 0;                    // HSPF_VARIANT env: kernel A/B switches (tuning only)
+  uint32_t variant = 0;                    // HSPF_VARIANT env: kernel A/B switches (tuning only), an OR of the bits below
+  // The bits of HSPF_VARIANT the engine reads (A/B measurements, tests).  Other bits that older notes speak of (14, 16, 24,
+  // 25, 26) are not read any more.
+  static constexpr uint32_t VAR_TWO_PHASE = 1u << 0;        // no fused path: every run takes the wide-mask path (and packed results are refused)
+  static constexpr uint32_t VAR_NO_NARROW = 1u << 1;        // no 4-byte state: neither k_fused's narrow state nor the lean sweep
+  static constexpr uint32_t VAR_NO_FW = 1u << 6;            // wide masks: k_relax + k_dag (the two-phase path) instead of k_fw
+  static constexpr uint32_t VAR_NO_SINGLE_LEAN = 1u << 12;  // one-workgroup path: k_single where k_single_lean would apply
+  static constexpr uint32_t VAR_NO_LEAN = 1u << 15;         // k_fused everywhere, never k_fused_lean
+  static constexpr uint32_t VAR_LEAN_NO_PLAN = 1u << 19;    // the lean sweep without its plan: stamped sweeps only
+  static constexpr uint32_t VAR_CLASSES_SERIAL = 1u << 20;  // run_classes: the classes one after the other, not on the lanes
+  static constexpr uint32_t VAR_NO_LEAF_ROOTS = 1u << 23;   // run_classes: leaf roots run like any other, no derived rows
+  static constexpr uint32_t VAR_EXACT_NOT_REPAIR = 1u << 27;  // dynamic pop orders and pop ranks: k_exact as before round 6, not k_repair
   uint32_t single_attr = 0;                // per k_single instantiation: its dynamic-LDS attribute has been set
   uint32_t single_max_n = 1024;            // HSPF_SINGLE_MAX_N env: largest graph that takes the one-workgroup-per-root kernel
   uint32_t lv_max_roots = 2;               // HSPF_LV_MAX_ROOTS env: runs of at most this many roots take the lane = vertex kernel (0: never)
@@ -440,25 +452,51 @@ uint32_t round_words(uint32_t w) {   // template instantiations of k_dag / k_emi
   return 16;
 }
 
-template <int W, bool GS = false>
-void launch_dag(dim3 grid, hipStream_t s, GraphDev g, const uint32_t *dist, uint32_t *hv, uint64_t *mask,
-                const uint32_t *roots, SlotTabs tabs, uint32_t nn, uint32_t io, int *changed, int sweep,
-                uint32_t epoch, uint32_t *lf, uint32_t hc, uint32_t *act) {
-  hipLaunchKernelGGL((k_dag<W, GS>), grid, dim3(256), 0, s, g, dist, hv, mask, roots, tabs, nn, io, changed,
-                     sweep, epoch, lf, hc, act, FailNone{});
+// ---- a runtime value as a template argument: f is a generic lambda that is called with the value as a std::integral_constant,
+// from which it makes a constant (`[&](auto c) { constexpr bool MAXINF = c; ... }`).  Every kernel family has ONE launch
+// function built from these (Run::launch_*, pick_single, pick_xcd): the launch is written once, and which combinations of
+// template arguments exist is written next to it, as the constants the lambdas derive.
+template <class F> decltype(auto) with_flag(bool b, F &&f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
 }
-template <int W, bool GS = false>
-void launch_dag_fail(dim3 grid, hipStream_t s, GraphDev g, const uint32_t *dist, uint32_t *hv, uint64_t *mask,
-                     const uint32_t *roots, SlotTabs tabs, uint32_t nn, uint32_t io, int *changed, int sweep,
-                     uint32_t epoch, uint32_t *lf, uint32_t hc, uint32_t *act, FailDev fd) {
-  hipLaunchKernelGGL((k_dag<W, GS, true>), grid, dim3(256), 0, s, g, dist, hv, mask, roots, tabs, nn, io, changed,
-                     sweep, epoch, lf, hc, act, fd);
+template <class F> decltype(auto) with_width(uint32_t w, F &&f) {   // mask words, rounded by round_words
+  switch (w) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
 }
-template <int W>
-void launch_emit(dim3 grid, hipStream_t s, uint32_t n, uint32_t nr, const uint32_t *dist, const uint32_t *hv,
-                 const uint64_t *mask, OutDev o, bool leaves, EmitLeaf el) {
-  if (leaves) hipLaunchKernelGGL((k_emit<W, true>), grid, dim3(256), 0, s, n, nr, dist, hv, mask, o, el);
-  else hipLaunchKernelGGL((k_emit<W, false>), grid, dim3(256), 0, s, n, nr, dist, hv, mask, o, el);
+template <class F> decltype(auto) with_vpt(uint32_t need, F &&f) {   // k_single's vertices per thread: 1, 2, 4 or 8
+  if (need <= 1) return f(std::integral_constant<int, 1>{});
+  if (need <= 2) return f(std::integral_constant<int, 2>{});
+  if (need <= 4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
+}
+template <bool NARROW> using StateWord = std::conditional_t<NARROW, uint32_t, uint64_t>;   // the packed state: 4 or 8 bytes
+
+// A kernel that needs an attribute set once per instantiation and context (dynamic LDS beyond 64 KB): the instantiation and
+// its bit in the context's record of the attributes set (hspf_ctx::single_attr / xcd_attr) come out of the same selection.
+template <class Args> struct KernelPick { void (*fn)(Args); uint32_t attr_bit; };
+
+// k_single<MAXINF, VPT, LL>: need_vpt vertices per thread rounded up to 1 / 2 / 4 / 8, LL = the link records are staged in LDS.
+KernelPick<SingleArgs> pick_single(bool maxinf, uint32_t need_vpt, bool lds_links) {
+  return with_flag(maxinf, [&](auto c) { constexpr bool MAXINF = c;
+  return with_vpt(need_vpt, [&](auto c) { constexpr int VPT = c;
+  return with_flag(lds_links, [&](auto c) { constexpr bool LL = c;
+    constexpr int vpt_log2 = VPT == 1 ? 0 : VPT == 2 ? 1 : VPT == 4 ? 2 : 3;
+    return KernelPick<SingleArgs>{k_single<MAXINF, VPT, LL>, 1u << ((vpt_log2 * 2 + (MAXINF ? 1 : 0)) * 2 + (LL ? 1 : 0))};
+  }); }); });
+}
+
+// k_xcd<MAXINF, PROF>: the attribute is recorded per MAXINF (PROF is one value for the life of the process).
+KernelPick<XcdArgs> pick_xcd(bool maxinf, bool prof) {
+  return with_flag(maxinf, [&](auto c) { constexpr bool MAXINF = c;
+  return with_flag(prof, [&](auto c) { constexpr bool PROF = c;
+    return KernelPick<XcdArgs>{k_xcd<MAXINF, PROF>, MAXINF ? 2u : 1u};
+  }); });
 }
 
 // Exclusive prefix sums of in[0..m) into out[0..m], out[m] = total (graph_build.hip.h).
@@ -1633,6 +1671,30 @@ struct Run {
   int upload_block();
   int init_state();
   template <class Launch, class Post> int run_phase(uint32_t est, uint32_t pre_zeroed, Launch &&launch, uint32_t &n_launch, Post &&post);
+  // One launch function per kernel family, each defined in front of the path that uses it: the template instantiation is
+  // chosen inside, from the run's state and the arguments, and the launch with its argument list is written once.
+  bool maxinf() const { return g->max_path_metric == HSPF_DIST_INF; }        // the kernels' MAXINF: distance sums may saturate
+  bool dyn_rows() const { return g->n_zero_rows && !g->hopcount_like; }      // FusedGraph::dyn_part is in use (k_fused_lean's ZROWS)
+  template <bool FAIL> typename FailArg<FAIL>::type fail_arg() const { if constexpr (FAIL) return fdv; else return FailNone{}; }
+  enum class LeanPass { Head, Tail, Dense, DenseBatchMajor, AllDue };        // what a launch of k_fused_lean is in the plan
+  void launch_init_fused(bool nar, uint32_t ns);
+  void launch_emit_fused(bool nar, const FusedParams &P, const OutDev &ode, uint32_t ns, uint32_t *lean_lf, int reset_guard, uint32_t fillw);
+  void launch_giant_part(uint32_t sweep, bool nar, const FusedParams &P);
+  void launch_fused(uint32_t sweep, bool nar, const FusedParams &P);
+  void launch_lean(LeanPass what, uint32_t sweep, const FusedParams &P, dim3 lgrid, PassGrid pgr, uint32_t base, uint32_t thr);
+  void launch_lv(const LvArgs &la, dim3 lgrid);
+  void launch_single_lean(const SingleArgs &sa, uint32_t thr);
+  void launch_init_fw_state(dim3 igrid);
+  void launch_fw_giant_part(uint32_t sweep, dim3 ggrid);
+  void launch_fw(uint32_t sweep);
+  void launch_relax(uint32_t sweep);
+  void launch_dag(uint32_t sweep, uint32_t epoch);
+  void launch_emit(dim3 egrid);
+  bool overflowed() const {            // a lane of the last fixed point left the fields of its state (status bits: last read-back)
+    bool o = false;
+    for (uint32_t r = 0; r < L; ++r) o = o || (ctx->h_lane_flags[r] & LF_OVERFLOW);
+    return o;
+  }
   int fused_run(int mode);
   int lv_run();
   int xcd_run();
@@ -1685,7 +1747,7 @@ int Run::prepare() {
   if (pk) max_slots = std::max(max_slots, pk->min_slots);
   want_mask = pk || out->first_hop_mask != nullptr;
   if (pk) out->n_mask_words = 1;                              // (`out` is the wrapper's placeholder in packed mode)
-  if (pk && (need_words > 1 || max_slots > (g->wide24_bad ? 16u : 24u) || n >= (1u << 23) || (ctx->variant & 1u))) {
+  if (pk && (need_words > 1 || max_slots > (g->wide24_bad ? 16u : 24u) || n >= (1u << 23) || (ctx->variant & hspf_ctx::VAR_TWO_PHASE))) {
     ctx->last_error = "packed results: a root of the run has more than " + std::to_string(g->wide24_bad ? 16 : 24) + " first-hop slots (or the fused path is off)";
     return HSPF_E_NO_PACKED;
   }
@@ -1712,14 +1774,14 @@ int Run::choose_state() {
   // 17-24 slots: the 8-byte state with a wider mask field and correspondingly fewer hop bits (32 - M); a root farther
   // than that many router hops from something raises LF_OVERFLOW and the run is redone on the two-phase path.
   const uint32_t fused_max_slots = g->wide24_bad ? 16u : 24u;
-  fused = !no_fused && !fail && max_slots <= fused_max_slots && n < (1u << 23) && !(ctx->variant & 1u);
+  fused = !no_fused && !fail && max_slots <= fused_max_slots && n < (1u << 23) && !(ctx->variant & hspf_ctx::VAR_TWO_PHASE);
   const uint32_t Mw = std::max(16u, max_slots);
   fp_wide = FusedParams{0u, Mw, Mw == 16u ? 0xFFFFu : (1u << (32u - Mw)) - 1u, 0xFFFFFFFFu, g->max_path_metric, 0xFFFFFFFFu,
                       g->hopcount_like ? 1u : 0u, 0xFFFFFFFFu};
   fp_narrow = fp_wide; fp_lean = fp_wide;
   narrow = false; lean = false;
   const bool pk_wide = pk && pk->force_wide;
-  if (fused && !g->narrow_bad && !(ctx->variant & 2u) && !pk_wide) {
+  if (fused && !g->narrow_bad && !(ctx->variant & hspf_ctx::VAR_NO_NARROW) && !pk_wide) {
     // field split of the 4-byte state: M mask bits = slots of this run, 7 hop bits (6 when that
     // leaves fewer than 13 distance bits), the rest distance; used when a link cost is at most
     // 1/8 of the distance range and there are at least 12 distance bits
@@ -1740,7 +1802,7 @@ int Run::choose_state() {
   // the run is redone by k_fused and the graph remembers).  The tag costs 3 of the 32 bits: 7 hop bits when that leaves a
   // distance field of at least 8 x wmax, else 6 and at least 4 x wmax.  Needs max_path_metric beyond the field (nothing to
   // prune inside it), no heavy work units, no giant rows.  HSPF_VARIANT bit 15: k_fused everywhere (A/B).
-  if (fused && !g->lean_bad && !(ctx->variant & (2u | 32768u)) && g->n_heavy_chunks == 0 && g->n_giant == 0 && !pk_wide) {
+  if (fused && !g->lean_bad && !(ctx->variant & (hspf_ctx::VAR_NO_NARROW | hspf_ctx::VAR_NO_LEAN)) && g->n_heavy_chunks == 0 && g->n_giant == 0 && !pk_wide) {
     const uint32_t M = std::max(max_slots, 1u);
     uint32_t H = 7u;
     if (M + 3u + H + 4u > 32u || (1u << (32u - M - 3u - H)) < 8u * (g->wmax + 1u)) H = 6u;
@@ -1790,7 +1852,8 @@ int Run::prepare_scratch() {
   if (ctx->h_lane_cap < L) {
     if (ctx->h_lane_flags) (void)hipHostFree(ctx->h_lane_flags);
     ctx->h_lane_flags = nullptr; ctx->h_lane_cap = 0;
-    HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_lane_flags, ((size_t)L + 256 + LEAN_CTL_WORDS + 4) * 4, hipHostMallocDefault));   // status bits | row counters | lean plan counters | misfit flag of a packed run
+    // status bits | row counters | lean plan counters | misfit flag of a packed run
+    HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_lane_flags, ((size_t)L + 256 + LEAN_CTL_WORDS + 4) * 4, hipHostMallocDefault));
     ctx->h_lane_cap = L;
   }
   // slices of the giant rows (FusedGraph::giant_part): tags, then GIANT_WORDS x 64 words per (batch, slice)
@@ -1827,7 +1890,7 @@ int Run::prepare_outputs() {
            !(run_flags & HSPF_RUN_COUNT_ROWS);
   xcdp = xcd_ok;
   if (xcd_ok && !ctx->xcd_always)
-    xcdp = !(single && g->lean && n <= (uint32_t)SINGLE_THREADS && !(ctx->variant & 4096u) && n_roots == 1);
+    xcdp = !(single && g->lean && n <= (uint32_t)SINGLE_THREADS && !(ctx->variant & hspf_ctx::VAR_NO_SINGLE_LEAN) && n_roots == 1);
   if (xcdp) single = false;
   // row-major output targets (device): the caller's device buffers, or staging for host output
   od = OutDev{};
@@ -1894,8 +1957,8 @@ int Run::upload_block() {
                         (g->n_zero_rows && !g->hopcount_like) ? (uint32_t *)ctx->dyn_part.p : (uint32_t *)nullptr, L};
     memcpy(h + w_fg, &fg, sizeof(FusedGraph));
     // An SPF instance repeats its runs (same graph, same roots): when the block is byte for byte the one the device
-    // already holds — same allocation, nothing in it is ever written by a kernel — the copy is skipped (HSPF_VARIANT bit
-    // 14 keeps it).  Otherwise the halves swap: the block just built becomes the reference.
+    // already holds — same allocation, nothing in it is ever written by a kernel — the copy is skipped (the HSPF_VARIANT
+    // bit 14 that kept it is gone).  Otherwise the halves swap: the block just built becomes the reference.
     st.dbg[2] = (uint32_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_entry).count();
     const bool same = ctx->up_valid && ctx->up_len == up_bytes && memcmp(h, prev, up_bytes) == 0;
     if (!same) {
@@ -1904,6 +1967,12 @@ int Run::upload_block() {
     }
   }
   return HSPF_OK;
+}
+
+void Run::launch_init_fw_state(dim3 igrid) {               // k_init_fw_state<W>
+  with_width(W, [&](auto c) { constexpr int WORDS = c;
+    hipLaunchKernelGGL(k_init_fw_state<WORDS>, igrid, dim3(256), 0, s, n, B, (const uint8_t *)g->d_leaf, d_dist, d_hv, d_mask);
+  });
 }
 
 // State of the wide-mask path (the fused path initialises per fused_run), grids, the events.
@@ -1917,7 +1986,7 @@ int Run::init_state() {
   // (the leaf is popped AFTER its parent, against the static (distance, index) order), the emit's derivation gives the right
   // triple but cannot raise LF_DYN any more (the status bits were read before it), and the caller would be told the order
   // is static (round 6: tests/test_gpu_fuzz.py, zero-metric instances, seed 5058).
-  use_fw = !fused && !fail && !(ctx->variant & 64u) && (!g->hopcount_like || W <= 4);
+  use_fw = !fused && !fail && !(ctx->variant & hspf_ctx::VAR_NO_FW) && (!g->hopcount_like || W <= 4);
   defer = use_fw && g->n_leaf != 0 && g->max_path_metric != HSPF_DIST_INF && !g->hopcount_like && g->n_zero_rows == 0;
   HIPCHK(ctx, hipEventRecord(ctx->ev[0], s));
   if (fused) {
@@ -1926,14 +1995,7 @@ int Run::init_state() {
   } else if (defer) {
     // k_fw with the leaves left to the emit: only the rows that take part are filled (distance, hops AND masks)
     HIPCHK(ctx, hipMemsetAsync(d_lf, 0, (size_t)L * 4, s));
-    const dim3 ig((unsigned)std::min<size_t>((rows / 64 + 3) / 4, 8192));
-    switch (W) {
-      case 1: hipLaunchKernelGGL(k_init_fw_state<1>, ig, dim3(256), 0, s, n, B, (const uint8_t *)g->d_leaf, d_dist, d_hv, d_mask); break;
-      case 2: hipLaunchKernelGGL(k_init_fw_state<2>, ig, dim3(256), 0, s, n, B, (const uint8_t *)g->d_leaf, d_dist, d_hv, d_mask); break;
-      case 4: hipLaunchKernelGGL(k_init_fw_state<4>, ig, dim3(256), 0, s, n, B, (const uint8_t *)g->d_leaf, d_dist, d_hv, d_mask); break;
-      case 8: hipLaunchKernelGGL(k_init_fw_state<8>, ig, dim3(256), 0, s, n, B, (const uint8_t *)g->d_leaf, d_dist, d_hv, d_mask); break;
-      default: hipLaunchKernelGGL(k_init_fw_state<16>, ig, dim3(256), 0, s, n, B, (const uint8_t *)g->d_leaf, d_dist, d_hv, d_mask); break;
-    }
+    launch_init_fw_state(dim3((unsigned)std::min<size_t>((rows / 64 + 3) / 4, 8192)));
   } else {
     HIPCHK(ctx, hipMemsetAsync(d_lf, 0, (size_t)L * 4, s));
     HIPCHK(ctx, hipMemsetAsync(d_dist, 0xFF, rows * 4, s));
@@ -2041,221 +2103,253 @@ static DivMagic div_magic_of(uint32_t d) {
 }
 static PassGrid pass_grid(uint32_t per_pass, uint32_t blocks) { return PassGrid{per_pass, blocks, div_magic_of(per_pass), div_magic_of(blocks)}; }
 
+// ---- the kernels of the packed state.  nar: the 4-byte state (StateWord), which never takes MAXINF: its distance field
+// saturates inside the word
+void Run::launch_init_fused(bool nar, uint32_t ns) {               // k_init_fused<ST>
+  with_flag(nar, [&](auto c) { constexpr bool NARROW = c; using ST = StateWord<NARROW>;
+    hipLaunchKernelGGL((k_init_fused<ST>), dim3((L + 3) / 4), dim3(256), 0, s, gd, (ST *)d_st, d_stamp, (uint8_t *)ctx->hnb.p, d_roots, tabs, L, ns);
+  });
+}
+
+// k_emit_fused<ST>.  lean_lf: the status bits when the state is the lean sweep's (its fields are checked on the way out), else null
+void Run::launch_emit_fused(bool nar, const FusedParams &P, const OutDev &ode, uint32_t ns, uint32_t *lean_lf, int reset_guard, uint32_t fillw) {
+  with_flag(nar, [&](auto c) { constexpr bool NARROW = c; using ST = StateWord<NARROW>;
+    hipLaunchKernelGGL((k_emit_fused<ST>), dim3((n + 63) / 64, B), dim3(256), 0, s, n, n_roots, (ST *)d_st, P, ode, ns, lean_lf,
+                       (const int *)d_changed, reset_guard, fillw);
+  });
+}
+
+// k_giant_part<ST, MAXINF, HC>: slices of the due giant rows, ahead of the sweep that merges them
+void Run::launch_giant_part(uint32_t sweep, bool nar, const FusedParams &P) {
+  const dim3 ggrid(g->n_giant_slices, B);
+  with_flag(nar, [&](auto c) { constexpr bool NARROW = c; using ST = StateWord<NARROW>;
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c && !NARROW;
+  with_flag(P.hc != 0u, [&](auto c) { constexpr bool HC = c;
+    hipLaunchKernelGGL((k_giant_part<ST, MAXINF, HC>), ggrid, dim3(256), 0, s, d_fg, (const int *)d_changed, (int)sweep, (const uint32_t *)d_stamp, n,
+                       (const ST *)d_st, (const uint32_t *)d_roots, net_nh, ignore_ovl, P);
+  }); }); });
+}
+
+// k_fused<ST, MAXINF, COUNT, UNITS>: COUNT = HSPF_RUN_COUNT_ROWS, UNITS = the graph has heavy chunks cut into work units
+void Run::launch_fused(uint32_t sweep, bool nar, const FusedParams &P) {
+  with_flag(nar, [&](auto c) { constexpr bool NARROW = c; using ST = StateWord<NARROW>;
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c && !NARROW;
+  with_flag(count_rows, [&](auto c) { constexpr bool COUNT = c;
+  with_flag(g->n_heavy_chunks != 0, [&](auto c) { constexpr bool UNITS = c;
+    hipLaunchKernelGGL((k_fused<ST, MAXINF, COUNT, UNITS>), fgrid, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n,
+                       gd.in_ptr, gd.out_ptr, gd.vflags, (ST *)d_st, d_roots, d_lf, net_nh, ignore_ovl, P, gd.in_src, gd.in_w, gd.out_dst, gd.e_in);
+  }); }); }); });
+}
+
+// k_fused_lean<COUNT, MODE, HEAD, BMAJ, ZROWS>.  MODE 0: a stamped sweep (HEAD: one of the plan's head sweeps, which count
+// their due rows), 1: dense passes (BMAJ: in batch-major placement; PassGrid::blocks = row blocks of one batch), 2: the
+// all-due stamped sweep.  ZROWS = the graph has RF_ZERO rows and is not hop-count-like (the count is kept current by
+// every patch path: cost-only, structural-incremental, rebuild); without them the kernel carries no zero-cost row path
+// and no LF_DYN bookkeeping
+void Run::launch_lean(LeanPass what, uint32_t sweep, const FusedParams &P, dim3 lgrid, PassGrid pgr, uint32_t base, uint32_t thr) {
+  auto launch = [&](auto mode, auto head, auto bmaj) { constexpr int MODE = mode; constexpr bool HEAD = head, BMAJ = bmaj;
+    static_assert((!HEAD || MODE == 0) && (!BMAJ || MODE == 1), "HEAD belongs to the stamped sweep, BMAJ to the dense passes");
+    with_flag(count_rows, [&](auto c) { constexpr bool COUNT = c;
+    with_flag(dyn_rows(), [&](auto c) { constexpr bool ZROWS = c;
+      hipLaunchKernelGGL((k_fused_lean<COUNT, MODE, HEAD, BMAJ, ZROWS>), lgrid, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n,
+                         (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (uint32_t *)d_st, (const uint32_t *)g->d_ell_od, d_roots, d_lf, net_nh,
+                         ignore_ovl, P, (uint32_t *)ctx->swcnt.p, B, pgr, base, thr);
+    }); });
+  };
+  using std::false_type; using std::true_type; using std::integral_constant;
+  switch (what) {
+    case LeanPass::Head:            return launch(integral_constant<int, 0>{}, true_type{}, false_type{});
+    case LeanPass::Tail:            return launch(integral_constant<int, 0>{}, false_type{}, false_type{});
+    case LeanPass::Dense:           return launch(integral_constant<int, 1>{}, false_type{}, false_type{});
+    case LeanPass::DenseBatchMajor: return launch(integral_constant<int, 1>{}, false_type{}, true_type{});
+    case LeanPass::AllDue:          return launch(integral_constant<int, 2>{}, false_type{}, false_type{});
+  }
+}
+
 // One fixed point over the packed state.  mode 0: 8-byte state, 1: 4-byte state (k_fused), 2: 4-byte state, lean sweep (k_fused_lean).
 int Run::fused_run(int mode) {
-      const bool nar = mode != 0, use_lean = mode == 2;
-      const FusedParams P = use_lean ? fp_lean : (nar ? fp_narrow : fp_wide);
-      const size_t esz = nar ? 4 : 8;
-      OutDev ode = od;                                           // packed results: the emit writes the state words of THIS width
-      if (pk) {
-        // a DEVICE destination is written in place by the emit: its size is checked BEFORE anything is launched (ADVICE r05:
-        // the check used to sit in deliver(), behind the kernels that had already overrun a short buffer)
-        if (!pk->host && !pk->dev_stage && (pk->row_off + (size_t)n_roots) * n * esz > pk->cap) {
-          ctx->last_error = "packed results: buffer too small, need " + std::to_string((pk->row_off + (size_t)n_roots) * n * esz) + " bytes";
-          return HSPF_E_INVAL;
-        }
-        ode.packed = pk_dev(esz); pk_mode = mode;
-      }
-      const uint32_t ns = use_lean ? n + 1u : n;                 // rows per batch slab (the lean sweep's pad row)
-      const size_t rows = (size_t)B * ns * 64;                   // (state rows of THIS width: shadows the member on purpose)
-      const uint32_t fillw = use_lean ? P.infw : 0xFFFFFFFFu;
-      // one fill launch (state, stamps, row flags, sweep flags, status bits, row counter), one launch for the roots
-      uint32_t pre_zeroed = std::min<uint32_t>(CHANGED_CAP, ctx->est_fused + 4096);
-      const bool have = pf.valid && pf.build_id == g->build_id && pf.n == n && pf.B == B && pf.esz == (uint32_t)esz &&
-                        pf.ns == ns && pf.fillw == fillw &&
-                        pf.L == L && (pf.kcnt || !count_rows) && pf.n_changed >= std::min<uint32_t>(CHANGED_CAP, 2u);
-      pf.valid = false;
-      if (have) pre_zeroed = pf.n_changed;      // run_phase clears whatever it needs beyond that
-      else
-        hipLaunchKernelGGL(k_init_fill, dim3(2048), dim3(256), 0, s, (uint4 *)d_st, rows * esz / 16, fillw, d_stamp, (size_t)B * n,
-                           (const uint8_t *)g->d_rowflags, (uint8_t *)ctx->hnb.p, n, d_changed, pre_zeroed, d_lf, L,
-                           count_rows ? d_kcnt : (uint32_t *)nullptr, -1, (uint32_t *)ctx->swcnt.p, ctx->swcnt.p ? LEAN_CTL_WORDS : 0u);
-      last_esz = (uint32_t)esz; last_ns = ns; last_fillw = fillw;
-      ctx->prefill.valid = false;                                // (a speculative fill of an earlier fused_run of this call is gone now)
-      spec_done = false;
-      spec_fill = nullptr;
-      spec_fill = [&, esz, fillw, rows](uint32_t last_sweep) {
-          const uint32_t nz = std::min<uint32_t>(CHANGED_CAP, ctx->est_fused + 4096);
-          // (the emit in front of this launch has reset the state slab under the same guard: stamps, flags and counters are left)
-          hipLaunchKernelGGL(k_init_fill, dim3(emit_reset ? 256 : 2048), dim3(256), 0, s, (uint4 *)d_st, emit_reset ? (size_t)0 : rows * esz / 16, fillw, d_stamp, (size_t)B * n,
-                             (const uint8_t *)g->d_rowflags, (uint8_t *)ctx->hnb.p, n, d_changed, nz, d_lf, L, d_kcnt, (int)last_sweep, (uint32_t *)ctx->swcnt.p, ctx->swcnt.p ? LEAN_CTL_WORDS : 0u);
-          spec_nz = nz;
-          spec_done = true;                                      // (valid only if the host finds the chunk converged, see below)
-        };
-      if (use_lean) st.dbg[0] = 1;                               // hspf_stats::dbg[0]: 1 = the run took the lean sweep
-      // k_emit_fused checks the lean state's fields on FINAL words; an emit behind a chunk that had not converged saw
-      // transient ones: its LF_OVERFLOW bits are dropped before the next chunk (the final emit tests every word again)
-      on_retry = nullptr;
-      if (use_lean) on_retry = [&]() { hipLaunchKernelGGL(k_clear_lane_flag, dim3((L + 255) / 256), dim3(256), 0, s, d_lf, L, (uint32_t)LF_OVERFLOW); };
-      if (giant && hipMemsetAsync(ctx->giant_part.p, 0, giant_tags * 4, s) != hipSuccess) { ctx->last_error = "giant tags"; return HSPF_E_HIP; }
-      const bool dyn_parts = g->n_zero_rows && !g->hopcount_like;      // FusedGraph::dyn_part is in use
-      const bool zrows = dyn_parts;                                    // k_fused_lean<.., ZROWS>: the same condition
-      if (use_lean && zrows) st.dbg[0] |= 2u;                          // hspf_stats::dbg[0] bit 1: ... with the zero-cost row instantiation
-      if (dyn_parts && hipMemsetAsync(ctx->dyn_part.p, 0, (size_t)DYN_PARTS * L * 4, s) != hipSuccess) { ctx->last_error = "dyn partials"; return HSPF_E_HIP; }
-      if (nar) hipLaunchKernelGGL((k_init_fused<uint32_t>), dim3((L + 3) / 4), dim3(256), 0, s, gd, (uint32_t *)d_st, d_stamp, (uint8_t *)ctx->hnb.p, d_roots, tabs, L, ns);
-      else     hipLaunchKernelGGL((k_init_fused<uint64_t>), dim3((L + 3) / 4), dim3(256), 0, s, gd, d_st, d_stamp, (uint8_t *)ctx->hnb.p, d_roots, tabs, L, ns);
-      uint32_t n_f = 0;
-      const bool maxinf = g->max_path_metric == HSPF_DIST_INF;
-      // The lean sweep's plan (k_fused_lean): launch index -> what the launch is.  [0, h) head sweeps (stamped, counting
-      // their due rows; skipped on the device once one of them saw the frontier cover `lean_dense_pct` of the rows),
-      // [h, h + nd) the dense stretch (launches of up to HSPF_DENSE_PASSES passes, `P` passes in all; a pass is skipped on
-      // the device when the passes before it changed less than `lean_stay_pct` of the rows), h + nd the all-due stamped
-      // sweep that makes the stamps valid again, then stamped tail sweeps until one changes nothing.  h and P are what
-      // the previous run of this context used (+ 1 spare pass): a cost or structural patch, other roots, another graph
-      // all start from there, and a fresh context from (4, 16).  HSPF_VARIANT bit19: stamped sweeps only.
-      const bool plan_on = use_lean && !(ctx->variant & 524288u);
-      // several passes per launch only where a pass — all batches of the call — is long against what the chip holds at
-      // once (2 048 workgroups): a short pass would run NEXT TO its successor instead of ahead of it
-      const bool multi = ctx->lean_dense_passes > 1u && (uint64_t)fgrid.x * B >= ctx->lean_multi_min_wgs;
-      const uint32_t per_launch = multi ? (uint32_t)std::min<uint64_t>(ctx->lean_dense_passes, ((1ull << 31) - 1u) / ((uint64_t)fgrid.x * B)) : 1u;
-      const uint32_t plan_h = plan_on ? std::min(ctx->lean_head, 60u) : 0u;
-      const uint32_t plan_P = plan_on ? std::min(std::max(ctx->lean_passes, 2u), std::min(ctx->lean_max_passes, 62u)) : 0u;
-      const uint32_t plan_nd = plan_on ? (plan_P + per_launch - 1u) / per_launch : 0u;
-      const uint64_t all_rows = (uint64_t)n * B;
-      // thresholds in sampled units (LEAN_SAMPLE): at least 1, so that "nothing counted" always reads as below
-      const uint32_t thr_enter = (uint32_t)std::min<uint64_t>(0xFFFFFFF0u, std::max<uint64_t>(1u, all_rows * ctx->lean_dense_pct / (100u * LEAN_SAMPLE)));
-      const uint32_t thr_stay = ctx->lean_stay_pct == 0u ? 0u : (uint32_t)std::min<uint64_t>(0xFFFFFFF0u, std::max<uint64_t>(1u, all_rows * ctx->lean_stay_pct / (100u * LEAN_SAMPLE)));
-      if (use_lean) {
-        int e2 = ensure(ctx, ctx->swcnt, LEAN_CTL_WORDS * 4, false);      // (the kernel takes the pointer in every mode)
-        if (e2) return e2;
-      }
-      uint32_t *d_ctl = (uint32_t *)ctx->swcnt.p;
-      // the run's launch-ahead estimate must reach past the all-due sweep: a chunk that ended inside the plan would pay a
-      // read-back (and an emit) for nothing
-      // (a context's first fused run starts from est_fused = 12: with the plan in front of them that would be six tail sweeps,
-      // and every further chunk costs a read-back and a speculative emit — twelve tail sweeps are launched ahead instead;
-      // a surplus launch exits at once)
-      if (plan_on) ctx->est_fused = std::max(ctx->est_fused, plan_h + plan_nd + (ctx->est_seen ? 2u : 13u));
-      ctx->est_seen = true;
-      rb_ctl = plan_on ? d_ctl : nullptr;
-      int r2 = run_phase(ctx->est_fused, pre_zeroed, [&](uint32_t sweep) {
-#define HSPF_LAUNCH_FUSED2(ST_, MI_, CN_, UN_, stp_) hipLaunchKernelGGL((k_fused<ST_, MI_, CN_, UN_>), fgrid, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n, gd.in_ptr, gd.out_ptr, gd.vflags, stp_, d_roots, d_lf, net_nh, ignore_ovl, P, gd.in_src, gd.in_w, gd.out_dst, gd.e_in)
-#define HSPF_LAUNCH_FUSED(ST_, MI_, CN_, stp_) do { if (units) HSPF_LAUNCH_FUSED2(ST_, MI_, CN_, true, stp_); else HSPF_LAUNCH_FUSED2(ST_, MI_, CN_, false, stp_); } while (0)
-        const bool units = g->n_heavy_chunks != 0;
-        if (use_lean) {
-          // k_fused_lean<COUNT, MODE, HEAD, BMAJ, ZROWS>: ZROWS = the graph has RF_ZERO rows and is not hop-count-like (the
-          // count is kept current by every patch path: cost-only, structural-incremental, rebuild); without them the
-          // kernel carries no zero-cost row path and no LF_DYN bookkeeping
-#define HSPF_LAUNCH_LEAN3(CN_, MD_, HD_, BM_, ZR_, grid_, pgr_, base_, thr_) hipLaunchKernelGGL((k_fused_lean<CN_, MD_, HD_, BM_, ZR_>), grid_, dim3(256), 0, s, d_fg, d_changed, (int)sweep, d_stamp, (const uint8_t *)ctx->hnb.p, n, (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (uint32_t *)d_st, (const uint32_t *)g->d_ell_od, d_roots, d_lf, net_nh, ignore_ovl, P, d_ctl, B, pgr_, base_, thr_)
-#define HSPF_LAUNCH_LEAN2(CN_, MD_, HD_, BM_, grid_, pgr_, base_, thr_) do { if (zrows) HSPF_LAUNCH_LEAN3(CN_, MD_, HD_, BM_, true, grid_, pgr_, base_, thr_); else HSPF_LAUNCH_LEAN3(CN_, MD_, HD_, BM_, false, grid_, pgr_, base_, thr_); } while (0)
-#define HSPF_LAUNCH_LEAN_C(MD_, HD_, grid_, pgr_, base_, thr_) do { if (count_rows) HSPF_LAUNCH_LEAN2(true, MD_, HD_, false, grid_, pgr_, base_, thr_); else HSPF_LAUNCH_LEAN2(false, MD_, HD_, false, grid_, pgr_, base_, thr_); } while (0)
-          // dense launch in batch-major placement (k_fused_lean<.., BMAJ, ..>; PassGrid::blocks = row blocks of one batch)
-#define HSPF_LAUNCH_LEAN_B(MD_, HD_, grid_, pgr_, base_, thr_) do { if (count_rows) HSPF_LAUNCH_LEAN2(true, MD_, HD_, true, grid_, pgr_, base_, thr_); else HSPF_LAUNCH_LEAN2(false, MD_, HD_, true, grid_, pgr_, base_, thr_); } while (0)
-          // at least 8 batches: each XCD takes whole batches (their state stays in its L2 across the passes); HSPF_VARIANT bit 24: off (A/B)
-          const uint32_t bm_blocks = (n + (uint32_t)FVPB - 1u) / (uint32_t)FVPB;
-          const bool bmaj = B >= 8u && 8ull * ((B + 7u) / 8u) * bm_blocks * per_launch < (1ull << 31);
-          const dim3 bgrid(8u * ((B + 7u) / 8u) * bm_blocks);        // one pass over all batches, batch-major
-          // (the stamped sweeps keep the row-major placement: in batch-major form they were slower — 4.48 against 4.33 ms for the
-          // ten areas of configs[3], profiles/r04_notes.md r04y)
-          const PassGrid pg0{};                                    // (the stamped modes: 2-D grid, no passes)
-          if (sweep < plan_h) HSPF_LAUNCH_LEAN_C(0, true, fgrid, pg0, 0u, thr_enter);
-          else if (sweep < plan_h + plan_nd) {                     // np passes, 1-D
-            const uint32_t base = (sweep - plan_h) * per_launch, np = std::min(per_launch, plan_P - base);
-            if (bmaj) HSPF_LAUNCH_LEAN_B(1, false, dim3(bgrid.x * np), pass_grid(bgrid.x, bm_blocks), base, thr_stay);
-            else      HSPF_LAUNCH_LEAN_C(1, false, dim3(fgrid.x * B * np), pass_grid(fgrid.x * B, fgrid.x), base, thr_stay);
-          } else if (plan_on && sweep == plan_h + plan_nd) HSPF_LAUNCH_LEAN_C(2, false, fgrid, pg0, 0u, 0u);
-          else HSPF_LAUNCH_LEAN_C(0, false, fgrid, pg0, 0u, 0u);
-#undef HSPF_LAUNCH_LEAN_C
-#undef HSPF_LAUNCH_LEAN_B
-#undef HSPF_LAUNCH_LEAN2
-#undef HSPF_LAUNCH_LEAN3
-          return;
-        }
-        if (giant) {                                   // slices of the due giant rows, ahead of the sweep that merges them
-          const dim3 ggrid(g->n_giant_slices, B);
-#define HSPF_LAUNCH_GIANT(ST_, MI_, stp_) do { if (P.hc) hipLaunchKernelGGL((k_giant_part<ST_, MI_, true>), ggrid, dim3(256), 0, s, d_fg, (const int *)d_changed, (int)sweep, (const uint32_t *)d_stamp, n, (const ST_ *)stp_, (const uint32_t *)d_roots, net_nh, ignore_ovl, P); \
-                                            else hipLaunchKernelGGL((k_giant_part<ST_, MI_, false>), ggrid, dim3(256), 0, s, d_fg, (const int *)d_changed, (int)sweep, (const uint32_t *)d_stamp, n, (const ST_ *)stp_, (const uint32_t *)d_roots, net_nh, ignore_ovl, P); } while (0)
-          if (nar)         HSPF_LAUNCH_GIANT(uint32_t, false, (uint32_t *)d_st);
-          else if (maxinf) HSPF_LAUNCH_GIANT(uint64_t, true, d_st);
-          else             HSPF_LAUNCH_GIANT(uint64_t, false, d_st);
-#undef HSPF_LAUNCH_GIANT
-        }
-        if (count_rows) {
-          if (nar)         HSPF_LAUNCH_FUSED(uint32_t, false, true, (uint32_t *)d_st);
-          else if (maxinf) HSPF_LAUNCH_FUSED(uint64_t, true, true, d_st);
-          else             HSPF_LAUNCH_FUSED(uint64_t, false, true, d_st);
-        } else {
-          if (nar)         HSPF_LAUNCH_FUSED(uint32_t, false, false, (uint32_t *)d_st);
-          else if (maxinf) HSPF_LAUNCH_FUSED(uint64_t, true, false, d_st);
-          else             HSPF_LAUNCH_FUSED(uint64_t, false, false, d_st);
-        }
-#undef HSPF_LAUNCH_FUSED2
-#undef HSPF_LAUNCH_FUSED
-      }, n_f, [&]() {
-        // results out of the packed state (speculative: valid when this chunk reached the fixed point and, for the
-        // 4-byte state, no lane overflowed; otherwise redone behind the next chunk / the wide run)
-        (void)hipEventRecord(ctx->ev[2], s);
-        if (dyn_parts) hipLaunchKernelGGL(k_lf_reduce, dim3((L + 255) / 256), dim3(256), 0, s, d_lf, (const uint32_t *)ctx->dyn_part.p, L);
-        // (with the speculative fill on, the emit resets the tiles it has read: first half of the next run's scratch fill)
-        const int rg = spec_fill ? (int)chunk_last : -1;
-        emit_reset = rg >= 0;
-        if (nar) hipLaunchKernelGGL((k_emit_fused<uint32_t>), dim3((n + 63) / 64, B), dim3(256), 0, s, n, n_roots, (uint32_t *)d_st, P, ode, ns, use_lean ? d_lf : (uint32_t *)nullptr, (const int *)d_changed, rg, fillw);
-        else     hipLaunchKernelGGL((k_emit_fused<uint64_t>), dim3((n + 63) / 64, B), dim3(256), 0, s, n, n_roots, d_st, P, ode, ns, (uint32_t *)nullptr, (const int *)d_changed, rg, fillw);
-        (void)hipEventRecord(ctx->ev[4], s);      // "results in place": the phase's read-back synchronises behind it
-        tail_done = true;
-      });
-      spec_fill = nullptr;
-      if (r2) return r2;
-      // run_phase returned: its last chunk converged, so the speculative fill behind that chunk's read-back went through
-      if (spec_done) ctx->prefill = hspf_ctx::Prefill{true, g->build_id, n, B, (uint32_t)esz, spec_nz, L, true, ns, fillw};
-      ctx->est_fused = n_f + 1;
-      st.n_relax_launches += n_f;
-      if (count_rows) for (uint32_t i = 0; i < 256; ++i) st.rows_recomputed += ctx->h_lane_flags[L + i];
-      if (plan_on) {
-        // what the plan's launches decided (counters read back with the sweep flags): the next plan
-        const uint32_t *hc = ctx->h_lane_flags + L + 256;
-        uint32_t trig = plan_h;                                    // first head sweep that was skipped (the sentinel), or none
-        for (uint32_t k = 0; k < plan_h; ++k) if (hc[LEAN_CTL_DUE + k * LEAN_CTL_STRIDE] == LEAN_SENTINEL) { trig = k; break; }
-        uint32_t used = 0;                                         // dense passes that did work
-        for (uint32_t k = 0; k < plan_P; ++k) if (hc[LEAN_CTL_PCH + k * LEAN_CTL_STRIDE] != 0u) used = k + 1u;
-        // hspf_stats::dbg[1] (lean sweep): dense passes that did work | head sweeps that ran << 8 | passes planned << 16 | head sweeps planned << 24
-        st.dbg[1] = (used & 0xFFu) | ((trig & 0xFFu) << 8) | ((plan_P & 0xFFu) << 16) | ((plan_h & 0x7Fu) << 24);
-        // every head sweep ran and the last one still was below the threshold: one more next time (the dense stretch
-        // starts a sweep later); some were skipped: exactly as many as ran
-        const bool last_triggers = plan_h != 0u && hc[LEAN_CTL_DUE + (plan_h - 1u) * LEAN_CTL_STRIDE] != LEAN_SENTINEL && hc[LEAN_CTL_DUE + (plan_h - 1u) * LEAN_CTL_STRIDE] >= thr_enter;
-        if (trig < plan_h) ctx->lean_head = std::max(trig, 1u);
-        else if (plan_h != 0u && !last_triggers && used >= 2u) ctx->lean_head = std::min(plan_h + 1u, 60u);
-        // the stretch: one spare pass beyond what did work; a stretch that used every pass grows by half
-        ctx->lean_passes = used >= plan_P ? std::min(ctx->lean_max_passes, plan_P + plan_P / 2u + 1u) : std::max(used + 1u, 2u);
-      }
-      return HSPF_OK;
+  const bool nar = mode != 0, use_lean = mode == 2;
+  const FusedParams P = use_lean ? fp_lean : (nar ? fp_narrow : fp_wide);
+  const size_t esz = nar ? 4 : 8;
+  OutDev ode = od;                                           // packed results: the emit writes the state words of THIS width
+  if (pk) {
+    // a DEVICE destination is written in place by the emit: its size is checked BEFORE anything is launched (ADVICE r05:
+    // the check used to sit in deliver(), behind the kernels that had already overrun a short buffer)
+    if (!pk->host && !pk->dev_stage && (pk->row_off + (size_t)n_roots) * n * esz > pk->cap) {
+      ctx->last_error = "packed results: buffer too small, need " + std::to_string((pk->row_off + (size_t)n_roots) * n * esz) + " bytes";
+      return HSPF_E_INVAL;
     }
+    ode.packed = pk_dev(esz); pk_mode = mode;
+  }
+  const uint32_t ns = use_lean ? n + 1u : n;                 // rows per batch slab (the lean sweep's pad row)
+  const size_t rows = (size_t)B * ns * 64;                   // (state rows of THIS width: shadows the member on purpose)
+  const uint32_t fillw = use_lean ? P.infw : 0xFFFFFFFFu;
+  // one fill launch (state, stamps, row flags, sweep flags, status bits, row counter), one launch for the roots
+  uint32_t pre_zeroed = std::min<uint32_t>(CHANGED_CAP, ctx->est_fused + 4096);
+  const bool have = pf.valid && pf.build_id == g->build_id && pf.n == n && pf.B == B && pf.esz == (uint32_t)esz &&
+                    pf.ns == ns && pf.fillw == fillw &&
+                    pf.L == L && (pf.kcnt || !count_rows) && pf.n_changed >= std::min<uint32_t>(CHANGED_CAP, 2u);
+  pf.valid = false;
+  if (have) pre_zeroed = pf.n_changed;      // run_phase clears whatever it needs beyond that
+  else
+    hipLaunchKernelGGL(k_init_fill, dim3(2048), dim3(256), 0, s, (uint4 *)d_st, rows * esz / 16, fillw, d_stamp, (size_t)B * n,
+                       (const uint8_t *)g->d_rowflags, (uint8_t *)ctx->hnb.p, n, d_changed, pre_zeroed, d_lf, L,
+                       count_rows ? d_kcnt : (uint32_t *)nullptr, -1, (uint32_t *)ctx->swcnt.p, ctx->swcnt.p ? LEAN_CTL_WORDS : 0u);
+  last_esz = (uint32_t)esz; last_ns = ns; last_fillw = fillw;
+  ctx->prefill.valid = false;                                // (a speculative fill of an earlier fused_run of this call is gone now)
+  spec_done = false;
+  spec_fill = nullptr;
+  spec_fill = [&, esz, fillw, rows](uint32_t last_sweep) {
+    const uint32_t nz = std::min<uint32_t>(CHANGED_CAP, ctx->est_fused + 4096);
+    // (the emit in front of this launch has reset the state slab under the same guard: stamps, flags and counters are left)
+    hipLaunchKernelGGL(k_init_fill, dim3(emit_reset ? 256 : 2048), dim3(256), 0, s, (uint4 *)d_st, emit_reset ? (size_t)0 : rows * esz / 16, fillw,
+                       d_stamp, (size_t)B * n, (const uint8_t *)g->d_rowflags, (uint8_t *)ctx->hnb.p, n, d_changed, nz, d_lf, L, d_kcnt, (int)last_sweep,
+                       (uint32_t *)ctx->swcnt.p, ctx->swcnt.p ? LEAN_CTL_WORDS : 0u);
+    spec_nz = nz;
+    spec_done = true;                                      // (valid only if the host finds the chunk converged, see below)
+  };
+  if (use_lean) st.dbg[0] = 1;                               // hspf_stats::dbg[0]: 1 = the run took the lean sweep
+  // k_emit_fused checks the lean state's fields on FINAL words; an emit behind a chunk that had not converged saw
+  // transient ones: its LF_OVERFLOW bits are dropped before the next chunk (the final emit tests every word again)
+  on_retry = nullptr;
+  if (use_lean) on_retry = [&]() { hipLaunchKernelGGL(k_clear_lane_flag, dim3((L + 255) / 256), dim3(256), 0, s, d_lf, L, (uint32_t)LF_OVERFLOW); };
+  if (giant && hipMemsetAsync(ctx->giant_part.p, 0, giant_tags * 4, s) != hipSuccess) { ctx->last_error = "giant tags"; return HSPF_E_HIP; }
+  const bool dyn_parts = dyn_rows();                               // FusedGraph::dyn_part is in use; k_fused_lean<.., ZROWS>: the same condition
+  if (use_lean && dyn_parts) st.dbg[0] |= 2u;                      // hspf_stats::dbg[0] bit 1: ... with the zero-cost row instantiation
+  if (dyn_parts && hipMemsetAsync(ctx->dyn_part.p, 0, (size_t)DYN_PARTS * L * 4, s) != hipSuccess) { ctx->last_error = "dyn partials"; return HSPF_E_HIP; }
+  launch_init_fused(nar, ns);
+  uint32_t n_f = 0;
+  // The lean sweep's plan (k_fused_lean): launch index -> what the launch is.  [0, h) head sweeps (stamped, counting
+  // their due rows; skipped on the device once one of them saw the frontier cover `lean_dense_pct` of the rows),
+  // [h, h + nd) the dense stretch (launches of up to HSPF_DENSE_PASSES passes, `P` passes in all; a pass is skipped on
+  // the device when the passes before it changed less than `lean_stay_pct` of the rows), h + nd the all-due stamped
+  // sweep that makes the stamps valid again, then stamped tail sweeps until one changes nothing.  h and P are what
+  // the previous run of this context used (+ 1 spare pass): a cost or structural patch, other roots, another graph
+  // all start from there, and a fresh context from (4, 16).  HSPF_VARIANT bit19: stamped sweeps only.
+  const bool plan_on = use_lean && !(ctx->variant & hspf_ctx::VAR_LEAN_NO_PLAN);
+  // several passes per launch only where a pass — all batches of the call — is long against what the chip holds at
+  // once (2 048 workgroups): a short pass would run NEXT TO its successor instead of ahead of it
+  const bool multi = ctx->lean_dense_passes > 1u && (uint64_t)fgrid.x * B >= ctx->lean_multi_min_wgs;
+  const uint32_t per_launch = multi ? (uint32_t)std::min<uint64_t>(ctx->lean_dense_passes, ((1ull << 31) - 1u) / ((uint64_t)fgrid.x * B)) : 1u;
+  const uint32_t plan_h = plan_on ? std::min(ctx->lean_head, 60u) : 0u;
+  const uint32_t plan_P = plan_on ? std::min(std::max(ctx->lean_passes, 2u), std::min(ctx->lean_max_passes, 62u)) : 0u;
+  const uint32_t plan_nd = plan_on ? (plan_P + per_launch - 1u) / per_launch : 0u;
+  const uint64_t all_rows = (uint64_t)n * B;
+  // thresholds in sampled units (LEAN_SAMPLE): at least 1, so that "nothing counted" always reads as below
+  const uint32_t thr_enter = (uint32_t)std::min<uint64_t>(0xFFFFFFF0u, std::max<uint64_t>(1u, all_rows * ctx->lean_dense_pct / (100u * LEAN_SAMPLE)));
+  const uint32_t thr_stay = ctx->lean_stay_pct == 0u ? 0u : (uint32_t)std::min<uint64_t>(0xFFFFFFF0u, std::max<uint64_t>(1u, all_rows * ctx->lean_stay_pct / (100u * LEAN_SAMPLE)));
+  if (use_lean) {
+    int e2 = ensure(ctx, ctx->swcnt, LEAN_CTL_WORDS * 4, false);      // (the kernel takes the pointer in every mode)
+    if (e2) return e2;
+  }
+  uint32_t *d_ctl = (uint32_t *)ctx->swcnt.p;
+  // the run's launch-ahead estimate must reach past the all-due sweep: a chunk that ended inside the plan would pay a
+  // read-back (and an emit) for nothing
+  // (a context's first fused run starts from est_fused = 12: with the plan in front of them that would be six tail sweeps,
+  // and every further chunk costs a read-back and a speculative emit — twelve tail sweeps are launched ahead instead;
+  // a surplus launch exits at once)
+  if (plan_on) ctx->est_fused = std::max(ctx->est_fused, plan_h + plan_nd + (ctx->est_seen ? 2u : 13u));
+  ctx->est_seen = true;
+  rb_ctl = plan_on ? d_ctl : nullptr;
+  int r2 = run_phase(ctx->est_fused, pre_zeroed, [&](uint32_t sweep) {
+    if (use_lean) {
+      // at least 8 batches: each XCD takes whole batches (their state stays in its L2 across the passes; the HSPF_VARIANT bit
+      // that switched this off for A/B runs is gone)
+      const uint32_t bm_blocks = (n + (uint32_t)FVPB - 1u) / (uint32_t)FVPB;
+      const bool bmaj = B >= 8u && 8ull * ((B + 7u) / 8u) * bm_blocks * per_launch < (1ull << 31);
+      const dim3 bgrid(8u * ((B + 7u) / 8u) * bm_blocks);        // one pass over all batches, batch-major
+      // (the stamped sweeps keep the row-major placement: in batch-major form they were slower — 4.48 against 4.33 ms for the
+      // ten areas of configs[3], profiles/r04_notes.md r04y)
+      const PassGrid pg0{};                                    // (the stamped modes: 2-D grid, no passes)
+      if (sweep < plan_h) launch_lean(LeanPass::Head, sweep, P, fgrid, pg0, 0u, thr_enter);
+      else if (sweep < plan_h + plan_nd) {                     // np passes, 1-D
+        const uint32_t base = (sweep - plan_h) * per_launch, np = std::min(per_launch, plan_P - base);
+        if (bmaj) launch_lean(LeanPass::DenseBatchMajor, sweep, P, dim3(bgrid.x * np), pass_grid(bgrid.x, bm_blocks), base, thr_stay);
+        else      launch_lean(LeanPass::Dense, sweep, P, dim3(fgrid.x * B * np), pass_grid(fgrid.x * B, fgrid.x), base, thr_stay);
+      } else if (plan_on && sweep == plan_h + plan_nd) launch_lean(LeanPass::AllDue, sweep, P, fgrid, pg0, 0u, 0u);
+      else launch_lean(LeanPass::Tail, sweep, P, fgrid, pg0, 0u, 0u);
+      return;
+    }
+    if (giant) launch_giant_part(sweep, nar, P);
+    launch_fused(sweep, nar, P);
+  }, n_f, [&]() {
+    // results out of the packed state (speculative: valid when this chunk reached the fixed point and, for the
+    // 4-byte state, no lane overflowed; otherwise redone behind the next chunk / the wide run)
+    (void)hipEventRecord(ctx->ev[2], s);
+    if (dyn_parts) hipLaunchKernelGGL(k_lf_reduce, dim3((L + 255) / 256), dim3(256), 0, s, d_lf, (const uint32_t *)ctx->dyn_part.p, L);
+    // (with the speculative fill on, the emit resets the tiles it has read: first half of the next run's scratch fill)
+    const int rg = spec_fill ? (int)chunk_last : -1;
+    emit_reset = rg >= 0;
+    launch_emit_fused(nar, P, ode, ns, use_lean ? d_lf : (uint32_t *)nullptr, rg, fillw);
+    (void)hipEventRecord(ctx->ev[4], s);      // "results in place": the phase's read-back synchronises behind it
+    tail_done = true;
+  });
+  spec_fill = nullptr;
+  if (r2) return r2;
+  // run_phase returned: its last chunk converged, so the speculative fill behind that chunk's read-back went through
+  if (spec_done) ctx->prefill = hspf_ctx::Prefill{true, g->build_id, n, B, (uint32_t)esz, spec_nz, L, true, ns, fillw};
+  ctx->est_fused = n_f + 1;
+  st.n_relax_launches += n_f;
+  if (count_rows) for (uint32_t i = 0; i < 256; ++i) st.rows_recomputed += ctx->h_lane_flags[L + i];
+  if (plan_on) {
+    // what the plan's launches decided (counters read back with the sweep flags): the next plan
+    const uint32_t *hc = ctx->h_lane_flags + L + 256;
+    uint32_t trig = plan_h;                                    // first head sweep that was skipped (the sentinel), or none
+    for (uint32_t k = 0; k < plan_h; ++k) if (hc[LEAN_CTL_DUE + k * LEAN_CTL_STRIDE] == LEAN_SENTINEL) { trig = k; break; }
+    uint32_t used = 0;                                         // dense passes that did work
+    for (uint32_t k = 0; k < plan_P; ++k) if (hc[LEAN_CTL_PCH + k * LEAN_CTL_STRIDE] != 0u) used = k + 1u;
+    // hspf_stats::dbg[1] (lean sweep): dense passes that did work | head sweeps that ran << 8 | passes planned << 16 | head sweeps planned << 24
+    st.dbg[1] = (used & 0xFFu) | ((trig & 0xFFu) << 8) | ((plan_P & 0xFFu) << 16) | ((plan_h & 0x7Fu) << 24);
+    // every head sweep ran and the last one still was below the threshold: one more next time (the dense stretch
+    // starts a sweep later); some were skipped: exactly as many as ran
+    const bool last_triggers = plan_h != 0u && hc[LEAN_CTL_DUE + (plan_h - 1u) * LEAN_CTL_STRIDE] != LEAN_SENTINEL && hc[LEAN_CTL_DUE + (plan_h - 1u) * LEAN_CTL_STRIDE] >= thr_enter;
+    if (trig < plan_h) ctx->lean_head = std::max(trig, 1u);
+    else if (plan_h != 0u && !last_triggers && used >= 2u) ctx->lean_head = std::min(plan_h + 1u, 60u);
+    // the stretch: one spare pass beyond what did work; a stretch that used every pass grows by half
+    ctx->lean_passes = used >= plan_P ? std::min(ctx->lean_max_passes, plan_P + plan_P / 2u + 1u) : std::max(used + 1u, 2u);
+  }
+  return HSPF_OK;
+}
+
+void Run::launch_lv(const LvArgs &la, dim3 lgrid) {               // k_lv<MAXINF>
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c;
+    hipLaunchKernelGGL((k_lv<MAXINF>), lgrid, dim3(256), 0, s, la);
+  });
+}
 
 // A few roots on a large graph: lane = vertex (k_lv), one launch per sweep over the root's own row-major state.
 int Run::lv_run() {
-      int r2;
-      if ((r2 = ensure(ctx, ctx->stamp, (size_t)n_roots * n * 4))) return r2;
-      uint32_t *a_stamp = (uint32_t *)ctx->stamp.p;
-      hipError_t er = hipMemsetAsync(d_lf, 0, (size_t)L * 4, s);
-      if (er == hipSuccess) er = hipMemsetAsync(d_st, 0xFF, (size_t)n_roots * n * 8, s);
-      if (er == hipSuccess) er = hipMemsetAsync(a_stamp, 0, (size_t)n_roots * n * 4, s);
-      if (er == hipSuccess && count_rows) er = hipMemsetAsync(d_kcnt, 0, 256 * 4, s);
-      if (er != hipSuccess) { ctx->last_error = std::string("lv init: ") + hipGetErrorString(er); return HSPF_E_HIP; }
-      hipLaunchKernelGGL(k_init_lv, dim3((n_roots + 63) / 64), dim3(64), 0, s, gd, d_st, a_stamp, d_roots, n_roots);
-      LvArgs la{d_changed, 0, n, a_stamp, d_st, d_roots, gd.in_ptr, gd.rowflags, gd.vflags,
-                gd, tabs, d_kcnt, fp_wide, net_nh, ignore_ovl, n_roots, count_rows ? 1u : 0u, d_lf,
-                (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (const uint32_t *)g->d_ell_od,
-                2u};
-      const bool mi = g->max_path_metric == HSPF_DIST_INF;
-      const dim3 lgrid((n + 255) / 256, n_roots);
-      uint32_t n_f = 0;
-      r2 = run_phase(ctx->est_lv, 0u, [&](uint32_t sweep) {
-        la.sweep = (int)sweep;
-        if (mi) hipLaunchKernelGGL((k_lv<true>), lgrid, dim3(256), 0, s, la);
-        else    hipLaunchKernelGGL((k_lv<false>), lgrid, dim3(256), 0, s, la);
-      }, n_f, [&]() {
-        (void)hipEventRecord(ctx->ev[2], s);
-        hipLaunchKernelGGL(k_emit_lv, lgrid, dim3(256), 0, s, n, (const uint64_t *)d_st, fp_wide, od);
-        (void)hipEventRecord(ctx->ev[4], s);
-        tail_done = true;
-      });
-      if (r2) return r2;
-      ctx->est_lv = n_f + 1;
-      st.n_relax_launches += n_f;
-      st.lane_vertex = 1;
-      if (count_rows) for (uint32_t i = 0; i < 128; ++i) st.rows_recomputed += ctx->h_lane_flags[L + i];
-      return HSPF_OK;
-    }
+  int r2;
+  if ((r2 = ensure(ctx, ctx->stamp, (size_t)n_roots * n * 4))) return r2;
+  uint32_t *a_stamp = (uint32_t *)ctx->stamp.p;
+  hipError_t er = hipMemsetAsync(d_lf, 0, (size_t)L * 4, s);
+  if (er == hipSuccess) er = hipMemsetAsync(d_st, 0xFF, (size_t)n_roots * n * 8, s);
+  if (er == hipSuccess) er = hipMemsetAsync(a_stamp, 0, (size_t)n_roots * n * 4, s);
+  if (er == hipSuccess && count_rows) er = hipMemsetAsync(d_kcnt, 0, 256 * 4, s);
+  if (er != hipSuccess) { ctx->last_error = std::string("lv init: ") + hipGetErrorString(er); return HSPF_E_HIP; }
+  hipLaunchKernelGGL(k_init_lv, dim3((n_roots + 63) / 64), dim3(64), 0, s, gd, d_st, a_stamp, d_roots, n_roots);
+  LvArgs la{d_changed, 0, n, a_stamp, d_st, d_roots, gd.in_ptr, gd.rowflags, gd.vflags,
+            gd, tabs, d_kcnt, fp_wide, net_nh, ignore_ovl, n_roots, count_rows ? 1u : 0u, d_lf,
+            (const uint32_t *)g->d_ell_so, (const uint32_t *)g->d_ell_w, (const uint32_t *)g->d_ell_od,
+            2u};
+  const dim3 lgrid((n + 255) / 256, n_roots);
+  uint32_t n_f = 0;
+  r2 = run_phase(ctx->est_lv, 0u, [&](uint32_t sweep) {
+    la.sweep = (int)sweep;
+    launch_lv(la, lgrid);
+  }, n_f, [&]() {
+    (void)hipEventRecord(ctx->ev[2], s);
+    hipLaunchKernelGGL(k_emit_lv, lgrid, dim3(256), 0, s, n, (const uint64_t *)d_st, fp_wide, od);
+    (void)hipEventRecord(ctx->ev[4], s);
+    tail_done = true;
+  });
+  if (r2) return r2;
+  ctx->est_lv = n_f + 1;
+  st.n_relax_launches += n_f;
+  st.lane_vertex = 1;
+  if (count_rows) for (uint32_t i = 0; i < 128; ++i) st.rows_recomputed += ctx->h_lane_flags[L + i];
+  return HSPF_OK;
+}
 
 // One to eight roots on a mid-size graph: one XCD per root, the state replicated in every CU's LDS, ONE launch (k_xcd).
 std::atomic<uint32_t> g_xcd_next{0};             // the XCD the next run's first root takes: concurrent runs (lanes, contexts) spread out
@@ -2279,19 +2373,18 @@ int Run::xcd_run() {
   hipError_t er = hipHostGetDevicePointer((void **)&d_hst, h_st, 0);
   if (er != hipSuccess) { ctx->last_error = std::string("k_xcd: pinned status words: ") + hipGetErrorString(er); return HSPF_E_HIP; }
   std::fill(h_st, h_st + XCD_MAX_ROOTS * XCD_MAX_WG, 0u);
-  const bool mi = g->max_path_metric == HSPF_DIST_INF;
   static const bool prof = getenv("HSPF_XCD_PROF") != nullptr;      // (tuning only: phase times of one workgroup on stderr)
-  void (*kern)(XcdArgs) = prof ? (mi ? k_xcd<true, true> : k_xcd<false, true>) : (mi ? k_xcd<true, false> : k_xcd<false, false>);
-  if (!(ctx->xcd_attr & (mi ? 2u : 1u))) {
+  const KernelPick<XcdArgs> kern = pick_xcd(maxinf(), prof);
+  if (!(ctx->xcd_attr & kern.attr_bit)) {
     // (the replica of the largest graph the path takes; the kernel's own few words of LDS sit next to it)
-    const hipError_t ea = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(XCD_MAX_N * 8u));
+    const hipError_t ea = hipFuncSetAttribute((const void *)kern.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(XCD_MAX_N * 8u));
     if (ea != hipSuccess) { ctx->last_error = std::string("k_xcd: dynamic LDS attribute: ") + hipGetErrorString(ea); return HSPF_E_HIP; }
-    ctx->xcd_attr |= mi ? 2u : 1u;
+    ctx->xcd_attr |= kern.attr_bit;
   }
   XcdArgs xa{d_fg, d_roots, fp_wide, net_nh, ignore_ovl, n_roots, ++ctx->xcd_epoch, n_wg, vw,
              g_xcd_next.fetch_add(n_roots, std::memory_order_relaxed) & 7u, n_pad, (uint32_t)(((1ull << 32) + vw - 1u) / vw), d_st, (uint32_t *)ctx->xcd_ctl.p, d_hst,
              (uint64_t)ctx->xcd_timeout_ms * 100000ull, ctx->xcd_skew ? 1u : 0u, od};
-  hipLaunchKernelGGL(kern, dim3(8u * n_wg), dim3(thr), (size_t)n * 8, s, xa);
+  hipLaunchKernelGGL(kern.fn, dim3(8u * n_wg), dim3(thr), (size_t)n * 8, s, xa);
   (void)hipEventRecord(ctx->ev[2], s);
   (void)hipEventRecord(ctx->ev[4], s);            // the kernel wrote the results in place (as k_single)
   tail_done = true;
@@ -2333,131 +2426,176 @@ int Run::xcd_run() {
   return HSPF_OK;
 }
 
+void Run::launch_single_lean(const SingleArgs &sa, uint32_t thr) {   // k_single_lean<MAXINF, RL>: RL = 4 or 8 in-links per row
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c;
+  with_flag(g->max_in_deg <= 4u, [&](auto c) { constexpr int RL = c ? 4 : 8;
+    hipLaunchKernelGGL((k_single_lean<MAXINF, RL>), dim3(n_roots), dim3(thr), (size_t)n * 8, s, sa);
+  }); });
+}
+
 // Small graphs: ONE workgroup per root, the whole state in LDS, one launch (k_single / k_single_lean).
 int Run::single_run() {
-      // every workgroup STORES its root's status word straight into the pinned host array: no memset, no copy back
-      uint32_t *d_hlf = nullptr;
-      hipError_t er = hipHostGetDevicePointer((void **)&d_hlf, ctx->h_lane_flags, 0);
-      if (er != hipSuccess) { ctx->last_error = std::string("single: pinned status words: ") + hipGetErrorString(er); return HSPF_E_HIP; }
-      for (uint32_t r = n_roots; r < L; ++r) ctx->h_lane_flags[r] = 0u;
-      if (er == hipSuccess && count_rows) er = hipMemsetAsync(d_kcnt, 0, 256 * 4, s);
-      if (er != hipSuccess) { ctx->last_error = std::string("single init: ") + hipGetErrorString(er); return HSPF_E_HIP; }
-      // the link records are staged in LDS when they fit next to the state; with many roots only while two workgroups
-      // still fit a CU (the staging itself is a pass over the links per root)
-      const size_t lds_full = single_lds_bytes(n, g->e_kept, true);
-      const bool lds_links = lds_full <= (n_roots > 256 ? SINGLE_LDS_MAX / 2 : SINGLE_LDS_MAX);
-      const size_t lds = single_lds_bytes(n, g->e_kept, lds_links);
-      const uint32_t thr = std::min<uint32_t>(SINGLE_THREADS, std::max<uint32_t>(64u, (n + 63u) / 64u * 64u));
-      const uint32_t need_vpt = (n + thr - 1) / thr;                  // 1 .. 8
-      SingleArgs sa{d_fg, d_roots, fp_wide, net_nh, ignore_ovl, n_roots, count_rows ? 1u : 0u, lds_links ? 1u : 0u, d_hlf, od};
-      const bool mi = g->max_path_metric == HSPF_DIST_INF;
-      void (*kern)(SingleArgs) = nullptr;
-#define HSPF_PICK(V_) (lds_links ? (mi ? k_single<true, V_, true> : k_single<false, V_, true>) : (mi ? k_single<true, V_, false> : k_single<false, V_, false>))
-      kern = need_vpt <= 1 ? HSPF_PICK(1) : need_vpt <= 2 ? HSPF_PICK(2) : need_vpt <= 4 ? HSPF_PICK(4) : HSPF_PICK(8);
-#undef HSPF_PICK
-      const int slot = ((need_vpt <= 1 ? 0 : need_vpt <= 2 ? 1 : need_vpt <= 4 ? 2 : 3) * 2 + (mi ? 1 : 0)) * 2 + (lds_links ? 1 : 0);
-      if (!(ctx->single_attr & (1u << slot))) {      // more than 64 KB of dynamic LDS has to be allowed per kernel, once
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SINGLE_LDS_MAX);
-        ctx->single_attr |= 1u << slot;
-      }
-      // the plainest graphs (routers only, no row flag, in-degrees <= 8) with one vertex per thread: the lean kernel
-      const bool lean = g->lean && n <= (uint32_t)SINGLE_THREADS && !(ctx->variant & 4096u);
-      if (lean && g->max_in_deg <= 4u) {
-        if (mi) hipLaunchKernelGGL((k_single_lean<true, 4>), dim3(n_roots), dim3(thr), (size_t)n * 8, s, sa);
-        else    hipLaunchKernelGGL((k_single_lean<false, 4>), dim3(n_roots), dim3(thr), (size_t)n * 8, s, sa);
-      } else if (lean) {
-        if (mi) hipLaunchKernelGGL((k_single_lean<true, 8>), dim3(n_roots), dim3(thr), (size_t)n * 8, s, sa);
-        else    hipLaunchKernelGGL((k_single_lean<false, 8>), dim3(n_roots), dim3(thr), (size_t)n * 8, s, sa);
-      } else
-      hipLaunchKernelGGL(kern, dim3(n_roots), dim3(thr), lds, s, sa);
-      (void)hipEventRecord(ctx->ev[2], s);
-      (void)hipEventRecord(ctx->ev[4], s);          // the kernel wrote the results in place: the run ends here, and the
-      tail_done = true;                             // synchronisation below covers it (as behind the emit of the other paths)
-      er = hipSuccess;
-      if (count_rows) er = hipMemcpyAsync(ctx->h_lane_flags + L, d_kcnt, 256 * 4, hipMemcpyDeviceToHost, s);
-      const hipError_t el = hipGetLastError();                         // the launch itself
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess || el != hipSuccess) {
-        ctx->last_error = std::string("k_single: ") + hipGetErrorString(er) + " / launch: " + hipGetErrorString(el) + " threads " +
-                          std::to_string(thr) + " lds " + std::to_string(lds);
-        return HSPF_E_HIP;
-      }
-      st.n_relax_launches = 1; st.single_wg = 1;
-      if (count_rows) {
-        for (uint32_t i = 0; i < 128; ++i) st.rows_recomputed += ctx->h_lane_flags[L + i];
-        for (uint32_t i = 0; i < 4; ++i) st.dbg[i] = ctx->h_lane_flags[L + 128 + i];   // sweeps, shader cycles, 100 MHz ticks, set-up cycles of workgroup 0 (this flag only: overwrites the host times)
-      }
-      narrow = false;
+  // every workgroup STORES its root's status word straight into the pinned host array: no memset, no copy back
+  uint32_t *d_hlf = nullptr;
+  hipError_t er = hipHostGetDevicePointer((void **)&d_hlf, ctx->h_lane_flags, 0);
+  if (er != hipSuccess) { ctx->last_error = std::string("single: pinned status words: ") + hipGetErrorString(er); return HSPF_E_HIP; }
+  for (uint32_t r = n_roots; r < L; ++r) ctx->h_lane_flags[r] = 0u;
+  if (er == hipSuccess && count_rows) er = hipMemsetAsync(d_kcnt, 0, 256 * 4, s);
+  if (er != hipSuccess) { ctx->last_error = std::string("single init: ") + hipGetErrorString(er); return HSPF_E_HIP; }
+  // the link records are staged in LDS when they fit next to the state; with many roots only while two workgroups
+  // still fit a CU (the staging itself is a pass over the links per root)
+  const size_t lds_full = single_lds_bytes(n, g->e_kept, true);
+  const bool lds_links = lds_full <= (n_roots > 256 ? SINGLE_LDS_MAX / 2 : SINGLE_LDS_MAX);
+  const size_t lds = single_lds_bytes(n, g->e_kept, lds_links);
+  const uint32_t thr = std::min<uint32_t>(SINGLE_THREADS, std::max<uint32_t>(64u, (n + 63u) / 64u * 64u));
+  const uint32_t need_vpt = (n + thr - 1) / thr;                  // 1 .. 8
+  SingleArgs sa{d_fg, d_roots, fp_wide, net_nh, ignore_ovl, n_roots, count_rows ? 1u : 0u, lds_links ? 1u : 0u, d_hlf, od};
+  const KernelPick<SingleArgs> kern = pick_single(maxinf(), need_vpt, lds_links);
+  if (!(ctx->single_attr & kern.attr_bit)) {     // more than 64 KB of dynamic LDS has to be allowed per kernel, once
+    (void)hipFuncSetAttribute((const void *)kern.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SINGLE_LDS_MAX);
+    ctx->single_attr |= kern.attr_bit;
+  }
+  // the plainest graphs (routers only, no row flag, in-degrees <= 8) with one vertex per thread: the lean kernel
+  const bool lean = g->lean && n <= (uint32_t)SINGLE_THREADS && !(ctx->variant & hspf_ctx::VAR_NO_SINGLE_LEAN);
+  if (lean) launch_single_lean(sa, thr);
+  else hipLaunchKernelGGL(kern.fn, dim3(n_roots), dim3(thr), lds, s, sa);
+  (void)hipEventRecord(ctx->ev[2], s);
+  (void)hipEventRecord(ctx->ev[4], s);          // the kernel wrote the results in place: the run ends here, and the
+  tail_done = true;                             // synchronisation below covers it (as behind the emit of the other paths)
+  er = hipSuccess;
+  if (count_rows) er = hipMemcpyAsync(ctx->h_lane_flags + L, d_kcnt, 256 * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t el = hipGetLastError();                         // the launch itself
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess || el != hipSuccess) {
+    ctx->last_error = std::string("k_single: ") + hipGetErrorString(er) + " / launch: " + hipGetErrorString(el) + " threads " +
+                      std::to_string(thr) + " lds " + std::to_string(lds);
+    return HSPF_E_HIP;
+  }
+  st.n_relax_launches = 1; st.single_wg = 1;
+  if (count_rows) {
+    for (uint32_t i = 0; i < 128; ++i) st.rows_recomputed += ctx->h_lane_flags[L + i];
+    for (uint32_t i = 0; i < 4; ++i) st.dbg[i] = ctx->h_lane_flags[L + 128 + i];   // sweeps, shader cycles, 100 MHz ticks, set-up cycles of workgroup 0 (this flag only: overwrites the host times)
+  }
+  narrow = false;
   return HSPF_OK;
 }
 
 // Every root has at most 24 first-hop slots: one fused fixed point over a packed state — which kernel, which width.
 int Run::path_fused() {
-    d_fg = (const FusedGraph *)(d_up + w_fg);
-    last_esz = 0;                    // state width of the last fused_run (0: none ran)
-    last_ns = n; last_fillw = 0xFFFFFFFFu;
-    spec_done = false;                   // the last fused_run's speculative fill was enqueued behind its last chunk
-    emit_reset = false;                  // the emit of the current chunk resets the state it has read (k_emit_fused reset_guard)
-    spec_nz = 0;
-    // Small graphs: one workgroup per root, the whole state in LDS, ONE launch (k_single) instead of a launch per sweep.
-    // Measured (profiles/r02e_single_threshold.jsonl, 4-neighbour grids, device time): 500 vertices 2.0-2.8x faster than
-    // the sweep engine for 1 / 64 / 1024 roots, 1024 vertices 1.7x / 2.0x / 1.0x, 2048 vertices 1.2x / 1.3x / 0.4x,
-    // 4096 vertices 0.4x: a sweep of the one-workgroup kernel is one long dependent chain at two waves per SIMD (~3 700
-    // cycles), so it wins only while the sweep engine is bound by its ~50 kernel boundaries.  Hence: up to
-    // ctx->single_max_n vertices (HSPF_SINGLE_MAX_N, default 1024; 0 switches the kernel off), twice that for at most
-    // one batch of roots.
-    // (smax / single: decided above, next to the output targets)
-    // A few roots on a larger graph: lane = vertex (k_lv), one launch per sweep over the root's own row-major state.  The
-    // lane = root engine spends a 256-byte row per useful 4-8 bytes there (isis-100k, one root: 25 launches x 21 us);
-    // the scattered gathers of k_lv cost less than that up to a handful of roots (profiles/r02_notes.md, r02k).
-    // (not on graphs with giant rows: a lane of k_lv walks its row alone — one root on isis-100k + a 5 000-router LAN took
-    // 6.9 ms there against 0.9 ms for 64 roots on the sweep engine with the row in slices, r02t)
-    // (lv: decided above)
-    if (single) {
-      if ((rc = single_run())) return rc;
-    } else if (lv) {
-      if ((rc = lv_run())) return rc;
-      narrow = false;
-    } else if (xcdp) {
-      if ((rc = xcd_run())) return rc;
-      if (delegated) return HSPF_OK;                             // gave up on a barrier: the launch-per-sweep path has done the run
-      narrow = false;
-    } else if (lean || narrow) {
-      auto overflowed = [&]() { bool o = false; for (uint32_t r = 0; r < L; ++r) o = o || (ctx->h_lane_flags[r] & LF_OVERFLOW); return o; };
-      bool done = false;
-      if (lean) {
-        if ((rc = fused_run(2))) return rc;
-        // the lean state's fields are tighter (three tag bits, "not reached" one link cost lower, a saturating hop field):
-        // a lane at their edge sends the run to k_fused, and the graph remembers
-        if (overflowed()) { g->lean_bad = true; st.dbg[0] = 0; } else done = true;
-      }
-      if (!done && narrow) {
-        if ((rc = fused_run(1))) return rc;
-        // did any lane leave the 4-byte fields?  (run_phase has brought the per-root status bits back)
-        if (overflowed()) { g->narrow_bad = true; st.narrow_overflow = 1; } else done = true;
-      }
-      narrow = done;                                             // a 4-byte run holds the results
+  d_fg = (const FusedGraph *)(d_up + w_fg);
+  last_esz = 0;                    // state width of the last fused_run (0: none ran)
+  last_ns = n; last_fillw = 0xFFFFFFFFu;
+  spec_done = false;                   // the last fused_run's speculative fill was enqueued behind its last chunk
+  emit_reset = false;                  // the emit of the current chunk resets the state it has read (k_emit_fused reset_guard)
+  spec_nz = 0;
+  // Small graphs: one workgroup per root, the whole state in LDS, ONE launch (k_single) instead of a launch per sweep.
+  // Measured (profiles/r02e_single_threshold.jsonl, 4-neighbour grids, device time): 500 vertices 2.0-2.8x faster than
+  // the sweep engine for 1 / 64 / 1024 roots, 1024 vertices 1.7x / 2.0x / 1.0x, 2048 vertices 1.2x / 1.3x / 0.4x,
+  // 4096 vertices 0.4x: a sweep of the one-workgroup kernel is one long dependent chain at two waves per SIMD (~3 700
+  // cycles), so it wins only while the sweep engine is bound by its ~50 kernel boundaries.  Hence: up to
+  // ctx->single_max_n vertices (HSPF_SINGLE_MAX_N, default 1024; 0 switches the kernel off), twice that for at most
+  // one batch of roots.
+  // (smax / single: decided above, next to the output targets)
+  // A few roots on a larger graph: lane = vertex (k_lv), one launch per sweep over the root's own row-major state.  The
+  // lane = root engine spends a 256-byte row per useful 4-8 bytes there (isis-100k, one root: 25 launches x 21 us);
+  // the scattered gathers of k_lv cost less than that up to a handful of roots (profiles/r02_notes.md, r02k).
+  // (not on graphs with giant rows: a lane of k_lv walks its row alone — one root on isis-100k + a 5 000-router LAN took
+  // 6.9 ms there against 0.9 ms for 64 roots on the sweep engine with the row in slices, r02t)
+  // (lv: decided above)
+  if (single) {
+    if ((rc = single_run())) return rc;
+  } else if (lv) {
+    if ((rc = lv_run())) return rc;
+    narrow = false;
+  } else if (xcdp) {
+    if ((rc = xcd_run())) return rc;
+    if (delegated) return HSPF_OK;                             // gave up on a barrier: the launch-per-sweep path has done the run
+    narrow = false;
+  } else if (lean || narrow) {
+    bool done = false;
+    if (lean) {
+      if ((rc = fused_run(2))) return rc;
+      // the lean state's fields are tighter (three tag bits, "not reached" one link cost lower, a saturating hop field):
+      // a lane at their edge sends the run to k_fused, and the graph remembers
+      if (overflowed()) { g->lean_bad = true; st.dbg[0] = 0; } else done = true;
     }
-    if (!single && !lv && !xcdp && !narrow && (rc = fused_run(0))) return rc;
-    if (!narrow && fp_wide.hmax < 0xFFFFu) {                       // more than 16 mask bits: did the hop field hold?
-      bool ovf = false;
-      for (uint32_t r = 0; r < L; ++r) ovf = ovf || (ctx->h_lane_flags[r] & LF_OVERFLOW);
-      if (ovf) {
-        g->wide24_bad = true;
-        delegated = true;                                        // (that call is the run: go() hands its code on)
-        return run_impl(ctx, g, roots, n_roots, run_flags, out, host_out, row_map, total_rows, true, pk);
-      }
+    if (!done && narrow) {
+      if ((rc = fused_run(1))) return rc;
+      // did any lane leave the 4-byte fields?  (run_phase has brought the per-root status bits back)
+      if (overflowed()) { g->narrow_bad = true; st.narrow_overflow = 1; } else done = true;
     }
-    st.state_bytes = narrow ? 4 : 8;
-    if (last_esz && !ctx->prefill.valid) {
-      // the next run's scratch, behind this one's emit (same shape assumed: an SPF instance repeats its root set) — unless
-      // the speculative fill behind the last chunk's read-back has done it already
-      const uint32_t nz = std::min<uint32_t>(CHANGED_CAP, ctx->est_fused + 4096);
-      hipLaunchKernelGGL(k_init_fill, dim3(2048), dim3(256), 0, s, (uint4 *)d_st, (size_t)B * last_ns * 64 * last_esz / 16, last_fillw, d_stamp, (size_t)B * n,
-                         (const uint8_t *)g->d_rowflags, (uint8_t *)ctx->hnb.p, n, d_changed, nz, d_lf, L, d_kcnt, -1, (uint32_t *)ctx->swcnt.p, ctx->swcnt.p ? LEAN_CTL_WORDS : 0u);
-      ctx->prefill = hspf_ctx::Prefill{true, g->build_id, n, B, last_esz, nz, L, true, last_ns, last_fillw};
+    narrow = done;                                             // a 4-byte run holds the results
+  }
+  if (!single && !lv && !xcdp && !narrow && (rc = fused_run(0))) return rc;
+  if (!narrow && fp_wide.hmax < 0xFFFFu) {                       // more than 16 mask bits: did the hop field hold?
+    if (overflowed()) {
+      g->wide24_bad = true;
+      delegated = true;                                        // (that call is the run: go() hands its code on)
+      return run_impl(ctx, g, roots, n_roots, run_flags, out, host_out, row_map, total_rows, true, pk);
     }
+  }
+  st.state_bytes = narrow ? 4 : 8;
+  if (last_esz && !ctx->prefill.valid) {
+    // the next run's scratch, behind this one's emit (same shape assumed: an SPF instance repeats its root set) — unless
+    // the speculative fill behind the last chunk's read-back has done it already
+    const uint32_t nz = std::min<uint32_t>(CHANGED_CAP, ctx->est_fused + 4096);
+    hipLaunchKernelGGL(k_init_fill, dim3(2048), dim3(256), 0, s, (uint4 *)d_st, (size_t)B * last_ns * 64 * last_esz / 16, last_fillw, d_stamp, (size_t)B * n,
+                       (const uint8_t *)g->d_rowflags, (uint8_t *)ctx->hnb.p, n, d_changed, nz, d_lf, L, d_kcnt, -1, (uint32_t *)ctx->swcnt.p,
+                       ctx->swcnt.p ? LEAN_CTL_WORDS : 0u);
+    ctx->prefill = hspf_ctx::Prefill{true, g->build_id, n, B, last_esz, nz, L, true, last_ns, last_fillw};
+  }
   return HSPF_OK;
+}
+
+// ---- the kernels of the wide-mask path.  k_fw<W, MAXINF, HC, LEAF> and k_fw_giant_part<the same>: on a hop-count-like
+// graph (HC) the plateau rule doubles the mask registers, and the run takes k_fw only with at most 4 mask words (use_fw), so
+// the wider HC instantiations do not exist; LEAF (the leaves are left to the emit: `defer`) exists without MAXINF and HC only —
+// init_state sets `defer` only where neither holds.
+template <int W, bool HC> constexpr int fw_words = HC && W > 4 ? 1 : W;
+template <bool MAXINF, bool HC> constexpr bool fw_leaf(bool defer) { return defer && !MAXINF && !HC; }
+
+void Run::launch_fw_giant_part(uint32_t sweep, dim3 ggrid) {       // slices of the due giant rows, ahead of the sweep that merges them
+  with_width(W, [&](auto c) { constexpr int WORDS = c;
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c;
+  with_flag(g->hopcount_like, [&](auto c) { constexpr bool HC = c;
+  with_flag(defer, [&](auto c) { constexpr bool LEAF = fw_leaf<MAXINF, HC>(c);
+    hipLaunchKernelGGL((k_fw_giant_part<fw_words<WORDS, HC>, MAXINF, HC, LEAF>), ggrid, dim3(256), 0, s, d_fg, (const uint32_t *)d_dist, (const uint32_t *)d_hv,
+                       (const uint64_t *)d_mask, (const uint32_t *)d_stamp, (const uint32_t *)d_roots, net_nh, ignore_ovl, (const int *)d_changed, (int)sweep);
+  }); }); }); });
+}
+
+void Run::launch_fw(uint32_t sweep) {
+  with_width(W, [&](auto c) { constexpr int WORDS = c;
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c;
+  with_flag(g->hopcount_like, [&](auto c) { constexpr bool HC = c;
+  with_flag(defer, [&](auto c) { constexpr bool LEAF = fw_leaf<MAXINF, HC>(c);
+    hipLaunchKernelGGL((k_fw<fw_words<WORDS, HC>, MAXINF, HC, LEAF>), grid, dim3(256), 0, s, d_fg, d_dist, d_hv, d_mask, d_stamp, d_roots, g->max_path_metric,
+                       net_nh, ignore_ovl, d_changed, (int)sweep, d_lf);
+  }); }); }); });
+}
+
+void Run::launch_relax(uint32_t sweep) {                           // k_relax<MAXINF, FAIL>: FAIL = a scenario run (hspf_run_failures*)
+  with_flag(maxinf(), [&](auto c) { constexpr bool MAXINF = c;
+  with_flag(fail != nullptr, [&](auto c) { constexpr bool FAIL = c;
+    hipLaunchKernelGGL((k_relax<MAXINF, FAIL>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf,
+                       fail_arg<FAIL>());
+  }); });
+}
+
+void Run::launch_dag(uint32_t sweep, uint32_t epoch) {             // k_dag<W, GS, FAIL>: GS with one mask word only
+  with_width(W, [&](auto c) { constexpr int WORDS = c; constexpr bool GS = WORDS == 1;
+  with_flag(fail != nullptr, [&](auto c) { constexpr bool FAIL = c;
+    hipLaunchKernelGGL((k_dag<WORDS, GS, FAIL>), grid, dim3(256), 0, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch,
+                       d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fail_arg<FAIL>());
+  }); });
+}
+
+void Run::launch_emit(dim3 egrid) {                                // k_emit<W, LEAF>: LEAF = the leaves' rows are derived here (`defer`)
+  const EmitLeaf el{(const FusedGraph *)(d_up + w_fg), d_roots, g->max_path_metric, net_nh, ignore_ovl};
+  with_width(W, [&](auto c) { constexpr int WORDS = c;
+  with_flag(defer, [&](auto c) { constexpr bool LEAF = c;
+    hipLaunchKernelGGL((k_emit<WORDS, LEAF>), egrid, dim3(256), 0, s, n, n_roots, d_dist, d_hv, d_mask, od, el);
+  }); });
 }
 
 int Run::path_wide() {
@@ -2477,28 +2615,11 @@ int Run::path_wide() {
     HIPCHK(ctx, hipMemsetAsync(d_stamp, 0, (size_t)B * n * 4, s));
     hipLaunchKernelGGL(k_init_fw, dim3((L + 3) / 4), dim3(256), 0, s, gd, d_dist, d_stamp, d_roots, L);
     if (giant) HIPCHK(ctx, hipMemsetAsync(ctx->giant_part.p, 0, giant_tags * 4, s));
-    const bool mi = g->max_path_metric == HSPF_DIST_INF, hcl = g->hopcount_like;
     const dim3 ggrid(std::max(g->n_giant_slices, 1u), B);
     uint32_t n_fw = 0;
     rc = run_phase(ctx->est_fw, 0u, [&](uint32_t sweep) {
-#define HSPF_FWG(W_, MI_, HC_) hipLaunchKernelGGL((k_fw_giant_part<W_, MI_, HC_>), ggrid, dim3(256), 0, s, d_fg, (const uint32_t *)d_dist, (const uint32_t *)d_hv, (const uint64_t *)d_mask, (const uint32_t *)d_stamp, (const uint32_t *)d_roots, net_nh, ignore_ovl, (const int *)d_changed, (int)sweep)
-#define HSPF_FW(W_) do { \
-      if (giant) { if (hcl) { if (mi) HSPF_FWG((W_ <= 4 ? W_ : 1), true, true); else HSPF_FWG((W_ <= 4 ? W_ : 1), false, true); } \
-                   else     { if (mi) HSPF_FWG(W_, true, false); else if (defer) hipLaunchKernelGGL((k_fw_giant_part<W_, false, false, true>), ggrid, dim3(256), 0, s, d_fg, (const uint32_t *)d_dist, (const uint32_t *)d_hv, (const uint64_t *)d_mask, (const uint32_t *)d_stamp, (const uint32_t *)d_roots, net_nh, ignore_ovl, (const int *)d_changed, (int)sweep); else HSPF_FWG(W_, false, false); } } \
-      if (hcl) { if (mi) hipLaunchKernelGGL((k_fw<(W_ <= 4 ? W_ : 1), true, true>), grid, dim3(256), 0, s, d_fg, d_dist, d_hv, d_mask, d_stamp, d_roots, g->max_path_metric, net_nh, ignore_ovl, d_changed, (int)sweep, d_lf); \
-                 else    hipLaunchKernelGGL((k_fw<(W_ <= 4 ? W_ : 1), false, true>), grid, dim3(256), 0, s, d_fg, d_dist, d_hv, d_mask, d_stamp, d_roots, g->max_path_metric, net_nh, ignore_ovl, d_changed, (int)sweep, d_lf); } \
-      else     { if (mi) hipLaunchKernelGGL((k_fw<W_, true, false>), grid, dim3(256), 0, s, d_fg, d_dist, d_hv, d_mask, d_stamp, d_roots, g->max_path_metric, net_nh, ignore_ovl, d_changed, (int)sweep, d_lf); \
-                 else if (defer) hipLaunchKernelGGL((k_fw<W_, false, false, true>), grid, dim3(256), 0, s, d_fg, d_dist, d_hv, d_mask, d_stamp, d_roots, g->max_path_metric, net_nh, ignore_ovl, d_changed, (int)sweep, d_lf); \
-                 else    hipLaunchKernelGGL((k_fw<W_, false, false>), grid, dim3(256), 0, s, d_fg, d_dist, d_hv, d_mask, d_stamp, d_roots, g->max_path_metric, net_nh, ignore_ovl, d_changed, (int)sweep, d_lf); } } while (0)
-      switch (W) {
-        case 1: HSPF_FW(1); break;
-        case 2: HSPF_FW(2); break;
-        case 4: HSPF_FW(4); break;
-        case 8: HSPF_FW(8); break;
-        default: HSPF_FW(16); break;
-      }
-#undef HSPF_FW
-#undef HSPF_FWG
+      if (giant) launch_fw_giant_part(sweep, ggrid);
+      launch_fw(sweep);
     }, n_fw, []() {});
     if (rc) return rc;
     ctx->est_fw = n_fw + 1;
@@ -2506,67 +2627,35 @@ int Run::path_wide() {
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], s));
     two_events = false;
   } else {
-  uint32_t n_relax = 0;
-  rc = run_phase(ctx->est_relax, 0u, [&](uint32_t sweep) {
-    if (fail) {
-      if (g->max_path_metric == HSPF_DIST_INF)
-        hipLaunchKernelGGL((k_relax<true, true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, fdv);
-      else
-        hipLaunchKernelGGL((k_relax<false, true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, fdv);
-    } else if (g->max_path_metric == HSPF_DIST_INF)
-      hipLaunchKernelGGL((k_relax<true>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, FailNone{});
-    else
-      hipLaunchKernelGGL((k_relax<false>), grid, dim3(256), 0, s, gd, d_dist, d_roots, g->max_path_metric, ignore_ovl, d_changed, (int)sweep, d_lf, FailNone{});
-  }, n_relax, []() {});
-  if (rc) return rc;
-  ctx->est_relax = n_relax + 1;
-  st.n_relax_launches = n_relax;
-  HIPCHK(ctx, hipEventRecord(ctx->ev[2], s));
+    uint32_t n_relax = 0;
+    rc = run_phase(ctx->est_relax, 0u, [&](uint32_t sweep) {
+      launch_relax(sweep);
+    }, n_relax, []() {});
+    if (rc) return rc;
+    ctx->est_relax = n_relax + 1;
+    st.n_relax_launches = n_relax;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[2], s));
 
-  // ---- phase 2: hops + first-hop masks over the tight-edge DAG
-  HIPCHK(ctx, hipMemsetAsync(d_mask, 0, rows * 8 * W, s));
-  HIPCHK(ctx, hipMemsetAsync(d_stamp, 0, (size_t)B * n * 4, s));       // activation stamps: every row due in sweep 0
-  uint32_t n_dag = 0;
-  uint32_t epoch = 1;
-  rc = run_phase(ctx->est_dag, 0u, [&](uint32_t sweep) {
-    if (epoch >= HV_EPOCH_MAX) {
-      hipLaunchKernelGGL(k_rebase, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_hv, rows);
-      epoch = 2;
-    }
-    if (fail) switch (W) {
-      case 1: launch_dag_fail<1, true>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
-      case 2: launch_dag_fail<2>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
-      case 4: launch_dag_fail<4>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
-      case 8: launch_dag_fail<8>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
-      default: launch_dag_fail<16>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp, fdv); break;
-    }
-    else switch (W) {
-      case 1: launch_dag<1, true>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
-      case 2: launch_dag<2>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
-      case 4: launch_dag<4>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
-      case 8: launch_dag<8>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
-      default: launch_dag<16>(grid, s, gd, d_dist, d_hv, d_mask, d_roots, tabs, net_nh, ignore_ovl, d_changed, (int)sweep, epoch, d_lf, g->hopcount_like ? 1u : 0u, d_stamp); break;
-    }
-    ++epoch;
-  }, n_dag, []() {});
-  if (rc) return rc;
-  ctx->est_dag = n_dag + 1;
-  st.n_dag_launches = n_dag;
-  HIPCHK(ctx, hipEventRecord(ctx->ev[3], s));
-
+    // ---- phase 2: hops + first-hop masks over the tight-edge DAG
+    HIPCHK(ctx, hipMemsetAsync(d_mask, 0, rows * 8 * W, s));
+    HIPCHK(ctx, hipMemsetAsync(d_stamp, 0, (size_t)B * n * 4, s));       // activation stamps: every row due in sweep 0
+    uint32_t n_dag = 0;
+    uint32_t epoch = 1;
+    rc = run_phase(ctx->est_dag, 0u, [&](uint32_t sweep) {
+      if (epoch >= HV_EPOCH_MAX) {
+        hipLaunchKernelGGL(k_rebase, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d_hv, rows);
+        epoch = 2;
+      }
+      launch_dag(sweep, epoch);
+      ++epoch;
+    }, n_dag, []() {});
+    if (rc) return rc;
+    ctx->est_dag = n_dag + 1;
+    st.n_dag_launches = n_dag;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[3], s));
   }
   // ---- emit row-major results
-  {
-    const dim3 egrid((n + 63) / 64, B, 1 + W);
-    const EmitLeaf el{(const FusedGraph *)(d_up + w_fg), d_roots, g->max_path_metric, net_nh, ignore_ovl};
-    switch (W) {
-      case 1: launch_emit<1>(egrid, s, n, n_roots, d_dist, d_hv, d_mask, od, defer, el); break;
-      case 2: launch_emit<2>(egrid, s, n, n_roots, d_dist, d_hv, d_mask, od, defer, el); break;
-      case 4: launch_emit<4>(egrid, s, n, n_roots, d_dist, d_hv, d_mask, od, defer, el); break;
-      case 8: launch_emit<8>(egrid, s, n, n_roots, d_dist, d_hv, d_mask, od, defer, el); break;
-      default: launch_emit<16>(egrid, s, n, n_roots, d_dist, d_hv, d_mask, od, defer, el); break;
-    }
-  }
+  launch_emit(dim3((n + 63) / 64, B, 1 + W));
 
   return HSPF_OK;
 }
@@ -2591,8 +2680,10 @@ int Run::repair_roots() {
       od.dist = (uint32_t *)ctx->o_dist.p; od.hops = (uint16_t *)ctx->o_hops.p; od.flags = (uint16_t *)ctx->o_flags.p; od.mask = (uint64_t *)ctx->o_mask.p;
       const FusedParams PP = pk_mode == 2 ? fp_lean : pk_mode == 1 ? fp_narrow : fp_wide;
       const dim3 ug((n + 255u) / 256u, nd);
-      if (pk_mode == 2 || pk_mode == 1) hipLaunchKernelGGL((kr_unpack_rows<4>), ug, dim3(256), 0, s, n, nd, (const uint32_t *)ctx->ex_list.p, (const void *)pk_dev(4), PP, od.dist, od.hops, od.flags, od.mask);
-      else                              hipLaunchKernelGGL((kr_unpack_rows<8>), ug, dim3(256), 0, s, n, nd, (const uint32_t *)ctx->ex_list.p, (const void *)pk_dev(8), PP, od.dist, od.hops, od.flags, od.mask);
+      with_flag(pk_mode == 2 || pk_mode == 1, [&](auto c) { constexpr int WB = c ? 4 : 8;      // kr_unpack_rows<WB>: bytes per packed word
+        hipLaunchKernelGGL((kr_unpack_rows<WB>), ug, dim3(256), 0, s, n, nd, (const uint32_t *)ctx->ex_list.p, (const void *)pk_dev(WB), PP, od.dist, od.hops,
+                           od.flags, od.mask);
+      });
       unpacked = true;
     }
     const size_t zl_off = ((size_t)n + 255u) & ~(size_t)255u;        // [zflag: n bytes | zl: n words | nz]
@@ -2694,8 +2785,10 @@ int Run::repair_roots() {
       fprintf(stderr, "[hspf repair trace] %u records (sweeps %u)\n", tr[0], 0u);
       for (uint32_t i = 0; i < cntt; ++i) {
         const uint32_t *t = tr.data() + 4 + 4 * i;
-        if ((t[0] >> 28) == 1u) fprintf(stderr, "  wake   for sweep %u: vertex %u by %u -> %s\n", t[0] & 0xFFFFFFu, t[1], t[2], t[3] ? "appended" : "already stamped");
-        else fprintf(stderr, "  eval   in sweep %u: vertex %u first parent's hops %u -> hops %u (was %u), changed %u, R of first parent %u\n", t[0] & 0xFFFFFFu, t[1], t[2] >> 16, t[2] & 0xFFFFu, t[3] >> 16, t[3] & 1u, (t[3] & 0xFFFEu) >> 1);
+        if ((t[0] >> 28) == 1u)
+          fprintf(stderr, "  wake   for sweep %u: vertex %u by %u -> %s\n", t[0] & 0xFFFFFFu, t[1], t[2], t[3] ? "appended" : "already stamped");
+        else fprintf(stderr, "  eval   in sweep %u: vertex %u first parent's hops %u -> hops %u (was %u), changed %u, R of first parent %u\n", t[0] & 0xFFFFFFu, t[1],
+                     t[2] >> 16, t[2] & 0xFFFFu, t[3] >> 16, t[3] & 1u, (t[3] & 0xFFFEu) >> 1);
       }
     }
     if (getenv("HSPF_REPAIR_PROF"))
@@ -2727,7 +2820,7 @@ int Run::exact_roots() {
   const bool tables = pk || (od.hops && od.flags && od.mask);      // everything k_repair reads and writes is there
   // HSPF_RUN_POP_RANK: every root goes through the repair (a root with a static order has nothing to put right there: its
   // ranks are the order of (distance, index)) and the ranks come out of two sorts; until round 6 the flag forced k_exact
-  const bool want_rank = (run_flags & HSPF_RUN_POP_RANK) && d_rank && tables && !(ctx->variant & (1u << 27));
+  const bool want_rank = (run_flags & HSPF_RUN_POP_RANK) && d_rank && tables && !(ctx->variant & hspf_ctx::VAR_EXACT_NOT_REPAIR);
   for (uint32_t r = 0; r < n_roots; ++r) {
     if (roots[r] == HSPF_NO_ROOT) continue;
     const uint32_t lf = ctx->h_lane_flags[r];
@@ -2736,7 +2829,7 @@ int Run::exact_roots() {
     else if (want_rank) dy.push_back(r);
     else if (lf & LF_DYN) {
       if (!pk && !od.hops && !od.mask) continue;                     // distances only: they are final as they are
-      if (tables && !(ctx->variant & (1u << 27))) dy.push_back(r); else ex.push_back(r);      // (HSPF_VARIANT bit 27: k_exact as before round 6 — tests, A/B)
+      if (tables && !(ctx->variant & hspf_ctx::VAR_EXACT_NOT_REPAIR)) dy.push_back(r); else ex.push_back(r);      // (HSPF_VARIANT bit 27: k_exact as before round 6 — tests, A/B)
     }
   }
   if ((rc = repair_roots())) return rc;
@@ -2765,8 +2858,7 @@ int Run::exact_roots() {
     a.root_list = (const uint32_t *)ctx->ex_list.p + dy.size();
     a.heap = (uint32_t *)ctx->ex_heap.p; a.pos = (uint32_t *)ctx->ex_pos.p;
     a.fail_pos = fdv.pos; a.fail_vtx = fdv.vtx;
-    if (fail) hipLaunchKernelGGL(k_exact_fail, dim3((a.n_exact + 63) / 64), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_exact, dim3((a.n_exact + 63) / 64), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(fail ? k_exact_fail : k_exact, dim3((a.n_exact + 63) / 64), dim3(64), 0, s, a);
   }
   if ((run_flags & HSPF_RUN_POP_RANK) && d_rank) {
     // pop_rank of padding roots
@@ -2792,9 +2884,10 @@ int Run::packed_finish() {
     if (pk_full || !oob.empty()) {
       const uint32_t nrows = pk_full ? n_roots : (uint32_t)oob.size();
       const uint32_t *rows_list = pk_full ? (const uint32_t *)nullptr : (const uint32_t *)ctx->ex_list.p;
-      const dim3 pg((n + 255u) / 256u, nrows);
-      if (pk_esz == 4) hipLaunchKernelGGL((k_pack_full<4>), pg, dim3(256), 0, s, n, nrows, rows_list, (const uint32_t *)od.dist, (const uint16_t *)od.hops, (const uint16_t *)od.flags, (const uint64_t *)od.mask, 1u, PP, (void *)pk_dev(4), d_misfit);
-      else             hipLaunchKernelGGL((k_pack_full<8>), pg, dim3(256), 0, s, n, nrows, rows_list, (const uint32_t *)od.dist, (const uint16_t *)od.hops, (const uint16_t *)od.flags, (const uint64_t *)od.mask, 1u, PP, (void *)pk_dev(8), d_misfit);
+      with_flag(pk_esz == 4, [&](auto c) { constexpr int WB = c ? 4 : 8;                        // k_pack_full<WB>: bytes per packed word
+        hipLaunchKernelGGL((k_pack_full<WB>), dim3((n + 255u) / 256u, nrows), dim3(256), 0, s, n, nrows, rows_list, (const uint32_t *)od.dist, (const uint16_t *)od.hops,
+                           (const uint16_t *)od.flags, (const uint64_t *)od.mask, 1u, PP, (void *)pk_dev(WB), d_misfit);
+      });
       HIPCHK(ctx, hipMemcpyAsync(ctx->h_lane_flags + L + 256 + LEAN_CTL_WORDS, d_misfit, 4, hipMemcpyDeviceToHost, s));
     }
     hspf_packed_layout &ly = pk->layout;
@@ -2907,7 +3000,9 @@ static int run_impl(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, u
           else if (memcmp(&first, &part.layout, sizeof(first)) != 0) { again = true; break; }
           const hspf_stats &p = ctx->stats;
           acc.n_roots += p.n_roots; acc.n_batches += p.n_batches; acc.n_relax_launches += p.n_relax_launches;
-          acc.n_exact_roots += p.n_exact_roots; acc.n_repaired_roots += p.n_repaired_roots; acc.repair_sweeps = std::max(acc.repair_sweeps, p.repair_sweeps); acc.repair_evals += p.repair_evals; acc.repair_groups += p.repair_groups; acc.ms_repair += p.ms_repair; acc.n_mask_words = std::max(acc.n_mask_words, p.n_mask_words);
+          acc.n_exact_roots += p.n_exact_roots; acc.n_repaired_roots += p.n_repaired_roots; acc.repair_sweeps = std::max(acc.repair_sweeps, p.repair_sweeps);
+          acc.repair_evals += p.repair_evals; acc.repair_groups += p.repair_groups; acc.ms_repair += p.ms_repair;
+          acc.n_mask_words = std::max(acc.n_mask_words, p.n_mask_words);
           acc.ms_total += p.ms_total; acc.ms_relax += p.ms_relax; acc.ms_finish += p.ms_finish; acc.ms_d2h += p.ms_d2h;
           acc.state_bytes = std::max(acc.state_bytes, p.state_bytes); acc.narrow_overflow += p.narrow_overflow; acc.rows_recomputed += p.rows_recomputed;
         }
@@ -2932,7 +3027,8 @@ static int run_impl(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots, u
         if (rc) return rc;
         const hspf_stats &p = ctx->stats;
         acc.n_roots += p.n_roots; acc.n_batches += p.n_batches; acc.n_relax_launches += p.n_relax_launches;
-        acc.n_dag_launches += p.n_dag_launches; acc.n_exact_roots += p.n_exact_roots; acc.n_repaired_roots += p.n_repaired_roots; acc.repair_sweeps = std::max(acc.repair_sweeps, p.repair_sweeps); acc.repair_evals += p.repair_evals; acc.repair_groups += p.repair_groups; acc.ms_repair += p.ms_repair;
+        acc.n_dag_launches += p.n_dag_launches; acc.n_exact_roots += p.n_exact_roots; acc.n_repaired_roots += p.n_repaired_roots;
+        acc.repair_sweeps = std::max(acc.repair_sweeps, p.repair_sweeps); acc.repair_evals += p.repair_evals; acc.repair_groups += p.repair_groups; acc.ms_repair += p.ms_repair;
         acc.n_mask_words = std::max(acc.n_mask_words, p.n_mask_words);
         acc.ms_total += p.ms_total; acc.ms_relax += p.ms_relax; acc.ms_dag += p.ms_dag; acc.ms_finish += p.ms_finish;
         acc.ms_d2h += p.ms_d2h; acc.state_bytes = std::max(acc.state_bytes, p.state_bytes);
@@ -2961,7 +3057,7 @@ static int run_classes(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots
   const uint32_t n = g->n;
   // widest mask field the 4-byte state can take on this graph (same rule as run_impl)
   uint32_t m_narrow = 0;
-  if (!g->narrow_bad && !(ctx->variant & 2u))
+  if (!g->narrow_bad && !(ctx->variant & hspf_ctx::VAR_NO_NARROW))
     for (uint32_t M = 16; M >= 1; --M) {
       const uint32_t H = (32u - M - 7u >= 13u) ? 7u : 6u, D = 32u - M - H;
       if (D >= 12u && g->wmax < (1u << (D - 3))) { m_narrow = M; break; }
@@ -2987,7 +3083,7 @@ static int run_classes(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots
   // 0xFFFFFFFF: the sweep kernels send such roots to the sequential kernel), not behind an overloaded or non-expandable
   // neighbour (its tree as a root is not its tree as a transit hop).  HSPF_VARIANT bit 23: off (A/B).
   std::vector<LeafRootJob> leaf_jobs;
-  if (!(ctx->variant & 8388608u) && !g->hopcount_like && g->max_path_metric != HSPF_DIST_INF && g->twoway.size() == g->col.size()) {
+  if (!(ctx->variant & hspf_ctx::VAR_NO_LEAF_ROOTS) && !g->hopcount_like && g->max_path_metric != HSPF_DIST_INF && g->twoway.size() == g->col.size()) {
     std::vector<std::pair<uint32_t, uint32_t>> where;          // (vertex, first index among the roots)
     where.reserve(n_roots);
     for (uint32_t i = 0; i < n_roots; ++i) if (roots[i] != HSPF_NO_ROOT) where.emplace_back(roots[i], i);
@@ -3022,7 +3118,7 @@ static int run_classes(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots
     }
   }
   const uint32_t n_run = n_roots - (uint32_t)leaf_jobs.size();
-  const bool fused_ok = n < (1u << 23) && !(ctx->variant & 1u);
+  const bool fused_ok = n < (1u << 23) && !(ctx->variant & hspf_ctx::VAR_TWO_PHASE);
   // off the two-phase path with everybody who does not need it, when that saves at least one 64-root batch there (a
   // two-phase batch moves 8W-byte mask rows and costs several fused ones)
   const bool split2 = fused_ok && cnt[2] > 0 && cnt[0] + cnt[1] > 0 && (cnt[2] + 63) / 64 < (n_run + 63) / 64;
@@ -3064,7 +3160,7 @@ static int run_classes(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots
   // more than the longer one (profiles/r04_notes.md, r04w).  HSPF_VARIANT bit 20: one after the other (A/B).
   int n_cls = 0, last_cls = -1;
   for (int c = 0; c < 3; ++c) if (start[c + 1] > start[c]) { ++n_cls; last_cls = c; }
-  const bool side_by_side = n_cls >= 2 && !ctx->parent && ctx->lanes_cfg > 0 && !(ctx->variant & 1048576u) &&
+  const bool side_by_side = n_cls >= 2 && !ctx->parent && ctx->lanes_cfg > 0 && !(ctx->variant & hspf_ctx::VAR_CLASSES_SERIAL) &&
                             (uint64_t)n * n_roots >= (1ull << 22) && lanes_ensure(ctx) == HSPF_OK;
   uint64_t cls_ticket[3] = {0, 0, 0};
   const auto t_cls = std::chrono::steady_clock::now();
@@ -3086,7 +3182,8 @@ static int run_classes(hspf_ctx *ctx, const hspf_graph *g, const uint32_t *roots
     if (rc) { if (!rc_first) rc_first = rc; continue; }          // (every submitted class is collected before the call returns)
     const hspf_stats &p = cls_ticket[c] ? lane_st : ctx->stats;
     acc.n_roots += p.n_roots; acc.n_batches += p.n_batches; acc.n_relax_launches += p.n_relax_launches;
-    acc.n_dag_launches += p.n_dag_launches; acc.n_exact_roots += p.n_exact_roots; acc.n_repaired_roots += p.n_repaired_roots; acc.repair_sweeps = std::max(acc.repair_sweeps, p.repair_sweeps); acc.repair_evals += p.repair_evals; acc.repair_groups += p.repair_groups; acc.ms_repair += p.ms_repair;
+    acc.n_dag_launches += p.n_dag_launches; acc.n_exact_roots += p.n_exact_roots; acc.n_repaired_roots += p.n_repaired_roots;
+    acc.repair_sweeps = std::max(acc.repair_sweeps, p.repair_sweeps); acc.repair_evals += p.repair_evals; acc.repair_groups += p.repair_groups; acc.ms_repair += p.ms_repair;
     acc.n_mask_words = std::max(acc.n_mask_words, p.n_mask_words);
     acc.ms_total += p.ms_total; acc.ms_relax += p.ms_relax; acc.ms_dag += p.ms_dag; acc.ms_finish += p.ms_finish;
     acc.state_bytes = std::max(acc.state_bytes, p.state_bytes); acc.narrow_overflow += p.narrow_overflow;
