@@ -3765,9 +3765,12 @@ __global__ __launch_bounds__(256) void k_anc_sweep(GraphDev g, const uint32_t *_
   const uint32_t root = roots[r];
   if (v >= n || root == INF) return;
   const uint32_t *D = dist + (size_t)r * n;
-  const uint16_t *H = hops + (size_t)r * n, *F = flags + (size_t)r * n;
-  if (!(F[v] & 1u) || v == root || H[v] < level) return;
-  if (F[root] & 2u) return;                                         // exact-kernel root: not handled (level_count says so)
+  const uint16_t *F = flags + (size_t)r * n;
+  // every vertex of the SPT takes part, whatever its hop count: `hops` is the FIRST discoverer's (spf.rs:667,676 keep the candidate's
+  // on an equal relaxation), so with real metrics a vertex of fewer than `level` hops can have a level-L router above it on another
+  // tight path (`hops` and `level` are not read here: the level's routers carry their own bit from k_anc_init)
+  if (!(F[v] & 1u) || v == root) return;
+  if (F[root] & 2u) return;                                        // exact-kernel root: not handled (level_count says so)
   uint64_t *A = anc + (size_t)r * n * W;
   const uint32_t dv = D[v];
   const bool v_net = (g.vflags[v] & 1u) != 0;
@@ -3783,7 +3786,6 @@ __global__ __launch_bounds__(256) void k_anc_sweep(GraphDev g, const uint32_t *_
       if (!(hc && v_net) || zdone) continue;                                    // static order: never a parent; hop-count-like: the first one only
       zdone = true;
     }
-    if (H[u] < level) continue;                                                 // nothing to inherit above the level
     for (uint32_t q = 0; q < W; ++q) {
       const uint64_t pu = A[(size_t)u * W + q], pv = A[(size_t)v * W + q];
       if (pu & ~pv) { A[(size_t)v * W + q] = pv | pu; any = true; }
